@@ -338,9 +338,17 @@ def main():
     ap.add_argument("--no-precision-report", action="store_true",
                     help="skip the fp64 / fp32-K* report on the fixture's 512 candidates (with --no-secondary and "
                          "--no-cpu-baseline every kernel row of a rocprofv3 --stats run is then ONE launch shape)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (the job-wide best score and its "
+                         "global candidate row) as DIR/best_score.npy and DIR/best_index.npy, float64; the inputs are seeded, "
+                         "so two builds run with the same arguments can be compared output for output")
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1 (ms_per_step is the time of one timed step)")
+    if args.warmup < 0:
+        ap.error("--warmup must be >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(spawn_ranks(args))
 
@@ -898,6 +906,12 @@ def main():
             Xs = np.random.default_rng(11).random((256, D))
             chk = eng.predict(post_ref, Xs, want_best=False)
             line["cpu_baseline"] = cpu_baseline(g, 2048, gpu_check=(Xs, chk["mu"].cpu().numpy(), chk["var"].cpu().numpy()))
+        if args.dump_outputs:
+            # the record the last timed step returned (ShardedSearch.step: best score, global row index), identical on every
+            # rank; the index is exact in float64
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            np.save(os.path.join(args.dump_outputs, "best_score.npy"), np.array([best[0]], dtype=np.float64))
+            np.save(os.path.join(args.dump_outputs, "best_index.npy"), np.array([best[1]], dtype=np.float64))
         print(json.dumps(line))
     search.close()
     if use_dist:

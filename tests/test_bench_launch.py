@@ -25,6 +25,12 @@ def test_gpus_must_match_world_size():
     assert "WORLD_SIZE=2" in r.stderr and r.stdout.strip() == ""
 
 
+def test_steps_below_one_is_refused():
+    """ms_per_step is the time of ONE timed step: a run with no timed step has none and must not print a line."""
+    r = _run(["--steps", "0"], timeout=120)
+    assert r.returncode != 0 and "--steps must be >= 1" in r.stderr and r.stdout.strip() == ""
+
+
 def test_gpus_2_without_gpu_fails_loudly():
     import torch
     if torch.cuda.is_available():
@@ -124,3 +130,21 @@ def test_chunked_config_keeps_the_roofline_fraction_below_one():
     assert line["scaling"] == "strong" and line["config"]["M_total"] == 262144
     assert 0 < line["roofline"]["frac"] <= 1.0
     assert line["roofline"]["launches"] == 4 * 2
+
+
+@pytest.mark.gpu
+def test_dump_outputs_holds_the_last_timed_steps_record(tmp_path):
+    """--dump-outputs DIR writes what the timed step returns (best score, global row index) as float64 .npy files, and it
+    is the record the JSON line reports; --steps sets the number of timed steps."""
+    import numpy as np
+    out = tmp_path / "outputs"
+    r = _run(["--steps", "4", "--warmup", "1", "--config", "c2", "--no-cpu-baseline", "--no-secondary",
+              "--no-precision-report", "--dump-outputs", str(out)])
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert line["steps"] == 4 and line["ms_per_step"] > 0
+    assert sorted(p.name for p in out.iterdir()) == ["best_index.npy", "best_score.npy"]
+    score, index = np.load(out / "best_score.npy"), np.load(out / "best_index.npy")
+    assert score.dtype == np.float64 and index.dtype == np.float64 and score.shape == index.shape == (1,)
+    assert score[0] == line["best"]["value"] and index[0] == line["best"]["index"]
+    assert 0 <= index[0] < line["config"]["M_total"]
