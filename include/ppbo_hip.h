@@ -46,8 +46,19 @@ extern "C" {
 
 typedef struct ppbo_ctx ppbo_ctx;
 
-/* kernel ids: src/kernels.py:19 (SE), :27 (RQ, alpha=2), :36 (camphor-copper, D must be 6) */
-enum { PPBO_KERNEL_SE = 0, PPBO_KERNEL_RQ = 1, PPBO_KERNEL_CAMPHOR = 2 };
+/* kernel ids: src/kernels.py:19 (SE), :27 (RQ, alpha=2), :36 (camphor-copper, D must be 6).
+ * The Matern kernels have no reference line; they are the GPy / scikit-learn Matern(nu) definition with
+ * r = |x - x'| and theta = [sigma, l, sigma_f]:
+ *   PPBO_KERNEL_MATERN52  k = sigma_f^2 (1 + a + a^2 / 3) exp(-a),  a = sqrt(5) r / l   (nu = 5/2)
+ *   PPBO_KERNEL_MATERN32  k = sigma_f^2 (1 + a) exp(-a),            a = sqrt(3) r / l   (nu = 3/2)
+ * Any other id is rejected with "invalid argument". */
+enum {
+  PPBO_KERNEL_SE = 0,
+  PPBO_KERNEL_RQ = 1,
+  PPBO_KERNEL_CAMPHOR = 2,
+  PPBO_KERNEL_MATERN52 = 3,
+  PPBO_KERNEL_MATERN32 = 4
+};
 
 /* candidate score folded into the running argmax */
 enum {

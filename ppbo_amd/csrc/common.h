@@ -172,21 +172,46 @@ void ppbo_lds_limit(ppbo_ctx* ctx, const void* kernel_fn, int bytes);
     if (!(cond)) return ppbo_set_error((ctx), -1, "invalid argument: %s", msg); \
   } while (0)
 
+// an entry point's kernel id and the camphor kernel's shape rule (D is the design's dimension)
+#define PPBO_REQUIRE_KERNEL(ctx, kernel_id, D)                                                  \
+  do {                                                                                          \
+    PPBO_REQUIRE(ctx, ppbo_kernel_id_valid(kernel_id), "kernel_id");                            \
+    PPBO_REQUIRE(ctx, (kernel_id) != PPBO_KERNEL_CAMPHOR || (D) == 6, "camphor kernel needs D == 6"); \
+  } while (0)
+
 // ---- kernel-function parameters (host-prepared, passed by value) ------------
 struct KernParams {
   double sf2;      // sigma_f^2
-  double c0;       // SE: 0.5/l^2     RQ: 1/(4 l^2)    camphor: 2/l^2
+  double c0;       // SE: 0.5/l^2     RQ: 1/(4 l^2)    camphor: 2/l^2    Matern-5/2: sqrt(5)/l    Matern-3/2: sqrt(3)/l
   double c1;       // camphor: 0.5/(l+0.05)^2
 };
+
+// the kernel ids every entry point accepts (include/ppbo_hip.h); anything else is "invalid argument"
+static inline bool ppbo_kernel_id_valid(int kernel_id) {
+  return kernel_id == PPBO_KERNEL_SE || kernel_id == PPBO_KERNEL_RQ || kernel_id == PPBO_KERNEL_CAMPHOR ||
+         kernel_id == PPBO_KERNEL_MATERN52 || kernel_id == PPBO_KERNEL_MATERN32;
+}
+// Matern kernels: functions of r = sqrt(r^2), evaluated from the same summed r^2 as SE / RQ
+template <int KID>
+constexpr bool kid_matern = (KID == PPBO_KERNEL_MATERN52 || KID == PPBO_KERNEL_MATERN32);
+// radial kernels: every path that forms r^2 (expansion or direct differences) takes them
+template <int KID>
+constexpr bool kid_radial = (KID == PPBO_KERNEL_SE || KID == PPBO_KERNEL_RQ || kid_matern<KID>);
 
 static inline KernParams make_kern_params(int kernel_id, const double theta[3]) {
   KernParams p;
   const double l = theta[1], sf = theta[2];
   p.sf2 = sf * sf;
   p.c1 = 0.0;
-  if (kernel_id == PPBO_KERNEL_SE) p.c0 = 0.5 / (l * l);
-  else if (kernel_id == PPBO_KERNEL_RQ) p.c0 = 1.0 / (4.0 * l * l);
-  else { p.c0 = 2.0 / (l * l); p.c1 = 0.5 / ((l + 0.05) * (l + 0.05)); }
+  p.c0 = 0.0;
+  switch (kernel_id) {
+    case PPBO_KERNEL_SE: p.c0 = 0.5 / (l * l); break;
+    case PPBO_KERNEL_RQ: p.c0 = 1.0 / (4.0 * l * l); break;
+    case PPBO_KERNEL_CAMPHOR: p.c0 = 2.0 / (l * l); p.c1 = 0.5 / ((l + 0.05) * (l + 0.05)); break;
+    case PPBO_KERNEL_MATERN52: p.c0 = 2.23606797749978969641 / l; break;
+    case PPBO_KERNEL_MATERN32: p.c0 = 1.73205080756887729353 / l; break;
+    default: break;   // rejected by every entry point before a launch (ppbo_kernel_id_valid)
+  }
   return p;
 }
 
@@ -276,26 +301,93 @@ __device__ __forceinline__ double exp_nonpos(double x) {
   return ldexp(q, (int)n);
 }
 
+// sqrt(s) for s >= 0 without the library's range handling: v_rsq_f64, then the Goldschmidt refinement the compiler
+// itself emits for sqrt() (one step on (g, h) = (s y, y / 2), two corrections of g against the residual s - g^2).
+// 9 VALU instructions in one dependent chain, one of them a transcendental; s = 0 (rsq = inf) selects 0.
+__device__ __forceinline__ double sqrt_nonneg(double s) {
+  const double y = __builtin_amdgcn_rsq(s);
+  double g = s * y, h = 0.5 * y;
+  const double r = __builtin_fma(-h, g, 0.5);
+  g = __builtin_fma(g, r, g);
+  h = __builtin_fma(h, r, h);
+  double d = __builtin_fma(-g, g, s);
+  g = __builtin_fma(d, h, g);
+  d = __builtin_fma(-g, g, s);
+  g = __builtin_fma(d, h, g);
+  return s > 0.0 ? g : 0.0;
+}
+
+// Matern pieces from r^2 (clipped at 0 by the caller): a = c r and e = exp(-a), formed once per pair and shared by the
+// value and the gradient.
+struct MaternAE { double a, e; };
+template <int KID>
+__device__ __forceinline__ MaternAE matern_ae(double s, const KernParams& p) {
+  static_assert(kid_matern<KID>, "Matern kernels only");
+  // (a capped where e is already 0: the value and gradient stay 0, never inf * 0, for the far rows some paths stage
+  // with r^2 = 1e300)
+  const double a = fmin(p.c0 * sqrt_nonneg(s), 800.0);
+  return MaternAE{a, exp_nonpos(-a)};
+}
+//   5/2: sf2 (1 + a + a^2/3) e      3/2: sf2 (1 + a) e          (times `scale` = sf2 or (1 - shrink) sf2)
+template <int KID>
+__device__ __forceinline__ double matern_value(const MaternAE& m, double scale) {
+  if constexpr (KID == PPBO_KERNEL_MATERN52) {
+    return scale * (__builtin_fma(m.a, __builtin_fma(m.a, 1.0 / 3.0, 1.0), 1.0) * m.e);
+  } else {
+    static_assert(KID == PPBO_KERNEL_MATERN32, "Matern kernels only");
+    return scale * ((1.0 + m.a) * m.e);
+  }
+}
+// g with grad_x k(x, x') = g (x - x'):   5/2: -sf2 (c^2/3) (1 + a) e      3/2: -sf2 c^2 e      (finite at r = 0)
+template <int KID>
+__device__ __forceinline__ double matern_grad(const MaternAE& m, const KernParams& p) {
+  const double c2 = p.c0 * p.c0;
+  if constexpr (KID == PPBO_KERNEL_MATERN52) {
+    return -(p.sf2 * c2 * (1.0 / 3.0)) * ((1.0 + m.a) * m.e);
+  } else {
+    static_assert(KID == PPBO_KERNEL_MATERN32, "Matern kernels only");
+    return -(p.sf2 * c2) * m.e;
+  }
+}
+
 // Kernel value from accumulated per-dimension terms.
-//   SE / RQ : s = sum_d (x_d - y_d)^2
+//   SE / RQ / Matern : s = sum_d (x_d - y_d)^2
 //   camphor : s = c0 * sum_{d in 0,1,3,4,5} sin^2(pi |dx_d|) + c1 * dx_2^2  (already scaled)
 template <int KID>
 __device__ __forceinline__ double kern_finish(double s, const KernParams& p) {
-  if (KID == PPBO_KERNEL_SE) return p.sf2 * exp_nonpos(-p.c0 * s);
-  if (KID == PPBO_KERNEL_RQ) {
+  if constexpr (KID == PPBO_KERNEL_SE) {
+    return p.sf2 * exp_nonpos(-p.c0 * s);
+  } else if constexpr (KID == PPBO_KERNEL_RQ) {
     const double t = 1.0 + s * p.c0;
     return p.sf2 / (t * t);
+  } else if constexpr (KID == PPBO_KERNEL_CAMPHOR) {
+    return p.sf2 * exp_nonpos(-s);
+  } else {
+    static_assert(kid_matern<KID>, "unknown kernel id");
+    return matern_value<KID>(matern_ae<KID>(s, p), p.sf2);
   }
-  return p.sf2 * exp_nonpos(-s);
+}
+
+// g with grad_x k = g (x - x') for SE / RQ, from w = alpha k (the ascent's and mean_grad's form; Matern: matern_grad)
+template <int KID>
+__device__ __forceinline__ double kern_grad_coef(double s, double w, const KernParams& p) {
+  if constexpr (KID == PPBO_KERNEL_SE) {
+    return -2.0 * p.c0 * w;
+  } else {
+    static_assert(KID == PPBO_KERNEL_RQ, "SE / RQ only");
+    return -4.0 * p.c0 * w / (1.0 + p.c0 * s);
+  }
 }
 
 template <int KID>
 __device__ __forceinline__ double kern_term(double dx, int d, const KernParams& p) {
-  if (KID == PPBO_KERNEL_CAMPHOR) {
+  if constexpr (KID == PPBO_KERNEL_CAMPHOR) {
     if (d == 2) return p.c1 * dx * dx;
     const double sn = sinpi(fabs(dx));
     return p.c0 * sn * sn;
+  } else {
+    static_assert(kid_radial<KID>, "unknown kernel id");
+    return dx * dx;
   }
-  return dx * dx;
 }
 #endif

@@ -1517,6 +1517,7 @@ int ppbo_gp_fit(ppbo_ctx* ctx, int kernel_id, const double* d_X, int N, int D, c
   PPBO_REQUIRE(ctx, (d_alpha && d_lam_diag && d_lam_off && d_G) || (!d_alpha && !d_lam_diag && !d_lam_off && !d_G),
                "the posterior outputs (alpha, lam_diag, lam_off, G) come together or not at all");
   PPBO_REQUIRE(ctx, N > 0 && D > 0 && m >= 1 && theta[0] > 0 && N % (m + 1) == 0, "sizes (N must be n_q*(m+1))");
+  PPBO_REQUIRE_KERNEL(ctx, kernel_id, D);
   PPBO_REQUIRE(ctx, d_L != d_Sigma && d_L != d_Sigma_inv && d_Linv != d_Sigma_inv && d_Linv != d_L, "outputs must not alias");
   hipStream_t s = (hipStream_t)stream;
   if (h_info) *h_info = 0;

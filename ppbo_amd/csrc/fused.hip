@@ -620,7 +620,10 @@ int ppbo_transposed_G(ppbo_ctx* ctx, const double* d_G, int N, double* d_Gt, voi
 // does the one-launch form take this model?  (a property of the MODEL, never of the candidate count: a sharded search
 // and the unsharded one must score a candidate with the same arithmetic)
 bool ppbo_fused_eligible(const ppbo_ctx* ctx, const ppbo_model* m) {
-  if (ctx->fused_score == 0 || m->d_G == nullptr || m->kstar_fp32 || m->kernel_id == PPBO_KERNEL_CAMPHOR) return false;
+  if (ctx->fused_score == 0 || m->d_G == nullptr || m->kstar_fp32) return false;
+  // the radial kernels only (the expansion-form K* tiles); camphor and anything else take the three-launch form
+  if (m->kernel_id != PPBO_KERNEL_SE && m->kernel_id != PPBO_KERNEL_RQ && m->kernel_id != PPBO_KERNEL_MATERN52 &&
+      m->kernel_id != PPBO_KERNEL_MATERN32) return false;
   // Default (PPBO_FUSED=1): the shapes where the one-launch form measured faster than the three-launch one -- two
   // workgroups of 8 wavefronts per CU (up to ~500 rows: 1.1x at N = 512, 1.2-1.5x below) and up to 16 dimensions (one
   // round of operand loads per K* tile).  PPBO_FUSED=2 also takes the 16-wavefront form (up to ~1000 rows, one workgroup
@@ -653,7 +656,9 @@ int ppbo_fused_score(ppbo_ctx* ctx, const ppbo_model* m, const double* Gt, int l
   switch (m->kernel_id) {
     case PPBO_KERNEL_SE: rc = fused_launch<PPBO_KERNEL_SE>(ctx, a, s); break;
     case PPBO_KERNEL_RQ: rc = fused_launch<PPBO_KERNEL_RQ>(ctx, a, s); break;
-    default: return ppbo_set_error(ctx, -1, "the one-launch scoring kernel takes the SE and RQ kernels");
+    case PPBO_KERNEL_MATERN52: rc = fused_launch<PPBO_KERNEL_MATERN52>(ctx, a, s); break;
+    case PPBO_KERNEL_MATERN32: rc = fused_launch<PPBO_KERNEL_MATERN32>(ctx, a, s); break;
+    default: return ppbo_set_error(ctx, -1, "the one-launch scoring kernel takes the SE, RQ and Matern kernels");
   }
   if (rc == 0 && a.stamps) {               // mean phase lengths over the workgroups, in us (s_memrealtime ticks at 100 MHz)
     std::vector<unsigned long long> h((size_t)nblk_dbg * 16);

@@ -180,12 +180,19 @@ __global__ __launch_bounds__(256) void gram_kernel(const double* __restrict__ X,
 
 template <int KID>
 __device__ __forceinline__ double gram_finish(double r2, const KernParams& p, double scale) {
-  if (KID == PPBO_KERNEL_SE) return scale * exp_nonpos(-p.c0 * r2);
-  const double t = 1.0 + r2 * p.c0;
-  return scale / (t * t);
+  if constexpr (KID == PPBO_KERNEL_SE) {
+    return scale * exp_nonpos(-p.c0 * r2);
+  } else if constexpr (KID == PPBO_KERNEL_RQ) {
+    const double t = 1.0 + r2 * p.c0;
+    return scale / (t * t);
+  } else {
+    // Matern: a^2 leads both kernels near r = 0, so the expansion form's r^2 serves them as well as it serves SE
+    static_assert(kid_matern<KID>, "the MFMA Gram takes the radial kernels");
+    return matern_value<KID>(matern_ae<KID>(r2, p), scale);
+  }
 }
 
-// SE / RQ Gram tile with the pairwise dot products on the fp64 matrix cores and the reference's
+// SE / RQ / Matern Gram tile with the pairwise dot products on the fp64 matrix cores and the reference's
 // expansion  r_ij^2 = (|x_i|^2 + |x_j|^2) - 2 x_i.x_j  (kernels.py:7-10), clipped at 0.  The MFMA chain
 // multiplies x_i by (-2 x_j): products and accumulation order are the same for (i,j) and (j,i), and
 // the norm sum commutes, so the matrix is bitwise symmetric by construction.
@@ -424,8 +431,7 @@ int ppbo_gram(ppbo_ctx* ctx, int kernel_id, const double* d_X, int N, int D, con
   PPBO_ENTER(ctx);
   PPBO_REQUIRE(ctx, d_X && d_Sigma && h_theta, "null pointer");
   PPBO_REQUIRE(ctx, N > 0 && D > 0 && D <= 64, "N>0, 0<D<=64");
-  PPBO_REQUIRE(ctx, kernel_id >= 0 && kernel_id <= 2, "kernel_id");
-  PPBO_REQUIRE(ctx, kernel_id != PPBO_KERNEL_CAMPHOR || D == 6, "camphor kernel needs D == 6");
+  PPBO_REQUIRE_KERNEL(ctx, kernel_id, D);
   const KernParams p = make_kern_params(kernel_id, h_theta);
   const int nt = (N + TS - 1) / TS;
   const int nblk = nt * (nt + 1) / 2;
@@ -435,17 +441,22 @@ int ppbo_gram(ppbo_ctx* ctx, int kernel_id, const double* d_X, int N, int D, con
   // tile order (PPBO_GRAM_VARIANT: 0 row-major over the upper triangle, 1 diagonal-major, -1 = by size)
   const int order = ctx->gram_variant >= 0 ? ctx->gram_variant : (N >= 4096 ? 1 : 0);
   if (kernel_id != PPBO_KERNEL_CAMPHOR) {
+#define GM_LAUNCH_K(KIDV, DPV)                                                                               \
+  do {                                                                                                       \
+    if (lds > 64 * 1024) ppbo_lds_limit(ctx, (const void*)gram_mfma_kernel<KIDV, DPV>, (int)lds);            \
+    gram_mfma_kernel<KIDV, DPV><<<nblk, 512, lds, s>>>(d_X, N, D, p, shrink, d_Sigma, nt, order);            \
+  } while (0)
 #define GM_LAUNCH(DPV)                                                                                       \
   do {                                                                                                       \
     constexpr int LDv = DPV + 2;                                                                             \
     constexpr int body = 2 * TS * LDv + 2 * TS + 8 * 16 * 18;                                                \
     const size_t lds = (size_t)body * sizeof(double);                                                        \
-    if (kernel_id == PPBO_KERNEL_SE) {                                                                       \
-      if (lds > 64 * 1024) ppbo_lds_limit(ctx, (const void*)gram_mfma_kernel<PPBO_KERNEL_SE, DPV>, (int)lds); \
-      gram_mfma_kernel<PPBO_KERNEL_SE, DPV><<<nblk, 512, lds, s>>>(d_X, N, D, p, shrink, d_Sigma, nt, order);       \
-    } else {                                                                                                 \
-      if (lds > 64 * 1024) ppbo_lds_limit(ctx, (const void*)gram_mfma_kernel<PPBO_KERNEL_RQ, DPV>, (int)lds); \
-      gram_mfma_kernel<PPBO_KERNEL_RQ, DPV><<<nblk, 512, lds, s>>>(d_X, N, D, p, shrink, d_Sigma, nt, order);       \
+    switch (kernel_id) {                                                                                     \
+      case PPBO_KERNEL_SE: GM_LAUNCH_K(PPBO_KERNEL_SE, DPV); break;                                          \
+      case PPBO_KERNEL_RQ: GM_LAUNCH_K(PPBO_KERNEL_RQ, DPV); break;                                          \
+      case PPBO_KERNEL_MATERN52: GM_LAUNCH_K(PPBO_KERNEL_MATERN52, DPV); break;                               \
+      case PPBO_KERNEL_MATERN32: GM_LAUNCH_K(PPBO_KERNEL_MATERN32, DPV); break;                               \
+      default: return ppbo_set_error(ctx, -1, "invalid argument: kernel_id");                                \
     }                                                                                                        \
   } while (0)
     if (D <= 4) GM_LAUNCH(4);
@@ -458,6 +469,7 @@ int ppbo_gram(ppbo_ctx* ctx, int kernel_id, const double* d_X, int N, int D, con
     else if (D <= 48) GM_LAUNCH(48);
     else GM_LAUNCH(64);
 #undef GM_LAUNCH
+#undef GM_LAUNCH_K
   } else {
     const size_t lds = ((size_t)2 * 12 * TS + (size_t)TS * TP) * sizeof(double);     // 12 staged features per row
     gram_kernel<PPBO_KERNEL_CAMPHOR><<<nblk, 256, lds, s>>>(d_X, N, D, p, shrink, d_Sigma, nt);
@@ -480,8 +492,7 @@ int ppbo_cross_cov(ppbo_ctx* ctx, int kernel_id, const double* d_X1, int n1, con
   PPBO_ENTER(ctx);
   PPBO_REQUIRE(ctx, d_X1 && d_X2 && d_K && h_theta, "null pointer");
   PPBO_REQUIRE(ctx, n1 > 0 && n2 > 0 && D > 0 && D <= 64 && ldk >= n2, "sizes (D<=64)");
-  PPBO_REQUIRE(ctx, kernel_id >= 0 && kernel_id <= 2, "kernel_id");
-  PPBO_REQUIRE(ctx, kernel_id != PPBO_KERNEL_CAMPHOR || D == 6, "camphor kernel needs D == 6");
+  PPBO_REQUIRE_KERNEL(ctx, kernel_id, D);
   const KernParams p = make_kern_params(kernel_id, h_theta);
   dim3 grid((n2 + TS - 1) / TS, (n1 + TS - 1) / TS);
   const size_t lds = (size_t)2 * (kernel_id == PPBO_KERNEL_CAMPHOR ? 12 : D) * TS * sizeof(double);
@@ -489,11 +500,16 @@ int ppbo_cross_cov(ppbo_ctx* ctx, int kernel_id, const double* d_X1, int n1, con
   if (lds > 64 * 1024) {   // D up to 64 needs up to 64 KB + padding
     ppbo_lds_limit(ctx, (const void*)crosscov_kernel<PPBO_KERNEL_SE>, 112 * 1024);
     ppbo_lds_limit(ctx, (const void*)crosscov_kernel<PPBO_KERNEL_RQ>, 112 * 1024);
+    ppbo_lds_limit(ctx, (const void*)crosscov_kernel<PPBO_KERNEL_MATERN52>, 112 * 1024);
+    ppbo_lds_limit(ctx, (const void*)crosscov_kernel<PPBO_KERNEL_MATERN32>, 112 * 1024);
   }
   switch (kernel_id) {
     case PPBO_KERNEL_SE: crosscov_kernel<PPBO_KERNEL_SE><<<grid, 256, lds, s>>>(d_X1, n1, d_X2, n2, D, p, d_K, ldk); break;
     case PPBO_KERNEL_RQ: crosscov_kernel<PPBO_KERNEL_RQ><<<grid, 256, lds, s>>>(d_X1, n1, d_X2, n2, D, p, d_K, ldk); break;
-    default: crosscov_kernel<PPBO_KERNEL_CAMPHOR><<<grid, 256, lds, s>>>(d_X1, n1, d_X2, n2, D, p, d_K, ldk); break;
+    case PPBO_KERNEL_CAMPHOR: crosscov_kernel<PPBO_KERNEL_CAMPHOR><<<grid, 256, lds, s>>>(d_X1, n1, d_X2, n2, D, p, d_K, ldk); break;
+    case PPBO_KERNEL_MATERN52: crosscov_kernel<PPBO_KERNEL_MATERN52><<<grid, 256, lds, s>>>(d_X1, n1, d_X2, n2, D, p, d_K, ldk); break;
+    case PPBO_KERNEL_MATERN32: crosscov_kernel<PPBO_KERNEL_MATERN32><<<grid, 256, lds, s>>>(d_X1, n1, d_X2, n2, D, p, d_K, ldk); break;
+    default: return ppbo_set_error(ctx, -1, "invalid argument: kernel_id");
   }
   PPBO_LAUNCH_CHECK(ctx);
   return 0;

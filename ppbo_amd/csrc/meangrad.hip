@@ -5,6 +5,8 @@
 //   RQ      dk/dx_d = -(x_d - x_i,d) / l^2 * k / (1 + r^2 / (4 l^2))         (kernels.py:27-34, alpha = 2)
 //   camphor dk/dx_d = -(2 pi / l^2) sin(2 pi (x_d - x_i,d)) * k  (d != 2),   -(x_2 - x_i,2) / (l + 0.05)^2 * k
 //                                                                            (kernels.py:36-53)
+//   Matern  dk/dx_d = -(x_d - x_i,d) sf^2 (c^2 / 3) (1 + a) e^-a  (5/2),  -(x_d - x_i,d) sf^2 c^2 e^-a  (3/2),  a = c r
+//                                                                            (common.h matern_grad; finite at r = 0)
 // One 256-thread workgroup per point: lanes stride over the N design rows with the point held in
 // registers, accumulate mu and D gradient components, then a shuffle + LDS reduction.  M is small here
 // (a few hundred ascent iterates), so the work per launch is M * N * D * ~6 flops -- microseconds.
@@ -35,16 +37,23 @@ __global__ __launch_bounds__(256) void mean_grad_kernel(const double* __restrict
       dx[d] = (d < D) ? xc[d] - xi[d] : 0.0;
       s += kern_term<KID>(dx[d], d, p);
     }
-    const double w = alpha[i] * kern_finish<KID>(s, p);
+    double w, coef;
+    if constexpr (kid_matern<KID>) {     // one exponential for the value and the gradient
+      const MaternAE ae = matern_ae<KID>(s, p);
+      w = alpha[i] * matern_value<KID>(ae, p.sf2);
+      coef = alpha[i] * matern_grad<KID>(ae, p);
+    } else {
+      w = alpha[i] * kern_finish<KID>(s, p);
+    }
     m += w;
-    if (KID == PPBO_KERNEL_CAMPHOR) {
+    if constexpr (KID == PPBO_KERNEL_CAMPHOR) {
 #pragma unroll
       for (int d = 0; d < DP; ++d) {
         if (d == 2) g[d] -= 2.0 * p.c1 * dx[d] * w;
         else if (d < 6) g[d] -= p.c0 * 3.14159265358979323846 * sinpi(2.0 * dx[d]) * w;
       }
     } else {
-      const double coef = (KID == PPBO_KERNEL_SE) ? -2.0 * p.c0 * w : -4.0 * p.c0 * w / (1.0 + p.c0 * s);
+      if constexpr (!kid_matern<KID>) coef = kern_grad_coef<KID>(s, w, p);
 #pragma unroll
       for (int d = 0; d < DP; ++d) g[d] += coef * dx[d];
     }
@@ -106,19 +115,31 @@ typedef float float2_t __attribute__((ext_vector_type(2)));
 // two candidates per packed operation (v_pk_add_f32 / v_pk_fma_f32: both halves at the price of one fp32 instruction)
 template <int KID>
 __device__ __forceinline__ float2_t screen_term2(float2_t dx, int d, float c0, float c1) {
-  if (KID == PPBO_KERNEL_CAMPHOR) {
+  if constexpr (KID == PPBO_KERNEL_CAMPHOR) {
     if (d == 2) return c1 * dx * dx;
     float2_t sn;
     sn.x = sinpif(fabsf(dx.x)); sn.y = sinpif(fabsf(dx.y));
     return c0 * sn * sn;
+  } else {
+    static_assert(kid_radial<KID>, "unknown kernel id");
+    return dx * dx;
   }
-  return dx * dx;
 }
 template <int KID>
 __device__ __forceinline__ float screen_finish(float s, float sf2, float c0) {
-  if (KID == PPBO_KERNEL_RQ) { const float t = 1.0f + s * c0; return sf2 * __builtin_amdgcn_rcpf(t * t); }
-  const float e = (KID == PPBO_KERNEL_SE) ? -c0 * s : -s;
-  return sf2 * __builtin_amdgcn_exp2f(fmaxf(e * 1.44269504088896340736f, -126.0f));
+  if constexpr (KID == PPBO_KERNEL_RQ) {
+    const float t = 1.0f + s * c0; return sf2 * __builtin_amdgcn_rcpf(t * t);
+  } else if constexpr (KID == PPBO_KERNEL_SE || KID == PPBO_KERNEL_CAMPHOR) {
+    const float e = (KID == PPBO_KERNEL_SE) ? -c0 * s : -s;
+    return sf2 * __builtin_amdgcn_exp2f(fmaxf(e * 1.44269504088896340736f, -126.0f));
+  } else {
+    // Matern: a = c r from v_sqrt_f32 (s >= 0: a sum of squares), e^-a by v_exp_f32 as above
+    static_assert(kid_matern<KID>, "unknown kernel id");
+    const float a = c0 * __builtin_amdgcn_sqrtf(s);
+    const float e = __builtin_amdgcn_exp2f(fmaxf(-a * 1.44269504088896340736f, -126.0f));
+    const float poly = (KID == PPBO_KERNEL_MATERN52) ? fmaf(a, fmaf(a, 1.0f / 3.0f, 1.0f), 1.0f) : 1.0f + a;
+    return sf2 * (poly * e);
+  }
 }
 template <int KID, int DP>
 __global__ __launch_bounds__(SCR_T) void mean_screen_kernel(const double* __restrict__ X, int N, int D, KernParams p,
@@ -336,16 +357,23 @@ __device__ __forceinline__ void eval_mean_grad(const double* __restrict__ X, int
       dx[d] = (d < D) ? xc[d] - xi[d * xs] : 0.0;
       s += kern_term<KID>(dx[d], d, p);
     }
-    const double w = alpha[i] * kern_finish<KID>(s, p);
+    double w, coef;
+    if constexpr (kid_matern<KID>) {     // one exponential for the value and the gradient
+      const MaternAE ae = matern_ae<KID>(s, p);
+      w = alpha[i] * matern_value<KID>(ae, p.sf2);
+      coef = alpha[i] * matern_grad<KID>(ae, p);
+    } else {
+      w = alpha[i] * kern_finish<KID>(s, p);
+    }
     m += w;
-    if (KID == PPBO_KERNEL_CAMPHOR) {
+    if constexpr (KID == PPBO_KERNEL_CAMPHOR) {
 #pragma unroll
       for (int d = 0; d < DP; ++d) {
         if (d == 2) g[d] -= 2.0 * p.c1 * dx[d] * w;
         else if (d < 6) g[d] -= p.c0 * 3.14159265358979323846 * sinpi(2.0 * dx[d]) * w;
       }
     } else {
-      const double coef = (KID == PPBO_KERNEL_SE) ? -2.0 * p.c0 * w : -4.0 * p.c0 * w / (1.0 + p.c0 * s);
+      if constexpr (!kid_matern<KID>) coef = kern_grad_coef<KID>(s, w, p);
 #pragma unroll
       for (int d = 0; d < DP; ++d) g[d] += coef * dx[d];
     }
@@ -569,8 +597,7 @@ extern "C" int ppbo_mean_grad(ppbo_ctx* ctx, const ppbo_model* m, const double* 
   PPBO_ENTER(ctx);
   PPBO_REQUIRE(ctx, m != nullptr && m->d_X && m->d_alpha, "model X/alpha");
   PPBO_REQUIRE(ctx, m->N > 0 && m->D > 0 && m->D <= 64, "model sizes (D<=64)");
-  PPBO_REQUIRE(ctx, m->kernel_id >= 0 && m->kernel_id <= 2, "kernel_id");
-  PPBO_REQUIRE(ctx, m->kernel_id != PPBO_KERNEL_CAMPHOR || m->D == 6, "camphor kernel needs D == 6");
+  PPBO_REQUIRE_KERNEL(ctx, m->kernel_id, m->D);
   PPBO_REQUIRE(ctx, d_Xc && d_mu && d_grad && M >= 0 && M < (1 << 30), "points / outputs");
   if (M == 0) return 0;
   hipStream_t s = (hipStream_t)stream;
@@ -578,7 +605,10 @@ extern "C" int ppbo_mean_grad(ppbo_ctx* ctx, const ppbo_model* m, const double* 
   switch (m->kernel_id) {
     case PPBO_KERNEL_SE: launch_mean_grad<PPBO_KERNEL_SE>(m, p, d_Xc, (int)M, d_mu, d_grad, s); break;
     case PPBO_KERNEL_RQ: launch_mean_grad<PPBO_KERNEL_RQ>(m, p, d_Xc, (int)M, d_mu, d_grad, s); break;
-    default: launch_mean_grad<PPBO_KERNEL_CAMPHOR>(m, p, d_Xc, (int)M, d_mu, d_grad, s); break;
+    case PPBO_KERNEL_CAMPHOR: launch_mean_grad<PPBO_KERNEL_CAMPHOR>(m, p, d_Xc, (int)M, d_mu, d_grad, s); break;
+    case PPBO_KERNEL_MATERN52: launch_mean_grad<PPBO_KERNEL_MATERN52>(m, p, d_Xc, (int)M, d_mu, d_grad, s); break;
+    case PPBO_KERNEL_MATERN32: launch_mean_grad<PPBO_KERNEL_MATERN32>(m, p, d_Xc, (int)M, d_mu, d_grad, s); break;
+    default: return ppbo_set_error(ctx, -1, "invalid argument: kernel_id");
   }
   PPBO_LAUNCH_CHECK(ctx);
   return 0;
@@ -606,8 +636,7 @@ extern "C" int ppbo_mean_ascent(ppbo_ctx* ctx, const ppbo_model* m, const double
   PPBO_ENTER(ctx);
   PPBO_REQUIRE(ctx, m != nullptr && m->d_X && m->d_alpha, "model X/alpha");
   PPBO_REQUIRE(ctx, m->N > 0 && m->D > 0 && m->D <= 64, "model sizes (D<=64)");
-  PPBO_REQUIRE(ctx, m->kernel_id >= 0 && m->kernel_id <= 2, "kernel_id");
-  PPBO_REQUIRE(ctx, m->kernel_id != PPBO_KERNEL_CAMPHOR || m->D == 6, "camphor kernel needs D == 6");
+  PPBO_REQUIRE_KERNEL(ctx, m->kernel_id, m->D);
   PPBO_REQUIRE(ctx, d_starts && d_x && d_mu && K > 0 && K <= 65536 && iters >= 0 && tol >= 0, "starts / outputs");
   hipStream_t s = (hipStream_t)stream;
   const KernParams p = make_kern_params(m->kernel_id, m->theta);
@@ -615,7 +644,10 @@ extern "C" int ppbo_mean_ascent(ppbo_ctx* ctx, const ppbo_model* m, const double
   switch (m->kernel_id) {
     case PPBO_KERNEL_SE: rc = launch_mean_ascent<PPBO_KERNEL_SE>(ctx, m, p, d_starts, nullptr, K, iters, tol, d_x, d_mu, d_iters, s); break;
     case PPBO_KERNEL_RQ: rc = launch_mean_ascent<PPBO_KERNEL_RQ>(ctx, m, p, d_starts, nullptr, K, iters, tol, d_x, d_mu, d_iters, s); break;
-    default: rc = launch_mean_ascent<PPBO_KERNEL_CAMPHOR>(ctx, m, p, d_starts, nullptr, K, iters, tol, d_x, d_mu, d_iters, s); break;
+    case PPBO_KERNEL_CAMPHOR: rc = launch_mean_ascent<PPBO_KERNEL_CAMPHOR>(ctx, m, p, d_starts, nullptr, K, iters, tol, d_x, d_mu, d_iters, s); break;
+    case PPBO_KERNEL_MATERN52: rc = launch_mean_ascent<PPBO_KERNEL_MATERN52>(ctx, m, p, d_starts, nullptr, K, iters, tol, d_x, d_mu, d_iters, s); break;
+    case PPBO_KERNEL_MATERN32: rc = launch_mean_ascent<PPBO_KERNEL_MATERN32>(ctx, m, p, d_starts, nullptr, K, iters, tol, d_x, d_mu, d_iters, s); break;
+    default: return ppbo_set_error(ctx, -1, "invalid argument: kernel_id");
   }
   if (rc) return rc;
   PPBO_LAUNCH_CHECK(ctx);
@@ -627,8 +659,7 @@ extern "C" int ppbo_mean_search(ppbo_ctx* ctx, const ppbo_model* m, const double
   PPBO_ENTER(ctx);
   PPBO_REQUIRE(ctx, m != nullptr && m->d_X && m->d_alpha, "model X/alpha");
   PPBO_REQUIRE(ctx, m->N > 0 && m->D > 0 && m->D <= 64, "model sizes (D<=64)");
-  PPBO_REQUIRE(ctx, m->kernel_id >= 0 && m->kernel_id <= 2, "kernel_id");
-  PPBO_REQUIRE(ctx, m->kernel_id != PPBO_KERNEL_CAMPHOR || m->D == 6, "camphor kernel needs D == 6");
+  PPBO_REQUIRE_KERNEL(ctx, m->kernel_id, m->D);
   PPBO_REQUIRE(ctx, d_cand && d_x && d_mu && M > 0 && M < ((int64_t)1 << 31), "candidates / outputs");
   PPBO_REQUIRE(ctx, K > 0 && K <= 1024 && sep >= 0 && iters >= 0 && tol >= 0, "K (<= 1024) / sep / iters / tol");
   hipStream_t s = (hipStream_t)stream;
@@ -658,7 +689,10 @@ extern "C" int ppbo_mean_search(ppbo_ctx* ctx, const ppbo_model* m, const double
   switch (m->kernel_id) {
     case PPBO_KERNEL_SE: if (int rc = launch_mean_ascent<PPBO_KERNEL_SE>(ctx, m, p, starts, count, K, iters, tol, d_x, d_mu, nullptr, s)) return rc; break;
     case PPBO_KERNEL_RQ: if (int rc = launch_mean_ascent<PPBO_KERNEL_RQ>(ctx, m, p, starts, count, K, iters, tol, d_x, d_mu, nullptr, s)) return rc; break;
-    default: if (int rc = launch_mean_ascent<PPBO_KERNEL_CAMPHOR>(ctx, m, p, starts, count, K, iters, tol, d_x, d_mu, nullptr, s)) return rc; break;
+    case PPBO_KERNEL_CAMPHOR: if (int rc = launch_mean_ascent<PPBO_KERNEL_CAMPHOR>(ctx, m, p, starts, count, K, iters, tol, d_x, d_mu, nullptr, s)) return rc; break;
+    case PPBO_KERNEL_MATERN52: if (int rc = launch_mean_ascent<PPBO_KERNEL_MATERN52>(ctx, m, p, starts, count, K, iters, tol, d_x, d_mu, nullptr, s)) return rc; break;
+    case PPBO_KERNEL_MATERN32: if (int rc = launch_mean_ascent<PPBO_KERNEL_MATERN32>(ctx, m, p, starts, count, K, iters, tol, d_x, d_mu, nullptr, s)) return rc; break;
+    default: return ppbo_set_error(ctx, -1, "invalid argument: kernel_id");
   }
   PPBO_LAUNCH_CHECK(ctx);
   if (h_found) {
@@ -695,8 +729,7 @@ extern "C" int ppbo_mean_search_multi(ppbo_ctx* ctx, const ppbo_model* m, const 
   PPBO_ENTER(ctx);
   PPBO_REQUIRE(ctx, m != nullptr && m->d_X && m->d_alpha, "model X/alpha");
   PPBO_REQUIRE(ctx, m->N > 0 && m->D > 0 && m->D <= 64, "model sizes (D<=64)");
-  PPBO_REQUIRE(ctx, m->kernel_id >= 0 && m->kernel_id <= 2, "kernel_id");
-  PPBO_REQUIRE(ctx, m->kernel_id != PPBO_KERNEL_CAMPHOR || m->D == 6, "camphor kernel needs D == 6");
+  PPBO_REQUIRE_KERNEL(ctx, m->kernel_id, m->D);
   PPBO_REQUIRE(ctx, d_pool && h_shifts && d_x && d_mu && M > 0 && E_rows >= 0 && M + E_rows + 1 < ((int64_t)1 << 31),
                "pool / shifts / extra points / outputs");
   if (E_rows > 0 && !d_extra) {       // NULL with a row count: the model's own design points
@@ -750,7 +783,10 @@ extern "C" int ppbo_mean_search_multi(ppbo_ctx* ctx, const ppbo_model* m, const 
       switch (m->kernel_id) {
         case PPBO_KERNEL_SE: launch_screen<PPBO_KERNEL_SE>(m, p, tb, nb, rows_per_split, n_split, part, extra_trial, s); break;
         case PPBO_KERNEL_RQ: launch_screen<PPBO_KERNEL_RQ>(m, p, tb, nb, rows_per_split, n_split, part, extra_trial, s); break;
-        default: launch_screen<PPBO_KERNEL_CAMPHOR>(m, p, tb, nb, rows_per_split, n_split, part, extra_trial, s); break;
+        case PPBO_KERNEL_CAMPHOR: launch_screen<PPBO_KERNEL_CAMPHOR>(m, p, tb, nb, rows_per_split, n_split, part, extra_trial, s); break;
+        case PPBO_KERNEL_MATERN52: launch_screen<PPBO_KERNEL_MATERN52>(m, p, tb, nb, rows_per_split, n_split, part, extra_trial, s); break;
+        case PPBO_KERNEL_MATERN32: launch_screen<PPBO_KERNEL_MATERN32>(m, p, tb, nb, rows_per_split, n_split, part, extra_trial, s); break;
+        default: return ppbo_set_error(ctx, -1, "invalid argument: kernel_id");
       }
       screen_sum_kernel<<<dim3((unsigned)((Mt + 255) / 256), nb), 256, 0, s>>>(part, n_split, Mt, M, extra_trial, mu + (size_t)t0 * Mt);
       PPBO_LAUNCH_CHECK(ctx);
@@ -785,7 +821,10 @@ extern "C" int ppbo_mean_search_multi(ppbo_ctx* ctx, const ppbo_model* m, const 
   switch (m->kernel_id) {
     case PPBO_KERNEL_SE: if (int rc = launch_mean_ascent<PPBO_KERNEL_SE>(ctx, m, p, starts, counts, T * K, iters, tol, d_x, d_mu, nullptr, s, K)) return rc; break;
     case PPBO_KERNEL_RQ: if (int rc = launch_mean_ascent<PPBO_KERNEL_RQ>(ctx, m, p, starts, counts, T * K, iters, tol, d_x, d_mu, nullptr, s, K)) return rc; break;
-    default: if (int rc = launch_mean_ascent<PPBO_KERNEL_CAMPHOR>(ctx, m, p, starts, counts, T * K, iters, tol, d_x, d_mu, nullptr, s, K)) return rc; break;
+    case PPBO_KERNEL_CAMPHOR: if (int rc = launch_mean_ascent<PPBO_KERNEL_CAMPHOR>(ctx, m, p, starts, counts, T * K, iters, tol, d_x, d_mu, nullptr, s, K)) return rc; break;
+    case PPBO_KERNEL_MATERN52: if (int rc = launch_mean_ascent<PPBO_KERNEL_MATERN52>(ctx, m, p, starts, counts, T * K, iters, tol, d_x, d_mu, nullptr, s, K)) return rc; break;
+    case PPBO_KERNEL_MATERN32: if (int rc = launch_mean_ascent<PPBO_KERNEL_MATERN32>(ctx, m, p, starts, counts, T * K, iters, tol, d_x, d_mu, nullptr, s, K)) return rc; break;
+    default: return ppbo_set_error(ctx, -1, "invalid argument: kernel_id");
   }
   PPBO_LAUNCH_CHECK(ctx);
   return 0;

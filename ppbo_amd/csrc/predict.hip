@@ -40,18 +40,31 @@ constexpr int KS_RJ = 32;   // X rows staged in LDS per step
 // then widened; every accumulation (mu, k*'Lambda k*, the MFMA contraction) stays fp64.
 template <int KID>
 __device__ __forceinline__ float kern_term32(float dx, int d, float c0, float c1) {
-  if (KID == PPBO_KERNEL_CAMPHOR) {
+  if constexpr (KID == PPBO_KERNEL_CAMPHOR) {
     if (d == 2) return c1 * dx * dx;
     const float sn = sinpif(fabsf(dx));
     return c0 * sn * sn;
+  } else {
+    static_assert(kid_radial<KID>, "unknown kernel id");
+    return dx * dx;
   }
-  return dx * dx;
 }
 template <int KID>
 __device__ __forceinline__ float kern_finish32(float s, float sf2, float c0) {
-  if (KID == PPBO_KERNEL_SE) return sf2 * expf(-c0 * s);
-  if (KID == PPBO_KERNEL_RQ) { const float t = 1.0f + s * c0; return sf2 / (t * t); }
-  return sf2 * expf(-s);
+  if constexpr (KID == PPBO_KERNEL_SE) {
+    return sf2 * expf(-c0 * s);
+  } else if constexpr (KID == PPBO_KERNEL_RQ) {
+    const float t = 1.0f + s * c0; return sf2 / (t * t);
+  } else if constexpr (KID == PPBO_KERNEL_CAMPHOR) {
+    return sf2 * expf(-s);
+  } else if constexpr (KID == PPBO_KERNEL_MATERN52) {
+    const float a = c0 * sqrtf(s);
+    return sf2 * (fmaf(a, fmaf(a, 1.0f / 3.0f, 1.0f), 1.0f) * expf(-a));
+  } else {
+    static_assert(KID == PPBO_KERNEL_MATERN32, "unknown kernel id");
+    const float a = c0 * sqrtf(s);
+    return sf2 * ((1.0f + a) * expf(-a));
+  }
 }
 
 template <int KID, int DP, bool F32 = false>
@@ -71,7 +84,7 @@ __global__ __launch_bounds__(KS_THREADS) void kstar_kernel(
   // candidates), those of a candidate once per thread.  Terms of size c0 cancel to the true exponent with an absolute
   // error of ~1e-15 (the kernel value moves by <= 1e-14 relative; Sigma / K* parity is asserted at 1e-12).
   constexpr bool CAMF = (KID == PPBO_KERNEL_CAMPHOR) && !F32 && DP == 12;   // (the only fp64 camphor bucket launched)
-  // SE / RQ use the reference's own expansion r^2 = (|x|^2 + |c|^2) - 2 x.c (kernels.py:7-10) with the
+  // SE / RQ / Matern use the reference's own expansion r^2 = (|x|^2 + |c|^2) - 2 x.c (kernels.py:7-10) with the
   // candidate pre-scaled by -2: one FMA per dimension and pair instead of a subtract and an FMA.  Its
   // rounding is the rounding every entry of Sigma already carries (posterior mean / variance move by
   // <= 3e-13 / 1e-13 sigma_f^2 on the fixtures against direct differences).  The camphor kernel needs the
@@ -837,7 +850,10 @@ int dispatch_kstar(const ppbo_model* m, const double* d_Xc, int M, double* Kt, i
   switch (m->kernel_id) {
     case PPBO_KERNEL_SE: return launch_kstar<PPBO_KERNEL_SE>(m, p, d_Xc, M, Kt, ldk, mu_part, t_part, q_per_split, n_split, with_lam, s);
     case PPBO_KERNEL_RQ: return launch_kstar<PPBO_KERNEL_RQ>(m, p, d_Xc, M, Kt, ldk, mu_part, t_part, q_per_split, n_split, with_lam, s);
-    default: return launch_kstar<PPBO_KERNEL_CAMPHOR>(m, p, d_Xc, M, Kt, ldk, mu_part, t_part, q_per_split, n_split, with_lam, s);
+    case PPBO_KERNEL_CAMPHOR: return launch_kstar<PPBO_KERNEL_CAMPHOR>(m, p, d_Xc, M, Kt, ldk, mu_part, t_part, q_per_split, n_split, with_lam, s);
+    case PPBO_KERNEL_MATERN52: return launch_kstar<PPBO_KERNEL_MATERN52>(m, p, d_Xc, M, Kt, ldk, mu_part, t_part, q_per_split, n_split, with_lam, s);
+    case PPBO_KERNEL_MATERN32: return launch_kstar<PPBO_KERNEL_MATERN32>(m, p, d_Xc, M, Kt, ldk, mu_part, t_part, q_per_split, n_split, with_lam, s);
+    default: return -1;   // (check_model rejects any other id first)
   }
 }
 
@@ -846,8 +862,7 @@ int check_model(ppbo_ctx* ctx, const ppbo_model* m) {
   PPBO_REQUIRE(ctx, m->d_X && m->d_alpha, "model X/alpha");
   PPBO_REQUIRE(ctx, m->N > 0 && m->D > 0 && m->D <= 64 && m->m >= 1, "model sizes (D<=64)");
   PPBO_REQUIRE(ctx, m->N % (m->m + 1) == 0, "N must be n_q*(m+1) (feedback_processing.py:110-130)");
-  PPBO_REQUIRE(ctx, m->kernel_id >= 0 && m->kernel_id <= 2, "kernel_id");
-  PPBO_REQUIRE(ctx, m->kernel_id != PPBO_KERNEL_CAMPHOR || m->D == 6, "camphor kernel needs D == 6");
+  PPBO_REQUIRE_KERNEL(ctx, m->kernel_id, m->D);
   return 0;
 }
 
@@ -1183,7 +1198,10 @@ int line_acq_impl(ppbo_ctx* ctx, const ppbo_model* model, const double* d_grid, 
     switch (model->kernel_id) {
       case PPBO_KERNEL_SE: line_prior_kernel<PPBO_KERNEL_SE><<<Bc, 256, 0, s>>>(xg, G, D, p, shrink, cov); break;
       case PPBO_KERNEL_RQ: line_prior_kernel<PPBO_KERNEL_RQ><<<Bc, 256, 0, s>>>(xg, G, D, p, shrink, cov); break;
-      default: line_prior_kernel<PPBO_KERNEL_CAMPHOR><<<Bc, 256, 0, s>>>(xg, G, D, p, shrink, cov); break;
+      case PPBO_KERNEL_CAMPHOR: line_prior_kernel<PPBO_KERNEL_CAMPHOR><<<Bc, 256, 0, s>>>(xg, G, D, p, shrink, cov); break;
+      case PPBO_KERNEL_MATERN52: line_prior_kernel<PPBO_KERNEL_MATERN52><<<Bc, 256, 0, s>>>(xg, G, D, p, shrink, cov); break;
+      case PPBO_KERNEL_MATERN32: line_prior_kernel<PPBO_KERNEL_MATERN32><<<Bc, 256, 0, s>>>(xg, G, D, p, shrink, cov); break;
+      default: return ppbo_set_error(ctx, -1, "invalid argument: kernel_id");
     }
     PPBO_LAUNCH_CHECK(ctx);
     GemmArgs y{};  // Y = G K*

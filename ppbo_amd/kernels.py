@@ -29,4 +29,14 @@ def camphor_copper_kernel(X1, X2, theta):
     return _eval("camphor_copper_kernel", X1, X2, theta)
 
 
-BY_NAME = {f.__name__: f for f in (SE_kernel, RQ_kernel, camphor_copper_kernel)}
+# No reference counterpart: the GPy / scikit-learn Matern(nu) kernels, k = sigma_f^2 (1 + a + a^2/3) e^-a with
+# a = sqrt(5) r / l (nu = 5/2) and k = sigma_f^2 (1 + a) e^-a with a = sqrt(3) r / l (nu = 3/2), theta = [sigma, l, sigma_f]
+def Matern52_kernel(X1, X2, theta):
+    return _eval("Matern52_kernel", X1, X2, theta)
+
+
+def Matern32_kernel(X1, X2, theta):
+    return _eval("Matern32_kernel", X1, X2, theta)
+
+
+BY_NAME = {f.__name__: f for f in (SE_kernel, RQ_kernel, camphor_copper_kernel, Matern52_kernel, Matern32_kernel)}

@@ -20,6 +20,19 @@ SCORE_CANDIDATES = 65536
 RFF_STARTS = 32            # refined starts per posterior sample (the reference: 5-30 L-BFGS-B runs)
 
 
+# smoothness nu of the Matern kernels (kernels.py); their spectral density is a multivariate Student-t
+MATERN_NU = {"Matern52_kernel": 2.5, "Matern32_kernel": 1.5}
+
+
+def matern_spectral_draw(F, D, lengthscale, nu, rng=np.random):
+    """F frequencies [F, D] from the spectral density of Matern(nu) with length scale l: a multivariate Student-t with
+    2 nu degrees of freedom and scale I / l^2, drawn as W = z / l * sqrt(2 nu / u), z ~ N(0, I_D), u ~ chi^2_{2 nu} per
+    feature.  E|w|^2 = D (2 nu / (2 nu - 2)) / l^2."""
+    z = rng.standard_normal((F, D))
+    u = rng.chisquare(2.0 * nu, size=F)
+    return z / lengthscale * np.sqrt(2.0 * nu / u)[:, None]
+
+
 class Hsampler:
     def __init__(self, gp_model, nFeatures=1000, engine=None):
         self.eng = engine if engine is not None else getattr(gp_model, "eng", None) or get_engine()
@@ -61,8 +74,10 @@ class Hsampler:
 
     # ---- basis -----------------------------------------------------------------
     def generate_basis(self):
-        if self.kernel == "SE_kernel":                        # only the SE spectral density is supported (:40-42)
+        if self.kernel == "SE_kernel":                        # the reference supports the SE spectral density only (:40-42)
             self.W = np.random.randn(self.nFeatures, self.D) / self.theta[1]
+        elif self.kernel in MATERN_NU:
+            self.W = matern_spectral_draw(self.nFeatures, self.D, self.theta[1], MATERN_NU[self.kernel])
         self.b = np.random.uniform(low=0, high=2 * np.pi, size=self.nFeatures)[:, None]
 
     def _scale(self):
