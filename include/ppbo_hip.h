@@ -359,6 +359,25 @@ PPBO_API int ppbo_mean_search_multi(ppbo_ctx* ctx, const ppbo_model* model, cons
                            int K, double sep, int iters, double tol, int screen_fp32, double* d_x, double* d_mu,
                            void* stream);
 
+/* ---- ARD: one length scale per input dimension (no reference counterpart) --------------------------------------------
+ * For a radial kernel (SE, RQ, Matern-5/2, Matern-3/2), k(x, x'; l_1..l_D) = k(s (.) x, s (.) x'; l = 1) with s_d = 1 / l_d.
+ * An ARD model therefore holds its SCALED rows in d_X and theta = [sigma, 1, sigma_f]; every other entry point runs on it
+ * unchanged.  Only what works in the caller's coordinates needs these three.
+ * ppbo_scale_points (no reference counterpart): d_out[i,d] = d_in[i,d] * h_scale[d] for M rows of D (in place allowed).
+ * ppbo_mean_search_multi_scaled / ppbo_mean_ascent_scaled (no reference counterpart): ppbo_mean_search_multi /
+ * ppbo_mean_ascent on such a model, with h_scale[D] = s.  Pool rotation, extra points, h_xprev, the [0,1]^D box, sep,
+ * tol and the returned points are all in the caller's coordinates; d_extra = NULL stands for the model's design points
+ * in those coordinates (its rows divided by s).  The mean is evaluated at s (.) x and its gradient scaled by s.  The
+ * camphor-copper kernel and a non-positive or non-finite scale are rejected with "invalid argument". */
+PPBO_API int ppbo_scale_points(ppbo_ctx* ctx, const double* d_in, int64_t M, int D, const double* h_scale, double* d_out,
+                      void* stream);
+PPBO_API int ppbo_mean_search_multi_scaled(ppbo_ctx* ctx, const ppbo_model* model, const double* d_pool, int64_t M,
+                           const double* h_shifts, int T, const double* d_extra, int E_rows, const double* h_xprev,
+                           int K, double sep, int iters, double tol, int screen_fp32, double* d_x, double* d_mu,
+                           const double* h_scale, void* stream);
+PPBO_API int ppbo_mean_ascent_scaled(ppbo_ctx* ctx, const ppbo_model* model, const double* d_starts, int K, int iters,
+                     double tol, double* d_x, double* d_mu, int* d_iters, const double* h_scale, void* stream);
+
 /* ---- K10: Monte-Carlo line acquisition -------------------------------------
  * replaces EI / varmax (src/acquisition.py:72-81, 170-178) for B lines of G points
  * with stored standard-normal draws d_z[S,G]: f = mu + chol(cov) z.

@@ -401,6 +401,28 @@ struct MeanEval {
   }
 };
 
+// ARD (ppbo_mean_ascent_scaled): the ascent runs in the caller's coordinates x over the model's scaled rows -- mu at
+// s (.) x, d mu / d x_d = s_d d mu / d x~_d.  The scaled point goes through LDS of its own (one barrier); the gradient's
+// partial sums are scaled by the threads that wrote them (eval_mean_grad: lane 16 k of each wavefront writes record
+// 4 wave + k), so the barrier behind the evaluation in bb_ascent_kernel still orders them before they are read.
+template <int KID, int DP, int NT>
+struct ScaledMeanEval {
+  MeanEval<KID, DP, NT> ev; const double* scale;   // scale: D values (device)
+  __device__ __forceinline__ void operator()(const double* sx, double (*red)[DP + 1]) const {
+    __shared__ double sxs[DP];
+    if (threadIdx.x < DP) sxs[threadIdx.x] = ((int)threadIdx.x < ev.D) ? sx[threadIdx.x] * scale[threadIdx.x] : 0.0;
+    __syncthreads();
+    ev(sxs, red);
+    const int lane = threadIdx.x & 63;
+    if ((lane & 15) == 0) {
+      double* r = red[4 * (threadIdx.x >> 6) + (lane >> 4)];
+#pragma unroll
+      for (int d = 0; d < DP; ++d)
+        if (d < ev.D) r[d] *= scale[d];
+    }
+  }
+};
+
 // one posterior sample of the utility in weight space (random_fourier_sampler.py:45-53,166):
 //   f(x) = a sum_f omega_f cos(w_f.x + b_f),   grad f = -a sum_f omega_f sin(w_f.x + b_f) w_f,   a = sqrt(2 sf^2 / F)
 template <int DP, int NT>
@@ -531,6 +553,14 @@ __global__ __launch_bounds__(256) void shift_points_kernel(const double* __restr
   out[i] = v - floor(v);
 }
 
+// out = in * scale row-wise (in place allowed): ARD's input scaling s (.) x and the gradient's way back
+__global__ __launch_bounds__(256) void scale_points_kernel(const double* in, int64_t n, int D,
+                                                           const double* __restrict__ scale, double* out) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  out[i] = in[i] * scale[i % D];
+}
+
 // out[d][r] = in[r][d]  (R x D row-major -> D x R): the ascent kernels read their operand transposed
 __global__ __launch_bounds__(256) void transpose_rows_kernel(const double* __restrict__ in, int R, int D,
                                                              double* __restrict__ out) {
@@ -539,9 +569,11 @@ __global__ __launch_bounds__(256) void transpose_rows_kernel(const double* __res
   for (int d = 0; d < D; ++d) out[(size_t)d * R + r] = in[(size_t)r * D + d];
 }
 
+// d_scale (ARD, radial kernels only): D values s_d on the device; the ascent then runs in the caller's coordinates
 template <int KID>
 int launch_mean_ascent(ppbo_ctx* ctx, const ppbo_model* m, const KernParams& p, const double* starts, const int* count, int K,
-                       int iters, double tol, double* x_out, double* mu_out, int* it_out, hipStream_t s, int per_trial = 0) {
+                       int iters, double tol, double* x_out, double* mu_out, int* it_out, hipStream_t s, int per_trial = 0,
+                       const double* d_scale = nullptr) {
   double* Xt = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_TRANSPOSE, (size_t)m->N * m->D * sizeof(double));
   if (!Xt) return (int)hipErrorOutOfMemory;
   transpose_rows_kernel<<<(m->N + 255) / 256, 256, 0, s>>>(m->d_X, m->N, m->D, Xt);
@@ -550,6 +582,13 @@ int launch_mean_ascent(ppbo_ctx* ctx, const ppbo_model* m, const KernParams& p, 
 #define MA_LAUNCH(DP, NT)                                                                                             \
   do {                                                                                                                \
     MeanEval<KID, DP, NT> ev{Xt, m->N, m->D, p, m->d_alpha};                                                        \
+    if constexpr (kid_radial<KID>) {                                                                                  \
+      if (d_scale) {                                                                                                  \
+        ScaledMeanEval<KID, DP, NT> sev{ev, d_scale};                                                                 \
+        bb_ascent_kernel<DP, ScaledMeanEval<KID, DP, NT>, NT><<<K, NT, 0, s>>>(sev, m->D, starts, count, iters, tol, x_out, mu_out, it_out, per_trial); \
+        break;                                                                                                        \
+      }                                                                                                               \
+    }                                                                                                                 \
     bb_ascent_kernel<DP, MeanEval<KID, DP, NT>, NT><<<K, NT, 0, s>>>(ev, m->D, starts, count, iters, tol, x_out, mu_out, it_out, per_trial); \
   } while (0)
   const bool tall = m->N >= 1024;
@@ -631,25 +670,68 @@ extern "C" int ppbo_shift_points(ppbo_ctx* ctx, const double* d_in, int64_t M, i
   return 0;
 }
 
-extern "C" int ppbo_mean_ascent(ppbo_ctx* ctx, const ppbo_model* m, const double* d_starts, int K, int iters,
-                                double tol, double* d_x, double* d_mu, int* d_iters, void* stream) {
+// the ARD entries take h_scale (D host values s_d = 1 / l_d) and refuse kernels that are not radial
+#define PPBO_REQUIRE_SCALE(ctx, m, h_scale)                                                                           \
+  do {                                                                                                                \
+    PPBO_REQUIRE(ctx, h_scale != nullptr, "h_scale (D values)");                                                      \
+    PPBO_REQUIRE(ctx, (m)->kernel_id != PPBO_KERNEL_CAMPHOR, "invalid argument: per-dimension scales need a radial kernel"); \
+    for (int _d = 0; _d < (m)->D; ++_d)                                                                               \
+      PPBO_REQUIRE(ctx, h_scale[_d] > 0.0 && std::isfinite(h_scale[_d]), "h_scale: positive finite values");          \
+  } while (0)
+
+static int mean_ascent_impl(ppbo_ctx* ctx, const ppbo_model* m, const double* d_starts, int K, int iters, double tol,
+                            double* d_x, double* d_mu, int* d_iters, const double* h_scale, void* stream) {
   PPBO_ENTER(ctx);
   PPBO_REQUIRE(ctx, m != nullptr && m->d_X && m->d_alpha, "model X/alpha");
   PPBO_REQUIRE(ctx, m->N > 0 && m->D > 0 && m->D <= 64, "model sizes (D<=64)");
   PPBO_REQUIRE_KERNEL(ctx, m->kernel_id, m->D);
   PPBO_REQUIRE(ctx, d_starts && d_x && d_mu && K > 0 && K <= 65536 && iters >= 0 && tol >= 0, "starts / outputs");
   hipStream_t s = (hipStream_t)stream;
+  double* d_scale = nullptr;
+  if (h_scale) {
+    PPBO_REQUIRE_SCALE(ctx, m, h_scale);
+    d_scale = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_SCALE, 64 * sizeof(double));
+    if (!d_scale) return (int)hipErrorOutOfMemory;
+    if (int rc = ppbo_upload_async(ctx, d_scale, h_scale, (size_t)m->D * sizeof(double), s)) return rc;
+  }
   const KernParams p = make_kern_params(m->kernel_id, m->theta);
   int rc = 0;
   switch (m->kernel_id) {
-    case PPBO_KERNEL_SE: rc = launch_mean_ascent<PPBO_KERNEL_SE>(ctx, m, p, d_starts, nullptr, K, iters, tol, d_x, d_mu, d_iters, s); break;
-    case PPBO_KERNEL_RQ: rc = launch_mean_ascent<PPBO_KERNEL_RQ>(ctx, m, p, d_starts, nullptr, K, iters, tol, d_x, d_mu, d_iters, s); break;
+    case PPBO_KERNEL_SE: rc = launch_mean_ascent<PPBO_KERNEL_SE>(ctx, m, p, d_starts, nullptr, K, iters, tol, d_x, d_mu, d_iters, s, 0, d_scale); break;
+    case PPBO_KERNEL_RQ: rc = launch_mean_ascent<PPBO_KERNEL_RQ>(ctx, m, p, d_starts, nullptr, K, iters, tol, d_x, d_mu, d_iters, s, 0, d_scale); break;
     case PPBO_KERNEL_CAMPHOR: rc = launch_mean_ascent<PPBO_KERNEL_CAMPHOR>(ctx, m, p, d_starts, nullptr, K, iters, tol, d_x, d_mu, d_iters, s); break;
-    case PPBO_KERNEL_MATERN52: rc = launch_mean_ascent<PPBO_KERNEL_MATERN52>(ctx, m, p, d_starts, nullptr, K, iters, tol, d_x, d_mu, d_iters, s); break;
-    case PPBO_KERNEL_MATERN32: rc = launch_mean_ascent<PPBO_KERNEL_MATERN32>(ctx, m, p, d_starts, nullptr, K, iters, tol, d_x, d_mu, d_iters, s); break;
+    case PPBO_KERNEL_MATERN52: rc = launch_mean_ascent<PPBO_KERNEL_MATERN52>(ctx, m, p, d_starts, nullptr, K, iters, tol, d_x, d_mu, d_iters, s, 0, d_scale); break;
+    case PPBO_KERNEL_MATERN32: rc = launch_mean_ascent<PPBO_KERNEL_MATERN32>(ctx, m, p, d_starts, nullptr, K, iters, tol, d_x, d_mu, d_iters, s, 0, d_scale); break;
     default: return ppbo_set_error(ctx, -1, "invalid argument: kernel_id");
   }
   if (rc) return rc;
+  PPBO_LAUNCH_CHECK(ctx);
+  return 0;
+}
+
+extern "C" int ppbo_mean_ascent(ppbo_ctx* ctx, const ppbo_model* m, const double* d_starts, int K, int iters,
+                                double tol, double* d_x, double* d_mu, int* d_iters, void* stream) {
+  return mean_ascent_impl(ctx, m, d_starts, K, iters, tol, d_x, d_mu, d_iters, nullptr, stream);
+}
+
+extern "C" int ppbo_mean_ascent_scaled(ppbo_ctx* ctx, const ppbo_model* m, const double* d_starts, int K, int iters,
+                                       double tol, double* d_x, double* d_mu, int* d_iters, const double* h_scale,
+                                       void* stream) {
+  if (!h_scale) { PPBO_ENTER(ctx); return ppbo_set_error(ctx, -1, "invalid argument: h_scale is NULL"); }
+  return mean_ascent_impl(ctx, m, d_starts, K, iters, tol, d_x, d_mu, d_iters, h_scale, stream);
+}
+
+extern "C" int ppbo_scale_points(ppbo_ctx* ctx, const double* d_in, int64_t M, int D, const double* h_scale,
+                                 double* d_out, void* stream) {
+  PPBO_ENTER(ctx);
+  PPBO_REQUIRE(ctx, d_in && d_out && h_scale && M >= 0 && D > 0 && D <= 64, "arguments (D <= 64)");
+  if (M == 0) return 0;
+  hipStream_t s = (hipStream_t)stream;
+  double* dsc = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_SCALE_PTS, 64 * sizeof(double));
+  if (!dsc) return (int)hipErrorOutOfMemory;
+  if (int rc = ppbo_upload_async(ctx, dsc, h_scale, (size_t)D * sizeof(double), s)) return rc;
+  const int64_t n = M * D;
+  scale_points_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(d_in, n, D, dsc, d_out);
   PPBO_LAUNCH_CHECK(ctx);
   return 0;
 }
@@ -703,6 +785,16 @@ extern "C" int ppbo_mean_search(ppbo_ctx* ctx, const ppbo_model* m, const double
 }
 
 
+// row splits of a screening launch: enough workgroups to fill the chip (2048), at most 16 splits of >= SCR_RJ rows
+static void screen_split(int blocks_x, int nb, int N, int& n_split, int& rows_per_split) {
+  n_split = (2048 + blocks_x * nb - 1) / (blocks_x * nb);
+  if (n_split > 16) n_split = 16;
+  if (n_split > (N + SCR_RJ - 1) / SCR_RJ) n_split = (N + SCR_RJ - 1) / SCR_RJ;
+  if (n_split < 1) n_split = 1;
+  rows_per_split = (N + n_split - 1) / n_split;
+  n_split = (N + rows_per_split - 1) / rows_per_split;
+}
+
 template <int KID>
 void launch_screen(const ppbo_model* m, const KernParams& p, const TrialCands& tc, int nb, int rows_per_split, int n_split,
                    double* part, int extra_trial, hipStream_t s) {
@@ -722,20 +814,22 @@ void launch_screen(const ppbo_model* m, const KernParams& p, const TrialCands& t
 #undef SCR_LAUNCH
 }
 
-extern "C" int ppbo_mean_search_multi(ppbo_ctx* ctx, const ppbo_model* m, const double* d_pool, int64_t M,
-                                      const double* h_shifts, int T, const double* d_extra, int E_rows,
-                                      const double* h_xprev, int K, double sep, int iters, double tol, int screen_fp32,
-                                      double* d_x, double* d_mu, void* stream) {
+static int mean_search_multi_impl(ppbo_ctx* ctx, const ppbo_model* m, const double* d_pool, int64_t M,
+                                  const double* h_shifts, int T, const double* d_extra, int E_rows,
+                                  const double* h_xprev, int K, double sep, int iters, double tol, int screen_fp32,
+                                  double* d_x, double* d_mu, const double* h_scale, void* stream) {
   PPBO_ENTER(ctx);
   PPBO_REQUIRE(ctx, m != nullptr && m->d_X && m->d_alpha, "model X/alpha");
   PPBO_REQUIRE(ctx, m->N > 0 && m->D > 0 && m->D <= 64, "model sizes (D<=64)");
   PPBO_REQUIRE_KERNEL(ctx, m->kernel_id, m->D);
   PPBO_REQUIRE(ctx, d_pool && h_shifts && d_x && d_mu && M > 0 && E_rows >= 0 && M + E_rows + 1 < ((int64_t)1 << 31),
                "pool / shifts / extra points / outputs");
-  if (E_rows > 0 && !d_extra) {       // NULL with a row count: the model's own design points
+  const bool design = E_rows > 0 && !d_extra;
+  if (design) {       // NULL with a row count: the model's own design points
     PPBO_REQUIRE(ctx, E_rows == m->N, "d_extra = NULL stands for the model's N design points: E_rows must be N");
     d_extra = m->d_X;
   }
+  if (h_scale) PPBO_REQUIRE_SCALE(ctx, m, h_scale);
   const int E = E_rows + (h_xprev ? 1 : 0);
   PPBO_REQUIRE(ctx, T >= 1 && T <= 64 && K > 0 && K <= 1024 && sep >= 0 && iters >= 0 && tol >= 0, "T (<= 64) / K (<= 1024) / sep / iters / tol");
   hipStream_t s = (hipStream_t)stream;
@@ -745,6 +839,7 @@ extern "C" int ppbo_mean_search_multi(ppbo_ctx* ctx, const ppbo_model* m, const 
   const int G = (int)((Mt + T_MAX - 1) / T_MAX);
   const int Tg = (int)((Mt + G - 1) / G);
   // workspace: shifts[T][D] + xprev[D] | mu[T][Mt] | gval[T][Tg] | starts[T][K][D] | gidx[T][Tg] (int) | counts[T] (int)
+  // (ARD: scale[D] + 1 / scale[D] and the design's rows in the caller's coordinates [N][D] in a slot of their own)
   const size_t nd = (size_t)(T + 1) * D + (size_t)T * Mt + (size_t)T * Tg + (size_t)T * K * D;
   double* base = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_SEARCH, nd * sizeof(double) + ((size_t)T * Tg + T + 16) * sizeof(int));
   if (!base) return (int)hipErrorOutOfMemory;
@@ -760,21 +855,36 @@ extern "C" int ppbo_mean_search_multi(ppbo_ctx* ctx, const ppbo_model* m, const 
   if (int rc = ppbo_upload_async(ctx, shifts, h_shifts, (size_t)T * D * sizeof(double), s)) return rc;
   if (h_xprev)
     if (int rc = ppbo_upload_async(ctx, xprev, h_xprev, (size_t)D * sizeof(double), s)) return rc;
+  double* d_scale = nullptr;
+  if (h_scale) {
+    // s and 1 / s in one upload; the design points (the model's scaled rows) are taken back to the caller's
+    // coordinates, x_i = x~_i / s, so that rotation, separation and box all live there
+    double* sc = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_SCALE_SEARCH,
+                                         (2 * (size_t)D + (design ? (size_t)m->N * D : 0)) * sizeof(double));
+    if (!sc) return (int)hipErrorOutOfMemory;
+    double hs[128];
+    for (int d = 0; d < D; ++d) { hs[d] = h_scale[d]; hs[D + d] = 1.0 / h_scale[d]; }
+    if (int rc = ppbo_upload_async(ctx, sc, hs, 2 * (size_t)D * sizeof(double), s)) return rc;
+    d_scale = sc;
+    if (design) {
+      double* xo = sc + 2 * D;
+      const int64_t n = (int64_t)m->N * D;
+      scale_points_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(m->d_X, n, D, sc + D, xo);
+      PPBO_LAUNCH_CHECK(ctx);
+      d_extra = xo;
+    }
+  }
   TrialCands tc;
   tc.pool = d_pool; tc.M = M; tc.shifts = shifts; tc.extra = d_extra; tc.xprev = h_xprev ? xprev : nullptr;
   tc.E_rows = E_rows; tc.E = E; tc.D = D;
   const KernParams p = make_kern_params(m->kernel_id, m->theta);
-  if (screen_fp32) {
+  if (screen_fp32 && !d_scale) {
     // the trials in batches of <= 8 (bounds the partial sums: 8 x n_split x Mt doubles)
     const int blocks_x = (int)((Mt + SCR_T * SCR_CPT - 1) / (SCR_T * SCR_CPT));
     for (int t0 = 0; t0 < T; t0 += 8) {
       const int nb = (T - t0 < 8) ? (T - t0) : 8;
-      int n_split = (2048 + blocks_x * nb - 1) / (blocks_x * nb);
-      if (n_split > 16) n_split = 16;
-      if (n_split > (m->N + SCR_RJ - 1) / SCR_RJ) n_split = (m->N + SCR_RJ - 1) / SCR_RJ;
-      if (n_split < 1) n_split = 1;
-      const int rows_per_split = (m->N + n_split - 1) / n_split;
-      n_split = (m->N + rows_per_split - 1) / rows_per_split;
+      int n_split, rows_per_split;
+      screen_split(blocks_x, nb, m->N, n_split, rows_per_split);
       double* part = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_PART, (size_t)nb * n_split * Mt * sizeof(double));
       if (!part) return (int)hipErrorOutOfMemory;
       TrialCands tb = tc;
@@ -793,7 +903,9 @@ extern "C" int ppbo_mean_search_multi(ppbo_ctx* ctx, const ppbo_model* m, const 
     }
   } else {
     // fp64 screening: every trial's candidates written out as rows and scored by ppbo_predict (mean only), exactly
-    // what the one-trial entry does with the rows ppbo_shift_points leaves
+    // what the one-trial entry does with the rows ppbo_shift_points leaves.  ARD: the rows are scaled to s (.) x first,
+    // and the fp32 screening takes them as the extra points of a one-trial launch of mean_screen_kernel (which reads
+    // extra points as they are), so that the kernel itself needs no scaled form
     double* rows = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_SEARCH_ROWS, (size_t)Mt * D * sizeof(double));
     if (!rows) return (int)hipErrorOutOfMemory;
     ppbo_model mean_only = *m;
@@ -801,10 +913,28 @@ extern "C" int ppbo_mean_search_multi(ppbo_ctx* ctx, const ppbo_model* m, const 
     for (int t = 0; t < T; ++t) {
       const long long nt = M + (t == 0 ? E : 0);
       trial_rows_kernel<<<(unsigned)((nt * D + 255) / 256), 256, 0, s>>>(tc, t, rows);
+      if (d_scale) scale_points_kernel<<<(unsigned)((nt * D + 255) / 256), 256, 0, s>>>(rows, nt * D, D, d_scale, rows);
       PPBO_LAUNCH_CHECK(ctx);
-      if (int rc = ppbo_predict(ctx, &mean_only, rows, nt, PPBO_SCORE_MEAN, 0.0, mu + (size_t)t * Mt, nullptr, nullptr, nullptr,
-                                nullptr, stream))
+      if (screen_fp32) {
+        TrialCands tr;
+        tr.pool = rows; tr.M = 0; tr.shifts = shifts; tr.extra = rows; tr.E_rows = (int)nt; tr.E = (int)nt; tr.D = D;
+        int n_split, rows_per_split;
+        screen_split((int)((nt + SCR_T * SCR_CPT - 1) / (SCR_T * SCR_CPT)), 1, m->N, n_split, rows_per_split);
+        double* part = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_PART, (size_t)n_split * nt * sizeof(double));
+        if (!part) return (int)hipErrorOutOfMemory;
+        switch (m->kernel_id) {   // (camphor-copper has no ARD form: refused above)
+          case PPBO_KERNEL_SE: launch_screen<PPBO_KERNEL_SE>(m, p, tr, 1, rows_per_split, n_split, part, 0, s); break;
+          case PPBO_KERNEL_RQ: launch_screen<PPBO_KERNEL_RQ>(m, p, tr, 1, rows_per_split, n_split, part, 0, s); break;
+          case PPBO_KERNEL_MATERN52: launch_screen<PPBO_KERNEL_MATERN52>(m, p, tr, 1, rows_per_split, n_split, part, 0, s); break;
+          case PPBO_KERNEL_MATERN32: launch_screen<PPBO_KERNEL_MATERN32>(m, p, tr, 1, rows_per_split, n_split, part, 0, s); break;
+          default: return ppbo_set_error(ctx, -1, "invalid argument: kernel_id");
+        }
+        screen_sum_kernel<<<dim3((unsigned)((nt + 255) / 256), 1), 256, 0, s>>>(part, n_split, nt, 0, 0, mu + (size_t)t * Mt);
+        PPBO_LAUNCH_CHECK(ctx);
+      } else if (int rc = ppbo_predict(ctx, &mean_only, rows, nt, PPBO_SCORE_MEAN, 0.0, mu + (size_t)t * Mt, nullptr, nullptr,
+                                       nullptr, nullptr, stream)) {
         return rc;
+      }
       if (nt < Mt) {
         // absent slots: -inf (0xFFF0000000000000 is not a byte pattern: a tiny fill kernel)
         fill_kernel<<<(unsigned)((Mt - nt + 255) / 256), 256, 0, s>>>(mu + (size_t)t * Mt + nt, Mt - nt, -INFINITY);
@@ -819,15 +949,33 @@ extern "C" int ppbo_mean_search_multi(ppbo_ctx* ctx, const ppbo_model* m, const 
   }
   PPBO_LAUNCH_CHECK(ctx);
   switch (m->kernel_id) {
-    case PPBO_KERNEL_SE: if (int rc = launch_mean_ascent<PPBO_KERNEL_SE>(ctx, m, p, starts, counts, T * K, iters, tol, d_x, d_mu, nullptr, s, K)) return rc; break;
-    case PPBO_KERNEL_RQ: if (int rc = launch_mean_ascent<PPBO_KERNEL_RQ>(ctx, m, p, starts, counts, T * K, iters, tol, d_x, d_mu, nullptr, s, K)) return rc; break;
+    case PPBO_KERNEL_SE: if (int rc = launch_mean_ascent<PPBO_KERNEL_SE>(ctx, m, p, starts, counts, T * K, iters, tol, d_x, d_mu, nullptr, s, K, d_scale)) return rc; break;
+    case PPBO_KERNEL_RQ: if (int rc = launch_mean_ascent<PPBO_KERNEL_RQ>(ctx, m, p, starts, counts, T * K, iters, tol, d_x, d_mu, nullptr, s, K, d_scale)) return rc; break;
     case PPBO_KERNEL_CAMPHOR: if (int rc = launch_mean_ascent<PPBO_KERNEL_CAMPHOR>(ctx, m, p, starts, counts, T * K, iters, tol, d_x, d_mu, nullptr, s, K)) return rc; break;
-    case PPBO_KERNEL_MATERN52: if (int rc = launch_mean_ascent<PPBO_KERNEL_MATERN52>(ctx, m, p, starts, counts, T * K, iters, tol, d_x, d_mu, nullptr, s, K)) return rc; break;
-    case PPBO_KERNEL_MATERN32: if (int rc = launch_mean_ascent<PPBO_KERNEL_MATERN32>(ctx, m, p, starts, counts, T * K, iters, tol, d_x, d_mu, nullptr, s, K)) return rc; break;
+    case PPBO_KERNEL_MATERN52: if (int rc = launch_mean_ascent<PPBO_KERNEL_MATERN52>(ctx, m, p, starts, counts, T * K, iters, tol, d_x, d_mu, nullptr, s, K, d_scale)) return rc; break;
+    case PPBO_KERNEL_MATERN32: if (int rc = launch_mean_ascent<PPBO_KERNEL_MATERN32>(ctx, m, p, starts, counts, T * K, iters, tol, d_x, d_mu, nullptr, s, K, d_scale)) return rc; break;
     default: return ppbo_set_error(ctx, -1, "invalid argument: kernel_id");
   }
   PPBO_LAUNCH_CHECK(ctx);
   return 0;
+}
+
+extern "C" int ppbo_mean_search_multi(ppbo_ctx* ctx, const ppbo_model* m, const double* d_pool, int64_t M,
+                                      const double* h_shifts, int T, const double* d_extra, int E_rows,
+                                      const double* h_xprev, int K, double sep, int iters, double tol, int screen_fp32,
+                                      double* d_x, double* d_mu, void* stream) {
+  return mean_search_multi_impl(ctx, m, d_pool, M, h_shifts, T, d_extra, E_rows, h_xprev, K, sep, iters, tol, screen_fp32,
+                                d_x, d_mu, nullptr, stream);
+}
+
+extern "C" int ppbo_mean_search_multi_scaled(ppbo_ctx* ctx, const ppbo_model* m, const double* d_pool, int64_t M,
+                                             const double* h_shifts, int T, const double* d_extra, int E_rows,
+                                             const double* h_xprev, int K, double sep, int iters, double tol,
+                                             int screen_fp32, double* d_x, double* d_mu, const double* h_scale,
+                                             void* stream) {
+  if (!h_scale) { PPBO_ENTER(ctx); return ppbo_set_error(ctx, -1, "invalid argument: h_scale is NULL"); }
+  return mean_search_multi_impl(ctx, m, d_pool, M, h_shifts, T, d_extra, E_rows, h_xprev, K, sep, iters, tol, screen_fp32,
+                                d_x, d_mu, h_scale, stream);
 }
 
 extern "C" int ppbo_rff_search(ppbo_ctx* ctx, const double* d_cand, int64_t M, int D, const double* d_W, int F,

@@ -67,6 +67,9 @@ class ShardedSearch:
 
     def __init__(self, engine, post, Xc_shard, shard_offset: int, score, mustar=0.0, group=None, collective="torch",
                  host_collective=False):
+        if getattr(post, "scale", None) is not None:
+            # the shards would have to be scaled on every rank; no multi-GPU run of that exists to test it
+            raise ValueError("ShardedSearch does not take a posterior with per-dimension length scales")
         self.eng, self.post, self.Xc = engine, post, engine.dev(Xc_shard)
         self.offset, self.score, self.mustar, self.group = int(shard_offset), score, float(mustar), group
         self.rank, self.world = rank_world(group)

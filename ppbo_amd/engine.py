@@ -13,6 +13,36 @@ from ._lib import KERNEL_IDS, SCORE_MEAN, SCORE_POINTWISE_EI, SCORE_VARIANCE, PP
 
 SHRINKAGE = 1e-6  # COVARIANCE_SHRINKAGE of the reference (gp_model.py:26)
 
+# ARD (one length scale per input dimension, no reference counterpart) is defined for these: for a radial kernel
+# k(x, x'; l_1..l_D) = k(s (.) x, s (.) x'; l = 1) with s_d = 1 / l_d, so an ARD posterior stores its rows scaled once and
+# every device path runs on them unchanged with theta = [sigma, 1, sigma_f]
+RADIAL_KERNELS = ("SE_kernel", "RQ_kernel", "Matern52_kernel", "Matern32_kernel")
+
+
+def lengthscales(theta, D, kernel):
+    """The one check of theta[1]: None for a scalar length scale (today's path, left exactly as it is), else the
+    length-D float64 vector of per-dimension length scales.  A vector is never collapsed to a scalar, even when its
+    entries are equal.  Raises ValueError for a vector with the camphor-copper kernel, of the wrong length, or with an
+    entry that is not positive and finite."""
+    l = theta[1]
+    if np.ndim(l) == 0:
+        return None
+    v = np.asarray(l, dtype=np.float64)
+    if kernel not in RADIAL_KERNELS:
+        raise ValueError(f"per-dimension length scales are defined for the radial kernels {RADIAL_KERNELS}, not {kernel}")
+    if v.ndim != 1 or v.size != D:
+        raise ValueError(f"theta[1] has shape {v.shape}: a scalar or one length scale per input dimension ({D}) is required")
+    if not (np.all(np.isfinite(v)) and np.all(v > 0)):
+        raise ValueError("theta[1]: every per-dimension length scale must be positive and finite")
+    return v
+
+
+def theta_key(theta):
+    """theta as a hashable, comparable tuple (sigma, l, sigma_f), l a float or a tuple of floats (the caches that are
+    keyed on theta)."""
+    l = theta[1]
+    return (float(theta[0]), float(l) if np.ndim(l) == 0 else tuple(float(v) for v in np.ravel(l)), float(theta[2]))
+
 
 class NotPositiveDefinite(RuntimeError):
     def __init__(self, msg, info=0):
@@ -22,9 +52,11 @@ class NotPositiveDefinite(RuntimeError):
 
 @dataclass
 class Posterior:
-    """Device-resident posterior state consumed by predict / predict_cov / line_acq."""
+    """Device-resident posterior state consumed by predict / predict_cov / line_acq.  With per-dimension length scales
+    (scale is not None) X holds the SCALED rows s (.) x_i and the device sees theta = [sigma, 1, sigma_f]; every Engine
+    method that takes points takes them in the caller's coordinates and maps them."""
     kernel: str
-    theta: tuple
+    theta: tuple             # theta_key(theta): the caller's theta
     m: int
     X: torch.Tensor          # [N, D]
     alpha: torch.Tensor      # [N]   Sigma^-1 f_MAP
@@ -33,6 +65,7 @@ class Posterior:
     G: torch.Tensor | None   # [N, N] R Lambda
     P: torch.Tensor | None = None  # posterior covariance (optional)
     Gt: torch.Tensor | None = None  # transpose of G in the one-launch scoring kernel's layout (formed on first use)
+    scale: np.ndarray | None = None  # ARD: s_d = 1 / l_d (None: a scalar length scale)
 
 
 def _ptr(t):
@@ -92,12 +125,52 @@ class Engine:
     def _theta(theta):
         return (C.c_double * 3)(float(theta[0]), float(theta[1]), float(theta[2]))
 
+    # ---- ARD: the one place that knows which coordinates the device works in ------------------------------------------
+    @staticmethod
+    def _dptr(a):
+        return a.ctypes.data_as(C.POINTER(C.c_double))
+
+    def scale_points(self, X, scale, out=None):
+        """out = X * scale row-wise (ppbo_scale_points; out may be X itself)."""
+        X = self.dev(X)
+        M, D = X.shape
+        sc = np.ascontiguousarray(np.asarray(scale, dtype=np.float64).reshape(-1))
+        if sc.size != D:
+            raise ValueError(f"scale_points: {sc.size} scales for {D} columns")
+        out = self.empty(M, D) if out is None else out
+        rc = self.lib.ppbo_scale_points(self.ctx, _ptr(X), M, D, self._dptr(sc), _ptr(out), self._stream())
+        self._check(rc, "ppbo_scale_points")
+        return out
+
+    def _ard(self, X, theta, kernel):
+        """(rows the device works on, theta it sees, scale or None) for the caller's rows X and theta."""
+        X = self.dev(X)
+        ls = lengthscales(theta, X.shape[1], kernel)
+        if ls is None:
+            return X, theta, None
+        scale = 1.0 / ls
+        return self.scale_points(X, scale), (float(theta[0]), 1.0, float(theta[2])), scale
+
+    def _points(self, post: Posterior, Xc):
+        """Points in the caller's coordinates -> the rows the posterior's device state is in."""
+        Xc = self.dev(Xc)
+        if post.scale is None:
+            return Xc
+        if Xc.dim() != 2 or Xc.shape[1] != post.X.shape[1]:
+            raise ValueError(f"points of shape {tuple(Xc.shape)} for a model of {post.X.shape[1]} dimensions")
+        return self.scale_points(Xc, post.scale)
+
+    def mean_posterior(self, X, theta, kernel, m, alpha):
+        """A Posterior usable for the mean only (alpha given, no variance state) at the caller's rows X."""
+        Xd, _, scale = self._ard(X, theta, kernel)
+        return Posterior(kernel, theta_key(theta), m, Xd, alpha, None, None, None, scale=scale)
+
     def _model(self, post: Posterior, with_var=True, kstar_fp32=False):
         N, D = post.X.shape
         md = _lib.Model()
         md.kernel_id = KERNEL_IDS[post.kernel]
         md.N, md.D, md.m = N, D, post.m
-        md.theta = self._theta(post.theta)
+        md.theta = self._theta(post.theta if post.scale is None else (post.theta[0], 1.0, post.theta[2]))
         md.d_X = post.X.data_ptr()
         md.d_alpha = post.alpha.data_ptr()
         md.d_lam_diag = post.lam_diag.data_ptr() if post.lam_diag is not None else 0
@@ -165,6 +238,7 @@ class Engine:
         """One shard of a sharded search, enqueue only (ppbo_predict_record): out[2] (device) = (best score,
         index_offset + first row index as a float64); nothing is read back, nothing synchronises."""
         Xc = self.dev(Xc)
+        Xc = self._points(post, Xc)
         md = self._model(post, score != SCORE_MEAN, kstar_fp32)
         rec = self.empty(2) if out is None else out
         rc = self.lib.ppbo_predict_record(self.ctx, C.byref(md), _ptr(Xc), Xc.shape[0], int(score), float(mustar),
@@ -175,7 +249,7 @@ class Engine:
     def search_sharded(self, post, Xc, score=SCORE_MEAN, mustar=0.0, index_offset=0, kstar_fp32=False):
         """One whole sharded search step in ONE library call (ppbo_search_sharded): score this rank's rows, RCCL
         all-gather of the 16-byte records (when dist_init has run on this ctx), reduction, one read-back."""
-        Xc = self.dev(Xc)
+        Xc = self._points(post, Xc)
         md = self._model(post, score != SCORE_MEAN, kstar_fp32)
         bv, bi = C.c_double(0.0), C.c_int64(-1)
         rc = self.lib.ppbo_search_sharded(self.ctx, C.byref(md), _ptr(Xc), Xc.shape[0], int(score), float(mustar),
@@ -199,7 +273,7 @@ class Engine:
 
     # ---- K1 / K2 --------------------------------------------------------
     def gram(self, X, theta, kernel="SE_kernel", shrink=SHRINKAGE, out=None):
-        X = self.dev(X)
+        X, theta, _ = self._ard(X, theta, kernel)
         N, D = X.shape
         S = self.empty(N, N) if out is None else out
         rc = self.lib.ppbo_gram(self.ctx, KERNEL_IDS[kernel], _ptr(X), N, D, self._theta(theta), shrink, _ptr(S),
@@ -214,7 +288,9 @@ class Engine:
         return out
 
     def cross_cov(self, X1, X2, theta, kernel="SE_kernel"):
-        X1, X2 = self.dev(X1), self.dev(X2)
+        X1, th, scale = self._ard(X1, theta, kernel)
+        X2 = self.dev(X2) if scale is None else self.scale_points(X2, scale)
+        theta = th
         n1, D = X1.shape
         n2 = X2.shape[0]
         K = self.empty(n1, n2)
@@ -400,7 +476,8 @@ class Engine:
         ONE host wait.  start_is_whitened: f_init holds z0 and the start is the prior draw L z0.
         Returns dict(Sigma, Sigma_inv, L, Linv, fMAP, post, stats, info); info = 2 (with post = None) when
         Sigma^-1 - Lambda_MAP is not positive definite (raises NotPositiveDefinite when Sigma itself is not)."""
-        X = self.dev(X)
+        key = theta_key(theta)
+        X, theta, scale = self._ard(X, theta, kernel)
         N, D = X.shape
         f0 = self.dev(f_init).reshape(-1)
         if f0.numel() != N:
@@ -423,14 +500,15 @@ class Engine:
             post = None
         else:
             self._check(rc, "ppbo_gp_fit", info.value)
-            post = Posterior(kernel, tuple(float(t) for t in theta), m, X, alpha, ld, lo, G, None) if want_posterior else None
+            post = Posterior(kernel, key, m, X, alpha, ld, lo, G, None, scale=scale) if want_posterior else None
         stats = dict(iterations=st.iterations, n_cholesky=st.n_cholesky, converged=bool(st.converged), T=st.T,
                      gradnorm=st.gradnorm, lbfgs_iterations=st.lbfgs_iterations, lbfgs_evals=st.lbfgs_evals,
                      lbfgs_status=st.lbfgs_status)
         return dict(Sigma=Sigma, Sigma_inv=Sinv, L=L, Linv=Linv, fMAP=fmap, post=post, stats=stats, info=info.value)
 
     def posterior(self, X, theta, kernel, Sigma_inv, fMAP, m, want_P=False) -> Posterior:
-        X = self.dev(X)
+        key = theta_key(theta)
+        X, _, scale = self._ard(X, theta, kernel)
         f = self.dev(fMAP).reshape(-1)
         N = f.numel()
         alpha, ld, lo = self.empty(N), self.empty(N), self.empty(N)
@@ -440,12 +518,12 @@ class Engine:
         rc = self.lib.ppbo_posterior(self.ctx, _ptr(Sigma_inv), _ptr(f), N, m, float(theta[0]), _ptr(alpha), _ptr(ld),
                                      _ptr(lo), _ptr(G), _ptr(P), C.byref(info), self._stream())
         self._check(rc, "ppbo_posterior", info.value)
-        return Posterior(kernel, tuple(float(t) for t in theta), m, X, alpha, ld, lo, G, P)
+        return Posterior(kernel, key, m, X, alpha, ld, lo, G, P, scale=scale)
 
     # ---- prediction ---------------------------------------------------------------
     def predict(self, post: Posterior, Xc, score=SCORE_MEAN, mustar=0.0, want_mu=True, want_var=True,
                 want_score=False, want_best=True, kstar_fp32=False):
-        Xc = self.dev(Xc)
+        Xc = self._points(post, Xc)
         M = Xc.shape[0]
         with_var = want_var or score != SCORE_MEAN
         md = self._model(post, with_var, kstar_fp32)
@@ -460,7 +538,7 @@ class Engine:
         return dict(mu=mu, var=var, score=sc, best_val=bv.value, best_idx=bi.value)
 
     def predict_cov(self, post: Posterior, Xc, shrink=SHRINKAGE):
-        Xc = self.dev(Xc)
+        Xc = self._points(post, Xc)
         M = Xc.shape[0]
         md = self._model(post, True)
         mu, cov = self.empty(M), self.empty(M, M)
@@ -470,20 +548,26 @@ class Engine:
         return mu, cov
 
     def mean_grad(self, post: Posterior, Xc):
-        """mu[M] and d mu / d x [M,D] at the rows of Xc (ppbo_mean_grad)."""
-        Xc = self.dev(Xc)
+        """mu[M] and d mu / d x [M,D] at the rows of Xc (ppbo_mean_grad).  ARD: the gradient is taken back to the caller's
+        coordinates, d mu / d x_d = s_d d mu / d x~_d."""
+        Xc = self._points(post, Xc)
         M, D = Xc.shape
         md = self._model(post, False)
         mu, grad = self.empty(M), self.empty(M, D)
         rc = self.lib.ppbo_mean_grad(self.ctx, C.byref(md), _ptr(Xc), M, _ptr(mu), _ptr(grad), self._stream())
         self._check(rc, "ppbo_mean_grad")
+        if post.scale is not None and M > 0:
+            self.scale_points(grad, post.scale, out=grad)
         return mu, grad
 
     def mean_search(self, post: Posterior, cand, K=32, sep=0.05, iters=100, tol=1e-9, sync=True):
         """Device-resident maximiser of the posterior mean over the rows of `cand` (ppbo_mean_search): returns the
         refined maxima x[found, D], mu[found] as NumPy arrays.  sync=False only enqueues (h_found = NULL: nothing
         synchronises) and returns the device tensors x[K, D], mu[K] -- rows that found no start carry mu = -inf -- so
-        that several searches can be queued behind each other and read back together."""
+        that several searches can be queued behind each other and read back together.  Not for an ARD posterior
+        (mean_search_multi is)."""
+        if post.scale is not None:
+            raise ValueError("mean_search has no per-dimension length-scale form: use mean_search_multi")
         cand = self.dev(cand)
         M, D = cand.shape
         md = self._model(post, False)
@@ -530,11 +614,16 @@ class Engine:
         md = self._model(post, False)
         xs, mus = self.empty(T, K, D), self.empty(T, K)
         dp = C.POINTER(C.c_double)
-        rc = self.lib.ppbo_mean_search_multi(self.ctx, C.byref(md), _ptr(pool), M, sh.ctypes.data_as(dp), T, _ptr(ex_ptr), E,
-                                             xp.ctypes.data_as(dp) if xp is not None else None, int(K), float(sep),
-                                             int(iters), float(tol), int(bool(screen_fp32)), _ptr(xs), _ptr(mus),
-                                             self._stream())
-        self._check(rc, "ppbo_mean_search_multi")
+        args = (self.ctx, C.byref(md), _ptr(pool), M, sh.ctypes.data_as(dp), T, _ptr(ex_ptr), E,
+                xp.ctypes.data_as(dp) if xp is not None else None, int(K), float(sep), int(iters), float(tol),
+                int(bool(screen_fp32)), _ptr(xs), _ptr(mus))
+        if post.scale is None:
+            rc = self.lib.ppbo_mean_search_multi(*args, self._stream())
+            self._check(rc, "ppbo_mean_search_multi")
+        else:       # everything in the caller's coordinates; "design" = the model's rows taken back to them
+            sc = np.ascontiguousarray(post.scale, dtype=np.float64)
+            rc = self.lib.ppbo_mean_search_multi_scaled(*args, self._dptr(sc), self._stream())
+            self._check(rc, "ppbo_mean_search_multi_scaled")
         return xs, mus
 
     def mean_ascent(self, post: Posterior, starts, iters=100, tol=1e-9):
@@ -543,9 +632,15 @@ class Engine:
         md = self._model(post, False)
         xs, mus = self.empty(K, D), self.empty(K)
         its = torch.zeros(K, dtype=torch.int32, device=self.device)
-        rc = self.lib.ppbo_mean_ascent(self.ctx, C.byref(md), _ptr(starts), K, int(iters), float(tol), _ptr(xs), _ptr(mus),
-                                       _ptr(its), self._stream())
-        self._check(rc, "ppbo_mean_ascent")
+        if post.scale is None:
+            rc = self.lib.ppbo_mean_ascent(self.ctx, C.byref(md), _ptr(starts), K, int(iters), float(tol), _ptr(xs), _ptr(mus),
+                                           _ptr(its), self._stream())
+            self._check(rc, "ppbo_mean_ascent")
+        else:       # starts, box and results in the caller's coordinates
+            sc = np.ascontiguousarray(post.scale, dtype=np.float64)
+            rc = self.lib.ppbo_mean_ascent_scaled(self.ctx, C.byref(md), _ptr(starts), K, int(iters), float(tol), _ptr(xs),
+                                                  _ptr(mus), _ptr(its), self._dptr(sc), self._stream())
+            self._check(rc, "ppbo_mean_ascent_scaled")
         return xs, mus, its
 
     def shift_points(self, pool, shift, out=None):
@@ -560,7 +655,9 @@ class Engine:
 
     def line_acq(self, post: Posterior, grid, z, mustar, shrink=SHRINKAGE, jitter=0.0):
         grid = self.dev(grid)
-        B, G, _ = grid.shape
+        B, G, D = grid.shape
+        if post.scale is not None:
+            grid = self._points(post, grid.reshape(B * G, D)).reshape(B, G, D)
         z = self.dev(z)
         S = z.shape[0]
         md = self._model(post, True)
@@ -572,11 +669,13 @@ class Engine:
 
     def line_acq_xi(self, post: Posterior, xis, xs, alphas, z, mustar, shrink=SHRINKAGE, jitter=0.0):
         """EI and varmax of the B lines {alpha * xis[b] + xs[b]} (ppbo_line_acq_xi): the grid points are formed on the
-        device.  alphas: [G] (shared by all lines) or [B, G]."""
+        device.  alphas: [G] (shared by all lines) or [B, G].  ARD: the line is linear in (xi, x), so s (.) xi and s (.) x
+        give the scaled points at the same alpha."""
         xis, xs, alphas, z = self.dev(xis), self.dev(xs), self.dev(alphas), self.dev(z)
         B, D = xis.shape
         if xs.shape != (B, D):
             raise ValueError("line_acq_xi: xis and xs must both be [B, D]")
+        xis, xs = self._points(post, xis), self._points(post, xs)
         per_line = alphas.dim() == 2
         G = alphas.shape[-1]
         if per_line and alphas.shape[0] != B:

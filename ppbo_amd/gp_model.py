@@ -21,7 +21,7 @@ import numpy as np
 import scipy.optimize
 
 from . import kernels as _kernels
-from .engine import NotPositiveDefinite, SCORE_MEAN, get_engine
+from .engine import NotPositiveDefinite, SCORE_MEAN, get_engine, lengthscales, theta_key
 from .feedback_processing import FeedbackProcessing
 
 SEARCH_CANDIDATES = 65536      # uniform candidates per mu_star trial
@@ -30,6 +30,26 @@ ASCENT_ITERS = 100             # cap on ascent iterations per start (all inside 
 POLISH_GRAD_TOL = 1e-6         # |projected grad mu| / |mu| above which mu_star's winner gets the L-BFGS-B polish
 APPEND_REFRESH = 64            # incremental mode: bordered updates of Sigma^-1 between two full inversions (measured:
                                # 32 appends leave |Sigma Sigma^-1 - I| where a full inversion leaves it, 8.2e-8 at N = 2048)
+
+
+def log_prior(theta):
+    """The reference's log-prior of theta (gp_model.py:287-290): lognormal on sigma (s = 1, scale e), on the length scale
+    (s = 0.5, scale e^-1.4) and on sigma_f (s = 0.5, scale e^1.7).  With per-dimension length scales the length-scale
+    prior applies to each l_d and the terms are summed (independent priors); a scalar l gives the reference's value."""
+    import scipy.stats
+    l = theta[1]
+    if np.ndim(l) == 0:
+        lp_l = np.log(scipy.stats.lognorm.pdf(l, s=0.5, scale=np.exp(-1.4)))
+    else:
+        lp_l = float(np.sum(np.log(scipy.stats.lognorm.pdf(np.asarray(l, dtype=float), s=0.5, scale=np.exp(-1.4)))))
+    return (np.log(scipy.stats.lognorm.pdf(theta[0], s=1, scale=np.exp(1))) + lp_l
+            + np.log(scipy.stats.lognorm.pdf(theta[2], s=0.5, scale=np.exp(1.7))))
+
+
+def _theta_list(theta):
+    """[sigma, l, sigma_f] with floats, l a float or a float64 vector (per-dimension length scales)."""
+    l = theta[1]
+    return [float(theta[0]), float(l) if np.ndim(l) == 0 else np.asarray(l, dtype=float).copy(), float(theta[2])]
 
 
 class GPModel:
@@ -75,6 +95,8 @@ class GPModel:
         self.xi_acquisition_function = s.xi_acquisition_function
         self.kernel = _kernels.BY_NAME[s.kernel]    # the reference eval()s the string (gp_model.py:48)
         self.theta_initial = s.theta_initial
+        if self.theta_initial is not None and self.theta_initial[1] is not None:
+            lengthscales(self.theta_initial, self.D, s.kernel)      # raises on a vector l the kernel / D cannot take
         self.theta = None
         self.fMAP = None
         self.fMAP_finding_trials = 1
@@ -195,14 +217,14 @@ class GPModel:
         st = self._sinv_state
         if self._dL is None:
             return
-        th = None if theta is None else tuple(float(t) for t in theta)
+        th = None if theta is None else theta_key(theta)
         if st is None or self._dL.shape[0] != self.N or (th is not None and st[1] != th):
             self._dL_stale = True
         else:
             self._dL_stale = False
 
     def update_Sigma_inv(self, theta):
-        th = tuple(float(t) for t in theta)
+        th = theta_key(theta)
         st = self._sinv_state
         done = False
         if (self.incremental and st is not None and self._dLinv is not None and self._dL is not None and st[1] == th
@@ -330,7 +352,6 @@ class GPModel:
     # ------------------------------------------------------------------ evidence / hyper-parameters
     def _evidence_core(self, eng, theta, f0):
         """One Laplace evidence on `eng` from the start vector f0 (device); returns (value incl. log-prior, log-evidence)."""
-        import scipy.stats
         Sig = eng.gram(self._dX, theta, self.kernel.__name__, self.COVARIANCE_SHRINKAGE)
         if self.fMAP_method == "whitened":
             Sinv, L = eng.pd_inverse_chol(Sig)
@@ -340,17 +361,15 @@ class GPModel:
         _, _, ld, lo = eng.laplace_terms(fm, self.m, theta[0])
         sgn, logdet, _ = eng.laplace_logdet(Sig, ld, lo, self.m)
         log_evidence = st["T"] - 0.5 * sgn * logdet
-        lp = (np.log(scipy.stats.lognorm.pdf(theta[0], s=1, scale=np.exp(1)))
-              + np.log(scipy.stats.lognorm.pdf(theta[1], s=0.5, scale=np.exp(-1.4)))
-              + np.log(scipy.stats.lognorm.pdf(theta[2], s=0.5, scale=np.exp(1.7))))
-        return log_evidence + lp, log_evidence
+        return log_evidence + log_prior(theta), log_evidence
 
     def evidence(self, theta, f_initial):
         """Laplace log-marginal likelihood + log-prior (gp_model.py:278-319) on the device.
         As in the reference, f_initial is IGNORED and redrawn from N(0, self.Sigma) (:294), the matrix is
         I + Sigma_theta*Lambda_MAP (plus sign, :302) and the determinant term is the sum of sign*logdet over the
-        LU factors (:307-310), i.e. sign(prod diag U) * sum log|diag U| with LAPACK's pivoting."""
-        theta = [float(t) for t in theta]
+        LU factors (:307-310), i.e. sign(prod diag U) * sum log|diag U| with LAPACK's pivoting.  theta[1] may be a
+        vector of per-dimension length scales (log_prior sums the length-scale prior over them)."""
+        theta = _theta_list(theta)
         if self.verbose:
             print("---------- Iter results ----------------")
         value, log_evidence = self._evidence_core(self.eng, theta, self._draw_prior())
@@ -374,13 +393,13 @@ class GPModel:
         of both is compared across ranks first and a mismatch raises.  NaN / inf -> -500 as in the reference
         (gp_model.py:314-316)."""
         from . import dist as _dist
-        thetas = [[float(t) for t in th] for th in thetas]
+        thetas = [_theta_list(th) for th in thetas]
         f0s = [self._draw_prior() for _ in thetas]
         rank, world = _dist.rank_world()
         if world > 1:
             # rank r evaluates thetas[r::world] and the values are merged BY POSITION: that is only meaningful when
             # every rank holds the same candidate list and the same start vectors, i.e. identical NumPy streams
-            tarr = np.asarray(thetas, dtype=float)
+            tarr = np.asarray([np.hstack([np.ravel(t) for t in th]) for th in thetas], dtype=float)
             _dist.assert_same_across_ranks(
                 [len(thetas), float(tarr.sum()), float((tarr * np.arange(1, tarr.size + 1).reshape(tarr.shape)).sum()),
                  float(f0s[0].sum().item()) if f0s else 0.0],
@@ -397,10 +416,21 @@ class GPModel:
         drives GPyOpt's Bayesian optimisation (20 initial + 40 iterations = 60 evidence fits); GPyOpt is replaced
         by the same budget of device evidence fits: 20 uniform draws over the reference's box (one concurrent
         batch), then 4 batches of 10 shrinking Gaussian perturbations of the incumbent.  The search TRAJECTORY is
-        unpinned (GPyOpt==1.2.6 absent); the objective is the pinned evidence()."""
+        unpinned (GPyOpt==1.2.6 absent); the objective is the pinned evidence().
+        Per-dimension length scales in theta_initial: the same 2-parameter search, 60 evidence fits and box, over a common
+        factor c of the initial profile, l = c p with p = l0 / geomean(l0), and sigma_f (fitting the D length scales
+        one by one needs evidence gradients, which the project does not have)."""
         if self.verbose:
             print("Hyperparameter optimization begins...")
         start = time.time()
+        l0 = self.theta_initial[1] if self.theta_initial is not None else None
+        profile = None
+        if l0 is not None and np.ndim(l0) != 0:
+            l0 = lengthscales(self.theta_initial, self.D, self.kernel.__name__)
+            profile = l0 / np.exp(np.mean(np.log(l0)))
+
+        def ls(c):
+            return float(c) if profile is None else float(c) * profile
         lo, hi = np.array([0.01, 0.1]), np.array([2.0, 15.0])
         best_v, best_t = -np.inf, None
         self.theta_search_log = []
@@ -410,14 +440,14 @@ class GPModel:
             else:
                 width = 0.25 * (hi - lo) * (0.5 ** (rnd - 1))
                 cands = np.clip(best_t + width * np.random.standard_normal((10, 2)), lo, hi)
-            vals = self.evidence_batch([[1.0, c[0], c[1]] for c in cands], workers=workers)
+            vals = self.evidence_batch([[1.0, ls(c[0]), c[1]] for c in cands], workers=workers)
             for c, v in zip(cands, vals):
                 self.theta_search_log.append((float(c[0]), float(c[1]), float(v)))
                 if v > best_v:
                     best_v, best_t = v, c
         if self.verbose:
             print("Optimization of hyperparameters took " + str(time.time() - start) + " seconds.")
-        self.theta = [1.0, float(best_t[0]), float(best_t[1])]
+        self.theta = [1.0, ls(best_t[0]), float(best_t[1])]
         if self.verbose:
             print("The optimized theta is " + str(self.theta))
 
@@ -505,10 +535,8 @@ class GPModel:
         self._refresh_mean_state(best)
 
     def _refresh_mean_state(self, fmap_dev):
-        from .engine import Posterior
         alpha = self.eng.dgemv(self._dSigma_inv, fmap_dev)
-        self._post_mean = Posterior(self.kernel.__name__, tuple(float(t) for t in self.theta), self.m, self._dX, alpha,
-                                    None, None, None)
+        self._post_mean = self.eng.mean_posterior(self._dX, self.theta, self.kernel.__name__, self.m, alpha)
 
     def _fit_fused(self, defer_posterior=False):
         """The default update (one prior-draw start, whitened search) as ONE library call: ppbo_gp_fit builds Sigma,
@@ -529,7 +557,7 @@ class GPModel:
         r = self.eng.gp_fit(self._dX, self.theta, self.kernel.__name__, self.m, z0, shrink=self.COVARIANCE_SHRINKAGE,
                             gtol=self.fMAP_gtol, start_is_whitened=True, want_Sigma=True,
                             want_posterior=not defer_posterior)
-        th = tuple(float(t) for t in self.theta)
+        th = theta_key(self.theta)
         self._dSigma, self._dSigma_inv, self._dL, self._dLinv = r["Sigma"], r["Sigma_inv"], r["L"], None
         self._sinv_state = (self.X.copy(), th, 0)
         self._dL_stale = False

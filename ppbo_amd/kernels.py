@@ -10,7 +10,8 @@ from .engine import get_engine
 
 
 def _eval(name, X1, X2, theta):
-    if theta[1] <= 0 or theta[2] <= 0:
+    # theta[1]: a scalar or, for the radial kernels, one length scale per input dimension (engine.lengthscales)
+    if np.any(np.asarray(theta[1]) <= 0) or theta[2] <= 0:
         print("Check hyperparameter values!")          # the reference only prints (src/kernels.py:22-23)
     X1 = np.atleast_2d(np.asarray(X1, dtype=np.float64))
     X2 = np.atleast_2d(np.asarray(X2, dtype=np.float64))

@@ -74,10 +74,13 @@ class Hsampler:
 
     # ---- basis -----------------------------------------------------------------
     def generate_basis(self):
+        # per-dimension length scales (ARD): column d of W is divided by l_d -- the spectral density of the scaled kernel --
+        # with the same draws in the same order as a scalar l
+        ls = self.theta[1] if np.ndim(self.theta[1]) == 0 else np.asarray(self.theta[1], dtype=float)
         if self.kernel == "SE_kernel":                        # the reference supports the SE spectral density only (:40-42)
-            self.W = np.random.randn(self.nFeatures, self.D) / self.theta[1]
+            self.W = np.random.randn(self.nFeatures, self.D) / ls
         elif self.kernel in MATERN_NU:
-            self.W = matern_spectral_draw(self.nFeatures, self.D, self.theta[1], MATERN_NU[self.kernel])
+            self.W = matern_spectral_draw(self.nFeatures, self.D, ls, MATERN_NU[self.kernel])
         self.b = np.random.uniform(low=0, high=2 * np.pi, size=self.nFeatures)[:, None]
 
     def _scale(self):
