@@ -457,6 +457,26 @@ PPBO_API int ppbo_laplace_logdet(ppbo_ctx* ctx, const double* d_Sigma, const dou
                         const double* d_lam_off, int N, int m, double* h_u_sign, double* h_u_logdet,
                         int* h_info, void* stream);
 
+/* ---- gradient of the Laplace evidence (no reference counterpart: the reference's theta search is derivative-free,
+ * src/gp_model.py:391-413) ----------------------------------------------------------------------------------------------
+ * ppbo_evidence_grad takes what one evidence leaves behind -- the rows d_X[N,D] and theta[3] as the device sees them (an
+ * ARD model passes its scaled rows and theta[1] = 1), the shrink, m, d_Sigma, d_Sigma_inv, d_fMAP and the star-form
+ * d_lam_diag / d_lam_off of Lambda(f_MAP) -- and returns
+ *   *h_u_sign, *h_u_logdet   bit-identical to ppbo_laplace_logdet on the same inputs (the same LU launches);
+ *   h_sums[D + 1]            h_sums[d] = sum_ij W_ij kappa'(rho_ij^2) (x_id - x_jd)^2 for d < D and
+ *                            h_sums[D] = sum_ij W_ij Sigma_ij, with rho^2 = |x_i - x_j|^2 / theta[1]^2 and
+ *                            W = 1/2 alpha alpha^T - 1/2 s_U Lambda A^-1 - 1/2 s_U (Sigma^-1 Q^-1 v) alpha^T
+ *                            (A = I + Sigma Lambda, Q = Sigma^-1 - Lambda, alpha = Sigma^-1 f_MAP, v the implicit f_MAP
+ *                            term).  The host forms dE/dl_d = -2 (1 - shrink) sigma_f^2 h_sums[d] /
+ *                            (theta[1]^2 l_d) and dE/dsigma_f = 2 h_sums[D] / sigma_f, plus the log-prior's terms.
+ * Deterministic: fixed-order reductions, no floating-point atomics.  Radial kernels only (camphor-copper: "invalid
+ * argument"); N <= 20480.  *h_info = 0; -k when u_kk == 0 (log|det A| = -inf); PPBO_ERR_NOT_PD with *h_info = 2 when Q
+ * is not positive definite (f_MAP is not a maximum, the implicit term is undefined). */
+PPBO_API int ppbo_evidence_grad(ppbo_ctx* ctx, int kernel_id, const double* d_X, int N, int D, const double theta[3],
+                       double shrink, int m, const double* d_Sigma, const double* d_Sigma_inv, const double* d_fMAP,
+                       const double* d_lam_diag, const double* d_lam_off, double* h_u_sign, double* h_u_logdet,
+                       double* h_sums, int* h_info, void* stream);
+
 /* ---- (e) the path's one collective, over RCCL / xGMI ---------------------------------------------------
  * Candidate rows are sharded over one process per GPU; every rank scores its shard with
  * ppbo_predict and contributes (best score, GLOBAL row index).  ppbo_argmax_allgather is ONE ncclAllGather of a

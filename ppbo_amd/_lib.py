@@ -93,6 +93,8 @@ SIGNATURES = {
     "ppbo_rff_omega_map": [_vp, _vp, _i, _i, _i, _d, _vp, _i, _d, C.POINTER(_d), C.POINTER(_d), C.POINTER(_i), _vp],
     "ppbo_lu_slogdet": [_vp, _vp, _i, _i, C.POINTER(_d), C.POINTER(_d), C.POINTER(_i), _vp],
     "ppbo_laplace_logdet": [_vp, _vp, _vp, _vp, _i, _i, C.POINTER(_d), C.POINTER(_d), C.POINTER(_i), _vp],
+    "ppbo_evidence_grad": [_vp, _i, _vp, _i, _i, _dp3, _d, _i, _vp, _vp, _vp, _vp, _vp, C.POINTER(_d), C.POINTER(_d), _dp3,
+                           C.POINTER(_i), _vp],
     "ppbo_dgemv": [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp],
     "ppbo_dist_unique_id": [_vp, _vp],
     "ppbo_dist_init": [_vp, _vp, _i, _i],

@@ -82,3 +82,9 @@ int ppbo_gemvT_beta_async(ppbo_ctx* ctx, const double* d_L, int N, int ldl, cons
                           PpboGate rider_gate = PpboGate(), PpboDotsOut dots = PpboDotsOut(), int* n_dot_parts = nullptr);
 // out[0] = sum_i x_i y_i  (deterministic single-block reduction)
 int ppbo_dot_async(ppbo_ctx* ctx, const double* d_x, const double* d_y, int N, double* d_out, hipStream_t s);
+// lu.hip: M = I + Sigma Lambda from the star-form Lambda (row pitch N), and the LU with partial pivoting of
+// ppbo_lu_slogdet in place, enqueued only: d_ipiv[N] (0-based pivot rows) and d_info (0 or the 1-based column of a zero
+// pivot) are kept on the device, d_out[0] = prod sign(u_ii), d_out[1] = sum log|u_ii|
+int ppbo_ipsl_async(ppbo_ctx* ctx, const double* d_Sigma, int N, int m, const double* d_lam_diag, const double* d_lam_off,
+                    double* d_M, hipStream_t s);
+int ppbo_getrf_async(ppbo_ctx* ctx, double* d_A, int N, int lda, int* d_ipiv, int* d_info, double* d_out, hipStream_t s);

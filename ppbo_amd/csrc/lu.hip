@@ -308,17 +308,16 @@ __global__ __launch_bounds__(256) void ipsl_kernel(const double* __restrict__ S,
 
 }  // namespace
 
-extern "C" {
+// ---- internal (linalg.h): the pieces of ppbo_laplace_logdet that csrc/evgrad.hip reuses ------------------------------
+int ppbo_ipsl_async(ppbo_ctx* ctx, const double* d_Sigma, int N, int m, const double* d_lam_diag, const double* d_lam_off,
+                    double* d_M, hipStream_t s) {
+  const int mblk = m + 1, n_q = N / mblk;
+  ipsl_kernel<<<dim3((N + 255) / 256, n_q), 256, 0, s>>>(d_Sigma, N, mblk, d_lam_diag, d_lam_off, d_M);
+  PPBO_LAUNCH_CHECK(ctx);
+  return 0;
+}
 
-int ppbo_lu_slogdet(ppbo_ctx* ctx, double* d_A, int N, int lda, double* h_u_sign, double* h_u_logdet, int* h_info,
-                    void* stream) {
-  PPBO_ENTER(ctx);
-  PPBO_REQUIRE(ctx, d_A && N > 0 && lda >= N, "matrix");
-  hipStream_t s = (hipStream_t)stream;
-  double* d_out = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_VEC, 4 * sizeof(double) + ((size_t)N + 8) * sizeof(int));
-  if (!d_out) return (int)hipErrorOutOfMemory;
-  int* d_ipiv = reinterpret_cast<int*>(d_out + 4);
-  int* d_info = d_ipiv + N;
+int ppbo_getrf_async(ppbo_ctx* ctx, double* d_A, int N, int lda, int* d_ipiv, int* d_info, double* d_out, hipStream_t s) {
   PPBO_HIP_CHECK(ctx, hipMemsetAsync(d_info, 0, sizeof(int), s));
   for (int k0 = 0; k0 < N; k0 += LNB) {
     const int nb = (N - k0 < LNB) ? (N - k0) : LNB;
@@ -341,6 +340,21 @@ int ppbo_lu_slogdet(ppbo_ctx* ctx, double* d_A, int N, int lda, double* h_u_sign
   }
   diag_slogdet_kernel<<<1, 1024, 0, s>>>(d_A, lda, N, d_out);
   PPBO_LAUNCH_CHECK(ctx);
+  return 0;
+}
+
+extern "C" {
+
+int ppbo_lu_slogdet(ppbo_ctx* ctx, double* d_A, int N, int lda, double* h_u_sign, double* h_u_logdet, int* h_info,
+                    void* stream) {
+  PPBO_ENTER(ctx);
+  PPBO_REQUIRE(ctx, d_A && N > 0 && lda >= N, "matrix");
+  hipStream_t s = (hipStream_t)stream;
+  double* d_out = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_VEC, 4 * sizeof(double) + ((size_t)N + 8) * sizeof(int));
+  if (!d_out) return (int)hipErrorOutOfMemory;
+  int* d_ipiv = reinterpret_cast<int*>(d_out + 4);
+  int* d_info = d_ipiv + N;
+  if (int rc = ppbo_getrf_async(ctx, d_A, N, lda, d_ipiv, d_info, d_out, s)) return rc;
   double h[2];
   int info = 0;
   PPBO_HIP_CHECK(ctx, hipMemcpyAsync(h, d_out, sizeof(h), hipMemcpyDeviceToHost, s));
@@ -358,11 +372,9 @@ int ppbo_laplace_logdet(ppbo_ctx* ctx, const double* d_Sigma, const double* d_la
   PPBO_REQUIRE(ctx, d_Sigma && d_lam_diag && d_lam_off, "null pointer");
   PPBO_REQUIRE(ctx, N > 0 && m >= 1 && N % (m + 1) == 0, "sizes");
   hipStream_t s = (hipStream_t)stream;
-  const int mblk = m + 1, n_q = N / mblk;
   double* M = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_LINALG, (size_t)2 * N * N * sizeof(double));
   if (!M) return (int)hipErrorOutOfMemory;
-  ipsl_kernel<<<dim3((N + 255) / 256, n_q), 256, 0, s>>>(d_Sigma, N, mblk, d_lam_diag, d_lam_off, M);
-  PPBO_LAUNCH_CHECK(ctx);
+  if (int rc = ppbo_ipsl_async(ctx, d_Sigma, N, m, d_lam_diag, d_lam_off, M, s)) return rc;
   return ppbo_lu_slogdet(ctx, M, N, N, h_u_sign, h_u_logdet, h_info, stream);
 }
 

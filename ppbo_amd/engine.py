@@ -394,6 +394,25 @@ class Engine:
         self._check(rc, "ppbo_laplace_logdet")
         return sg.value, ld.value, info.value
 
+    def evidence_grad(self, X, theta, kernel, Sigma, Sigma_inv, fMAP, lam_diag, lam_off, m, shrink=SHRINKAGE):
+        """ppbo_evidence_grad at one evidence's state (X and theta in the caller's coordinates; Sigma, Sigma^-1, f_MAP and
+        the star-form Lambda(f_MAP) as the evidence formed them).  Returns (s_U, log|det A|, sums[D + 1], info) with the
+        sign and log-determinant bit-identical to laplace_logdet; sums as include/ppbo_hip.h defines them, for the rows
+        the device works on (scaled by 1 / l for per-dimension length scales).  Raises ValueError for a kernel that is
+        not radial and NotPositiveDefinite (info = 2) when Sigma^-1 - Lambda is not positive definite."""
+        if kernel not in RADIAL_KERNELS:
+            raise ValueError(f"the evidence gradient is defined for the radial kernels {RADIAL_KERNELS}, not {kernel}")
+        Xd, th, _ = self._ard(X, theta, kernel)
+        N, D = Xd.shape
+        f = self.dev(fMAP).reshape(-1)
+        sg, ld, info = C.c_double(0.0), C.c_double(0.0), C.c_int(0)
+        sums = np.zeros(D + 1)
+        rc = self.lib.ppbo_evidence_grad(self.ctx, KERNEL_IDS[kernel], _ptr(Xd), N, D, self._theta(th), float(shrink), int(m),
+                                         _ptr(Sigma), _ptr(Sigma_inv), _ptr(f), _ptr(lam_diag), _ptr(lam_off), C.byref(sg),
+                                         C.byref(ld), self._dptr(sums), C.byref(info), self._stream())
+        self._check(rc, "ppbo_evidence_grad", info.value)
+        return sg.value, ld.value, sums, info.value
+
     def dgemv(self, A, x, trans=False, lower=False):
         A, x = self.dev(A), self.dev(x).reshape(-1)
         N = A.shape[0]

@@ -21,13 +21,16 @@ import numpy as np
 import scipy.optimize
 
 from . import kernels as _kernels
-from .engine import NotPositiveDefinite, SCORE_MEAN, get_engine, lengthscales, theta_key
+from .engine import NotPositiveDefinite, RADIAL_KERNELS, SCORE_MEAN, get_engine, lengthscales, theta_key
 from .feedback_processing import FeedbackProcessing
 
 SEARCH_CANDIDATES = 65536      # uniform candidates per mu_star trial
 ASCENT_STARTS = 32             # best well-separated candidates refined together on the device
 ASCENT_ITERS = 100             # cap on ascent iterations per start (all inside one mean_ascent_kernel launch)
 POLISH_GRAD_TOL = 1e-6         # |projected grad mu| / |mu| above which mu_star's winner gets the L-BFGS-B polish
+ARD_FIT_GTOL = 1e-6            # optimize_theta_ard: f_MAP tolerance of each evaluation (the gradient's implicit term
+                               # assumes grad T = 0; its error is of the order of |grad T|)
+THETA_BOX = ((0.01, 2.0), (0.1, 15.0))    # the reference's search box for l and sigma_f (gp_model.py:397-398), sigma = 1
 APPEND_REFRESH = 64            # incremental mode: bordered updates of Sigma^-1 between two full inversions (measured:
                                # 32 appends leave |Sigma Sigma^-1 - I| where a full inversion leaves it, 8.2e-8 at N = 2048)
 
@@ -44,6 +47,15 @@ def log_prior(theta):
         lp_l = float(np.sum(np.log(scipy.stats.lognorm.pdf(np.asarray(l, dtype=float), s=0.5, scale=np.exp(-1.4)))))
     return (np.log(scipy.stats.lognorm.pdf(theta[0], s=1, scale=np.exp(1))) + lp_l
             + np.log(scipy.stats.lognorm.pdf(theta[2], s=0.5, scale=np.exp(1.7))))
+
+
+def log_prior_grad(theta):
+    """Gradient of log_prior with respect to (l, sigma_f): each lognormal term gives -(1 + (ln x - ln scale) / s^2) / x.
+    A scalar l gives two entries, a vector of D length scales D + 1."""
+    l = np.ravel(np.asarray(theta[1], dtype=float))
+    gl = -(1.0 + (np.log(l) + 1.4) / 0.25) / l
+    sf = float(theta[2])
+    return np.append(gl, -(1.0 + (np.log(sf) - 1.7) / 0.25) / sf)
 
 
 def _theta_list(theta):
@@ -76,6 +88,8 @@ class GPModel:
         # SciPy's included, picks its own: DESIGN 5); anything else: the exact Newton trust region on f alone, which
         # follows SciPy trust-exact's iteration rules
         self.fMAP_method = fMAP_method if fMAP_method is not None else getattr(PPBO_settings, "fMAP_method", "whitened")
+        # update_model(optimize_theta=True): "search" (optimize_theta) or "ard-gradient" (optimize_theta_ard)
+        self.theta_optimizer = getattr(PPBO_settings, "theta_optimizer", "search")
         if self.fMAP_method not in ("whitened", "trust-region"):
             raise ValueError("fMAP_method must be 'whitened' or 'trust-region'")
         self.fit_log = []            # one dict per update_fMAP trial: iterations, n_cholesky, warm, seconds
@@ -350,15 +364,20 @@ class GPModel:
         return 8 if N <= 2048 else (4 if N <= 4096 else 2)
 
     # ------------------------------------------------------------------ evidence / hyper-parameters
-    def _evidence_core(self, eng, theta, f0):
-        """One Laplace evidence on `eng` from the start vector f0 (device); returns (value incl. log-prior, log-evidence)."""
+    def _evidence_fit(self, eng, theta, f0, gtol=1e-4):
+        """The Gram matrix, its inverse, f_MAP from f0 and Lambda(f_MAP) of one Laplace evidence on `eng`."""
         Sig = eng.gram(self._dX, theta, self.kernel.__name__, self.COVARIANCE_SHRINKAGE)
         if self.fMAP_method == "whitened":
             Sinv, L = eng.pd_inverse_chol(Sig)
         else:
             Sinv, L = eng.pd_inverse(Sig), None
-        fm, st = eng.fit_fmap(Sinv, f0, self.m, theta[0], gtol=1e-4, maxiter=500, L=L)
+        fm, st = eng.fit_fmap(Sinv, f0, self.m, theta[0], gtol=gtol, maxiter=500, L=L)
         _, _, ld, lo = eng.laplace_terms(fm, self.m, theta[0])
+        return Sig, Sinv, fm, st, ld, lo
+
+    def _evidence_core(self, eng, theta, f0):
+        """One Laplace evidence on `eng` from the start vector f0 (device); returns (value incl. log-prior, log-evidence)."""
+        Sig, _, _, st, ld, lo = self._evidence_fit(eng, theta, f0)
         sgn, logdet, _ = eng.laplace_logdet(Sig, ld, lo, self.m)
         log_evidence = st["T"] - 0.5 * sgn * logdet
         return log_evidence + log_prior(theta), log_evidence
@@ -449,6 +468,102 @@ class GPModel:
             print("Optimization of hyperparameters took " + str(time.time() - start) + " seconds.")
         self.theta = [1.0, ls(best_t[0]), float(best_t[1])]
         if self.verbose:
+            print("The optimized theta is " + str(self.theta))
+
+    def evidence_grad(self, theta, f_initial=None, gtol=None):
+        """evidence() and its gradient with respect to (l, sigma_f), sigma fixed (no reference counterpart).
+        Returns (value, grad, log_evidence, s_U, f_MAP): value = log-evidence + log-prior as evidence() computes it (the
+        same Gram, inverse, fit and LU; the start is f_initial, or a prior draw from the global stream when it is None,
+        and f_MAP is found to gtol, default 1e-4 as in evidence()); grad has one entry per length scale (one for a
+        scalar l, D for a vector) followed by dE/dsigma_f; s_U is the sign of the LU's prod u_kk, f_MAP the device
+        vector.  A non-finite value maps to -500 with a zero gradient.  Raises ValueError for the camphor-copper
+        kernel and NotPositiveDefinite when Sigma or Sigma^-1 - Lambda(f_MAP) is not positive definite."""
+        theta = _theta_list(theta)
+        kern = self.kernel.__name__
+        if kern not in RADIAL_KERNELS:
+            raise ValueError(f"the evidence gradient is defined for the radial kernels {RADIAL_KERNELS}, not {kern}")
+        ls = lengthscales(theta, self.D, kern)
+        f0 = self._draw_prior() if f_initial is None else self.eng.dev(f_initial).reshape(-1)
+        Sig, Sinv, fm, st, ld, lo = self._evidence_fit(self.eng, theta, f0, 1e-4 if gtol is None else float(gtol))
+        sgn, logdet, sums, _ = self.eng.evidence_grad(self._dX, theta, kern, Sig, Sinv, fm, ld, lo, self.m,
+                                                      self.COVARIANCE_SHRINKAGE)
+        log_evidence = st["T"] - 0.5 * sgn * logdet
+        value = log_evidence + log_prior(theta)
+        sf = theta[2]
+        # dSigma_ij/dl_d = -2 (1 - eps) sf^2 kappa'(rho^2) (x_id - x_jd)^2 / (l_dev^2 l_d), l_dev = 1 for ARD rows
+        coef = -2.0 * (1.0 - self.COVARIANCE_SHRINKAGE) * sf * sf
+        raw = sums[:-1]
+        if ls is None:
+            gl = np.array([coef * float(np.sum(raw)) / theta[1] ** 3])
+        else:
+            gl = coef * raw / ls
+        grad = np.append(gl, 2.0 * sums[-1] / sf) + log_prior_grad(theta)
+        if not np.isfinite(value) or not np.all(np.isfinite(grad)):
+            return -500.0, np.zeros_like(grad), log_evidence, sgn, fm
+        return float(value), grad, log_evidence, sgn, fm
+
+    def optimize_theta_ard(self, maxfun=60, start=None):
+        """Evidence maximisation over one length scale per input dimension and sigma_f, sigma fixed to 1 (no reference
+        counterpart; GPy / scikit-learn's ARD fit).  L-BFGS-B over (log l_1..log l_D, log sigma_f) with evidence_grad's
+        device gradient, inside the reference's box (l_d in [0.01, 2], sigma_f in [0.1, 15]).  Starts from `start` (a
+        theta; a scalar l is broadcast to D) or the current theta.  Each evaluation's f_MAP search starts at the previous
+        evaluation's f_MAP; the first at the model's f_MAP when it has N rows, else at one prior draw from the global
+        stream.  At most `maxfun` evidence fits, every one logged in theta_search_log as (l, sigma_f, value); theta
+        becomes the best one seen, so never a worse one than the start."""
+        kern = self.kernel.__name__
+        if kern not in RADIAL_KERNELS:
+            raise ValueError(f"per-dimension length scales are defined for the radial kernels {RADIAL_KERNELS}, not {kern}")
+        if self.verbose:
+            print("Hyperparameter optimization (ARD, evidence gradient) begins...")
+        t0 = time.time()
+        if start is None:
+            if self.theta is None:
+                self.set_theta()
+            start = self.theta
+        start = _theta_list(start)
+        l0 = lengthscales(start, self.D, kern)
+        l0 = np.full(self.D, float(start[1])) if l0 is None else l0
+        D = self.D
+        (llo, lhi), (slo, shi) = THETA_BOX
+        lo = np.log(np.append(np.full(D, llo), slo))
+        hi = np.log(np.append(np.full(D, lhi), shi))
+        p0 = np.clip(np.log(np.append(l0, float(start[2]))), lo, hi)
+        if self.fMAP is not None and len(self.fMAP) == self.N:
+            f_state = [self.eng.dev(self.fMAP)]
+        else:
+            f_state = [self._draw_prior()]
+        best = {"v": -np.inf, "p": p0}
+        self.theta_search_log = []
+
+        class _Budget(Exception):
+            pass
+
+        def fg(p):
+            if len(self.theta_search_log) >= maxfun:
+                raise _Budget()
+            p = np.clip(np.asarray(p, dtype=float), lo, hi)
+            q = np.exp(p)
+            theta = [1.0, q[:D].copy(), float(q[D])]
+            try:
+                v, g, _, _, fm = self.evidence_grad(theta, f_initial=f_state[0], gtol=ARD_FIT_GTOL)
+                if v != -500.0:
+                    f_state[0] = fm
+            except NotPositiveDefinite:
+                v, g = -500.0, np.zeros(D + 1)
+            self.theta_search_log.append((q[:D].copy(), float(q[D]), float(v)))
+            if v > best["v"]:
+                best["v"], best["p"] = v, p.copy()
+            return -v, -(g * q)                   # d/dlog x = x d/dx
+
+        try:
+            scipy.optimize.minimize(fg, p0, jac=True, method="L-BFGS-B", bounds=list(zip(lo, hi)),
+                                    options=dict(maxfun=maxfun, maxiter=maxfun))
+        except _Budget:
+            pass
+        q = np.exp(best["p"])
+        self.theta = [1.0, q[:D].copy(), float(q[D])]
+        if self.verbose:
+            print("Optimization of hyperparameters took " + str(time.time() - t0) + " seconds.")
             print("The optimized theta is " + str(self.theta))
 
     # ------------------------------------------------------------------ f_MAP
@@ -672,7 +787,10 @@ class GPModel:
             else:
                 self.update_fMAP()
             if optimize_theta:
-                self.optimize_theta()
+                if self.theta_optimizer == "ard-gradient":
+                    self.optimize_theta_ard()
+                else:
+                    self.optimize_theta()
                 self.update_fMAP()
                 self.update_Sigma(self.theta)
                 self.update_Sigma_inv(self.theta)

@@ -18,6 +18,7 @@ _STRATEGY_TABLE = {
     "COORDINATE-VARMAX": ("varmax", True, False),
 }
 STRATEGIES = tuple(_STRATEGY_TABLE)
+THETA_OPTIMIZERS = ("search", "ard-gradient")
 
 _FIXED = dict(
     fMAP_optimizer="trust-exact",          # :41  (the HIP fit is a trust-region Newton as well)
@@ -31,15 +32,22 @@ class PPBO_settings:
                  verbose=True, EI_EXR_mc_samples=150, EI_EXR_BO_maxiter=20, mustar_finding_trials=3,
                  kernel="SE_kernel", skip_computations_during_initialization=True,
                  skip_xstaroptimization_during_initialization=False, alpha_grid_distribution="equispaced",
-                 fMAP_method="whitened"):
+                 fMAP_method="whitened", theta_optimizer="search"):
         """fMAP_method (not a reference option): "whitened" = L-BFGS in z = L^-1 f finished by the trust
         region (the default; O(N^2) per iteration), "trust-region" = the exact Newton trust region on f alone, which
         follows SciPy trust-exact's iteration rules (the reference's optimiser class, src/gp_model.py:382-384) -- the
-        parity mode for flows that want the reference's basin behaviour at sigma << sigma_f."""
+        parity mode for flows that want the reference's basin behaviour at sigma << sigma_f.
+        theta_optimizer (not a reference option): how update_model(optimize_theta=True) fits theta.  "search" = the
+        derivative-free 60-fit search over (l, sigma_f) of GPModel.optimize_theta (the default); "ard-gradient" =
+        GPModel.optimize_theta_ard, L-BFGS-B with the device's evidence gradient over one length scale per dimension and
+        sigma_f (radial kernels only)."""
         if fMAP_method not in ("whitened", "trust-region"):
             raise ValueError("fMAP_method must be 'whitened' or 'trust-region'")
+        if theta_optimizer not in THETA_OPTIMIZERS:
+            raise ValueError(f"theta_optimizer must be one of {THETA_OPTIMIZERS}, not {theta_optimizer!r}")
         vars(self).update(_FIXED)
         self.fMAP_method = fMAP_method
+        self.theta_optimizer = theta_optimizer
         vars(self).update(
             D=D, original_bounds=bounds, verbose=verbose, kernel=kernel,
             user_feedback_grid_size=user_feedback_grid_size,
