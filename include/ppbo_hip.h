@@ -378,6 +378,40 @@ PPBO_API int ppbo_mean_search_multi_scaled(ppbo_ctx* ctx, const ppbo_model* mode
 PPBO_API int ppbo_mean_ascent_scaled(ppbo_ctx* ctx, const ppbo_model* model, const double* d_starts, int K, int iters,
                      double tol, double* d_x, double* d_mu, int* d_iters, const double* h_scale, void* stream);
 
+/* ---- camphor-copper with one length scale per coordinate (no reference counterpart) ------------------------------------
+ * The camphor-copper kernel with l_0..l_5 (x, y, z, alpha, beta, gamma; z is the non-periodic coordinate 2) is SE with
+ * l = 1 on embedded rows e(x) in R^11:
+ *   camphor(x, x'; l, sigma_f) = SE(e(x), e(x'); 1, sigma_f),   |e_d(x) - e_d(x')|^2 = 4 sin^2(pi (x_d - x'_d)) / l_d^2,
+ * column order (c0, s0, c1, s1, z, c3, s3, c4, s4, c5, s5) with c_d = cos(2 pi x_d) / l_d, s_d = sin(2 pi x_d) / l_d and
+ * z = x_2 / l_2.  The reference's kernel is l = (l, l, l + 0.05, l, l, l).  Such a model holds its EMBEDDED rows in d_X
+ * (D = 11), kernel_id = PPBO_KERNEL_SE and theta = [sigma, 1, sigma_f]; the Gram, fit, posterior, evidence and its
+ * gradient, prediction and the line acquisition run on it unchanged.  h_l[6] are the length scales (host); every entry
+ * below rejects a non-positive or non-finite one, and a model that is not SE at D = 11, with "invalid argument".
+ * ppbo_camphor_embed: d_out[M,11] = e(d_in[M,6]) (one memory-bound pass; an output that overlaps the input is
+ *   rejected, as is M beyond one launch grid, 2^31 - 1 blocks of 256 / 6 rows).
+ * ppbo_camphor_line_points: the embedded grid d_out[B*G,11] of the B lines x_b + alpha_g xi_b (d_xi, d_x [B,6]; d_alpha
+ *   [G], or [B,G] with alpha_per_line), formed in the caller's coordinates; ppbo_line_acq takes it as d_grid[B,G,11]
+ *   (d_out must not overlap the inputs).
+ * ppbo_mean_grad_camphor: mu[M] and d mu / d x [M,6] at d_xc[M,6] in the caller's coordinates (the 11-D gradient of
+ *   ppbo_mean_grad pulled back through de/dx: 2 pi (c_d g_s - s_d g_c) for a periodic d, g_z / l_2 for z).
+ * ppbo_mean_search_multi_camphor / ppbo_mean_ascent_camphor: ppbo_mean_search_multi / ppbo_mean_ascent on such a model,
+ *   with d_Xc[N,6] = the model's design rows in the caller's coordinates.  Pool rotation, extra points (NULL with
+ *   E_rows = N: d_Xc), h_xprev, the [0,1]^6 box, sep, tol and the results are in the caller's coordinates; candidates are
+ *   screened on their embedded rows, the ascent evaluates mu and its gradient on d_Xc with the camphor form
+ *   s = sum_{d != 2} (2 / l_d^2) sin^2(pi dx_d) + dx_2^2 / (2 l_2^2). */
+PPBO_API int ppbo_camphor_embed(ppbo_ctx* ctx, const double* d_in, int64_t M, const double* h_l, double* d_out, void* stream);
+PPBO_API int ppbo_camphor_line_points(ppbo_ctx* ctx, const double* d_xi, const double* d_x, const double* d_alpha,
+                             int alpha_per_line, int B, int G, const double* h_l, double* d_out, void* stream);
+PPBO_API int ppbo_mean_grad_camphor(ppbo_ctx* ctx, const ppbo_model* model, const double* d_xc, int64_t M,
+                           const double* h_l, double* d_mu, double* d_grad, void* stream);
+PPBO_API int ppbo_mean_search_multi_camphor(ppbo_ctx* ctx, const ppbo_model* model, const double* d_pool, int64_t M,
+                           const double* h_shifts, int T, const double* d_extra, int E_rows, const double* h_xprev,
+                           int K, double sep, int iters, double tol, int screen_fp32, double* d_x, double* d_mu,
+                           const double* d_Xc, const double* h_l, void* stream);
+PPBO_API int ppbo_mean_ascent_camphor(ppbo_ctx* ctx, const ppbo_model* model, const double* d_starts, int K, int iters,
+                     double tol, double* d_x, double* d_mu, int* d_iters, const double* d_Xc, const double* h_l,
+                     void* stream);
+
 /* ---- K10: Monte-Carlo line acquisition -------------------------------------
  * replaces EI / varmax (src/acquisition.py:72-81, 170-178) for B lines of G points
  * with stored standard-normal draws d_z[S,G]: f = mu + chol(cov) z.

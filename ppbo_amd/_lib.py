@@ -83,6 +83,12 @@ SIGNATURES = {
     "ppbo_mean_search_multi_scaled": [_vp, C.POINTER(Model), _vp, _i64, C.POINTER(_d), _i, _vp, _i, C.POINTER(_d), _i, _d, _i, _d,
                                       _i, _vp, _vp, C.POINTER(_d), _vp],
     "ppbo_mean_ascent_scaled": [_vp, C.POINTER(Model), _vp, _i, _i, _d, _vp, _vp, _vp, C.POINTER(_d), _vp],
+    "ppbo_camphor_embed": [_vp, _vp, _i64, C.POINTER(_d), _vp, _vp],
+    "ppbo_camphor_line_points": [_vp, _vp, _vp, _vp, _i, _i, _i, C.POINTER(_d), _vp, _vp],
+    "ppbo_mean_grad_camphor": [_vp, C.POINTER(Model), _vp, _i64, C.POINTER(_d), _vp, _vp, _vp],
+    "ppbo_mean_search_multi_camphor": [_vp, C.POINTER(Model), _vp, _i64, C.POINTER(_d), _i, _vp, _i, C.POINTER(_d), _i, _d, _i,
+                                       _d, _i, _vp, _vp, _vp, C.POINTER(_d), _vp],
+    "ppbo_mean_ascent_camphor": [_vp, C.POINTER(Model), _vp, _i, _i, _d, _vp, _vp, _vp, _vp, C.POINTER(_d), _vp],
     "ppbo_line_acq": [_vp, C.POINTER(Model), _vp, _i, _i, _d, _vp, _i, _d, _d, _vp, _vp, _vp],
     "ppbo_line_acq_xi": [_vp, C.POINTER(Model), _vp, _vp, _vp, _i, _i, _i, _d, _vp, _i, _d, _d, _vp, _vp, _vp],
     "ppbo_randn": [_vp, C.c_uint64, _vp, _i64, _vp],

@@ -11,6 +11,7 @@
 // registers, accumulate mu and D gradient components, then a shuffle + LDS reduction.  M is small here
 // (a few hundred ascent iterates), so the work per launch is M * N * D * ~6 flops -- microseconds.
 #include "common.h"
+#include "camphor.h"
 #include "rffmath.h"
 
 namespace {
@@ -423,6 +424,49 @@ struct ScaledMeanEval {
   }
 };
 
+// camphor-copper with one length scale per coordinate (ppbo_mean_ascent_camphor): mu and its gradient in the caller's
+// coordinates over the design's caller-coordinate rows (X transposed, [6][N]) -- the camphor form of eval_mean_grad with
+// a coefficient per coordinate, c.k[d] = 2 / l_d^2 (periodic) and 1 / (2 l_2^2) (z); the same reduction records.
+template <int DP, int NT>
+struct CamphorMeanEval {
+  static_assert(DP >= CAMPHOR_D, "six coordinates");
+  const double* X; int N; double sf2; CamphorCoef c; const double* alpha;
+  __device__ __forceinline__ void operator()(const double* sx, double (*red)[DP + 1]) const {
+    double xc[CAMPHOR_D], g[DP];
+#pragma unroll
+    for (int d = 0; d < DP; ++d) g[d] = 0.0;
+#pragma unroll
+    for (int d = 0; d < CAMPHOR_D; ++d) xc[d] = sx[d];
+    double m = 0.0;
+    for (int i = threadIdx.x; i < N; i += NT) {
+      double dx[CAMPHOR_D], s = 0.0;
+#pragma unroll
+      for (int d = 0; d < CAMPHOR_D; ++d) {
+        dx[d] = xc[d] - X[(size_t)d * N + i];
+        if (d == 2) s += c.k[2] * dx[d] * dx[d];
+        else { const double sn = sinpi(fabs(dx[d])); s += c.k[d] * sn * sn; }
+      }
+      const double w = alpha[i] * (sf2 * exp_nonpos(-s));
+      m += w;
+#pragma unroll
+      for (int d = 0; d < CAMPHOR_D; ++d) {
+        if (d == 2) g[d] -= 2.0 * c.k[2] * dx[d] * w;
+        else g[d] -= c.k[d] * 3.14159265358979323846 * sinpi(2.0 * dx[d]) * w;
+      }
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    m = row16_sum_dpp(m);
+#pragma unroll
+    for (int d = 0; d < DP; ++d) g[d] = row16_sum_dpp(g[d]);
+    if ((lane & 15) == 0) {
+      double* r = red[4 * wave + (lane >> 4)];
+      r[DP] = m;
+#pragma unroll
+      for (int d = 0; d < DP; ++d) r[d] = g[d];
+    }
+  }
+};
+
 // one posterior sample of the utility in weight space (random_fourier_sampler.py:45-53,166):
 //   f(x) = a sum_f omega_f cos(w_f.x + b_f),   grad f = -a sum_f omega_f sin(w_f.x + b_f) w_f,   a = sqrt(2 sf^2 / F)
 template <int DP, int NT>
@@ -569,11 +613,12 @@ __global__ __launch_bounds__(256) void transpose_rows_kernel(const double* __res
   for (int d = 0; d < D; ++d) out[(size_t)d * R + r] = in[(size_t)r * D + d];
 }
 
-// d_scale (ARD, radial kernels only): D values s_d on the device; the ascent then runs in the caller's coordinates
+// d_scale (ARD, radial kernels only): D values s_d on the device; the ascent then runs in the caller's coordinates.
+// cam (camphor-copper only): per-coordinate coefficients; m is then the caller-coordinate view of an embedded model
 template <int KID>
 int launch_mean_ascent(ppbo_ctx* ctx, const ppbo_model* m, const KernParams& p, const double* starts, const int* count, int K,
                        int iters, double tol, double* x_out, double* mu_out, int* it_out, hipStream_t s, int per_trial = 0,
-                       const double* d_scale = nullptr) {
+                       const double* d_scale = nullptr, const CamphorCoef* cam = nullptr) {
   double* Xt = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_TRANSPOSE, (size_t)m->N * m->D * sizeof(double));
   if (!Xt) return (int)hipErrorOutOfMemory;
   transpose_rows_kernel<<<(m->N + 255) / 256, 256, 0, s>>>(m->d_X, m->N, m->D, Xt);
@@ -586,6 +631,13 @@ int launch_mean_ascent(ppbo_ctx* ctx, const ppbo_model* m, const KernParams& p, 
       if (d_scale) {                                                                                                  \
         ScaledMeanEval<KID, DP, NT> sev{ev, d_scale};                                                                 \
         bb_ascent_kernel<DP, ScaledMeanEval<KID, DP, NT>, NT><<<K, NT, 0, s>>>(sev, m->D, starts, count, iters, tol, x_out, mu_out, it_out, per_trial); \
+        break;                                                                                                        \
+      }                                                                                                               \
+    }                                                                                                                 \
+    if constexpr (KID == PPBO_KERNEL_CAMPHOR && DP == 8) {                                                            \
+      if (cam) {                                                                                                      \
+        CamphorMeanEval<DP, NT> cev{Xt, m->N, p.sf2, *cam, m->d_alpha};                                               \
+        bb_ascent_kernel<DP, CamphorMeanEval<DP, NT>, NT><<<K, NT, 0, s>>>(cev, m->D, starts, count, iters, tol, x_out, mu_out, it_out, per_trial); \
         break;                                                                                                        \
       }                                                                                                               \
     }                                                                                                                 \
@@ -680,7 +732,8 @@ extern "C" int ppbo_shift_points(ppbo_ctx* ctx, const double* d_in, int64_t M, i
   } while (0)
 
 static int mean_ascent_impl(ppbo_ctx* ctx, const ppbo_model* m, const double* d_starts, int K, int iters, double tol,
-                            double* d_x, double* d_mu, int* d_iters, const double* h_scale, void* stream) {
+                            double* d_x, double* d_mu, int* d_iters, const double* h_scale, void* stream,
+                            const CamphorCoef* cam = nullptr) {
   PPBO_ENTER(ctx);
   PPBO_REQUIRE(ctx, m != nullptr && m->d_X && m->d_alpha, "model X/alpha");
   PPBO_REQUIRE(ctx, m->N > 0 && m->D > 0 && m->D <= 64, "model sizes (D<=64)");
@@ -699,7 +752,7 @@ static int mean_ascent_impl(ppbo_ctx* ctx, const ppbo_model* m, const double* d_
   switch (m->kernel_id) {
     case PPBO_KERNEL_SE: rc = launch_mean_ascent<PPBO_KERNEL_SE>(ctx, m, p, d_starts, nullptr, K, iters, tol, d_x, d_mu, d_iters, s, 0, d_scale); break;
     case PPBO_KERNEL_RQ: rc = launch_mean_ascent<PPBO_KERNEL_RQ>(ctx, m, p, d_starts, nullptr, K, iters, tol, d_x, d_mu, d_iters, s, 0, d_scale); break;
-    case PPBO_KERNEL_CAMPHOR: rc = launch_mean_ascent<PPBO_KERNEL_CAMPHOR>(ctx, m, p, d_starts, nullptr, K, iters, tol, d_x, d_mu, d_iters, s); break;
+    case PPBO_KERNEL_CAMPHOR: rc = launch_mean_ascent<PPBO_KERNEL_CAMPHOR>(ctx, m, p, d_starts, nullptr, K, iters, tol, d_x, d_mu, d_iters, s, 0, nullptr, cam); break;
     case PPBO_KERNEL_MATERN52: rc = launch_mean_ascent<PPBO_KERNEL_MATERN52>(ctx, m, p, d_starts, nullptr, K, iters, tol, d_x, d_mu, d_iters, s, 0, d_scale); break;
     case PPBO_KERNEL_MATERN32: rc = launch_mean_ascent<PPBO_KERNEL_MATERN32>(ctx, m, p, d_starts, nullptr, K, iters, tol, d_x, d_mu, d_iters, s, 0, d_scale); break;
     default: return ppbo_set_error(ctx, -1, "invalid argument: kernel_id");
@@ -719,6 +772,33 @@ extern "C" int ppbo_mean_ascent_scaled(ppbo_ctx* ctx, const ppbo_model* m, const
                                        void* stream) {
   if (!h_scale) { PPBO_ENTER(ctx); return ppbo_set_error(ctx, -1, "invalid argument: h_scale is NULL"); }
   return mean_ascent_impl(ctx, m, d_starts, K, iters, tol, d_x, d_mu, d_iters, h_scale, stream);
+}
+
+// the caller-coordinate view of a camphor model (SE on embedded rows): kernel camphor at D = 6 over d_Xc, the same
+// alpha and theta; its KernParams carry sf2 only, the coefficients travel in cc
+static int camphor_view(ppbo_ctx* ctx, const ppbo_model* m, const double* d_Xc, const double* h_l, ppbo_model& cm,
+                        CamphorCoef& cc) {
+  PPBO_REQUIRE_CAMPHOR_MODEL(ctx, m);
+  PPBO_REQUIRE_CAMPHOR_L(ctx, h_l);
+  PPBO_REQUIRE(ctx, d_Xc != nullptr, "d_Xc (the design rows in the caller's coordinates)");
+  cm = *m;
+  cm.kernel_id = PPBO_KERNEL_CAMPHOR;
+  cm.D = CAMPHOR_D;
+  cm.d_X = d_Xc;
+  cm.d_G = nullptr;
+  cm.d_Gt = nullptr;
+  cc = camphor_coef(h_l);
+  return 0;
+}
+
+extern "C" int ppbo_mean_ascent_camphor(ppbo_ctx* ctx, const ppbo_model* m, const double* d_starts, int K, int iters,
+                                        double tol, double* d_x, double* d_mu, int* d_iters, const double* d_Xc,
+                                        const double* h_l, void* stream) {
+  PPBO_ENTER(ctx);
+  ppbo_model cm;
+  CamphorCoef cc;
+  if (int rc = camphor_view(ctx, m, d_Xc, h_l, cm, cc)) return rc;
+  return mean_ascent_impl(ctx, &cm, d_starts, K, iters, tol, d_x, d_mu, d_iters, nullptr, stream, &cc);
 }
 
 extern "C" int ppbo_scale_points(ppbo_ctx* ctx, const double* d_in, int64_t M, int D, const double* h_scale,
@@ -817,7 +897,9 @@ void launch_screen(const ppbo_model* m, const KernParams& p, const TrialCands& t
 static int mean_search_multi_impl(ppbo_ctx* ctx, const ppbo_model* m, const double* d_pool, int64_t M,
                                   const double* h_shifts, int T, const double* d_extra, int E_rows,
                                   const double* h_xprev, int K, double sep, int iters, double tol, int screen_fp32,
-                                  double* d_x, double* d_mu, const double* h_scale, void* stream) {
+                                  double* d_x, double* d_mu, const double* h_scale, void* stream,
+                                  const ppbo_model* emb = nullptr, const double* h_l = nullptr,
+                                  const CamphorCoef* cam = nullptr) {
   PPBO_ENTER(ctx);
   PPBO_REQUIRE(ctx, m != nullptr && m->d_X && m->d_alpha, "model X/alpha");
   PPBO_REQUIRE(ctx, m->N > 0 && m->D > 0 && m->D <= 64, "model sizes (D<=64)");
@@ -878,7 +960,7 @@ static int mean_search_multi_impl(ppbo_ctx* ctx, const ppbo_model* m, const doub
   tc.pool = d_pool; tc.M = M; tc.shifts = shifts; tc.extra = d_extra; tc.xprev = h_xprev ? xprev : nullptr;
   tc.E_rows = E_rows; tc.E = E; tc.D = D;
   const KernParams p = make_kern_params(m->kernel_id, m->theta);
-  if (screen_fp32 && !d_scale) {
+  if (screen_fp32 && !d_scale && !emb) {
     // the trials in batches of <= 8 (bounds the partial sums: 8 x n_split x Mt doubles)
     const int blocks_x = (int)((Mt + SCR_T * SCR_CPT - 1) / (SCR_T * SCR_CPT));
     for (int t0 = 0; t0 < T; t0 += 8) {
@@ -906,24 +988,37 @@ static int mean_search_multi_impl(ppbo_ctx* ctx, const ppbo_model* m, const doub
     // what the one-trial entry does with the rows ppbo_shift_points leaves.  ARD: the rows are scaled to s (.) x first,
     // and the fp32 screening takes them as the extra points of a one-trial launch of mean_screen_kernel (which reads
     // extra points as they are), so that the kernel itself needs no scaled form
+    // camphor (emb: the embedded model, m its caller-coordinate view): the candidates are embedded and screened on
+    // the embedded model, as SE
     double* rows = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_SEARCH_ROWS, (size_t)Mt * D * sizeof(double));
     if (!rows) return (int)hipErrorOutOfMemory;
-    ppbo_model mean_only = *m;
+    double* erows = rows;
+    int De = D;
+    if (emb) {
+      erows = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_CAMPHOR_ROWS, (size_t)Mt * CAMPHOR_E * sizeof(double));
+      if (!erows) return (int)hipErrorOutOfMemory;
+      De = CAMPHOR_E;
+    }
+    const ppbo_model* sm = emb ? emb : m;
+    const KernParams sp = emb ? make_kern_params(PPBO_KERNEL_SE, emb->theta) : p;
+    ppbo_model mean_only = *sm;
     mean_only.d_G = nullptr;
     for (int t = 0; t < T; ++t) {
       const long long nt = M + (t == 0 ? E : 0);
       trial_rows_kernel<<<(unsigned)((nt * D + 255) / 256), 256, 0, s>>>(tc, t, rows);
       if (d_scale) scale_points_kernel<<<(unsigned)((nt * D + 255) / 256), 256, 0, s>>>(rows, nt * D, D, d_scale, rows);
       PPBO_LAUNCH_CHECK(ctx);
+      if (emb)
+        if (int rc = ppbo_camphor_embed(ctx, rows, nt, h_l, erows, stream)) return rc;
       if (screen_fp32) {
         TrialCands tr;
-        tr.pool = rows; tr.M = 0; tr.shifts = shifts; tr.extra = rows; tr.E_rows = (int)nt; tr.E = (int)nt; tr.D = D;
+        tr.pool = erows; tr.M = 0; tr.shifts = shifts; tr.extra = erows; tr.E_rows = (int)nt; tr.E = (int)nt; tr.D = De;
         int n_split, rows_per_split;
         screen_split((int)((nt + SCR_T * SCR_CPT - 1) / (SCR_T * SCR_CPT)), 1, m->N, n_split, rows_per_split);
         double* part = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_PART, (size_t)n_split * nt * sizeof(double));
         if (!part) return (int)hipErrorOutOfMemory;
-        switch (m->kernel_id) {   // (camphor-copper has no ARD form: refused above)
-          case PPBO_KERNEL_SE: launch_screen<PPBO_KERNEL_SE>(m, p, tr, 1, rows_per_split, n_split, part, 0, s); break;
+        switch (sm->kernel_id) {   // (camphor-copper has no ARD form: refused above; the camphor model screens as SE)
+          case PPBO_KERNEL_SE: launch_screen<PPBO_KERNEL_SE>(sm, sp, tr, 1, rows_per_split, n_split, part, 0, s); break;
           case PPBO_KERNEL_RQ: launch_screen<PPBO_KERNEL_RQ>(m, p, tr, 1, rows_per_split, n_split, part, 0, s); break;
           case PPBO_KERNEL_MATERN52: launch_screen<PPBO_KERNEL_MATERN52>(m, p, tr, 1, rows_per_split, n_split, part, 0, s); break;
           case PPBO_KERNEL_MATERN32: launch_screen<PPBO_KERNEL_MATERN32>(m, p, tr, 1, rows_per_split, n_split, part, 0, s); break;
@@ -931,7 +1026,7 @@ static int mean_search_multi_impl(ppbo_ctx* ctx, const ppbo_model* m, const doub
         }
         screen_sum_kernel<<<dim3((unsigned)((nt + 255) / 256), 1), 256, 0, s>>>(part, n_split, nt, 0, 0, mu + (size_t)t * Mt);
         PPBO_LAUNCH_CHECK(ctx);
-      } else if (int rc = ppbo_predict(ctx, &mean_only, rows, nt, PPBO_SCORE_MEAN, 0.0, mu + (size_t)t * Mt, nullptr, nullptr,
+      } else if (int rc = ppbo_predict(ctx, &mean_only, erows, nt, PPBO_SCORE_MEAN, 0.0, mu + (size_t)t * Mt, nullptr, nullptr,
                                        nullptr, nullptr, stream)) {
         return rc;
       }
@@ -951,7 +1046,7 @@ static int mean_search_multi_impl(ppbo_ctx* ctx, const ppbo_model* m, const doub
   switch (m->kernel_id) {
     case PPBO_KERNEL_SE: if (int rc = launch_mean_ascent<PPBO_KERNEL_SE>(ctx, m, p, starts, counts, T * K, iters, tol, d_x, d_mu, nullptr, s, K, d_scale)) return rc; break;
     case PPBO_KERNEL_RQ: if (int rc = launch_mean_ascent<PPBO_KERNEL_RQ>(ctx, m, p, starts, counts, T * K, iters, tol, d_x, d_mu, nullptr, s, K, d_scale)) return rc; break;
-    case PPBO_KERNEL_CAMPHOR: if (int rc = launch_mean_ascent<PPBO_KERNEL_CAMPHOR>(ctx, m, p, starts, counts, T * K, iters, tol, d_x, d_mu, nullptr, s, K)) return rc; break;
+    case PPBO_KERNEL_CAMPHOR: if (int rc = launch_mean_ascent<PPBO_KERNEL_CAMPHOR>(ctx, m, p, starts, counts, T * K, iters, tol, d_x, d_mu, nullptr, s, K, nullptr, cam)) return rc; break;
     case PPBO_KERNEL_MATERN52: if (int rc = launch_mean_ascent<PPBO_KERNEL_MATERN52>(ctx, m, p, starts, counts, T * K, iters, tol, d_x, d_mu, nullptr, s, K, d_scale)) return rc; break;
     case PPBO_KERNEL_MATERN32: if (int rc = launch_mean_ascent<PPBO_KERNEL_MATERN32>(ctx, m, p, starts, counts, T * K, iters, tol, d_x, d_mu, nullptr, s, K, d_scale)) return rc; break;
     default: return ppbo_set_error(ctx, -1, "invalid argument: kernel_id");
@@ -976,6 +1071,19 @@ extern "C" int ppbo_mean_search_multi_scaled(ppbo_ctx* ctx, const ppbo_model* m,
   if (!h_scale) { PPBO_ENTER(ctx); return ppbo_set_error(ctx, -1, "invalid argument: h_scale is NULL"); }
   return mean_search_multi_impl(ctx, m, d_pool, M, h_shifts, T, d_extra, E_rows, h_xprev, K, sep, iters, tol, screen_fp32,
                                 d_x, d_mu, h_scale, stream);
+}
+
+extern "C" int ppbo_mean_search_multi_camphor(ppbo_ctx* ctx, const ppbo_model* m, const double* d_pool, int64_t M,
+                                              const double* h_shifts, int T, const double* d_extra, int E_rows,
+                                              const double* h_xprev, int K, double sep, int iters, double tol,
+                                              int screen_fp32, double* d_x, double* d_mu, const double* d_Xc,
+                                              const double* h_l, void* stream) {
+  PPBO_ENTER(ctx);
+  ppbo_model cm;
+  CamphorCoef cc;
+  if (int rc = camphor_view(ctx, m, d_Xc, h_l, cm, cc)) return rc;
+  return mean_search_multi_impl(ctx, &cm, d_pool, M, h_shifts, T, d_extra, E_rows, h_xprev, K, sep, iters, tol, screen_fp32,
+                                d_x, d_mu, nullptr, stream, m, h_l, &cc);
 }
 
 extern "C" int ppbo_rff_search(ppbo_ctx* ctx, const double* d_cand, int64_t M, int D, const double* d_W, int F,

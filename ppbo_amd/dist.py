@@ -70,6 +70,8 @@ class ShardedSearch:
         if getattr(post, "scale", None) is not None:
             # the shards would have to be scaled on every rank; no multi-GPU run of that exists to test it
             raise ValueError("ShardedSearch does not take a posterior with per-dimension length scales")
+        if getattr(post, "camphor", None) is not None:
+            raise ValueError("ShardedSearch does not take a camphor_copper_ard_kernel posterior")
         self.eng, self.post, self.Xc = engine, post, engine.dev(Xc_shard)
         self.offset, self.score, self.mustar, self.group = int(shard_offset), score, float(mustar), group
         self.rank, self.world = rank_world(group)

@@ -18,12 +18,37 @@ SHRINKAGE = 1e-6  # COVARIANCE_SHRINKAGE of the reference (gp_model.py:26)
 # every device path runs on them unchanged with theta = [sigma, 1, sigma_f]
 RADIAL_KERNELS = ("SE_kernel", "RQ_kernel", "Matern52_kernel", "Matern32_kernel")
 
+# camphor-copper with one length scale per coordinate (no reference counterpart): with e(x) in R^11 the embedding of
+# include/ppbo_hip.h, camphor(x, x'; l_0..l_5) = SE(e(x), e(x'); 1), so such a posterior stores its rows embedded and the
+# device sees SE with theta = [sigma, 1, sigma_f].  A scalar l is the reference's profile (l, l, l + 0.05, l, l, l).
+CAMPHOR_ARD = "camphor_copper_ard_kernel"
+CAMPHOR_PROFILE = np.array([0.0, 0.0, 0.05, 0.0, 0.0, 0.0])
+# the kernels whose length scales the evidence gradient and optimize_theta_ard fit one by one
+ARD_KERNELS = RADIAL_KERNELS + (CAMPHOR_ARD,)
+
+
+def camphor_lengthscales(theta, D):
+    """The six length scales of camphor_copper_ard_kernel: theta[1] a length-6 vector, or a scalar l standing for the
+    profile (l, l, l + 0.05, l, l, l).  Raises ValueError unless D == 6 and every entry is positive and finite."""
+    if D != 6:
+        raise ValueError(f"{CAMPHOR_ARD} needs D == 6, not {D}")
+    l = theta[1]
+    v = float(l) + CAMPHOR_PROFILE if np.ndim(l) == 0 else np.asarray(l, dtype=np.float64).copy()
+    if v.ndim != 1 or v.size != 6:
+        raise ValueError(f"theta[1] has shape {v.shape}: a scalar or one length scale per coordinate (6) is required")
+    if not (np.all(np.isfinite(v)) and np.all(v > 0)):
+        raise ValueError("theta[1]: every camphor length scale must be positive and finite")
+    return v
+
 
 def lengthscales(theta, D, kernel):
     """The one check of theta[1]: None for a scalar length scale (today's path, left exactly as it is), else the
     length-D float64 vector of per-dimension length scales.  A vector is never collapsed to a scalar, even when its
     entries are equal.  Raises ValueError for a vector with the camphor-copper kernel, of the wrong length, or with an
-    entry that is not positive and finite."""
+    entry that is not positive and finite.  camphor_copper_ard_kernel: always the six length scales
+    (camphor_lengthscales; a scalar is expanded to the reference's profile)."""
+    if kernel == CAMPHOR_ARD:
+        return camphor_lengthscales(theta, D)
     l = theta[1]
     if np.ndim(l) == 0:
         return None
@@ -66,6 +91,13 @@ class Posterior:
     P: torch.Tensor | None = None  # posterior covariance (optional)
     Gt: torch.Tensor | None = None  # transpose of G in the one-launch scoring kernel's layout (formed on first use)
     scale: np.ndarray | None = None  # ARD: s_d = 1 / l_d (None: a scalar length scale)
+    camphor: np.ndarray | None = None  # camphor_copper_ard_kernel: l_0..l_5; X then holds the embedded rows [N, 11]
+    Xc: torch.Tensor | None = None     # ... and this the caller's rows [N, 6] (mu_star searches in their coordinates)
+
+    @property
+    def embedded(self):
+        """The device works on rows the caller's points must be mapped to (ARD scaling or the camphor embedding)."""
+        return self.scale is not None or self.camphor is not None
 
 
 def _ptr(t):
@@ -142,9 +174,27 @@ class Engine:
         self._check(rc, "ppbo_scale_points")
         return out
 
+    def camphor_embed(self, X, ls):
+        """e(X) [M, 11] of the caller's rows X [M, 6] for the camphor length scales ls (ppbo_camphor_embed)."""
+        X = self.dev(X)
+        if X.dim() != 2 or X.shape[1] != 6:
+            raise ValueError(f"camphor_embed: points of shape {tuple(X.shape)}, [M, 6] required")
+        l = np.ascontiguousarray(ls, dtype=np.float64)
+        out = self.empty(X.shape[0], 11)
+        rc = self.lib.ppbo_camphor_embed(self.ctx, _ptr(X), X.shape[0], self._dptr(l), _ptr(out), self._stream())
+        self._check(rc, "ppbo_camphor_embed")
+        return out
+
+    @staticmethod
+    def _kid(kernel):
+        """The device's kernel id: camphor_copper_ard_kernel is SE on embedded rows."""
+        return KERNEL_IDS["SE_kernel" if kernel == CAMPHOR_ARD else kernel]
+
     def _ard(self, X, theta, kernel):
         """(rows the device works on, theta it sees, scale or None) for the caller's rows X and theta."""
         X = self.dev(X)
+        if kernel == CAMPHOR_ARD:
+            return self.camphor_embed(X, camphor_lengthscales(theta, X.shape[1])), (float(theta[0]), 1.0, float(theta[2])), None
         ls = lengthscales(theta, X.shape[1], kernel)
         if ls is None:
             return X, theta, None
@@ -154,23 +204,35 @@ class Engine:
     def _points(self, post: Posterior, Xc):
         """Points in the caller's coordinates -> the rows the posterior's device state is in."""
         Xc = self.dev(Xc)
-        if post.scale is None:
+        if not post.embedded:
             return Xc
-        if Xc.dim() != 2 or Xc.shape[1] != post.X.shape[1]:
-            raise ValueError(f"points of shape {tuple(Xc.shape)} for a model of {post.X.shape[1]} dimensions")
+        D = post.X.shape[1] if post.camphor is None else 6
+        if Xc.dim() != 2 or Xc.shape[1] != D:
+            raise ValueError(f"points of shape {tuple(Xc.shape)} for a model of {D} dimensions")
+        if post.camphor is not None:
+            return self.camphor_embed(Xc, post.camphor)
         return self.scale_points(Xc, post.scale)
+
+    def _camphor_fields(self, X, theta, kernel):
+        """The Posterior fields of a camphor_copper_ard_kernel model (its six length scales and a copy of the caller's
+        rows), else {}."""
+        if kernel != CAMPHOR_ARD:
+            return {}
+        X = self.dev(X)
+        return dict(camphor=camphor_lengthscales(theta, X.shape[1]), Xc=X.clone())
 
     def mean_posterior(self, X, theta, kernel, m, alpha):
         """A Posterior usable for the mean only (alpha given, no variance state) at the caller's rows X."""
         Xd, _, scale = self._ard(X, theta, kernel)
-        return Posterior(kernel, theta_key(theta), m, Xd, alpha, None, None, None, scale=scale)
+        return Posterior(kernel, theta_key(theta), m, Xd, alpha, None, None, None, scale=scale,
+                         **self._camphor_fields(X, theta, kernel))
 
     def _model(self, post: Posterior, with_var=True, kstar_fp32=False):
         N, D = post.X.shape
         md = _lib.Model()
-        md.kernel_id = KERNEL_IDS[post.kernel]
+        md.kernel_id = self._kid(post.kernel)
         md.N, md.D, md.m = N, D, post.m
-        md.theta = self._theta(post.theta if post.scale is None else (post.theta[0], 1.0, post.theta[2]))
+        md.theta = self._theta(post.theta if not post.embedded else (post.theta[0], 1.0, post.theta[2]))
         md.d_X = post.X.data_ptr()
         md.d_alpha = post.alpha.data_ptr()
         md.d_lam_diag = post.lam_diag.data_ptr() if post.lam_diag is not None else 0
@@ -248,7 +310,10 @@ class Engine:
 
     def search_sharded(self, post, Xc, score=SCORE_MEAN, mustar=0.0, index_offset=0, kstar_fp32=False):
         """One whole sharded search step in ONE library call (ppbo_search_sharded): score this rank's rows, RCCL
-        all-gather of the 16-byte records (when dist_init has run on this ctx), reduction, one read-back."""
+        all-gather of the 16-byte records (when dist_init has run on this ctx), reduction, one read-back.  Not for a
+        camphor_copper_ard_kernel posterior."""
+        if post.camphor is not None:
+            raise ValueError("search_sharded does not take a camphor_copper_ard_kernel posterior")
         Xc = self._points(post, Xc)
         md = self._model(post, score != SCORE_MEAN, kstar_fp32)
         bv, bi = C.c_double(0.0), C.c_int64(-1)
@@ -276,7 +341,7 @@ class Engine:
         X, theta, _ = self._ard(X, theta, kernel)
         N, D = X.shape
         S = self.empty(N, N) if out is None else out
-        rc = self.lib.ppbo_gram(self.ctx, KERNEL_IDS[kernel], _ptr(X), N, D, self._theta(theta), shrink, _ptr(S),
+        rc = self.lib.ppbo_gram(self.ctx, self._kid(kernel), _ptr(X), N, D, self._theta(theta), shrink, _ptr(S),
                                 self._stream())
         self._check(rc, "ppbo_gram")
         return S
@@ -289,12 +354,15 @@ class Engine:
 
     def cross_cov(self, X1, X2, theta, kernel="SE_kernel"):
         X1, th, scale = self._ard(X1, theta, kernel)
-        X2 = self.dev(X2) if scale is None else self.scale_points(X2, scale)
+        if kernel == CAMPHOR_ARD:
+            X2 = self._ard(X2, theta, kernel)[0]
+        else:
+            X2 = self.dev(X2) if scale is None else self.scale_points(X2, scale)
         theta = th
         n1, D = X1.shape
         n2 = X2.shape[0]
         K = self.empty(n1, n2)
-        rc = self.lib.ppbo_cross_cov(self.ctx, KERNEL_IDS[kernel], _ptr(X1), n1, _ptr(X2), n2, D, self._theta(theta),
+        rc = self.lib.ppbo_cross_cov(self.ctx, self._kid(kernel), _ptr(X1), n1, _ptr(X2), n2, D, self._theta(theta),
                                      _ptr(K), n2, self._stream())
         self._check(rc, "ppbo_cross_cov")
         return K
@@ -398,16 +466,17 @@ class Engine:
         """ppbo_evidence_grad at one evidence's state (X and theta in the caller's coordinates; Sigma, Sigma^-1, f_MAP and
         the star-form Lambda(f_MAP) as the evidence formed them).  Returns (s_U, log|det A|, sums[D + 1], info) with the
         sign and log-determinant bit-identical to laplace_logdet; sums as include/ppbo_hip.h defines them, for the rows
-        the device works on (scaled by 1 / l for per-dimension length scales).  Raises ValueError for a kernel that is
-        not radial and NotPositiveDefinite (info = 2) when Sigma^-1 - Lambda is not positive definite."""
-        if kernel not in RADIAL_KERNELS:
-            raise ValueError(f"the evidence gradient is defined for the radial kernels {RADIAL_KERNELS}, not {kernel}")
+        the device works on (scaled by 1 / l for per-dimension length scales; camphor_copper_ard_kernel: the 11 embedded
+        columns).  Raises ValueError for a kernel outside ARD_KERNELS and NotPositiveDefinite (info = 2) when
+        Sigma^-1 - Lambda is not positive definite."""
+        if kernel not in ARD_KERNELS:
+            raise ValueError(f"the evidence gradient is defined for the kernels {ARD_KERNELS}, not {kernel}")
         Xd, th, _ = self._ard(X, theta, kernel)
         N, D = Xd.shape
         f = self.dev(fMAP).reshape(-1)
         sg, ld, info = C.c_double(0.0), C.c_double(0.0), C.c_int(0)
         sums = np.zeros(D + 1)
-        rc = self.lib.ppbo_evidence_grad(self.ctx, KERNEL_IDS[kernel], _ptr(Xd), N, D, self._theta(th), float(shrink), int(m),
+        rc = self.lib.ppbo_evidence_grad(self.ctx, self._kid(kernel), _ptr(Xd), N, D, self._theta(th), float(shrink), int(m),
                                          _ptr(Sigma), _ptr(Sigma_inv), _ptr(f), _ptr(lam_diag), _ptr(lam_off), C.byref(sg),
                                          C.byref(ld), self._dptr(sums), C.byref(info), self._stream())
         self._check(rc, "ppbo_evidence_grad", info.value)
@@ -496,6 +565,7 @@ class Engine:
         Returns dict(Sigma, Sigma_inv, L, Linv, fMAP, post, stats, info); info = 2 (with post = None) when
         Sigma^-1 - Lambda_MAP is not positive definite (raises NotPositiveDefinite when Sigma itself is not)."""
         key = theta_key(theta)
+        cam = self._camphor_fields(X, theta, kernel)
         X, theta, scale = self._ard(X, theta, kernel)
         N, D = X.shape
         f0 = self.dev(f_init).reshape(-1)
@@ -512,14 +582,14 @@ class Engine:
         opts = _lib.FitOpts(float(gtol), int(maxiter), int(verbose), 0.0, int(lbfgs_max_evals), 0, int(bool(start_is_whitened)))
         st = _lib.FitStats()
         info = C.c_int(0)
-        rc = self.lib.ppbo_gp_fit(self.ctx, KERNEL_IDS[kernel], _ptr(X), N, D, self._theta(theta), float(shrink), int(m),
+        rc = self.lib.ppbo_gp_fit(self.ctx, self._kid(kernel), _ptr(X), N, D, self._theta(theta), float(shrink), int(m),
                                   _ptr(f0), C.byref(opts), _ptr(Sigma), _ptr(Sinv), _ptr(L), _ptr(Linv), _ptr(fmap),
                                   _ptr(alpha), _ptr(ld), _ptr(lo), _ptr(G), C.byref(st), C.byref(info), self._stream())
         if rc == PPBO_ERR_NOT_PD and info.value == 2:
             post = None
         else:
             self._check(rc, "ppbo_gp_fit", info.value)
-            post = Posterior(kernel, key, m, X, alpha, ld, lo, G, None, scale=scale) if want_posterior else None
+            post = Posterior(kernel, key, m, X, alpha, ld, lo, G, None, scale=scale, **cam) if want_posterior else None
         stats = dict(iterations=st.iterations, n_cholesky=st.n_cholesky, converged=bool(st.converged), T=st.T,
                      gradnorm=st.gradnorm, lbfgs_iterations=st.lbfgs_iterations, lbfgs_evals=st.lbfgs_evals,
                      lbfgs_status=st.lbfgs_status)
@@ -527,6 +597,7 @@ class Engine:
 
     def posterior(self, X, theta, kernel, Sigma_inv, fMAP, m, want_P=False) -> Posterior:
         key = theta_key(theta)
+        cam = self._camphor_fields(X, theta, kernel)
         X, _, scale = self._ard(X, theta, kernel)
         f = self.dev(fMAP).reshape(-1)
         N = f.numel()
@@ -537,7 +608,7 @@ class Engine:
         rc = self.lib.ppbo_posterior(self.ctx, _ptr(Sigma_inv), _ptr(f), N, m, float(theta[0]), _ptr(alpha), _ptr(ld),
                                      _ptr(lo), _ptr(G), _ptr(P), C.byref(info), self._stream())
         self._check(rc, "ppbo_posterior", info.value)
-        return Posterior(kernel, key, m, X, alpha, ld, lo, G, P, scale=scale)
+        return Posterior(kernel, key, m, X, alpha, ld, lo, G, P, scale=scale, **cam)
 
     # ---- prediction ---------------------------------------------------------------
     def predict(self, post: Posterior, Xc, score=SCORE_MEAN, mustar=0.0, want_mu=True, want_var=True,
@@ -568,7 +639,20 @@ class Engine:
 
     def mean_grad(self, post: Posterior, Xc):
         """mu[M] and d mu / d x [M,D] at the rows of Xc (ppbo_mean_grad).  ARD: the gradient is taken back to the caller's
-        coordinates, d mu / d x_d = s_d d mu / d x~_d."""
+        coordinates, d mu / d x_d = s_d d mu / d x~_d; camphor_copper_ard_kernel: through the embedding's Jacobian
+        (ppbo_mean_grad_camphor)."""
+        if post.camphor is not None:
+            Xc = self.dev(Xc)
+            if Xc.dim() != 2 or Xc.shape[1] != 6:
+                raise ValueError(f"points of shape {tuple(Xc.shape)} for a model of 6 dimensions")
+            M = Xc.shape[0]
+            md = self._model(post, False)
+            mu, grad = self.empty(M), self.empty(M, 6)
+            l = np.ascontiguousarray(post.camphor, dtype=np.float64)
+            rc = self.lib.ppbo_mean_grad_camphor(self.ctx, C.byref(md), _ptr(Xc), M, self._dptr(l), _ptr(mu), _ptr(grad),
+                                                 self._stream())
+            self._check(rc, "ppbo_mean_grad_camphor")
+            return mu, grad
         Xc = self._points(post, Xc)
         M, D = Xc.shape
         md = self._model(post, False)
@@ -584,8 +668,8 @@ class Engine:
         refined maxima x[found, D], mu[found] as NumPy arrays.  sync=False only enqueues (h_found = NULL: nothing
         synchronises) and returns the device tensors x[K, D], mu[K] -- rows that found no start carry mu = -inf -- so
         that several searches can be queued behind each other and read back together.  Not for an ARD posterior
-        (mean_search_multi is)."""
-        if post.scale is not None:
+        (mean_search_multi is), nor for a camphor_copper_ard_kernel posterior."""
+        if post.embedded:
             raise ValueError("mean_search has no per-dimension length-scale form: use mean_search_multi")
         cand = self.dev(cand)
         M, D = cand.shape
@@ -608,9 +692,10 @@ class Engine:
         nothing synchronises."""
         pool = self.dev(pool)
         M, D = pool.shape
-        if D != post.X.shape[1]:
+        Dm = post.X.shape[1] if post.camphor is None else 6       # camphor: the search is in the caller's 6 coordinates
+        if D != Dm:
             # the library strides pool, shifts and extra by the MODEL's D: a mismatch would read out of bounds on the device
-            raise ValueError(f"mean_search_multi: pool has {D} columns, the model {post.X.shape[1]}")
+            raise ValueError(f"mean_search_multi: pool has {D} columns, the model {Dm}")
         sh = np.ascontiguousarray(np.atleast_2d(np.asarray(shifts, dtype=np.float64)))
         T = sh.shape[0]
         if sh.shape[1] != D:
@@ -636,7 +721,11 @@ class Engine:
         args = (self.ctx, C.byref(md), _ptr(pool), M, sh.ctypes.data_as(dp), T, _ptr(ex_ptr), E,
                 xp.ctypes.data_as(dp) if xp is not None else None, int(K), float(sep), int(iters), float(tol),
                 int(bool(screen_fp32)), _ptr(xs), _ptr(mus))
-        if post.scale is None:
+        if post.camphor is not None:     # the caller's coordinates; "design" = the caller's rows kept in post.Xc
+            l = np.ascontiguousarray(post.camphor, dtype=np.float64)
+            rc = self.lib.ppbo_mean_search_multi_camphor(*args, _ptr(post.Xc), self._dptr(l), self._stream())
+            self._check(rc, "ppbo_mean_search_multi_camphor")
+        elif post.scale is None:
             rc = self.lib.ppbo_mean_search_multi(*args, self._stream())
             self._check(rc, "ppbo_mean_search_multi")
         else:       # everything in the caller's coordinates; "design" = the model's rows taken back to them
@@ -651,7 +740,14 @@ class Engine:
         md = self._model(post, False)
         xs, mus = self.empty(K, D), self.empty(K)
         its = torch.zeros(K, dtype=torch.int32, device=self.device)
-        if post.scale is None:
+        if post.camphor is not None:
+            if D != 6:
+                raise ValueError(f"mean_ascent: starts of shape {tuple(starts.shape)} for a model of 6 dimensions")
+            l = np.ascontiguousarray(post.camphor, dtype=np.float64)
+            rc = self.lib.ppbo_mean_ascent_camphor(self.ctx, C.byref(md), _ptr(starts), K, int(iters), float(tol), _ptr(xs),
+                                                   _ptr(mus), _ptr(its), _ptr(post.Xc), self._dptr(l), self._stream())
+            self._check(rc, "ppbo_mean_ascent_camphor")
+        elif post.scale is None:
             rc = self.lib.ppbo_mean_ascent(self.ctx, C.byref(md), _ptr(starts), K, int(iters), float(tol), _ptr(xs), _ptr(mus),
                                            _ptr(its), self._stream())
             self._check(rc, "ppbo_mean_ascent")
@@ -675,8 +771,9 @@ class Engine:
     def line_acq(self, post: Posterior, grid, z, mustar, shrink=SHRINKAGE, jitter=0.0):
         grid = self.dev(grid)
         B, G, D = grid.shape
-        if post.scale is not None:
-            grid = self._points(post, grid.reshape(B * G, D)).reshape(B, G, D)
+        if post.embedded:
+            grid = self._points(post, grid.reshape(B * G, D))
+            grid = grid.reshape(B, G, grid.shape[1])
         z = self.dev(z)
         S = z.shape[0]
         md = self._model(post, True)
@@ -689,16 +786,32 @@ class Engine:
     def line_acq_xi(self, post: Posterior, xis, xs, alphas, z, mustar, shrink=SHRINKAGE, jitter=0.0):
         """EI and varmax of the B lines {alpha * xis[b] + xs[b]} (ppbo_line_acq_xi): the grid points are formed on the
         device.  alphas: [G] (shared by all lines) or [B, G].  ARD: the line is linear in (xi, x), so s (.) xi and s (.) x
-        give the scaled points at the same alpha."""
+        give the scaled points at the same alpha.  camphor_copper_ard_kernel: the line is not linear in the embedding, so
+        its embedded grid is formed in the caller's coordinates (ppbo_camphor_line_points) and scored by ppbo_line_acq."""
         xis, xs, alphas, z = self.dev(xis), self.dev(xs), self.dev(alphas), self.dev(z)
         B, D = xis.shape
         if xs.shape != (B, D):
             raise ValueError("line_acq_xi: xis and xs must both be [B, D]")
-        xis, xs = self._points(post, xis), self._points(post, xs)
         per_line = alphas.dim() == 2
         G = alphas.shape[-1]
         if per_line and alphas.shape[0] != B:
             raise ValueError("line_acq_xi: per-line abscissae must be [B, G]")
+        if post.camphor is not None:
+            if D != 6:
+                raise ValueError(f"line_acq_xi: lines of {D} coordinates for a model of 6")
+            grid = self.empty(B, G, 11)
+            l = np.ascontiguousarray(post.camphor, dtype=np.float64)
+            rc = self.lib.ppbo_camphor_line_points(self.ctx, _ptr(xis), _ptr(xs), _ptr(alphas), int(per_line), B, G,
+                                                   self._dptr(l), _ptr(grid), self._stream())
+            self._check(rc, "ppbo_camphor_line_points")
+            S = z.shape[0]
+            md = self._model(post, True)
+            ei, vm = self.empty(B), self.empty(B)
+            rc = self.lib.ppbo_line_acq(self.ctx, C.byref(md), _ptr(grid), B, G, float(shrink), _ptr(z), S, float(mustar),
+                                        float(jitter), _ptr(ei), _ptr(vm), self._stream())
+            self._check(rc, "ppbo_line_acq")
+            return ei, vm
+        xis, xs = self._points(post, xis), self._points(post, xs)
         S = z.shape[0]
         md = self._model(post, True)
         ei, vm = self.empty(B), self.empty(B)

@@ -21,7 +21,8 @@ import numpy as np
 import scipy.optimize
 
 from . import kernels as _kernels
-from .engine import NotPositiveDefinite, RADIAL_KERNELS, SCORE_MEAN, get_engine, lengthscales, theta_key
+from .engine import (ARD_KERNELS, CAMPHOR_ARD, NotPositiveDefinite, SCORE_MEAN, get_engine, lengthscales,
+                     theta_key)
 from .feedback_processing import FeedbackProcessing
 
 SEARCH_CANDIDATES = 65536      # uniform candidates per mu_star trial
@@ -56,6 +57,16 @@ def log_prior_grad(theta):
     gl = -(1.0 + (np.log(l) + 1.4) / 0.25) / l
     sf = float(theta[2])
     return np.append(gl, -(1.0 + (np.log(sf) - 1.7) / 0.25) / sf)
+
+
+def camphor_coordinate_sums(sums):
+    """The evidence gradient's 11 per-column sums of camphor_copper_ard_kernel's embedded rows (c0, s0, c1, s1, z, c3, s3,
+    c4, s4, c5, s5; include/ppbo_hip.h) -> one per coordinate: every column scales with 1 / l_d of its coordinate, so the
+    cos and sin columns of a periodic coordinate add up."""
+    s = np.asarray(sums, dtype=float)
+    if s.shape != (11,):
+        raise ValueError(f"camphor_coordinate_sums: 11 embedded-column sums, not {s.shape}")
+    return np.array([s[0] + s[1], s[2] + s[3], s[4], s[5] + s[6], s[7] + s[8], s[9] + s[10]])
 
 
 def _theta_list(theta):
@@ -375,12 +386,19 @@ class GPModel:
         _, _, ld, lo = eng.laplace_terms(fm, self.m, theta[0])
         return Sig, Sinv, fm, st, ld, lo
 
+    def _prior_theta(self, theta):
+        """theta as log_prior sees it: camphor_copper_ard_kernel's length scales always as the six l_d (a scalar expanded
+        to the reference's profile), so that its prior is the sum over the six coordinates."""
+        if self.kernel.__name__ == CAMPHOR_ARD:
+            return [theta[0], lengthscales(theta, self.D, CAMPHOR_ARD), theta[2]]
+        return theta
+
     def _evidence_core(self, eng, theta, f0):
         """One Laplace evidence on `eng` from the start vector f0 (device); returns (value incl. log-prior, log-evidence)."""
         Sig, _, _, st, ld, lo = self._evidence_fit(eng, theta, f0)
         sgn, logdet, _ = eng.laplace_logdet(Sig, ld, lo, self.m)
         log_evidence = st["T"] - 0.5 * sgn * logdet
-        return log_evidence + log_prior(theta), log_evidence
+        return log_evidence + log_prior(self._prior_theta(theta)), log_evidence
 
     def evidence(self, theta, f_initial):
         """Laplace log-marginal likelihood + log-prior (gp_model.py:278-319) on the device.
@@ -438,13 +456,14 @@ class GPModel:
         unpinned (GPyOpt==1.2.6 absent); the objective is the pinned evidence().
         Per-dimension length scales in theta_initial: the same 2-parameter search, 60 evidence fits and box, over a common
         factor c of the initial profile, l = c p with p = l0 / geomean(l0), and sigma_f (fitting the D length scales
-        one by one needs evidence gradients, which the project does not have)."""
+        one by one is optimize_theta_ard).  camphor_copper_ard_kernel always searches its profile, a scalar l standing for
+        (l, l, l + 0.05, l, l, l)."""
         if self.verbose:
             print("Hyperparameter optimization begins...")
         start = time.time()
         l0 = self.theta_initial[1] if self.theta_initial is not None else None
         profile = None
-        if l0 is not None and np.ndim(l0) != 0:
+        if l0 is not None and (np.ndim(l0) != 0 or self.kernel.__name__ == CAMPHOR_ARD):
             l0 = lengthscales(self.theta_initial, self.D, self.kernel.__name__)
             profile = l0 / np.exp(np.mean(np.log(l0)))
 
@@ -476,23 +495,27 @@ class GPModel:
         same Gram, inverse, fit and LU; the start is f_initial, or a prior draw from the global stream when it is None,
         and f_MAP is found to gtol, default 1e-4 as in evidence()); grad has one entry per length scale (one for a
         scalar l, D for a vector) followed by dE/dsigma_f; s_U is the sign of the LU's prod u_kk, f_MAP the device
-        vector.  A non-finite value maps to -500 with a zero gradient.  Raises ValueError for the camphor-copper
-        kernel and NotPositiveDefinite when Sigma or Sigma^-1 - Lambda(f_MAP) is not positive definite."""
+        vector; six for camphor_copper_ard_kernel, whose scalar l stands for its profile).  A non-finite value maps to
+        -500 with a zero gradient.  Raises ValueError for the camphor-copper kernel and NotPositiveDefinite when Sigma or
+        Sigma^-1 - Lambda(f_MAP) is not positive definite."""
         theta = _theta_list(theta)
         kern = self.kernel.__name__
-        if kern not in RADIAL_KERNELS:
-            raise ValueError(f"the evidence gradient is defined for the radial kernels {RADIAL_KERNELS}, not {kern}")
+        if kern not in ARD_KERNELS:
+            raise ValueError(f"the evidence gradient is defined for the kernels {ARD_KERNELS}, not {kern}")
         ls = lengthscales(theta, self.D, kern)
         f0 = self._draw_prior() if f_initial is None else self.eng.dev(f_initial).reshape(-1)
         Sig, Sinv, fm, st, ld, lo = self._evidence_fit(self.eng, theta, f0, 1e-4 if gtol is None else float(gtol))
         sgn, logdet, sums, _ = self.eng.evidence_grad(self._dX, theta, kern, Sig, Sinv, fm, ld, lo, self.m,
                                                       self.COVARIANCE_SHRINKAGE)
         log_evidence = st["T"] - 0.5 * sgn * logdet
-        value = log_evidence + log_prior(theta)
+        value = log_evidence + log_prior(self._prior_theta(theta))
         sf = theta[2]
         # dSigma_ij/dl_d = -2 (1 - eps) sf^2 kappa'(rho^2) (x_id - x_jd)^2 / (l_dev^2 l_d), l_dev = 1 for ARD rows
         coef = -2.0 * (1.0 - self.COVARIANCE_SHRINKAGE) * sf * sf
         raw = sums[:-1]
+        if kern == CAMPHOR_ARD:
+            raw = camphor_coordinate_sums(raw)
+            theta = self._prior_theta(theta)
         if ls is None:
             gl = np.array([coef * float(np.sum(raw)) / theta[1] ** 3])
         else:
@@ -509,10 +532,11 @@ class GPModel:
         theta; a scalar l is broadcast to D) or the current theta.  Each evaluation's f_MAP search starts at the previous
         evaluation's f_MAP; the first at the model's f_MAP when it has N rows, else at one prior draw from the global
         stream.  At most `maxfun` evidence fits, every one logged in theta_search_log as (l, sigma_f, value); theta
-        becomes the best one seen, so never a worse one than the start."""
+        becomes the best one seen, so never a worse one than the start.  camphor_copper_ard_kernel: a scalar l in the
+        start is expanded to its profile (l, l, l + 0.05, l, l, l)."""
         kern = self.kernel.__name__
-        if kern not in RADIAL_KERNELS:
-            raise ValueError(f"per-dimension length scales are defined for the radial kernels {RADIAL_KERNELS}, not {kern}")
+        if kern not in ARD_KERNELS:
+            raise ValueError(f"per-dimension length scales are fitted for the kernels {ARD_KERNELS}, not {kern}")
         if self.verbose:
             print("Hyperparameter optimization (ARD, evidence gradient) begins...")
         t0 = time.time()

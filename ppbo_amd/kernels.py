@@ -40,4 +40,12 @@ def Matern32_kernel(X1, X2, theta):
     return _eval("Matern32_kernel", X1, X2, theta)
 
 
-BY_NAME = {f.__name__: f for f in (SE_kernel, RQ_kernel, camphor_copper_kernel, Matern52_kernel, Matern32_kernel)}
+# No reference counterpart: camphor-copper with one length scale per coordinate (x, y, z, alpha, beta, gamma),
+# theta = [sigma, l, sigma_f] with l a length-6 vector or a scalar standing for the reference's (l, l, l + 0.05, l, l, l);
+# evaluated as SE on the embedded rows of engine.camphor_embed
+def camphor_copper_ard_kernel(X1, X2, theta):
+    return _eval("camphor_copper_ard_kernel", X1, X2, theta)
+
+
+BY_NAME = {f.__name__: f for f in (SE_kernel, RQ_kernel, camphor_copper_kernel, Matern52_kernel, Matern32_kernel,
+                                   camphor_copper_ard_kernel)}

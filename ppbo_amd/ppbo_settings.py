@@ -40,7 +40,7 @@ class PPBO_settings:
         theta_optimizer (not a reference option): how update_model(optimize_theta=True) fits theta.  "search" = the
         derivative-free 60-fit search over (l, sigma_f) of GPModel.optimize_theta (the default); "ard-gradient" =
         GPModel.optimize_theta_ard, L-BFGS-B with the device's evidence gradient over one length scale per dimension and
-        sigma_f (radial kernels only)."""
+        sigma_f (radial kernels and camphor_copper_ard_kernel)."""
         if fMAP_method not in ("whitened", "trust-region"):
             raise ValueError("fMAP_method must be 'whitened' or 'trust-region'")
         if theta_optimizer not in THETA_OPTIMIZERS:
