@@ -284,7 +284,8 @@ typedef struct ppbo_model {
   const double* d_alpha;    /* [N]   */
   const double* d_lam_diag; /* [N]  Lambda_MAP diagonal   */
   const double* d_lam_off;  /* [N]  Lambda_MAP star edges */
-  const double* d_G;        /* [N,N] R W, see ppbo_posterior.  Block lower triangular, and stored that way: every
+  const double* d_G;        /* [N,N] R W, see ppbo_posterior (or H, for the *_edge entry points: see ppbo_posterior_edge).
+                             * Block lower triangular, and stored that way: every
                              * entry right of the last star that reaches into its row must be an explicit ZERO
                              * (ppbo_posterior / ppbo_gp_fit write them): the contractions round their K ranges up to
                              * whole 16-column chunks and read up to 15 of those zeros per row */
@@ -536,6 +537,53 @@ PPBO_API int ppbo_argmax_allgather_record(ppbo_ctx* ctx, const double* d_record,
  * candidate set; the reference itself is process-per-run (ppbo_numerical_main.py:192-193). */
 PPBO_API int ppbo_search_sharded(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc, int64_t M, int score_kind,
                         double mustar, int64_t index_offset, double* h_best_val, int64_t* h_best_idx, void* stream);
+
+/* ---- the variance operator in EDGE form ----------------------------------------------------------------------------
+ * Lambda_MAP = sum over the E = N - n_q star edges (obs_q, j) of w_j (e_obs - e_j)(e_obs - e_j)^T, so with D the E x N
+ * edge incidence matrix and e = diag(w) D k* (e_j = w_j (k*_obs - k*_j)) the variance term is |G k*|^2 = e^T (D P D^T) e,
+ * P = B^-1.  Ordering the coordinates as [n_q observation values; the E edge differences x_obs - x_j, star-major] turns
+ * B into the congruent Btilde (positive definite exactly when B is); with Btilde = L L^T, D P D^T = L22^-T L22^-1 for
+ * the trailing E x E block L22, hence
+ *   sigma^2(x) = sigma_f^2 + k*^T Lambda k* + |H e|^2,   H = L22^-1 (lower triangular, E x E).
+ * No square root of the sign-changing edge weights is taken.  H is stored in the N x N d_G of the node form: rows and
+ * columns [0, n_q) zero, edge (q, t) (pseudo row q (m + 1) + 1 + t) at row / column n_q + q m + t, zeros above the
+ * diagonal.  Its contraction costs (E / N)^2 of the node form's and ends at each row's own diagonal instead of at the end
+ * of its star.
+ * ppbo_posterior_form: PPBO_FORM_NODE when the one-launch scoring kernel (fused.hip, node form only) takes a model of
+ * this shape by default (radial kernel, D <= 16, up to ~500 rows), else PPBO_FORM_EDGE -- which form the caller should
+ * build.  It does not depend on the ctx's PPBO_FUSED setting: the shapes that only PPBO_FUSED=2 sends to the one-launch
+ * kernel (up to ~1000 rows, or D > 16) get the edge form, and are then scored by the three-launch path.
+ * ppbo_posterior_edge / ppbo_gp_fit_edge: ppbo_posterior / ppbo_gp_fit writing H instead of G (same arguments, same
+ * PPBO_ERR_NOT_PD / h_info reporting; d_P, when asked for, is formed as ppbo_posterior forms it, from a second
+ * factorization in node coordinates whose failure is reported the same way).
+ * The *_edge consumers: the entry point of the same name for a model whose d_G holds H (d_Gt is not read). */
+enum { PPBO_FORM_NODE = 0, PPBO_FORM_EDGE = 1 };
+PPBO_API int ppbo_posterior_form(ppbo_ctx* ctx, int kernel_id, int N, int D, int m);
+PPBO_API int ppbo_posterior_edge(ppbo_ctx* ctx, const double* d_Sigma_inv, const double* d_fMAP, int N, int m,
+                        double sigma, double* d_alpha, double* d_lam_diag, double* d_lam_off,
+                        double* d_H, double* d_P, int* h_info, void* stream);
+PPBO_API int ppbo_gp_fit_edge(ppbo_ctx* ctx, int kernel_id, const double* d_X, int N, int D, const double theta[3],
+                     double shrink, int m, const double* d_f_init, const ppbo_fit_opts* opts, double* d_Sigma,
+                     double* d_Sigma_inv, double* d_L, double* d_Linv, double* d_fMAP, double* d_alpha,
+                     double* d_lam_diag, double* d_lam_off, double* d_H, ppbo_fit_stats* h_stats, int* h_info,
+                     void* stream);
+PPBO_API int ppbo_predict_edge(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc, int64_t M,
+                      int score_kind, double mustar, double* d_mu, double* d_var, double* d_score,
+                      double* h_best_val, int64_t* h_best_idx, void* stream);
+PPBO_API int ppbo_predict_record_edge(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc, int64_t M,
+                             int score_kind, double mustar, int64_t index_offset, double* d_record, void* stream);
+PPBO_API int ppbo_search_sharded_edge(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc, int64_t M,
+                             int score_kind, double mustar, int64_t index_offset, double* h_best_val,
+                             int64_t* h_best_idx, void* stream);
+PPBO_API int ppbo_predict_cov_edge(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc, int M,
+                          double shrink, double* d_mu, double* d_cov, void* stream);
+PPBO_API int ppbo_line_acq_edge(ppbo_ctx* ctx, const ppbo_model* model, const double* d_grid, int B, int G,
+                       double shrink, const double* d_z, int S, double mustar, double jitter, double* d_ei,
+                       double* d_varmax, void* stream);
+PPBO_API int ppbo_line_acq_xi_edge(ppbo_ctx* ctx, const ppbo_model* model, const double* d_xi, const double* d_x,
+                          const double* d_alpha, int alpha_per_line, int B, int G, double shrink,
+                          const double* d_z, int S, double mustar, double jitter, double* d_ei,
+                          double* d_varmax, void* stream);
 /* the reduction alone, for callers that run the all-gather themselves (torch.distributed in ppbo_amd/dist.py):
  * d_records[world][2] = (value, global index as a double) per rank, already gathered in device memory; one
  * single-wavefront kernel applies the rule above and ONE 16-byte record is copied back. */

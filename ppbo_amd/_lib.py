@@ -108,9 +108,14 @@ SIGNATURES = {
     "ppbo_argmax_allgather": [_vp, _d, _i64, C.POINTER(_d), C.POINTER(_i64), _vp],
     "ppbo_argmax_allgather_record": [_vp, _vp, C.POINTER(_d), C.POINTER(_i64), _vp],
     "ppbo_search_sharded": [_vp, C.POINTER(Model), _vp, _i64, _i, _d, _i64, C.POINTER(_d), C.POINTER(_i64), _vp],
+    "ppbo_posterior_form": [_vp, _i, _i, _i, _i],
     "ppbo_argmax_combine": [_vp, _vp, _i, C.POINTER(_d), C.POINTER(_i64), _vp],
     "ppbo_dgemm": [_vp, _i, _i, _i, _i, _i, _d, _vp, _i, _vp, _i, _d, _vp, _i, _vp],
 }
+# the edge-form entry points take exactly the arguments of their node-form namesakes
+for _n in ("ppbo_posterior", "ppbo_gp_fit", "ppbo_predict", "ppbo_predict_record", "ppbo_search_sharded",
+           "ppbo_predict_cov", "ppbo_line_acq", "ppbo_line_acq_xi"):
+    SIGNATURES[_n + "_edge"] = SIGNATURES[_n]
 
 _lib = None
 ABI_VERSION = 6     # must equal PPBO_ABI_VERSION of include/ppbo_hip.h

@@ -58,6 +58,9 @@ struct ppbo_ctx {
   // the host-polled searches let the runtime wait (hipStreamSynchronize) when their progress word has been still for
   // this long, and carry on if that advanced the search (PPBO_POLL_LIMIT_MS; tests set it to 0 to walk that path)
   int poll_limit_ms = 5000;
+  // the variance operator of the model(s) of the running entry point is in EDGE form (H = L22^-1 of the edge-coordinate
+  // factor, ppbo_posterior_edge) instead of the node form G = R Lambda; set only for the duration of a *_edge entry point
+  int op_edge = 0;
   hipStream_t side_stream = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   int syrk_cfg = 0;       // PPBO_SYRK_CFG: tile configuration of Sigma^-1 = Linv^T Linv (0 = by size; 1 / 2 / 3 = 128 / 64 / 32)
@@ -113,6 +116,16 @@ int ppbo_fused_score(ppbo_ctx* ctx, const ppbo_model* m, const double* Gt, int l
 int ppbo_predict_record_publish(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc, int64_t M, int score_kind,
                                 double mustar, int64_t index_offset, double* d_record, unsigned long long* d_flag,
                                 unsigned long long epoch, hipStream_t s);
+
+// the *_edge entry points: run the node-form entry with ctx->op_edge raised for its duration
+struct PpboEdgeScope {
+  ppbo_ctx* ctx; int prev;
+  explicit PpboEdgeScope(ppbo_ctx* c) : ctx(c), prev(c ? c->op_edge : 0) { if (ctx) ctx->op_edge = 1; }
+  ~PpboEdgeScope() { if (ctx) ctx->op_edge = prev; }
+};
+// first row / column of an edge-form operator that the contractions read: the n_q observation coordinates hold zeros,
+// the K loops start at n_q rounded down to the chunk depth
+inline int ppbo_edge_k0(int n_q) { return n_q & ~15; }
 
 // Every extern "C" entry runs on its ctx's device and leaves the caller's current device as it found it.
 struct PpboDeviceGuard {

@@ -293,6 +293,91 @@ __global__ __launch_bounds__(256) void g_build_kernel(const double* __restrict__
   G[(size_t)blockIdx.y * N + j] = acc;
 }
 
+// ---- the posterior in EDGE form (ppbo_posterior_edge) ----
+// Lambda_MAP = sum over the star edges (obs_q, j) of w_j (e_obs - e_j)(e_obs - e_j)' (laplace_kernel: lam_diag[j] = w_j,
+// lam_off[j] = -w_j), so the variance term needs B = Sigma^-1 - Lambda only through D P D' (D the E x N edge incidence,
+// P = B^-1).  In the coordinates y = Dbar x = [x_obs (n_q); x_obs - x_j (E = N - n_q edges, star-major)] the matrix
+// Btilde = Dbar^-T B Dbar^-1 has Dbar^-1's columns 1_star(q) (observation coordinate q) and -e_j (edge j):
+//   obs-obs   1_p' Sigma^-1 1_q                 (U below)
+//   obs-edge  -1_p' Sigma^-1 e_j = -T[j][p]     (T: the star sums of Sigma^-1's rows)
+//   edge-edge Sigma^-1[i][j] + delta_ij lam_off[j]
+// It is congruent to B (positive definite exactly when B is); with Btilde = L L', D P D' = L22^-T L22^-1, L22 the
+// trailing E x E block, so |G k*|^2 = |H e|^2 with H = L22^-1 and e_j = lam_off[j] (k*_j - k*_obs).  No square root of
+// the (sign-changing) edge weights is taken.
+__device__ __forceinline__ int edge_node(int e, int m) { const int q = e / m; return q * (m + 1) + 1 + (e - q * m); }
+
+// compensated (TwoSum) accumulation: the star sums of Sigma^-1 cancel to a small fraction of their terms (cond ~ 1e7)
+struct CompSum {
+  double s = 0.0, c = 0.0;
+  __device__ __forceinline__ void add(double x) {
+    const double t = s + x, bp = t - s;
+    c += (s - (t - bp)) + (x - bp);
+    s = t;
+  }
+  __device__ __forceinline__ double value() const { return s + c; }
+};
+
+// Tt[q][i] = sum over star q of Sigma^-1[k][i] (= row i's star-q sum: Sigma^-1 is symmetric)   ([n_q][N]); one thread per
+// column i, the star's rows walked in order: every load of a wavefront is one contiguous 512-byte row piece
+__global__ __launch_bounds__(256) void star_colsum_kernel(const double* __restrict__ Sinv, int N, int mblk,
+                                                          double* __restrict__ Tt) {
+  const int i = blockIdx.x * 256 + threadIdx.x, q = blockIdx.y;
+  if (i >= N) return;
+  const double* r = Sinv + (size_t)q * mblk * N + i;
+  CompSum t;
+  for (int k = 0; k < mblk; ++k) t.add(r[(size_t)k * N]);
+  Tt[(size_t)q * N + i] = t.value();
+}
+
+// U[p][q] = sum over star p of Tt[q][i] = 1_p' Sigma^-1 1_q   ([n_q][n_q])
+__global__ __launch_bounds__(64) void star_sum2_kernel(const double* __restrict__ Tt, int N, int mblk, int n_q,
+                                                       double* __restrict__ U) {
+  const int q = blockIdx.x * 64 + threadIdx.x, p = blockIdx.y;
+  if (q >= n_q) return;
+  const double* t = Tt + (size_t)q * N + (size_t)p * mblk;
+  CompSum u;
+  for (int k = 0; k < mblk; ++k) u.add(t[k]);
+  U[(size_t)p * n_q + q] = u.value();
+}
+
+// Btilde [N][N], one workgroup per row, coordinates [n_q observation coordinates; edges star-major]
+__global__ __launch_bounds__(256) void form_edge_kernel(const double* __restrict__ Sinv, int N, int mblk, int n_q,
+                                                        const double* __restrict__ Tt, const double* __restrict__ U,
+                                                        const double* __restrict__ lam_off, double* __restrict__ Bt) {
+  const int c = blockIdx.x, m = mblk - 1;
+  double* dst = Bt + (size_t)c * N;
+  if (c < n_q) {
+    const double* tc = Tt + (size_t)c * N;
+    for (int j = threadIdx.x; j < N; j += 256)
+      store_through(dst + j, j < n_q ? U[(size_t)c * n_q + j] : -tc[edge_node(j - n_q, m)]);
+    return;
+  }
+  const int i = edge_node(c - n_q, m);
+  const double* src = Sinv + (size_t)i * N;
+  for (int j = threadIdx.x; j < N; j += 256) {
+    double v;
+    if (j < n_q) {
+      v = -Tt[(size_t)j * N + i];
+    } else {
+      const int k = edge_node(j - n_q, m);
+      v = src[k];
+      if (k == i) v += lam_off[i];
+    }
+    store_through(dst + j, v);
+  }
+}
+
+// H from the triangular inverse of the whole factor (whose trailing E x E block is L22^-1): zero the observation rows and
+// columns it filled, and everything right of each row's 64 x 64 diagonal block, which it left unwritten (it writes the
+// blocks' own upper triangles as zeros)
+__global__ __launch_bounds__(256) void edge_frame_kernel(double* __restrict__ H, int N, int n_q) {
+  const int r = blockIdx.y;
+  const int lim = r < n_q ? 0 : ((r >> 6) + 1) * 64;
+  double* row = H + (size_t)r * N;
+  for (int c = blockIdx.x * 256 + threadIdx.x; c < N; c += gridDim.x * 256)
+    if (c < n_q || c >= lim) row[c] = 0.0;
+}
+
 struct Vecs {  // one evaluation point
   double *f, *v, *beta, *ld, *lo, *g;
   double fSf, gn2, Tlik;
@@ -1478,12 +1563,37 @@ int posterior_async(ppbo_ctx* ctx, const double* d_Sigma_inv, const double* d_fM
   double* R = H + nn;
   if (int rc = ppbo_gemv_async(ctx, d_Sigma_inv, N, N, d_fMAP, d_alpha, 0, 0, s)) return rc;
   laplace_kernel<<<(n_q + 3) / 4, 256, 0, s>>>(d_fMAP, N, mblk, n_q, sigma, nullptr, nullptr, d_lam_diag, d_lam_off);
-  form_shifted_kernel<<<N, 256, 0, s>>>(d_Sigma_inv, N, mblk, d_lam_diag, d_lam_off, 0.0, H, nullptr);
-  PPBO_LAUNCH_CHECK(ctx);
-  if (int rc = ppbo_potrf_async(ctx, H, N, N, d_info, s)) return rc;
-  if (int rc2 = ppbo_trtri_async(ctx, H, N, N, R, N, s, 0, nullptr, d_P ? 1 : 0)) return rc2;   // R^T R reads above the blocks, G = R Lambda does not
-  g_build_kernel<<<dim3((N + 255) / 256, N), 256, 0, s>>>(R, N, mblk, d_lam_diag, d_lam_off, d_G);
-  PPBO_LAUNCH_CHECK(ctx);
+  if (ctx->op_edge) {
+    // edge form: Btilde in H (its star sums staged in R's half), factor, H = inverse of the trailing E x E block written
+    // into d_G at (n_q, n_q); the rest of d_G -- the observation rows / columns and everything above the diagonal,
+    // which the contractions read up to the end of their 16-column chunks -- is zero
+    double* Tt = R;
+    double* U = R + (size_t)N * n_q;
+    star_colsum_kernel<<<dim3((N + 255) / 256, n_q), 256, 0, s>>>(d_Sigma_inv, N, mblk, Tt);
+    star_sum2_kernel<<<dim3((n_q + 63) / 64, n_q), 64, 0, s>>>(Tt, N, mblk, n_q, U);
+    form_edge_kernel<<<N, 256, 0, s>>>(d_Sigma_inv, N, mblk, n_q, Tt, U, d_lam_off, H);
+    PPBO_LAUNCH_CHECK(ctx);
+    if (int rc = ppbo_potrf_async(ctx, H, N, N, d_info, s)) return rc;
+    // (L^-1)_22 = L22^-1: the whole factor is inverted (the N x N doubling has no ragged levels where E often would:
+    // 1984 = 1024 + 960 cost five more GEMM launches per fit than 2048) and the observation part cleared behind it
+    if (int rc2 = ppbo_trtri_async(ctx, H, N, N, d_G, N, s, 0, nullptr, 0)) return rc2;
+    edge_frame_kernel<<<dim3((N + 511) / 512, N), 256, 0, s>>>(d_G, N, n_q);
+    PPBO_LAUNCH_CHECK(ctx);
+    if (!d_P) return 0;
+    // P = B^-1 on the node-form path: the factorization repeats the one above in node coordinates; its info word goes to
+    // d_info[1], which ppbo_posterior reports (PPBO_ERR_NOT_PD) should that factor fail where the edge one did not
+    form_shifted_kernel<<<N, 256, 0, s>>>(d_Sigma_inv, N, mblk, d_lam_diag, d_lam_off, 0.0, H, nullptr);
+    PPBO_LAUNCH_CHECK(ctx);
+    if (int rc = ppbo_potrf_async(ctx, H, N, N, d_info + 1, s)) return rc;
+    if (int rc2 = ppbo_trtri_async(ctx, H, N, N, R, N, s)) return rc2;
+  } else {
+    form_shifted_kernel<<<N, 256, 0, s>>>(d_Sigma_inv, N, mblk, d_lam_diag, d_lam_off, 0.0, H, nullptr);
+    PPBO_LAUNCH_CHECK(ctx);
+    if (int rc = ppbo_potrf_async(ctx, H, N, N, d_info, s)) return rc;
+    if (int rc2 = ppbo_trtri_async(ctx, H, N, N, R, N, s, 0, nullptr, d_P ? 1 : 0)) return rc2;   // R^T R reads above the blocks, G = R Lambda does not
+    g_build_kernel<<<dim3((N + 255) / 256, N), 256, 0, s>>>(R, N, mblk, d_lam_diag, d_lam_off, d_G);
+    PPBO_LAUNCH_CHECK(ctx);
+  }
   if (d_P) {
     GemmArgs g{};  // P = R^T R
     g.A = R; g.lda = N; g.B = R; g.ldb = N; g.C = d_P; g.ldc = N;
@@ -1630,12 +1740,30 @@ int ppbo_posterior(ppbo_ctx* ctx, const double* d_Sigma_inv, const double* d_fMA
   // triangular inverse of a failed factor is wasted work, but a failure is the rare case)
   if (int rc = posterior_async(ctx, d_Sigma_inv, d_fMAP, N, m, sigma, d_alpha, d_lam_diag, d_lam_off, d_G, d_P, d_info, s))
     return rc;
-  int info = 0;
-  PPBO_HIP_CHECK(ctx, hipMemcpyAsync(&info, d_info, sizeof(int), hipMemcpyDeviceToHost, s));
+  int info[2] = {0, 0};
+  const bool two = ctx->op_edge && d_P;      // edge form with P: a second factorization (node coordinates) for P
+  PPBO_HIP_CHECK(ctx, hipMemcpyAsync(info, d_info, (two ? 2 : 1) * sizeof(int), hipMemcpyDeviceToHost, s));
   PPBO_HIP_CHECK(ctx, hipStreamSynchronize(s));
-  if (h_info) *h_info = info;
-  if (info != 0) return ppbo_set_error(ctx, PPBO_ERR_NOT_PD, "matrix is not positive definite (leading minor %d)", info);
+  const int bad = info[0] != 0 ? info[0] : info[1];
+  if (h_info) *h_info = bad;
+  if (bad != 0) return ppbo_set_error(ctx, PPBO_ERR_NOT_PD, "matrix is not positive definite (leading minor %d)", bad);
   return 0;
+}
+
+int ppbo_posterior_edge(ppbo_ctx* ctx, const double* d_Sigma_inv, const double* d_fMAP, int N, int m, double sigma,
+                        double* d_alpha, double* d_lam_diag, double* d_lam_off, double* d_H, double* d_P, int* h_info,
+                        void* stream) {
+  PpboEdgeScope es(ctx);
+  return ppbo_posterior(ctx, d_Sigma_inv, d_fMAP, N, m, sigma, d_alpha, d_lam_diag, d_lam_off, d_H, d_P, h_info, stream);
+}
+
+int ppbo_gp_fit_edge(ppbo_ctx* ctx, int kernel_id, const double* d_X, int N, int D, const double theta[3], double shrink,
+                     int m, const double* d_f_init, const ppbo_fit_opts* opts, double* d_Sigma, double* d_Sigma_inv,
+                     double* d_L, double* d_Linv, double* d_fMAP, double* d_alpha, double* d_lam_diag, double* d_lam_off,
+                     double* d_H, ppbo_fit_stats* h_stats, int* h_info, void* stream) {
+  PpboEdgeScope es(ctx);
+  return ppbo_gp_fit(ctx, kernel_id, d_X, N, D, theta, shrink, m, d_f_init, opts, d_Sigma, d_Sigma_inv, d_L, d_Linv,
+                     d_fMAP, d_alpha, d_lam_diag, d_lam_off, d_H, h_stats, h_info, stream);
 }
 
 }  // extern "C"

@@ -632,6 +632,16 @@ bool ppbo_fused_eligible(const ppbo_ctx* ctx, const ppbo_model* m) {
   return ctx->fused_score >= 2 && (fused_split(m->N, m->m + 1, 256) >= 0 || fused_split(m->N, m->m + 1, 512) >= 0);
 }
 
+extern "C" int ppbo_posterior_form(ppbo_ctx* ctx, int kernel_id, int N, int D, int m) {
+  PPBO_ENTER(ctx);
+  PPBO_REQUIRE(ctx, N > 0 && D > 0 && m >= 1 && N % (m + 1) == 0, "sizes (N must be n_q*(m+1))");
+  // the default (PPBO_FUSED=1) shapes of ppbo_fused_eligible, whatever this ctx's PPBO_FUSED says: the form is a property
+  // of the model's shape, so that ctxs with different scoring switches build the same posterior
+  const bool radial = kernel_id == PPBO_KERNEL_SE || kernel_id == PPBO_KERNEL_RQ || kernel_id == PPBO_KERNEL_MATERN52 ||
+                      kernel_id == PPBO_KERNEL_MATERN32;
+  return (radial && D <= 16 && fused_split(N, m + 1, 256) >= 0) ? PPBO_FORM_NODE : PPBO_FORM_EDGE;
+}
+
 // scores M candidates in one launch; blk_best (device, (M + 31) / 32 records) receives the per-block bests when not NULL.
 // Gt: the transpose of G framed with zeros (ppbo_fused_transposed_G), row stride ldgt.
 int ppbo_fused_score(ppbo_ctx* ctx, const ppbo_model* m, const double* Gt, int ldgt, const double* d_Xc, long long M,

@@ -72,7 +72,7 @@ __global__ __launch_bounds__(KS_THREADS) void kstar_kernel(
     const double* __restrict__ X, int N, int D, KernParams p, const double* __restrict__ alpha,
     const double* __restrict__ lam_diag, const double* __restrict__ lam_off, int mblk,
     const double* __restrict__ Xc, int M, double* __restrict__ Kt, int ldk, double* __restrict__ mu_part,
-    double* __restrict__ t_part, int q_per_split, int n_q) {
+    double* __restrict__ t_part, int q_per_split, int n_q, int edge_k0) {
   __shared__ __attribute__((aligned(16))) double xs[KS_RJ * DP];
   __shared__ double s_alpha[KS_RJ], s_ld[KS_RJ], s_lo[KS_RJ], s_nx[KS_RJ];
   const int c0 = (blockIdx.x * KS_THREADS + threadIdx.x) * KS_CPT;
@@ -125,6 +125,7 @@ __global__ __launch_bounds__(KS_THREADS) void kstar_kernel(
   const bool vec = (Kt != nullptr) && ((ldk & 1) == 0) && (c0 + KS_CPT - 1 < M);
   const bool has_lam = (lam_diag != nullptr);
   int rb = 0;  // row index inside the current star block (splits start on a block edge)
+  int qs = j_beg / mblk;  // ... and that block's star
   for (int row0 = j_beg; row0 < j_end; row0 += KS_RJ) {
     __syncthreads();
     if (CAMF) {                            // phi of the staged rows: (cos, sin)(2 pi x_k) for k = 0, 1, 3, 4, 5; then x_2
@@ -217,14 +218,37 @@ __global__ __launch_bounds__(KS_THREADS) void kstar_kernel(
         for (int q = 0; q < KS_CPT; ++q) kv[q] = kern_finish<KID>(sv[q], p);
       }
       if (Kt) {
-        double* dst = Kt + (size_t)(row0 + r) * ldk + c0;
-        if (vec) {      // 1 GB streamed out once, read back by the next kernel
+        // node form: row j holds k*_j.  Edge form (edge_k0 >= 0): row n_q + q m + t holds the edge value
+        // lam_off[j] (k*_j - k*_obs) of pseudo row j = q (m + 1) + 1 + t; row q (an observation coordinate, a zero column
+        // of H) holds zeros where the contraction reads it, i.e. from edge_k0 on
+        int drow = row0 + r;
+        bool wr = true;
+        double ev[KS_CPT];
+        if (edge_k0 >= 0) {
+          if (rb == 0) {
+            drow = qs;
+            wr = qs >= edge_k0;
 #pragma unroll
-          for (int q = 0; q < KS_CPT; q += 2) store_through2(dst + q, kv[q], kv[q + 1]);
+            for (int q = 0; q < KS_CPT; ++q) ev[q] = 0.0;
+          } else {
+            drow = n_q + qs * (mblk - 1) + rb - 1;
+            const double lo = s_lo[r];
+#pragma unroll
+            for (int q = 0; q < KS_CPT; ++q) ev[q] = lo * (kv[q] - ko[q]);
+          }
+        } else {
+#pragma unroll
+          for (int q = 0; q < KS_CPT; ++q) ev[q] = kv[q];
+        }
+        double* dst = Kt + (size_t)drow * ldk + c0;
+        if (!wr) {
+        } else if (vec) {      // 1 GB streamed out once, read back by the next kernel
+#pragma unroll
+          for (int q = 0; q < KS_CPT; q += 2) store_through2(dst + q, ev[q], ev[q + 1]);
         } else {
 #pragma unroll
           for (int q = 0; q < KS_CPT; ++q)
-            if (c0 + q < M) dst[q] = kv[q];
+            if (c0 + q < M) dst[q] = ev[q];
         }
       }
       const double a = s_alpha[r];
@@ -241,7 +265,7 @@ __global__ __launch_bounds__(KS_THREADS) void kstar_kernel(
           for (int q = 0; q < KS_CPT; ++q) tl[q] += kv[q] * (ld * kv[q] + lo2 * ko[q]);
         }
       }
-      if (++rb == mblk) rb = 0;
+      if (++rb == mblk) { rb = 0; ++qs; }
     }
   }
 #pragma unroll
@@ -254,11 +278,15 @@ __global__ __launch_bounds__(KS_THREADS) void kstar_kernel(
 }
 
 // Y = G K* ; slab[mt][c] = sum over the BM rows of tile mt of Y[i,c]^2
-template <class C, int MINW, bool ALWAYS_FAST>
+// EDGE: an edge-form operator (H lower triangular, zero in its first n_q rows and columns).  G and Kt then arrive offset
+// by kshift = n_q rounded down to the chunk depth (G + kshift, Kt + kshift ldk): the K loop starts at 0 of the shifted
+// operands, so the main loop is the node form's own code (a non-zero start in the loop cost 16 more bytes of spilled
+// state per lane and ~5 % of the matrix-core rate)
+template <class C, int MINW, bool ALWAYS_FAST, bool EDGE>
 __global__ __launch_bounds__(C::NT, MINW) void quadform_kernel(const double* __restrict__ G, int N,
                                                                const double* __restrict__ Kt, int ldk, int M,
                                                                int tri_block, double* __restrict__ slab, int ntm,
-                                                               int ntn, int swizzle, int n_rows) {
+                                                               int ntn, int swizzle, int n_rows, int kshift) {
   int id = blockIdx.x;
   if (swizzle & 1) {                   // XCD-aware: consecutive logical ids share an XCD / L2 (workgroup b runs on XCD b % 8)
     const int per = gridDim.x >> 3, rem = gridDim.x & 7;
@@ -287,15 +315,16 @@ __global__ __launch_bounds__(C::NT, MINW) void quadform_kernel(const double* __r
   // G is zero right of the last star that reaches into this row tile; the K range ends there, rounded UP to the chunk
   // depth (g_build_kernel writes the zeros of every row explicitly, so the extra columns multiply zeros): every K
   // range is then a whole number of chunks whatever the star size -- m = 25, the reference's default, has 26-row stars
-  const int e = (((m0 + C::BM + tri_block - 1) / tri_block) * tri_block + BK - 1) & ~(BK - 1);
-  const int kend = e < N ? e : N;
+  // Edge form: the K range of a tile ends with the tile's rows, that of a wavefront with its 32 rows (both shifted)
+  const int e = EDGE ? m0 + C::BM : (((m0 + C::BM + tri_block - 1) / tri_block) * tri_block + BK - 1) & ~(BK - 1);
+  const int kend = (e < N ? e : N) - kshift;
   double4_t acc[C::TM][C::TN];
   zero_acc<C>(acc);
   // rows of this wavefront end at m0 + (wm+1)*TM*16: G is zero beyond the end of their last star block
   const int wrow_beg = m0 + ((int)(threadIdx.x >> 6) / C::WN) * C::TM * 16;
   const int wrow_end = wrow_beg + C::TM * 16;
   // (a wavefront whose rows all lie in the zero frame below the real matrix multiplies nothing)
-  const int wk = wrow_beg >= n_rows ? 0 : ((wrow_end + tri_block - 1) / tri_block) * tri_block;
+  const int wk = wrow_beg >= n_rows ? 0 : (EDGE ? wrow_end : ((wrow_end + tri_block - 1) / tri_block) * tri_block) - kshift;
   mainloop<C, KC, RC, ALWAYS_FAST>(G, N, Kt, ldk, N, M, m0, n0, 0, kend, acc, wk < kend ? wk : kend);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int wm = wave / C::WN, wn = wave % C::WN;
@@ -336,10 +365,17 @@ using QF5 = Cfg<8, 2, 2, 4>;   // 256 x 128 tile, 16 waves of 32x64, 1 WG/CU: K*
 // predict_passes pads its operands so that this always holds.
 template <class C, int MINW>
 int launch_quadform(ppbo_ctx* ctx, const double* G, int N, int g_rows, int n_rows, const double* Kt, int ldk, int Mc,
-                    int mblk, double* slab, hipStream_t s) {
+                    int mblk, double* slab, int edge_k0, hipStream_t s) {
   const size_t lds = C::LDS_DOUBLES * sizeof(double);
-  ppbo_lds_limit(ctx, (const void*)quadform_kernel<C, MINW, true>, (int)lds);
-  ppbo_lds_limit(ctx, (const void*)quadform_kernel<C, MINW, false>, (int)lds);
+  const bool edge = edge_k0 >= 0;
+  const int kshift = edge ? edge_k0 : 0;
+  if (edge) {
+    ppbo_lds_limit(ctx, (const void*)quadform_kernel<C, MINW, true, true>, (int)lds);
+    ppbo_lds_limit(ctx, (const void*)quadform_kernel<C, MINW, false, true>, (int)lds);
+  } else {
+    ppbo_lds_limit(ctx, (const void*)quadform_kernel<C, MINW, true, false>, (int)lds);
+    ppbo_lds_limit(ctx, (const void*)quadform_kernel<C, MINW, false, false>, (int)lds);
+  }
   const int ntm = (g_rows + C::BM - 1) / C::BM, ntn = (Mc + C::BN - 1) / C::BN;
   const int grid = ntm * ntn;
   // PPBO_QF_ORDER; default: candidate-tile fastest in chunks of 128 tiles (514; measured best at N >= 2048:
@@ -350,8 +386,12 @@ int launch_quadform(ppbo_ctx* ctx, const double* G, int N, int g_rows, int n_row
   // every tile in bounds, 16-byte aligned, and every K range a multiple of 16?
   const bool fast = (g_rows % C::BM == 0) && (ldk >= ntn * C::BN) && (N % BK == 0) && (ldk % 2 == 0) &&
                     ((reinterpret_cast<uintptr_t>(G) & 15) == 0) && ((reinterpret_cast<uintptr_t>(Kt) & 15) == 0);
-  if (fast) quadform_kernel<C, MINW, true><<<grid, C::NT, lds, s>>>(G, N, Kt, ldk, Mc, mblk, slab, ntm, ntn, swz, n_rows);
-  else quadform_kernel<C, MINW, false><<<grid, C::NT, lds, s>>>(G, N, Kt, ldk, Mc, mblk, slab, ntm, ntn, swz, n_rows);
+  const double* Gs = G + kshift;
+  const double* Ks = Kt + (size_t)kshift * ldk;
+  if (edge && fast) quadform_kernel<C, MINW, true, true><<<grid, C::NT, lds, s>>>(Gs, N, Ks, ldk, Mc, mblk, slab, ntm, ntn, swz, n_rows, kshift);
+  else if (edge) quadform_kernel<C, MINW, false, true><<<grid, C::NT, lds, s>>>(Gs, N, Ks, ldk, Mc, mblk, slab, ntm, ntn, swz, n_rows, kshift);
+  else if (fast) quadform_kernel<C, MINW, true, false><<<grid, C::NT, lds, s>>>(G, N, Kt, ldk, Mc, mblk, slab, ntm, ntn, swz, n_rows, 0);
+  else quadform_kernel<C, MINW, false, false><<<grid, C::NT, lds, s>>>(G, N, Kt, ldk, Mc, mblk, slab, ntm, ntn, swz, n_rows, 0);
   PPBO_LAUNCH_CHECK(ctx);
   return 0;
 }
@@ -364,14 +404,14 @@ int launch_quadform(ppbo_ctx* ctx, const double* G, int N, int g_rows, int n_row
 int quadform_variant(const ppbo_ctx* ctx) { return ctx->qf_variant; }
 
 int dispatch_quadform(ppbo_ctx* ctx, const double* G, int N, int g_rows, int n_rows, const double* Kt, int ldk, int Mc,
-                      int mblk, double* slab, hipStream_t s) {
+                      int mblk, double* slab, int edge_k0, hipStream_t s) {
   switch (quadform_variant(ctx)) {
-    case 1: return launch_quadform<QF1, 4>(ctx, G, N, g_rows, n_rows, Kt, ldk, Mc, mblk, slab, s);
-    case 2: return launch_quadform<QF2, 4>(ctx, G, N, g_rows, n_rows, Kt, ldk, Mc, mblk, slab, s);
-    case 3: return launch_quadform<QF3, 4>(ctx, G, N, g_rows, n_rows, Kt, ldk, Mc, mblk, slab, s);
-    case 4: return launch_quadform<QF4, 8>(ctx, G, N, g_rows, n_rows, Kt, ldk, Mc, mblk, slab, s);
-    case 5: return launch_quadform<QF5, 4>(ctx, G, N, g_rows, n_rows, Kt, ldk, Mc, mblk, slab, s);
-    default: return launch_quadform<QF0, 2>(ctx, G, N, g_rows, n_rows, Kt, ldk, Mc, mblk, slab, s);
+    case 1: return launch_quadform<QF1, 4>(ctx, G, N, g_rows, n_rows, Kt, ldk, Mc, mblk, slab, edge_k0, s);
+    case 2: return launch_quadform<QF2, 4>(ctx, G, N, g_rows, n_rows, Kt, ldk, Mc, mblk, slab, edge_k0, s);
+    case 3: return launch_quadform<QF3, 4>(ctx, G, N, g_rows, n_rows, Kt, ldk, Mc, mblk, slab, edge_k0, s);
+    case 4: return launch_quadform<QF4, 8>(ctx, G, N, g_rows, n_rows, Kt, ldk, Mc, mblk, slab, edge_k0, s);
+    case 5: return launch_quadform<QF5, 4>(ctx, G, N, g_rows, n_rows, Kt, ldk, Mc, mblk, slab, edge_k0, s);
+    default: return launch_quadform<QF0, 2>(ctx, G, N, g_rows, n_rows, Kt, ldk, Mc, mblk, slab, edge_k0, s);
   }
 }
 
@@ -427,6 +467,20 @@ __global__ void lam_apply_kernel(const double* __restrict__ Kt, int ld, int N, i
     zo += lo * kj;
   }
   Z[(size_t)i * ld + c] = zo;
+}
+
+// E = the edge-layout K* of an edge-form model from the node-layout one: row q < n_q is zero, row n_q + q m + t holds
+// lam_off[j] (K*[j] - K*[obs_q]) for pseudo row j = q (m + 1) + 1 + t (kstar_kernel writes the same values in its epilogue)
+__global__ __launch_bounds__(128) void edge_apply_kernel(const double* __restrict__ Kt, int ld, int M, int mblk, int n_q,
+                                                         const double* __restrict__ lam_off, double* __restrict__ E) {
+  const int c = blockIdx.x * 128 + threadIdx.x, r = blockIdx.y;
+  if (c >= M) return;
+  double v = 0.0;
+  if (r >= n_q) {
+    const int m = mblk - 1, q = (r - n_q) / m, obs = q * mblk, j = obs + 1 + (r - n_q - q * m);
+    v = lam_off[j] * (Kt[(size_t)j * ld + c] - Kt[(size_t)obs * ld + c]);
+  }
+  E[(size_t)r * ld + c] = v;
 }
 
 // prior block of one line: cov_b[g][h] = (1-s) k(x_g, x_h), diagonal (1-s) sf2 + s sf2  (gp_model.py:447)
@@ -808,7 +862,7 @@ __global__ __launch_bounds__(256) void randn_kernel(unsigned long long seed, dou
 
 template <int KID>
 int launch_kstar(const ppbo_model* m, const KernParams& p, const double* d_Xc, int M, double* Kt, int ldk,
-                 double* mu_part, double* t_part, int q_per_split, int n_split, bool with_lam, hipStream_t s) {
+                 double* mu_part, double* t_part, int q_per_split, int n_split, bool with_lam, int edge_k0, hipStream_t s) {
   dim3 grid((M + KS_THREADS * KS_CPT - 1) / (KS_THREADS * KS_CPT), n_split);
   const int mblk = m->m + 1, n_q = (m->N + mblk - 1) / mblk;
   const double* ld = with_lam ? m->d_lam_diag : nullptr;
@@ -816,7 +870,7 @@ int launch_kstar(const ppbo_model* m, const KernParams& p, const double* d_Xc, i
 #define KS_LAUNCH32(DP)                                                                                              \
   kstar_kernel<KID, DP, true><<<grid, KS_THREADS, 0, s>>>(m->d_X, m->N, m->D, p, m->d_alpha, ld, lo, mblk, d_Xc, M, \
                                                           Kt, ldk, mu_part, with_lam ? t_part : nullptr,            \
-                                                          q_per_split, n_q)
+                                                          q_per_split, n_q, edge_k0)
   if (m->kstar_fp32) {       // the fp32-tolerance report: the BASELINE shapes get their own bucket, the rest a generic one
     if (KID == PPBO_KERNEL_CAMPHOR || m->D <= 6) KS_LAUNCH32(6);
     else if (m->D <= 20) KS_LAUNCH32(20);
@@ -827,7 +881,7 @@ int launch_kstar(const ppbo_model* m, const KernParams& p, const double* d_Xc, i
 #define KS_LAUNCH(DP)                                                                                          \
   kstar_kernel<KID, DP><<<grid, KS_THREADS, 0, s>>>(m->d_X, m->N, m->D, p, m->d_alpha, ld, lo, mblk, d_Xc, M, \
                                                     Kt, ldk, mu_part, with_lam ? t_part : nullptr,            \
-                                                    q_per_split, n_q)
+                                                    q_per_split, n_q, edge_k0)
   if (KID == PPBO_KERNEL_CAMPHOR) KS_LAUNCH(12);      // the feature form: 12 staged values per row
   else if (m->D <= 4) KS_LAUNCH(4);
   else if (m->D <= 6) KS_LAUNCH(6);
@@ -844,15 +898,16 @@ int launch_kstar(const ppbo_model* m, const KernParams& p, const double* d_Xc, i
   return 0;
 }
 
+// edge_k0 >= 0: K* in the edge layout of an edge-form model (kstar_kernel), which needs with_lam
 int dispatch_kstar(const ppbo_model* m, const double* d_Xc, int M, double* Kt, int ldk, double* mu_part,
-                   double* t_part, int q_per_split, int n_split, bool with_lam, hipStream_t s) {
+                   double* t_part, int q_per_split, int n_split, bool with_lam, hipStream_t s, int edge_k0 = -1) {
   const KernParams p = make_kern_params(m->kernel_id, m->theta);
   switch (m->kernel_id) {
-    case PPBO_KERNEL_SE: return launch_kstar<PPBO_KERNEL_SE>(m, p, d_Xc, M, Kt, ldk, mu_part, t_part, q_per_split, n_split, with_lam, s);
-    case PPBO_KERNEL_RQ: return launch_kstar<PPBO_KERNEL_RQ>(m, p, d_Xc, M, Kt, ldk, mu_part, t_part, q_per_split, n_split, with_lam, s);
-    case PPBO_KERNEL_CAMPHOR: return launch_kstar<PPBO_KERNEL_CAMPHOR>(m, p, d_Xc, M, Kt, ldk, mu_part, t_part, q_per_split, n_split, with_lam, s);
-    case PPBO_KERNEL_MATERN52: return launch_kstar<PPBO_KERNEL_MATERN52>(m, p, d_Xc, M, Kt, ldk, mu_part, t_part, q_per_split, n_split, with_lam, s);
-    case PPBO_KERNEL_MATERN32: return launch_kstar<PPBO_KERNEL_MATERN32>(m, p, d_Xc, M, Kt, ldk, mu_part, t_part, q_per_split, n_split, with_lam, s);
+    case PPBO_KERNEL_SE: return launch_kstar<PPBO_KERNEL_SE>(m, p, d_Xc, M, Kt, ldk, mu_part, t_part, q_per_split, n_split, with_lam, edge_k0, s);
+    case PPBO_KERNEL_RQ: return launch_kstar<PPBO_KERNEL_RQ>(m, p, d_Xc, M, Kt, ldk, mu_part, t_part, q_per_split, n_split, with_lam, edge_k0, s);
+    case PPBO_KERNEL_CAMPHOR: return launch_kstar<PPBO_KERNEL_CAMPHOR>(m, p, d_Xc, M, Kt, ldk, mu_part, t_part, q_per_split, n_split, with_lam, edge_k0, s);
+    case PPBO_KERNEL_MATERN52: return launch_kstar<PPBO_KERNEL_MATERN52>(m, p, d_Xc, M, Kt, ldk, mu_part, t_part, q_per_split, n_split, with_lam, edge_k0, s);
+    case PPBO_KERNEL_MATERN32: return launch_kstar<PPBO_KERNEL_MATERN32>(m, p, d_Xc, M, Kt, ldk, mu_part, t_part, q_per_split, n_split, with_lam, edge_k0, s);
     default: return -1;   // (check_model rejects any other id first)
   }
 }
@@ -897,7 +952,9 @@ static int predict_passes(ppbo_ctx* ctx, const ppbo_model* model, const double* 
                "variance / EI scores need model->d_G");
   PPBO_REQUIRE(ctx, !want_var || (model->d_lam_diag && model->d_lam_off), "model Lambda");
   const int N = model->N, mblk = model->m + 1, n_q = N / mblk;
-  if (want_var && ppbo_fused_eligible(ctx, model)) {
+  // an edge-form operator is always contracted by the three-launch form (the one-launch kernel reads node-form G)
+  const int edge_k0 = (want_var && ctx->op_edge) ? ppbo_edge_k0(n_q) : -1;
+  if (want_var && edge_k0 < 0 && ppbo_fused_eligible(ctx, model)) {
     // Models of up to 1024 rows: ONE launch forms K* in LDS, contracts it with G on the matrix cores and scores
     // (fused.hip) -- no K* in HBM, no slab pass, no candidate chunks -- then the one-workgroup argmax.  The choice
     // depends on the model only: a shard of a sharded search scores a candidate exactly as the unsharded search does.
@@ -970,12 +1027,12 @@ static int predict_passes(ppbo_ctx* ctx, const ppbo_model* model, const double* 
     double* slab = part + (size_t)2 * n_split_eff * Mc;
     {
       PpboProfScope pf(ctx, ppbo_ctx::PF_KSTAR, s);
-      dispatch_kstar(model, xc, Mc, Kt, ldk, mu_part, t_part, q_per_split, n_split_eff, want_var, s);
+      dispatch_kstar(model, xc, Mc, Kt, ldk, mu_part, t_part, q_per_split, n_split_eff, want_var, s, edge_k0);
     }
     PPBO_LAUNCH_CHECK(ctx);
     if (want_var) {
       PpboProfScope pf(ctx, ppbo_ctx::PF_QUADFORM, s);
-      if (int rc = dispatch_quadform(ctx, Gq, Nk, g_rows, N, Kt, ldk, Mc, mblk, slab, s)) return rc;
+      if (int rc = dispatch_quadform(ctx, Gq, Nk, g_rows, N, Kt, ldk, Mc, mblk, slab, edge_k0, s)) return rc;
     }
     const int sblocks = score_blocks(Mc);
     PpboProfScope pfs(ctx, ppbo_ctx::PF_SCORE, s);
@@ -1085,10 +1142,15 @@ int ppbo_predict_cov(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc,
   g.A = Kt; g.lda = ld; g.B = Z; g.ldb = ld; g.C = d_cov; g.ldc = M;
   g.M = M; g.N = M; g.K = N; g.alpha = 1.0; g.beta = 1.0; g.tri_block = 1;
   if (int rc = ppbo_gemm_launch(ctx, g, 1, 0, s)) return rc;
-  // + (G K*)' (G K*)
+  // + (G K*)' (G K*); edge form: (H E)' (H E), E (in Z, whose product above is enqueued first) the edge-layout K*
   GemmArgs y{};
   y.A = model->d_G; y.lda = N; y.B = Kt; y.ldb = ld; y.C = Y; y.ldc = ld;
   y.M = N; y.N = M; y.K = N; y.alpha = 1.0; y.beta = 0.0; y.khi_mode = 1; y.tri_block = mblk;
+  if (ctx->op_edge) {
+    edge_apply_kernel<<<dim3((M + 127) / 128, N), 128, 0, s>>>(Kt, ld, M, mblk, n_q, model->d_lam_off, Z);
+    PPBO_LAUNCH_CHECK(ctx);
+    y.B = Z; y.tri_block = 1;    // H lower triangular
+  }
   if (int rc = ppbo_gemm_launch(ctx, y, 0, 0, s)) return rc;
   GemmArgs c{};
   c.A = Y; c.lda = ld; c.B = Y; c.ldb = ld; c.C = d_cov; c.ldc = M;
@@ -1133,11 +1195,15 @@ int line_acq_impl(ppbo_ctx* ctx, const ppbo_model* model, const double* d_grid, 
   if (!Gq) return (int)hipErrorOutOfMemory;
   PPBO_LAUNCH_CHECK(ctx);
   const int ld = ((Bc_max * G) + 127) & ~127;
-  double* ws = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_KSTAR, (size_t)(Nk + g_rows) * ld * sizeof(double));
+  // edge form: Y = H E with E the edge-layout K* beside the node-layout one (which the mean and K*' Lambda K* read)
+  const bool edge = ctx->op_edge != 0;
+  double* ws = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_KSTAR, (size_t)((edge ? 2 : 1) * Nk + g_rows) * ld * sizeof(double));
   if (!ws) return (int)hipErrorOutOfMemory;
   double* Kt = ws;
   double* Y = ws + (size_t)Nk * ld;
+  double* Ke = edge ? Y + (size_t)g_rows * ld : nullptr;
   if (Nk != N) PPBO_HIP_CHECK(ctx, hipMemsetAsync(Kt + (size_t)N * ld, 0, (size_t)(Nk - N) * ld * sizeof(double), s));
+  if (edge && Nk != N) PPBO_HIP_CHECK(ctx, hipMemsetAsync(Ke + (size_t)N * ld, 0, (size_t)(Nk - N) * ld * sizeof(double), s));
   double* gridws = nullptr;
   if (!d_grid) {
     gridws = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_SEARCH, (size_t)Bc_max * G * D * sizeof(double));
@@ -1207,6 +1273,11 @@ int line_acq_impl(ppbo_ctx* ctx, const ppbo_model* model, const double* d_grid, 
     GemmArgs y{};  // Y = G K*
     y.A = Gq; y.lda = Nk; y.B = Kt; y.ldb = ld; y.C = Y; y.ldc = ld;
     y.M = g_rows; y.N = (M + 127) & ~127; y.K = Nk; y.alpha = 1.0; y.beta = 0.0; y.khi_mode = 1; y.tri_block = mblk;
+    if (edge) {
+      edge_apply_kernel<<<dim3((M + 127) / 128, N), 128, 0, s>>>(Kt, ld, M, mblk, n_q, model->d_lam_off, Ke);
+      PPBO_LAUNCH_CHECK(ctx);
+      y.B = Ke; y.tri_block = 1;   // H lower triangular
+    }
     // (rows [N, g_rows) of Y come out as zeros, columns [M, y.N) as whatever the K* padding holds: neither is read)
     // column tiles in chunks through all row tiles, heaviest first (a chunk's slice of K* -- 134 MB at 64 tiles -- stays
     // in the Infinity Cache); equal chunks of at most 72 tiles: a ragged last chunk costs 5 % (512 lines: 280 tiles in
@@ -1274,6 +1345,41 @@ int ppbo_line_acq_xi(ppbo_ctx* ctx, const ppbo_model* model, const double* d_xi,
   PPBO_REQUIRE(ctx, d_xi && d_x && d_alpha, "xi / x / alpha");
   return line_acq_impl(ctx, model, nullptr, d_xi, d_x, d_alpha, alpha_per_line != 0, B, G, shrink, d_z, S, mustar,
                        jitter, d_ei, d_varmax, (hipStream_t)stream);
+}
+
+// the same entry points for a model whose d_G holds an edge-form operator (ppbo_posterior_edge)
+int ppbo_predict_edge(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc, int64_t M, int score_kind,
+                      double mustar, double* d_mu, double* d_var, double* d_score, double* h_best_val,
+                      int64_t* h_best_idx, void* stream) {
+  PpboEdgeScope es(ctx);
+  return ppbo_predict(ctx, model, d_Xc, M, score_kind, mustar, d_mu, d_var, d_score, h_best_val, h_best_idx, stream);
+}
+
+int ppbo_predict_record_edge(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc, int64_t M, int score_kind,
+                             double mustar, int64_t index_offset, double* d_record, void* stream) {
+  PpboEdgeScope es(ctx);
+  return ppbo_predict_record(ctx, model, d_Xc, M, score_kind, mustar, index_offset, d_record, stream);
+}
+
+int ppbo_predict_cov_edge(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc, int M, double shrink,
+                          double* d_mu, double* d_cov, void* stream) {
+  PpboEdgeScope es(ctx);
+  return ppbo_predict_cov(ctx, model, d_Xc, M, shrink, d_mu, d_cov, stream);
+}
+
+int ppbo_line_acq_edge(ppbo_ctx* ctx, const ppbo_model* model, const double* d_grid, int B, int G, double shrink,
+                       const double* d_z, int S, double mustar, double jitter, double* d_ei, double* d_varmax,
+                       void* stream) {
+  PpboEdgeScope es(ctx);
+  return ppbo_line_acq(ctx, model, d_grid, B, G, shrink, d_z, S, mustar, jitter, d_ei, d_varmax, stream);
+}
+
+int ppbo_line_acq_xi_edge(ppbo_ctx* ctx, const ppbo_model* model, const double* d_xi, const double* d_x,
+                          const double* d_alpha, int alpha_per_line, int B, int G, double shrink, const double* d_z,
+                          int S, double mustar, double jitter, double* d_ei, double* d_varmax, void* stream) {
+  PpboEdgeScope es(ctx);
+  return ppbo_line_acq_xi(ctx, model, d_xi, d_x, d_alpha, alpha_per_line, B, G, shrink, d_z, S, mustar, jitter, d_ei,
+                          d_varmax, stream);
 }
 
 int ppbo_randn(ppbo_ctx* ctx, uint64_t seed, double* d_out, int64_t n, void* stream) {

@@ -86,6 +86,8 @@ class ShardedSearch:
         from .engine import SCORE_MEAN, _ptr
         self._md = engine._model(post, score != SCORE_MEAN)
         self._md_ref = _C.byref(self._md)
+        self._search_fn = engine._entry("ppbo_search_sharded", post)    # the entry points for the posterior's form
+        self._record_fn = engine._entry("ppbo_predict_record", post)
         self._xc_ptr, self._M = _ptr(self.Xc), int(self.Xc.shape[0])
         self._bv, self._bi = _C.c_double(0.0), _C.c_int64(-1)
         self._bv_ref, self._bi_ref = _C.byref(self._bv), _C.byref(self._bi)
@@ -109,11 +111,11 @@ class ShardedSearch:
         # a stream synchronisation for 16 bytes (~10 us of a 120 us step at C2)
         single = self.world == 1 and not self.host and not (dist.is_available() and dist.is_initialized())
         if (self.collective == "capi" or single) and not self.host:
-            rc = eng.lib.ppbo_search_sharded(eng.ctx, self._md_ref, self._xc_ptr, self._M, int(self.score), self.mustar,
+            rc = self._search_fn(eng.ctx, self._md_ref, self._xc_ptr, self._M, int(self.score), self.mustar,
                                              self.offset, self._bv_ref, self._bi_ref, eng._stream())
             eng._check(rc, "ppbo_search_sharded")
             return self._bv.value, self._bi.value
-        rc = eng.lib.ppbo_predict_record(eng.ctx, self._md_ref, self._xc_ptr, self._M, int(self.score), self.mustar,
+        rc = self._record_fn(eng.ctx, self._md_ref, self._xc_ptr, self._M, int(self.score), self.mustar,
                                          self.offset, self._rec_ptr, eng._stream())
         eng._check(rc, "ppbo_predict_record")
         if self.world == 1 and not dist.is_initialized():
@@ -183,11 +185,15 @@ def assert_same_across_ranks(values, what: str, device=None, group=None):
 def broadcast_posterior(post, src: int = 0, group=None):
     """SURVEY 2.1 C2 / 8(e), the alternative to replicated fits: the rank `src` has fitted the model, every other rank
     holds a Posterior of the same shapes (e.g. from torch.empty_like) and receives alpha, Lambda_MAP (star form) and G
-    by ONE broadcast each (RCCL over xGMI: 8 N^2 bytes for G, 33.5 MB at N = 2048).  In place; returns post."""
+    by ONE broadcast each (RCCL over xGMI: 8 N^2 bytes for G, 33.5 MB at N = 2048), and the form G is in (node / edge).
+    In place; returns post."""
     if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
         return post
     for t in (post.alpha, post.lam_diag, post.lam_off, post.G):
         if t is not None:
             dist.broadcast(t, src=src, group=group)
+    form = torch.tensor([float(post.form)], dtype=torch.float64, device=post.alpha.device)
+    dist.broadcast(form, src=src, group=group)
+    post.form = int(form.item())
     post.Gt = None            # the cached transpose of G (engine._model) belongs to the old contents
     return post

@@ -11,6 +11,10 @@ import torch
 from . import _lib
 from ._lib import KERNEL_IDS, SCORE_MEAN, SCORE_POINTWISE_EI, SCORE_VARIANCE, PPBO_ERR_NOT_PD  # noqa: F401
 
+# Posterior.form: which variance operator G holds (include/ppbo_hip.h, PPBO_FORM_*)
+FORM_NODE = 0   # G = R Lambda, block lower triangular [N, N]
+FORM_EDGE = 1   # H = L22^-1 of the edge-coordinate factor, rows / columns [n_q, N) (ppbo_posterior_edge)
+
 SHRINKAGE = 1e-6  # COVARIANCE_SHRINKAGE of the reference (gp_model.py:26)
 
 # ARD (one length scale per input dimension, no reference counterpart) is defined for these: for a radial kernel
@@ -87,12 +91,13 @@ class Posterior:
     alpha: torch.Tensor      # [N]   Sigma^-1 f_MAP
     lam_diag: torch.Tensor   # [N]   Lambda_MAP (star form)
     lam_off: torch.Tensor    # [N]
-    G: torch.Tensor | None   # [N, N] R Lambda
+    G: torch.Tensor | None   # [N, N] the variance operator: R Lambda (form FORM_NODE) or H (FORM_EDGE)
     P: torch.Tensor | None = None  # posterior covariance (optional)
     Gt: torch.Tensor | None = None  # transpose of G in the one-launch scoring kernel's layout (formed on first use)
     scale: np.ndarray | None = None  # ARD: s_d = 1 / l_d (None: a scalar length scale)
     camphor: np.ndarray | None = None  # camphor_copper_ard_kernel: l_0..l_5; X then holds the embedded rows [N, 11]
     Xc: torch.Tensor | None = None     # ... and this the caller's rows [N, 6] (mu_star searches in their coordinates)
+    form: int = FORM_NODE              # FORM_NODE / FORM_EDGE: how G is to be read (the *_edge entry points take FORM_EDGE)
 
     @property
     def embedded(self):
@@ -240,7 +245,7 @@ class Engine:
         md.d_G = post.G.data_ptr() if (with_var and post.G is not None) else 0
         md.kstar_fp32 = int(bool(kstar_fp32))
         md.d_Gt = 0
-        if md.d_G and N <= 1024 and post.kernel != "camphor_copper_kernel":
+        if md.d_G and post.form == FORM_NODE and N <= 1024 and post.kernel != "camphor_copper_kernel":
             # models the one-launch scoring kernel takes: its matrix-core loop reads G transposed -- formed ONCE per
             # posterior here (the library would otherwise do it in a workspace on every call)
             if post.Gt is None or post.Gt.device != post.G.device:
@@ -250,6 +255,18 @@ class Engine:
                 torch.cuda.current_stream(self.device).synchronize()
             md.d_Gt = post.Gt.data_ptr()
         return md
+
+    def _entry(self, name, post):
+        """The library entry point `name` for post's operator form (its *_edge namesake for FORM_EDGE)."""
+        return getattr(self.lib, name + "_edge" if post.form == FORM_EDGE else name)
+
+    def posterior_form(self, kernel, N, D, m):
+        """The operator form to build for a model of this shape (ppbo_posterior_form): FORM_NODE where the one-launch
+        scoring kernel takes the model, FORM_EDGE elsewhere.  D: the device's row width (embedded rows for camphor)."""
+        rc = self.lib.ppbo_posterior_form(self.ctx, self._kid(kernel), int(N), int(D), int(m))
+        if rc < 0:
+            self._check(rc, "ppbo_posterior_form")
+        return rc
 
     def transposed_G(self, G):
         """G [N, N] -> its transpose in the layout of ppbo_model.d_Gt (ppbo_transposed_G)."""
@@ -303,8 +320,8 @@ class Engine:
         Xc = self._points(post, Xc)
         md = self._model(post, score != SCORE_MEAN, kstar_fp32)
         rec = self.empty(2) if out is None else out
-        rc = self.lib.ppbo_predict_record(self.ctx, C.byref(md), _ptr(Xc), Xc.shape[0], int(score), float(mustar),
-                                          int(index_offset), _ptr(rec), self._stream())
+        rc = self._entry("ppbo_predict_record", post)(self.ctx, C.byref(md), _ptr(Xc), Xc.shape[0], int(score),
+                                                      float(mustar), int(index_offset), _ptr(rec), self._stream())
         self._check(rc, "ppbo_predict_record")
         return rec
 
@@ -317,8 +334,9 @@ class Engine:
         Xc = self._points(post, Xc)
         md = self._model(post, score != SCORE_MEAN, kstar_fp32)
         bv, bi = C.c_double(0.0), C.c_int64(-1)
-        rc = self.lib.ppbo_search_sharded(self.ctx, C.byref(md), _ptr(Xc), Xc.shape[0], int(score), float(mustar),
-                                          int(index_offset), C.byref(bv), C.byref(bi), self._stream())
+        rc = self._entry("ppbo_search_sharded", post)(self.ctx, C.byref(md), _ptr(Xc), Xc.shape[0], int(score),
+                                                      float(mustar), int(index_offset), C.byref(bv), C.byref(bi),
+                                                      self._stream())
         self._check(rc, "ppbo_search_sharded")
         return bv.value, bi.value
 
@@ -557,17 +575,20 @@ class Engine:
         return out, stats
 
     def gp_fit(self, X, theta, kernel, m, f_init, shrink=SHRINKAGE, gtol=1e-4, maxiter=0, verbose=0, lbfgs_max_evals=0,
-               start_is_whitened=False, want_Sigma=True, want_Linv=False, want_posterior=True):
+               start_is_whitened=False, want_Sigma=True, want_Linv=False, want_posterior=True, form=None):
         """One whole GP fit in one library call (ppbo_gp_fit): Sigma, its Cholesky factor and inverse, f_MAP from one
         start by the whitened search, and the posterior state -- the work of update_Sigma + update_Sigma_inv +
         update_fMAP + the posterior (src/gp_model.py:91-117), everything enqueued behind each other on one stream with
         ONE host wait.  start_is_whitened: f_init holds z0 and the start is the prior draw L z0.
         Returns dict(Sigma, Sigma_inv, L, Linv, fMAP, post, stats, info); info = 2 (with post = None) when
-        Sigma^-1 - Lambda_MAP is not positive definite (raises NotPositiveDefinite when Sigma itself is not)."""
+        Sigma^-1 - Lambda_MAP is not positive definite (raises NotPositiveDefinite when Sigma itself is not).
+        form: the posterior's operator form (None: posterior_form's choice for this shape)."""
         key = theta_key(theta)
         cam = self._camphor_fields(X, theta, kernel)
         X, theta, scale = self._ard(X, theta, kernel)
         N, D = X.shape
+        if form is None:
+            form = self.posterior_form(kernel, N, D, m)
         f0 = self.dev(f_init).reshape(-1)
         if f0.numel() != N:
             raise ValueError(f"gp_fit: the start vector has {f0.numel()} entries, the design {N} rows")
@@ -582,33 +603,39 @@ class Engine:
         opts = _lib.FitOpts(float(gtol), int(maxiter), int(verbose), 0.0, int(lbfgs_max_evals), 0, int(bool(start_is_whitened)))
         st = _lib.FitStats()
         info = C.c_int(0)
-        rc = self.lib.ppbo_gp_fit(self.ctx, self._kid(kernel), _ptr(X), N, D, self._theta(theta), float(shrink), int(m),
+        fit_fn = self.lib.ppbo_gp_fit_edge if form == FORM_EDGE else self.lib.ppbo_gp_fit
+        rc = fit_fn(self.ctx, self._kid(kernel), _ptr(X), N, D, self._theta(theta), float(shrink), int(m),
                                   _ptr(f0), C.byref(opts), _ptr(Sigma), _ptr(Sinv), _ptr(L), _ptr(Linv), _ptr(fmap),
                                   _ptr(alpha), _ptr(ld), _ptr(lo), _ptr(G), C.byref(st), C.byref(info), self._stream())
         if rc == PPBO_ERR_NOT_PD and info.value == 2:
             post = None
         else:
             self._check(rc, "ppbo_gp_fit", info.value)
-            post = Posterior(kernel, key, m, X, alpha, ld, lo, G, None, scale=scale, **cam) if want_posterior else None
+            post = Posterior(kernel, key, m, X, alpha, ld, lo, G, None, scale=scale, form=form,
+                             **cam) if want_posterior else None
         stats = dict(iterations=st.iterations, n_cholesky=st.n_cholesky, converged=bool(st.converged), T=st.T,
                      gradnorm=st.gradnorm, lbfgs_iterations=st.lbfgs_iterations, lbfgs_evals=st.lbfgs_evals,
                      lbfgs_status=st.lbfgs_status)
         return dict(Sigma=Sigma, Sigma_inv=Sinv, L=L, Linv=Linv, fMAP=fmap, post=post, stats=stats, info=info.value)
 
-    def posterior(self, X, theta, kernel, Sigma_inv, fMAP, m, want_P=False) -> Posterior:
+    def posterior(self, X, theta, kernel, Sigma_inv, fMAP, m, want_P=False, form=None) -> Posterior:
+        """form: FORM_NODE / FORM_EDGE, None: posterior_form's choice for this shape."""
         key = theta_key(theta)
         cam = self._camphor_fields(X, theta, kernel)
         X, _, scale = self._ard(X, theta, kernel)
         f = self.dev(fMAP).reshape(-1)
         N = f.numel()
+        if form is None:
+            form = self.posterior_form(kernel, N, X.shape[1], m)
         alpha, ld, lo = self.empty(N), self.empty(N), self.empty(N)
         G = self.empty(N, N)
         P = self.empty(N, N) if want_P else None
         info = C.c_int(0)
-        rc = self.lib.ppbo_posterior(self.ctx, _ptr(Sigma_inv), _ptr(f), N, m, float(theta[0]), _ptr(alpha), _ptr(ld),
-                                     _ptr(lo), _ptr(G), _ptr(P), C.byref(info), self._stream())
+        post_fn = self.lib.ppbo_posterior_edge if form == FORM_EDGE else self.lib.ppbo_posterior
+        rc = post_fn(self.ctx, _ptr(Sigma_inv), _ptr(f), N, m, float(theta[0]), _ptr(alpha), _ptr(ld),
+                     _ptr(lo), _ptr(G), _ptr(P), C.byref(info), self._stream())
         self._check(rc, "ppbo_posterior", info.value)
-        return Posterior(kernel, key, m, X, alpha, ld, lo, G, P, scale=scale, **cam)
+        return Posterior(kernel, key, m, X, alpha, ld, lo, G, P, scale=scale, form=form, **cam)
 
     # ---- prediction ---------------------------------------------------------------
     def predict(self, post: Posterior, Xc, score=SCORE_MEAN, mustar=0.0, want_mu=True, want_var=True,
@@ -621,8 +648,8 @@ class Engine:
         var = self.empty(M) if (want_var and with_var) else None
         sc = self.empty(M) if want_score else None
         bv, bi = C.c_double(0.0), C.c_int64(-1)
-        rc = self.lib.ppbo_predict(self.ctx, C.byref(md), _ptr(Xc), M, int(score), float(mustar), _ptr(mu), _ptr(var),
-                                   _ptr(sc), C.byref(bv) if want_best else None, C.byref(bi) if want_best else None,
+        rc = self._entry("ppbo_predict", post)(self.ctx, C.byref(md), _ptr(Xc), M, int(score), float(mustar), _ptr(mu),
+                                               _ptr(var), _ptr(sc), C.byref(bv) if want_best else None, C.byref(bi) if want_best else None,
                                    self._stream())
         self._check(rc, "ppbo_predict")
         return dict(mu=mu, var=var, score=sc, best_val=bv.value, best_idx=bi.value)
@@ -632,8 +659,8 @@ class Engine:
         M = Xc.shape[0]
         md = self._model(post, True)
         mu, cov = self.empty(M), self.empty(M, M)
-        rc = self.lib.ppbo_predict_cov(self.ctx, C.byref(md), _ptr(Xc), M, float(shrink), _ptr(mu), _ptr(cov),
-                                       self._stream())
+        rc = self._entry("ppbo_predict_cov", post)(self.ctx, C.byref(md), _ptr(Xc), M, float(shrink), _ptr(mu),
+                                                   _ptr(cov), self._stream())
         self._check(rc, "ppbo_predict_cov")
         return mu, cov
 
@@ -778,8 +805,8 @@ class Engine:
         S = z.shape[0]
         md = self._model(post, True)
         ei, vm = self.empty(B), self.empty(B)
-        rc = self.lib.ppbo_line_acq(self.ctx, C.byref(md), _ptr(grid), B, G, float(shrink), _ptr(z), S, float(mustar),
-                                    float(jitter), _ptr(ei), _ptr(vm), self._stream())
+        rc = self._entry("ppbo_line_acq", post)(self.ctx, C.byref(md), _ptr(grid), B, G, float(shrink), _ptr(z), S,
+                                                float(mustar), float(jitter), _ptr(ei), _ptr(vm), self._stream())
         self._check(rc, "ppbo_line_acq")
         return ei, vm
 
@@ -807,16 +834,16 @@ class Engine:
             S = z.shape[0]
             md = self._model(post, True)
             ei, vm = self.empty(B), self.empty(B)
-            rc = self.lib.ppbo_line_acq(self.ctx, C.byref(md), _ptr(grid), B, G, float(shrink), _ptr(z), S, float(mustar),
-                                        float(jitter), _ptr(ei), _ptr(vm), self._stream())
+            rc = self._entry("ppbo_line_acq", post)(self.ctx, C.byref(md), _ptr(grid), B, G, float(shrink), _ptr(z), S,
+                                                    float(mustar), float(jitter), _ptr(ei), _ptr(vm), self._stream())
             self._check(rc, "ppbo_line_acq")
             return ei, vm
         xis, xs = self._points(post, xis), self._points(post, xs)
         S = z.shape[0]
         md = self._model(post, True)
         ei, vm = self.empty(B), self.empty(B)
-        rc = self.lib.ppbo_line_acq_xi(self.ctx, C.byref(md), _ptr(xis), _ptr(xs), _ptr(alphas), int(per_line), B, G,
-                                       float(shrink), _ptr(z), S, float(mustar), float(jitter), _ptr(ei), _ptr(vm),
+        rc = self._entry("ppbo_line_acq_xi", post)(self.ctx, C.byref(md), _ptr(xis), _ptr(xs), _ptr(alphas),
+                                                   int(per_line), B, G, float(shrink), _ptr(z), S, float(mustar), float(jitter), _ptr(ei), _ptr(vm),
                                        self._stream())
         self._check(rc, "ppbo_line_acq_xi")
         return ei, vm
