@@ -472,6 +472,16 @@ PPBO_API int ppbo_rff_search(ppbo_ctx* ctx, const double* d_cand, int64_t M, int
                     const double* d_b, double sigma_f, const double* d_omega, int K, double sep, int iters,
                     double tol, double* d_x, double* d_val, int* h_found, void* stream);
 
+/* ppbo_rff_search for a camphor-copper basis (camphor_copper_kernel, camphor_copper_ard_kernel): the features live on
+ * the embedded point e(x) in R^11 of the camphor section above, phi(x) = sqrt(2 sf^2 / F) cos(W e(x) + b) with
+ * d_W[F,11], and the search runs in the caller's six coordinates.  d_cand[M,6] are embedded (ppbo_camphor_embed) and
+ * scored (ppbo_rff_score); the starts are chosen on d_cand, so sep is in the caller's units; each ascent forms e(x)
+ * and pulls the gradient back through de/dx (2 pi (c_d g_s - s_d g_c) for a periodic d, g_z / l_2 for z).
+ * h_l[6]: the length scales (the scalar kernel: l, l, l + 0.05, l, l, l).  d_x[K,6] / d_val[K] as ppbo_rff_search. */
+PPBO_API int ppbo_rff_search_camphor(ppbo_ctx* ctx, const double* d_cand, int64_t M, const double* h_l, const double* d_W,
+                    int F, const double* d_b, double sigma_f, const double* d_omega, int K, double sep, int iters,
+                    double tol, double* d_x, double* d_val, int* h_found, void* stream);
+
 /* ---- generic fp64 MFMA GEMM (exposed for tests and host-side composition) ----
  * C[M,N] = alpha op(A) op(B) + beta C.  transA/transB: 0 = as stored, 1 = transposed. */
 PPBO_API int ppbo_dgemm(ppbo_ctx* ctx, int transA, int transB, int M, int N, int K, double alpha,

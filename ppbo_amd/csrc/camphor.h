@@ -1,6 +1,6 @@
 // The camphor-copper kernel with one length scale per coordinate (include/ppbo_hip.h): SE with l = 1 on the embedded
 // rows e(x) in R^11, column order (c0, s0, c1, s1, z, c3, s3, c4, s4, c5, s5).  Shared by camphor.hip (embedding, line
-// points, mean gradient) and meangrad.hip (mu_star in the caller's coordinates).
+// points, mean gradient) and meangrad.hip (mu_star and the RFF search in the caller's coordinates).
 #pragma once
 #include "common.h"
 
@@ -31,6 +31,22 @@ static inline CamphorCoef camphor_coef(const double* h_l) {
   for (int d = 0; d < CAMPHOR_D; ++d) c.k[d] = (d == 2 ? 0.5 : 2.0) / (h_l[d] * h_l[d]);
   return c;
 }
+
+namespace {
+// L.v[d] for a lane-dependent d without dynamic indexing of a by-value argument (which would go through scratch)
+__device__ __forceinline__ double camphor_pick(const CamphorInvL& L, int d) {
+  return d == 0 ? L.v[0] : d == 1 ? L.v[1] : d == 2 ? L.v[2] : d == 3 ? L.v[3] : d == 4 ? L.v[4] : L.v[5];
+}
+
+// the embedded columns of coordinate d of one point with value v
+__device__ __forceinline__ void camphor_embed_one(double v, int d, const CamphorInvL& L, double* __restrict__ row) {
+  const double il = camphor_pick(L, d);
+  double* o = row + camphor_col(d);
+  if (d == 2) { o[0] = v * il; return; }
+  o[0] = cospi(2.0 * v) * il;
+  o[1] = sinpi(2.0 * v) * il;
+}
+}  // namespace
 
 // h_l: six positive finite length scales; a model: SE at D = 11 (embedded rows, theta = [sigma, 1, sigma_f])
 #define PPBO_REQUIRE_CAMPHOR_L(ctx, h_l) \

@@ -21,20 +21,6 @@ inline bool camphor_overlap(const double* a, long long na, const double* b, long
   return a < b + nb && b < a + na;
 }
 
-// L.v[d] for a lane-dependent d without dynamic indexing of a by-value argument (which would go through scratch)
-__device__ __forceinline__ double camphor_pick(const CamphorInvL& L, int d) {
-  return d == 0 ? L.v[0] : d == 1 ? L.v[1] : d == 2 ? L.v[2] : d == 3 ? L.v[3] : d == 4 ? L.v[4] : L.v[5];
-}
-
-// the embedded columns of coordinate d of one point with value v
-__device__ __forceinline__ void camphor_embed_one(double v, int d, const CamphorInvL& L, double* __restrict__ row) {
-  const double il = camphor_pick(L, d);
-  double* o = row + camphor_col(d);
-  if (d == 2) { o[0] = v * il; return; }
-  o[0] = cospi(2.0 * v) * il;
-  o[1] = sinpi(2.0 * v) * il;
-}
-
 __global__ __launch_bounds__(256) void camphor_embed_kernel(const double* __restrict__ in, int64_t n, CamphorInvL L,
                                                             double* __restrict__ out) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;     // i = row * 6 + d

@@ -467,6 +467,30 @@ struct CamphorMeanEval {
   }
 };
 
+// the per-feature body of a posterior sample in weight space, shared by RffEval and CamphorRffEval (a macro, so that
+// RffEval compiles to the instruction stream it had as a loop body of its own): with W (the transposed basis [D][F]),
+// F, D, b, omega, amp, P, the point xc[NC] and the accumulators m, g[NC] in scope, feature f's phase, its cosine into m
+// and its sine times w_f into g
+#define RFF_FEATURE_BODY(NC)                                                                                   \
+  {                                                                                                            \
+    const double* __restrict__ wf = W + f;                 /* coalesced per coordinate */                      \
+    double wv[NC], ph = b[f];                                                                                  \
+    _Pragma("unroll") for (int d = 0; d < NC; ++d) { wv[d] = (d < D) ? wf[(size_t)d * F] : 0.0; ph = fma(wv[d], xc[d], ph); } \
+    /* cos and sin = cos(. - pi/2) by the branch-free polynomial of the RFF kernels (2 x 20 instructions against a  \
+       library sincos with its own range reduction); phases beyond its range take the library path */          \
+    double sn, cs;                                                                                             \
+    if (fabs(ph) < 0.5 * RFF_COS_FAST_RANGE) {                                                                 \
+      cs = rff_cos_fast(ph, P);                                                                                \
+      sn = rff_cos_fast(ph - 1.57079632679489661923, P);                                                       \
+    } else {                                                                                                   \
+      sincos(ph, &sn, &cs);                                                                                    \
+    }                                                                                                          \
+    const double om = amp * omega[f];                                                                          \
+    m = fma(om, cs, m);                                                                                        \
+    const double c = -om * sn;                                                                                 \
+    _Pragma("unroll") for (int d = 0; d < NC; ++d) g[d] = fma(c, wv[d], g[d]);                                 \
+  }
+
 // one posterior sample of the utility in weight space (random_fourier_sampler.py:45-53,166):
 //   f(x) = a sum_f omega_f cos(w_f.x + b_f),   grad f = -a sum_f omega_f sin(w_f.x + b_f) w_f,   a = sqrt(2 sf^2 / F)
 template <int DP, int NT>
@@ -477,26 +501,7 @@ struct RffEval {
 #pragma unroll
     for (int d = 0; d < DP; ++d) { xc[d] = sx[d]; g[d] = 0.0; }
     double m = 0.0;
-    for (int f = threadIdx.x; f < F; f += NT) {
-      const double* __restrict__ wf = W + f;                 // W: the transposed basis [D][F] (coalesced per coordinate)
-      double wv[DP], ph = b[f];
-#pragma unroll
-      for (int d = 0; d < DP; ++d) { wv[d] = (d < D) ? wf[(size_t)d * F] : 0.0; ph = fma(wv[d], xc[d], ph); }
-      // cos and sin = cos(. - pi/2) by the branch-free polynomial of the RFF kernels (2 x 20 instructions against a
-      // library sincos with its own range reduction); phases beyond its range take the library path
-      double sn, cs;
-      if (fabs(ph) < 0.5 * RFF_COS_FAST_RANGE) {
-        cs = rff_cos_fast(ph, P);
-        sn = rff_cos_fast(ph - 1.57079632679489661923, P);
-      } else {
-        sincos(ph, &sn, &cs);
-      }
-      const double om = amp * omega[f];
-      m = fma(om, cs, m);
-      const double c = -om * sn;
-#pragma unroll
-      for (int d = 0; d < DP; ++d) g[d] = fma(c, wv[d], g[d]);
-    }
+    for (int f = threadIdx.x; f < F; f += NT) RFF_FEATURE_BODY(DP)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     m = row16_sum_dpp(m);
 #pragma unroll
@@ -506,6 +511,47 @@ struct RffEval {
       r[DP] = m;
 #pragma unroll
       for (int d = 0; d < DP; ++d) r[d] = g[d];
+    }
+  }
+};
+
+// one camphor-copper posterior sample in the caller's coordinates (ppbo_rff_search_camphor): the basis lives on the
+// embedded point e(x) in R^11 (camphor.h), f(x) = a sum_f omega_f cos(w_f.e(x) + b_f).  The threads of wavefront 0
+// form e(sx) once per evaluation in LDS (camphor_embed_one: the bits ppbo_camphor_embed writes), every thread runs
+// RffEval's per-feature body (RFF_FEATURE_BODY) over its features at D = 11 and pulls its partial gradient back through de/dx before
+// the same fixed-order reductions: d f / d x_d = 2 pi (c_d g_s - s_d g_c) for a periodic d, g_z / l_2 for z.
+// The records are RffEval's at DP = 8 (six live coordinates).
+template <int NT>
+struct CamphorRffEval {
+  static constexpr int DP = 8, DE = CAMPHOR_E;             // records of 8 columns; 11 embedded columns
+  const double* W; int F; const double* b; const double* omega; double amp; RffPoly P;   // W: transposed [11][F]
+  CamphorInvL L;
+  __device__ __forceinline__ void operator()(const double* sx, double (*red)[DP + 1]) const {
+    __shared__ double se[DE];
+    if (threadIdx.x < CAMPHOR_D) camphor_embed_one(sx[threadIdx.x], (int)threadIdx.x, L, se);
+    __syncthreads();
+    constexpr int D = DE;
+    double xc[DE], g[DE];                                    // the embedded point and the gradient in e
+#pragma unroll
+    for (int k = 0; k < DE; ++k) { xc[k] = se[k]; g[k] = 0.0; }
+    double m = 0.0;
+    for (int f = threadIdx.x; f < F; f += NT) RFF_FEATURE_BODY(DE)
+    double gx[DP];                                           // ... pulled back to the caller's coordinates
+#pragma unroll
+    for (int d = 0; d < DP; ++d) {
+      if (d >= CAMPHOR_D) { gx[d] = 0.0; continue; }
+      const int c = camphor_col(d);
+      gx[d] = (d == 2) ? g[c] * L.v[2] : 6.28318530717958647693 * (xc[c] * g[c + 1] - xc[c + 1] * g[c]);
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    m = row16_sum_dpp(m);
+#pragma unroll
+    for (int d = 0; d < DP; ++d) gx[d] = row16_sum_dpp(gx[d]);
+    if ((lane & 15) == 0) {
+      double* r = red[4 * wave + (lane >> 4)];
+      r[DP] = m;
+#pragma unroll
+      for (int d = 0; d < DP; ++d) r[d] = gx[d];
     }
   }
 };
@@ -667,6 +713,25 @@ int launch_rff_ascent(ppbo_ctx* ctx, const double* W_rows, int F, int D, const d
   else if (D <= 24) { if (wide) RA_LAUNCH(24, 512); else RA_LAUNCH(24, 256); }
   else RA_LAUNCH(64, 256);
 #undef RA_LAUNCH
+  return 0;
+}
+
+// the camphor form of launch_rff_ascent: W_rows [F][11], starts / results in the caller's six coordinates
+int launch_rff_ascent_camphor(ppbo_ctx* ctx, const double* W_rows, int F, const double* b, const double* omega, double amp,
+                              const CamphorInvL& L, const double* starts, const int* count, int K, int iters, double tol,
+                              double* x_out, double* v_out, hipStream_t s) {
+  double* W = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_TRANSPOSE, (size_t)F * CAMPHOR_E * sizeof(double));
+  if (!W) return (int)hipErrorOutOfMemory;
+  transpose_rows_kernel<<<(F + 255) / 256, 256, 0, s>>>(W_rows, F, CAMPHOR_E, W);
+#define RC_LAUNCH(NT)                                                                                          \
+  do {                                                                                                         \
+    CamphorRffEval<NT> ev{W, F, b, omega, amp, make_rff_poly(1.0), L};                                         \
+    bb_ascent_kernel<8, CamphorRffEval<NT>, NT><<<K, NT, 0, s>>>(ev, CAMPHOR_D, starts, count, iters, tol, x_out, v_out, nullptr, 0); \
+  } while (0)
+  // 11 embedded columns of point, gradient and feature row: ~170 VGPRs, so at most two wavefronts per SIMD (1024
+  // threads would spill)
+  if (F >= 1024) RC_LAUNCH(512); else RC_LAUNCH(256);
+#undef RC_LAUNCH
   return 0;
 }
 
@@ -1113,6 +1178,49 @@ extern "C" int ppbo_rff_search(ppbo_ctx* ctx, const double* d_cand, int64_t M, i
   }
   if (int rc = launch_rff_ascent(ctx, d_W, F, D, d_b, d_omega, std::sqrt(2.0 * sigma_f * sigma_f / (double)F), starts, count, K,
                                  iters, tol, d_x, d_val, s))
+    return rc;
+  PPBO_LAUNCH_CHECK(ctx);
+  if (h_found) {
+    PPBO_HIP_CHECK(ctx, hipMemcpyAsync(h_found, count, sizeof(int), hipMemcpyDeviceToHost, s));
+    PPBO_HIP_CHECK(ctx, hipStreamSynchronize(s));
+  }
+  return 0;
+}
+
+extern "C" int ppbo_rff_search_camphor(ppbo_ctx* ctx, const double* d_cand, int64_t M, const double* h_l, const double* d_W,
+                                       int F, const double* d_b, double sigma_f, const double* d_omega, int K, double sep,
+                                       int iters, double tol, double* d_x, double* d_val, int* h_found, void* stream) {
+  PPBO_ENTER(ctx);
+  PPBO_REQUIRE(ctx, d_cand && d_W && d_b && d_omega && d_x && d_val, "null pointer");
+  PPBO_REQUIRE_CAMPHOR_L(ctx, h_l);
+  PPBO_REQUIRE(ctx, M > 0 && M < ((int64_t)1 << 31) && F > 0, "sizes");
+  PPBO_REQUIRE(ctx, K > 0 && K <= 1024 && sep >= 0 && iters >= 0 && tol >= 0, "K (<= 1024) / sep / iters / tol");
+  hipStream_t s = (hipStream_t)stream;
+  const int D = CAMPHOR_D;
+  const int T_MAX = select_capacity(D);
+  const int G = (int)((M + T_MAX - 1) / T_MAX);
+  const int T = (int)((M + G - 1) / G);
+  const size_t nd = (size_t)M + T + (size_t)K * D;
+  double* sc = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_SEARCH, nd * sizeof(double) + ((size_t)T + 16) * sizeof(int));
+  if (!sc) return (int)hipErrorOutOfMemory;
+  double* gval = sc + M;
+  double* starts = gval + T;
+  int* gidx = (int*)(starts + (size_t)K * D);
+  int* count = gidx + T;
+  // screening on the embedded candidates: the SE scorer at D = 11
+  double* e = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_CAMPHOR_ROWS, (size_t)M * CAMPHOR_E * sizeof(double));
+  if (!e) return (int)hipErrorOutOfMemory;
+  if (int rc = ppbo_camphor_embed(ctx, d_cand, M, h_l, e, stream)) return rc;
+  if (int rc = ppbo_rff_score(ctx, e, M, CAMPHOR_E, d_W, F, d_b, sigma_f, d_omega, sc, nullptr, nullptr, stream)) return rc;
+  // start selection on the caller-coordinate rows: sep is in the caller's units
+  group_max_kernel<<<(T + 255) / 256, 256, 0, s>>>(sc, M, G, T, gval, gidx);
+  {
+    const size_t sel_lds = (size_t)T * (1 + D) * sizeof(double);
+    if (sel_lds > 64 * 1024) ppbo_lds_limit(ctx, (const void*)select_starts_kernel, 150 * 1024);
+    select_starts_kernel<<<1, 1024, sel_lds, s>>>(gval, gidx, T, d_cand, D, K, sep * sep, starts, count, TrialCands{});
+  }
+  if (int rc = launch_rff_ascent_camphor(ctx, d_W, F, d_b, d_omega, std::sqrt(2.0 * sigma_f * sigma_f / (double)F),
+                                         camphor_inv_l(h_l), starts, count, K, iters, tol, d_x, d_val, s))
     return rc;
   PPBO_LAUNCH_CHECK(ctx);
   if (h_found) {

@@ -849,10 +849,22 @@ class Engine:
         return ei, vm
 
     # ---- RFF -------------------------------------------------------------------------
+    @staticmethod
+    def _rff_widths(what, D, W, b, omega=None):
+        """F = W.shape[0]; raises ValueError unless W is [F, D] for points of D columns and b (and omega) have F entries."""
+        if W.dim() != 2 or W.shape[1] != D:
+            raise ValueError(f"{what}: basis W of shape {tuple(W.shape)} for points of {D} columns ([F, {D}] required)")
+        F = W.shape[0]
+        if b.numel() != F:
+            raise ValueError(f"{what}: b has {b.numel()} entries for {F} features")
+        if omega is not None and omega.numel() != F:
+            raise ValueError(f"{what}: omega has {omega.numel()} entries for {F} features")
+        return F
+
     def rff_project(self, X, W, b, sigma_f, out=None):
         X, W, b = self.dev(X), self.dev(W), self.dev(b).reshape(-1)
         N, D = X.shape
-        F = W.shape[0]
+        F = self._rff_widths("rff_project", D, W, b)
         Phi = self.empty(F, N) if out is None else out
         rc = self.lib.ppbo_rff_project(self.ctx, _ptr(X), N, D, _ptr(W), F, _ptr(b), float(sigma_f), _ptr(Phi),
                                        self._stream())
@@ -862,7 +874,7 @@ class Engine:
     def rff_score(self, Xc, W, b, sigma_f, omega, want_score=True):
         Xc, W, b, omega = self.dev(Xc), self.dev(W), self.dev(b).reshape(-1), self.dev(omega).reshape(-1)
         M, D = Xc.shape
-        F = W.shape[0]
+        F = self._rff_widths("rff_score", D, W, b, omega)
         sc = self.empty(M) if want_score else None
         bv, bi = C.c_double(0.0), C.c_int64(-1)
         rc = self.lib.ppbo_rff_score(self.ctx, _ptr(Xc), M, D, _ptr(W), F, _ptr(b), float(sigma_f), _ptr(omega),
@@ -893,12 +905,33 @@ class Engine:
         x[found, D], values[found] as NumPy arrays."""
         cand, W, b, omega = self.dev(cand), self.dev(W), self.dev(b).reshape(-1), self.dev(omega).reshape(-1)
         M, D = cand.shape
-        F = W.shape[0]
+        F = self._rff_widths("rff_search", D, W, b, omega)
         xs, vals = self.empty(K, D), self.empty(K)
         found = C.c_int(0)
         rc = self.lib.ppbo_rff_search(self.ctx, _ptr(cand), M, D, _ptr(W), F, _ptr(b), float(sigma_f), _ptr(omega), int(K),
                                       float(sep), int(iters), float(tol), _ptr(xs), _ptr(vals), C.byref(found), self._stream())
         self._check(rc, "ppbo_rff_search")
+        n = found.value
+        return xs[:n].cpu().numpy(), vals[:n].cpu().numpy()
+
+    def rff_search_camphor(self, cand, ls, W, b, sigma_f, omega, K=32, sep=0.05, iters=200, tol=1e-10):
+        """rff_search for a camphor-copper basis (ppbo_rff_search_camphor): W [F, 11] acts on the embedding e(x) of the
+        six length scales ls; cand [M, 6], the box, sep and the refined maxima x[found, 6] are in the caller's
+        coordinates.  Returns x[found, 6], values[found] as NumPy arrays."""
+        cand, W, b, omega = self.dev(cand), self.dev(W), self.dev(b).reshape(-1), self.dev(omega).reshape(-1)
+        if cand.dim() != 2 or cand.shape[1] != 6:
+            raise ValueError(f"rff_search_camphor: candidates of shape {tuple(cand.shape)}, [M, 6] required")
+        M = cand.shape[0]
+        F = self._rff_widths("rff_search_camphor", 11, W, b, omega)
+        l = np.ascontiguousarray(ls, dtype=np.float64).reshape(-1)
+        if l.size != 6:
+            raise ValueError(f"rff_search_camphor: {l.size} length scales, 6 required")
+        xs, vals = self.empty(K, 6), self.empty(K)
+        found = C.c_int(0)
+        rc = self.lib.ppbo_rff_search_camphor(self.ctx, _ptr(cand), M, self._dptr(l), _ptr(W), F, _ptr(b), float(sigma_f),
+                                              _ptr(omega), int(K), float(sep), int(iters), float(tol), _ptr(xs), _ptr(vals),
+                                              C.byref(found), self._stream())
+        self._check(rc, "ppbo_rff_search_camphor")
         n = found.value
         return xs[:n].cpu().numpy(), vals[:n].cpu().numpy()
 

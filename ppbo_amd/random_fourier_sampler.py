@@ -7,6 +7,12 @@ Differences in *cost*, not in results: the reference's weight-space Hessian is d
 here the diagonal is kept as a vector (the dense forms are still produced on request for
 attribute compatibility).  The L-BFGS-B multi-start of return_xstar (:143-176) is one device
 enqueue: batched candidate scoring, start selection and the whole multi-start gradient ascent (ppbo_rff_search).
+
+Spectral bases (the reference has the SE one only, :40-42): SE, RQ (alpha = 2, a Gamma scale mixture of SE), the
+Matern kernels (Student-t) and the camphor-copper kernels.  camphor(x, x'; l_0..l_5) = SE(e(x), e(x'); 1) for the
+11-column embedding e of engine.py / include/ppbo_hip.h, so a camphor basis is the unit SE basis on e: W is [F, 11],
+Phi(X) is formed on the embedded rows, and every method that takes or returns a point works in the caller's six
+coordinates (phi / Dphi through e and its Jacobian; the search by ppbo_rff_search_camphor).
 """
 from __future__ import annotations
 
@@ -14,7 +20,7 @@ import time
 
 import numpy as np
 
-from .engine import get_engine
+from .engine import camphor_lengthscales, get_engine
 
 SCORE_CANDIDATES = 65536
 RFF_STARTS = 32            # refined starts per posterior sample (the reference: 5-30 L-BFGS-B runs)
@@ -31,6 +37,50 @@ def matern_spectral_draw(F, D, lengthscale, nu, rng=np.random):
     z = rng.standard_normal((F, D))
     u = rng.chisquare(2.0 * nu, size=F)
     return z / lengthscale * np.sqrt(2.0 * nu / u)[:, None]
+
+
+RQ_ALPHA = 2.0               # the reference's RQ kernel fixes alpha = 2 (src/kernels.py:27-34)
+CAMPHOR_KERNELS = ("camphor_copper_kernel", "camphor_copper_ard_kernel")
+CAMPHOR_E = 11               # width of the camphor embedding e(x)
+
+
+def rq_spectral_draw(F, D, lengthscale, alpha=RQ_ALPHA, rng=np.random):
+    """F frequencies [F, D] from the spectral density of RQ(alpha) with length scale l.  (1 + r^2 / (2 alpha l^2))^-alpha
+    = E_tau[exp(-tau r^2 / (2 l^2))] with tau ~ Gamma(shape alpha, rate alpha), so a draw is the SE draw of length scale
+    l / sqrt(tau): W = z sqrt(tau) / l, z ~ N(0, I_D), one tau per feature.  Draw order: the F x D normals, then the F
+    gammas."""
+    z = rng.standard_normal((F, D))
+    tau = rng.gamma(alpha, 1.0 / alpha, size=F)
+    return z * np.sqrt(tau)[:, None] / lengthscale
+
+
+def camphor_embed_host(x, ls):
+    """e(x) [n, 11] of caller rows x [n, 6]: (cos 2 pi x_d, sin 2 pi x_d) / l_d for d != 2, x_2 / l_2 for z, in the
+    column order (c0, s0, c1, s1, z, c3, s3, c4, s4, c5, s5) of include/ppbo_hip.h."""
+    x = np.atleast_2d(np.asarray(x, dtype=float))
+    cols = []
+    for d in range(6):
+        if d == 2:
+            cols.append(x[:, 2] / ls[2])
+        else:
+            cols += [np.cos(2 * np.pi * x[:, d]) / ls[d], np.sin(2 * np.pi * x[:, d]) / ls[d]]
+    return np.stack(cols, axis=1)
+
+
+def camphor_embed_jacobian(x, ls):
+    """de/dx [11, 6] at one caller point x: d c_d / d x_d = -2 pi s_d, d s_d / d x_d = 2 pi c_d, d z / d x_2 = 1 / l_2."""
+    e = camphor_embed_host(x, ls)[0]
+    J = np.zeros((CAMPHOR_E, 6))
+    c = 0
+    for d in range(6):
+        if d == 2:
+            J[c, 2] = 1.0 / ls[2]
+            c += 1
+        else:
+            J[c, d] = -2 * np.pi * e[c + 1]
+            J[c + 1, d] = 2 * np.pi * e[c]
+            c += 2
+    return J
 
 
 class Hsampler:
@@ -63,6 +113,9 @@ class Hsampler:
         dX = getattr(gp_model, "_dX", None)
         if dX is not None and tuple(dX.shape) == tuple(np.shape(self.X)) and dX.device == self.eng.device:
             self._dcache["X"] = (self.X, dX)
+        # camphor kernels: the six length scales, and the model's posteriors whose embedded rows e(X) can be reused
+        self.camphor_l = camphor_lengthscales(self.theta, self.D) if self.kernel in CAMPHOR_KERNELS else None
+        self._posts = (getattr(gp_model, "_post", None), getattr(gp_model, "_post_mean", None))
 
     def _dev(self, name):
         arr = getattr(self, name)
@@ -76,31 +129,92 @@ class Hsampler:
     def generate_basis(self):
         # per-dimension length scales (ARD): column d of W is divided by l_d -- the spectral density of the scaled kernel --
         # with the same draws in the same order as a scalar l
-        ls = self.theta[1] if np.ndim(self.theta[1]) == 0 else np.asarray(self.theta[1], dtype=float)
-        if self.kernel == "SE_kernel":                        # the reference supports the SE spectral density only (:40-42)
-            self.W = np.random.randn(self.nFeatures, self.D) / ls
-        elif self.kernel in MATERN_NU:
-            self.W = matern_spectral_draw(self.nFeatures, self.D, ls, MATERN_NU[self.kernel])
+        if self.kernel in CAMPHOR_KERNELS:
+            # the unit SE basis on the embedding: the length scales live in e(x)
+            self.camphor_l = camphor_lengthscales(self.theta, self.D)
+            self.W = np.random.randn(self.nFeatures, CAMPHOR_E)
+        else:
+            ls = self.theta[1] if np.ndim(self.theta[1]) == 0 else np.asarray(self.theta[1], dtype=float)
+            if self.kernel == "SE_kernel":                        # the reference supports the SE spectral density only (:40-42)
+                self.W = np.random.randn(self.nFeatures, self.D) / ls
+            elif self.kernel in MATERN_NU:
+                self.W = matern_spectral_draw(self.nFeatures, self.D, ls, MATERN_NU[self.kernel])
+            elif self.kernel == "RQ_kernel":
+                self.W = rq_spectral_draw(self.nFeatures, self.D, ls)
+            else:
+                raise ValueError(f"Hsampler has no spectral basis for the kernel {self.kernel!r}")
         self.b = np.random.uniform(low=0, high=2 * np.pi, size=self.nFeatures)[:, None]
+
+    # ---- camphor: the embedding --------------------------------------------------
+    def _camphor(self):
+        """The six camphor length scales, or None for the other kernels."""
+        if self.kernel not in CAMPHOR_KERNELS:
+            return None
+        l = self.__dict__.get("camphor_l")
+        if l is None:
+            l = self.camphor_l = camphor_lengthscales(self.theta, self.D)
+        return l
+
+    def _check_W(self):
+        """A basis whose width does not fit the kernel (11 for camphor, D otherwise) would be read as another basis."""
+        want = CAMPHOR_E if self._camphor() is not None else self.D
+        if np.ndim(self.W) != 2 or np.shape(self.W)[1] != want:
+            raise ValueError(f"Hsampler.W has shape {np.shape(self.W)}: [nFeatures, {want}] required for {self.kernel}")
+
+    def _dev_embedded_X(self):
+        """Device copy of e(X) [N, 11]: the posterior's own embedded rows where the model has them at these length
+        scales, else ppbo_camphor_embed of X; made once per X object."""
+        l = self._camphor()
+        hit = self._dcache.get("E")
+        if hit is not None and hit[0] is self.X and np.array_equal(hit[1], l):
+            return hit[2]
+        E = None
+        for post in self.__dict__.get("_posts", ()):
+            if (post is not None and post.camphor is not None and np.array_equal(post.camphor, l)
+                    and tuple(post.X.shape) == (np.shape(self.X)[0], CAMPHOR_E)):
+                E = post.X
+                break
+        if E is None:
+            E = self.eng.camphor_embed(self._dev("X"), l)
+        self._dcache["E"] = (self.X, l.copy(), E)
+        return E
+
+    def _points(self, Xc):
+        """Caller-coordinate points -> the rows the basis acts on (embedded for camphor, else as they are)."""
+        l = self._camphor()
+        return Xc if l is None else self.eng.camphor_embed(Xc, l)
 
     def _scale(self):
         return np.sqrt(2.0 * self.theta[2] ** 2 / self.nFeatures)
 
     def phiVec(self, x):
+        self._check_W()
         x = np.atleast_2d(np.asarray(x, dtype=float))
-        return self.eng.rff_project(x, self.W, self.b.ravel(), self.theta[2]).cpu().numpy()
+        return self.eng.rff_project(self._points(x), self.W, self.b.ravel(), self.theta[2]).cpu().numpy()
 
     def phi(self, x):
-        return self._scale() * np.cos(self.W @ np.asarray(x, dtype=float) + self.b.ravel())
+        self._check_W()
+        l = self._camphor()
+        x = np.asarray(x, dtype=float)
+        e = x if l is None else camphor_embed_host(x, l)[0]
+        return self._scale() * np.cos(self.W @ e + self.b.ravel())
 
     def Dphi(self, x):
-        return -self._scale() * np.sin(self.W @ np.asarray(x, dtype=float) + self.b.ravel())[:, None] * self.W
+        self._check_W()
+        l = self._camphor()
+        x = np.asarray(x, dtype=float)
+        if l is None:
+            return -self._scale() * np.sin(self.W @ x + self.b.ravel())[:, None] * self.W
+        e = camphor_embed_host(x, l)[0]
+        return -self._scale() * np.sin(self.W @ e + self.b.ravel())[:, None] * (self.W @ camphor_embed_jacobian(x, l))
 
     def DDphi(self, x):
         raise NotImplementedError
 
     def update_phi_X(self):
-        self._dPhi = self.eng.rff_project(self._dev("X"), self._dev("W"), self._dev("b"), self.theta[2])
+        self._check_W()
+        X = self._dev("X") if self._camphor() is None else self._dev_embedded_X()
+        self._dPhi = self.eng.rff_project(X, self._dev("W"), self._dev("b"), self.theta[2])
         self._phi_X = None
 
     @property
@@ -203,7 +317,8 @@ class Hsampler:
     # ---- maximiser of one posterior sample --------------------------------------------
     def score_candidates(self, Xc, omega):
         """phi(x)^T omega for many candidates on the device; returns (scores, best value, best index)."""
-        sc, bv, bi = self.eng.rff_score(Xc, self._dev("W"), self._dev("b"), self.theta[2], omega)
+        self._check_W()
+        sc, bv, bi = self.eng.rff_score(self._points(Xc), self._dev("W"), self._dev("b"), self.theta[2], omega)
         return sc.cpu().numpy(), bv, bi
 
     def return_xstar(self, omega):
@@ -212,6 +327,7 @@ class Hsampler:
         uniform pool plus such perturbations, keeps the RFF_STARTS best that are > 0.05 apart and runs the whole
         projected gradient ascent of each inside one kernel; the best refined point is returned."""
         import torch
+        self._check_W()
         start = time.time()
         D = self.D
         pool = self.__dict__.get("_pool")
@@ -230,7 +346,12 @@ class Hsampler:
         work[M:].copy_(self.eng.dev(near))
         # 100 Barzilai-Borwein iterations per start: the winning start is stationary after ~50 (tests/probes/
         # rff_ascent_scale.py: the same maximum at 50, 100 and 200), the cap only bounds the starts that keep bouncing
-        xs, vals = self.eng.rff_search(work, self._dev("W"), self._dev("b"), self.theta[2], omega, K=RFF_STARTS, iters=100)
+        l = self._camphor()
+        if l is None:
+            xs, vals = self.eng.rff_search(work, self._dev("W"), self._dev("b"), self.theta[2], omega, K=RFF_STARTS, iters=100)
+        else:       # camphor: the same pool and starts in the caller's coordinates, features on the embedding
+            xs, vals = self.eng.rff_search_camphor(work, l, self._dev("W"), self._dev("b"), self.theta[2], omega,
+                                                   K=RFF_STARTS, iters=100)
         if self.verbose:
             print("Optimization of f_approx took " + str(time.time() - start) + " seconds.")
         if len(vals) == 0 or not np.isfinite(vals).any():
@@ -238,10 +359,12 @@ class Hsampler:
         return xs[int(np.nanargmax(vals))]
 
     def return_xstar_for_dim(self, omega, dim, x_ref):
+        self._check_W()
         x_ref = np.array(x_ref, dtype=float)
         grid = np.tile(x_ref, (4096, 1))
         grid[:, dim - 1] = np.linspace(0, 1, 4096)
-        _, _, bi = self.eng.rff_score(grid, self._dev("W"), self._dev("b"), self.theta[2], omega, want_score=False)
+        _, _, bi = self.eng.rff_score(self._points(grid), self._dev("W"), self._dev("b"), self.theta[2], omega,
+                                      want_score=False)
         return grid[bi]
 
     def sample_xstar(self):
