@@ -483,7 +483,9 @@ PPBO_API int ppbo_rff_search_camphor(ppbo_ctx* ctx, const double* d_cand, int64_
                     double tol, double* d_x, double* d_val, int* h_found, void* stream);
 
 /* ---- generic fp64 MFMA GEMM (exposed for tests and host-side composition) ----
- * C[M,N] = alpha op(A) op(B) + beta C.  transA/transB: 0 = as stored, 1 = transposed. */
+ * C[M,N] = alpha op(A) op(B) + beta C.  transA/transB: 0 = as stored, 1 = transposed.  Row-major storage with leading
+ * dimensions lda >= (transA ? M : K), ldb >= (transB ? K : N), ldc >= N; a shorter one is "invalid argument".  K = 0
+ * gives C = beta C; C is not read when beta == 0. */
 PPBO_API int ppbo_dgemm(ppbo_ctx* ctx, int transA, int transB, int M, int N, int K, double alpha,
                const double* d_A, int lda, const double* d_B, int ldb, double beta,
                double* d_C, int ldc, void* stream);

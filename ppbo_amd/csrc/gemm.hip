@@ -144,6 +144,8 @@ extern "C" int ppbo_dgemm(ppbo_ctx* ctx, int transA, int transB, int M, int N, i
   PPBO_ENTER(ctx);
   PPBO_REQUIRE(ctx, d_A && d_B && d_C, "null pointer");
   PPBO_REQUIRE(ctx, M >= 0 && N >= 0 && K >= 0, "sizes");
+  // a leading dimension shorter than its row would make rows overlap silently
+  PPBO_REQUIRE(ctx, lda >= (transA ? M : K) && ldb >= (transB ? K : N) && ldc >= N, "leading dimension shorter than a row");
   GemmArgs g{};
   g.A = d_A; g.lda = lda; g.B = d_B; g.ldb = ldb; g.C = d_C; g.ldc = ldc;
   g.M = M; g.N = N; g.K = K; g.alpha = alpha; g.beta = beta;

@@ -3,6 +3,7 @@ vectors produced by the reference.  Run with `pytest -m gpu` on an MI355X."""
 import numpy as np
 import pytest
 
+import dense_ref as dr
 from conftest import golden_names
 from oracle import ppbo_oracle as orc
 
@@ -432,12 +433,19 @@ def test_full_size_c3_properties(eng, golden):
     assert np.allclose(host(part["mu"]), host(full["mu"])[30000:31000], rtol=0, atol=1e-12)
     assert np.allclose(host(part["var"]), host(full["var"])[30000:31000], rtol=0, atol=1e-12)
     idx = np.random.default_rng(2).choice(M, 256, replace=False)
+    sf2 = float(g["theta"][2]) ** 2
+    # the oracle from the CPU alone: Sigma^-1, P and the variance operator from orc.gram (a wrong device Sigma^-1
+    # would cancel out of an oracle built on it)
+    cpu = dr.CpuModel(g["X"], g["theta"], str(g["kernel"]), int(g["m"]), g["fMAP"])
+    mu0, var0 = cpu.mean_var(Xc[idx])
+    assert rel(host(full["mu"])[idx], mu0) < 1e-6
+    assert np.abs(host(full["var"])[idx] - var0).max() <= 1e-6 * sf2
+    # and the identity check on the device's own Sigma^-1
     Sinv_h = host(Sinv)
     P = orc.posterior_covariance(Sinv_h, g["fMAP"], int(g["m"]), float(g["theta"][0]))
     lam = orc.lambda_dense(g["fMAP"], int(g["m"]), float(g["theta"][0]))
     A = orc.variance_operator(Sinv_h, P, faithful=False, lam=lam)
     mu0, var0 = orc.predict_mean_var(Xc[idx], g["X"], g["theta"], Sinv_h @ g["fMAP"], A)
-    sf2 = float(g["theta"][2]) ** 2
     assert rel(host(full["mu"])[idx], mu0) < 1e-6
     assert np.abs(host(full["var"])[idx] - var0).max() <= 1e-6 * sf2
 
@@ -512,10 +520,16 @@ def test_c5_size_camphor_properties(eng):
     post = eng.posterior(X, th, kernel, Sinv, fm, m, want_P=True)
     Xc = np.random.default_rng(1).random((4096, D))
     out = eng.predict(post, Xc)
-    # oracle with the device's Sigma^-1 / P (an N=4096 CPU inverse is the slow part; identities are what is checked)
     sub = np.random.default_rng(3).choice(4096, 64, replace=False)
-    K = orc.cross_cov(X, Xc[sub], th, kernel)
     f = host(fm)
+    # the oracle from the CPU alone at the device's f_MAP (the point the posterior is taken at; the fit is checked by
+    # its convergence): Sigma^-1, P and the variance operator from orc.gram, no device intermediate
+    cpu = dr.CpuModel(X, th, kernel, m, f)
+    mu0, var0 = cpu.mean_var(Xc[sub])
+    assert rel(host(out["mu"])[sub], mu0) < 1e-6
+    assert np.abs(host(out["var"])[sub] - var0).max() <= 1e-6 * th[2] ** 2
+    # and the identity checks on the device's own Sigma^-1 / P
+    K = orc.cross_cov(X, Xc[sub], th, kernel)
     Sinv_h, P_h = host(Sinv), host(post.P)
     mu0 = K.T @ (Sinv_h @ f)
     lam = orc.lambda_dense(f, m, th[0])
