@@ -482,6 +482,42 @@ PPBO_API int ppbo_rff_search_camphor(ppbo_ctx* ctx, const double* d_cand, int64_
                     int F, const double* d_b, double sigma_f, const double* d_omega, int K, double sep, int iters,
                     double tol, double* d_x, double* d_val, int* h_found, void* stream);
 
+/* ---- batches of posterior samples: S weight vectors omega_s per enqueue ----------------------------------------
+ * The upstream workflow draws the posterior of the maximiser with one Hsampler.sample_xstar() per sample
+ * (src/random_fourier_sampler.py:143-176 per sample, :207-220 for the weight draw).  These entries serve S samples at
+ * once: one scoring launch forms the cosine features of a candidate tile once and contracts them with all S weight
+ * vectors on the fp64 matrix cores, one selection launch serves every sample and one ascent launch runs S x K starts.
+ * At most PPBO_RFF_MULTI_MAX_S samples per call (larger batches go in chunks). */
+#define PPBO_RFF_MULTI_MAX_S 1024
+
+/* Omega[s][f] = omega_MAP[f] + sqrt(cov_diag[f]) z[s][f] for s < S: S draws of the weights from their Laplace
+ * posterior N(omega_MAP, diag(cov_diag)) (src/random_fourier_sampler.py:207-220, the dense covariance is diagonal),
+ * z the ppbo_randn stream of `seed` at index s F + f -- bitwise reproducible for a given seed.  d_omegas[S,F]. */
+PPBO_API int ppbo_rff_omega_draws(ppbo_ctx* ctx, uint64_t seed, const double* d_omega_map, const double* d_cov_diag, int F,
+                         int S, double* d_omegas, void* stream);
+
+/* ppbo_rff_score for S weight vectors: d_score[s][c] = phi(x_c)^T omega_s, d_omegas[S,F] row-major, d_score[S,M]
+ * (:166,170 per sample).  Every feature summed in one fixed order: a repeated call is bitwise equal.
+ * "invalid argument": null pointers, M outside 1 .. 2^31 - 1, D outside 1 .. 64, S outside 1 .. PPBO_RFF_MULTI_MAX_S. */
+PPBO_API int ppbo_rff_score_multi(ppbo_ctx* ctx, const double* d_Xc, int64_t M, int D, const double* d_W, int F,
+                         const double* d_b, double sigma_f, const double* d_omegas, int S, double* d_score,
+                         void* stream);
+
+/* ppbo_rff_search for S weight vectors over one shared candidate set (:143-176 per sample): scores every candidate for
+ * every sample (ppbo_rff_score_multi), picks each sample's K best starts > sep apart in its own scores, and ascends all
+ * S x K starts in one launch, workgroup s K + k on omega_s.  d_x[S,K,D] / d_val[S,K]: refined maxima of sample s in
+ * rows < d_found[s] (an int array on the device), value -inf in the others.  Enqueued only: nothing is read back.
+ * "invalid argument" as ppbo_rff_score_multi, and K outside 1 .. 1024. */
+PPBO_API int ppbo_rff_search_multi(ppbo_ctx* ctx, const double* d_cand, int64_t M, int D, const double* d_W, int F,
+                          const double* d_b, double sigma_f, const double* d_omegas, int S, int K, double sep, int iters,
+                          double tol, double* d_x, double* d_val, int* d_found, void* stream);
+
+/* ppbo_rff_search_multi for a camphor-copper basis, as ppbo_rff_search_camphor: h_l[6] length scales, d_W[F,11],
+ * d_cand[M,6] embedded once and scored at D = 11; selection, box, sep and d_x[S,K,6] in the caller's coordinates. */
+PPBO_API int ppbo_rff_search_multi_camphor(ppbo_ctx* ctx, const double* d_cand, int64_t M, const double* h_l,
+                          const double* d_W, int F, const double* d_b, double sigma_f, const double* d_omegas, int S, int K,
+                          double sep, int iters, double tol, double* d_x, double* d_val, int* d_found, void* stream);
+
 /* ---- generic fp64 MFMA GEMM (exposed for tests and host-side composition) ----
  * C[M,N] = alpha op(A) op(B) + beta C.  transA/transB: 0 = as stored, 1 = transposed.  Row-major storage with leading
  * dimensions lda >= (transA ? M : K), ldb >= (transB ? K : N), ldc >= N; a shorter one is "invalid argument".  K = 0

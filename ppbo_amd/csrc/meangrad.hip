@@ -556,6 +556,28 @@ struct CamphorRffEval {
   }
 };
 
+// the batched forms (ppbo_rff_search_multi / _camphor): one launch runs S x K starts, workgroup s K + k on sample s, whose
+// weights follow sample 0's at s F.  They ARE the single-sample evaluations with omega moved to the workgroup's sample.
+template <int DP, int NT>
+struct RffMultiEval {
+  RffEval<DP, NT> ev; int per;               // ev.omega: the [S, F] weights; per = K starts per sample
+  __device__ __forceinline__ void operator()(const double* sx, double (*red)[DP + 1]) const {
+    RffEval<DP, NT> e = ev;
+    e.omega = ev.omega + (size_t)(blockIdx.x / per) * ev.F;
+    e(sx, red);
+  }
+};
+template <int NT>
+struct CamphorRffMultiEval {
+  static constexpr int DP = CamphorRffEval<NT>::DP;
+  CamphorRffEval<NT> ev; int per;
+  __device__ __forceinline__ void operator()(const double* sx, double (*red)[DP + 1]) const {
+    CamphorRffEval<NT> e = ev;
+    e.omega = ev.omega + (size_t)(blockIdx.x / per) * ev.F;
+    e(sx, red);
+  }
+};
+
 // fixed-order sum of the NW records of column c
 template <int NW, int DP>
 __device__ __forceinline__ double red_col(const double (*red)[DP + 1], int c) {
@@ -732,6 +754,42 @@ int launch_rff_ascent_camphor(ppbo_ctx* ctx, const double* W_rows, int F, const 
   // threads would spill)
   if (F >= 1024) RC_LAUNCH(512); else RC_LAUNCH(256);
 #undef RC_LAUNCH
+  return 0;
+}
+
+// launch_rff_ascent / launch_rff_ascent_camphor for S samples of K starts each: S K workgroups, count[s] starts exist
+int launch_rff_ascent_multi(ppbo_ctx* ctx, const double* W_rows, int F, int D, const double* b, const double* omegas,
+                            double amp, const double* starts, const int* count, int S, int K, int iters, double tol,
+                            double* x_out, double* v_out, hipStream_t s) {
+  double* W = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_TRANSPOSE, (size_t)F * D * sizeof(double));
+  if (!W) return (int)hipErrorOutOfMemory;
+  transpose_rows_kernel<<<(F + 255) / 256, 256, 0, s>>>(W_rows, F, D, W);
+#define RAM_LAUNCH(DP, NT)                                                                                     \
+  do {                                                                                                         \
+    RffMultiEval<DP, NT> ev{RffEval<DP, NT>{W, F, D, b, omegas, amp, make_rff_poly(1.0)}, K};                  \
+    bb_ascent_kernel<DP, RffMultiEval<DP, NT>, NT><<<S * K, NT, 0, s>>>(ev, D, starts, count, iters, tol, x_out, v_out, nullptr, K); \
+  } while (0)
+  const bool wide = F >= 1024;
+  if (D <= 8) { if (wide) RAM_LAUNCH(8, 1024); else RAM_LAUNCH(8, 256); }
+  else if (D <= 24) { if (wide) RAM_LAUNCH(24, 512); else RAM_LAUNCH(24, 256); }
+  else RAM_LAUNCH(64, 256);
+#undef RAM_LAUNCH
+  return 0;
+}
+
+int launch_rff_ascent_multi_camphor(ppbo_ctx* ctx, const double* W_rows, int F, const double* b, const double* omegas,
+                                    double amp, const CamphorInvL& L, const double* starts, const int* count, int S, int K,
+                                    int iters, double tol, double* x_out, double* v_out, hipStream_t s) {
+  double* W = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_TRANSPOSE, (size_t)F * CAMPHOR_E * sizeof(double));
+  if (!W) return (int)hipErrorOutOfMemory;
+  transpose_rows_kernel<<<(F + 255) / 256, 256, 0, s>>>(W_rows, F, CAMPHOR_E, W);
+#define RCM_LAUNCH(NT)                                                                                         \
+  do {                                                                                                         \
+    CamphorRffMultiEval<NT> ev{CamphorRffEval<NT>{W, F, b, omegas, amp, make_rff_poly(1.0), L}, K};            \
+    bb_ascent_kernel<8, CamphorRffMultiEval<NT>, NT><<<S * K, NT, 0, s>>>(ev, CAMPHOR_D, starts, count, iters, tol, x_out, v_out, nullptr, K); \
+  } while (0)
+  if (F >= 1024) RCM_LAUNCH(512); else RCM_LAUNCH(256);
+#undef RCM_LAUNCH
   return 0;
 }
 
@@ -1228,4 +1286,69 @@ extern "C" int ppbo_rff_search_camphor(ppbo_ctx* ctx, const double* d_cand, int6
     PPBO_HIP_CHECK(ctx, hipStreamSynchronize(s));
   }
   return 0;
+}
+
+// ppbo_rff_search(_camphor) for S samples over one candidate set: l = NULL the plain basis at D columns, else the camphor
+// basis (d_cand in the caller's six coordinates, scored on its embedding)
+static int rff_search_multi_impl(ppbo_ctx* ctx, const double* d_cand, int64_t M, int D, const double* h_l, const double* d_W,
+                                 int F, const double* d_b, double sigma_f, const double* d_omegas, int S, int K, double sep,
+                                 int iters, double tol, double* d_x, double* d_val, int* d_found, void* stream) {
+  PPBO_REQUIRE(ctx, d_cand && d_W && d_b && d_omegas && d_x && d_val && d_found, "null pointer");
+  PPBO_REQUIRE(ctx, M > 0 && M < ((int64_t)1 << 31) && D > 0 && D <= 64 && F > 0, "sizes (D <= 64)");
+  PPBO_REQUIRE(ctx, S > 0 && S <= PPBO_RFF_MULTI_MAX_S, "S (1 .. PPBO_RFF_MULTI_MAX_S samples)");
+  PPBO_REQUIRE(ctx, K > 0 && K <= 1024 && sep >= 0 && iters >= 0 && tol >= 0, "K (<= 1024) / sep / iters / tol");
+  hipStream_t s = (hipStream_t)stream;
+  const int T_MAX = select_capacity(D);
+  const int G = (int)((M + T_MAX - 1) / T_MAX);
+  const int T = (int)((M + G - 1) / G);
+  // workspace: scores[S][M] | gval[S][T] | starts[S][K][D] | gidx[S][T] (int); the start counts go to d_found
+  const size_t nd = (size_t)S * M + (size_t)S * T + (size_t)S * K * D;
+  double* sc = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_SEARCH, nd * sizeof(double) + ((size_t)S * T + 16) * sizeof(int));
+  if (!sc) return ppbo_set_error(ctx, (int)hipErrorOutOfMemory, "invalid argument: no workspace for %d samples of %lld candidates",
+                                 S, (long long)M);
+  double* gval = sc + (size_t)S * M;
+  double* starts = gval + (size_t)S * T;
+  int* gidx = (int*)(starts + (size_t)S * K * D);
+  if (h_l) {
+    double* e = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_CAMPHOR_ROWS, (size_t)M * CAMPHOR_E * sizeof(double));
+    if (!e) return ppbo_set_error(ctx, (int)hipErrorOutOfMemory, "invalid argument: no workspace for the embedded candidates");
+    if (int rc = ppbo_camphor_embed(ctx, d_cand, M, h_l, e, stream)) return rc;
+    if (int rc = ppbo_rff_score_multi(ctx, e, M, CAMPHOR_E, d_W, F, d_b, sigma_f, d_omegas, S, sc, stream)) return rc;
+  } else if (int rc = ppbo_rff_score_multi(ctx, d_cand, M, D, d_W, F, d_b, sigma_f, d_omegas, S, sc, stream)) {
+    return rc;
+  }
+  // one "trial" per sample over the shared candidates: each sample's K starts are > sep apart in its own scores
+  group_max_kernel<<<dim3((T + 255) / 256, S), 256, 0, s>>>(sc, M, G, T, gval, gidx);
+  {
+    const size_t sel_lds = (size_t)T * (1 + D) * sizeof(double);
+    if (sel_lds > 64 * 1024) ppbo_lds_limit(ctx, (const void*)select_starts_kernel, 150 * 1024);
+    select_starts_kernel<<<S, 1024, sel_lds, s>>>(gval, gidx, T, d_cand, D, K, sep * sep, starts, d_found, TrialCands{});
+  }
+  PPBO_LAUNCH_CHECK(ctx);
+  const double amp = std::sqrt(2.0 * sigma_f * sigma_f / (double)F);
+  const int rc = h_l ? launch_rff_ascent_multi_camphor(ctx, d_W, F, d_b, d_omegas, amp, camphor_inv_l(h_l), starts, d_found,
+                                                       S, K, iters, tol, d_x, d_val, s)
+                     : launch_rff_ascent_multi(ctx, d_W, F, D, d_b, d_omegas, amp, starts, d_found, S, K, iters, tol, d_x,
+                                               d_val, s);
+  if (rc) return rc;
+  PPBO_LAUNCH_CHECK(ctx);
+  return 0;
+}
+
+extern "C" int ppbo_rff_search_multi(ppbo_ctx* ctx, const double* d_cand, int64_t M, int D, const double* d_W, int F,
+                                     const double* d_b, double sigma_f, const double* d_omegas, int S, int K, double sep,
+                                     int iters, double tol, double* d_x, double* d_val, int* d_found, void* stream) {
+  PPBO_ENTER(ctx);
+  return rff_search_multi_impl(ctx, d_cand, M, D, nullptr, d_W, F, d_b, sigma_f, d_omegas, S, K, sep, iters, tol, d_x, d_val,
+                               d_found, stream);
+}
+
+extern "C" int ppbo_rff_search_multi_camphor(ppbo_ctx* ctx, const double* d_cand, int64_t M, const double* h_l,
+                                             const double* d_W, int F, const double* d_b, double sigma_f,
+                                             const double* d_omegas, int S, int K, double sep, int iters, double tol,
+                                             double* d_x, double* d_val, int* d_found, void* stream) {
+  PPBO_ENTER(ctx);
+  PPBO_REQUIRE_CAMPHOR_L(ctx, h_l);
+  return rff_search_multi_impl(ctx, d_cand, M, CAMPHOR_D, h_l, d_W, F, d_b, sigma_f, d_omegas, S, K, sep, iters, tol, d_x,
+                               d_val, d_found, stream);
 }

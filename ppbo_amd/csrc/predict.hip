@@ -860,6 +860,16 @@ __global__ __launch_bounds__(256) void randn_kernel(unsigned long long seed, dou
   if (2 * pair + 1 < n) out[2 * pair + 1] = rad * sn;
 }
 
+// Omega[s][f] = omega_MAP[f] + sqrt(cov_diag[f]) z[s][f] in place over the randn_kernel draws z (ppbo_rff_omega_draws);
+// product and sum rounded separately (no contraction), as the host states them
+__global__ __launch_bounds__(256) void omega_draws_kernel(const double* __restrict__ om, const double* __restrict__ cov,
+                                                          int F, long long n, double* __restrict__ out) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int f = (int)(i % F);
+  out[i] = __dadd_rn(om[f], __dmul_rn(sqrt(cov[f]), out[i]));
+}
+
 template <int KID>
 int launch_kstar(const ppbo_model* m, const KernParams& p, const double* d_Xc, int M, double* Kt, int ldk,
                  double* mu_part, double* t_part, int q_per_split, int n_split, bool with_lam, int edge_k0, hipStream_t s) {
@@ -1388,6 +1398,20 @@ int ppbo_randn(ppbo_ctx* ctx, uint64_t seed, double* d_out, int64_t n, void* str
   const long long pairs = (n + 1) / 2;
   PPBO_REQUIRE(ctx, (pairs + 255) / 256 < ((long long)1 << 31), "n too large for one launch");
   randn_kernel<<<(unsigned)((pairs + 255) / 256), 256, 0, (hipStream_t)stream>>>((unsigned long long)seed, d_out, (long long)n);
+  PPBO_LAUNCH_CHECK(ctx);
+  return 0;
+}
+
+int ppbo_rff_omega_draws(ppbo_ctx* ctx, uint64_t seed, const double* d_omega_map, const double* d_cov_diag, int F, int S,
+                         double* d_omegas, void* stream) {
+  PPBO_ENTER(ctx);
+  PPBO_REQUIRE(ctx, d_omega_map && d_cov_diag && d_omegas, "null pointer");
+  PPBO_REQUIRE(ctx, F > 0 && S > 0, "F / S");
+  const long long n = (long long)S * F, pairs = (n + 1) / 2;
+  PPBO_REQUIRE(ctx, (n + 255) / 256 < ((long long)1 << 31), "S x F too large for one launch");
+  hipStream_t s = (hipStream_t)stream;
+  randn_kernel<<<(unsigned)((pairs + 255) / 256), 256, 0, s>>>((unsigned long long)seed, d_omegas, n);
+  omega_draws_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(d_omega_map, d_cov_diag, F, n, d_omegas);
   PPBO_LAUNCH_CHECK(ctx);
   return 0;
 }

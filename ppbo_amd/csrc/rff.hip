@@ -270,6 +270,105 @@ __global__ __launch_bounds__(256, MINW) void rff_score_mfma_kernel(const double*
   }
 }
 
+// K8 for S weight vectors at once (ppbo_rff_score_multi): score[s][c] = a sum_f Omega[s][f] cos(w_f.x_c + b_f).
+// The phase tile comes off the matrix cores as in rff_score_mfma_kernel, and after the cosine register r of lane
+// (lr, lk) holds feature lk + 4r of candidate lr: exactly the B fragment (k = lk, n = lr) of features 4r..4r+3.  So the
+// second contraction acc[s16][c16] += Omega^T[16 samples x 4 features] . cos[4 features x 16 candidates] is four more
+// v_mfma_f64_16x16x4f64 per 16-sample block with no lane movement; the A fragments of Omega come from LDS, staged beside
+// W and b.  One workgroup: 4 wavefronts x CG groups of 16 candidates, SB blocks of 16 samples (blockIdx.y), every
+// feature in one fixed order (no split, no atomics: a call is bitwise repeatable).  Padded features carry Omega = 0,
+// padded samples are never written.
+template <int DP, int CG, int SB>
+__global__ __launch_bounds__(256) void rff_score_multi_kernel(const double* __restrict__ Xc, int M, int D,
+                                                              const double* __restrict__ W, int F,
+                                                              const double* __restrict__ b,
+                                                              const double* __restrict__ omegas, int S, RffPoly P,
+                                                              double* __restrict__ score) {
+  constexpr int Q = DP / 4, LD = DP + 2, RJ = 32, NS = 16 * SB, LO = RJ + 1;
+  __shared__ __attribute__((aligned(16))) double ws[RJ * LD];
+  __shared__ double s_b[RJ];
+  __shared__ double s_om[NS * LO];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, lr = lane & 15, lk = lane >> 4;
+  const int cw = blockIdx.x * (64 * CG) + wv * (16 * CG);
+  const int s0 = blockIdx.y * NS;
+  double xb[CG][Q];
+  double4_t acc[CG][SB];
+#pragma unroll
+  for (int g = 0; g < CG; ++g) {
+    const int c = cw + 16 * g + lr;
+#pragma unroll
+    for (int kk = 0; kk < Q; ++kk) {
+      const int d = kk * 4 + lk;
+      xb[g][kk] = (d < D && c < M) ? Xc[(size_t)c * D + d] : 0.0;
+    }
+#pragma unroll
+    for (int j = 0; j < SB; ++j) acc[g][j] = double4_t{0.0, 0.0, 0.0, 0.0};
+  }
+  for (int r0 = 0; r0 < F; r0 += RJ) {
+    __syncthreads();
+    for (int e = threadIdx.x; e < RJ * DP; e += 256) {
+      const int r = e / DP, d = e - r * DP;
+      const int f = r0 + r;
+      ws[r * LD + d] = (f < F && d < D) ? W[(size_t)f * D + d] : 0.0;
+    }
+    if (threadIdx.x < RJ) {
+      const int f = r0 + threadIdx.x;
+      s_b[threadIdx.x] = (f < F) ? b[f] : 0.0;
+    }
+    for (int e = threadIdx.x; e < NS * RJ; e += 256) {
+      const int j = e / RJ, r = e - j * RJ;
+      const int s = s0 + j, f = r0 + r;
+      s_om[j * LO + r] = (s < S && f < F) ? omegas[(size_t)s * F + f] : 0.0;   // zero weight kills padded rows
+    }
+    __syncthreads();
+#pragma unroll 1
+    for (int t = 0; t < RJ / 16; ++t) {
+      if (r0 + 16 * t >= F) break;
+      double af[Q], br[4];
+#pragma unroll
+      for (int kk = 0; kk < Q; ++kk) af[kk] = ws[(16 * t + lr) * LD + kk * 4 + lk];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) br[r] = s_b[16 * t + lk + 4 * r];
+#pragma unroll
+      for (int g = 0; g < CG; ++g) {
+        double4_t ph = double4_t{br[0], br[1], br[2], br[3]};
+#pragma unroll
+        for (int kk = 0; kk < Q; ++kk) ph = __builtin_amdgcn_mfma_f64_16x16x4f64(af[kk], xb[g][kk], ph, 0, 0, 0);
+        double v[4];
+        bool big = false;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) big |= !(fabs(ph[r]) < RFF_COS_FAST_RANGE);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[r] = rff_cos_fast(ph[r], P);
+        if (__builtin_amdgcn_ballot_w64(big)) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r)
+            if (!(fabs(ph[r]) < RFF_COS_FAST_RANGE)) v[r] = P.c[0] * rff_cos_slow(ph[r]);
+        }
+        // k-step r of the second product: A[i = lr][k = lk] = Omega[sample 16 j + lr][feature 16 t + 4 r + lk]
+#pragma unroll
+        for (int j = 0; j < SB; ++j)
+#pragma unroll
+          for (int r = 0; r < 4; ++r)
+            acc[g][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(s_om[(16 * j + lr) * LO + 16 * t + 4 * r + lk], v[r],
+                                                             acc[g][j], 0, 0, 0);
+      }
+    }
+  }
+  // C/D map of the f64 form: acc[g][j][r] is sample 16 j + lk + 4 r of candidate lr
+#pragma unroll
+  for (int g = 0; g < CG; ++g) {
+    const int c = cw + 16 * g + lr;
+#pragma unroll
+    for (int j = 0; j < SB; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int s = s0 + 16 * j + lk + 4 * r;
+        if (s < S && c < M) score[(size_t)s * M + c] = acc[g][j][r];
+      }
+  }
+}
+
 // partial[split][n] = sum_{f in split} Phi[f][n] omega[f]
 __global__ __launch_bounds__(256) void phiT_omega_kernel(const double* __restrict__ Phi, int F, int N,
                                                          const double* __restrict__ omega, int f_per_split,
@@ -766,6 +865,42 @@ int ppbo_rff_score(ppbo_ctx* ctx, const double* d_Xc, int64_t M, int D, const do
     PPBO_LAUNCH_CHECK(ctx);
   }
   return merge_chunk_bests(ctx, chunk_best, (int)n_chunks, h_best_val, h_best_idx, s);
+}
+
+int ppbo_rff_score_multi(ppbo_ctx* ctx, const double* d_Xc, int64_t M, int D, const double* d_W, int F,
+                         const double* d_b, double sigma_f, const double* d_omegas, int S, double* d_score,
+                         void* stream) {
+  PPBO_ENTER(ctx);
+  PPBO_REQUIRE(ctx, d_Xc && d_W && d_b && d_omegas && d_score, "null pointer");
+  PPBO_REQUIRE(ctx, M > 0 && M < ((int64_t)1 << 31) && D > 0 && D <= 64 && F > 0, "sizes (D <= 64)");
+  PPBO_REQUIRE(ctx, S > 0 && S <= PPBO_RFF_MULTI_MAX_S, "S (1 .. PPBO_RFF_MULTI_MAX_S samples)");
+  hipStream_t s = (hipStream_t)stream;
+  const RffPoly P = make_rff_poly(std::sqrt(2.0 * sigma_f * sigma_f / (double)F));
+  // one 16-sample block per workgroup for a handful of samples, four otherwise (the cosines are formed once per block
+  // of 64 samples; 4 x 4 accumulator tiles per lane)
+  const bool one = S <= 16;
+  const int mi = (int)M;
+#define RMM_GO(DP, CG, SB)                                                                                         \
+  rff_score_multi_kernel<DP, CG, SB><<<dim3((mi + 64 * CG - 1) / (64 * CG), (S + 16 * SB - 1) / (16 * SB)), 256, 0, s>>>( \
+      d_Xc, mi, D, d_W, F, d_b, d_omegas, S, P, d_score)
+#define RMM_LAUNCH(DP, CG)        \
+  do {                            \
+    if (one) RMM_GO(DP, CG, 1);   \
+    else RMM_GO(DP, CG, 4);       \
+  } while (0)
+  if (D <= 4) RMM_LAUNCH(4, 4);
+  else if (D <= 8) RMM_LAUNCH(8, 4);
+  else if (D <= 12) RMM_LAUNCH(12, 4);
+  else if (D <= 16) RMM_LAUNCH(16, 4);
+  else if (D <= 20) RMM_LAUNCH(20, 4);
+  else if (D <= 24) RMM_LAUNCH(24, 4);
+  else if (D <= 32) RMM_LAUNCH(32, 4);
+  else if (D <= 48) RMM_LAUNCH(48, 2);
+  else RMM_LAUNCH(64, 2);
+#undef RMM_LAUNCH
+#undef RMM_GO
+  PPBO_LAUNCH_CHECK(ctx);
+  return 0;
 }
 
 int ppbo_rff_terms(ppbo_ctx* ctx, const double* d_Phi, int F, int N, int m, double sigma,

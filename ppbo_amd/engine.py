@@ -15,6 +15,7 @@ from ._lib import KERNEL_IDS, SCORE_MEAN, SCORE_POINTWISE_EI, SCORE_VARIANCE, PP
 FORM_NODE = 0   # G = R Lambda, block lower triangular [N, N]
 FORM_EDGE = 1   # H = L22^-1 of the edge-coordinate factor, rows / columns [n_q, N) (ppbo_posterior_edge)
 
+RFF_MULTI_MAX_S = 1024  # PPBO_RFF_MULTI_MAX_S: posterior samples per batched RFF enqueue (include/ppbo_hip.h)
 SHRINKAGE = 1e-6  # COVARIANCE_SHRINKAGE of the reference (gp_model.py:26)
 
 # ARD (one length scale per input dimension, no reference counterpart) is defined for these: for a radial kernel
@@ -934,6 +935,90 @@ class Engine:
         self._check(rc, "ppbo_rff_search_camphor")
         n = found.value
         return xs[:n].cpu().numpy(), vals[:n].cpu().numpy()
+
+    # ---- batches of posterior samples (S weight vectors per call) ---------------------------
+    @staticmethod
+    def _rff_multi_widths(what, D, W, b, omegas, K=None):
+        """(F, S) for S weight vectors omegas [S, F] (NumPy arrays or tensors: only their shapes are read, so this runs
+        before anything goes to the device); raises ValueError unless W is [F, D] for points of 1..64 columns, b has F
+        entries, 1 <= S <= RFF_MULTI_MAX_S and (given) 1 <= K <= 1024."""
+        if not 1 <= D <= 64:
+            raise ValueError(f"{what}: points of {D} columns (1..64 supported)")
+        if len(W.shape) != 2 or W.shape[1] != D:
+            raise ValueError(f"{what}: basis W of shape {tuple(W.shape)} for points of {D} columns ([F, {D}] required)")
+        F = W.shape[0]
+        if int(np.prod(b.shape)) != F:
+            raise ValueError(f"{what}: b has {int(np.prod(b.shape))} entries for {F} features")
+        if len(omegas.shape) != 2 or omegas.shape[1] != F:
+            raise ValueError(f"{what}: omegas of shape {tuple(omegas.shape)}, [S, {F}] required")
+        S = omegas.shape[0]
+        if not 1 <= S <= RFF_MULTI_MAX_S:
+            raise ValueError(f"{what}: {S} samples per call (1..{RFF_MULTI_MAX_S})")
+        if K is not None and not 1 <= K <= 1024:
+            raise ValueError(f"{what}: K = {K} starts per sample (1..1024)")
+        return F, S
+
+    def rff_omega_draws(self, seed, omega_map, cov_diag, n):
+        """[n, F] draws omega_MAP + sqrt(cov_diag) z of the posterior weights on the device (ppbo_rff_omega_draws), z the
+        ppbo_randn stream of `seed`: bitwise reproducible."""
+        om, cov = self.dev(omega_map).reshape(-1), self.dev(cov_diag).reshape(-1)
+        F = om.numel()
+        if cov.numel() != F:
+            raise ValueError(f"rff_omega_draws: cov_diag has {cov.numel()} entries for {F} features")
+        if int(n) < 1:
+            raise ValueError(f"rff_omega_draws: n = {n} draws")
+        out = self.empty(int(n), F)
+        rc = self.lib.ppbo_rff_omega_draws(self.ctx, int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(om), _ptr(cov), F, int(n), _ptr(out),
+                                           self._stream())
+        self._check(rc, "ppbo_rff_omega_draws")
+        return out
+
+    def rff_score_multi(self, Xc, W, b, sigma_f, omegas):
+        """phi(x_c)^T omega_s for S weight vectors omegas [S, F] (ppbo_rff_score_multi): a [S, M] device tensor."""
+        if len(Xc.shape) != 2:
+            raise ValueError(f"rff_score_multi: candidates of shape {tuple(Xc.shape)}, [M, D] required")
+        M, D = Xc.shape
+        F, S = self._rff_multi_widths("rff_score_multi", D, W, b, omegas)
+        Xc, W, b, omegas = self.dev(Xc), self.dev(W), self.dev(b).reshape(-1), self.dev(omegas)
+        sc = self.empty(S, M)
+        rc = self.lib.ppbo_rff_score_multi(self.ctx, _ptr(Xc), M, D, _ptr(W), F, _ptr(b), float(sigma_f), _ptr(omegas), S,
+                                           _ptr(sc), self._stream())
+        self._check(rc, "ppbo_rff_score_multi")
+        return sc
+
+    def _rff_search_multi(self, what, cand, D, ls, W, b, sigma_f, omegas, K, sep, iters, tol):
+        if len(cand.shape) != 2 or cand.shape[1] != D:
+            raise ValueError(f"{what}: candidates of shape {tuple(cand.shape)}, [M, {D}] required")
+        M = cand.shape[0]
+        F, S = self._rff_multi_widths(what, D if ls is None else 11, W, b, omegas, int(K))
+        cand, W, b, omegas = self.dev(cand), self.dev(W), self.dev(b).reshape(-1), self.dev(omegas)
+        xs, vals = self.empty(S, K, D), self.empty(S, K)
+        found = torch.zeros(S, dtype=torch.int32, device=self.device)
+        if ls is None:
+            rc = self.lib.ppbo_rff_search_multi(self.ctx, _ptr(cand), M, D, _ptr(W), F, _ptr(b), float(sigma_f), _ptr(omegas),
+                                                S, int(K), float(sep), int(iters), float(tol), _ptr(xs), _ptr(vals),
+                                                _ptr(found), self._stream())
+        else:
+            l = np.ascontiguousarray(ls, dtype=np.float64).reshape(-1)
+            if l.size != 6:
+                raise ValueError(f"{what}: {l.size} length scales, 6 required")
+            rc = self.lib.ppbo_rff_search_multi_camphor(self.ctx, _ptr(cand), M, self._dptr(l), _ptr(W), F, _ptr(b),
+                                                        float(sigma_f), _ptr(omegas), S, int(K), float(sep), int(iters),
+                                                        float(tol), _ptr(xs), _ptr(vals), _ptr(found), self._stream())
+        self._check(rc, f"ppbo_{what}")
+        return xs.cpu().numpy(), vals.cpu().numpy(), found.cpu().numpy()
+
+    def rff_search_multi(self, cand, W, b, sigma_f, omegas, K=32, sep=0.05, iters=200, tol=1e-10):
+        """rff_search for S weight vectors omegas [S, F] over the same candidates (ppbo_rff_search_multi): returns
+        x [S, K, D], values [S, K], found [S] as NumPy; sample s's refined maxima are its rows < found[s], the others
+        hold -inf values."""
+        D = cand.shape[1] if len(cand.shape) == 2 else 0
+        return self._rff_search_multi("rff_search_multi", cand, D, None, W, b, sigma_f, omegas, K, sep, iters, tol)
+
+    def rff_search_multi_camphor(self, cand, ls, W, b, sigma_f, omegas, K=32, sep=0.05, iters=200, tol=1e-10):
+        """rff_search_multi for a camphor-copper basis (ppbo_rff_search_multi_camphor): W [F, 11], cand [M, 6] and the
+        results x [S, K, 6] in the caller's coordinates."""
+        return self._rff_search_multi("rff_search_multi_camphor", cand, 6, ls, W, b, sigma_f, omegas, K, sep, iters, tol)
 
     def rff_terms(self, Phi, omega, m, sigma):
         Phi, omega = self.dev(Phi), self.dev(omega).reshape(-1)

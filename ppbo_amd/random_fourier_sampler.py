@@ -20,7 +20,7 @@ import time
 
 import numpy as np
 
-from .engine import camphor_lengthscales, get_engine
+from .engine import RFF_MULTI_MAX_S, camphor_lengthscales, get_engine
 
 SCORE_CANDIDATES = 65536
 RFF_STARTS = 32            # refined starts per posterior sample (the reference: 5-30 L-BFGS-B runs)
@@ -81,6 +81,30 @@ def camphor_embed_jacobian(x, ls):
             J[c + 1, d] = 2 * np.pi * e[c]
             c += 2
     return J
+
+
+def draw_seed(rng=np.random):
+    """A 63-bit seed for the device draws from the global NumPy stream (np.random.seed keeps whole runs reproducible)."""
+    return int(rng.randint(0, 2 ** 62)) * 2 + int(rng.randint(0, 2))
+
+
+def omega_draws_host(omega_map, cov_diag, z):
+    """The batched weight draw Omega[s] = omega_MAP + sqrt(cov_diag) z[s] (ppbo_rff_omega_draws) for given normals z."""
+    return np.asarray(omega_map, dtype=float) + np.sqrt(np.asarray(cov_diag, dtype=float)) * np.asarray(z, dtype=float)
+
+
+def best_per_sample(x, val, found):
+    """Per sample s of a batched search (x [S, K, D], val [S, K], found [S]): the best of its refined maxima (rows
+    < found[s], finite values only) -> (X [S, D], V [S], the samples without one).  Those rows of X / V hold NaN."""
+    x, val, found = np.asarray(x, dtype=float), np.asarray(val, dtype=float), np.asarray(found).ravel()
+    S, K = val.shape
+    live = (np.arange(K)[None, :] < found[:, None]) & np.isfinite(val)
+    v = np.where(live, val, -np.inf)
+    k = np.argmax(v, axis=1)
+    ok = live.any(axis=1)
+    X = np.where(ok[:, None], x[np.arange(S), k], np.nan)
+    V = np.where(ok, v[np.arange(S), k], np.nan)
+    return X, V, np.flatnonzero(~ok)
 
 
 class Hsampler:
@@ -326,9 +350,27 @@ class Hsampler:
         of the posterior mean on NumPy phi / Dphi; here ONE device enqueue (ppbo_rff_search) scores a rotated resident
         uniform pool plus such perturbations, keeps the RFF_STARTS best that are > 0.05 apart and runs the whole
         projected gradient ascent of each inside one kernel; the best refined point is returned."""
-        import torch
         self._check_W()
         start = time.time()
+        work = self._xstar_candidates()
+        # 100 Barzilai-Borwein iterations per start: the winning start is stationary after ~50 (tests/probes/
+        # rff_ascent_scale.py: the same maximum at 50, 100 and 200), the cap only bounds the starts that keep bouncing
+        l = self._camphor()
+        if l is None:
+            xs, vals = self.eng.rff_search(work, self._dev("W"), self._dev("b"), self.theta[2], omega, K=RFF_STARTS, iters=100)
+        else:       # camphor: the same pool and starts in the caller's coordinates, features on the embedding
+            xs, vals = self.eng.rff_search_camphor(work, l, self._dev("W"), self._dev("b"), self.theta[2], omega,
+                                                   K=RFF_STARTS, iters=100)
+        if self.verbose:
+            print("Optimization of f_approx took " + str(time.time() - start) + " seconds.")
+        if len(vals) == 0 or not np.isfinite(vals).any():
+            return None
+        return xs[int(np.nanargmax(vals))]
+
+    def _xstar_candidates(self):
+        """The candidates of a maximiser search: the model's resident uniform pool under a fresh rotation, followed by
+        uniform perturbations of GP_xstars_local (a [M + k, D] device tensor; draws from the global NumPy stream)."""
+        import torch
         D = self.D
         pool = self.__dict__.get("_pool")
         if pool is None:
@@ -344,19 +386,7 @@ class Hsampler:
         work = torch.empty((M + k, D), dtype=torch.float64, device=self.eng.device)
         self.eng.shift_points(pool, np.random.uniform(0, 1, D), out=work[:M])
         work[M:].copy_(self.eng.dev(near))
-        # 100 Barzilai-Borwein iterations per start: the winning start is stationary after ~50 (tests/probes/
-        # rff_ascent_scale.py: the same maximum at 50, 100 and 200), the cap only bounds the starts that keep bouncing
-        l = self._camphor()
-        if l is None:
-            xs, vals = self.eng.rff_search(work, self._dev("W"), self._dev("b"), self.theta[2], omega, K=RFF_STARTS, iters=100)
-        else:       # camphor: the same pool and starts in the caller's coordinates, features on the embedding
-            xs, vals = self.eng.rff_search_camphor(work, l, self._dev("W"), self._dev("b"), self.theta[2], omega,
-                                                   K=RFF_STARTS, iters=100)
-        if self.verbose:
-            print("Optimization of f_approx took " + str(time.time() - start) + " seconds.")
-        if len(vals) == 0 or not np.isfinite(vals).any():
-            return None
-        return xs[int(np.nanargmax(vals))]
+        return work
 
     def return_xstar_for_dim(self, omega, dim, x_ref):
         self._check_W()
@@ -372,6 +402,58 @@ class Hsampler:
         while xstar is None:
             xstar = self.return_xstar(self.sample_omega())
         return xstar
+
+    # ---- the posterior distribution of the maximiser: many samples per call ----------------------
+    def sample_omegas(self, n, seed=None):
+        """[n, nFeatures] draws of the weights from N(omega_MAP, diag(cov_diag)) on the device (ppbo_rff_omega_draws),
+        bitwise reproducible for a seed; seed=None takes one from the global NumPy stream.  Unlike sample_omega there
+        is no fallback to omega_MAP: without a covariance it raises RuntimeError."""
+        if self.cov_diag is None or self.omega_MAP is None:
+            raise RuntimeError("Hsampler.sample_omegas: no posterior covariance (run update_omega_MAP and "
+                               "update_covariancematrix first)")
+        if seed is None:
+            seed = draw_seed()
+        return self.eng.rff_omega_draws(seed, self._dev("omega_MAP"), self._dev("cov_diag"), int(n))
+
+    def sample_xstars(self, n, omegas=None, seed=None, starts=RFF_STARTS):
+        """n samples of the maximiser x* of the posterior utility: (X [n, D], values [n]), row k the best refined
+        maximiser of sample k in the caller's coordinates (camphor: [n, 6]) and phi(x)^T omega_k there.  What n calls
+        of sample_xstar compute, in batches of up to RFF_MULTI_MAX_S samples per device enqueue (ppbo_rff_search_multi):
+        the candidates are built once per call as in return_xstar and shared by all samples.  omegas [n, F] (host or
+        device) replaces the device draws.  A sample whose search finds nothing is redrawn once per batch; if its
+        redraw finds nothing either, RuntimeError."""
+        self._check_W()
+        n = int(n)
+        if n < 1:
+            raise ValueError(f"sample_xstars: n = {n} samples")
+        F = self.nFeatures if self.W is None else np.shape(self.W)[0]
+        if omegas is None:
+            omegas = self.sample_omegas(n, seed)
+        elif tuple(omegas.shape) != (n, F):
+            raise ValueError(f"sample_xstars: omegas of shape {tuple(omegas.shape)}, [{n}, {F}] required")
+        omegas = self.eng.dev(omegas)
+        work = self._xstar_candidates()
+        l = self._camphor()
+
+        def search(om):
+            if l is None:
+                return self.eng.rff_search_multi(work, self._dev("W"), self._dev("b"), self.theta[2], om, K=starts,
+                                                 iters=100)
+            return self.eng.rff_search_multi_camphor(work, l, self._dev("W"), self._dev("b"), self.theta[2], om,
+                                                     K=starts, iters=100)
+
+        X = np.empty((n, self.D if l is None else 6))
+        V = np.empty(n)
+        for c0 in range(0, n, RFF_MULTI_MAX_S):
+            c1 = min(n, c0 + RFF_MULTI_MAX_S)
+            X[c0:c1], V[c0:c1], missing = best_per_sample(*search(omegas[c0:c1]))
+            if missing.size:
+                # as sample_xstar: a sample without a maximiser is drawn again (once per batch, here)
+                xr, vr, still = best_per_sample(*search(self.sample_omegas(missing.size)))
+                if still.size:
+                    raise RuntimeError(f"sample_xstars: {still.size} redrawn samples found no maximiser")
+                X[c0 + missing], V[c0 + missing] = xr, vr
+        return X, V
 
     def sample_xstar_for_dim(self, dim, x_ref):
         return self.return_xstar_for_dim(self.sample_omega(), dim, x_ref)
