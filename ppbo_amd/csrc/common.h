@@ -11,6 +11,7 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -191,6 +192,25 @@ void ppbo_lds_limit(ppbo_ctx* ctx, const void* kernel_fn, int bytes);
     PPBO_REQUIRE(ctx, ppbo_kernel_id_valid(kernel_id), "kernel_id");                            \
     PPBO_REQUIRE(ctx, (kernel_id) != PPBO_KERNEL_CAMPHOR || (D) == 6, "camphor kernel needs D == 6"); \
   } while (0)
+
+// fn(std::integral_constant<int, KID>{}) for the runtime kernel id, returning fn's status.  RADIAL_ONLY leaves camphor-
+// copper out at compile time (nothing is instantiated for it).  An id without a branch sets `err` on ctx (a NULL ctx
+// sets nothing) and returns -1.
+template <bool RADIAL_ONLY = false, class Fn>
+static inline int ppbo_kernel_dispatch(ppbo_ctx* ctx, int kernel_id, Fn&& fn,
+                                       const char* err = "invalid argument: kernel_id") {
+  switch (kernel_id) {
+    case PPBO_KERNEL_SE: return fn(std::integral_constant<int, PPBO_KERNEL_SE>{});
+    case PPBO_KERNEL_RQ: return fn(std::integral_constant<int, PPBO_KERNEL_RQ>{});
+    case PPBO_KERNEL_MATERN52: return fn(std::integral_constant<int, PPBO_KERNEL_MATERN52>{});
+    case PPBO_KERNEL_MATERN32: return fn(std::integral_constant<int, PPBO_KERNEL_MATERN32>{});
+    case PPBO_KERNEL_CAMPHOR:
+      if constexpr (!RADIAL_ONLY) return fn(std::integral_constant<int, PPBO_KERNEL_CAMPHOR>{});
+      break;
+    default: break;
+  }
+  return ppbo_set_error(ctx, -1, "%s", err);
+}
 
 // ---- kernel-function parameters (host-prepared, passed by value) ------------
 struct KernParams {

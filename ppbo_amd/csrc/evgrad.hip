@@ -222,12 +222,6 @@ __global__ __launch_bounds__(256) void evg_reduce_kernel(const double* __restric
   if (threadIdx.x == 0) out[o] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-template <int KID>
-void evg_pair_launch(dim3 grid, hipStream_t s, const double* X, int N, int D, KernParams p, const double* alpha,
-                     const double* w, const double* Z, const double* S, const double* d_sgn, double* part) {
-  evg_pair_kernel<KID><<<grid, 256, 0, s>>>(X, N, D, p, alpha, w, Z, S, d_sgn, part);
-}
-
 }  // namespace
 
 extern "C" {
@@ -299,17 +293,11 @@ int ppbo_evidence_grad(ppbo_ctx* ctx, int kernel_id, const double* d_X, int N, i
   // the pair reduction
   const KernParams kp = make_kern_params(kernel_id, theta);
   const dim3 pg(nt, nt, nz);
-  switch (kernel_id) {
-    case PPBO_KERNEL_SE: evg_pair_launch<PPBO_KERNEL_SE>(pg, s, d_X, N, D, kp, alpha, w, bC, d_Sigma, lu_out, part); break;
-    case PPBO_KERNEL_RQ: evg_pair_launch<PPBO_KERNEL_RQ>(pg, s, d_X, N, D, kp, alpha, w, bC, d_Sigma, lu_out, part); break;
-    case PPBO_KERNEL_MATERN52:
-      evg_pair_launch<PPBO_KERNEL_MATERN52>(pg, s, d_X, N, D, kp, alpha, w, bC, d_Sigma, lu_out, part);
-      break;
-    case PPBO_KERNEL_MATERN32:
-      evg_pair_launch<PPBO_KERNEL_MATERN32>(pg, s, d_X, N, D, kp, alpha, w, bC, d_Sigma, lu_out, part);
-      break;
-    default: return ppbo_set_error(ctx, -1, "invalid argument: kernel_id");
-  }
+  if (int rc = ppbo_kernel_dispatch<true>(ctx, kernel_id, [&](auto kid) {
+        evg_pair_kernel<decltype(kid)::value><<<pg, 256, 0, s>>>(d_X, N, D, kp, alpha, w, bC, d_Sigma, lu_out, part);
+        return 0;
+      }))
+    return rc;
   evg_reduce_kernel<<<D + 1, 256, 0, s>>>(part, ntiles, D, out);
   PPBO_LAUNCH_CHECK(ctx);
   double h[2];

@@ -662,14 +662,9 @@ int ppbo_fused_score(ppbo_ctx* ctx, const ppbo_model* m, const double* Gt, int l
   }
   a.ncu = ctx->n_cu > 0 ? ctx->n_cu : 256;
   a.delay = (ctx->fused_dbg >> 4) & 15;
-  int rc;
-  switch (m->kernel_id) {
-    case PPBO_KERNEL_SE: rc = fused_launch<PPBO_KERNEL_SE>(ctx, a, s); break;
-    case PPBO_KERNEL_RQ: rc = fused_launch<PPBO_KERNEL_RQ>(ctx, a, s); break;
-    case PPBO_KERNEL_MATERN52: rc = fused_launch<PPBO_KERNEL_MATERN52>(ctx, a, s); break;
-    case PPBO_KERNEL_MATERN32: rc = fused_launch<PPBO_KERNEL_MATERN32>(ctx, a, s); break;
-    default: return ppbo_set_error(ctx, -1, "the one-launch scoring kernel takes the SE, RQ and Matern kernels");
-  }
+  const int rc = ppbo_kernel_dispatch<true>(
+      ctx, m->kernel_id, [&](auto kid) { return fused_launch<decltype(kid)::value>(ctx, a, s); },
+      "the one-launch scoring kernel takes the SE, RQ and Matern kernels");
   if (rc == 0 && a.stamps) {               // mean phase lengths over the workgroups, in us (s_memrealtime ticks at 100 MHz)
     std::vector<unsigned long long> h((size_t)nblk_dbg * 16);
     (void)hipStreamSynchronize(s);

@@ -440,25 +440,17 @@ int ppbo_gram(ppbo_ctx* ctx, int kernel_id, const double* d_X, int N, int D, con
   PpboProfScope pf(ctx, ppbo_ctx::PF_GRAM, s);
   // tile order (PPBO_GRAM_VARIANT: 0 row-major over the upper triangle, 1 diagonal-major, -1 = by size)
   const int order = ctx->gram_variant >= 0 ? ctx->gram_variant : (N >= 4096 ? 1 : 0);
-  if (kernel_id != PPBO_KERNEL_CAMPHOR) {
-#define GM_LAUNCH_K(KIDV, DPV)                                                                               \
-  do {                                                                                                       \
-    if (lds > 64 * 1024) ppbo_lds_limit(ctx, (const void*)gram_mfma_kernel<KIDV, DPV>, (int)lds);            \
-    gram_mfma_kernel<KIDV, DPV><<<nblk, 512, lds, s>>>(d_X, N, D, p, shrink, d_Sigma, nt, order);            \
-  } while (0)
+  // the radial kernels: the MFMA form, one bucket per dimension range
 #define GM_LAUNCH(DPV)                                                                                       \
   do {                                                                                                       \
     constexpr int LDv = DPV + 2;                                                                             \
     constexpr int body = 2 * TS * LDv + 2 * TS + 8 * 16 * 18;                                                \
     const size_t lds = (size_t)body * sizeof(double);                                                        \
-    switch (kernel_id) {                                                                                     \
-      case PPBO_KERNEL_SE: GM_LAUNCH_K(PPBO_KERNEL_SE, DPV); break;                                          \
-      case PPBO_KERNEL_RQ: GM_LAUNCH_K(PPBO_KERNEL_RQ, DPV); break;                                          \
-      case PPBO_KERNEL_MATERN52: GM_LAUNCH_K(PPBO_KERNEL_MATERN52, DPV); break;                               \
-      case PPBO_KERNEL_MATERN32: GM_LAUNCH_K(PPBO_KERNEL_MATERN32, DPV); break;                               \
-      default: return ppbo_set_error(ctx, -1, "invalid argument: kernel_id");                                \
-    }                                                                                                        \
+    if (lds > 64 * 1024) ppbo_lds_limit(ctx, (const void*)gram_mfma_kernel<KID, DPV>, (int)lds);             \
+    gram_mfma_kernel<KID, DPV><<<nblk, 512, lds, s>>>(d_X, N, D, p, shrink, d_Sigma, nt, order);             \
   } while (0)
+  auto radial = [&](auto kid) {
+    constexpr int KID = decltype(kid)::value;
     if (D <= 4) GM_LAUNCH(4);
     else if (D <= 8) GM_LAUNCH(8);
     else if (D <= 12) GM_LAUNCH(12);
@@ -468,8 +460,11 @@ int ppbo_gram(ppbo_ctx* ctx, int kernel_id, const double* d_X, int N, int D, con
     else if (D <= 32) GM_LAUNCH(32);
     else if (D <= 48) GM_LAUNCH(48);
     else GM_LAUNCH(64);
+    return 0;
+  };
 #undef GM_LAUNCH
-#undef GM_LAUNCH_K
+  if (kernel_id != PPBO_KERNEL_CAMPHOR) {
+    if (int rc = ppbo_kernel_dispatch<true>(ctx, kernel_id, radial)) return rc;
   } else {
     const size_t lds = ((size_t)2 * 12 * TS + (size_t)TS * TP) * sizeof(double);     // 12 staged features per row
     gram_kernel<PPBO_KERNEL_CAMPHOR><<<nblk, 256, lds, s>>>(d_X, N, D, p, shrink, d_Sigma, nt);
@@ -497,20 +492,13 @@ int ppbo_cross_cov(ppbo_ctx* ctx, int kernel_id, const double* d_X1, int n1, con
   dim3 grid((n2 + TS - 1) / TS, (n1 + TS - 1) / TS);
   const size_t lds = (size_t)2 * (kernel_id == PPBO_KERNEL_CAMPHOR ? 12 : D) * TS * sizeof(double);
   hipStream_t s = (hipStream_t)stream;
-  if (lds > 64 * 1024) {   // D up to 64 needs up to 64 KB + padding
-    ppbo_lds_limit(ctx, (const void*)crosscov_kernel<PPBO_KERNEL_SE>, 112 * 1024);
-    ppbo_lds_limit(ctx, (const void*)crosscov_kernel<PPBO_KERNEL_RQ>, 112 * 1024);
-    ppbo_lds_limit(ctx, (const void*)crosscov_kernel<PPBO_KERNEL_MATERN52>, 112 * 1024);
-    ppbo_lds_limit(ctx, (const void*)crosscov_kernel<PPBO_KERNEL_MATERN32>, 112 * 1024);
-  }
-  switch (kernel_id) {
-    case PPBO_KERNEL_SE: crosscov_kernel<PPBO_KERNEL_SE><<<grid, 256, lds, s>>>(d_X1, n1, d_X2, n2, D, p, d_K, ldk); break;
-    case PPBO_KERNEL_RQ: crosscov_kernel<PPBO_KERNEL_RQ><<<grid, 256, lds, s>>>(d_X1, n1, d_X2, n2, D, p, d_K, ldk); break;
-    case PPBO_KERNEL_CAMPHOR: crosscov_kernel<PPBO_KERNEL_CAMPHOR><<<grid, 256, lds, s>>>(d_X1, n1, d_X2, n2, D, p, d_K, ldk); break;
-    case PPBO_KERNEL_MATERN52: crosscov_kernel<PPBO_KERNEL_MATERN52><<<grid, 256, lds, s>>>(d_X1, n1, d_X2, n2, D, p, d_K, ldk); break;
-    case PPBO_KERNEL_MATERN32: crosscov_kernel<PPBO_KERNEL_MATERN32><<<grid, 256, lds, s>>>(d_X1, n1, d_X2, n2, D, p, d_K, ldk); break;
-    default: return ppbo_set_error(ctx, -1, "invalid argument: kernel_id");
-  }
+  if (int rc = ppbo_kernel_dispatch(ctx, kernel_id, [&](auto kid) {
+        // D up to 64 needs up to 64 KB + padding (camphor-copper: 12 staged features, never)
+        if (lds > 64 * 1024) ppbo_lds_limit(ctx, (const void*)crosscov_kernel<decltype(kid)::value>, 112 * 1024);
+        crosscov_kernel<decltype(kid)::value><<<grid, 256, lds, s>>>(d_X1, n1, d_X2, n2, D, p, d_K, ldk);
+        return 0;
+      }))
+    return rc;
   PPBO_LAUNCH_CHECK(ctx);
   return 0;
 }

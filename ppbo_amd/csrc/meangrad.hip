@@ -337,6 +337,40 @@ static inline int select_capacity(int D) {
   return cap > 4096 ? 4096 : (cap < 64 ? 64 : cap);
 }
 
+// The start selection of every search: B score vectors (trials, samples) of Mt candidates each, cut into Tg groups of G
+// consecutive rows (Tg <= select_capacity), reduced to K starts per vector.  alloc() lays out WS_SEARCH as
+//   head[n_head] | scores[B][Mt] | gval[B][Tg] | starts[B][K][D] | gidx[B][Tg] (int) | counts (int)
+// with room for n_counts ints beyond 16 of slack; the caller scores into `scores`, then select() runs.
+struct StartSelection {
+  long long Mt; int B, D, K;
+  int G = 0, Tg = 0;
+  double *head = nullptr, *scores = nullptr, *gval = nullptr, *starts = nullptr;
+  int *gidx = nullptr, *counts = nullptr;
+  bool alloc(ppbo_ctx* ctx, size_t n_head, size_t n_counts) {
+    const int T_MAX = select_capacity(D);
+    G = (int)((Mt + T_MAX - 1) / T_MAX);
+    Tg = (int)((Mt + G - 1) / G);
+    const size_t nd = n_head + (size_t)B * Mt + (size_t)B * Tg + (size_t)B * K * D;
+    head = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_SEARCH, nd * sizeof(double) + ((size_t)B * Tg + n_counts + 16) * sizeof(int));
+    if (!head) return false;
+    scores = head + n_head;
+    gval = scores + (size_t)B * Mt;
+    starts = gval + (size_t)B * Tg;
+    gidx = (int*)(starts + (size_t)B * K * D);
+    counts = gidx + (size_t)B * Tg;
+    return true;
+  }
+  // each group's best row survives (group_max_kernel); one workgroup per vector picks its starts, pairwise more than
+  // sep apart, among the survivors held in LDS (select_starts_kernel) and writes their number to out_counts[b].  The
+  // coordinates come from cand (rows) or tc (tc.pool set).
+  void select(ppbo_ctx* ctx, double sep, const double* cand, const TrialCands& tc, int* out_counts, hipStream_t s) const {
+    group_max_kernel<<<dim3((Tg + 255) / 256, B), 256, 0, s>>>(scores, Mt, G, Tg, gval, gidx);
+    const size_t sel_lds = (size_t)Tg * (1 + D) * sizeof(double);
+    if (sel_lds > 64 * 1024) ppbo_lds_limit(ctx, (const void*)select_starts_kernel, 150 * 1024);
+    select_starts_kernel<<<B, 1024, sel_lds, s>>>(gval, gidx, Tg, cand, D, K, sep * sep, starts, out_counts, tc);
+  }
+};
+
 // mu and its gradient at the point held in LDS (sx), partial sums of this thread's rows reduced into red[wave][.]
 // TR: X is given TRANSPOSED ([D][N]): the threads of a wavefront then read consecutive addresses per coordinate.  With
 // row-major X every lane reads its own row (a 8 D-byte segment each, 64 cache lines per load instruction) and the
@@ -557,22 +591,14 @@ struct CamphorRffEval {
 };
 
 // the batched forms (ppbo_rff_search_multi / _camphor): one launch runs S x K starts, workgroup s K + k on sample s, whose
-// weights follow sample 0's at s F.  They ARE the single-sample evaluations with omega moved to the workgroup's sample.
-template <int DP, int NT>
-struct RffMultiEval {
-  RffEval<DP, NT> ev; int per;               // ev.omega: the [S, F] weights; per = K starts per sample
-  __device__ __forceinline__ void operator()(const double* sx, double (*red)[DP + 1]) const {
-    RffEval<DP, NT> e = ev;
-    e.omega = ev.omega + (size_t)(blockIdx.x / per) * ev.F;
-    e(sx, red);
-  }
-};
-template <int NT>
-struct CamphorRffMultiEval {
-  static constexpr int DP = CamphorRffEval<NT>::DP;
-  CamphorRffEval<NT> ev; int per;
-  __device__ __forceinline__ void operator()(const double* sx, double (*red)[DP + 1]) const {
-    CamphorRffEval<NT> e = ev;
+// weights follow sample 0's at s F.  They ARE the single-sample evaluations (RffEval, CamphorRffEval) with omega moved
+// to the workgroup's sample.
+template <class EV>
+struct RffSampleEval {
+  EV ev; int per;                            // ev.omega: the [S, F] weights; per = K starts per sample
+  template <class RED>
+  __device__ __forceinline__ void operator()(const double* sx, RED red) const {
+    EV e = ev;
     e.omega = ev.omega + (size_t)(blockIdx.x / per) * ev.F;
     e(sx, red);
   }
@@ -702,7 +728,7 @@ int launch_mean_ascent(ppbo_ctx* ctx, const ppbo_model* m, const KernParams& p, 
         break;                                                                                                        \
       }                                                                                                               \
     }                                                                                                                 \
-    if constexpr (KID == PPBO_KERNEL_CAMPHOR && DP == 8) {                                                            \
+    if constexpr (KID == PPBO_KERNEL_CAMPHOR) {                                                                       \
       if (cam) {                                                                                                      \
         CamphorMeanEval<DP, NT> cev{Xt, m->N, p.sf2, *cam, m->d_alpha};                                               \
         bb_ascent_kernel<DP, CamphorMeanEval<DP, NT>, NT><<<K, NT, 0, s>>>(cev, m->D, starts, count, iters, tol, x_out, mu_out, it_out, per_trial); \
@@ -713,95 +739,67 @@ int launch_mean_ascent(ppbo_ctx* ctx, const ppbo_model* m, const KernParams& p, 
   } while (0)
   const bool tall = m->N >= 1024;
   if (KID == PPBO_KERNEL_CAMPHOR || m->D <= 8) { if (tall) MA_LAUNCH(8, 1024); else MA_LAUNCH(8, 256); }
-  else if (m->D <= 24) { if (tall) MA_LAUNCH(24, 512); else MA_LAUNCH(24, 256); }
-  else MA_LAUNCH(64, 256);
+  else if constexpr (KID != PPBO_KERNEL_CAMPHOR) {     // (camphor-copper: D = 6)
+    if (m->D <= 24) { if (tall) MA_LAUNCH(24, 512); else MA_LAUNCH(24, 256); }
+    else MA_LAUNCH(64, 256);
+  }
 #undef MA_LAUNCH
   return 0;
 }
 
-int launch_rff_ascent(ppbo_ctx* ctx, const double* W_rows, int F, int D, const double* b, const double* omega, double amp,
-                      const double* starts, const int* count, int K, int iters, double tol, double* x_out,
-                      double* v_out, hipStream_t s) {
-  double* W = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_TRANSPOSE, (size_t)F * D * sizeof(double));
+// one ascent launch of an RFF posterior sample: S = 0 one sample, K workgroups; S > 0 S samples of K starts each, S K
+// workgroups (RffSampleEval), count[s] starts exist
+template <int DP, int NT, class EV>
+void rff_ascent_run(const EV& ev, int D, int S, int K, const double* starts, const int* count, int iters, double tol,
+                    double* x_out, double* v_out, hipStream_t s) {
+  if (S > 0)
+    bb_ascent_kernel<DP, RffSampleEval<EV>, NT><<<S * K, NT, 0, s>>>(RffSampleEval<EV>{ev, K}, D, starts, count, iters, tol,
+                                                                     x_out, v_out, nullptr, K);
+  else
+    bb_ascent_kernel<DP, EV, NT><<<K, NT, 0, s>>>(ev, D, starts, count, iters, tol, x_out, v_out, nullptr, 0);
+}
+
+// the RFF ascent over the basis W_rows [F][D] (h_l = NULL) or the camphor basis W_rows [F][11] with starts and results in
+// the caller's six coordinates (h_l: its length scales)
+int launch_rff_ascent(ppbo_ctx* ctx, const double* W_rows, int F, int D, const double* h_l, const double* b,
+                      const double* omega, double amp, const double* starts, const int* count, int S, int K, int iters,
+                      double tol, double* x_out, double* v_out, hipStream_t s) {
+  const int DW = h_l ? CAMPHOR_E : D;
+  double* W = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_TRANSPOSE, (size_t)F * DW * sizeof(double));
   if (!W) return (int)hipErrorOutOfMemory;
-  transpose_rows_kernel<<<(F + 255) / 256, 256, 0, s>>>(W_rows, F, D, W);
-#define RA_LAUNCH(DP, NT)                                                                                      \
-  do {                                                                                                         \
-    RffEval<DP, NT> ev{W, F, D, b, omega, amp, make_rff_poly(1.0)};                                            \
-    bb_ascent_kernel<DP, RffEval<DP, NT>, NT><<<K, NT, 0, s>>>(ev, D, starts, count, iters, tol, x_out, v_out, nullptr, 0); \
-  } while (0)
+  transpose_rows_kernel<<<(F + 255) / 256, 256, 0, s>>>(W_rows, F, DW, W);
+  const RffPoly P = make_rff_poly(1.0);
   const bool wide = F >= 1024;
-  if (D <= 8) { if (wide) RA_LAUNCH(8, 1024); else RA_LAUNCH(8, 256); }
-  else if (D <= 24) { if (wide) RA_LAUNCH(24, 512); else RA_LAUNCH(24, 256); }
-  else RA_LAUNCH(64, 256);
+  if (h_l) {
+    const CamphorInvL L = camphor_inv_l(h_l);
+#define RA_LAUNCH(NT) \
+  rff_ascent_run<8, NT>(CamphorRffEval<NT>{W, F, b, omega, amp, P, L}, CAMPHOR_D, S, K, starts, count, iters, tol, x_out, v_out, s)
+    // 11 embedded columns of point, gradient and feature row: ~170 VGPRs, so at most two wavefronts per SIMD (1024
+    // threads would spill)
+    if (wide) RA_LAUNCH(512); else RA_LAUNCH(256);
 #undef RA_LAUNCH
-  return 0;
-}
-
-// the camphor form of launch_rff_ascent: W_rows [F][11], starts / results in the caller's six coordinates
-int launch_rff_ascent_camphor(ppbo_ctx* ctx, const double* W_rows, int F, const double* b, const double* omega, double amp,
-                              const CamphorInvL& L, const double* starts, const int* count, int K, int iters, double tol,
-                              double* x_out, double* v_out, hipStream_t s) {
-  double* W = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_TRANSPOSE, (size_t)F * CAMPHOR_E * sizeof(double));
-  if (!W) return (int)hipErrorOutOfMemory;
-  transpose_rows_kernel<<<(F + 255) / 256, 256, 0, s>>>(W_rows, F, CAMPHOR_E, W);
-#define RC_LAUNCH(NT)                                                                                          \
-  do {                                                                                                         \
-    CamphorRffEval<NT> ev{W, F, b, omega, amp, make_rff_poly(1.0), L};                                         \
-    bb_ascent_kernel<8, CamphorRffEval<NT>, NT><<<K, NT, 0, s>>>(ev, CAMPHOR_D, starts, count, iters, tol, x_out, v_out, nullptr, 0); \
-  } while (0)
-  // 11 embedded columns of point, gradient and feature row: ~170 VGPRs, so at most two wavefronts per SIMD (1024
-  // threads would spill)
-  if (F >= 1024) RC_LAUNCH(512); else RC_LAUNCH(256);
-#undef RC_LAUNCH
-  return 0;
-}
-
-// launch_rff_ascent / launch_rff_ascent_camphor for S samples of K starts each: S K workgroups, count[s] starts exist
-int launch_rff_ascent_multi(ppbo_ctx* ctx, const double* W_rows, int F, int D, const double* b, const double* omegas,
-                            double amp, const double* starts, const int* count, int S, int K, int iters, double tol,
-                            double* x_out, double* v_out, hipStream_t s) {
-  double* W = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_TRANSPOSE, (size_t)F * D * sizeof(double));
-  if (!W) return (int)hipErrorOutOfMemory;
-  transpose_rows_kernel<<<(F + 255) / 256, 256, 0, s>>>(W_rows, F, D, W);
-#define RAM_LAUNCH(DP, NT)                                                                                     \
-  do {                                                                                                         \
-    RffMultiEval<DP, NT> ev{RffEval<DP, NT>{W, F, D, b, omegas, amp, make_rff_poly(1.0)}, K};                  \
-    bb_ascent_kernel<DP, RffMultiEval<DP, NT>, NT><<<S * K, NT, 0, s>>>(ev, D, starts, count, iters, tol, x_out, v_out, nullptr, K); \
-  } while (0)
-  const bool wide = F >= 1024;
-  if (D <= 8) { if (wide) RAM_LAUNCH(8, 1024); else RAM_LAUNCH(8, 256); }
-  else if (D <= 24) { if (wide) RAM_LAUNCH(24, 512); else RAM_LAUNCH(24, 256); }
-  else RAM_LAUNCH(64, 256);
-#undef RAM_LAUNCH
-  return 0;
-}
-
-int launch_rff_ascent_multi_camphor(ppbo_ctx* ctx, const double* W_rows, int F, const double* b, const double* omegas,
-                                    double amp, const CamphorInvL& L, const double* starts, const int* count, int S, int K,
-                                    int iters, double tol, double* x_out, double* v_out, hipStream_t s) {
-  double* W = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_TRANSPOSE, (size_t)F * CAMPHOR_E * sizeof(double));
-  if (!W) return (int)hipErrorOutOfMemory;
-  transpose_rows_kernel<<<(F + 255) / 256, 256, 0, s>>>(W_rows, F, CAMPHOR_E, W);
-#define RCM_LAUNCH(NT)                                                                                         \
-  do {                                                                                                         \
-    CamphorRffMultiEval<NT> ev{CamphorRffEval<NT>{W, F, b, omegas, amp, make_rff_poly(1.0), L}, K};            \
-    bb_ascent_kernel<8, CamphorRffMultiEval<NT>, NT><<<S * K, NT, 0, s>>>(ev, CAMPHOR_D, starts, count, iters, tol, x_out, v_out, nullptr, K); \
-  } while (0)
-  if (F >= 1024) RCM_LAUNCH(512); else RCM_LAUNCH(256);
-#undef RCM_LAUNCH
+  } else {
+#define RA_LAUNCH(DP, NT) \
+  rff_ascent_run<DP, NT>(RffEval<DP, NT>{W, F, D, b, omega, amp, P}, D, S, K, starts, count, iters, tol, x_out, v_out, s)
+    if (D <= 8) { if (wide) RA_LAUNCH(8, 1024); else RA_LAUNCH(8, 256); }
+    else if (D <= 24) { if (wide) RA_LAUNCH(24, 512); else RA_LAUNCH(24, 256); }
+    else RA_LAUNCH(64, 256);
+#undef RA_LAUNCH
+  }
   return 0;
 }
 
 template <int KID>
-void launch_mean_grad(const ppbo_model* m, const KernParams& p, const double* d_Xc, int M, double* d_mu,
-                      double* d_grad, hipStream_t s) {
-  if (KID == PPBO_KERNEL_CAMPHOR || m->D <= 8)
-    mean_grad_kernel<KID, 8><<<M, 256, 0, s>>>(m->d_X, m->N, m->D, p, m->d_alpha, d_Xc, d_mu, d_grad);
-  else if (m->D <= 24)
-    mean_grad_kernel<KID, 24><<<M, 256, 0, s>>>(m->d_X, m->N, m->D, p, m->d_alpha, d_Xc, d_mu, d_grad);
-  else
-    mean_grad_kernel<KID, 64><<<M, 256, 0, s>>>(m->d_X, m->N, m->D, p, m->d_alpha, d_Xc, d_mu, d_grad);
+int launch_mean_grad(const ppbo_model* m, const KernParams& p, const double* d_Xc, int M, double* d_mu, double* d_grad,
+                     hipStream_t s) {
+#define MG_LAUNCH(DP) mean_grad_kernel<KID, DP><<<M, 256, 0, s>>>(m->d_X, m->N, m->D, p, m->d_alpha, d_Xc, d_mu, d_grad)
+  if (KID == PPBO_KERNEL_CAMPHOR || m->D <= 8) MG_LAUNCH(8);
+  else if constexpr (KID != PPBO_KERNEL_CAMPHOR) {     // (camphor-copper: D = 6)
+    if (m->D <= 24) MG_LAUNCH(24);
+    else MG_LAUNCH(64);
+  }
+#undef MG_LAUNCH
+  return 0;
 }
 
 }  // namespace
@@ -816,14 +814,10 @@ extern "C" int ppbo_mean_grad(ppbo_ctx* ctx, const ppbo_model* m, const double* 
   if (M == 0) return 0;
   hipStream_t s = (hipStream_t)stream;
   const KernParams p = make_kern_params(m->kernel_id, m->theta);
-  switch (m->kernel_id) {
-    case PPBO_KERNEL_SE: launch_mean_grad<PPBO_KERNEL_SE>(m, p, d_Xc, (int)M, d_mu, d_grad, s); break;
-    case PPBO_KERNEL_RQ: launch_mean_grad<PPBO_KERNEL_RQ>(m, p, d_Xc, (int)M, d_mu, d_grad, s); break;
-    case PPBO_KERNEL_CAMPHOR: launch_mean_grad<PPBO_KERNEL_CAMPHOR>(m, p, d_Xc, (int)M, d_mu, d_grad, s); break;
-    case PPBO_KERNEL_MATERN52: launch_mean_grad<PPBO_KERNEL_MATERN52>(m, p, d_Xc, (int)M, d_mu, d_grad, s); break;
-    case PPBO_KERNEL_MATERN32: launch_mean_grad<PPBO_KERNEL_MATERN32>(m, p, d_Xc, (int)M, d_mu, d_grad, s); break;
-    default: return ppbo_set_error(ctx, -1, "invalid argument: kernel_id");
-  }
+  if (int rc = ppbo_kernel_dispatch(ctx, m->kernel_id, [&](auto kid) {
+        return launch_mean_grad<decltype(kid)::value>(m, p, d_Xc, (int)M, d_mu, d_grad, s);
+      }))
+    return rc;
   PPBO_LAUNCH_CHECK(ctx);
   return 0;
 }
@@ -871,16 +865,12 @@ static int mean_ascent_impl(ppbo_ctx* ctx, const ppbo_model* m, const double* d_
     if (int rc = ppbo_upload_async(ctx, d_scale, h_scale, (size_t)m->D * sizeof(double), s)) return rc;
   }
   const KernParams p = make_kern_params(m->kernel_id, m->theta);
-  int rc = 0;
-  switch (m->kernel_id) {
-    case PPBO_KERNEL_SE: rc = launch_mean_ascent<PPBO_KERNEL_SE>(ctx, m, p, d_starts, nullptr, K, iters, tol, d_x, d_mu, d_iters, s, 0, d_scale); break;
-    case PPBO_KERNEL_RQ: rc = launch_mean_ascent<PPBO_KERNEL_RQ>(ctx, m, p, d_starts, nullptr, K, iters, tol, d_x, d_mu, d_iters, s, 0, d_scale); break;
-    case PPBO_KERNEL_CAMPHOR: rc = launch_mean_ascent<PPBO_KERNEL_CAMPHOR>(ctx, m, p, d_starts, nullptr, K, iters, tol, d_x, d_mu, d_iters, s, 0, nullptr, cam); break;
-    case PPBO_KERNEL_MATERN52: rc = launch_mean_ascent<PPBO_KERNEL_MATERN52>(ctx, m, p, d_starts, nullptr, K, iters, tol, d_x, d_mu, d_iters, s, 0, d_scale); break;
-    case PPBO_KERNEL_MATERN32: rc = launch_mean_ascent<PPBO_KERNEL_MATERN32>(ctx, m, p, d_starts, nullptr, K, iters, tol, d_x, d_mu, d_iters, s, 0, d_scale); break;
-    default: return ppbo_set_error(ctx, -1, "invalid argument: kernel_id");
-  }
-  if (rc) return rc;
+  // (d_scale is NULL for camphor-copper, cam for every other kernel)
+  if (int rc = ppbo_kernel_dispatch(ctx, m->kernel_id, [&](auto kid) {
+        return launch_mean_ascent<decltype(kid)::value>(ctx, m, p, d_starts, nullptr, K, iters, tol, d_x, d_mu, d_iters, s,
+                                                        0, d_scale, cam);
+      }))
+    return rc;
   PPBO_LAUNCH_CHECK(ctx);
   return 0;
 }
@@ -948,40 +938,22 @@ extern "C" int ppbo_mean_search(ppbo_ctx* ctx, const ppbo_model* m, const double
   PPBO_REQUIRE(ctx, d_cand && d_x && d_mu && M > 0 && M < ((int64_t)1 << 31), "candidates / outputs");
   PPBO_REQUIRE(ctx, K > 0 && K <= 1024 && sep >= 0 && iters >= 0 && tol >= 0, "K (<= 1024) / sep / iters / tol");
   hipStream_t s = (hipStream_t)stream;
-  const int D = m->D;
-  const int T_MAX = select_capacity(D);
-  const int G = (int)((M + T_MAX - 1) / T_MAX);
-  const int T = (int)((M + G - 1) / G);
-  // workspace: mu[M] | gval[T] | starts[K*D] | gidx[T] (int) | count (int)
-  const size_t nd = (size_t)M + T + (size_t)K * D;
-  double* mu = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_SEARCH, nd * sizeof(double) + ((size_t)T + 16) * sizeof(int));
-  if (!mu) return (int)hipErrorOutOfMemory;
-  double* gval = mu + M;
-  double* starts = gval + T;
-  int* gidx = (int*)(starts + (size_t)K * D);
-  int* count = gidx + T;
+  StartSelection sel{M, 1, m->D, K};
+  if (!sel.alloc(ctx, 0, 0)) return (int)hipErrorOutOfMemory;
   ppbo_model mean_only = *m;
   mean_only.d_G = nullptr;
-  if (int rc = ppbo_predict(ctx, &mean_only, d_cand, M, PPBO_SCORE_MEAN, 0.0, mu, nullptr, nullptr, nullptr, nullptr, stream))
+  if (int rc = ppbo_predict(ctx, &mean_only, d_cand, M, PPBO_SCORE_MEAN, 0.0, sel.scores, nullptr, nullptr, nullptr, nullptr,
+                            stream))
     return rc;
-  group_max_kernel<<<(T + 255) / 256, 256, 0, s>>>(mu, M, G, T, gval, gidx);
-  {
-    const size_t sel_lds = (size_t)T * (1 + D) * sizeof(double);
-    if (sel_lds > 64 * 1024) ppbo_lds_limit(ctx, (const void*)select_starts_kernel, 150 * 1024);
-    select_starts_kernel<<<1, 1024, sel_lds, s>>>(gval, gidx, T, d_cand, D, K, sep * sep, starts, count, TrialCands{});
-  }
+  sel.select(ctx, sep, d_cand, TrialCands{}, sel.counts, s);
   const KernParams p = make_kern_params(m->kernel_id, m->theta);
-  switch (m->kernel_id) {
-    case PPBO_KERNEL_SE: if (int rc = launch_mean_ascent<PPBO_KERNEL_SE>(ctx, m, p, starts, count, K, iters, tol, d_x, d_mu, nullptr, s)) return rc; break;
-    case PPBO_KERNEL_RQ: if (int rc = launch_mean_ascent<PPBO_KERNEL_RQ>(ctx, m, p, starts, count, K, iters, tol, d_x, d_mu, nullptr, s)) return rc; break;
-    case PPBO_KERNEL_CAMPHOR: if (int rc = launch_mean_ascent<PPBO_KERNEL_CAMPHOR>(ctx, m, p, starts, count, K, iters, tol, d_x, d_mu, nullptr, s)) return rc; break;
-    case PPBO_KERNEL_MATERN52: if (int rc = launch_mean_ascent<PPBO_KERNEL_MATERN52>(ctx, m, p, starts, count, K, iters, tol, d_x, d_mu, nullptr, s)) return rc; break;
-    case PPBO_KERNEL_MATERN32: if (int rc = launch_mean_ascent<PPBO_KERNEL_MATERN32>(ctx, m, p, starts, count, K, iters, tol, d_x, d_mu, nullptr, s)) return rc; break;
-    default: return ppbo_set_error(ctx, -1, "invalid argument: kernel_id");
-  }
+  if (int rc = ppbo_kernel_dispatch(ctx, m->kernel_id, [&](auto kid) {
+        return launch_mean_ascent<decltype(kid)::value>(ctx, m, p, sel.starts, sel.counts, K, iters, tol, d_x, d_mu, nullptr, s);
+      }))
+    return rc;
   PPBO_LAUNCH_CHECK(ctx);
   if (h_found) {
-    PPBO_HIP_CHECK(ctx, hipMemcpyAsync(h_found, count, sizeof(int), hipMemcpyDeviceToHost, s));
+    PPBO_HIP_CHECK(ctx, hipMemcpyAsync(h_found, sel.counts, sizeof(int), hipMemcpyDeviceToHost, s));
     PPBO_HIP_CHECK(ctx, hipStreamSynchronize(s));
   }
   return 0;
@@ -999,12 +971,12 @@ static void screen_split(int blocks_x, int nb, int N, int& n_split, int& rows_pe
 }
 
 template <int KID>
-void launch_screen(const ppbo_model* m, const KernParams& p, const TrialCands& tc, int nb, int rows_per_split, int n_split,
-                   double* part, int extra_trial, hipStream_t s) {
+int launch_screen(const ppbo_model* m, const KernParams& p, const TrialCands& tc, int nb, int rows_per_split, int n_split,
+                  double* part, int extra_trial, hipStream_t s) {
   const long long Mt = tc.M + tc.E;
   const dim3 grid((unsigned)((Mt + SCR_T * SCR_CPT - 1) / (SCR_T * SCR_CPT)), n_split, nb);
 #define SCR_LAUNCH(DP) mean_screen_kernel<KID, DP><<<grid, SCR_T, 0, s>>>(m->d_X, m->N, m->D, p, m->d_alpha, tc, rows_per_split, n_split, part, extra_trial)
-  if (KID == PPBO_KERNEL_CAMPHOR) SCR_LAUNCH(6);
+  if constexpr (KID == PPBO_KERNEL_CAMPHOR) SCR_LAUNCH(6);     // (D = 6: a bucket of its own)
   else if (m->D <= 4) SCR_LAUNCH(4);
   else if (m->D <= 8) SCR_LAUNCH(8);
   else if (m->D <= 12) SCR_LAUNCH(12);
@@ -1015,6 +987,7 @@ void launch_screen(const ppbo_model* m, const KernParams& p, const TrialCands& t
   else if (m->D <= 48) SCR_LAUNCH(48);
   else SCR_LAUNCH(64);
 #undef SCR_LAUNCH
+  return 0;
 }
 
 static int mean_search_multi_impl(ppbo_ctx* ctx, const ppbo_model* m, const double* d_pool, int64_t M,
@@ -1040,21 +1013,13 @@ static int mean_search_multi_impl(ppbo_ctx* ctx, const ppbo_model* m, const doub
   hipStream_t s = (hipStream_t)stream;
   const int D = m->D;
   const long long Mt = M + E;
-  const int T_MAX = select_capacity(D);
-  const int G = (int)((Mt + T_MAX - 1) / T_MAX);
-  const int Tg = (int)((Mt + G - 1) / G);
-  // workspace: shifts[T][D] + xprev[D] | mu[T][Mt] | gval[T][Tg] | starts[T][K][D] | gidx[T][Tg] (int) | counts[T] (int)
+  // workspace: shifts[T][D] + xprev[D] ahead of the start selection's T score vectors; counts[T]
   // (ARD: scale[D] + 1 / scale[D] and the design's rows in the caller's coordinates [N][D] in a slot of their own)
-  const size_t nd = (size_t)(T + 1) * D + (size_t)T * Mt + (size_t)T * Tg + (size_t)T * K * D;
-  double* base = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_SEARCH, nd * sizeof(double) + ((size_t)T * Tg + T + 16) * sizeof(int));
-  if (!base) return (int)hipErrorOutOfMemory;
-  double* shifts = base;
+  StartSelection sel{Mt, T, D, K};
+  if (!sel.alloc(ctx, (size_t)(T + 1) * D, T)) return (int)hipErrorOutOfMemory;
+  double* shifts = sel.head;
   double* xprev = shifts + (size_t)T * D;
-  double* mu = xprev + D;
-  double* gval = mu + (size_t)T * Mt;
-  double* starts = gval + (size_t)T * Tg;
-  int* gidx = (int*)(starts + (size_t)T * K * D);
-  int* counts = gidx + (size_t)T * Tg;
+  double* mu = sel.scores;
   // the shifts and the previous x* leave the host through pinned upload slots of the ctx (ppbo_upload_async): the call
   // has consumed h_shifts / h_xprev when it returns and never blocks on the stream
   if (int rc = ppbo_upload_async(ctx, shifts, h_shifts, (size_t)T * D * sizeof(double), s)) return rc;
@@ -1095,14 +1060,10 @@ static int mean_search_multi_impl(ppbo_ctx* ctx, const ppbo_model* m, const doub
       TrialCands tb = tc;
       tb.shifts = shifts + (size_t)t0 * D;
       const int extra_trial = (t0 == 0 && E > 0) ? 0 : -1;     // only the job's trial 0 sees the extra points
-      switch (m->kernel_id) {
-        case PPBO_KERNEL_SE: launch_screen<PPBO_KERNEL_SE>(m, p, tb, nb, rows_per_split, n_split, part, extra_trial, s); break;
-        case PPBO_KERNEL_RQ: launch_screen<PPBO_KERNEL_RQ>(m, p, tb, nb, rows_per_split, n_split, part, extra_trial, s); break;
-        case PPBO_KERNEL_CAMPHOR: launch_screen<PPBO_KERNEL_CAMPHOR>(m, p, tb, nb, rows_per_split, n_split, part, extra_trial, s); break;
-        case PPBO_KERNEL_MATERN52: launch_screen<PPBO_KERNEL_MATERN52>(m, p, tb, nb, rows_per_split, n_split, part, extra_trial, s); break;
-        case PPBO_KERNEL_MATERN32: launch_screen<PPBO_KERNEL_MATERN32>(m, p, tb, nb, rows_per_split, n_split, part, extra_trial, s); break;
-        default: return ppbo_set_error(ctx, -1, "invalid argument: kernel_id");
-      }
+      if (int rc = ppbo_kernel_dispatch(ctx, m->kernel_id, [&](auto kid) {
+            return launch_screen<decltype(kid)::value>(m, p, tb, nb, rows_per_split, n_split, part, extra_trial, s);
+          }))
+        return rc;
       screen_sum_kernel<<<dim3((unsigned)((Mt + 255) / 256), nb), 256, 0, s>>>(part, n_split, Mt, M, extra_trial, mu + (size_t)t0 * Mt);
       PPBO_LAUNCH_CHECK(ctx);
     }
@@ -1140,13 +1101,11 @@ static int mean_search_multi_impl(ppbo_ctx* ctx, const ppbo_model* m, const doub
         screen_split((int)((nt + SCR_T * SCR_CPT - 1) / (SCR_T * SCR_CPT)), 1, m->N, n_split, rows_per_split);
         double* part = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_PART, (size_t)n_split * nt * sizeof(double));
         if (!part) return (int)hipErrorOutOfMemory;
-        switch (sm->kernel_id) {   // (camphor-copper has no ARD form: refused above; the camphor model screens as SE)
-          case PPBO_KERNEL_SE: launch_screen<PPBO_KERNEL_SE>(sm, sp, tr, 1, rows_per_split, n_split, part, 0, s); break;
-          case PPBO_KERNEL_RQ: launch_screen<PPBO_KERNEL_RQ>(m, p, tr, 1, rows_per_split, n_split, part, 0, s); break;
-          case PPBO_KERNEL_MATERN52: launch_screen<PPBO_KERNEL_MATERN52>(m, p, tr, 1, rows_per_split, n_split, part, 0, s); break;
-          case PPBO_KERNEL_MATERN32: launch_screen<PPBO_KERNEL_MATERN32>(m, p, tr, 1, rows_per_split, n_split, part, 0, s); break;
-          default: return ppbo_set_error(ctx, -1, "invalid argument: kernel_id");
-        }
+        // (camphor-copper has no ARD form: refused above; the camphor model screens as SE)
+        if (int rc = ppbo_kernel_dispatch<true>(ctx, sm->kernel_id, [&](auto kid) {
+              return launch_screen<decltype(kid)::value>(sm, sp, tr, 1, rows_per_split, n_split, part, 0, s);
+            }))
+          return rc;
         screen_sum_kernel<<<dim3((unsigned)((nt + 255) / 256), 1), 256, 0, s>>>(part, n_split, nt, 0, 0, mu + (size_t)t * Mt);
         PPBO_LAUNCH_CHECK(ctx);
       } else if (int rc = ppbo_predict(ctx, &mean_only, erows, nt, PPBO_SCORE_MEAN, 0.0, mu + (size_t)t * Mt, nullptr, nullptr,
@@ -1159,21 +1118,14 @@ static int mean_search_multi_impl(ppbo_ctx* ctx, const ppbo_model* m, const doub
       }
     }
   }
-  group_max_kernel<<<dim3((Tg + 255) / 256, T), 256, 0, s>>>(mu, Mt, G, Tg, gval, gidx);
-  {
-    const size_t sel_lds = (size_t)Tg * (1 + D) * sizeof(double);
-    if (sel_lds > 64 * 1024) ppbo_lds_limit(ctx, (const void*)select_starts_kernel, 150 * 1024);
-    select_starts_kernel<<<T, 1024, sel_lds, s>>>(gval, gidx, Tg, nullptr, D, K, sep * sep, starts, counts, tc);
-  }
+  sel.select(ctx, sep, nullptr, tc, sel.counts, s);
   PPBO_LAUNCH_CHECK(ctx);
-  switch (m->kernel_id) {
-    case PPBO_KERNEL_SE: if (int rc = launch_mean_ascent<PPBO_KERNEL_SE>(ctx, m, p, starts, counts, T * K, iters, tol, d_x, d_mu, nullptr, s, K, d_scale)) return rc; break;
-    case PPBO_KERNEL_RQ: if (int rc = launch_mean_ascent<PPBO_KERNEL_RQ>(ctx, m, p, starts, counts, T * K, iters, tol, d_x, d_mu, nullptr, s, K, d_scale)) return rc; break;
-    case PPBO_KERNEL_CAMPHOR: if (int rc = launch_mean_ascent<PPBO_KERNEL_CAMPHOR>(ctx, m, p, starts, counts, T * K, iters, tol, d_x, d_mu, nullptr, s, K, nullptr, cam)) return rc; break;
-    case PPBO_KERNEL_MATERN52: if (int rc = launch_mean_ascent<PPBO_KERNEL_MATERN52>(ctx, m, p, starts, counts, T * K, iters, tol, d_x, d_mu, nullptr, s, K, d_scale)) return rc; break;
-    case PPBO_KERNEL_MATERN32: if (int rc = launch_mean_ascent<PPBO_KERNEL_MATERN32>(ctx, m, p, starts, counts, T * K, iters, tol, d_x, d_mu, nullptr, s, K, d_scale)) return rc; break;
-    default: return ppbo_set_error(ctx, -1, "invalid argument: kernel_id");
-  }
+  // (d_scale is NULL for camphor-copper, cam for every other kernel)
+  if (int rc = ppbo_kernel_dispatch(ctx, m->kernel_id, [&](auto kid) {
+        return launch_mean_ascent<decltype(kid)::value>(ctx, m, p, sel.starts, sel.counts, T * K, iters, tol, d_x, d_mu,
+                                                        nullptr, s, K, d_scale, cam);
+      }))
+    return rc;
   PPBO_LAUNCH_CHECK(ctx);
   return 0;
 }
@@ -1209,40 +1161,46 @@ extern "C" int ppbo_mean_search_multi_camphor(ppbo_ctx* ctx, const ppbo_model* m
                                 d_x, d_mu, nullptr, stream, m, h_l, &cc);
 }
 
+// the single-sample RFF search: l = NULL the plain basis at D columns, else the camphor basis (d_cand in the caller's six
+// coordinates, scored on its embedding)
+static int rff_search_impl(ppbo_ctx* ctx, const double* d_cand, int64_t M, int D, const double* h_l, const double* d_W,
+                           int F, const double* d_b, double sigma_f, const double* d_omega, int K, double sep, int iters,
+                           double tol, double* d_x, double* d_val, int* h_found, void* stream) {
+  PPBO_REQUIRE(ctx, K > 0 && K <= 1024 && sep >= 0 && iters >= 0 && tol >= 0, "K (<= 1024) / sep / iters / tol");
+  hipStream_t s = (hipStream_t)stream;
+  StartSelection sel{M, 1, D, K};
+  if (!sel.alloc(ctx, 0, 0)) return (int)hipErrorOutOfMemory;
+  const double* rows = d_cand;
+  int Dr = D;
+  if (h_l) {   // screening on the embedded candidates: the plain scorer at D = 11
+    double* e = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_CAMPHOR_ROWS, (size_t)M * CAMPHOR_E * sizeof(double));
+    if (!e) return (int)hipErrorOutOfMemory;
+    if (int rc = ppbo_camphor_embed(ctx, d_cand, M, h_l, e, stream)) return rc;
+    rows = e;
+    Dr = CAMPHOR_E;
+  }
+  if (int rc = ppbo_rff_score(ctx, rows, M, Dr, d_W, F, d_b, sigma_f, d_omega, sel.scores, nullptr, nullptr, stream)) return rc;
+  // start selection on the caller-coordinate rows: sep is in the caller's units
+  sel.select(ctx, sep, d_cand, TrialCands{}, sel.counts, s);
+  if (int rc = launch_rff_ascent(ctx, d_W, F, D, h_l, d_b, d_omega, std::sqrt(2.0 * sigma_f * sigma_f / (double)F), sel.starts,
+                                 sel.counts, 0, K, iters, tol, d_x, d_val, s))
+    return rc;
+  PPBO_LAUNCH_CHECK(ctx);
+  if (h_found) {
+    PPBO_HIP_CHECK(ctx, hipMemcpyAsync(h_found, sel.counts, sizeof(int), hipMemcpyDeviceToHost, s));
+    PPBO_HIP_CHECK(ctx, hipStreamSynchronize(s));
+  }
+  return 0;
+}
+
 extern "C" int ppbo_rff_search(ppbo_ctx* ctx, const double* d_cand, int64_t M, int D, const double* d_W, int F,
                                const double* d_b, double sigma_f, const double* d_omega, int K, double sep, int iters,
                                double tol, double* d_x, double* d_val, int* h_found, void* stream) {
   PPBO_ENTER(ctx);
   PPBO_REQUIRE(ctx, d_cand && d_W && d_b && d_omega && d_x && d_val, "null pointer");
   PPBO_REQUIRE(ctx, M > 0 && M < ((int64_t)1 << 31) && D > 0 && D <= 64 && F > 0, "sizes (D <= 64)");
-  PPBO_REQUIRE(ctx, K > 0 && K <= 1024 && sep >= 0 && iters >= 0 && tol >= 0, "K (<= 1024) / sep / iters / tol");
-  hipStream_t s = (hipStream_t)stream;
-  const int T_MAX = select_capacity(D);
-  const int G = (int)((M + T_MAX - 1) / T_MAX);
-  const int T = (int)((M + G - 1) / G);
-  const size_t nd = (size_t)M + T + (size_t)K * D;
-  double* sc = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_SEARCH, nd * sizeof(double) + ((size_t)T + 16) * sizeof(int));
-  if (!sc) return (int)hipErrorOutOfMemory;
-  double* gval = sc + M;
-  double* starts = gval + T;
-  int* gidx = (int*)(starts + (size_t)K * D);
-  int* count = gidx + T;
-  if (int rc = ppbo_rff_score(ctx, d_cand, M, D, d_W, F, d_b, sigma_f, d_omega, sc, nullptr, nullptr, stream)) return rc;
-  group_max_kernel<<<(T + 255) / 256, 256, 0, s>>>(sc, M, G, T, gval, gidx);
-  {
-    const size_t sel_lds = (size_t)T * (1 + D) * sizeof(double);
-    if (sel_lds > 64 * 1024) ppbo_lds_limit(ctx, (const void*)select_starts_kernel, 150 * 1024);
-    select_starts_kernel<<<1, 1024, sel_lds, s>>>(gval, gidx, T, d_cand, D, K, sep * sep, starts, count, TrialCands{});
-  }
-  if (int rc = launch_rff_ascent(ctx, d_W, F, D, d_b, d_omega, std::sqrt(2.0 * sigma_f * sigma_f / (double)F), starts, count, K,
-                                 iters, tol, d_x, d_val, s))
-    return rc;
-  PPBO_LAUNCH_CHECK(ctx);
-  if (h_found) {
-    PPBO_HIP_CHECK(ctx, hipMemcpyAsync(h_found, count, sizeof(int), hipMemcpyDeviceToHost, s));
-    PPBO_HIP_CHECK(ctx, hipStreamSynchronize(s));
-  }
-  return 0;
+  return rff_search_impl(ctx, d_cand, M, D, nullptr, d_W, F, d_b, sigma_f, d_omega, K, sep, iters, tol, d_x, d_val, h_found,
+                         stream);
 }
 
 extern "C" int ppbo_rff_search_camphor(ppbo_ctx* ctx, const double* d_cand, int64_t M, const double* h_l, const double* d_W,
@@ -1252,40 +1210,8 @@ extern "C" int ppbo_rff_search_camphor(ppbo_ctx* ctx, const double* d_cand, int6
   PPBO_REQUIRE(ctx, d_cand && d_W && d_b && d_omega && d_x && d_val, "null pointer");
   PPBO_REQUIRE_CAMPHOR_L(ctx, h_l);
   PPBO_REQUIRE(ctx, M > 0 && M < ((int64_t)1 << 31) && F > 0, "sizes");
-  PPBO_REQUIRE(ctx, K > 0 && K <= 1024 && sep >= 0 && iters >= 0 && tol >= 0, "K (<= 1024) / sep / iters / tol");
-  hipStream_t s = (hipStream_t)stream;
-  const int D = CAMPHOR_D;
-  const int T_MAX = select_capacity(D);
-  const int G = (int)((M + T_MAX - 1) / T_MAX);
-  const int T = (int)((M + G - 1) / G);
-  const size_t nd = (size_t)M + T + (size_t)K * D;
-  double* sc = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_SEARCH, nd * sizeof(double) + ((size_t)T + 16) * sizeof(int));
-  if (!sc) return (int)hipErrorOutOfMemory;
-  double* gval = sc + M;
-  double* starts = gval + T;
-  int* gidx = (int*)(starts + (size_t)K * D);
-  int* count = gidx + T;
-  // screening on the embedded candidates: the SE scorer at D = 11
-  double* e = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_CAMPHOR_ROWS, (size_t)M * CAMPHOR_E * sizeof(double));
-  if (!e) return (int)hipErrorOutOfMemory;
-  if (int rc = ppbo_camphor_embed(ctx, d_cand, M, h_l, e, stream)) return rc;
-  if (int rc = ppbo_rff_score(ctx, e, M, CAMPHOR_E, d_W, F, d_b, sigma_f, d_omega, sc, nullptr, nullptr, stream)) return rc;
-  // start selection on the caller-coordinate rows: sep is in the caller's units
-  group_max_kernel<<<(T + 255) / 256, 256, 0, s>>>(sc, M, G, T, gval, gidx);
-  {
-    const size_t sel_lds = (size_t)T * (1 + D) * sizeof(double);
-    if (sel_lds > 64 * 1024) ppbo_lds_limit(ctx, (const void*)select_starts_kernel, 150 * 1024);
-    select_starts_kernel<<<1, 1024, sel_lds, s>>>(gval, gidx, T, d_cand, D, K, sep * sep, starts, count, TrialCands{});
-  }
-  if (int rc = launch_rff_ascent_camphor(ctx, d_W, F, d_b, d_omega, std::sqrt(2.0 * sigma_f * sigma_f / (double)F),
-                                         camphor_inv_l(h_l), starts, count, K, iters, tol, d_x, d_val, s))
-    return rc;
-  PPBO_LAUNCH_CHECK(ctx);
-  if (h_found) {
-    PPBO_HIP_CHECK(ctx, hipMemcpyAsync(h_found, count, sizeof(int), hipMemcpyDeviceToHost, s));
-    PPBO_HIP_CHECK(ctx, hipStreamSynchronize(s));
-  }
-  return 0;
+  return rff_search_impl(ctx, d_cand, M, CAMPHOR_D, h_l, d_W, F, d_b, sigma_f, d_omega, K, sep, iters, tol, d_x, d_val,
+                         h_found, stream);
 }
 
 // ppbo_rff_search(_camphor) for S samples over one candidate set: l = NULL the plain basis at D columns, else the camphor
@@ -1298,39 +1224,27 @@ static int rff_search_multi_impl(ppbo_ctx* ctx, const double* d_cand, int64_t M,
   PPBO_REQUIRE(ctx, S > 0 && S <= PPBO_RFF_MULTI_MAX_S, "S (1 .. PPBO_RFF_MULTI_MAX_S samples)");
   PPBO_REQUIRE(ctx, K > 0 && K <= 1024 && sep >= 0 && iters >= 0 && tol >= 0, "K (<= 1024) / sep / iters / tol");
   hipStream_t s = (hipStream_t)stream;
-  const int T_MAX = select_capacity(D);
-  const int G = (int)((M + T_MAX - 1) / T_MAX);
-  const int T = (int)((M + G - 1) / G);
-  // workspace: scores[S][M] | gval[S][T] | starts[S][K][D] | gidx[S][T] (int); the start counts go to d_found
-  const size_t nd = (size_t)S * M + (size_t)S * T + (size_t)S * K * D;
-  double* sc = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_SEARCH, nd * sizeof(double) + ((size_t)S * T + 16) * sizeof(int));
-  if (!sc) return ppbo_set_error(ctx, (int)hipErrorOutOfMemory, "invalid argument: no workspace for %d samples of %lld candidates",
-                                 S, (long long)M);
-  double* gval = sc + (size_t)S * M;
-  double* starts = gval + (size_t)S * T;
-  int* gidx = (int*)(starts + (size_t)S * K * D);
+  // one "trial" per sample over the shared candidates: each sample's K starts are > sep apart in its own scores; the
+  // start counts go to d_found
+  StartSelection sel{M, S, D, K};
+  if (!sel.alloc(ctx, 0, 0))
+    return ppbo_set_error(ctx, (int)hipErrorOutOfMemory, "invalid argument: no workspace for %d samples of %lld candidates",
+                          S, (long long)M);
+  const double* rows = d_cand;
+  int Dr = D;
   if (h_l) {
     double* e = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_CAMPHOR_ROWS, (size_t)M * CAMPHOR_E * sizeof(double));
     if (!e) return ppbo_set_error(ctx, (int)hipErrorOutOfMemory, "invalid argument: no workspace for the embedded candidates");
     if (int rc = ppbo_camphor_embed(ctx, d_cand, M, h_l, e, stream)) return rc;
-    if (int rc = ppbo_rff_score_multi(ctx, e, M, CAMPHOR_E, d_W, F, d_b, sigma_f, d_omegas, S, sc, stream)) return rc;
-  } else if (int rc = ppbo_rff_score_multi(ctx, d_cand, M, D, d_W, F, d_b, sigma_f, d_omegas, S, sc, stream)) {
-    return rc;
+    rows = e;
+    Dr = CAMPHOR_E;
   }
-  // one "trial" per sample over the shared candidates: each sample's K starts are > sep apart in its own scores
-  group_max_kernel<<<dim3((T + 255) / 256, S), 256, 0, s>>>(sc, M, G, T, gval, gidx);
-  {
-    const size_t sel_lds = (size_t)T * (1 + D) * sizeof(double);
-    if (sel_lds > 64 * 1024) ppbo_lds_limit(ctx, (const void*)select_starts_kernel, 150 * 1024);
-    select_starts_kernel<<<S, 1024, sel_lds, s>>>(gval, gidx, T, d_cand, D, K, sep * sep, starts, d_found, TrialCands{});
-  }
+  if (int rc = ppbo_rff_score_multi(ctx, rows, M, Dr, d_W, F, d_b, sigma_f, d_omegas, S, sel.scores, stream)) return rc;
+  sel.select(ctx, sep, d_cand, TrialCands{}, d_found, s);
   PPBO_LAUNCH_CHECK(ctx);
-  const double amp = std::sqrt(2.0 * sigma_f * sigma_f / (double)F);
-  const int rc = h_l ? launch_rff_ascent_multi_camphor(ctx, d_W, F, d_b, d_omegas, amp, camphor_inv_l(h_l), starts, d_found,
-                                                       S, K, iters, tol, d_x, d_val, s)
-                     : launch_rff_ascent_multi(ctx, d_W, F, D, d_b, d_omegas, amp, starts, d_found, S, K, iters, tol, d_x,
-                                               d_val, s);
-  if (rc) return rc;
+  if (int rc = launch_rff_ascent(ctx, d_W, F, D, h_l, d_b, d_omegas, std::sqrt(2.0 * sigma_f * sigma_f / (double)F),
+                                 sel.starts, d_found, S, K, iters, tol, d_x, d_val, s))
+    return rc;
   PPBO_LAUNCH_CHECK(ctx);
   return 0;
 }

@@ -883,8 +883,10 @@ int launch_kstar(const ppbo_model* m, const KernParams& p, const double* d_Xc, i
                                                           q_per_split, n_q, edge_k0)
   if (m->kstar_fp32) {       // the fp32-tolerance report: the BASELINE shapes get their own bucket, the rest a generic one
     if (KID == PPBO_KERNEL_CAMPHOR || m->D <= 6) KS_LAUNCH32(6);
-    else if (m->D <= 20) KS_LAUNCH32(20);
-    else KS_LAUNCH32(64);
+    else if constexpr (KID != PPBO_KERNEL_CAMPHOR) {     // (camphor-copper: D = 6)
+      if (m->D <= 20) KS_LAUNCH32(20);
+      else KS_LAUNCH32(64);
+    }
     return 0;
   }
 #undef KS_LAUNCH32
@@ -892,7 +894,7 @@ int launch_kstar(const ppbo_model* m, const KernParams& p, const double* d_Xc, i
   kstar_kernel<KID, DP><<<grid, KS_THREADS, 0, s>>>(m->d_X, m->N, m->D, p, m->d_alpha, ld, lo, mblk, d_Xc, M, \
                                                     Kt, ldk, mu_part, with_lam ? t_part : nullptr,            \
                                                     q_per_split, n_q, edge_k0)
-  if (KID == PPBO_KERNEL_CAMPHOR) KS_LAUNCH(12);      // the feature form: 12 staged values per row
+  if constexpr (KID == PPBO_KERNEL_CAMPHOR) KS_LAUNCH(12);      // the feature form: 12 staged values per row
   else if (m->D <= 4) KS_LAUNCH(4);
   else if (m->D <= 6) KS_LAUNCH(6);
   else if (m->D <= 8) KS_LAUNCH(8);
@@ -912,14 +914,11 @@ int launch_kstar(const ppbo_model* m, const KernParams& p, const double* d_Xc, i
 int dispatch_kstar(const ppbo_model* m, const double* d_Xc, int M, double* Kt, int ldk, double* mu_part,
                    double* t_part, int q_per_split, int n_split, bool with_lam, hipStream_t s, int edge_k0 = -1) {
   const KernParams p = make_kern_params(m->kernel_id, m->theta);
-  switch (m->kernel_id) {
-    case PPBO_KERNEL_SE: return launch_kstar<PPBO_KERNEL_SE>(m, p, d_Xc, M, Kt, ldk, mu_part, t_part, q_per_split, n_split, with_lam, edge_k0, s);
-    case PPBO_KERNEL_RQ: return launch_kstar<PPBO_KERNEL_RQ>(m, p, d_Xc, M, Kt, ldk, mu_part, t_part, q_per_split, n_split, with_lam, edge_k0, s);
-    case PPBO_KERNEL_CAMPHOR: return launch_kstar<PPBO_KERNEL_CAMPHOR>(m, p, d_Xc, M, Kt, ldk, mu_part, t_part, q_per_split, n_split, with_lam, edge_k0, s);
-    case PPBO_KERNEL_MATERN52: return launch_kstar<PPBO_KERNEL_MATERN52>(m, p, d_Xc, M, Kt, ldk, mu_part, t_part, q_per_split, n_split, with_lam, edge_k0, s);
-    case PPBO_KERNEL_MATERN32: return launch_kstar<PPBO_KERNEL_MATERN32>(m, p, d_Xc, M, Kt, ldk, mu_part, t_part, q_per_split, n_split, with_lam, edge_k0, s);
-    default: return -1;   // (check_model rejects any other id first)
-  }
+  // (no ctx: an unknown id returns -1 and sets no message; check_model rejects any such id first)
+  return ppbo_kernel_dispatch(nullptr, m->kernel_id, [&](auto kid) {
+    return launch_kstar<decltype(kid)::value>(m, p, d_Xc, M, Kt, ldk, mu_part, t_part, q_per_split, n_split, with_lam,
+                                              edge_k0, s);
+  });
 }
 
 int check_model(ppbo_ctx* ctx, const ppbo_model* m) {
@@ -1271,14 +1270,11 @@ int line_acq_impl(ppbo_ctx* ctx, const ppbo_model* model, const double* d_grid, 
     }
     score_kernel<<<score_blocks(M), SC_THREADS, 0, s>>>(part, n_split_eff, nullptr, nullptr, 0, M, 0.0, PPBO_SCORE_MEAN,
                                                         0.0, 0, mu, nullptr, nullptr, nullptr);
-    switch (model->kernel_id) {
-      case PPBO_KERNEL_SE: line_prior_kernel<PPBO_KERNEL_SE><<<Bc, 256, 0, s>>>(xg, G, D, p, shrink, cov); break;
-      case PPBO_KERNEL_RQ: line_prior_kernel<PPBO_KERNEL_RQ><<<Bc, 256, 0, s>>>(xg, G, D, p, shrink, cov); break;
-      case PPBO_KERNEL_CAMPHOR: line_prior_kernel<PPBO_KERNEL_CAMPHOR><<<Bc, 256, 0, s>>>(xg, G, D, p, shrink, cov); break;
-      case PPBO_KERNEL_MATERN52: line_prior_kernel<PPBO_KERNEL_MATERN52><<<Bc, 256, 0, s>>>(xg, G, D, p, shrink, cov); break;
-      case PPBO_KERNEL_MATERN32: line_prior_kernel<PPBO_KERNEL_MATERN32><<<Bc, 256, 0, s>>>(xg, G, D, p, shrink, cov); break;
-      default: return ppbo_set_error(ctx, -1, "invalid argument: kernel_id");
-    }
+    if (int rc = ppbo_kernel_dispatch(ctx, model->kernel_id, [&](auto kid) {
+          line_prior_kernel<decltype(kid)::value><<<Bc, 256, 0, s>>>(xg, G, D, p, shrink, cov);
+          return 0;
+        }))
+      return rc;
     PPBO_LAUNCH_CHECK(ctx);
     GemmArgs y{};  // Y = G K*
     y.A = Gq; y.lda = Nk; y.B = Kt; y.ldb = ld; y.C = Y; y.ldc = ld;

@@ -901,40 +901,42 @@ class Engine:
         self._check(rc, "ppbo_randn")
         return out
 
+    def _rff_search(self, what, cand, ls, W, b, sigma_f, omega, K, sep, iters, tol):
+        cand, W, b, omega = self.dev(cand), self.dev(W), self.dev(b).reshape(-1), self.dev(omega).reshape(-1)
+        if ls is None:
+            M, D = cand.shape
+        else:
+            if cand.dim() != 2 or cand.shape[1] != 6:
+                raise ValueError(f"{what}: candidates of shape {tuple(cand.shape)}, [M, 6] required")
+            M, D = cand.shape[0], 6
+        F = self._rff_widths(what, D if ls is None else 11, W, b, omega)
+        xs, vals = self.empty(K, D), self.empty(K)
+        found = C.c_int(0)
+        if ls is None:
+            rc = self.lib.ppbo_rff_search(self.ctx, _ptr(cand), M, D, _ptr(W), F, _ptr(b), float(sigma_f), _ptr(omega),
+                                          int(K), float(sep), int(iters), float(tol), _ptr(xs), _ptr(vals), C.byref(found),
+                                          self._stream())
+        else:
+            l = np.ascontiguousarray(ls, dtype=np.float64).reshape(-1)
+            if l.size != 6:
+                raise ValueError(f"{what}: {l.size} length scales, 6 required")
+            rc = self.lib.ppbo_rff_search_camphor(self.ctx, _ptr(cand), M, self._dptr(l), _ptr(W), F, _ptr(b), float(sigma_f),
+                                                  _ptr(omega), int(K), float(sep), int(iters), float(tol), _ptr(xs), _ptr(vals),
+                                                  C.byref(found), self._stream())
+        self._check(rc, f"ppbo_{what}")
+        n = found.value
+        return xs[:n].cpu().numpy(), vals[:n].cpu().numpy()
+
     def rff_search(self, cand, W, b, sigma_f, omega, K=32, sep=0.05, iters=200, tol=1e-10):
         """Device-resident maximiser of phi(x)^T omega over the rows of `cand` (ppbo_rff_search): refined maxima
         x[found, D], values[found] as NumPy arrays."""
-        cand, W, b, omega = self.dev(cand), self.dev(W), self.dev(b).reshape(-1), self.dev(omega).reshape(-1)
-        M, D = cand.shape
-        F = self._rff_widths("rff_search", D, W, b, omega)
-        xs, vals = self.empty(K, D), self.empty(K)
-        found = C.c_int(0)
-        rc = self.lib.ppbo_rff_search(self.ctx, _ptr(cand), M, D, _ptr(W), F, _ptr(b), float(sigma_f), _ptr(omega), int(K),
-                                      float(sep), int(iters), float(tol), _ptr(xs), _ptr(vals), C.byref(found), self._stream())
-        self._check(rc, "ppbo_rff_search")
-        n = found.value
-        return xs[:n].cpu().numpy(), vals[:n].cpu().numpy()
+        return self._rff_search("rff_search", cand, None, W, b, sigma_f, omega, K, sep, iters, tol)
 
     def rff_search_camphor(self, cand, ls, W, b, sigma_f, omega, K=32, sep=0.05, iters=200, tol=1e-10):
         """rff_search for a camphor-copper basis (ppbo_rff_search_camphor): W [F, 11] acts on the embedding e(x) of the
         six length scales ls; cand [M, 6], the box, sep and the refined maxima x[found, 6] are in the caller's
         coordinates.  Returns x[found, 6], values[found] as NumPy arrays."""
-        cand, W, b, omega = self.dev(cand), self.dev(W), self.dev(b).reshape(-1), self.dev(omega).reshape(-1)
-        if cand.dim() != 2 or cand.shape[1] != 6:
-            raise ValueError(f"rff_search_camphor: candidates of shape {tuple(cand.shape)}, [M, 6] required")
-        M = cand.shape[0]
-        F = self._rff_widths("rff_search_camphor", 11, W, b, omega)
-        l = np.ascontiguousarray(ls, dtype=np.float64).reshape(-1)
-        if l.size != 6:
-            raise ValueError(f"rff_search_camphor: {l.size} length scales, 6 required")
-        xs, vals = self.empty(K, 6), self.empty(K)
-        found = C.c_int(0)
-        rc = self.lib.ppbo_rff_search_camphor(self.ctx, _ptr(cand), M, self._dptr(l), _ptr(W), F, _ptr(b), float(sigma_f),
-                                              _ptr(omega), int(K), float(sep), int(iters), float(tol), _ptr(xs), _ptr(vals),
-                                              C.byref(found), self._stream())
-        self._check(rc, "ppbo_rff_search_camphor")
-        n = found.value
-        return xs[:n].cpu().numpy(), vals[:n].cpu().numpy()
+        return self._rff_search("rff_search_camphor", cand, ls, W, b, sigma_f, omega, K, sep, iters, tol)
 
     # ---- batches of posterior samples (S weight vectors per call) ---------------------------
     @staticmethod
