@@ -518,6 +518,34 @@ PPBO_API int ppbo_rff_search_multi_camphor(ppbo_ctx* ctx, const double* d_cand, 
                           const double* d_W, int F, const double* d_b, double sigma_f, const double* d_omegas, int S, int K,
                           double sep, int iters, double tol, double* d_x, double* d_val, int* d_found, void* stream);
 
+/* ---- pathwise posterior samples (decoupled sampling, Wilson et al. 2020, on the Laplace posterior) -----------------
+ * g_s(x) = phi(x)^T w_s + k(x, X) v_s with prior weights w_s ~ N(0, I_F) and v_s = Sigma^-1 (f_s - Phi(X)^T w_s),
+ * f_s ~ N(f_MAP, P): a draw from the GP posterior itself (no reference counterpart: src/random_fourier_sampler.py samples
+ * the weight-space posterior with a diagonal covariance).  The host assembles d_Wp[S,F] and d_V[S,N] from resident
+ * pieces (ppbo_randn, ppbo_potrf, ppbo_dgemm); these entries evaluate and maximise the S paths.  Radial kernels only
+ * (SE, RQ, Matern-5/2, Matern-3/2): PPBO_KERNEL_CAMPHOR is "invalid argument".
+ *
+ * ppbo_path_score_multi: d_score[s][c] = phi(x_c)^T w_s + sum_i V[s][i] k(x_c, x_i), d_score[S,M] row-major.  One launch:
+ * per candidate tile the cosine tile and the tile of k(x_c, x_i) are formed in turn and contracted with [W_prior | V]
+ * on the fp64 matrix cores, inner dimension F + N in one fixed order (a repeated call is bitwise equal).  d_Xc[M,D],
+ * d_W[F,D] and d_X[N,D] in the SAME coordinates, theta = (sigma, l, sigma_f) the kernel's there; per-dimension length
+ * scales: the rows scaled by s = 1 / l as the model holds them, W unscaled (w_f / s), theta[1] = 1.
+ * "invalid argument" as ppbo_rff_score_multi, and N < 1. */
+PPBO_API int ppbo_path_score_multi(ppbo_ctx* ctx, int kernel_id, const double theta[3], const double* d_Xc, int64_t M, int D,
+                          const double* d_W, int F, const double* d_b, const double* d_Wp, const double* d_X, int N,
+                          const double* d_V, int S, double* d_score, void* stream);
+
+/* ppbo_rff_search_multi for S paths: scores every candidate for every path (ppbo_path_score_multi), picks each path's K
+ * best starts > sep apart in its own scores, and ascends all S x K starts in one launch with the value and gradient of
+ * g_s (both halves) evaluated per iterate.  d_cand[M,D], the [0,1]^D box, sep and d_x[S,K,D] in the caller's coordinates
+ * with d_W[F,D] the basis there; h_scale = NULL: d_X[N,D] the design, theta its kernel's; h_scale[D] = 1 / l (ARD): d_X
+ * the scaled rows and theta[1] = 1.  d_x / d_val / d_found as ppbo_rff_search_multi.  Enqueued only.
+ * "invalid argument" as ppbo_path_score_multi, K outside 1 .. 1024, a scale that is not positive and finite. */
+PPBO_API int ppbo_path_search_multi(ppbo_ctx* ctx, int kernel_id, const double theta[3], const double* d_cand, int64_t M,
+                          int D, const double* d_W, int F, const double* d_b, const double* d_Wp, const double* d_X, int N,
+                          const double* d_V, const double* h_scale, int S, int K, double sep, int iters, double tol,
+                          double* d_x, double* d_val, int* d_found, void* stream);
+
 /* ---- generic fp64 MFMA GEMM (exposed for tests and host-side composition) ----
  * C[M,N] = alpha op(A) op(B) + beta C.  transA/transB: 0 = as stored, 1 = transposed.  Row-major storage with leading
  * dimensions lda >= (transA ? M : K), ldb >= (transB ? K : N), ldc >= N; a shorter one is "invalid argument".  K = 0

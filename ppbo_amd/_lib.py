@@ -102,6 +102,9 @@ SIGNATURES = {
     "ppbo_rff_search_multi": [_vp, _vp, _i64, _i, _vp, _i, _vp, _d, _vp, _i, _i, _d, _i, _d, _vp, _vp, _vp, _vp],
     "ppbo_rff_search_multi_camphor": [_vp, _vp, _i64, C.POINTER(_d), _vp, _i, _vp, _d, _vp, _i, _i, _d, _i, _d, _vp, _vp,
                                       _vp, _vp],
+    "ppbo_path_score_multi": [_vp, _i, _dp3, _vp, _i64, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp],
+    "ppbo_path_search_multi": [_vp, _i, _dp3, _vp, _i64, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, C.POINTER(_d), _i, _i, _d, _i, _d,
+                               _vp, _vp, _vp, _vp],
     "ppbo_rff_terms": [_vp, _vp, _i, _i, _i, _d, _vp, C.POINTER(_d), _vp, _vp, _vp],
     "ppbo_rff_omega_map": [_vp, _vp, _i, _i, _i, _d, _vp, _i, _d, C.POINTER(_d), C.POINTER(_d), C.POINTER(_i), _vp],
     "ppbo_lu_slogdet": [_vp, _vp, _i, _i, C.POINTER(_d), C.POINTER(_d), C.POINTER(_i), _vp],

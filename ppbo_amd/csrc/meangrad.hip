@@ -604,6 +604,68 @@ struct RffSampleEval {
   }
 };
 
+// one pathwise posterior sample (ppbo_path_search_multi): g(x) = a sum_f w_f cos(w_f.x + b_f) + sum_i v_i k(x, x_i) and its
+// gradient -- RffEval's feature half (RFF_FEATURE_BODY) and the kernel half of eval_mean_grad (radial kernels, the design
+// transposed [D][N]) with sample s's v_s for alpha, summed into ONE set of records: the design rows first, then the
+// features, each thread's share in index order.  scale (ARD, D device values s_d, else NULL): the box and the basis live
+// in the caller's coordinates x, the design holds the scaled rows, so the kernel half runs at s (.) x and its gradient
+// is taken back (d / d x_d = s_d d / d x~_d) before the feature half joins it.  One workgroup = one start of sample
+// blockIdx.x / per, whose weights follow sample 0's at s F (wp) and s N (v), as RffSampleEval moves omega.
+template <int KID, int DP, int NT>
+struct PathEval {
+  static_assert(kid_radial<KID>, "radial kernels only");
+  const double* W; int F, D; const double* b; const double* wp; double amp; RffPoly P;   // W: the transposed basis [D][F]
+  const double* X; int N; KernParams p; const double* v; const double* scale; int per;
+  __device__ __forceinline__ void operator()(const double* sx, double (*red)[DP + 1]) const {
+    const int smp = blockIdx.x / per;
+    double xc[DP], g[DP];
+#pragma unroll
+    for (int d = 0; d < DP; ++d) { xc[d] = (scale && d < D) ? sx[d] * scale[d] : sx[d]; g[d] = 0.0; }
+    double m = 0.0;
+    const double* __restrict__ alpha = v + (size_t)smp * N;
+    for (int i = threadIdx.x; i < N; i += NT) {
+      const double* __restrict__ xi = X + i;
+      double dx[DP], s = 0.0;
+#pragma unroll
+      for (int d = 0; d < DP; ++d) {
+        dx[d] = (d < D) ? xc[d] - xi[(size_t)d * N] : 0.0;
+        s += dx[d] * dx[d];
+      }
+      double w, coef;
+      if constexpr (kid_matern<KID>) {
+        const MaternAE ae = matern_ae<KID>(s, p);
+        w = alpha[i] * matern_value<KID>(ae, p.sf2);
+        coef = alpha[i] * matern_grad<KID>(ae, p);
+      } else {
+        w = alpha[i] * kern_finish<KID>(s, p);
+        coef = kern_grad_coef<KID>(s, w, p);
+      }
+      m += w;
+#pragma unroll
+      for (int d = 0; d < DP; ++d) g[d] += coef * dx[d];
+    }
+    if (scale) {
+#pragma unroll
+      for (int d = 0; d < DP; ++d) {
+        if (d < D) g[d] *= scale[d];
+        xc[d] = sx[d];
+      }
+    }
+    const double* __restrict__ omega = wp + (size_t)smp * F;
+    for (int f = threadIdx.x; f < F; f += NT) RFF_FEATURE_BODY(DP)
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    m = row16_sum_dpp(m);
+#pragma unroll
+    for (int d = 0; d < DP; ++d) g[d] = row16_sum_dpp(g[d]);
+    if ((lane & 15) == 0) {
+      double* r = red[4 * wave + (lane >> 4)];
+      r[DP] = m;
+#pragma unroll
+      for (int d = 0; d < DP; ++d) r[d] = g[d];
+    }
+  }
+};
+
 // fixed-order sum of the NW records of column c
 template <int NW, int DP>
 __device__ __forceinline__ double red_col(const double (*red)[DP + 1], int c) {
@@ -786,6 +848,32 @@ int launch_rff_ascent(ppbo_ctx* ctx, const double* W_rows, int F, int D, const d
     else RA_LAUNCH(64, 256);
 #undef RA_LAUNCH
   }
+  return 0;
+}
+
+// the pathwise ascent: S x K workgroups over the basis W_rows [F][D] and the design X_rows [N][D], both transposed into
+// one workspace slot ([D][F] | [D][N])
+template <int KID>
+int launch_path_ascent(ppbo_ctx* ctx, const KernParams& p, const double* W_rows, int F, int D, const double* b,
+                       const double* wp, double amp, const double* X_rows, int N, const double* v, const double* d_scale,
+                       const double* starts, const int* count, int S, int K, int iters, double tol, double* x_out,
+                       double* v_out, hipStream_t s) {
+  double* W = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_TRANSPOSE, ((size_t)F + N) * D * sizeof(double));
+  if (!W) return (int)hipErrorOutOfMemory;
+  double* Xt = W + (size_t)F * D;
+  transpose_rows_kernel<<<(F + 255) / 256, 256, 0, s>>>(W_rows, F, D, W);
+  transpose_rows_kernel<<<(N + 255) / 256, 256, 0, s>>>(X_rows, N, D, Xt);
+  const RffPoly P = make_rff_poly(1.0);
+  const bool wide = F + N >= 1024;
+#define PA_LAUNCH(DP, NT)                                                                                          \
+  bb_ascent_kernel<DP, PathEval<KID, DP, NT>, NT><<<S * K, NT, 0, s>>>(                                            \
+      PathEval<KID, DP, NT>{W, F, D, b, wp, amp, P, Xt, N, p, v, d_scale, K}, D, starts, count, iters, tol, x_out, \
+      v_out, nullptr, K)
+  // threads per start as launch_rff_ascent
+  if (D <= 8) { if (wide) PA_LAUNCH(8, 1024); else PA_LAUNCH(8, 256); }
+  else if (D <= 24) { if (wide) PA_LAUNCH(24, 512); else PA_LAUNCH(24, 256); }
+  else PA_LAUNCH(64, 256);
+#undef PA_LAUNCH
   return 0;
 }
 
@@ -1265,4 +1353,58 @@ extern "C" int ppbo_rff_search_multi_camphor(ppbo_ctx* ctx, const double* d_cand
   PPBO_REQUIRE_CAMPHOR_L(ctx, h_l);
   return rff_search_multi_impl(ctx, d_cand, M, CAMPHOR_D, h_l, d_W, F, d_b, sigma_f, d_omegas, S, K, sep, iters, tol, d_x,
                                d_val, d_found, stream);
+}
+
+// ppbo_rff_search_multi for pathwise samples g_s = phi^T w_s + k(., X) v_s: the same three stages with the scoring launch
+// and the evaluator of the ascent replaced (ppbo_path_score_multi, PathEval)
+extern "C" int ppbo_path_search_multi(ppbo_ctx* ctx, int kernel_id, const double theta[3], const double* d_cand, int64_t M,
+                                      int D, const double* d_W, int F, const double* d_b, const double* d_Wp,
+                                      const double* d_X, int N, const double* d_V, const double* h_scale, int S, int K,
+                                      double sep, int iters, double tol, double* d_x, double* d_val, int* d_found,
+                                      void* stream) {
+  PPBO_ENTER(ctx);
+  PPBO_REQUIRE(ctx, theta && d_cand && d_W && d_b && d_Wp && d_X && d_V && d_x && d_val && d_found, "null pointer");
+  PPBO_REQUIRE(ctx, M > 0 && M < ((int64_t)1 << 31) && D > 0 && D <= 64 && F > 0 && N > 0, "sizes (D <= 64)");
+  PPBO_REQUIRE(ctx, S > 0 && S <= PPBO_RFF_MULTI_MAX_S, "S (1 .. PPBO_RFF_MULTI_MAX_S samples)");
+  PPBO_REQUIRE(ctx, K > 0 && K <= 1024 && sep >= 0 && iters >= 0 && tol >= 0, "K (<= 1024) / sep / iters / tol");
+  PPBO_REQUIRE(ctx, kernel_id != PPBO_KERNEL_CAMPHOR && ppbo_kernel_id_valid(kernel_id),
+               "kernel_id (a radial kernel: SE, RQ, Matern-5/2, Matern-3/2)");
+  if (h_scale)
+    for (int d = 0; d < D; ++d)
+      PPBO_REQUIRE(ctx, h_scale[d] > 0.0 && std::isfinite(h_scale[d]), "h_scale: positive finite values");
+  hipStream_t s = (hipStream_t)stream;
+  StartSelection sel{M, S, D, K};
+  if (!sel.alloc(ctx, 0, 0))
+    return ppbo_set_error(ctx, (int)hipErrorOutOfMemory, "invalid argument: no workspace for %d samples of %lld candidates",
+                          S, (long long)M);
+  // ARD: the scoring launch works in the model's coordinates -- the candidates scaled, the basis unscaled (w / s).(s x)
+  // = w.x -- in a slot of their own: s[D] | 1 / s[D] | cand s [M][D] | W / s [F][D]
+  const double *rows = d_cand, *Wm = d_W, *d_scale = nullptr;
+  if (h_scale) {
+    double* sc = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_SCALE_SEARCH, (2 * (size_t)D + ((size_t)M + F) * D) * sizeof(double));
+    if (!sc) return (int)hipErrorOutOfMemory;
+    double hs[128];
+    for (int d = 0; d < D; ++d) { hs[d] = h_scale[d]; hs[D + d] = 1.0 / h_scale[d]; }
+    if (int rc = ppbo_upload_async(ctx, sc, hs, 2 * (size_t)D * sizeof(double), s)) return rc;
+    double* cs = sc + 2 * D;
+    double* Ws = cs + (size_t)M * D;
+    scale_points_kernel<<<(unsigned)((M * D + 255) / 256), 256, 0, s>>>(d_cand, M * D, D, sc, cs);
+    scale_points_kernel<<<(unsigned)(((int64_t)F * D + 255) / 256), 256, 0, s>>>(d_W, (int64_t)F * D, D, sc + D, Ws);
+    PPBO_LAUNCH_CHECK(ctx);
+    rows = cs; Wm = Ws; d_scale = sc;
+  }
+  if (int rc = ppbo_path_score_multi(ctx, kernel_id, theta, rows, M, D, Wm, F, d_b, d_Wp, d_X, N, d_V, S, sel.scores, stream))
+    return rc;
+  // start selection on the caller-coordinate rows: sep is in the caller's units
+  sel.select(ctx, sep, d_cand, TrialCands{}, d_found, s);
+  PPBO_LAUNCH_CHECK(ctx);
+  const KernParams p = make_kern_params(kernel_id, theta);
+  const double amp = std::sqrt(2.0 * theta[2] * theta[2] / (double)F);
+  if (int rc = ppbo_kernel_dispatch<true>(ctx, kernel_id, [&](auto kid) -> int {
+        return launch_path_ascent<decltype(kid)::value>(ctx, p, d_W, F, D, d_b, d_Wp, amp, d_X, N, d_V, d_scale, sel.starts,
+                                                        d_found, S, K, iters, tol, d_x, d_val, s);
+      }))
+    return rc;
+  PPBO_LAUNCH_CHECK(ctx);
+  return 0;
 }

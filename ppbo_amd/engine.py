@@ -1022,6 +1022,64 @@ class Engine:
         results x [S, K, 6] in the caller's coordinates."""
         return self._rff_search_multi("rff_search_multi_camphor", cand, 6, ls, W, b, sigma_f, omegas, K, sep, iters, tol)
 
+    # ---- pathwise posterior samples g_s = phi^T w_s + k(., X) v_s -------------------------------------------
+    @staticmethod
+    def _path_widths(what, D, W, b, Wp, V, X, kernel, theta, K=None):
+        """(F, S, N, scale) of S paths (W_prior [S, F], V [S, N]) over the design X [N, D]: the checks of
+        _rff_multi_widths, V's shape, a radial kernel and theta[1] (lengthscales); only shapes are read, so this runs
+        before anything goes to the device.  scale: 1 / l for per-dimension length scales, else None."""
+        F, S = Engine._rff_multi_widths(what, D, W, b, Wp, K)
+        if kernel not in RADIAL_KERNELS:
+            raise ValueError(f"{what}: pathwise samples are defined for the radial kernels {RADIAL_KERNELS}, not {kernel}")
+        if len(X.shape) != 2 or X.shape[1] != D or X.shape[0] < 1:
+            raise ValueError(f"{what}: design of shape {tuple(X.shape)}, [N, {D}] required")
+        N = X.shape[0]
+        if len(V.shape) != 2 or tuple(V.shape) != (S, N):
+            raise ValueError(f"{what}: V of shape {tuple(V.shape)}, [{S}, {N}] required")
+        ls = lengthscales(theta, D, kernel)
+        return F, S, N, None if ls is None else 1.0 / ls
+
+    def path_score_multi(self, Xc, W, b, theta, kernel, X, Wp, V):
+        """g_s(x_c) = phi(x_c)^T w_s + k(x_c, X) v_s for S paths (ppbo_path_score_multi): a [S, M] device tensor.  Xc [M, D],
+        the basis W [F, D] and the design X [N, D] in the caller's coordinates, Wp [S, F], V [S, N]; per-dimension length
+        scales go through the input scaling (rows times 1 / l, basis times l)."""
+        if len(Xc.shape) != 2:
+            raise ValueError(f"path_score_multi: candidates of shape {tuple(Xc.shape)}, [M, D] required")
+        M, D = Xc.shape
+        F, S, N, scale = self._path_widths("path_score_multi", D, W, b, Wp, V, X, kernel, theta)
+        Xc, W, b, X, Wp, V = self.dev(Xc), self.dev(W), self.dev(b).reshape(-1), self.dev(X), self.dev(Wp), self.dev(V)
+        th = theta
+        if scale is not None:
+            Xc, X, W = self.scale_points(Xc, scale), self.scale_points(X, scale), self.scale_points(W, 1.0 / scale)
+            th = (float(theta[0]), 1.0, float(theta[2]))
+        sc = self.empty(S, M)
+        rc = self.lib.ppbo_path_score_multi(self.ctx, self._kid(kernel), self._theta(th), _ptr(Xc), M, D, _ptr(W), F, _ptr(b),
+                                            _ptr(Wp), _ptr(X), N, _ptr(V), S, _ptr(sc), self._stream())
+        self._check(rc, "ppbo_path_score_multi")
+        return sc
+
+    def path_search_multi(self, cand, W, b, theta, kernel, X, Wp, V, K=32, sep=0.05, iters=200, tol=1e-10):
+        """rff_search_multi for S paths (ppbo_path_search_multi): returns x [S, K, D], values [S, K], found [S] as NumPy;
+        path s's refined maxima are its rows < found[s], the others hold -inf values.  Arguments as path_score_multi."""
+        if len(cand.shape) != 2:
+            raise ValueError(f"path_search_multi: candidates of shape {tuple(cand.shape)}, [M, D] required")
+        M, D = cand.shape
+        F, S, N, scale = self._path_widths("path_search_multi", D, W, b, Wp, V, X, kernel, theta, int(K))
+        cand, W, b, X, Wp, V = self.dev(cand), self.dev(W), self.dev(b).reshape(-1), self.dev(X), self.dev(Wp), self.dev(V)
+        th, hs = theta, None
+        if scale is not None:
+            X = self.scale_points(X, scale)
+            th = (float(theta[0]), 1.0, float(theta[2]))
+            scale = np.ascontiguousarray(scale, dtype=np.float64)      # (kept alive until the call has returned)
+            hs = self._dptr(scale)
+        xs, vals = self.empty(S, K, D), self.empty(S, K)
+        found = torch.zeros(S, dtype=torch.int32, device=self.device)
+        rc = self.lib.ppbo_path_search_multi(self.ctx, self._kid(kernel), self._theta(th), _ptr(cand), M, D, _ptr(W), F,
+                                             _ptr(b), _ptr(Wp), _ptr(X), N, _ptr(V), hs, S, int(K), float(sep), int(iters),
+                                             float(tol), _ptr(xs), _ptr(vals), _ptr(found), self._stream())
+        self._check(rc, "ppbo_path_search_multi")
+        return xs.cpu().numpy(), vals.cpu().numpy(), found.cpu().numpy()
+
     def rff_terms(self, Phi, omega, m, sigma):
         Phi, omega = self.dev(Phi), self.dev(omega).reshape(-1)
         F, N = Phi.shape

@@ -13,6 +13,10 @@ Matern kernels (Student-t) and the camphor-copper kernels.  camphor(x, x'; l_0..
 11-column embedding e of engine.py / include/ppbo_hip.h, so a camphor basis is the unit SE basis on e: W is [F, 11],
 Phi(X) is formed on the embedded rows, and every method that takes or returns a point works in the caller's six
 coordinates (phi / Dphi through e and its Jacobian; the search by ppbo_rff_search_camphor).
+
+Beyond the reference: sample_paths draws from the GP's own Laplace posterior by Matheron's rule (PosteriorPaths:
+g_s = phi^T w_s + k(., X) v_s, ppbo_path_score_multi / ppbo_path_search_multi), where the weight-space posterior above keeps
+only a diagonal covariance; sample_xstars(..., posterior="pathwise") searches those paths.
 """
 from __future__ import annotations
 
@@ -107,6 +111,44 @@ def best_per_sample(x, val, found):
     return X, V, np.flatnonzero(~ok)
 
 
+class PosteriorPaths:
+    """n pathwise (decoupled, Wilson et al. 2020) samples of the utility from the GP's Laplace posterior,
+
+        g_s(x) = phi(x)^T w_s + k(x, X) v_s,     w_s ~ N(0, I_F),   v_s = Sigma^-1 (f_s - Phi(X)^T w_s),   f_s ~ N(f_MAP, P)
+
+    W_prior [n, F] and V [n, N] stay on the device; the basis, design, kernel and theta are the sampler's at the time of
+    the draw (made by Hsampler.sample_paths)."""
+
+    def __init__(self, sampler, W_prior, V):
+        self._hs = sampler
+        self.eng = sampler.eng
+        self.W_prior, self.V = W_prior, V
+        self.n = int(W_prior.shape[0])
+        self.kernel, self.theta = sampler.kernel, sampler.theta
+        self._W, self._b, self._X = sampler._dev("W"), sampler._dev("b"), sampler._dev("X")
+
+    def evaluate(self, Xq):
+        """g_s(x_q) for every path: a [n, M] device tensor (ppbo_path_score_multi, RFF_MULTI_MAX_S paths per launch)."""
+        import torch
+        Xq = self.eng.dev(Xq)
+        out = [self.eng.path_score_multi(Xq, self._W, self._b, self.theta, self.kernel, self._X, self.W_prior[c0:c0 + RFF_MULTI_MAX_S],
+                                         self.V[c0:c0 + RFF_MULTI_MAX_S]) for c0 in range(0, self.n, RFF_MULTI_MAX_S)]
+        return out[0] if len(out) == 1 else torch.cat(out, dim=0)
+
+    def xstars(self, starts=RFF_STARTS):
+        """(X [n, D], values [n]): the best refined maximiser of every path over the candidates of return_xstar and
+        g_s there (ppbo_path_search_multi).  A path whose search finds nothing is a RuntimeError."""
+        work = self._hs._xstar_candidates()
+        X, V = np.empty((self.n, work.shape[1])), np.empty(self.n)
+        for c0 in range(0, self.n, RFF_MULTI_MAX_S):
+            c1 = min(self.n, c0 + RFF_MULTI_MAX_S)
+            X[c0:c1], V[c0:c1], missing = best_per_sample(*self.eng.path_search_multi(
+                work, self._W, self._b, self.theta, self.kernel, self._X, self.W_prior[c0:c1], self.V[c0:c1], K=starts, iters=100))
+            if missing.size:
+                raise RuntimeError(f"PosteriorPaths.xstars: {missing.size} paths found no maximiser")
+        return X, V
+
+
 class Hsampler:
     def __init__(self, gp_model, nFeatures=1000, engine=None):
         self.eng = engine if engine is not None else getattr(gp_model, "eng", None) or get_engine()
@@ -140,6 +182,7 @@ class Hsampler:
         # camphor kernels: the six length scales, and the model's posteriors whose embedded rows e(X) can be reused
         self.camphor_l = camphor_lengthscales(self.theta, self.D) if self.kernel in CAMPHOR_KERNELS else None
         self._posts = (getattr(gp_model, "_post", None), getattr(gp_model, "_post_mean", None))
+        self._gp = gp_model       # sample_paths reads the fit (Sigma_inv, fMAP, posterior_covariance) when it is called
 
     def _dev(self, name):
         arr = getattr(self, name)
@@ -415,13 +458,65 @@ class Hsampler:
             seed = draw_seed()
         return self.eng.rff_omega_draws(seed, self._dev("omega_MAP"), self._dev("cov_diag"), int(n))
 
-    def sample_xstars(self, n, omegas=None, seed=None, starts=RFF_STARTS):
+    def sample_paths(self, n, seed=None):
+        """n pathwise samples of the utility from the GP's Laplace posterior (PosteriorPaths): prior weights W_prior
+        [n, F] and normals z [n, N] from the ppbo_randn stream of `seed` (W_prior[s, f] at index s F + f, z[s, i] at
+        n F + s N + i: bitwise reproducible; seed=None takes one from the global NumPy stream), f_s = f_MAP + L z_s with
+        L L^T = posterior_covariance (ppbo_potrf), V = (F_s - W_prior Phi(X)) Sigma^-1 (three ppbo_dgemm on the resident
+        Phi(X) and Sigma^-1).  The fit is read from the gp_model the sampler was built on; without one it raises
+        RuntimeError.  Not for the camphor-copper kernels."""
+        import torch
+        if self._camphor() is not None:
+            raise NotImplementedError(f"Hsampler.sample_paths: pathwise samples are not implemented for {self.kernel}")
+        self._check_W()
+        n = int(n)
+        if n < 1:
+            raise ValueError(f"sample_paths: n = {n} samples")
+        gp = self.__dict__.get("_gp")
+        Sinv = getattr(gp, "_dSigma_inv", None)
+        if Sinv is None:
+            Sinv = getattr(gp, "Sigma_inv", None)
+        fmap = getattr(gp, "fMAP", None)
+        P = getattr(gp, "posterior_covariance", None) if (Sinv is not None and fmap is not None) else None
+        if P is None:
+            raise RuntimeError("Hsampler.sample_paths: no fitted posterior (run update_model on the GP model first)")
+        post = getattr(gp, "_post", None)
+        if getattr(post, "P", None) is not None:
+            P = post.P                                         # the device copy behind the NumPy attribute
+        N = np.shape(self.X)[0]
+        if tuple(Sinv.shape) != (N, N) or tuple(P.shape) != (N, N) or np.size(fmap) != N:
+            raise RuntimeError(f"Hsampler.sample_paths: the GP model's fit is not of this sampler's design ({N} points): "
+                               "run update_model, then build the sampler")
+        if self._dPhi is None or tuple(self._dPhi.shape) != (np.shape(self.W)[0], N):
+            raise RuntimeError("Hsampler.sample_paths: no Phi(X) of this basis (run update_phi_X first)")
+        F = self._dPhi.shape[0]
+        if seed is None:
+            seed = draw_seed()
+        eng = self.eng
+        draws = eng.randn(seed, n * (F + N))
+        W_prior, z = draws[:n * F].view(n, F), draws[n * F:].view(n, N)
+        L = torch.tril(eng.potrf_(eng.dev(P).clone()))
+        Fs = eng.dev(fmap).reshape(1, N).repeat(n, 1)
+        eng.dgemm(z, L, transB=True, beta=1.0, C_out=Fs)                  # F_s = f_MAP + z L^T
+        eng.dgemm(W_prior, self._dPhi, alpha=-1.0, beta=1.0, C_out=Fs)    # ... - W_prior Phi(X)
+        V = eng.dgemm(Fs, eng.dev(Sinv))                                  # Sigma^-1 is symmetric
+        return PosteriorPaths(self, W_prior, V)
+
+    def sample_xstars(self, n, omegas=None, seed=None, starts=RFF_STARTS, posterior="weights"):
         """n samples of the maximiser x* of the posterior utility: (X [n, D], values [n]), row k the best refined
         maximiser of sample k in the caller's coordinates (camphor: [n, 6]) and phi(x)^T omega_k there.  What n calls
         of sample_xstar compute, in batches of up to RFF_MULTI_MAX_S samples per device enqueue (ppbo_rff_search_multi):
         the candidates are built once per call as in return_xstar and shared by all samples.  omegas [n, F] (host or
         device) replaces the device draws.  A sample whose search finds nothing is redrawn once per batch; if its
-        redraw finds nothing either, RuntimeError."""
+        redraw finds nothing either, RuntimeError.
+        posterior="pathwise": the samples are paths of the GP's own Laplace posterior instead,
+        sample_paths(n, seed).xstars(starts) (omegas does not apply); any other value is a ValueError."""
+        if posterior not in ("weights", "pathwise"):
+            raise ValueError(f"sample_xstars: posterior = {posterior!r} ('weights' or 'pathwise')")
+        if posterior == "pathwise":
+            if omegas is not None:
+                raise ValueError("sample_xstars: omegas are draws of the weight-space posterior, not of posterior='pathwise'")
+            return self.sample_paths(n, seed).xstars(starts)
         self._check_W()
         n = int(n)
         if n < 1:
