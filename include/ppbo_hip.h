@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define PPBO_ABI_VERSION 6
+#define PPBO_ABI_VERSION 7
 #define PPBO_ERR_NOT_PD 1001
 
 /* The library is built with -fvisibility=hidden: the entry points declared here are its ONLY dynamic symbols
@@ -241,14 +241,14 @@ PPBO_API int ppbo_fit_fmap_whitened(ppbo_ctx* ctx, const double* d_L, int ldl, c
  *     outputs (d_Sigma_inv, d_L, d_Linv, d_fMAP) are undefined in that case.
  * Outputs (device, caller-owned): d_Sigma [N,N] (NULL to skip), d_Sigma_inv [N,N], d_L [N,N] (Cholesky factor of
  * Sigma, lower triangle valid), d_Linv [N,N] (NULL: kept in a workspace), d_fMAP [N], and -- all four or none --
- * d_alpha, d_lam_diag, d_lam_off [N], d_G [N,N] as ppbo_posterior defines them.
+ * d_alpha, d_lam_diag, d_lam_off [N], d_G [N,N] as ppbo_posterior defines them (form: as there).
  * Returns PPBO_ERR_NOT_PD with *h_info = 1 when Sigma is not positive definite, *h_info = 2 when Sigma^-1 - Lambda_MAP
  * is not (f_MAP and the factors of Sigma are valid then; the reference prints its '---!!!---' line and keeps the
  * previous posterior, src/gp_model.py:118-120). */
 PPBO_API int ppbo_gp_fit(ppbo_ctx* ctx, int kernel_id, const double* d_X, int N, int D, const double theta[3], double shrink,
                 int m, const double* d_f_init, const ppbo_fit_opts* opts, double* d_Sigma, double* d_Sigma_inv,
                 double* d_L, double* d_Linv, double* d_fMAP, double* d_alpha, double* d_lam_diag, double* d_lam_off,
-                double* d_G, ppbo_fit_stats* h_stats, int* h_info, void* stream);
+                double* d_G, int form, ppbo_fit_stats* h_stats, int* h_info, void* stream);
 
 /* T(f) and grad T(f) for a given f (src/gp_model.py:221-240); h_T / d_grad may be NULL */
 PPBO_API int ppbo_T_and_grad(ppbo_ctx* ctx, const double* d_Sigma_inv, const double* d_f, int N, int m,
@@ -260,12 +260,14 @@ PPBO_API int ppbo_T_and_grad(ppbo_ctx* ctx, const double* d_Sigma_inv, const dou
  * W = -Lambda_MAP, B = Sigma^-1 + W = L_B L_B^T, R = L_B^-1:
  *   d_alpha[N] = Sigma^-1 f_MAP;  d_G[N,N] = R W (block lower triangular);
  *   k*^T A k* = k*^T W k* - |G k*|^2   (Woodbury; identical operator).
- * d_P (optional, may be NULL) = posterior_covariance = B^-1 (src/gp_model.py:117).
+ * form = PPBO_FORM_NODE writes that G; PPBO_FORM_EDGE writes H, the same operator in edge coordinates ("the variance
+ * operator in EDGE form" below) -- hand the same value on as ppbo_model.form.  Any other value is refused.
+ * d_P (optional, may be NULL) = posterior_covariance = B^-1 (src/gp_model.py:117), whatever the form.
  * Returns PPBO_ERR_NOT_PD when B is not positive definite (the reference prints
  * '---!!!--- Posterior covariance matrix is not PSD ---!!!---' and continues). */
 PPBO_API int ppbo_posterior(ppbo_ctx* ctx, const double* d_Sigma_inv, const double* d_fMAP, int N, int m,
                    double sigma, double* d_alpha, double* d_lam_diag, double* d_lam_off,
-                   double* d_G, double* d_P, int* h_info, void* stream);
+                   double* d_G, double* d_P, int form, int* h_info, void* stream);
 
 /* ---- K2+K3+K4: batched candidate scoring with on-device argmax ------------
  * replaces mu_pred (src/gp_model.py:454-458) / diag of mu_Sigma_pred (:441-452)
@@ -277,6 +279,7 @@ PPBO_API int ppbo_posterior(ppbo_ctx* ctx, const double* d_Sigma_inv, const doub
  * Any N = n_q (m + 1), any m, any M: where N is not a multiple of the 128-row tile / 16-deep chunk of the variance
  * contraction (m = 25, the reference's default) the call works on a zero-framed copy of G in a ctx workspace (from
  * 2048 candidates on; ~3 N^2 x 8 bytes moved per call), and K* is always padded to whole 128-candidate tiles. */
+enum { PPBO_FORM_NODE = 0, PPBO_FORM_EDGE = 1 };   /* the two layouts of a variance operator: "EDGE form" below */
 typedef struct ppbo_model {
   int kernel_id, N, D, m;
   double theta[3];
@@ -284,7 +287,7 @@ typedef struct ppbo_model {
   const double* d_alpha;    /* [N]   */
   const double* d_lam_diag; /* [N]  Lambda_MAP diagonal   */
   const double* d_lam_off;  /* [N]  Lambda_MAP star edges */
-  const double* d_G;        /* [N,N] R W, see ppbo_posterior (or H, for the *_edge entry points: see ppbo_posterior_edge).
+  const double* d_G;        /* [N,N] the variance operator in the layout `form` names: R W (ppbo_posterior) or H.
                              * Block lower triangular, and stored that way: every
                              * entry right of the last star that reaches into its row must be an explicit ZERO
                              * (ppbo_posterior / ppbo_gp_fit write them): the contractions round their K ranges up to
@@ -295,6 +298,12 @@ typedef struct ppbo_model {
   const double* d_Gt;       /* optional (ABI 6): the TRANSPOSE of d_G as ppbo_transposed_G writes it.  Models of up to ~500
                              * rows are scored by one launch (csrc/fused.hip) whose matrix-core loop reads G transposed;
                              * NULL: the library forms the transpose in a workspace on every call (2-4 us) */
+  int form;                 /* (ABI 7) what d_G holds: PPBO_FORM_NODE (0, so a zero-initialised model is a node-form one),
+                             * G = R W as ppbo_posterior / ppbo_gp_fit write it with that form, or PPBO_FORM_EDGE, H = L22^-1
+                             * ("the variance operator in EDGE form" below); it must be the form the operator was built
+                             * with -- read by the other rule an operator gives a finite, plausible and wrong variance.
+                             * d_Gt is not read for the edge form.  Any other value is refused ("invalid argument").
+                             * Ignored where no operator is read: d_G == NULL, and the mean-only ppbo_mean_* entries */
 } ppbo_model;
 
 /* The transpose of G = R Lambda in the layout the one-launch scoring kernel reads: d_Gt[rows][ld] with
@@ -629,37 +638,12 @@ PPBO_API int ppbo_search_sharded(ppbo_ctx* ctx, const ppbo_model* model, const d
  * this shape by default (radial kernel, D <= 16, up to ~500 rows), else PPBO_FORM_EDGE -- which form the caller should
  * build.  It does not depend on the ctx's PPBO_FUSED setting: the shapes that only PPBO_FUSED=2 sends to the one-launch
  * kernel (up to ~1000 rows, or D > 16) get the edge form, and are then scored by the three-launch path.
- * ppbo_posterior_edge / ppbo_gp_fit_edge: ppbo_posterior / ppbo_gp_fit writing H instead of G (same arguments, same
- * PPBO_ERR_NOT_PD / h_info reporting; d_P, when asked for, is formed as ppbo_posterior forms it, from a second
- * factorization in node coordinates whose failure is reported the same way).
- * The *_edge consumers: the entry point of the same name for a model whose d_G holds H (d_Gt is not read). */
-enum { PPBO_FORM_NODE = 0, PPBO_FORM_EDGE = 1 };
+ * The `form` argument of ppbo_posterior / ppbo_gp_fit selects what they write to d_G (same PPBO_ERR_NOT_PD / h_info
+ * reporting either way; with PPBO_FORM_EDGE d_P, when asked for, is formed as for the node form, from a second
+ * factorization in node coordinates whose failure is reported the same way), and ppbo_model.form tells every consumer
+ * of the operator (ppbo_predict, ppbo_predict_record, ppbo_predict_cov, ppbo_line_acq, ppbo_line_acq_xi,
+ * ppbo_search_sharded) which of the two it holds. */
 PPBO_API int ppbo_posterior_form(ppbo_ctx* ctx, int kernel_id, int N, int D, int m);
-PPBO_API int ppbo_posterior_edge(ppbo_ctx* ctx, const double* d_Sigma_inv, const double* d_fMAP, int N, int m,
-                        double sigma, double* d_alpha, double* d_lam_diag, double* d_lam_off,
-                        double* d_H, double* d_P, int* h_info, void* stream);
-PPBO_API int ppbo_gp_fit_edge(ppbo_ctx* ctx, int kernel_id, const double* d_X, int N, int D, const double theta[3],
-                     double shrink, int m, const double* d_f_init, const ppbo_fit_opts* opts, double* d_Sigma,
-                     double* d_Sigma_inv, double* d_L, double* d_Linv, double* d_fMAP, double* d_alpha,
-                     double* d_lam_diag, double* d_lam_off, double* d_H, ppbo_fit_stats* h_stats, int* h_info,
-                     void* stream);
-PPBO_API int ppbo_predict_edge(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc, int64_t M,
-                      int score_kind, double mustar, double* d_mu, double* d_var, double* d_score,
-                      double* h_best_val, int64_t* h_best_idx, void* stream);
-PPBO_API int ppbo_predict_record_edge(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc, int64_t M,
-                             int score_kind, double mustar, int64_t index_offset, double* d_record, void* stream);
-PPBO_API int ppbo_search_sharded_edge(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc, int64_t M,
-                             int score_kind, double mustar, int64_t index_offset, double* h_best_val,
-                             int64_t* h_best_idx, void* stream);
-PPBO_API int ppbo_predict_cov_edge(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc, int M,
-                          double shrink, double* d_mu, double* d_cov, void* stream);
-PPBO_API int ppbo_line_acq_edge(ppbo_ctx* ctx, const ppbo_model* model, const double* d_grid, int B, int G,
-                       double shrink, const double* d_z, int S, double mustar, double jitter, double* d_ei,
-                       double* d_varmax, void* stream);
-PPBO_API int ppbo_line_acq_xi_edge(ppbo_ctx* ctx, const ppbo_model* model, const double* d_xi, const double* d_x,
-                          const double* d_alpha, int alpha_per_line, int B, int G, double shrink,
-                          const double* d_z, int S, double mustar, double jitter, double* d_ei,
-                          double* d_varmax, void* stream);
 /* the reduction alone, for callers that run the all-gather themselves (torch.distributed in ppbo_amd/dist.py):
  * d_records[world][2] = (value, global index as a double) per rank, already gathered in device memory; one
  * single-wavefront kernel applies the rule above and ONE 16-byte record is copied back. */

@@ -36,7 +36,7 @@ class Model(C.Structure):
     _fields_ = [("kernel_id", C.c_int), ("N", C.c_int), ("D", C.c_int), ("m", C.c_int),
                 ("theta", C.c_double * 3), ("d_X", C.c_void_p), ("d_alpha", C.c_void_p),
                 ("d_lam_diag", C.c_void_p), ("d_lam_off", C.c_void_p), ("d_G", C.c_void_p), ("kstar_fp32", C.c_int),
-                ("d_Gt", C.c_void_p)]
+                ("d_Gt", C.c_void_p), ("form", C.c_int)]
 
 
 _vp, _i, _d, _i64 = C.c_void_p, C.c_int, C.c_double, C.c_int64
@@ -66,9 +66,9 @@ SIGNATURES = {
     "ppbo_fit_fmap": [_vp, _vp, _i, _i, _d, _vp, C.POINTER(FitOpts), _vp, C.POINTER(FitStats), _vp],
     "ppbo_fit_fmap_whitened": [_vp, _vp, _i, _vp, _i, _i, _d, _vp, C.POINTER(FitOpts), _vp, C.POINTER(FitStats), _vp],
     "ppbo_gp_fit": [_vp, _i, _vp, _i, _i, _dp3, _d, _i, _vp, C.POINTER(FitOpts), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                    C.POINTER(FitStats), C.POINTER(_i), _vp],
+                    _i, C.POINTER(FitStats), C.POINTER(_i), _vp],
     "ppbo_T_and_grad": [_vp, _vp, _vp, _i, _i, _d, C.POINTER(_d), _vp, _vp],
-    "ppbo_posterior": [_vp, _vp, _vp, _i, _i, _d, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i), _vp],
+    "ppbo_posterior": [_vp, _vp, _vp, _i, _i, _d, _vp, _vp, _vp, _vp, _vp, _i, C.POINTER(_i), _vp],
     "ppbo_predict": [_vp, C.POINTER(Model), _vp, _i64, _i, _d, _vp, _vp, _vp, C.POINTER(_d), C.POINTER(_i64), _vp],
     "ppbo_predict_record": [_vp, C.POINTER(Model), _vp, _i64, _i, _d, _i64, _vp, _vp],
     "ppbo_predict_cov": [_vp, C.POINTER(Model), _vp, _i, _d, _vp, _vp, _vp],
@@ -122,13 +122,9 @@ SIGNATURES = {
     "ppbo_argmax_combine": [_vp, _vp, _i, C.POINTER(_d), C.POINTER(_i64), _vp],
     "ppbo_dgemm": [_vp, _i, _i, _i, _i, _i, _d, _vp, _i, _vp, _i, _d, _vp, _i, _vp],
 }
-# the edge-form entry points take exactly the arguments of their node-form namesakes
-for _n in ("ppbo_posterior", "ppbo_gp_fit", "ppbo_predict", "ppbo_predict_record", "ppbo_search_sharded",
-           "ppbo_predict_cov", "ppbo_line_acq", "ppbo_line_acq_xi"):
-    SIGNATURES[_n + "_edge"] = SIGNATURES[_n]
 
 _lib = None
-ABI_VERSION = 6     # must equal PPBO_ABI_VERSION of include/ppbo_hip.h
+ABI_VERSION = 7     # must equal PPBO_ABI_VERSION of include/ppbo_hip.h
 
 
 def _check_stamp():

@@ -59,9 +59,6 @@ struct ppbo_ctx {
   // the host-polled searches let the runtime wait (hipStreamSynchronize) when their progress word has been still for
   // this long, and carry on if that advanced the search (PPBO_POLL_LIMIT_MS; tests set it to 0 to walk that path)
   int poll_limit_ms = 5000;
-  // the variance operator of the model(s) of the running entry point is in EDGE form (H = L22^-1 of the edge-coordinate
-  // factor, ppbo_posterior_edge) instead of the node form G = R Lambda; set only for the duration of a *_edge entry point
-  int op_edge = 0;
   hipStream_t side_stream = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   int syrk_cfg = 0;       // PPBO_SYRK_CFG: tile configuration of Sigma^-1 = Linv^T Linv (0 = by size; 1 / 2 / 3 = 128 / 64 / 32)
@@ -118,12 +115,6 @@ int ppbo_predict_record_publish(ppbo_ctx* ctx, const ppbo_model* model, const do
                                 double mustar, int64_t index_offset, double* d_record, unsigned long long* d_flag,
                                 unsigned long long epoch, hipStream_t s);
 
-// the *_edge entry points: run the node-form entry with ctx->op_edge raised for its duration
-struct PpboEdgeScope {
-  ppbo_ctx* ctx; int prev;
-  explicit PpboEdgeScope(ppbo_ctx* c) : ctx(c), prev(c ? c->op_edge : 0) { if (ctx) ctx->op_edge = 1; }
-  ~PpboEdgeScope() { if (ctx) ctx->op_edge = prev; }
-};
 // first row / column of an edge-form operator that the contractions read: the n_q observation coordinates hold zeros,
 // the K loops start at n_q rounded down to the chunk depth
 inline int ppbo_edge_k0(int n_q) { return n_q & ~15; }
@@ -185,6 +176,10 @@ void ppbo_lds_limit(ppbo_ctx* ctx, const void* kernel_fn, int bytes);
   do {                                                                  \
     if (!(cond)) return ppbo_set_error((ctx), -1, "invalid argument: %s", msg); \
   } while (0)
+
+// the form of a variance operator: ppbo_model.form, or the form parameter of ppbo_posterior / ppbo_gp_fit
+#define PPBO_REQUIRE_FORM(ctx, form) \
+  PPBO_REQUIRE(ctx, (form) == PPBO_FORM_NODE || (form) == PPBO_FORM_EDGE, "form (PPBO_FORM_NODE or PPBO_FORM_EDGE)")
 
 // an entry point's kernel id and the camphor kernel's shape rule (D is the design's dimension)
 #define PPBO_REQUIRE_KERNEL(ctx, kernel_id, D)                                                  \

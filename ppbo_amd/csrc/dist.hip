@@ -224,12 +224,6 @@ int ppbo_search_sharded(ppbo_ctx* ctx, const ppbo_model* model, const double* d_
   return gather_reduce_readback(ctx, dev + 2, h_best_val, h_best_idx, (hipStream_t)stream);
 }
 
-int ppbo_search_sharded_edge(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc, int64_t M, int score_kind,
-                             double mustar, int64_t index_offset, double* h_best_val, int64_t* h_best_idx, void* stream) {
-  PpboEdgeScope es(ctx);
-  return ppbo_search_sharded(ctx, model, d_Xc, M, score_kind, mustar, index_offset, h_best_val, h_best_idx, stream);
-}
-
 int ppbo_argmax_combine(ppbo_ctx* ctx, const double* d_records, int world, double* h_best_val, int64_t* h_best_idx,
                         void* stream) {
   PPBO_ENTER(ctx);

@@ -255,7 +255,7 @@ int ppbo_evidence_grad(ppbo_ctx* ctx, int kernel_id, const double* d_X, int N, i
 
   // alpha, Q^-1 = (Sigma^-1 - Lambda)^-1 and Q's PD check (G lands in bA and is not used)
   int pinfo = 0;
-  const int prc = ppbo_posterior(ctx, d_Sigma_inv, d_fMAP, N, m, theta[0], alpha, ld2, lo2, bA, bB, &pinfo, stream);
+  const int prc = ppbo_posterior(ctx, d_Sigma_inv, d_fMAP, N, m, theta[0], alpha, ld2, lo2, bA, bB, PPBO_FORM_NODE, &pinfo, stream);
   if (prc == PPBO_ERR_NOT_PD) {
     if (h_info) *h_info = 2;
     return ppbo_set_error(ctx, PPBO_ERR_NOT_PD, "Sigma^-1 - Lambda_MAP is not positive definite (leading minor %d): "

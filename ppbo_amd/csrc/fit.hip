@@ -293,7 +293,7 @@ __global__ __launch_bounds__(256) void g_build_kernel(const double* __restrict__
   G[(size_t)blockIdx.y * N + j] = acc;
 }
 
-// ---- the posterior in EDGE form (ppbo_posterior_edge) ----
+// ---- the posterior in EDGE form (ppbo_posterior with PPBO_FORM_EDGE) ----
 // Lambda_MAP = sum over the star edges (obs_q, j) of w_j (e_obs - e_j)(e_obs - e_j)' (laplace_kernel: lam_diag[j] = w_j,
 // lam_off[j] = -w_j), so the variance term needs B = Sigma^-1 - Lambda only through D P D' (D the E x N edge incidence,
 // P = B^-1).  In the coordinates y = Dbar x = [x_obs (n_q); x_obs - x_j (E = N - n_q edges, star-major)] the matrix
@@ -1554,8 +1554,8 @@ __global__ void publish_info_kernel(const int* __restrict__ info, int n, double*
 }
 
 int posterior_async(ppbo_ctx* ctx, const double* d_Sigma_inv, const double* d_fMAP, int N, int m, double sigma,
-                    double* d_alpha, double* d_lam_diag, double* d_lam_off, double* d_G, double* d_P, int* d_info,
-                    hipStream_t s) {
+                    double* d_alpha, double* d_lam_diag, double* d_lam_off, double* d_G, int form, double* d_P,
+                    int* d_info, hipStream_t s) {
   const int mblk = m + 1, n_q = N / mblk;
   const size_t nn = (size_t)N * N;
   double* H = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_LINALG, 2 * nn * sizeof(double));
@@ -1563,7 +1563,7 @@ int posterior_async(ppbo_ctx* ctx, const double* d_Sigma_inv, const double* d_fM
   double* R = H + nn;
   if (int rc = ppbo_gemv_async(ctx, d_Sigma_inv, N, N, d_fMAP, d_alpha, 0, 0, s)) return rc;
   laplace_kernel<<<(n_q + 3) / 4, 256, 0, s>>>(d_fMAP, N, mblk, n_q, sigma, nullptr, nullptr, d_lam_diag, d_lam_off);
-  if (ctx->op_edge) {
+  if (form == PPBO_FORM_EDGE) {
     // edge form: Btilde in H (its star sums staged in R's half), factor, H = inverse of the trailing E x E block written
     // into d_G at (n_q, n_q); the rest of d_G -- the observation rows / columns and everything above the diagonal,
     // which the contractions read up to the end of their 16-column chunks -- is zero
@@ -1621,9 +1621,10 @@ int ppbo_fit_fmap_whitened(ppbo_ctx* ctx, const double* d_L, int ldl, const doub
 int ppbo_gp_fit(ppbo_ctx* ctx, int kernel_id, const double* d_X, int N, int D, const double theta[3], double shrink,
                 int m, const double* d_f_init, const ppbo_fit_opts* opts, double* d_Sigma, double* d_Sigma_inv,
                 double* d_L, double* d_Linv, double* d_fMAP, double* d_alpha, double* d_lam_diag, double* d_lam_off,
-                double* d_G, ppbo_fit_stats* h_stats, int* h_info, void* stream) {
+                double* d_G, int form, ppbo_fit_stats* h_stats, int* h_info, void* stream) {
   PPBO_ENTER(ctx);
   PPBO_REQUIRE(ctx, d_X && theta && d_f_init && d_Sigma_inv && d_L && d_fMAP, "null pointer");
+  PPBO_REQUIRE_FORM(ctx, form);
   PPBO_REQUIRE(ctx, (d_alpha && d_lam_diag && d_lam_off && d_G) || (!d_alpha && !d_lam_diag && !d_lam_off && !d_G),
                "the posterior outputs (alpha, lam_diag, lam_off, G) come together or not at all");
   PPBO_REQUIRE(ctx, N > 0 && D > 0 && m >= 1 && theta[0] > 0 && N % (m + 1) == 0, "sizes (N must be n_q*(m+1))");
@@ -1702,8 +1703,8 @@ int ppbo_gp_fit(ppbo_ctx* ctx, int kernel_id, const double* d_X, int N, int D, c
     return rc;
   }
   if (d_G)
-    if (int rc2 = posterior_async(ctx, d_Sigma_inv, d_fMAP, N, m, theta[0], d_alpha, d_lam_diag, d_lam_off, d_G, nullptr,
-                                  d_info + 1, s)) {
+    if (int rc2 = posterior_async(ctx, d_Sigma_inv, d_fMAP, N, m, theta[0], d_alpha, d_lam_diag, d_lam_off, d_G, form,
+                                  nullptr, d_info + 1, s)) {
       (void)hipStreamSynchronize(s);
       return rc2;
     }
@@ -1727,10 +1728,11 @@ int ppbo_gp_fit(ppbo_ctx* ctx, int kernel_id, const double* d_X, int N, int D, c
 }
 
 int ppbo_posterior(ppbo_ctx* ctx, const double* d_Sigma_inv, const double* d_fMAP, int N, int m, double sigma,
-                   double* d_alpha, double* d_lam_diag, double* d_lam_off, double* d_G, double* d_P, int* h_info,
-                   void* stream) {
+                   double* d_alpha, double* d_lam_diag, double* d_lam_off, double* d_G, double* d_P, int form,
+                   int* h_info, void* stream) {
   PPBO_ENTER(ctx);
   PPBO_REQUIRE(ctx, d_Sigma_inv && d_fMAP && d_alpha && d_lam_diag && d_lam_off && d_G, "null pointer");
+  PPBO_REQUIRE_FORM(ctx, form);
   PPBO_REQUIRE(ctx, N > 0 && m >= 1 && sigma > 0 && N % (m + 1) == 0, "sizes");
   hipStream_t s = (hipStream_t)stream;
   if (h_info) *h_info = 0;
@@ -1738,32 +1740,17 @@ int ppbo_posterior(ppbo_ctx* ctx, const double* d_Sigma_inv, const double* d_fMA
   if (!d_info) return (int)hipErrorOutOfMemory;
   // everything is enqueued first, the factorization's info word is looked at last: one host wait per call (the
   // triangular inverse of a failed factor is wasted work, but a failure is the rare case)
-  if (int rc = posterior_async(ctx, d_Sigma_inv, d_fMAP, N, m, sigma, d_alpha, d_lam_diag, d_lam_off, d_G, d_P, d_info, s))
+  if (int rc = posterior_async(ctx, d_Sigma_inv, d_fMAP, N, m, sigma, d_alpha, d_lam_diag, d_lam_off, d_G, form, d_P,
+                               d_info, s))
     return rc;
   int info[2] = {0, 0};
-  const bool two = ctx->op_edge && d_P;      // edge form with P: a second factorization (node coordinates) for P
+  const bool two = form == PPBO_FORM_EDGE && d_P;   // a second factorization (node coordinates) for P
   PPBO_HIP_CHECK(ctx, hipMemcpyAsync(info, d_info, (two ? 2 : 1) * sizeof(int), hipMemcpyDeviceToHost, s));
   PPBO_HIP_CHECK(ctx, hipStreamSynchronize(s));
   const int bad = info[0] != 0 ? info[0] : info[1];
   if (h_info) *h_info = bad;
   if (bad != 0) return ppbo_set_error(ctx, PPBO_ERR_NOT_PD, "matrix is not positive definite (leading minor %d)", bad);
   return 0;
-}
-
-int ppbo_posterior_edge(ppbo_ctx* ctx, const double* d_Sigma_inv, const double* d_fMAP, int N, int m, double sigma,
-                        double* d_alpha, double* d_lam_diag, double* d_lam_off, double* d_H, double* d_P, int* h_info,
-                        void* stream) {
-  PpboEdgeScope es(ctx);
-  return ppbo_posterior(ctx, d_Sigma_inv, d_fMAP, N, m, sigma, d_alpha, d_lam_diag, d_lam_off, d_H, d_P, h_info, stream);
-}
-
-int ppbo_gp_fit_edge(ppbo_ctx* ctx, int kernel_id, const double* d_X, int N, int D, const double theta[3], double shrink,
-                     int m, const double* d_f_init, const ppbo_fit_opts* opts, double* d_Sigma, double* d_Sigma_inv,
-                     double* d_L, double* d_Linv, double* d_fMAP, double* d_alpha, double* d_lam_diag, double* d_lam_off,
-                     double* d_H, ppbo_fit_stats* h_stats, int* h_info, void* stream) {
-  PpboEdgeScope es(ctx);
-  return ppbo_gp_fit(ctx, kernel_id, d_X, N, D, theta, shrink, m, d_f_init, opts, d_Sigma, d_Sigma_inv, d_L, d_Linv,
-                     d_fMAP, d_alpha, d_lam_diag, d_lam_off, d_H, h_stats, h_info, stream);
 }
 
 }  // extern "C"

@@ -621,6 +621,7 @@ int ppbo_transposed_G(ppbo_ctx* ctx, const double* d_G, int N, double* d_Gt, voi
 // and the unsharded one must score a candidate with the same arithmetic)
 bool ppbo_fused_eligible(const ppbo_ctx* ctx, const ppbo_model* m) {
   if (ctx->fused_score == 0 || m->d_G == nullptr || m->kstar_fp32) return false;
+  if (m->form != PPBO_FORM_NODE) return false;   // the matrix-core loop reads node-form G (transposed)
   // the radial kernels only (the expansion-form K* tiles); camphor and anything else take the three-launch form
   if (m->kernel_id != PPBO_KERNEL_SE && m->kernel_id != PPBO_KERNEL_RQ && m->kernel_id != PPBO_KERNEL_MATERN52 &&
       m->kernel_id != PPBO_KERNEL_MATERN32) return false;

@@ -927,6 +927,7 @@ int check_model(ppbo_ctx* ctx, const ppbo_model* m) {
   PPBO_REQUIRE(ctx, m->N > 0 && m->D > 0 && m->D <= 64 && m->m >= 1, "model sizes (D<=64)");
   PPBO_REQUIRE(ctx, m->N % (m->m + 1) == 0, "N must be n_q*(m+1) (feedback_processing.py:110-130)");
   PPBO_REQUIRE_KERNEL(ctx, m->kernel_id, m->D);
+  if (m->d_G) PPBO_REQUIRE_FORM(ctx, m->form);   // the form of d_G: without an operator there is nothing to misread
   return 0;
 }
 
@@ -962,8 +963,8 @@ static int predict_passes(ppbo_ctx* ctx, const ppbo_model* model, const double* 
   PPBO_REQUIRE(ctx, !want_var || (model->d_lam_diag && model->d_lam_off), "model Lambda");
   const int N = model->N, mblk = model->m + 1, n_q = N / mblk;
   // an edge-form operator is always contracted by the three-launch form (the one-launch kernel reads node-form G)
-  const int edge_k0 = (want_var && ctx->op_edge) ? ppbo_edge_k0(n_q) : -1;
-  if (want_var && edge_k0 < 0 && ppbo_fused_eligible(ctx, model)) {
+  const int edge_k0 = (want_var && model->form == PPBO_FORM_EDGE) ? ppbo_edge_k0(n_q) : -1;
+  if (ppbo_fused_eligible(ctx, model)) {
     // Models of up to 1024 rows: ONE launch forms K* in LDS, contracts it with G on the matrix cores and scores
     // (fused.hip) -- no K* in HBM, no slab pass, no candidate chunks -- then the one-workgroup argmax.  The choice
     // depends on the model only: a shard of a sharded search scores a candidate exactly as the unsharded search does.
@@ -1155,7 +1156,7 @@ int ppbo_predict_cov(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc,
   GemmArgs y{};
   y.A = model->d_G; y.lda = N; y.B = Kt; y.ldb = ld; y.C = Y; y.ldc = ld;
   y.M = N; y.N = M; y.K = N; y.alpha = 1.0; y.beta = 0.0; y.khi_mode = 1; y.tri_block = mblk;
-  if (ctx->op_edge) {
+  if (model->form == PPBO_FORM_EDGE) {
     edge_apply_kernel<<<dim3((M + 127) / 128, N), 128, 0, s>>>(Kt, ld, M, mblk, n_q, model->d_lam_off, Z);
     PPBO_LAUNCH_CHECK(ctx);
     y.B = Z; y.tri_block = 1;    // H lower triangular
@@ -1205,7 +1206,7 @@ int line_acq_impl(ppbo_ctx* ctx, const ppbo_model* model, const double* d_grid, 
   PPBO_LAUNCH_CHECK(ctx);
   const int ld = ((Bc_max * G) + 127) & ~127;
   // edge form: Y = H E with E the edge-layout K* beside the node-layout one (which the mean and K*' Lambda K* read)
-  const bool edge = ctx->op_edge != 0;
+  const bool edge = model->form == PPBO_FORM_EDGE;
   double* ws = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_KSTAR, (size_t)((edge ? 2 : 1) * Nk + g_rows) * ld * sizeof(double));
   if (!ws) return (int)hipErrorOutOfMemory;
   double* Kt = ws;
@@ -1351,41 +1352,6 @@ int ppbo_line_acq_xi(ppbo_ctx* ctx, const ppbo_model* model, const double* d_xi,
   PPBO_REQUIRE(ctx, d_xi && d_x && d_alpha, "xi / x / alpha");
   return line_acq_impl(ctx, model, nullptr, d_xi, d_x, d_alpha, alpha_per_line != 0, B, G, shrink, d_z, S, mustar,
                        jitter, d_ei, d_varmax, (hipStream_t)stream);
-}
-
-// the same entry points for a model whose d_G holds an edge-form operator (ppbo_posterior_edge)
-int ppbo_predict_edge(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc, int64_t M, int score_kind,
-                      double mustar, double* d_mu, double* d_var, double* d_score, double* h_best_val,
-                      int64_t* h_best_idx, void* stream) {
-  PpboEdgeScope es(ctx);
-  return ppbo_predict(ctx, model, d_Xc, M, score_kind, mustar, d_mu, d_var, d_score, h_best_val, h_best_idx, stream);
-}
-
-int ppbo_predict_record_edge(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc, int64_t M, int score_kind,
-                             double mustar, int64_t index_offset, double* d_record, void* stream) {
-  PpboEdgeScope es(ctx);
-  return ppbo_predict_record(ctx, model, d_Xc, M, score_kind, mustar, index_offset, d_record, stream);
-}
-
-int ppbo_predict_cov_edge(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc, int M, double shrink,
-                          double* d_mu, double* d_cov, void* stream) {
-  PpboEdgeScope es(ctx);
-  return ppbo_predict_cov(ctx, model, d_Xc, M, shrink, d_mu, d_cov, stream);
-}
-
-int ppbo_line_acq_edge(ppbo_ctx* ctx, const ppbo_model* model, const double* d_grid, int B, int G, double shrink,
-                       const double* d_z, int S, double mustar, double jitter, double* d_ei, double* d_varmax,
-                       void* stream) {
-  PpboEdgeScope es(ctx);
-  return ppbo_line_acq(ctx, model, d_grid, B, G, shrink, d_z, S, mustar, jitter, d_ei, d_varmax, stream);
-}
-
-int ppbo_line_acq_xi_edge(ppbo_ctx* ctx, const ppbo_model* model, const double* d_xi, const double* d_x,
-                          const double* d_alpha, int alpha_per_line, int B, int G, double shrink, const double* d_z,
-                          int S, double mustar, double jitter, double* d_ei, double* d_varmax, void* stream) {
-  PpboEdgeScope es(ctx);
-  return ppbo_line_acq_xi(ctx, model, d_xi, d_x, d_alpha, alpha_per_line, B, G, shrink, d_z, S, mustar, jitter, d_ei,
-                          d_varmax, stream);
 }
 
 int ppbo_randn(ppbo_ctx* ctx, uint64_t seed, double* d_out, int64_t n, void* stream) {

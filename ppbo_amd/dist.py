@@ -86,8 +86,7 @@ class ShardedSearch:
         from .engine import SCORE_MEAN, _ptr
         self._md = engine._model(post, score != SCORE_MEAN)
         self._md_ref = _C.byref(self._md)
-        self._search_fn = engine._entry("ppbo_search_sharded", post)    # the entry points for the posterior's form
-        self._record_fn = engine._entry("ppbo_predict_record", post)
+        self._search_fn, self._record_fn = engine.lib.ppbo_search_sharded, engine.lib.ppbo_predict_record
         self._xc_ptr, self._M = _ptr(self.Xc), int(self.Xc.shape[0])
         self._bv, self._bi = _C.c_double(0.0), _C.c_int64(-1)
         self._bv_ref, self._bi_ref = _C.byref(self._bv), _C.byref(self._bi)

@@ -13,7 +13,7 @@ from ._lib import KERNEL_IDS, SCORE_MEAN, SCORE_POINTWISE_EI, SCORE_VARIANCE, PP
 
 # Posterior.form: which variance operator G holds (include/ppbo_hip.h, PPBO_FORM_*)
 FORM_NODE = 0   # G = R Lambda, block lower triangular [N, N]
-FORM_EDGE = 1   # H = L22^-1 of the edge-coordinate factor, rows / columns [n_q, N) (ppbo_posterior_edge)
+FORM_EDGE = 1   # H = L22^-1 of the edge-coordinate factor, rows / columns [n_q, N)
 
 RFF_MULTI_MAX_S = 1024  # PPBO_RFF_MULTI_MAX_S: posterior samples per batched RFF enqueue (include/ppbo_hip.h)
 SHRINKAGE = 1e-6  # COVARIANCE_SHRINKAGE of the reference (gp_model.py:26)
@@ -98,7 +98,7 @@ class Posterior:
     scale: np.ndarray | None = None  # ARD: s_d = 1 / l_d (None: a scalar length scale)
     camphor: np.ndarray | None = None  # camphor_copper_ard_kernel: l_0..l_5; X then holds the embedded rows [N, 11]
     Xc: torch.Tensor | None = None     # ... and this the caller's rows [N, 6] (mu_star searches in their coordinates)
-    form: int = FORM_NODE              # FORM_NODE / FORM_EDGE: how G is to be read (the *_edge entry points take FORM_EDGE)
+    form: int = FORM_NODE              # FORM_NODE / FORM_EDGE: how G is to be read (ppbo_model.form)
 
     @property
     def embedded(self):
@@ -246,6 +246,7 @@ class Engine:
         md.d_G = post.G.data_ptr() if (with_var and post.G is not None) else 0
         md.kstar_fp32 = int(bool(kstar_fp32))
         md.d_Gt = 0
+        md.form = post.form
         if md.d_G and post.form == FORM_NODE and N <= 1024 and post.kernel != "camphor_copper_kernel":
             # models the one-launch scoring kernel takes: its matrix-core loop reads G transposed -- formed ONCE per
             # posterior here (the library would otherwise do it in a workspace on every call)
@@ -256,10 +257,6 @@ class Engine:
                 torch.cuda.current_stream(self.device).synchronize()
             md.d_Gt = post.Gt.data_ptr()
         return md
-
-    def _entry(self, name, post):
-        """The library entry point `name` for post's operator form (its *_edge namesake for FORM_EDGE)."""
-        return getattr(self.lib, name + "_edge" if post.form == FORM_EDGE else name)
 
     def posterior_form(self, kernel, N, D, m):
         """The operator form to build for a model of this shape (ppbo_posterior_form): FORM_NODE where the one-launch
@@ -321,8 +318,8 @@ class Engine:
         Xc = self._points(post, Xc)
         md = self._model(post, score != SCORE_MEAN, kstar_fp32)
         rec = self.empty(2) if out is None else out
-        rc = self._entry("ppbo_predict_record", post)(self.ctx, C.byref(md), _ptr(Xc), Xc.shape[0], int(score),
-                                                      float(mustar), int(index_offset), _ptr(rec), self._stream())
+        rc = self.lib.ppbo_predict_record(self.ctx, C.byref(md), _ptr(Xc), Xc.shape[0], int(score), float(mustar),
+                                          int(index_offset), _ptr(rec), self._stream())
         self._check(rc, "ppbo_predict_record")
         return rec
 
@@ -335,9 +332,8 @@ class Engine:
         Xc = self._points(post, Xc)
         md = self._model(post, score != SCORE_MEAN, kstar_fp32)
         bv, bi = C.c_double(0.0), C.c_int64(-1)
-        rc = self._entry("ppbo_search_sharded", post)(self.ctx, C.byref(md), _ptr(Xc), Xc.shape[0], int(score),
-                                                      float(mustar), int(index_offset), C.byref(bv), C.byref(bi),
-                                                      self._stream())
+        rc = self.lib.ppbo_search_sharded(self.ctx, C.byref(md), _ptr(Xc), Xc.shape[0], int(score), float(mustar),
+                                          int(index_offset), C.byref(bv), C.byref(bi), self._stream())
         self._check(rc, "ppbo_search_sharded")
         return bv.value, bi.value
 
@@ -604,10 +600,10 @@ class Engine:
         opts = _lib.FitOpts(float(gtol), int(maxiter), int(verbose), 0.0, int(lbfgs_max_evals), 0, int(bool(start_is_whitened)))
         st = _lib.FitStats()
         info = C.c_int(0)
-        fit_fn = self.lib.ppbo_gp_fit_edge if form == FORM_EDGE else self.lib.ppbo_gp_fit
-        rc = fit_fn(self.ctx, self._kid(kernel), _ptr(X), N, D, self._theta(theta), float(shrink), int(m),
+        rc = self.lib.ppbo_gp_fit(self.ctx, self._kid(kernel), _ptr(X), N, D, self._theta(theta), float(shrink), int(m),
                                   _ptr(f0), C.byref(opts), _ptr(Sigma), _ptr(Sinv), _ptr(L), _ptr(Linv), _ptr(fmap),
-                                  _ptr(alpha), _ptr(ld), _ptr(lo), _ptr(G), C.byref(st), C.byref(info), self._stream())
+                                  _ptr(alpha), _ptr(ld), _ptr(lo), _ptr(G), int(form), C.byref(st), C.byref(info),
+                                  self._stream())
         if rc == PPBO_ERR_NOT_PD and info.value == 2:
             post = None
         else:
@@ -632,9 +628,8 @@ class Engine:
         G = self.empty(N, N)
         P = self.empty(N, N) if want_P else None
         info = C.c_int(0)
-        post_fn = self.lib.ppbo_posterior_edge if form == FORM_EDGE else self.lib.ppbo_posterior
-        rc = post_fn(self.ctx, _ptr(Sigma_inv), _ptr(f), N, m, float(theta[0]), _ptr(alpha), _ptr(ld),
-                     _ptr(lo), _ptr(G), _ptr(P), C.byref(info), self._stream())
+        rc = self.lib.ppbo_posterior(self.ctx, _ptr(Sigma_inv), _ptr(f), N, m, float(theta[0]), _ptr(alpha), _ptr(ld),
+                                     _ptr(lo), _ptr(G), _ptr(P), int(form), C.byref(info), self._stream())
         self._check(rc, "ppbo_posterior", info.value)
         return Posterior(kernel, key, m, X, alpha, ld, lo, G, P, scale=scale, form=form, **cam)
 
@@ -649,8 +644,8 @@ class Engine:
         var = self.empty(M) if (want_var and with_var) else None
         sc = self.empty(M) if want_score else None
         bv, bi = C.c_double(0.0), C.c_int64(-1)
-        rc = self._entry("ppbo_predict", post)(self.ctx, C.byref(md), _ptr(Xc), M, int(score), float(mustar), _ptr(mu),
-                                               _ptr(var), _ptr(sc), C.byref(bv) if want_best else None, C.byref(bi) if want_best else None,
+        rc = self.lib.ppbo_predict(self.ctx, C.byref(md), _ptr(Xc), M, int(score), float(mustar), _ptr(mu), _ptr(var),
+                                   _ptr(sc), C.byref(bv) if want_best else None, C.byref(bi) if want_best else None,
                                    self._stream())
         self._check(rc, "ppbo_predict")
         return dict(mu=mu, var=var, score=sc, best_val=bv.value, best_idx=bi.value)
@@ -660,8 +655,8 @@ class Engine:
         M = Xc.shape[0]
         md = self._model(post, True)
         mu, cov = self.empty(M), self.empty(M, M)
-        rc = self._entry("ppbo_predict_cov", post)(self.ctx, C.byref(md), _ptr(Xc), M, float(shrink), _ptr(mu),
-                                                   _ptr(cov), self._stream())
+        rc = self.lib.ppbo_predict_cov(self.ctx, C.byref(md), _ptr(Xc), M, float(shrink), _ptr(mu), _ptr(cov),
+                                       self._stream())
         self._check(rc, "ppbo_predict_cov")
         return mu, cov
 
@@ -802,12 +797,15 @@ class Engine:
         if post.embedded:
             grid = self._points(post, grid.reshape(B * G, D))
             grid = grid.reshape(B, G, grid.shape[1])
-        z = self.dev(z)
-        S = z.shape[0]
+        return self._line_acq(post, grid, self.dev(z), mustar, shrink, jitter)
+
+    def _line_acq(self, post, grid, z, mustar, shrink, jitter):
+        """ppbo_line_acq on a device grid [B, G, D'] that is already in the rows' coordinates."""
+        B, G = grid.shape[:2]
         md = self._model(post, True)
         ei, vm = self.empty(B), self.empty(B)
-        rc = self._entry("ppbo_line_acq", post)(self.ctx, C.byref(md), _ptr(grid), B, G, float(shrink), _ptr(z), S,
-                                                float(mustar), float(jitter), _ptr(ei), _ptr(vm), self._stream())
+        rc = self.lib.ppbo_line_acq(self.ctx, C.byref(md), _ptr(grid), B, G, float(shrink), _ptr(z), z.shape[0],
+                                    float(mustar), float(jitter), _ptr(ei), _ptr(vm), self._stream())
         self._check(rc, "ppbo_line_acq")
         return ei, vm
 
@@ -832,19 +830,13 @@ class Engine:
             rc = self.lib.ppbo_camphor_line_points(self.ctx, _ptr(xis), _ptr(xs), _ptr(alphas), int(per_line), B, G,
                                                    self._dptr(l), _ptr(grid), self._stream())
             self._check(rc, "ppbo_camphor_line_points")
-            S = z.shape[0]
-            md = self._model(post, True)
-            ei, vm = self.empty(B), self.empty(B)
-            rc = self._entry("ppbo_line_acq", post)(self.ctx, C.byref(md), _ptr(grid), B, G, float(shrink), _ptr(z), S,
-                                                    float(mustar), float(jitter), _ptr(ei), _ptr(vm), self._stream())
-            self._check(rc, "ppbo_line_acq")
-            return ei, vm
+            return self._line_acq(post, grid, z, mustar, shrink, jitter)
         xis, xs = self._points(post, xis), self._points(post, xs)
         S = z.shape[0]
         md = self._model(post, True)
         ei, vm = self.empty(B), self.empty(B)
-        rc = self._entry("ppbo_line_acq_xi", post)(self.ctx, C.byref(md), _ptr(xis), _ptr(xs), _ptr(alphas),
-                                                   int(per_line), B, G, float(shrink), _ptr(z), S, float(mustar), float(jitter), _ptr(ei), _ptr(vm),
+        rc = self.lib.ppbo_line_acq_xi(self.ctx, C.byref(md), _ptr(xis), _ptr(xs), _ptr(alphas), int(per_line), B, G,
+                                       float(shrink), _ptr(z), S, float(mustar), float(jitter), _ptr(ei), _ptr(vm),
                                        self._stream())
         self._check(rc, "ppbo_line_acq_xi")
         return ei, vm

@@ -1,4 +1,4 @@
-"""NumPy statement of the edge-form variance operator (ppbo_posterior_edge, include/ppbo_hip.h).
+"""NumPy statement of the edge-form variance operator (ppbo_posterior with PPBO_FORM_EDGE, include/ppbo_hip.h).
 
 Lambda = sum over the star edges (obs_q, j) of w_j (e_obs - e_j)(e_obs - e_j)' (lam_diag[j] = w_j, lam_off[j] = -w_j,
 lam_diag[obs] = the star's sum), B = Sigma^-1 - Lambda, P = B^-1.  With D the E x N edge incidence and e = diag(w) D k*:

@@ -29,7 +29,7 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, s), f"libppbo_hip.so does not export {s}"
         assert s in _lib.SIGNATURES, f"ctypes binding lacks {s}"
     assert set(_lib.SIGNATURES) == set(header_symbols())
-    assert lib.ppbo_abi_version() == _lib.ABI_VERSION == 6
+    assert lib.ppbo_abi_version() == _lib.ABI_VERSION == 7
 
 
 def test_library_exports_nothing_but_the_c_abi():
@@ -47,6 +47,47 @@ def test_library_exports_nothing_but_the_c_abi():
     exported = sorted(n for n in names if not n.startswith("__hip_"))
     assert exported == header_symbols(), sorted(set(exported) ^ set(header_symbols()))
     assert all(n.startswith("__hip_cuid_") for n in names if n.startswith("__hip_"))
+
+
+def test_no_edge_twins_anywhere():
+    """The operator's form is ppbo_model.form / the form argument, never a function name."""
+    import shutil
+    import subprocess
+    from ppbo_amd import _lib
+    if not os.path.exists(_lib.LIB_PATH):
+        from ppbo_amd.build import build
+        build(verbose=False)
+    nm = shutil.which("nm") or "/opt/rocm/lib/llvm/bin/llvm-nm"
+    out = subprocess.run([nm, "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    exported = [ln.split()[-1] for ln in out.splitlines() if ln.strip()]
+    assert len(exported) > 50
+    for names in (header_symbols(), list(_lib.SIGNATURES), exported):
+        assert not [n for n in names if n.endswith("_edge")]
+
+
+def test_model_struct_matches_the_header(tmp_path):
+    """_lib.Model is ppbo_model: `form` is its last member, and the size and every field offset are what the C compiler
+    gives the header's struct."""
+    import ctypes as C
+    import shutil
+    import subprocess
+    from ppbo_amd import _lib
+    names = [f[0] for f in _lib.Model._fields_]
+    assert names[-1] == "form" and _lib.Model.form.size == C.sizeof(C.c_int)
+    assert _lib.Model().form == 0          # a zero-initialised model is a node-form model
+    cc = shutil.which("cc") or shutil.which("gcc") or shutil.which("clang")
+    assert cc, "no C compiler to lay out ppbo_model with"
+    src = tmp_path / "layout.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "ppbo_hip.h"\n'
+                   'int main(void) { printf("%zu", sizeof(ppbo_model));\n'
+                   + "".join(f'  printf(" %zu", offsetof(ppbo_model, {n}));\n' for n in names)
+                   + '  printf(" %d %d", PPBO_FORM_NODE, PPBO_FORM_EDGE); return 0; }\n')
+    exe = tmp_path / "layout"
+    subprocess.run([cc, "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
+    out = [int(v) for v in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
+    assert out[0] == C.sizeof(_lib.Model)
+    assert out[1:-2] == [getattr(_lib.Model, n).offset for n in names]
+    assert out[-2:] == [0, 1]
 
 
 def test_no_gpu_means_loud_failure():

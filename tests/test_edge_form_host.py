@@ -1,4 +1,4 @@
-"""CPU-only: the edge-form identity of ppbo_posterior_edge in NumPy (tests/probes/edge_form_identity.py)."""
+"""CPU-only: the edge-form identity of ppbo_posterior (PPBO_FORM_EDGE) in NumPy (tests/probes/edge_form_identity.py)."""
 import importlib.util
 import os
 

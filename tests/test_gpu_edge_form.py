@@ -1,5 +1,6 @@
-"""GPU: the variance operator in edge form (ppbo_posterior_edge / ppbo_gp_fit_edge and the *_edge consumers) against the
-node form on the same posterior and against the golden vectors.  tests/probes/edge_form_identity.py states the identity."""
+"""GPU: the variance operator in edge form (ppbo_posterior / ppbo_gp_fit with PPBO_FORM_EDGE, and every consumer of a
+model whose `form` says so) against the node form on the same posterior and against the golden vectors.
+tests/probes/edge_form_identity.py states the identity."""
 import os
 
 import numpy as np
@@ -167,3 +168,87 @@ def test_edge_form_with_fp32_kstar(eng, name):
     c = host(eng.predict(edge, Xc, score=SCORE_VARIANCE)["var"])
     assert np.abs(a - b).max() <= 5e-8 * sf2
     assert np.abs(b - c).max() <= 1e-4 * sf2
+
+
+def test_a_form_outside_node_and_edge_is_refused(eng):
+    """ppbo_model.form = 2, and ppbo_posterior(..., form = 2): a negative status and a message naming the form, from the
+    argument checks (nothing is launched)."""
+    import ctypes as C
+    from ppbo_amd.engine import FORM_EDGE, _ptr
+    g = load("smoke")
+    th, kern, m = g["theta"], str(g["kernel"]), int(g["m"])
+    Sinv = eng.pd_inverse(eng.gram(g["X"], th, kern))
+    post = eng.posterior(g["X"], th, kern, Sinv, g["fMAP"], m, form=FORM_EDGE)
+    md = eng._model(post, True)
+    md.form = 2
+    N, D = post.X.shape
+    M, B, G, S = 64, 2, 16, 8
+    Xc = eng.dev(np.random.default_rng(0).random((M, D)))
+    z = eng.dev(np.random.default_rng(1).standard_normal((S, G)))
+    mu, var, cov, ei, vm = eng.empty(M), eng.empty(M), eng.empty(M, M), eng.empty(B), eng.empty(B)
+    buf = C.create_string_buffer(256)
+
+    def refused(rc):
+        assert rc < 0
+        eng.lib.ppbo_last_error(eng.ctx, buf, 256)
+        assert b"invalid argument" in buf.value and b"form" in buf.value, buf.value
+
+    refused(eng.lib.ppbo_predict(eng.ctx, C.byref(md), _ptr(Xc), M, 0, 0.0, _ptr(mu), _ptr(var), None, None, None,
+                                 eng._stream()))
+    refused(eng.lib.ppbo_predict_cov(eng.ctx, C.byref(md), _ptr(Xc), M, 0.0, _ptr(mu), _ptr(cov), eng._stream()))
+    refused(eng.lib.ppbo_line_acq(eng.ctx, C.byref(md), _ptr(Xc), B, G, 0.0, _ptr(z), S, 0.0, 0.0, _ptr(ei), _ptr(vm),
+                                  eng._stream()))
+    f = eng.dev(g["fMAP"]).reshape(-1)
+    info = C.c_int(0)
+    refused(eng.lib.ppbo_posterior(eng.ctx, _ptr(Sinv), _ptr(f), N, m, float(th[0]), _ptr(eng.empty(N)), _ptr(eng.empty(N)),
+                                   _ptr(eng.empty(N)), _ptr(eng.empty(N, N)), None, 2, C.byref(info), eng._stream()))
+    md.form = FORM_EDGE     # the same descriptor with its own form is taken
+    assert eng.lib.ppbo_predict(eng.ctx, C.byref(md), _ptr(Xc), M, 0, 0.0, _ptr(mu), _ptr(var), None, None, None,
+                                eng._stream()) == 0
+
+
+@pytest.mark.parametrize("name", [n for n in ("smoke", "c3") if n in ALL])
+def test_alternating_forms_on_one_engine_match_single_form_engines(name):
+    """One engine serving a node-form and an edge-form posterior in turn (node, edge, node, edge) computes, bit for bit,
+    what an engine that only ever saw one of the two computes: the form travels with the model, no call leaves anything
+    behind for the next.  Every path compared here (posterior, predict, predict_cov, line_acq_xi) repeats bit for bit
+    between two engines of the same form."""
+    from ppbo_amd.engine import FORM_EDGE, FORM_NODE, SCORE_POINTWISE_EI, Engine
+    g = load(name)
+    th, kern, m, sf2 = g["theta"], str(g["kernel"]), int(g["m"]), float(g["theta"][2]) ** 2
+    rng = np.random.default_rng(17)
+    D = int(g["D"])
+    Xc = np.concatenate([g["Xc"][:1000], rng.random((3000, D))])
+    B, G, S = 6, 70, 150
+    al = np.linspace(0.005, 0.995, G)
+    xis = np.eye(D)[np.arange(B) % D]
+    xs = rng.random((B, D))
+    xs[np.arange(B), np.arange(B) % D] = 0.0
+    z = rng.standard_normal((S, G))
+    mustar = float(np.max(g["mu"]))
+
+    def build(e, form):
+        return e.posterior(g["X"], th, kern, e.pd_inverse(e.gram(g["X"], th, kern)), g["fMAP"], m, form=form)
+
+    def calls(e, post):
+        p = e.predict(post, Xc, score=SCORE_POINTWISE_EI, mustar=mustar, want_score=True)
+        out = [host(p["mu"]), host(p["var"]), host(p["score"]), np.array([p["best_val"], p["best_idx"]])]
+        out += [host(t) for t in e.predict_cov(post, g["line_grid"])]
+        out += [host(t) for t in e.line_acq_xi(post, xis, xs, al, z, float(g["line_mustar"]), jitter=1e-9 * sf2)]
+        return out
+
+    forms = (FORM_NODE, FORM_EDGE)
+    mixed = Engine(0)
+    posts = {f: build(mixed, f) for f in forms}
+    got = [(f, calls(mixed, posts[f])) for f in forms + forms]
+    mixed.close()
+    for form in forms:
+        alone = Engine(0)
+        post = build(alone, form)
+        assert np.array_equal(host(post.G), host(posts[form].G))
+        want = [calls(alone, post) for _ in range(2)]
+        alone.close()
+        for w, (_, r) in zip(want, [x for x in got if x[0] == form]):
+            assert len(w) == len(r) == 8
+            for a, b in zip(w, r):
+                assert np.array_equal(a, b)
