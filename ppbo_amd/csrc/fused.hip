@@ -297,6 +297,9 @@ __global__ __launch_bounds__(64 * NW, 4) void fused_score_kernel(const FusedArgs
     cc[ct] = cnd < a.M ? cnd : a.M - 1;
     nc[ct] = fs_sumsq(a.Xc + (size_t)cc[ct] * D, D);
   }
+  // is |c|^2 of the candidate this lane FINISHES (thread t < 32: candidate t = column lr of column tile t >> 4) non-finite?
+  // Decided here, where the norm is at hand, and carried to the end as a lane mask
+  const bool cbad = !(fabs((lane >> 4) & 1 ? nc[1] : nc[0]) < INFINITY);
   // operand addressing of the K* tiles, fixed per lane for the whole kernel: candidates through a buffer descriptor on the
   // workgroup's 32 rows of Xc (rows past M read as zeros), design points through one on X (rows past N likewise); the
   // pass, tile and dimension offsets are wave-uniform and travel in the scalar offset / the immediate
@@ -373,10 +376,13 @@ __global__ __launch_bounds__(64 * NW, 4) void fused_score_kernel(const FusedArgs
 #pragma unroll
           for (int s4 = 0; s4 < 4; ++s4) {
             af[s4] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(xr, voffx + 32 * s4, sx, 0));
-            // -2 c, and an explicit zero beyond D (the load finds the next candidate's first coordinates there)
-            const double mk = (d0 + 4 * s4 + lk < D) ? -2.0 : 0.0;
-            bf[0][s4] = mk * __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(cr, voffc0 + 32 * s4, sc, 0));
-            bf[1][s4] = mk * __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(cr, voffc1 + 32 * s4, sc, 0));
+            // -2 c, and an explicit zero beyond D: the load finds the next candidate's first coordinates there, which may
+            // be NaN or infinite -- selected away, not multiplied by zero
+            const bool in = d0 + 4 * s4 + lk < D;
+            const double c0v = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(cr, voffc0 + 32 * s4, sc, 0));
+            const double c1v = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(cr, voffc1 + 32 * s4, sc, 0));
+            bf[0][s4] = in ? -2.0 * c0v : 0.0;
+            bf[1][s4] = in ? -2.0 * c1v : 0.0;
           }
 #pragma unroll
           for (int s4 = 0; s4 < 4; ++s4) {
@@ -501,9 +507,13 @@ __global__ __launch_bounds__(64 * NW, 4) void fused_score_kernel(const FusedArgs
     double m = 0.0, tt = 0.0, qq = 0.0;
 #pragma unroll
     for (int w = 0; w < NW; ++w) { m += red_m[w * 32 + t]; tt += red_d[w * 32 + t] + red_t[w * 32 + t]; qq += red_q[w * 32 + t]; }
+    // A candidate with a NaN or infinite coordinate gets NaN results (cbad): the K* tiles clip r^2 with fmax, which drops
+    // a NaN, so its sums above are those of a row on top of every design row or infinitely far from all of them.
+    if (cbad) { m = NAN; tt = NAN; }
     const double var = a.sf2 + tt + qq;
     double sc;
-    if (a.kind == PPBO_SCORE_MEAN) sc = m;
+    if (m != m) sc = m;
+    else if (a.kind == PPBO_SCORE_MEAN) sc = m;
     else if (a.kind == PPBO_SCORE_VARIANCE) sc = var;
     else {
       const double d = m - a.mustar;

@@ -271,8 +271,19 @@ __global__ __launch_bounds__(KS_THREADS) void kstar_kernel(
 #pragma unroll
   for (int q = 0; q < KS_CPT; ++q) {
     if (c0 + q < M) {
-      mu_part[(size_t)blockIdx.y * M + c0 + q] = mu[q];
-      if (t_part) t_part[(size_t)blockIdx.y * M + c0 + q] = tl[q];
+      // A candidate with a NaN or infinite coordinate leaves as NaN partial sums (score_kernel then gives the row NaN
+      // results): the pair loop clips r^2 with fmax, which drops a NaN, so its sums are those of a row on top of every
+      // design row or infinitely far from all of them.  |c|^2 says so where it is formed; the other forms look at the
+      // coordinates once more here, after the pair loop, where the registers are free
+      bool finite;
+      if (EXPAND) finite = nc[q] < INFINITY;
+      else {
+        double chk = 0.0;
+        for (int d = 0; d < D; ++d) chk = fma(Xc[(size_t)(c0 + q) * D + d], 0.0, chk);
+        finite = chk == 0.0;
+      }
+      mu_part[(size_t)blockIdx.y * M + c0 + q] = finite ? mu[q] : NAN;
+      if (t_part) t_part[(size_t)blockIdx.y * M + c0 + q] = finite ? tl[q] : NAN;
     }
   }
 }
@@ -1087,7 +1098,7 @@ int ppbo_predict(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc, int
                               &chunk_best, &n_chunks, s, hr.d_flag, hr.epoch))
     return rc;
   if (int rc = ppbo_host_record_wait(ctx, hr, s)) return rc;
-  if (h_best_val) *h_best_val = hr.h_rec[1] < 0.0 ? 0.0 : hr.h_rec[0];
+  if (h_best_val) *h_best_val = hr.h_rec[0];      // (NaN, -1) when no candidate has a non-NaN score
   if (h_best_idx) *h_best_idx = (int64_t)hr.h_rec[1];
   return 0;
 }

@@ -78,7 +78,8 @@ __global__ __launch_bounds__(SC_THREADS) void score_kernel(const double* __restr
     for (int w = 0; w < SC_WAVES; ++w) { mu += part[0][w][lane]; t += part[1][w][lane]; q += part[2][w][lane]; }
     const double var = slab ? sf2 + t + q : sf2;
     double sc;
-    if (kind == PPBO_SCORE_MEAN) sc = mu;
+    if (mu != mu) sc = mu;                 // a NaN mean (kstar_kernel: a candidate with a non-finite coordinate) never scores
+    else if (kind == PPBO_SCORE_MEAN) sc = mu;
     else if (kind == PPBO_SCORE_VARIANCE) sc = var;
     else {
       const double d = mu - mustar;
