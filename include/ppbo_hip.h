@@ -326,6 +326,32 @@ PPBO_API int ppbo_predict(ppbo_ctx* ctx, const ppbo_model* model, const double* 
 PPBO_API int ppbo_predict_record(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc, int64_t M,
                         int score_kind, double mustar, int64_t index_offset, double* d_record, void* stream);
 
+/* ---- duels: mean, variance and win probability of f(a) - f(b) for M pairs (no reference counterpart) ----------------
+ * The likelihood of the model is a probit on differences of noisy utilities (src/gp_model.py:176-204, sum_Phi:
+ * Phi((f_obs - f_j) / (sqrt2 sigma)) per pseudo-observation); this entry extends those lines from the fitted rows to
+ * any two points under the Laplace posterior.  The reference itself never predicts a comparison: the only route there
+ * is the dense M x M covariance of mu_Sigma_pred (:441-452).  With d = k(a, X) - k(b, X):
+ *   mu_d  = d' alpha
+ *   var_d = Var[f(a) - f(b)] = (2 sigma_f^2 - 2 k(a, b)) + d' Lambda d + |G d|^2   (the operator of ppbo_posterior on d)
+ *   p     = P(a > b) = Phi(mu_d / sqrt(2 sigma^2 + max(var_d, 0))),  sigma = theta[0]
+ * d is formed directly (both points against each design row in one instruction chain), so a near-tie keeps its digits,
+ * a == b gives mu_d = var_d = 0 and p = 1/2 exactly, and swapping the sides negates mu_d bit for bit.  The prior term
+ * 2 sigma_f^2 - 2 k(a, b) comes from the direct differences a - b in a form that does not cancel at small distances; it
+ * is NOT shrunk (mu_Sigma_pred shrinks its M x M prior block by 1e-6).
+ * d_Xa / d_Xb [M, D]: the two sides in the MODEL's coordinates, as ppbo_predict takes d_Xc (scaled rows of an ARD model,
+ * embedded rows of a camphor model with per-coordinate length scales).  Outputs, each may be NULL: d_mu, d_var, d_prob,
+ * d_score [M] (the quantity score_kind names) and h_best_val / h_best_idx, the largest score and its FIRST index; NaN
+ * never wins, (NaN, -1) when nothing scored.  A pair with a NaN or infinite coordinate on either side gets NaN outputs.
+ * PPBO_PAIR_MEAN with d_var == d_prob == NULL reads neither d_G nor Lambda and runs no contraction.  Pairs go in
+ * chunks of 65536 through ppbo_predict's workspaces; both operator forms take the same three launches, whatever N.
+ * "invalid argument": a NULL model, d_Xa or d_Xb; M outside 1 .. 2^31 - 1; an unknown score_kind; model->kstar_fp32 set
+ * (fp64 only); a model without d_G (or Lambda) when the variance, the probability or a score other than the mean is
+ * asked for. */
+enum { PPBO_PAIR_MEAN = 0, PPBO_PAIR_VARIANCE = 1, PPBO_PAIR_PROB = 2 };
+PPBO_API int ppbo_predict_pairs(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xa, const double* d_Xb, int64_t M,
+                       int score_kind, double* d_mu, double* d_var, double* d_prob, double* d_score,
+                       double* h_best_val, int64_t* h_best_idx, void* stream);
+
 /* full predictive covariance of small sets (the G=70 line grid of EI):
  * d_cov[M,M] = (1-s)K(Xc,Xc) + s sigma_f^2 I - K*^T A K*  (src/gp_model.py:447-450) */
 PPBO_API int ppbo_predict_cov(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc, int M,

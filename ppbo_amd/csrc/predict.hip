@@ -288,6 +288,170 @@ __global__ __launch_bounds__(KS_THREADS) void kstar_kernel(
   }
 }
 
+// Pass 1 of ppbo_predict_pairs: the column of a DUEL, d = k(a, X) - k(b, X), in place of k*.  One lane = ONE pair, its two
+// points in the registers kstar_kernel gives its two candidates (two pairs per lane would spill in the DP = 64 bucket).
+// Both points meet each staged design row in the same instruction chain (q = 0: a, q = 1: b; the expansion form, or the
+// camphor feature form), so a == b gives ka == kb bit for bit and swapping the sides negates dv exactly.  Everything
+// that kstar_kernel does with kv is done with dv = ka - kb: the mean sum, the star sums of d' Lambda d (ko = the
+// observation row's dv) and the stored column in node or edge form -- all of them linear or quadratic in the column.
+// fp64 only.  Launch geometry: kstar_kernel's row splits, KS_THREADS pairs per workgroup.
+template <int KID, int DP>
+__global__ __launch_bounds__(KS_THREADS) void kstar_pair_kernel(
+    const double* __restrict__ X, int N, int D, KernParams p, const double* __restrict__ alpha,
+    const double* __restrict__ lam_diag, const double* __restrict__ lam_off, int mblk,
+    const double* __restrict__ Xa, const double* __restrict__ Xb, int M, double* __restrict__ Kt, int ldk,
+    double* __restrict__ mu_part, double* __restrict__ t_part, int q_per_split, int n_q, int edge_k0) {
+  static_assert(KID != PPBO_KERNEL_CAMPHOR || DP == 12, "camphor-copper: the feature form only");
+  __shared__ __attribute__((aligned(16))) double xs[KS_RJ * DP];
+  __shared__ double s_alpha[KS_RJ], s_ld[KS_RJ], s_lo[KS_RJ], s_nx[KS_RJ];
+  constexpr bool CAMF = (KID == PPBO_KERNEL_CAMPHOR);     // see kstar_kernel for both forms
+  const int c = blockIdx.x * KS_THREADS + threadIdx.x;
+  const bool live = c < M;
+  double xc[2][DP], nc[2];
+  double mu = 0.0, tl = 0.0, ko = 0.0;
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    const double* __restrict__ src = (q == 0 ? Xa : Xb) + (size_t)(live ? c : 0) * D;
+    nc[q] = 0.0;
+    if constexpr (CAMF) {
+#pragma unroll
+      for (int k = 0; k < 5; ++k) {
+        const double v = live ? src[k < 2 ? k : k + 1] : 0.0;
+        double sn, cs;
+        sincospi(2.0 * v, &sn, &cs);
+        xc[q][k] = -0.5 * p.c0 * cs;
+        xc[q][5 + k] = -0.5 * p.c0 * sn;
+      }
+      xc[q][10] = live ? src[2] : 0.0;
+      xc[q][11] = 0.0;
+    } else {
+#pragma unroll
+      for (int d = 0; d < DP; ++d) {
+        double v = (d < D && live) ? src[d] : 0.0;
+        nc[q] = fma(v, v, nc[q]);
+        xc[q][d] = -2.0 * v;
+      }
+    }
+  }
+  const int j_beg = blockIdx.y * q_per_split * mblk;
+  int j_end = j_beg + q_per_split * mblk;
+  if (j_end > N) j_end = N;
+  const bool has_lam = (lam_diag != nullptr);
+  int rb = 0;  // row index inside the current star block (splits start on a block edge)
+  int qs = j_beg / mblk;  // ... and that block's star
+  for (int row0 = j_beg; row0 < j_end; row0 += KS_RJ) {
+    __syncthreads();
+    if constexpr (CAMF) {
+      for (int e = threadIdx.x; e < KS_RJ * 6; e += KS_THREADS) {
+        const int r = e / 6, k = e - r * 6;
+        const int j = row0 + r;
+        if (k < 5) {
+          const double v = (j < j_end) ? X[(size_t)j * D + (k < 2 ? k : k + 1)] : 0.0;
+          double sn, cs;
+          sincospi(2.0 * v, &sn, &cs);
+          xs[r * DP + k] = cs;
+          xs[r * DP + 5 + k] = sn;
+        } else {
+          xs[r * DP + 10] = (j < j_end) ? X[(size_t)j * D + 2] : 0.0;
+          xs[r * DP + 11] = 0.0;
+        }
+      }
+    } else {
+      for (int e = threadIdx.x; e < KS_RJ * DP; e += KS_THREADS) {
+        const int r = e / DP, d = e - r * DP;
+        const int j = row0 + r;
+        xs[e] = (j < j_end && d < D) ? X[(size_t)j * D + d] : 0.0;
+      }
+    }
+    if (threadIdx.x < KS_RJ) {
+      const int j = row0 + threadIdx.x;
+      const bool ok = j < j_end;
+      s_alpha[threadIdx.x] = ok ? alpha[j] : 0.0;
+      s_ld[threadIdx.x] = (ok && has_lam) ? lam_diag[j] : 0.0;
+      s_lo[threadIdx.x] = (ok && has_lam) ? lam_off[j] : 0.0;
+      if (!CAMF) {
+        double nx = 0.0;
+        if (ok)
+          for (int d = 0; d < D; ++d) { const double v = X[(size_t)j * D + d]; nx = fma(v, v, nx); }
+        s_nx[threadIdx.x] = nx;
+      }
+    }
+    __syncthreads();
+    const int rmax = (j_end - row0 < KS_RJ) ? (j_end - row0) : KS_RJ;
+    for (int r = 0; r < rmax; ++r) {
+      const double* __restrict__ xr = xs + r * DP;
+      double sv[2] = {0.0, 0.0}, kv[2];
+      if constexpr (CAMF) {
+#pragma unroll
+        for (int d = 0; d < 10; ++d) {
+          const double x = xr[d];
+#pragma unroll
+          for (int q = 0; q < 2; ++q) sv[q] = fma(x, xc[q][d], sv[q]);
+        }
+        const double x2 = xr[10], base = 2.5 * p.c0;
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+          const double dd = x2 - xc[q][10];
+          sv[q] = fma(p.c1 * dd, dd, sv[q] + base);
+        }
+      } else {
+#pragma unroll
+        for (int d = 0; d < DP; ++d) {
+          const double x = xr[d];
+#pragma unroll
+          for (int q = 0; q < 2; ++q) sv[q] = fma(x, xc[q][d], sv[q]);
+        }
+        const double nx = s_nx[r];
+#pragma unroll
+        for (int q = 0; q < 2; ++q) sv[q] = fmax(sv[q] + (nx + nc[q]), 0.0);
+      }
+#pragma unroll
+      for (int q = 0; q < 2; ++q) kv[q] = kern_finish<KID>(sv[q], p);
+      // the two values as opaque registers: the subtraction must not be contracted with the product that ends
+      // kern_finish (fma(sf2, ea, -(sf2 eb)) is not 0 when ea == eb)
+      asm volatile("" : "+v"(kv[0]), "+v"(kv[1]));
+      const double dv = kv[0] - kv[1];
+      if (Kt) {
+        // the layouts of kstar_kernel: node form row j, edge form row n_q + q m + t = lam_off[j] (d_j - d_obs)
+        int drow = row0 + r;
+        bool wr = true;
+        double ev = dv;
+        if (edge_k0 >= 0) {
+          if (rb == 0) {
+            drow = qs;
+            wr = qs >= edge_k0;
+            ev = 0.0;
+          } else {
+            drow = n_q + qs * (mblk - 1) + rb - 1;
+            ev = s_lo[r] * (dv - ko);
+          }
+        }
+        if (wr && live) store_through(Kt + (size_t)drow * ldk + c, ev);
+      }
+      mu += s_alpha[r] * dv;
+      if (has_lam) {
+        const double ld = s_ld[r];
+        if (rb == 0) { ko = dv; tl += ld * dv * dv; }
+        else tl += dv * (ld * dv + 2.0 * s_lo[r] * ko);
+      }
+      if (++rb == mblk) { rb = 0; ++qs; }
+    }
+  }
+  if (live) {
+    // a non-finite coordinate in either point: NaN partial sums (kstar_kernel; the fmax above drops a NaN)
+    bool finite;
+    if constexpr (CAMF) {
+      double chk = 0.0;
+      for (int d = 0; d < D; ++d) chk = fma(Xb[(size_t)c * D + d], 0.0, fma(Xa[(size_t)c * D + d], 0.0, chk));
+      finite = chk == 0.0;
+    } else {
+      finite = (nc[0] + nc[1]) < INFINITY;
+    }
+    mu_part[(size_t)blockIdx.y * M + c] = finite ? mu : NAN;
+    if (t_part) t_part[(size_t)blockIdx.y * M + c] = finite ? tl : NAN;
+  }
+}
+
 // Y = G K* ; slab[mt][c] = sum over the BM rows of tile mt of Y[i,c]^2
 // EDGE: an edge-form operator (H lower triangular, zero in its first n_q rows and columns).  G and Kt then arrive offset
 // by kshift = n_q rounded down to the chunk depth (G + kshift, Kt + kshift ldk): the K loop starts at 0 of the shifted
@@ -932,6 +1096,35 @@ int dispatch_kstar(const ppbo_model* m, const double* d_Xc, int M, double* Kt, i
   });
 }
 
+// kstar_pair_kernel in launch_kstar's D buckets (fp64 only); n_split rows splits as there, KS_THREADS pairs per workgroup
+template <int KID>
+int launch_kstar_pair(const ppbo_model* m, const KernParams& p, const double* d_Xa, const double* d_Xb, int M, double* Kt,
+                      int ldk, double* mu_part, double* t_part, int q_per_split, int n_split, bool with_lam, int edge_k0,
+                      hipStream_t s) {
+  dim3 grid((M + KS_THREADS - 1) / KS_THREADS, n_split);
+  const int mblk = m->m + 1, n_q = (m->N + mblk - 1) / mblk;
+  const double* ld = with_lam ? m->d_lam_diag : nullptr;
+  const double* lo = with_lam ? m->d_lam_off : nullptr;
+#define KSP_LAUNCH(DP)                                                                                               \
+  kstar_pair_kernel<KID, DP><<<grid, KS_THREADS, 0, s>>>(m->d_X, m->N, m->D, p, m->d_alpha, ld, lo, mblk, d_Xa, d_Xb, M, \
+                                                         Kt, ldk, mu_part, with_lam ? t_part : nullptr, q_per_split,   \
+                                                         n_q, edge_k0)
+  if constexpr (KID == PPBO_KERNEL_CAMPHOR) KSP_LAUNCH(12);
+  else if (m->D <= 4) KSP_LAUNCH(4);
+  else if (m->D <= 6) KSP_LAUNCH(6);
+  else if (m->D <= 8) KSP_LAUNCH(8);
+  else if (m->D <= 10) KSP_LAUNCH(10);
+  else if (m->D <= 12) KSP_LAUNCH(12);
+  else if (m->D <= 16) KSP_LAUNCH(16);
+  else if (m->D <= 20) KSP_LAUNCH(20);
+  else if (m->D <= 24) KSP_LAUNCH(24);
+  else if (m->D <= 32) KSP_LAUNCH(32);
+  else if (m->D <= 48) KSP_LAUNCH(48);
+  else KSP_LAUNCH(64);
+#undef KSP_LAUNCH
+  return 0;
+}
+
 int check_model(ppbo_ctx* ctx, const ppbo_model* m) {
   PPBO_REQUIRE(ctx, m != nullptr, "model");
   PPBO_REQUIRE(ctx, m->d_X && m->d_alpha, "model X/alpha");
@@ -1111,6 +1304,107 @@ int ppbo_predict_record(ppbo_ctx* ctx, const ppbo_model* model, const double* d_
   int n_chunks = 0;
   return predict_passes(ctx, model, d_Xc, M, score_kind, mustar, nullptr, nullptr, nullptr, true, d_record,
                         index_offset, &chunk_best, &n_chunks, (hipStream_t)stream);
+}
+
+// Duels: per chunk of 65536 pairs kstar_pair -> quadform -> pair_score -> one-workgroup argmax, with predict_passes'
+// workspaces and operand padding.  Both operator forms take these three launches (the one-launch kernel of fused.hip
+// holds one point per column).
+int ppbo_predict_pairs(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xa, const double* d_Xb, int64_t M,
+                       int score_kind, double* d_mu, double* d_var, double* d_prob, double* d_score, double* h_best_val,
+                       int64_t* h_best_idx, void* stream) {
+  PPBO_ENTER(ctx);
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = check_model(ctx, model)) return rc;
+  PPBO_REQUIRE(ctx, d_Xa != nullptr && d_Xb != nullptr, "pairs (d_Xa / d_Xb)");
+  PPBO_REQUIRE(ctx, M >= 1 && M <= (int64_t)0x7fffffff, "pair count (1 .. 2^31 - 1)");
+  PPBO_REQUIRE(ctx, score_kind == PPBO_PAIR_MEAN || score_kind == PPBO_PAIR_VARIANCE || score_kind == PPBO_PAIR_PROB,
+               "score_kind");
+  PPBO_REQUIRE(ctx, !model->kstar_fp32, "pairs are fp64 only (kstar_fp32)");
+  const bool want_var = d_var || d_prob || score_kind != PPBO_PAIR_MEAN;
+  PPBO_REQUIRE(ctx, !want_var || model->d_G != nullptr, "variance / probability need model->d_G");
+  PPBO_REQUIRE(ctx, !want_var || (model->d_lam_diag && model->d_lam_off), "model Lambda");
+  const bool want_best = h_best_val || h_best_idx;
+  PpboHostRecord hr{};
+  if (want_best)
+    if (int rc = ppbo_host_record(ctx, &hr)) return rc;
+  const int N = model->N, mblk = model->m + 1, n_q = N / mblk;
+  const int edge_k0 = (want_var && model->form == PPBO_FORM_EDGE) ? ppbo_edge_k0(n_q) : -1;
+  const KernParams p = make_kern_params(model->kernel_id, model->theta);
+  const int64_t chunk_cap = 65536;
+  const int64_t n_chunks = (M + chunk_cap - 1) / chunk_cap;
+  const int qf_bm = (quadform_variant(ctx) == 5) ? 256 : 128;
+  const int ntm = (N + qf_bm - 1) / qf_bm;
+  int Nk = N, g_rows = N;
+  const double* Gq = nullptr;
+  if (want_var) {
+    Gq = padded_G(ctx, model, qf_bm, M >= 2048, &Nk, &g_rows, s);
+    if (!Gq) return (int)hipErrorOutOfMemory;
+    PPBO_LAUNCH_CHECK(ctx);
+  }
+  const int Mc_max = (int)(M < chunk_cap ? M : chunk_cap);
+  const int ldk = (Mc_max + 127) & ~127;
+  const int n_split = pick_split(Mc_max, n_q);
+  const int q_per_split = (n_q + n_split - 1) / n_split;
+  const int n_split_eff = (n_q + q_per_split - 1) / q_per_split;
+  double* Kt = nullptr;
+  if (want_var) {
+    Kt = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_KSTAR, (size_t)Nk * ldk * sizeof(double));
+    if (!Kt) return (int)hipErrorOutOfMemory;
+    if (Nk != N) PPBO_HIP_CHECK(ctx, hipMemsetAsync(Kt + (size_t)N * ldk, 0, (size_t)(Nk - N) * ldk * sizeof(double), s));
+  }
+  double* part = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_PART, (size_t)(2 * n_split_eff + ntm) * Mc_max * sizeof(double));
+  if (!part) return (int)hipErrorOutOfMemory;
+  const int sblocks_max = score_blocks(Mc_max);
+  Best* bests = (Best*)ppbo_workspace(ctx, ppbo_ctx::WS_SMALL, (size_t)(sblocks_max + n_chunks) * sizeof(Best));
+  if (!bests) return (int)hipErrorOutOfMemory;
+  Best* chunk_best = bests + sblocks_max;
+  const double two_sigma2 = 2.0 * model->theta[0] * model->theta[0];
+  for (int64_t ch = 0; ch < n_chunks; ++ch) {
+    const int64_t c_beg = ch * chunk_cap;
+    const int Mc = (int)((M - c_beg) < chunk_cap ? (M - c_beg) : chunk_cap);
+    const double* xa = d_Xa + (size_t)c_beg * model->D;
+    const double* xb = d_Xb + (size_t)c_beg * model->D;
+    double* mu_part = part;
+    double* t_part = part + (size_t)n_split_eff * Mc;
+    double* slab = part + (size_t)2 * n_split_eff * Mc;
+    const int sblocks = score_blocks(Mc);
+    const bool one = (n_chunks == 1);
+    if (int rc = ppbo_kernel_dispatch(ctx, model->kernel_id, [&](auto kid) {
+          constexpr int KID = decltype(kid)::value;
+          {
+            PpboProfScope pf(ctx, ppbo_ctx::PF_KSTAR, s);
+            launch_kstar_pair<KID>(model, p, xa, xb, Mc, Kt, ldk, mu_part, t_part, q_per_split, n_split_eff, want_var,
+                                   edge_k0, s);
+          }
+          PPBO_LAUNCH_CHECK(ctx);
+          if (want_var) {
+            PpboProfScope pf(ctx, ppbo_ctx::PF_QUADFORM, s);
+            if (int rc2 = dispatch_quadform(ctx, Gq, Nk, g_rows, N, Kt, ldk, Mc, mblk, slab, edge_k0, s)) return rc2;
+          }
+          PpboProfScope pfs(ctx, ppbo_ctx::PF_SCORE, s);
+          pair_score_kernel<KID><<<sblocks, SC_THREADS, 0, s>>>(
+              mu_part, n_split_eff, t_part, want_var ? slab : nullptr, ntm, Mc, xa, xb, model->D, p, two_sigma2, score_kind,
+              (long long)c_beg, d_mu ? d_mu + c_beg : nullptr, d_var ? d_var + c_beg : nullptr,
+              d_prob ? d_prob + c_beg : nullptr, d_score ? d_score + c_beg : nullptr, want_best ? bests : nullptr);
+          PPBO_LAUNCH_CHECK(ctx);
+          return 0;
+        }))
+      return rc;
+    if (want_best) {
+      argmax_final_kernel<<<1, 256, 0, s>>>(bests, sblocks, chunk_best + ch, one ? hr.d_rec : nullptr, 0,
+                                            one ? hr.d_flag : nullptr, hr.epoch);
+      PPBO_LAUNCH_CHECK(ctx);
+    }
+  }
+  if (!want_best) return 0;
+  if (n_chunks > 1) {
+    best_record_kernel<<<1, 64, 0, s>>>(chunk_best, (int)n_chunks, 0, hr.d_rec, hr.d_flag, hr.epoch);
+    PPBO_LAUNCH_CHECK(ctx);
+  }
+  if (int rc = ppbo_host_record_wait(ctx, hr, s)) return rc;
+  if (h_best_val) *h_best_val = hr.h_rec[0];      // (NaN, -1) when no pair has a non-NaN score
+  if (h_best_idx) *h_best_idx = (int64_t)hr.h_rec[1];
+  return 0;
 }
 
 }  // extern "C"

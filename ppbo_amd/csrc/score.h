@@ -105,6 +105,98 @@ __global__ __launch_bounds__(SC_THREADS) void score_kernel(const double* __restr
   if (lane == 0) blk_best[blockIdx.x] = b;
 }
 
+// 1 - k(a, b) / sigma_f^2 from s, the summed kern_term<KID> of the DIRECT differences a - b, in a form that does not
+// cancel where the two points nearly coincide (2 sigma_f^2 - 2 k(a, b) formed from k itself keeps 1e-16 sigma_f^2 of
+// absolute error, all of the value at r ~ 1e-8 l); exactly 0 at s = 0
+template <int KID>
+__device__ __forceinline__ double kern_one_minus(double s, const KernParams& p) {
+  if constexpr (KID == PPBO_KERNEL_SE) {
+    return -expm1(-p.c0 * s);
+  } else if constexpr (KID == PPBO_KERNEL_RQ) {
+    const double u = p.c0 * s, t = 1.0 + u;
+    return u * (2.0 + u) / (t * t);
+  } else if constexpr (KID == PPBO_KERNEL_CAMPHOR) {
+    return -expm1(-s);
+  } else {
+    // Matern: 1 - (1 + a + w a^2) e^-a = e^-a (e^a - 1 - a - w a^2), w = 1/3 (5/2) or 0 (3/2), a = c r.  Below a = 1 the
+    // bracket is its series (1/2 - w) a^2 + sum_{k >= 3} a^k / k! (all terms positive; a^21 / 21! < 2e-20); above, the
+    // closed form loses at most three bits
+    static_assert(kid_matern<KID>, "unknown kernel id");
+    constexpr double w = (KID == PPBO_KERNEL_MATERN52) ? 1.0 / 3.0 : 0.0;
+    const double a = p.c0 * sqrt(s);
+    if (a >= 1.0) return 1.0 - fma(a, fma(a, w, 1.0), 1.0) * exp(-a);
+    double term = a * a * 0.5, g = 0.0;
+#pragma unroll
+    for (int k = 3; k <= 20; ++k) { term *= a / (double)k; g += term; }
+    return ((0.5 - w) * a * a + g) * exp(-a);
+  }
+}
+
+// Pass 3 of ppbo_predict_pairs: score_kernel's slab sums (same geometry) for the column d = k(a, X) - k(b, X), then
+//   mu_d = sum of the mean partials,   var_d = c(a, b) + d' Lambda d + |G d|^2,   c(a, b) = 2 sigma_f^2 - 2 k(a, b),
+//   p = Phi(mu_d / sqrt(2 sigma^2 + max(var_d, 0)))
+// c(a, b) comes from the direct differences a - b of the two rows (wavefront w sums the dimensions w, w + SC_WAVES, ...
+// beside its slabs; the sums meet in wavefront order).  A NaN mean (a non-finite coordinate) gives NaN everywhere.
+template <int KID>
+__global__ __launch_bounds__(SC_THREADS) void pair_score_kernel(const double* __restrict__ mu_part, int n_mu,
+                                                                const double* __restrict__ t_part,
+                                                                const double* __restrict__ slab, int n_slab, int M,
+                                                                const double* __restrict__ Xa,
+                                                                const double* __restrict__ Xb, int D, KernParams p,
+                                                                double two_sigma2, int kind, long long idx_base,
+                                                                double* __restrict__ mu_out, double* __restrict__ var_out,
+                                                                double* __restrict__ prob_out,
+                                                                double* __restrict__ score_out, Best* __restrict__ blk_best) {
+  __shared__ double part[4][SC_WAVES][SC_CAND];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int c = blockIdx.x * SC_CAND + lane;
+  double pm = 0.0, pt = 0.0, pq = 0.0, ps = 0.0;
+  if (c < M) {
+    for (int s = wave; s < n_mu; s += SC_WAVES) pm += mu_part[(size_t)s * M + c];
+    if (slab) {
+      for (int s = wave; s < n_mu; s += SC_WAVES) pt += t_part[(size_t)s * M + c];
+      for (int s = wave; s < n_slab; s += SC_WAVES) pq += slab[(size_t)s * M + c];
+      for (int d = wave; d < D; d += SC_WAVES) ps += kern_term<KID>(Xa[(size_t)c * D + d] - Xb[(size_t)c * D + d], d, p);
+    }
+  }
+  part[0][wave][lane] = pm;
+  part[1][wave][lane] = pt;
+  part[2][wave][lane] = pq;
+  part[3][wave][lane] = ps;
+  __syncthreads();
+  if (wave != 0) return;                 // the rest is one wavefront's work
+  Best b{0.0, -1};
+  if (c < M) {
+    double mu = 0.0, t = 0.0, q = 0.0, s = 0.0;
+#pragma unroll
+    for (int w = 0; w < SC_WAVES; ++w) { mu += part[0][w][lane]; t += part[1][w][lane]; q += part[2][w][lane]; s += part[3][w][lane]; }
+    double var = NAN, pr = NAN, sc = mu;   // mean only (no slab): nothing but mu is formed
+    if (slab) {
+      var = 2.0 * p.sf2 * kern_one_minus<KID>(s, p) + t + q;
+      const double den = sqrt(two_sigma2 + fmax(var, 0.0));
+      // den = 0 (no noise, no variance): the sign of mu_d decides, a tie is 1/2
+      pr = norm_cdf(den > 0.0 ? mu / den : (mu > 0.0 ? INFINITY : (mu < 0.0 ? -INFINITY : 0.0)));
+      if (mu != mu) { var = mu; pr = mu; }
+      if (kind == PPBO_PAIR_VARIANCE) sc = var;
+      else if (kind == PPBO_PAIR_PROB) sc = pr;
+    }
+    if (mu_out) mu_out[c] = mu;
+    if (var_out) var_out[c] = var;
+    if (prob_out) prob_out[c] = pr;
+    if (score_out) score_out[c] = sc;
+    if (sc == sc) { b.val = sc; b.idx = idx_base + c; }
+  }
+  if (!blk_best) return;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    Best other;
+    other.val = __shfl_xor(b.val, o, 64);
+    other.idx = __shfl_xor(b.idx, o, 64);
+    b = best_merge(b, other);
+  }
+  if (lane == 0) blk_best[blockIdx.x] = b;
+}
+
 // per-block records of one launch -> *out; with `record` also the 16-byte (value, GLOBAL index as a double: exact
 // below 2^53; index + record_offset; (NaN, -1) when nothing scored) record that the sharded search all-gathers, and
 // with `publish` the flag publish[0] raised to `epoch` AFTER the record with system-scope release semantics (the

@@ -10,6 +10,7 @@ import torch
 
 from . import _lib
 from ._lib import KERNEL_IDS, SCORE_MEAN, SCORE_POINTWISE_EI, SCORE_VARIANCE, PPBO_ERR_NOT_PD  # noqa: F401
+from ._lib import PAIR_MEAN, PAIR_VARIANCE, PAIR_PROB  # noqa: F401
 
 # Posterior.form: which variance operator G holds (include/ppbo_hip.h, PPBO_FORM_*)
 FORM_NODE = 0   # G = R Lambda, block lower triangular [N, N]
@@ -649,6 +650,42 @@ class Engine:
                                    self._stream())
         self._check(rc, "ppbo_predict")
         return dict(mu=mu, var=var, score=sc, best_val=bv.value, best_idx=bi.value)
+
+    @staticmethod
+    def _pair_shapes(post: Posterior, Xa, Xb):
+        """The refusals of predict_pairs that shapes alone decide (before anything reaches the device): returns M."""
+        sa, sb = tuple(np.shape(Xa)), tuple(np.shape(Xb))
+        D = 6 if post.camphor is not None else post.X.shape[1]
+        if len(sa) != 2 or sa != sb:
+            raise ValueError(f"predict_pairs: the two sides have shapes {sa} and {sb}; two equal [M, D] sets are required")
+        if sa[1] != D:
+            raise ValueError(f"predict_pairs: points of width {sa[1]} for a model of {D} dimensions")
+        if sa[0] < 1:
+            raise ValueError("predict_pairs: no pairs")
+        return sa[0]
+
+    def predict_pairs(self, post: Posterior, Xa, Xb, score=PAIR_PROB, want_mu=True, want_var=True, want_prob=True,
+                      want_score=False, want_best=True):
+        """Duels (ppbo_predict_pairs): for the M pairs (Xa[i], Xb[i]) in the caller's coordinates the posterior mean and
+        variance of f(a) - f(b) and p = P(a > b), as device tensors mu / var / prob / score (None where not asked for),
+        with best_val / best_idx = the largest score (the quantity `score` names) and its first row.  PAIR_MEAN without
+        var and prob needs no variance operator."""
+        M = self._pair_shapes(post, Xa, Xb)
+        if score not in (PAIR_MEAN, PAIR_VARIANCE, PAIR_PROB):
+            raise ValueError(f"predict_pairs: unknown score kind {score}")
+        Xa, Xb = self._points(post, Xa), self._points(post, Xb)
+        with_var = want_var or want_prob or score != PAIR_MEAN
+        md = self._model(post, with_var)
+        mu = self.empty(M) if want_mu else None
+        var = self.empty(M) if want_var else None
+        pr = self.empty(M) if want_prob else None
+        sc = self.empty(M) if want_score else None
+        bv, bi = C.c_double(0.0), C.c_int64(-1)
+        rc = self.lib.ppbo_predict_pairs(self.ctx, C.byref(md), _ptr(Xa), _ptr(Xb), M, int(score), _ptr(mu), _ptr(var),
+                                         _ptr(pr), _ptr(sc), C.byref(bv) if want_best else None,
+                                         C.byref(bi) if want_best else None, self._stream())
+        self._check(rc, "ppbo_predict_pairs")
+        return dict(mu=mu, var=var, prob=pr, score=sc, best_val=bv.value, best_idx=bi.value)
 
     def predict_cov(self, post: Posterior, Xc, shrink=SHRINKAGE):
         Xc = self._points(post, Xc)

@@ -866,6 +866,16 @@ class GPModel:
         mu, cov = self.eng.predict_cov(self._post, np.atleast_2d(X_pred), self.COVARIANCE_SHRINKAGE)
         return mu.cpu().numpy(), cov.cpu().numpy()
 
+    def preference_pred(self, Xa, Xb):
+        """(mu_d, var_d, p) as NumPy arrays for the duels (Xa[i], Xb[i]): the posterior mean and variance of
+        f(a) - f(b) and p = P(a > b) = Phi(mu_d / sqrt(2 sigma^2 + var_d)) (ppbo_predict_pairs; no reference
+        counterpart).  Host or device input; one pair may be given as two 1-D vectors."""
+        if self._post is None or self._post.G is None:
+            raise RuntimeError("posterior covariance unavailable (skipped during initialisation, gp_model.py:106-107)")
+        Xa, Xb = (x if x.dim() == 2 else x.reshape(1, -1) for x in (self.eng.dev(Xa), self.eng.dev(Xb)))
+        out = self.eng.predict_pairs(self._post, Xa, Xb, want_best=False)
+        return out["mu"].cpu().numpy(), out["var"].cpu().numpy(), out["prob"].cpu().numpy()
+
     def mu_pred(self, X_pred):
         x = np.asarray(X_pred, dtype=float).reshape(1, self.D)
         out = self.eng.predict(self._mean_post(), x, score=SCORE_MEAN, want_var=False, want_best=False)

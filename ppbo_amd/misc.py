@@ -39,6 +39,20 @@ def std_normal_pdf(x):
     return np.exp(-0.5 * np.square(x)) / np.sqrt(2.0 * np.pi)
 
 
+def preference_probability(mu_d, var_d, sigma):
+    """P(a > b) = Phi(mu_d / sqrt(2 sigma^2 + max(var_d, 0))) for the posterior mean and variance of f(a) - f(b)
+    (GPModel.preference_pred, ppbo_predict_pairs): the probit of the likelihood (src/gp_model.py:176-204) with the
+    posterior variance of the difference beside the 2 sigma^2 of two noisy utilities.  A negative variance (rounding
+    at a tie) counts as 0; with no noise and no variance the sign of mu_d decides and a tie is 1/2.  NumPy in and out."""
+    from scipy.special import ndtr
+    mu = np.asarray(mu_d, dtype=float)
+    den = np.sqrt(2.0 * float(sigma) ** 2 + np.maximum(np.asarray(var_d, dtype=float), 0.0))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        z = np.where(den > 0.0, mu / den, np.where(mu > 0.0, np.inf, np.where(mu < 0.0, -np.inf, 0.0)))
+    z = np.where(np.isnan(mu) | np.isnan(den), np.nan, z)
+    return ndtr(z)
+
+
 def regularize_covariance(X, reg_level=1e-4, pos_diag=True, jitter=1e-7):
     """src/misc.py:71-88 on the device (ppbo_regularize_covariance): negative diagonal -> jitter when pos_diag,
     shrink toward tr(X)/n I; the SVD round trip is the identity and is not executed."""
