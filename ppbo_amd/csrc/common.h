@@ -26,7 +26,7 @@ struct ppbo_ctx {
   int device = 0;
   std::string err;
   // named workspace slots
-  enum { WS_KSTAR = 0, WS_PART, WS_SCRATCH, WS_LINALG, WS_LINALG2, WS_VEC, WS_SMALL, WS_POTRF, WS_APPEND, WS_DIST, WS_LBFGS, WS_SEARCH, WS_SEARCH_SMALL, WS_LBFGS_U, WS_TRANSPOSE, WS_GPAD, WS_SEARCH_ROWS, WS_SCALE, WS_SCALE_PTS, WS_SCALE_SEARCH, WS_EVGRAD, WS_EVGRAD_VEC, WS_CAMPHOR, WS_CAMPHOR_ROWS, WS_COUNT };
+  enum { WS_KSTAR = 0, WS_PART, WS_SCRATCH, WS_LINALG, WS_LINALG2, WS_VEC, WS_SMALL, WS_POTRF, WS_APPEND, WS_DIST, WS_LBFGS, WS_SEARCH, WS_SEARCH_SMALL, WS_LBFGS_U, WS_TRANSPOSE, WS_GPAD, WS_SEARCH_ROWS, WS_SCALE, WS_SCALE_PTS, WS_SCALE_SEARCH, WS_EVGRAD, WS_EVGRAD_VEC, WS_CAMPHOR, WS_CAMPHOR_ROWS, WS_KSTAR_GEO, WS_COUNT };
   void* ws[WS_COUNT] = {};
   size_t ws_bytes[WS_COUNT] = {};
   void* pinned = nullptr;  // small pinned host staging buffer
@@ -49,6 +49,9 @@ struct ppbo_ctx {
   // PPBO_FUSED: 1 (default) = models of up to 1024 rows are scored by the one-launch kernel of fused.hip, 0 = always the
   // three-launch form (kstar -> quadform -> score)
   int fused_score = 1;
+  // PPBO_KSTAR_STAR: 1 (default) = kstar_kernel forms the rows of a collinear star from two inner products per star
+  // (star_geom_kernel's table), 0 = always one inner product per row
+  int kstar_star = 1;
   int gemm_big16 = 1;     // PPBO_GEMM_BIG16: large GEMMs on 16 wavefronts of 32 x 32 (default since round 6) instead of 8 of 32 x 64
   int n_cu = 0;           // compute units of the device (hipDeviceProp_t::multiProcessorCount)
   int fused_dbg = 0;      // PPBO_FUSED_DBG: measurement switches of fused.hip (results are wrong when set)
@@ -257,6 +260,12 @@ typedef double double2_t __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ void store_through2(double* p, double x, double y) {
   const double2_t v = {x, y};
   asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
+}
+
+// *p for a wave-uniform p into memory that no launch in flight writes (model arrays, a table the previous launch left):
+// through the constant address space, so the value arrives by a scalar load and occupies no vector register
+__device__ __forceinline__ double uniform_load(const double* p) {
+  return *reinterpret_cast<const __attribute__((address_space(4))) double*>(reinterpret_cast<uintptr_t>(p));
 }
 
 // the value lane ^ 1 holds (DPP quad_perm [1,0,3,2]): two 32-bit moves, no LDS

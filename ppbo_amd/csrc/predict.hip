@@ -7,10 +7,17 @@
 //   mu(x)  = k*' alpha
 //   var(x) = sigma_f^2 - k*' A k*,  A = Sigma^-1 - Sigma^-1 P Sigma^-1  (gp_model.py:449)
 //          = sigma_f^2 + k*' Lambda k* + |G k*|^2                        (Woodbury, same operator)
-// Pass 1 (kstar_kernel, VALU): one lane = two candidates held in registers, X rows staged in LDS
-//   and read as broadcasts (SE / RQ: the reference's expansion with the candidate pre-scaled by -2, one FMA
-//   per dimension; camphor: differences); writes K*[N, Mc] (j-major) once and reduces mu and k*'Lambda k*
-//   in registers.
+// Pass 1 (star_geom_kernel, then kstar_kernel, VALU): one lane = two candidates held in registers.  SE / RQ / Matern in
+//   fp64: the m + 1 rows of a star lie on one line x_obs + s_j xi, so |c - x_j|^2 = r0^2 - 2 s_j beta + s_j^2 |xi|^2 with
+//   r0^2 = |c - x_obs|^2 and beta = xi.(c - x_obs): two inner products of depth D per (candidate, star), from x_obs and xi
+//   staged in LDS, then two FMAs, the clip and the kernel function per row; s_j, s_j^2 |xi|^2, alpha and Lambda of the
+//   row arrive by scalar loads.  star_geom_kernel forms xi, s_j and a collinearity flag per star on every call (N D
+//   doubles read; nothing cached); a star that is not collinear to 2^-50, the fp32 evaluation and camphor take one inner
+//   product per row from X rows staged in LDS and read as broadcasts (SE / RQ / Matern: the reference's expansion with the
+//   candidate pre-scaled by -2, one FMA per dimension; camphor: its feature form).  Writes K*[N, Mc] (j-major) once and
+//   reduces mu and k*'Lambda k* in registers.  C3 (N = 2048, D = 20, 65536 candidates): 0.336 -> 0.259 ms + 0.011 ms for
+//   the geometry, 122 M -> 80 M vector and 15.8 M -> 0.7 M LDS instructions per launch
+//   (profiles/r15_kstar_star_form.txt).  PPBO_KSTAR_STAR=0: always one inner product per row.
 // Pass 2 (quadform_kernel, fp64 MFMA): Y = G K* on 128x128 tiles (16 wavefronts of 32x32), K range cut
 //   at the block-triangular edge per wavefront, epilogue = column sums of Y^2 into per-row-tile slabs.
 //   Workgroups are ordered candidate-tile-fastest in chunks of 128 tiles (PPBO_QF_ORDER, default 514):
@@ -67,14 +74,73 @@ __device__ __forceinline__ float kern_finish32(float s, float sf2, float c0) {
   }
 }
 
+// The star-geometry table of a model, [2 N + n_q + n_q D] doubles: s[N], g[N], collinear[n_q] (1.0 / 0.0), xi[n_q][D].
+// The rows of star q are its observation x_obs and m points that the feedback places on ONE line through it
+// (feedback_processing.py:110-130), x_j = x_obs + s_j xi, so for a candidate c
+//   |c - x_j|^2 = |c - x_obs|^2 - 2 s_j xi.(c - x_obs) + s_j^2 |xi|^2 = r0^2 - 2 s_j beta + g_j:
+// two inner products per (candidate, star) in place of one per (candidate, row).  xi = the star's difference x_j - x_obs
+// of largest norm (the lowest such row), s_j = (x_j - x_obs).xi / |xi|^2, g_j = s_j^2 |xi|^2.  collinear is a CONDITION:
+//   max_{j, d} |x_jd - x_obs,d - s_j xi_d| <= 2^-50 max(|x|_inf of the star, |xi|_inf)
+// (rows built as x_obs + s xi in fp64 sit at 2^-53); a star that misses it, or holds a non-finite coordinate, keeps
+// kstar_kernel's inner product per row.  xi = 0 (every row equals x_obs): collinear, every s_j = 0.
+constexpr int SG_STARS = 4;   // stars per workgroup, one wavefront each (no LDS, no barrier)
+inline size_t star_geo_doubles(int N, int n_q, int D) { return (size_t)2 * N + n_q + (size_t)n_q * D; }
+__global__ __launch_bounds__(64 * SG_STARS) void star_geom_kernel(const double* __restrict__ X, int N, int D, int mblk,
+                                                                  int n_q, double* __restrict__ geo) {
+  const int lane = threadIdx.x & 63, q = blockIdx.x * SG_STARS + (threadIdx.x >> 6);
+  if (q >= n_q) return;       // (a whole wavefront)
+  const double* __restrict__ xo = X + (size_t)q * mblk * D;
+  double best = -1.0;
+  int bj = 0;
+  for (int r = lane; r < mblk; r += 64) {
+    double n2 = 0.0;
+    for (int d = 0; d < D; ++d) { const double v = xo[(size_t)r * D + d] - xo[d]; n2 = fma(v, v, n2); }
+    if (n2 > best) { best = n2; bj = r; }            // (a NaN norm is never taken: the row's residual is NaN below)
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    const double ob = __shfl_xor(best, o, 64);
+    const int oj = __shfl_xor(bj, o, 64);
+    if (ob > best || (ob == best && oj < bj)) { best = ob; bj = oj; }
+  }
+  const double xi2 = fmax(best, 0.0);
+  const double* __restrict__ xb = xo + (size_t)bj * D;
+  double resid = 0.0, big = 0.0;
+  bool bad = false;
+  for (int r = lane; r < mblk; r += 64) {
+    const double* __restrict__ xr = xo + (size_t)r * D;
+    double dot = 0.0;
+    for (int d = 0; d < D; ++d) dot = fma(xr[d] - xo[d], xb[d] - xo[d], dot);
+    const double sj = xi2 > 0.0 ? dot / xi2 : 0.0;
+    for (int d = 0; d < D; ++d) {
+      const double z = xb[d] - xo[d];
+      const double e = fabs((xr[d] - xo[d]) - sj * z);
+      bad |= !(e == e);                              // (fmax drops a NaN)
+      resid = fmax(resid, e);
+      big = fmax(big, fmax(fabs(xr[d]), fabs(z)));
+    }
+    geo[(size_t)q * mblk + r] = sj;
+    geo[(size_t)N + (size_t)q * mblk + r] = sj * sj * xi2;
+  }
+  resid = wave_max(resid);
+  big = wave_max(big);
+  bad = __ballot(bad) != 0;
+  double* __restrict__ xi = geo + (size_t)2 * N + n_q + (size_t)q * D;
+  for (int d = lane; d < D; d += 64) xi[d] = xb[d] - xo[d];
+  if (lane == 0) geo[(size_t)2 * N + q] = (!bad && resid <= 0x1.0p-50 * big) ? 1.0 : 0.0;
+}
+
+// (the fp64 radial buckets up to DP = 20 are held to 128 VGPRs = 4 wavefronts per SIMD, the occupancy the flagship shape
+// D = 20 had before the star path added r0^2 and beta to the live set; SE fits there without scratch.  RQ and the Matern
+// kernels would spill two registers at DP = 20 and are left unbound in that bucket: three wavefronts, no scratch)
 template <int KID, int DP, bool F32 = false>
-__global__ __launch_bounds__(KS_THREADS) void kstar_kernel(
+__global__ __launch_bounds__(KS_THREADS, (!F32 && KID != PPBO_KERNEL_CAMPHOR && (DP < 20 || (DP == 20 && KID == PPBO_KERNEL_SE))) ? 4 : 1) void kstar_kernel(
     const double* __restrict__ X, int N, int D, KernParams p, const double* __restrict__ alpha,
     const double* __restrict__ lam_diag, const double* __restrict__ lam_off, int mblk,
     const double* __restrict__ Xc, int M, double* __restrict__ Kt, int ldk, double* __restrict__ mu_part,
-    double* __restrict__ t_part, int q_per_split, int n_q, int edge_k0) {
+    double* __restrict__ t_part, int q_per_split, int n_q, int edge_k0, const double* __restrict__ geo) {
   __shared__ __attribute__((aligned(16))) double xs[KS_RJ * DP];
   __shared__ double s_alpha[KS_RJ], s_ld[KS_RJ], s_lo[KS_RJ], s_nx[KS_RJ];
+  __shared__ int s_col[KS_RJ];
   const int c0 = (blockIdx.x * KS_THREADS + threadIdx.x) * KS_CPT;
   // The camphor kernel in FEATURE form (fp64 path; DP = 12): sin^2(pi (a - b)) = (1 - cos 2pi a cos 2pi b - sin 2pi a sin 2pi b) / 2
   // turns kernels.py:36-53's exponent  c0 sum_k sin^2(pi |a_k - b_k|) + c1 (a_2 - b_2)^2  into
@@ -90,6 +156,16 @@ __global__ __launch_bounds__(KS_THREADS) void kstar_kernel(
   // <= 3e-13 / 1e-13 sigma_f^2 on the fixtures against direct differences).  The camphor kernel needs the
   // differences themselves.
   constexpr bool EXPAND = (KID != PPBO_KERNEL_CAMPHOR) && !F32;
+  // The STAR path (the expansion-form kernels, geo = star_geom_kernel's table): a collinear star's rows come from
+  //   r^2 = max(r0^2 - 2 s_j beta + g_j, 0),  r0^2 = |c - x_obs|^2 and beta = xi.(c - x_obs) formed at the star's first row
+  // from direct differences (x_obs and xi staged in LDS, xi in the place of the star's second row): two depth-D inner
+  // products per star, then two FMAs and the clip per row -- no LDS row, no |x_j|^2.  The rows are then staged in steps
+  // of WHOLE stars (stars of more than KS_RJ rows: pieces of one star), so that a star's first two rows always sit in
+  // one step.  A star whose flag is clear takes the inner product per row, bit for bit what geo == nullptr computes
+  // (a row's value does not depend on how the rows are cut into steps).  The branch is uniform per workgroup.
+  const bool use_geo = EXPAND && geo != nullptr;
+  const double* __restrict__ geo_col = use_geo ? geo + (size_t)2 * N : nullptr;
+  const double* __restrict__ geo_xi = use_geo ? geo_col + n_q : nullptr;
   double xc[KS_CPT][DP], nc[KS_CPT], mu[KS_CPT], tl[KS_CPT], ko[KS_CPT];
   float xcf[KS_CPT][DP];
   const float c0f = (float)p.c0, c1f = (float)p.c1, sf2f = (float)p.sf2;
@@ -119,6 +195,13 @@ __global__ __launch_bounds__(KS_THREADS) void kstar_kernel(
       xc[q][d] = v;
     }
   }
+  // |c|^2 of the lane's candidates, in a slot of the lane's own: read by the plain rows and at the end, so not held in
+  // registers across the rows of the collinear stars (the D = 20 bucket has none to spare at four wavefronts per SIMD)
+  __shared__ double s_nc[EXPAND ? KS_CPT * KS_THREADS : 1];
+  if (EXPAND) {
+#pragma unroll
+    for (int q = 0; q < KS_CPT; ++q) s_nc[q * KS_THREADS + threadIdx.x] = nc[q];
+  }
   const int j_beg = blockIdx.y * q_per_split * mblk;
   int j_end = j_beg + q_per_split * mblk;
   if (j_end > N) j_end = N;
@@ -126,8 +209,144 @@ __global__ __launch_bounds__(KS_THREADS) void kstar_kernel(
   const bool has_lam = (lam_diag != nullptr);
   int rb = 0;  // row index inside the current star block (splits start on a block edge)
   int qs = j_beg / mblk;  // ... and that block's star
-  for (int row0 = j_beg; row0 < j_end; row0 += KS_RJ) {
+  // staged row r of the step at row0, from its r^2 (sv; F32: from kv itself) on: the kernel value, the stored entry, the sums
+  // a, ld, lo: alpha, lam_diag and lam_off of the row
+  auto finish_row = [&](int row0, int r, double (&sv)[KS_CPT], double (&kv)[KS_CPT], double a, double ld, double lo) __attribute__((always_inline)) {
+    if (!F32) {
+#pragma unroll
+      for (int q = 0; q < KS_CPT; ++q) kv[q] = kern_finish<KID>(sv[q], p);
+    }
+    if (Kt) {
+      // node form: row j holds k*_j.  Edge form (edge_k0 >= 0): row n_q + q m + t holds the edge value
+      // lam_off[j] (k*_j - k*_obs) of pseudo row j = q (m + 1) + 1 + t; row q (an observation coordinate, a zero column
+      // of H) holds zeros where the contraction reads it, i.e. from edge_k0 on
+      int drow = row0 + r;
+      bool wr = true;
+      double ev[KS_CPT];
+      if (edge_k0 >= 0) {
+        if (rb == 0) {
+          drow = qs;
+          wr = qs >= edge_k0;
+#pragma unroll
+          for (int q = 0; q < KS_CPT; ++q) ev[q] = 0.0;
+        } else {
+          drow = n_q + qs * (mblk - 1) + rb - 1;
+#pragma unroll
+          for (int q = 0; q < KS_CPT; ++q) ev[q] = lo * (kv[q] - ko[q]);
+        }
+      } else {
+#pragma unroll
+        for (int q = 0; q < KS_CPT; ++q) ev[q] = kv[q];
+      }
+      double* dst = Kt + (size_t)drow * ldk + c0;
+      if (!wr) {
+      } else if (vec) {      // 1 GB streamed out once, read back by the next kernel
+#pragma unroll
+        for (int q = 0; q < KS_CPT; q += 2) store_through2(dst + q, ev[q], ev[q + 1]);
+      } else {
+#pragma unroll
+        for (int q = 0; q < KS_CPT; ++q)
+          if (c0 + q < M) dst[q] = ev[q];
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < KS_CPT; ++q) mu[q] += a * kv[q];
+    if (has_lam) {
+      if (rb == 0) {
+#pragma unroll
+        for (int q = 0; q < KS_CPT; ++q) { ko[q] = kv[q]; tl[q] += ld * kv[q] * kv[q]; }
+      } else {
+        const double lo2 = 2.0 * lo;
+#pragma unroll
+        for (int q = 0; q < KS_CPT; ++q) tl[q] += kv[q] * (ld * kv[q] + lo2 * ko[q]);
+      }
+    }
+    if (++rb == mblk) { rb = 0; ++qs; }
+  };
+  // ... with r^2 from the staged row itself: one inner product (or sum of terms) of depth D per candidate
+  auto plain_row = [&](int row0, int r) __attribute__((always_inline)) {
+    const double* __restrict__ xr = xs + r * DP;
+    double sv[KS_CPT];
+    double kv[KS_CPT];
+#pragma unroll
+    for (int q = 0; q < KS_CPT; ++q) sv[q] = 0.0;
+    if (F32) {
+      float sf[KS_CPT];
+#pragma unroll
+      for (int q = 0; q < KS_CPT; ++q) sf[q] = 0.0f;
+#pragma unroll
+      for (int d = 0; d < DP; ++d) {
+        const float x = (float)xr[d];
+#pragma unroll
+        for (int q = 0; q < KS_CPT; ++q) sf[q] += kern_term32<KID>(x - xcf[q][d], d, c0f, c1f);
+      }
+#pragma unroll
+      for (int q = 0; q < KS_CPT; ++q) kv[q] = (double)kern_finish32<KID>(sf[q], sf2f, c0f);
+    } else if (EXPAND) {
+#pragma unroll
+      for (int d = 0; d < DP; ++d) {
+        const double x = xr[d];
+#pragma unroll
+        for (int q = 0; q < KS_CPT; ++q) sv[q] = fma(x, xc[q][d], sv[q]);
+      }
+      const double nx = s_nx[r];
+#pragma unroll
+      for (int q = 0; q < KS_CPT; ++q) sv[q] = fmax(sv[q] + (nx + s_nc[q * KS_THREADS + threadIdx.x]), 0.0);
+    } else if (CAMF) {
+#pragma unroll
+      for (int d = 0; d < 10; ++d) {
+        const double x = xr[d];
+#pragma unroll
+        for (int q = 0; q < KS_CPT; ++q) sv[q] = fma(x, xc[q][d], sv[q]);
+      }
+      const double x2 = xr[10], base = 2.5 * p.c0;
+#pragma unroll
+      for (int q = 0; q < KS_CPT; ++q) {
+        const double dd = x2 - xc[q][10];
+        sv[q] = fma(p.c1 * dd, dd, sv[q] + base);
+      }
+    } else {
+#pragma unroll
+      for (int d = 0; d < DP; ++d) {
+        const double x = xr[d];
+#pragma unroll
+        for (int q = 0; q < KS_CPT; ++q) sv[q] += kern_term<KID>(x - xc[q][d], d, p);
+      }
+    }
+    finish_row(row0, r, sv, kv, s_alpha[r], s_ld[r], s_lo[r]);
+  };
+  const bool pieces = mblk > KS_RJ;
+  int len = 0;
+  for (int row0 = j_beg; row0 < j_end; row0 += len) {
+    len = (j_end - row0 < KS_RJ) ? (j_end - row0) : KS_RJ;
+    if (use_geo) {                         // whole stars, or a piece of one (splits end on a star edge)
+      const int whole = pieces ? mblk - rb : (KS_RJ / mblk) * mblk;
+      if (whole < len) len = whole;
+    }
+    // (with a table the lane's index is opaque per step: a staged element's row, star and addresses are formed here, not
+    // held in registers across the row loops)
+    int tid = threadIdx.x;
+    if (use_geo) asm volatile("" : "+v"(tid));
     __syncthreads();
+    if (use_geo) {
+      // a collinear star leaves x_obs and xi in the first two rows of its place (a piece: of the step, whichever rows
+      // of the star it holds) and reads no other row; any other star stages its rows
+      const int nst = len < 2 ? 2 : len;
+      for (int e = tid; e < nst * DP; e += KS_THREADS) {
+        const int r = e / DP, d = e - r * DP;
+        const int sq = pieces ? 0 : r / mblk, pos = r - sq * mblk;
+        const int star = qs + sq;
+        double v = 0.0;
+        if (geo_col[star] != 0.0) {
+          if (pos > 1) continue;
+          if (d < D) v = pos ? geo_xi[(size_t)star * D + d] : X[(size_t)star * mblk * D + d];
+        } else {
+          if (r >= len) continue;
+          if (d < D) v = X[(size_t)(row0 + r) * D + d];
+        }
+        xs[e] = v;
+      }
+    } else
     if (CAMF) {                            // phi of the staged rows: (cos, sin)(2 pi x_k) for k = 0, 1, 3, 4, 5; then x_2
       for (int e = threadIdx.x; e < KS_RJ * 6; e += KS_THREADS) {
         const int r = e / 6, k = e - r * 6;
@@ -149,141 +368,88 @@ __global__ __launch_bounds__(KS_THREADS) void kstar_kernel(
       const int j = row0 + r;
       xs[e] = (j < j_end && d < D) ? X[(size_t)j * D + d] : 0.0;
     }
-    if (threadIdx.x < KS_RJ) {
-      const int j = row0 + threadIdx.x;
-      const bool ok = j < j_end;
-      s_alpha[threadIdx.x] = ok ? alpha[j] : 0.0;
-      s_ld[threadIdx.x] = (ok && has_lam) ? lam_diag[j] : 0.0;
-      s_lo[threadIdx.x] = (ok && has_lam) ? lam_off[j] : 0.0;
+    if (tid < KS_RJ) {
+      const int j = row0 + tid;
+      const bool ok = j < j_end && (!use_geo || tid < len);
+      bool col = false;
+      if (use_geo) {
+        col = ok && geo_col[qs + (pieces ? 0 : tid / mblk)] != 0.0;
+        s_col[tid] = col;
+      }
+      if (!col) {                          // (the rows of a collinear star take these three by scalar loads)
+        s_alpha[tid] = ok ? alpha[j] : 0.0;
+        s_ld[tid] = (ok && has_lam) ? lam_diag[j] : 0.0;
+        s_lo[tid] = (ok && has_lam) ? lam_off[j] : 0.0;
+      }
       if (EXPAND) {
         double nx = 0.0;
-        if (ok)
+        if (ok && !col)
           for (int d = 0; d < D; ++d) { const double v = X[(size_t)j * D + d]; nx = fma(v, v, nx); }
-        s_nx[threadIdx.x] = nx;
+        s_nx[tid] = nx;
       }
     }
     __syncthreads();
-    const int rmax = (j_end - row0 < KS_RJ) ? (j_end - row0) : KS_RJ;
-    for (int r = 0; r < rmax; ++r) {
-      const double* __restrict__ xr = xs + r * DP;
-      double sv[KS_CPT];
-      double kv[KS_CPT];
-#pragma unroll
-      for (int q = 0; q < KS_CPT; ++q) sv[q] = 0.0;
-      if (F32) {
-        float sf[KS_CPT];
-#pragma unroll
-        for (int q = 0; q < KS_CPT; ++q) sf[q] = 0.0f;
-#pragma unroll
-        for (int d = 0; d < DP; ++d) {
-          const float x = (float)xr[d];
-#pragma unroll
-          for (int q = 0; q < KS_CPT; ++q) sf[q] += kern_term32<KID>(x - xcf[q][d], d, c0f, c1f);
-        }
-#pragma unroll
-        for (int q = 0; q < KS_CPT; ++q) kv[q] = (double)kern_finish32<KID>(sf[q], sf2f, c0f);
-      } else if (EXPAND) {
-#pragma unroll
-        for (int d = 0; d < DP; ++d) {
-          const double x = xr[d];
-#pragma unroll
-          for (int q = 0; q < KS_CPT; ++q) sv[q] = fma(x, xc[q][d], sv[q]);
-        }
-        const double nx = s_nx[r];
-#pragma unroll
-        for (int q = 0; q < KS_CPT; ++q) sv[q] = fmax(sv[q] + (nx + nc[q]), 0.0);
-      } else if (CAMF) {
-#pragma unroll
-        for (int d = 0; d < 10; ++d) {
-          const double x = xr[d];
-#pragma unroll
-          for (int q = 0; q < KS_CPT; ++q) sv[q] = fma(x, xc[q][d], sv[q]);
-        }
-        const double x2 = xr[10], base = 2.5 * p.c0;
-#pragma unroll
-        for (int q = 0; q < KS_CPT; ++q) {
-          const double dd = x2 - xc[q][10];
-          sv[q] = fma(p.c1 * dd, dd, sv[q] + base);
-        }
-      } else {
-#pragma unroll
-        for (int d = 0; d < DP; ++d) {
-          const double x = xr[d];
-#pragma unroll
-          for (int q = 0; q < KS_CPT; ++q) sv[q] += kern_term<KID>(x - xc[q][d], d, p);
-        }
+#pragma unroll 1
+    for (int r = 0; r < len;) {
+      // the staged rows of ONE star (all the staged rows without a table)
+      int r_end = len;
+      if (use_geo && r + mblk - rb < len) r_end = r + mblk - rb;
+      if (!use_geo || __builtin_amdgcn_readfirstlane(s_col[r]) == 0) {
+#pragma unroll 1
+        for (; r < r_end; ++r) plain_row(row0, r);
+        continue;
       }
-      if (!F32) {
+      if constexpr (EXPAND) {
+        // r0^2 = |c - x_obs|^2 and beta = xi.(c - x_obs) from direct differences; xc holds -2 c
+        const double* __restrict__ xo = xs + r * DP;
+        double r0[KS_CPT], be[KS_CPT];
 #pragma unroll
-        for (int q = 0; q < KS_CPT; ++q) kv[q] = kern_finish<KID>(sv[q], p);
-      }
-      if (Kt) {
-        // node form: row j holds k*_j.  Edge form (edge_k0 >= 0): row n_q + q m + t holds the edge value
-        // lam_off[j] (k*_j - k*_obs) of pseudo row j = q (m + 1) + 1 + t; row q (an observation coordinate, a zero column
-        // of H) holds zeros where the contraction reads it, i.e. from edge_k0 on
-        int drow = row0 + r;
-        bool wr = true;
-        double ev[KS_CPT];
-        if (edge_k0 >= 0) {
-          if (rb == 0) {
-            drow = qs;
-            wr = qs >= edge_k0;
+        for (int q = 0; q < KS_CPT; ++q) { r0[q] = 0.0; be[q] = 0.0; }
 #pragma unroll
-            for (int q = 0; q < KS_CPT; ++q) ev[q] = 0.0;
-          } else {
-            drow = n_q + qs * (mblk - 1) + rb - 1;
-            const double lo = s_lo[r];
+        for (int d = 0; d < DP; ++d) {
+          const double o = xo[d], z = xo[DP + d];
 #pragma unroll
-            for (int q = 0; q < KS_CPT; ++q) ev[q] = lo * (kv[q] - ko[q]);
+          for (int q = 0; q < KS_CPT; ++q) {
+            const double df = fma(-0.5, xc[q][d], -o);
+            r0[q] = fma(df, df, r0[q]);
+            be[q] = fma(z, df, be[q]);
           }
-        } else {
-#pragma unroll
-          for (int q = 0; q < KS_CPT; ++q) ev[q] = kv[q];
         }
-        double* dst = Kt + (size_t)drow * ldk + c0;
-        if (!wr) {
-        } else if (vec) {      // 1 GB streamed out once, read back by the next kernel
+#pragma unroll 1
+        for (; r < r_end; ++r) {           // (the observation row: s = g = 0, r^2 = r0^2)
+          // the row's five coefficients by scalar loads: the star path has no vector register to hold them in
+          const int j = row0 + r;
+          const double m2s = -2.0 * uniform_load(geo + j), g = uniform_load(geo + (size_t)N + j);
+          double sv[KS_CPT], kv[KS_CPT];
 #pragma unroll
-          for (int q = 0; q < KS_CPT; q += 2) store_through2(dst + q, ev[q], ev[q + 1]);
-        } else {
-#pragma unroll
-          for (int q = 0; q < KS_CPT; ++q)
-            if (c0 + q < M) dst[q] = ev[q];
+          for (int q = 0; q < KS_CPT; ++q) sv[q] = fmax(fma(m2s, be[q], r0[q] + g), 0.0);
+          finish_row(row0, r, sv, kv, uniform_load(alpha + j), has_lam ? uniform_load(lam_diag + j) : 0.0,
+                     has_lam ? uniform_load(lam_off + j) : 0.0);
         }
       }
-      const double a = s_alpha[r];
-#pragma unroll
-      for (int q = 0; q < KS_CPT; ++q) mu[q] += a * kv[q];
-      if (has_lam) {
-        const double ld = s_ld[r];
-        if (rb == 0) {
-#pragma unroll
-          for (int q = 0; q < KS_CPT; ++q) { ko[q] = kv[q]; tl[q] += ld * kv[q] * kv[q]; }
-        } else {
-          const double lo2 = 2.0 * s_lo[r];
-#pragma unroll
-          for (int q = 0; q < KS_CPT; ++q) tl[q] += kv[q] * (ld * kv[q] + lo2 * ko[q]);
-        }
-      }
-      if (++rb == mblk) { rb = 0; ++qs; }
     }
   }
+  // (the lane's first candidate once more, from an opaque lane index: nothing of the epilogue's addresses is carried
+  // through the row loops)
+  int tide = threadIdx.x;
+  asm volatile("" : "+v"(tide));
+  const int ce = (blockIdx.x * KS_THREADS + tide) * KS_CPT;
 #pragma unroll
   for (int q = 0; q < KS_CPT; ++q) {
-    if (c0 + q < M) {
+    if (ce + q < M) {
       // A candidate with a NaN or infinite coordinate leaves as NaN partial sums (score_kernel then gives the row NaN
       // results): the pair loop clips r^2 with fmax, which drops a NaN, so its sums are those of a row on top of every
       // design row or infinitely far from all of them.  |c|^2 says so where it is formed; the other forms look at the
       // coordinates once more here, after the pair loop, where the registers are free
       bool finite;
-      if (EXPAND) finite = nc[q] < INFINITY;
+      if (EXPAND) finite = s_nc[q * KS_THREADS + threadIdx.x] < INFINITY;
       else {
         double chk = 0.0;
-        for (int d = 0; d < D; ++d) chk = fma(Xc[(size_t)(c0 + q) * D + d], 0.0, chk);
+        for (int d = 0; d < D; ++d) chk = fma(Xc[(size_t)(ce + q) * D + d], 0.0, chk);
         finite = chk == 0.0;
       }
-      mu_part[(size_t)blockIdx.y * M + c0 + q] = finite ? mu[q] : NAN;
-      if (t_part) t_part[(size_t)blockIdx.y * M + c0 + q] = finite ? tl[q] : NAN;
+      mu_part[(size_t)blockIdx.y * M + ce + q] = finite ? mu[q] : NAN;
+      if (t_part) t_part[(size_t)blockIdx.y * M + ce + q] = finite ? tl[q] : NAN;
     }
   }
 }
@@ -1047,7 +1213,8 @@ __global__ __launch_bounds__(256) void omega_draws_kernel(const double* __restri
 
 template <int KID>
 int launch_kstar(const ppbo_model* m, const KernParams& p, const double* d_Xc, int M, double* Kt, int ldk,
-                 double* mu_part, double* t_part, int q_per_split, int n_split, bool with_lam, int edge_k0, hipStream_t s) {
+                 double* mu_part, double* t_part, int q_per_split, int n_split, bool with_lam, int edge_k0,
+                 const double* geo, hipStream_t s) {
   dim3 grid((M + KS_THREADS * KS_CPT - 1) / (KS_THREADS * KS_CPT), n_split);
   const int mblk = m->m + 1, n_q = (m->N + mblk - 1) / mblk;
   const double* ld = with_lam ? m->d_lam_diag : nullptr;
@@ -1055,7 +1222,7 @@ int launch_kstar(const ppbo_model* m, const KernParams& p, const double* d_Xc, i
 #define KS_LAUNCH32(DP)                                                                                              \
   kstar_kernel<KID, DP, true><<<grid, KS_THREADS, 0, s>>>(m->d_X, m->N, m->D, p, m->d_alpha, ld, lo, mblk, d_Xc, M, \
                                                           Kt, ldk, mu_part, with_lam ? t_part : nullptr,            \
-                                                          q_per_split, n_q, edge_k0)
+                                                          q_per_split, n_q, edge_k0, nullptr)
   if (m->kstar_fp32) {       // the fp32-tolerance report: the BASELINE shapes get their own bucket, the rest a generic one
     if (KID == PPBO_KERNEL_CAMPHOR || m->D <= 6) KS_LAUNCH32(6);
     else if constexpr (KID != PPBO_KERNEL_CAMPHOR) {     // (camphor-copper: D = 6)
@@ -1068,7 +1235,7 @@ int launch_kstar(const ppbo_model* m, const KernParams& p, const double* d_Xc, i
 #define KS_LAUNCH(DP)                                                                                          \
   kstar_kernel<KID, DP><<<grid, KS_THREADS, 0, s>>>(m->d_X, m->N, m->D, p, m->d_alpha, ld, lo, mblk, d_Xc, M, \
                                                     Kt, ldk, mu_part, with_lam ? t_part : nullptr,            \
-                                                    q_per_split, n_q, edge_k0)
+                                                    q_per_split, n_q, edge_k0, geo)
   if constexpr (KID == PPBO_KERNEL_CAMPHOR) KS_LAUNCH(12);      // the feature form: 12 staged values per row
   else if (m->D <= 4) KS_LAUNCH(4);
   else if (m->D <= 6) KS_LAUNCH(6);
@@ -1086,14 +1253,31 @@ int launch_kstar(const ppbo_model* m, const KernParams& p, const double* d_Xc, i
 }
 
 // edge_k0 >= 0: K* in the edge layout of an edge-form model (kstar_kernel), which needs with_lam
+// geo: the model's star-geometry table (star_geometry), or NULL = one inner product per row
 int dispatch_kstar(const ppbo_model* m, const double* d_Xc, int M, double* Kt, int ldk, double* mu_part,
-                   double* t_part, int q_per_split, int n_split, bool with_lam, hipStream_t s, int edge_k0 = -1) {
+                   double* t_part, int q_per_split, int n_split, bool with_lam, hipStream_t s, int edge_k0 = -1,
+                   const double* geo = nullptr) {
   const KernParams p = make_kern_params(m->kernel_id, m->theta);
   // (no ctx: an unknown id returns -1 and sets no message; check_model rejects any such id first)
   return ppbo_kernel_dispatch(nullptr, m->kernel_id, [&](auto kid) {
     return launch_kstar<decltype(kid)::value>(m, p, d_Xc, M, Kt, ldk, mu_part, t_part, q_per_split, n_split, with_lam,
-                                              edge_k0, s);
+                                              edge_k0, geo, s);
   });
+}
+
+// star_geom_kernel on `s` into the ctx's table for this model: the operand `geo` of the K* launch enqueued behind it.
+// Formed in front of EVERY K* launch, i.e. once per chunk of 65536 candidates (N D doubles read, ~10 microseconds):
+// nothing is cached, so nothing can go stale when a model's rows are updated in place.  NULL (and no launch) where the K* launch has no star path: PPBO_KSTAR_STAR=0, the
+// fp32 evaluation, camphor-copper.  *oom is set when the table could not be allocated
+// (ppbo_workspace has left the message in ctx->err).
+const double* star_geometry(ppbo_ctx* ctx, const ppbo_model* m, hipStream_t s, bool* oom) {
+  *oom = false;
+  if (!ctx->kstar_star || m->kstar_fp32 || m->kernel_id == PPBO_KERNEL_CAMPHOR) return nullptr;
+  const int mblk = m->m + 1, n_q = m->N / mblk;
+  double* geo = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_KSTAR_GEO, star_geo_doubles(m->N, n_q, m->D) * sizeof(double));
+  if (!geo) { *oom = true; return nullptr; }
+  star_geom_kernel<<<(n_q + SG_STARS - 1) / SG_STARS, 64 * SG_STARS, 0, s>>>(m->d_X, m->N, m->D, mblk, n_q, geo);
+  return geo;
 }
 
 // kstar_pair_kernel in launch_kstar's D buckets (fp64 only); n_split rows splits as there, KS_THREADS pairs per workgroup
@@ -1241,7 +1425,10 @@ static int predict_passes(ppbo_ctx* ctx, const ppbo_model* model, const double* 
     double* slab = part + (size_t)2 * n_split_eff * Mc;
     {
       PpboProfScope pf(ctx, ppbo_ctx::PF_KSTAR, s);
-      dispatch_kstar(model, xc, Mc, Kt, ldk, mu_part, t_part, q_per_split, n_split_eff, want_var, s, edge_k0);
+      bool oom = false;
+      const double* geo = star_geometry(ctx, model, s, &oom);
+      if (oom) return (int)hipErrorOutOfMemory;
+      dispatch_kstar(model, xc, Mc, Kt, ldk, mu_part, t_part, q_per_split, n_split_eff, want_var, s, edge_k0, geo);
     }
     PPBO_LAUNCH_CHECK(ctx);
     if (want_var) {
