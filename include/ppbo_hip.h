@@ -373,6 +373,18 @@ PPBO_API int ppbo_mean_grad(ppbo_ctx* ctx, const ppbo_model* model, const double
  * ascent from each -- the WHOLE iteration inside one kernel, one workgroup per start, no host round trip.
  * d_x[K,D] / d_mu[K]: the refined maxima (rows >= *h_found: mu = -inf).  h_found may be NULL (then nothing
  * synchronises).  ppbo_mean_ascent is the last stage alone, from caller-chosen starts (d_iters[K] optional).
+ * The start selection, the same in every search of this library (tests/search_ref.py restates it in NumPy):
+ *   - the survivor capacity is cap = clamp(147456 / (8 + 8 D), 64, 4096), rounded down (survivors and their coordinates
+ *     in one workgroup's LDS); the M scored rows are cut into groups of G = ceil(M / cap) CONSECUTIVE rows, ceil(M / G)
+ *     groups in all (the last one may be short);
+ *   - a group's survivor is its first maximum (strict >: of equal scores the smaller row index wins); NaN never wins,
+ *     and a group whose rows are all NaN or -inf yields no survivor;
+ *   - then at most K greedy picks: each is the first maximum among the live survivors (ties again to the smaller
+ *     index), and after it every live survivor with sum_d (x_d - x*_d)^2 <= sep^2 is struck -- inclusive, so a
+ *     survivor exactly `sep` away goes, and so does the winner itself (sep = 0 strikes the winner and its duplicates);
+ *     the picks stop early when no survivor above -inf is left, so *h_found may be less than K;
+ *   - distances are plain Euclidean in the coordinates of d_cand (the caller's coordinates in the ARD and camphor forms).
+ * iters = 0 returns the picked rows (clipped to the unit box) and the mean there.
  * ppbo_shift_points: d_out = frac(d_in + h_shift[D]) row-wise -- a rotation of a RESIDENT uniform candidate pool,
  * so that repeated searches see fresh candidates without regenerating and uploading M x D numbers. */
 PPBO_API int ppbo_mean_search(ppbo_ctx* ctx, const ppbo_model* model, const double* d_cand, int64_t M, int K, double sep,

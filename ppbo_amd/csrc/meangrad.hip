@@ -81,7 +81,7 @@ __global__ __launch_bounds__(256) void mean_grad_kernel(const double* __restrict
 // Device-resident maximiser of the posterior mean (ppbo_mean_search): what mu_star's differential evolution
 // (gp_model.py:415-437) is replaced by, without a host round trip per iterate.
 //   1. group_max_kernel: the M scored candidates are cut into T <= 4096 groups of consecutive rows (T such that the
-//      survivors and their coordinates fit one workgroup's LDS: 2622 at D = 6, 914 at D = 20); each group's best row
+//      survivors and their coordinates fit one workgroup's LDS: 2633 at D = 6, 877 at D = 20); each group's best row
 //      survives (the candidates are i.i.d. uniform, so this is a thinning, not a loss of coverage; the best candidate
 //      always survives).
 //   2. select_starts_kernel (one workgroup): greedy choice of the K best survivors that are pairwise more than
