@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define PPBO_ABI_VERSION 7
+#define PPBO_ABI_VERSION 8
 #define PPBO_ERR_NOT_PD 1001
 
 /* The library is built with -fvisibility=hidden: the entry points declared here are its ONLY dynamic symbols
@@ -282,6 +282,42 @@ PPBO_API int ppbo_posterior(ppbo_ctx* ctx, const double* d_Sigma_inv, const doub
  * contraction (m = 25, the reference's default) the call works on a zero-framed copy of G in a ctx workspace (from
  * 2048 candidates on; ~3 N^2 x 8 bytes moved per call), and K* is always padded to whole 128-candidate tiles. */
 enum { PPBO_FORM_NODE = 0, PPBO_FORM_EDGE = 1 };   /* the two layouts of a variance operator: "EDGE form" below */
+
+/* ---- the coordinate map of a model (ABI 8; no reference counterpart) -----------------------------------------------------
+ * A model with per-dimension length scales holds rows in coordinates other than the caller's.  Which ones is data of the
+ * model -- ppbo_model.coords -- not a function name and not state of the ctx: rows read with the wrong map, or with none,
+ * give a finite, plausible and wrong maximiser.
+ * PPBO_COORDS_MODEL (0, a zero-initialised struct): the caller's coordinates are the model's; h_coef and d_Xc are not read.
+ * PPBO_COORDS_SCALED, ARD for a radial kernel (SE, RQ, Matern-5/2, Matern-3/2): k(x, x'; l_1..l_D) = k(s (.) x, s (.) x';
+ *   l = 1) with s_d = 1 / l_d, so the model holds its SCALED rows in d_X and theta = [sigma, 1, sigma_f]; h_coef = s[D].
+ *   ppbo_scale_points (no reference counterpart): d_out[i,d] = d_in[i,d] * h_scale[d] for M rows of D (in place allowed).
+ * PPBO_COORDS_CAMPHOR, camphor-copper with l_0..l_5 (x, y, z, alpha, beta, gamma; z is the non-periodic coordinate 2): SE
+ *   with l = 1 on embedded rows e(x) in R^11,
+ *     camphor(x, x'; l, sigma_f) = SE(e(x), e(x'); 1, sigma_f),   |e_d(x) - e_d(x')|^2 = 4 sin^2(pi (x_d - x'_d)) / l_d^2,
+ *   column order (c0, s0, c1, s1, z, c3, s3, c4, s4, c5, s5) with c_d = cos(2 pi x_d) / l_d, s_d = sin(2 pi x_d) / l_d and
+ *   z = x_2 / l_2.  The reference's kernel is l = (l, l, l + 0.05, l, l, l).  The model holds its EMBEDDED rows in d_X
+ *   (D = 11), kernel_id = PPBO_KERNEL_SE and theta = [sigma, 1, sigma_f]; h_coef = l[6] and d_Xc[N,6] = its design rows in
+ *   the caller's coordinates.
+ *   ppbo_camphor_embed: d_out[M,11] = e(d_in[M,6]) for the length scales h_l[6] (one memory-bound pass; an output that
+ *     overlaps the input is rejected, as is M beyond one launch grid, 2^31 - 1 blocks of 256 / 6 rows).
+ *   ppbo_camphor_line_points: the embedded grid d_out[B*G,11] of the B lines x_b + alpha_g xi_b (d_xi, d_x [B,6]; d_alpha
+ *     [G], or [B,G] with alpha_per_line), formed in the caller's coordinates; ppbo_line_acq takes it as d_grid[B,G,11]
+ *     (d_out must not overlap the inputs).
+ * Who reads it: ppbo_mean_grad, ppbo_mean_ascent and ppbo_mean_search_multi read model->coords; ppbo_rff_search,
+ * ppbo_rff_search_multi and ppbo_path_search_multi, which have no model, take a `const ppbo_coords*` (NULL = the identity).
+ * With a map, points, pool rotation, extra points, h_xprev, the [0,1]^D box, sep, tol, the returned points and gradients
+ * are all in the caller's coordinates (D = 6 for CAMPHOR).  ppbo_mean_search refuses a map.  EVERY other entry that takes a
+ * model (ppbo_predict*, ppbo_predict_pairs, ppbo_predict_cov, ppbo_line_acq*, ppbo_search_sharded) ignores coords, as the
+ * fit and evidence entries know none: they take rows in the MODEL's coordinates (scaled or embedded by the caller).
+ * "invalid argument", with nothing launched: a kind outside 0..2; SCALED with PPBO_KERNEL_CAMPHOR; CAMPHOR on a model that
+ * is not SE at D = 11, or without d_Xc; a coefficient array that is NULL or has a non-positive or non-finite entry. */
+enum { PPBO_COORDS_MODEL = 0, PPBO_COORDS_SCALED = 1, PPBO_COORDS_CAMPHOR = 2 };
+typedef struct ppbo_coords {
+  int kind;              /* PPBO_COORDS_* */
+  const double* h_coef;  /* host, read during the call only.  SCALED: s[D] = 1 / l_d.  CAMPHOR: l[6] */
+  const double* d_Xc;    /* CAMPHOR, model entries only: the design rows in the caller's coordinates [N,6] */
+} ppbo_coords;
+
 typedef struct ppbo_model {
   int kernel_id, N, D, m;
   double theta[3];
@@ -306,6 +342,8 @@ typedef struct ppbo_model {
                              * with -- read by the other rule an operator gives a finite, plausible and wrong variance.
                              * d_Gt is not read for the edge form.  Any other value is refused ("invalid argument").
                              * Ignored where no operator is read: d_G == NULL, and the mean-only ppbo_mean_* entries */
+  ppbo_coords coords;       /* (ABI 8) the coordinates d_X is in, relative to the caller's ("the coordinate map of a model"
+                             * above); zero-initialised: the same */
 } ppbo_model;
 
 /* The transpose of G = R Lambda in the layout the one-launch scoring kernel reads: d_Gt[rows][ld] with
@@ -358,11 +396,13 @@ PPBO_API int ppbo_predict_cov(ppbo_ctx* ctx, const ppbo_model* model, const doub
                      double shrink, double* d_mu, double* d_cov, void* stream);
 
 /* ---- f-2: posterior mean with its analytic gradient ----------------------------
- * d_mu[M] = K*^T alpha (src/gp_model.py:454-458), d_grad[M,D] = d mu / d x in the model's scaled
- * coordinates.  The reference has no gradient: mu_star (src/gp_model.py:415-437) maximises mu_pred by
+ * d_mu[M] = K*^T alpha (src/gp_model.py:454-458), d_grad[M,D] = d mu / d x at d_Xc[M,D], both in the caller's
+ * coordinates (model->coords).  SCALED: mu at s (.) x, d mu / d x_d = s_d d mu / d x~_d.  CAMPHOR (D = 6): the 11-D
+ * gradient on e(x) pulled back through de/dx, 2 pi (c_d g_s - s_d g_c) for a periodic d, g_z / l_2 for z.
+ * The reference has no gradient: mu_star (src/gp_model.py:415-437) maximises mu_pred by
  * differential evolution; the drop-in refines the best candidates of the batched search by a
- * multi-start ascent on these gradients instead.  Only kernel_id, N, D, theta, d_X, d_alpha of the
- * model are read. */
+ * multi-start ascent on these gradients instead.  Only kernel_id, N, D, theta, d_X, d_alpha and coords of
+ * the model are read. */
 PPBO_API int ppbo_mean_grad(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc, int64_t M,
                    double* d_mu, double* d_grad, void* stream);
 
@@ -383,8 +423,12 @@ PPBO_API int ppbo_mean_grad(ppbo_ctx* ctx, const ppbo_model* model, const double
  *     index), and after it every live survivor with sum_d (x_d - x*_d)^2 <= sep^2 is struck -- inclusive, so a
  *     survivor exactly `sep` away goes, and so does the winner itself (sep = 0 strikes the winner and its duplicates);
  *     the picks stop early when no survivor above -inf is left, so *h_found may be less than K;
- *   - distances are plain Euclidean in the coordinates of d_cand (the caller's coordinates in the ARD and camphor forms).
+ *   - distances are plain Euclidean in the coordinates of d_cand (the caller's coordinates under a coordinate map).
  * iters = 0 returns the picked rows (clipped to the unit box) and the mean there.
+ * ppbo_mean_search (one trial) has no form for a coordinate map: model->coords.kind != 0 is "invalid argument".
+ * ppbo_mean_ascent under a map: starts, box, tol and results in the caller's coordinates; SCALED evaluates the mean at
+ * s (.) x and scales its gradient by s, CAMPHOR evaluates mu and its gradient on d_Xc with the camphor form
+ * s = sum_{d != 2} (2 / l_d^2) sin^2(pi dx_d) + dx_2^2 / (2 l_2^2).
  * ppbo_shift_points: d_out = frac(d_in + h_shift[D]) row-wise -- a rotation of a RESIDENT uniform candidate pool,
  * so that repeated searches see fresh candidates without regenerating and uploading M x D numbers. */
 PPBO_API int ppbo_mean_search(ppbo_ctx* ctx, const ppbo_model* model, const double* d_cand, int64_t M, int K, double sep,
@@ -403,64 +447,20 @@ PPBO_API int ppbo_shift_points(ppbo_ctx* ctx, const double* d_in, int64_t M, int
  * screen_fp32 = 1: the candidates are RANKED by a mean whose kernel values are evaluated in fp32 (packed fp32 math,
  * v_exp_f32; accumulated in fp64; relative error ~1e-6) -- every reported value and point comes from the fp64 ascent;
  * 0: ranked by the fp64 mean of ppbo_predict, as ppbo_mean_search does (bit-identical results to T such calls).
- * d_x[T,K,D], d_mu[T,K]: the refined maxima per trial (rows that found no start: mu = -inf).  Nothing synchronises. */
+ * d_x[T,K,D], d_mu[T,K]: the refined maxima per trial (rows that found no start: mu = -inf).  Nothing synchronises.
+ * Under a coordinate map (model->coords) d_extra = NULL with E_rows = N stands for the design in the caller's coordinates
+ * (SCALED: the model's rows divided by s; CAMPHOR: d_Xc), and the candidates are screened on their scaled / embedded rows. */
 PPBO_API int ppbo_mean_search_multi(ppbo_ctx* ctx, const ppbo_model* model, const double* d_pool, int64_t M,
                            const double* h_shifts, int T, const double* d_extra, int E_rows, const double* h_xprev,
                            int K, double sep, int iters, double tol, int screen_fp32, double* d_x, double* d_mu,
                            void* stream);
 
-/* ---- ARD: one length scale per input dimension (no reference counterpart) --------------------------------------------
- * For a radial kernel (SE, RQ, Matern-5/2, Matern-3/2), k(x, x'; l_1..l_D) = k(s (.) x, s (.) x'; l = 1) with s_d = 1 / l_d.
- * An ARD model therefore holds its SCALED rows in d_X and theta = [sigma, 1, sigma_f]; every other entry point runs on it
- * unchanged.  Only what works in the caller's coordinates needs these three.
- * ppbo_scale_points (no reference counterpart): d_out[i,d] = d_in[i,d] * h_scale[d] for M rows of D (in place allowed).
- * ppbo_mean_search_multi_scaled / ppbo_mean_ascent_scaled (no reference counterpart): ppbo_mean_search_multi /
- * ppbo_mean_ascent on such a model, with h_scale[D] = s.  Pool rotation, extra points, h_xprev, the [0,1]^D box, sep,
- * tol and the returned points are all in the caller's coordinates; d_extra = NULL stands for the model's design points
- * in those coordinates (its rows divided by s).  The mean is evaluated at s (.) x and its gradient scaled by s.  The
- * camphor-copper kernel and a non-positive or non-finite scale are rejected with "invalid argument". */
+/* ---- into a model's coordinates ("the coordinate map of a model" above) ------------------------------------------------ */
 PPBO_API int ppbo_scale_points(ppbo_ctx* ctx, const double* d_in, int64_t M, int D, const double* h_scale, double* d_out,
                       void* stream);
-PPBO_API int ppbo_mean_search_multi_scaled(ppbo_ctx* ctx, const ppbo_model* model, const double* d_pool, int64_t M,
-                           const double* h_shifts, int T, const double* d_extra, int E_rows, const double* h_xprev,
-                           int K, double sep, int iters, double tol, int screen_fp32, double* d_x, double* d_mu,
-                           const double* h_scale, void* stream);
-PPBO_API int ppbo_mean_ascent_scaled(ppbo_ctx* ctx, const ppbo_model* model, const double* d_starts, int K, int iters,
-                     double tol, double* d_x, double* d_mu, int* d_iters, const double* h_scale, void* stream);
-
-/* ---- camphor-copper with one length scale per coordinate (no reference counterpart) ------------------------------------
- * The camphor-copper kernel with l_0..l_5 (x, y, z, alpha, beta, gamma; z is the non-periodic coordinate 2) is SE with
- * l = 1 on embedded rows e(x) in R^11:
- *   camphor(x, x'; l, sigma_f) = SE(e(x), e(x'); 1, sigma_f),   |e_d(x) - e_d(x')|^2 = 4 sin^2(pi (x_d - x'_d)) / l_d^2,
- * column order (c0, s0, c1, s1, z, c3, s3, c4, s4, c5, s5) with c_d = cos(2 pi x_d) / l_d, s_d = sin(2 pi x_d) / l_d and
- * z = x_2 / l_2.  The reference's kernel is l = (l, l, l + 0.05, l, l, l).  Such a model holds its EMBEDDED rows in d_X
- * (D = 11), kernel_id = PPBO_KERNEL_SE and theta = [sigma, 1, sigma_f]; the Gram, fit, posterior, evidence and its
- * gradient, prediction and the line acquisition run on it unchanged.  h_l[6] are the length scales (host); every entry
- * below rejects a non-positive or non-finite one, and a model that is not SE at D = 11, with "invalid argument".
- * ppbo_camphor_embed: d_out[M,11] = e(d_in[M,6]) (one memory-bound pass; an output that overlaps the input is
- *   rejected, as is M beyond one launch grid, 2^31 - 1 blocks of 256 / 6 rows).
- * ppbo_camphor_line_points: the embedded grid d_out[B*G,11] of the B lines x_b + alpha_g xi_b (d_xi, d_x [B,6]; d_alpha
- *   [G], or [B,G] with alpha_per_line), formed in the caller's coordinates; ppbo_line_acq takes it as d_grid[B,G,11]
- *   (d_out must not overlap the inputs).
- * ppbo_mean_grad_camphor: mu[M] and d mu / d x [M,6] at d_xc[M,6] in the caller's coordinates (the 11-D gradient of
- *   ppbo_mean_grad pulled back through de/dx: 2 pi (c_d g_s - s_d g_c) for a periodic d, g_z / l_2 for z).
- * ppbo_mean_search_multi_camphor / ppbo_mean_ascent_camphor: ppbo_mean_search_multi / ppbo_mean_ascent on such a model,
- *   with d_Xc[N,6] = the model's design rows in the caller's coordinates.  Pool rotation, extra points (NULL with
- *   E_rows = N: d_Xc), h_xprev, the [0,1]^6 box, sep, tol and the results are in the caller's coordinates; candidates are
- *   screened on their embedded rows, the ascent evaluates mu and its gradient on d_Xc with the camphor form
- *   s = sum_{d != 2} (2 / l_d^2) sin^2(pi dx_d) + dx_2^2 / (2 l_2^2). */
 PPBO_API int ppbo_camphor_embed(ppbo_ctx* ctx, const double* d_in, int64_t M, const double* h_l, double* d_out, void* stream);
 PPBO_API int ppbo_camphor_line_points(ppbo_ctx* ctx, const double* d_xi, const double* d_x, const double* d_alpha,
                              int alpha_per_line, int B, int G, const double* h_l, double* d_out, void* stream);
-PPBO_API int ppbo_mean_grad_camphor(ppbo_ctx* ctx, const ppbo_model* model, const double* d_xc, int64_t M,
-                           const double* h_l, double* d_mu, double* d_grad, void* stream);
-PPBO_API int ppbo_mean_search_multi_camphor(ppbo_ctx* ctx, const ppbo_model* model, const double* d_pool, int64_t M,
-                           const double* h_shifts, int T, const double* d_extra, int E_rows, const double* h_xprev,
-                           int K, double sep, int iters, double tol, int screen_fp32, double* d_x, double* d_mu,
-                           const double* d_Xc, const double* h_l, void* stream);
-PPBO_API int ppbo_mean_ascent_camphor(ppbo_ctx* ctx, const ppbo_model* model, const double* d_starts, int K, int iters,
-                     double tol, double* d_x, double* d_mu, int* d_iters, const double* d_Xc, const double* h_l,
-                     void* stream);
 
 /* ---- K10: Monte-Carlo line acquisition -------------------------------------
  * replaces EI / varmax (src/acquisition.py:72-81, 170-178) for B lines of G points
@@ -516,20 +516,17 @@ PPBO_API int ppbo_rff_omega_map(ppbo_ctx* ctx, const double* d_Phi, int F, int N
  * L-BFGS-B starts on NumPy phi / Dphi (src/random_fourier_sampler.py:143-176).  Scores the M candidates
  * (ppbo_rff_score), keeps the K best that are > sep apart and runs the whole projected Barzilai-Borwein ascent of
  * each inside one kernel with the analytic gradient -a sum_f omega_f sin(w_f.x + b_f) w_f (:51-53).
- * d_x[K,D] / d_val[K]: refined maxima (rows >= *h_found: value -inf). */
+ * d_x[K,D] / d_val[K]: refined maxima (rows >= *h_found: value -inf).
+ * coords = NULL (or kind 0): d_W[F,D] acts on the points themselves.  PPBO_COORDS_CAMPHOR, a camphor-copper basis
+ * (camphor_copper_kernel, camphor_copper_ard_kernel; D must be 6): the features live on the embedded point e(x) in R^11,
+ * phi(x) = sqrt(2 sf^2 / F) cos(W e(x) + b) with d_W[F,11], and the search runs in the caller's six coordinates.
+ * d_cand[M,6] are embedded (ppbo_camphor_embed) and scored (ppbo_rff_score); the starts are chosen on d_cand, so sep is in
+ * the caller's units; each ascent forms e(x) and pulls the gradient back through de/dx (2 pi (c_d g_s - s_d g_c) for a
+ * periodic d, g_z / l_2 for z).  h_coef = l[6] (the scalar kernel: l, l, l + 0.05, l, l, l); d_Xc is not read.
+ * PPBO_COORDS_SCALED is "invalid argument": a scaled basis is a basis (W s). */
 PPBO_API int ppbo_rff_search(ppbo_ctx* ctx, const double* d_cand, int64_t M, int D, const double* d_W, int F,
-                    const double* d_b, double sigma_f, const double* d_omega, int K, double sep, int iters,
-                    double tol, double* d_x, double* d_val, int* h_found, void* stream);
-
-/* ppbo_rff_search for a camphor-copper basis (camphor_copper_kernel, camphor_copper_ard_kernel): the features live on
- * the embedded point e(x) in R^11 of the camphor section above, phi(x) = sqrt(2 sf^2 / F) cos(W e(x) + b) with
- * d_W[F,11], and the search runs in the caller's six coordinates.  d_cand[M,6] are embedded (ppbo_camphor_embed) and
- * scored (ppbo_rff_score); the starts are chosen on d_cand, so sep is in the caller's units; each ascent forms e(x)
- * and pulls the gradient back through de/dx (2 pi (c_d g_s - s_d g_c) for a periodic d, g_z / l_2 for z).
- * h_l[6]: the length scales (the scalar kernel: l, l, l + 0.05, l, l, l).  d_x[K,6] / d_val[K] as ppbo_rff_search. */
-PPBO_API int ppbo_rff_search_camphor(ppbo_ctx* ctx, const double* d_cand, int64_t M, const double* h_l, const double* d_W,
-                    int F, const double* d_b, double sigma_f, const double* d_omega, int K, double sep, int iters,
-                    double tol, double* d_x, double* d_val, int* h_found, void* stream);
+                    const double* d_b, double sigma_f, const double* d_omega, const ppbo_coords* coords, int K,
+                    double sep, int iters, double tol, double* d_x, double* d_val, int* h_found, void* stream);
 
 /* ---- batches of posterior samples: S weight vectors omega_s per enqueue ----------------------------------------
  * The upstream workflow draws the posterior of the maximiser with one Hsampler.sample_xstar() per sample
@@ -556,16 +553,13 @@ PPBO_API int ppbo_rff_score_multi(ppbo_ctx* ctx, const double* d_Xc, int64_t M, 
  * every sample (ppbo_rff_score_multi), picks each sample's K best starts > sep apart in its own scores, and ascends all
  * S x K starts in one launch, workgroup s K + k on omega_s.  d_x[S,K,D] / d_val[S,K]: refined maxima of sample s in
  * rows < d_found[s] (an int array on the device), value -inf in the others.  Enqueued only: nothing is read back.
+ * coords as ppbo_rff_search: with PPBO_COORDS_CAMPHOR d_W[F,11], d_cand[M,6] embedded once and scored at D = 11;
+ * selection, box, sep and d_x[S,K,6] in the caller's coordinates.
  * "invalid argument" as ppbo_rff_score_multi, and K outside 1 .. 1024. */
 PPBO_API int ppbo_rff_search_multi(ppbo_ctx* ctx, const double* d_cand, int64_t M, int D, const double* d_W, int F,
-                          const double* d_b, double sigma_f, const double* d_omegas, int S, int K, double sep, int iters,
-                          double tol, double* d_x, double* d_val, int* d_found, void* stream);
-
-/* ppbo_rff_search_multi for a camphor-copper basis, as ppbo_rff_search_camphor: h_l[6] length scales, d_W[F,11],
- * d_cand[M,6] embedded once and scored at D = 11; selection, box, sep and d_x[S,K,6] in the caller's coordinates. */
-PPBO_API int ppbo_rff_search_multi_camphor(ppbo_ctx* ctx, const double* d_cand, int64_t M, const double* h_l,
-                          const double* d_W, int F, const double* d_b, double sigma_f, const double* d_omegas, int S, int K,
-                          double sep, int iters, double tol, double* d_x, double* d_val, int* d_found, void* stream);
+                          const double* d_b, double sigma_f, const double* d_omegas, const ppbo_coords* coords, int S,
+                          int K, double sep, int iters, double tol, double* d_x, double* d_val, int* d_found,
+                          void* stream);
 
 /* ---- pathwise posterior samples (decoupled sampling, Wilson et al. 2020, on the Laplace posterior) -----------------
  * g_s(x) = phi(x)^T w_s + k(x, X) v_s with prior weights w_s ~ N(0, I_F) and v_s = Sigma^-1 (f_s - Phi(X)^T w_s),
@@ -587,12 +581,13 @@ PPBO_API int ppbo_path_score_multi(ppbo_ctx* ctx, int kernel_id, const double th
 /* ppbo_rff_search_multi for S paths: scores every candidate for every path (ppbo_path_score_multi), picks each path's K
  * best starts > sep apart in its own scores, and ascends all S x K starts in one launch with the value and gradient of
  * g_s (both halves) evaluated per iterate.  d_cand[M,D], the [0,1]^D box, sep and d_x[S,K,D] in the caller's coordinates
- * with d_W[F,D] the basis there; h_scale = NULL: d_X[N,D] the design, theta its kernel's; h_scale[D] = 1 / l (ARD): d_X
- * the scaled rows and theta[1] = 1.  d_x / d_val / d_found as ppbo_rff_search_multi.  Enqueued only.
- * "invalid argument" as ppbo_path_score_multi, K outside 1 .. 1024, a scale that is not positive and finite. */
+ * with d_W[F,D] the basis there; coords = NULL (or kind 0): d_X[N,D] the design, theta its kernel's; PPBO_COORDS_SCALED
+ * (h_coef[D] = 1 / l, ARD): d_X the scaled rows and theta[1] = 1.  d_x / d_val / d_found as ppbo_rff_search_multi.
+ * Enqueued only.  "invalid argument" as ppbo_path_score_multi, K outside 1 .. 1024, a scale that is not positive and
+ * finite, PPBO_COORDS_CAMPHOR (as the camphor kernel id). */
 PPBO_API int ppbo_path_search_multi(ppbo_ctx* ctx, int kernel_id, const double theta[3], const double* d_cand, int64_t M,
                           int D, const double* d_W, int F, const double* d_b, const double* d_Wp, const double* d_X, int N,
-                          const double* d_V, const double* h_scale, int S, int K, double sep, int iters, double tol,
+                          const double* d_V, const ppbo_coords* coords, int S, int K, double sep, int iters, double tol,
                           double* d_x, double* d_val, int* d_found, void* stream);
 
 /* ---- generic fp64 MFMA GEMM (exposed for tests and host-side composition) ----

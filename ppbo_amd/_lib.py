@@ -33,11 +33,34 @@ class FitStats(C.Structure):
                 ("lbfgs_iterations", C.c_int), ("lbfgs_evals", C.c_int), ("lbfgs_status", C.c_int)]
 
 
+COORDS_MODEL, COORDS_SCALED, COORDS_CAMPHOR = 0, 1, 2   # ppbo_coords.kind (PPBO_COORDS_*)
+
+
+class Coords(C.Structure):
+    _fields_ = [("kind", C.c_int), ("h_coef", C.POINTER(C.c_double)), ("d_Xc", C.c_void_p)]
+
+
 class Model(C.Structure):
     _fields_ = [("kernel_id", C.c_int), ("N", C.c_int), ("D", C.c_int), ("m", C.c_int),
                 ("theta", C.c_double * 3), ("d_X", C.c_void_p), ("d_alpha", C.c_void_p),
                 ("d_lam_diag", C.c_void_p), ("d_lam_off", C.c_void_p), ("d_G", C.c_void_p), ("kstar_fp32", C.c_int),
-                ("d_Gt", C.c_void_p), ("form", C.c_int)]
+                ("d_Gt", C.c_void_p), ("form", C.c_int), ("coords", Coords)]
+
+
+
+
+def coords(kind=COORDS_MODEL, coef=None, d_Xc=None):
+    """A ppbo_coords of `kind` over the host coefficients `coef` (SCALED: s = 1 / l; CAMPHOR: the six length scales) and,
+    for a camphor model, the device address d_Xc of its rows in the caller's coordinates.  The float64 copy of `coef`
+    that h_coef points into stays referenced from the struct, so it lives as long as the struct does."""
+    import numpy as np
+    co = Coords()
+    co.kind = kind
+    if coef is not None:
+        co._coef = np.ascontiguousarray(coef, dtype=np.float64).reshape(-1)
+        co.h_coef = co._coef.ctypes.data_as(C.POINTER(C.c_double))
+    co.d_Xc = d_Xc
+    return co
 
 
 _vp, _i, _d, _i64 = C.c_void_p, C.c_int, C.c_double, C.c_int64
@@ -82,30 +105,21 @@ SIGNATURES = {
     "ppbo_shift_points": [_vp, _vp, _i64, _i, C.POINTER(_d), _vp, _vp],
     "ppbo_mean_search_multi": [_vp, C.POINTER(Model), _vp, _i64, C.POINTER(_d), _i, _vp, _i, C.POINTER(_d), _i, _d, _i, _d, _i, _vp, _vp, _vp],
     "ppbo_scale_points": [_vp, _vp, _i64, _i, C.POINTER(_d), _vp, _vp],
-    "ppbo_mean_search_multi_scaled": [_vp, C.POINTER(Model), _vp, _i64, C.POINTER(_d), _i, _vp, _i, C.POINTER(_d), _i, _d, _i, _d,
-                                      _i, _vp, _vp, C.POINTER(_d), _vp],
-    "ppbo_mean_ascent_scaled": [_vp, C.POINTER(Model), _vp, _i, _i, _d, _vp, _vp, _vp, C.POINTER(_d), _vp],
     "ppbo_camphor_embed": [_vp, _vp, _i64, C.POINTER(_d), _vp, _vp],
     "ppbo_camphor_line_points": [_vp, _vp, _vp, _vp, _i, _i, _i, C.POINTER(_d), _vp, _vp],
-    "ppbo_mean_grad_camphor": [_vp, C.POINTER(Model), _vp, _i64, C.POINTER(_d), _vp, _vp, _vp],
-    "ppbo_mean_search_multi_camphor": [_vp, C.POINTER(Model), _vp, _i64, C.POINTER(_d), _i, _vp, _i, C.POINTER(_d), _i, _d, _i,
-                                       _d, _i, _vp, _vp, _vp, C.POINTER(_d), _vp],
-    "ppbo_mean_ascent_camphor": [_vp, C.POINTER(Model), _vp, _i, _i, _d, _vp, _vp, _vp, _vp, C.POINTER(_d), _vp],
     "ppbo_line_acq": [_vp, C.POINTER(Model), _vp, _i, _i, _d, _vp, _i, _d, _d, _vp, _vp, _vp],
     "ppbo_line_acq_xi": [_vp, C.POINTER(Model), _vp, _vp, _vp, _i, _i, _i, _d, _vp, _i, _d, _d, _vp, _vp, _vp],
     "ppbo_randn": [_vp, C.c_uint64, _vp, _i64, _vp],
     "ppbo_rff_project": [_vp, _vp, _i, _i, _vp, _i, _vp, _d, _vp, _vp],
     "ppbo_rff_score": [_vp, _vp, _i64, _i, _vp, _i, _vp, _d, _vp, _vp, C.POINTER(_d), C.POINTER(_i64), _vp],
-    "ppbo_rff_search": [_vp, _vp, _i64, _i, _vp, _i, _vp, _d, _vp, _i, _d, _i, _d, _vp, _vp, C.POINTER(_i), _vp],
-    "ppbo_rff_search_camphor": [_vp, _vp, _i64, C.POINTER(_d), _vp, _i, _vp, _d, _vp, _i, _d, _i, _d, _vp, _vp, C.POINTER(_i),
-                                _vp],
+    "ppbo_rff_search": [_vp, _vp, _i64, _i, _vp, _i, _vp, _d, _vp, C.POINTER(Coords), _i, _d, _i, _d, _vp, _vp, C.POINTER(_i),
+                        _vp],
     "ppbo_rff_omega_draws": [_vp, C.c_uint64, _vp, _vp, _i, _i, _vp, _vp],
     "ppbo_rff_score_multi": [_vp, _vp, _i64, _i, _vp, _i, _vp, _d, _vp, _i, _vp, _vp],
-    "ppbo_rff_search_multi": [_vp, _vp, _i64, _i, _vp, _i, _vp, _d, _vp, _i, _i, _d, _i, _d, _vp, _vp, _vp, _vp],
-    "ppbo_rff_search_multi_camphor": [_vp, _vp, _i64, C.POINTER(_d), _vp, _i, _vp, _d, _vp, _i, _i, _d, _i, _d, _vp, _vp,
-                                      _vp, _vp],
+    "ppbo_rff_search_multi": [_vp, _vp, _i64, _i, _vp, _i, _vp, _d, _vp, C.POINTER(Coords), _i, _i, _d, _i, _d, _vp, _vp, _vp,
+                              _vp],
     "ppbo_path_score_multi": [_vp, _i, _dp3, _vp, _i64, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp],
-    "ppbo_path_search_multi": [_vp, _i, _dp3, _vp, _i64, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, C.POINTER(_d), _i, _i, _d, _i, _d,
+    "ppbo_path_search_multi": [_vp, _i, _dp3, _vp, _i64, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, C.POINTER(Coords), _i, _i, _d, _i, _d,
                                _vp, _vp, _vp, _vp],
     "ppbo_rff_terms": [_vp, _vp, _i, _i, _i, _d, _vp, C.POINTER(_d), _vp, _vp, _vp],
     "ppbo_rff_omega_map": [_vp, _vp, _i, _i, _i, _d, _vp, _i, _d, C.POINTER(_d), C.POINTER(_d), C.POINTER(_i), _vp],
@@ -126,7 +140,7 @@ SIGNATURES = {
 }
 
 _lib = None
-ABI_VERSION = 7     # must equal PPBO_ABI_VERSION of include/ppbo_hip.h
+ABI_VERSION = 8     # must equal PPBO_ABI_VERSION of include/ppbo_hip.h
 
 
 def _check_stamp():

@@ -1,6 +1,7 @@
 // The camphor-copper kernel with one length scale per coordinate (include/ppbo_hip.h): SE with l = 1 on the embedded
 // rows e(x) in R^11, column order (c0, s0, c1, s1, z, c3, s3, c4, s4, c5, s5).  Shared by camphor.hip (embedding, line
-// points, mean gradient) and meangrad.hip (mu_star and the RFF search in the caller's coordinates).
+// points, the gradient's pull-back) and meangrad.hip (the mean gradient, mu_star and the RFF search in the caller's
+// coordinates).
 #pragma once
 #include "common.h"
 
@@ -54,3 +55,7 @@ __device__ __forceinline__ void camphor_embed_one(double v, int d, const Camphor
 #define PPBO_REQUIRE_CAMPHOR_MODEL(ctx, m)                                                                         \
   PPBO_REQUIRE(ctx, (m) != nullptr && (m)->d_X && (m)->d_alpha && (m)->N > 0 && (m)->kernel_id == PPBO_KERNEL_SE && \
                         (m)->D == CAMPHOR_E, "a camphor model is SE on embedded rows (D = 11) with X / alpha")
+
+// d_grad[M][6] from the embedded points d_e and a gradient d_g on them (both [M][11]); inv_lz = 1 / l_2 (camphor.hip)
+int ppbo_camphor_pullback(ppbo_ctx* ctx, const double* d_e, const double* d_g, int64_t M, double inv_lz, double* d_grad,
+                          hipStream_t s);

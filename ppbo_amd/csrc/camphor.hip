@@ -5,10 +5,10 @@
 // exactly and the whole SE machinery runs on the embedded rows.  What works in the caller's coordinates is here:
 //   ppbo_camphor_embed        e of M rows: one thread per (row, coordinate), sinpi / cospi (exact range reduction)
 //   ppbo_camphor_line_points  the embedded points of B lines x_b + alpha_g xi_b (the line is not linear in e)
-//   ppbo_mean_grad_camphor    ppbo_mean_grad on the embedded points, the gradient pulled back through de/dx:
+//   ppbo_camphor_pullback     (internal) a gradient on the embedded points pulled back through de/dx, for ppbo_mean_grad:
 //                             d mu / d x_d = 2 pi (c_d g_s - s_d g_c) (periodic d),  g_z / l_2 (z)
-// mu_star in the caller's coordinates (ppbo_mean_search_multi_camphor, ppbo_mean_ascent_camphor) lives in meangrad.hip
-// beside the search it reuses.
+// Everything that reads a model's coordinate map (ppbo_coords with PPBO_COORDS_CAMPHOR: the mean gradient, mu_star and
+// the RFF search in the caller's coordinates) lives in meangrad.hip beside the search it reuses.
 #include "camphor.h"
 
 namespace {
@@ -88,23 +88,10 @@ extern "C" int ppbo_camphor_line_points(ppbo_ctx* ctx, const double* d_xi, const
   return 0;
 }
 
-extern "C" int ppbo_mean_grad_camphor(ppbo_ctx* ctx, const ppbo_model* m, const double* d_xc, int64_t M,
-                                      const double* h_l, double* d_mu, double* d_grad, void* stream) {
-  PPBO_ENTER(ctx);
-  PPBO_REQUIRE_CAMPHOR_MODEL(ctx, m);
-  PPBO_REQUIRE_CAMPHOR_L(ctx, h_l);
-  PPBO_REQUIRE(ctx, d_xc && d_mu && d_grad && M >= 0 && M < (1 << 30) && M <= CAMPHOR_MAX_ROWS, "points / outputs");
-  if (M == 0) return 0;
-  hipStream_t s = (hipStream_t)stream;
-  // workspace: the embedded points [M][11] | their gradient [M][11]
-  double* e = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_CAMPHOR, (size_t)2 * M * CAMPHOR_E * sizeof(double));
-  if (!e) return (int)hipErrorOutOfMemory;
-  double* g = e + (size_t)M * CAMPHOR_E;
+int ppbo_camphor_pullback(ppbo_ctx* ctx, const double* d_e, const double* d_g, int64_t M, double inv_lz, double* d_grad,
+                          hipStream_t s) {
   const int64_t n = M * CAMPHOR_D;
-  camphor_embed_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(d_xc, n, camphor_inv_l(h_l), e);
-  PPBO_LAUNCH_CHECK(ctx);
-  if (int rc = ppbo_mean_grad(ctx, m, e, M, d_mu, g, stream)) return rc;
-  camphor_pullback_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(e, g, n, 1.0 / h_l[2], d_grad);
+  camphor_pullback_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(d_e, d_g, n, inv_lz, d_grad);
   PPBO_LAUNCH_CHECK(ctx);
   return 0;
 }

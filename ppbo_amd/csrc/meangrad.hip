@@ -436,7 +436,7 @@ struct MeanEval {
   }
 };
 
-// ARD (ppbo_mean_ascent_scaled): the ascent runs in the caller's coordinates x over the model's scaled rows -- mu at
+// ARD (PPBO_COORDS_SCALED): the ascent runs in the caller's coordinates x over the model's scaled rows -- mu at
 // s (.) x, d mu / d x_d = s_d d mu / d x~_d.  The scaled point goes through LDS of its own (one barrier); the gradient's
 // partial sums are scaled by the threads that wrote them (eval_mean_grad: lane 16 k of each wavefront writes record
 // 4 wave + k), so the barrier behind the evaluation in bb_ascent_kernel still orders them before they are read.
@@ -458,7 +458,7 @@ struct ScaledMeanEval {
   }
 };
 
-// camphor-copper with one length scale per coordinate (ppbo_mean_ascent_camphor): mu and its gradient in the caller's
+// camphor-copper with one length scale per coordinate (PPBO_COORDS_CAMPHOR): mu and its gradient in the caller's
 // coordinates over the design's caller-coordinate rows (X transposed, [6][N]) -- the camphor form of eval_mean_grad with
 // a coefficient per coordinate, c.k[d] = 2 / l_d^2 (periodic) and 1 / (2 l_2^2) (z); the same reduction records.
 template <int DP, int NT>
@@ -549,7 +549,7 @@ struct RffEval {
   }
 };
 
-// one camphor-copper posterior sample in the caller's coordinates (ppbo_rff_search_camphor): the basis lives on the
+// one camphor-copper posterior sample in the caller's coordinates (ppbo_rff_search, PPBO_COORDS_CAMPHOR): the basis lives on the
 // embedded point e(x) in R^11 (camphor.h), f(x) = a sum_f omega_f cos(w_f.e(x) + b_f).  The threads of wavefront 0
 // form e(sx) once per evaluation in LDS (camphor_embed_one: the bits ppbo_camphor_embed writes), every thread runs
 // RffEval's per-feature body (RFF_FEATURE_BODY) over its features at D = 11 and pulls its partial gradient back through de/dx before
@@ -590,7 +590,7 @@ struct CamphorRffEval {
   }
 };
 
-// the batched forms (ppbo_rff_search_multi / _camphor): one launch runs S x K starts, workgroup s K + k on sample s, whose
+// the batched forms (ppbo_rff_search_multi): one launch runs S x K starts, workgroup s K + k on sample s, whose
 // weights follow sample 0's at s F.  They ARE the single-sample evaluations (RffEval, CamphorRffEval) with omega moved
 // to the workgroup's sample.
 template <class EV>
@@ -769,12 +769,73 @@ __global__ __launch_bounds__(256) void transpose_rows_kernel(const double* __res
   for (int d = 0; d < D; ++d) out[(size_t)d * R + r] = in[(size_t)r * D + d];
 }
 
-// d_scale (ARD, radial kernels only): D values s_d on the device; the ascent then runs in the caller's coordinates.
-// cam (camphor-copper only): per-coordinate coefficients; m is then the caller-coordinate view of an embedded model
+// A call's coordinate map (ppbo_coords), resolved on the host: what the launchers need of it.
+struct CoordMap {
+  int kind = PPBO_COORDS_MODEL, D = 0;
+  const double* h_coef = nullptr;    // SCALED: s[D]; CAMPHOR: l[6] (host)
+  double* d_scale = nullptr;         // SCALED, after upload(): s[D] | 1 / s[D] on the device
+  CamphorCoef cam;                   // CAMPHOR: the camphor form's coefficients ...
+  CamphorInvL inv_l;                 // ... and 1 / l
+  const ppbo_model* model = nullptr; // model entries: the model in the CALLER's coordinates -- the model itself, or `view`
+  ppbo_model view;                   // CAMPHOR: kernel camphor at D = 6 over d_Xc with the embedded model's alpha and theta
+                                     // (its KernParams carry sf2 only, the coefficients travel in cam)
+  // s and 1 / s in one upload (nothing for the other kinds); after every refusal of the entry, ahead of its launches
+  int upload(ppbo_ctx* ctx, hipStream_t s) {
+    if (kind != PPBO_COORDS_SCALED) return 0;
+    d_scale = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_SCALE, 128 * sizeof(double));
+    if (!d_scale) return (int)hipErrorOutOfMemory;
+    double hs[128];
+    for (int d = 0; d < D; ++d) { hs[d] = h_coef[d]; hs[D + d] = 1.0 / h_coef[d]; }
+    return ppbo_upload_async(ctx, d_scale, hs, 2 * (size_t)D * sizeof(double), s);
+  }
+};
+
+// The one validation of a map (c = NULL: the identity) over points of D <= 64 caller coordinates and a kernel id
+static int resolve_coords(ppbo_ctx* ctx, const ppbo_coords* c, int kernel_id, int D, CoordMap& co) {
+  co.D = D;
+  if (!c || c->kind == PPBO_COORDS_MODEL) return 0;
+  PPBO_REQUIRE(ctx, c->kind == PPBO_COORDS_SCALED || c->kind == PPBO_COORDS_CAMPHOR, "coords.kind (PPBO_COORDS_*)");
+  if (c->kind == PPBO_COORDS_SCALED) {
+    PPBO_REQUIRE(ctx, c->h_coef != nullptr, "coords.h_coef (D scales)");
+    PPBO_REQUIRE(ctx, kernel_id != PPBO_KERNEL_CAMPHOR, "per-dimension scales need a radial kernel");
+    for (int d = 0; d < D; ++d)
+      PPBO_REQUIRE(ctx, c->h_coef[d] > 0.0 && std::isfinite(c->h_coef[d]), "coords.h_coef: positive finite scales");
+  } else {
+    PPBO_REQUIRE_CAMPHOR_L(ctx, c->h_coef);
+    PPBO_REQUIRE(ctx, D == CAMPHOR_D, "camphor coordinates: six of them");
+    co.cam = camphor_coef(c->h_coef);
+    co.inv_l = camphor_inv_l(c->h_coef);
+  }
+  co.kind = c->kind;
+  co.h_coef = c->h_coef;
+  return 0;
+}
+
+// ... of a model's map, behind the checks every mean entry makes of its model
+static int resolve_model_coords(ppbo_ctx* ctx, const ppbo_model* m, CoordMap& co) {
+  PPBO_REQUIRE(ctx, m != nullptr && m->d_X && m->d_alpha, "model X/alpha");
+  PPBO_REQUIRE(ctx, m->N > 0 && m->D > 0 && m->D <= 64, "model sizes (D<=64)");
+  PPBO_REQUIRE_KERNEL(ctx, m->kernel_id, m->D);
+  co.model = m;
+  if (m->coords.kind != PPBO_COORDS_CAMPHOR) return resolve_coords(ctx, &m->coords, m->kernel_id, m->D, co);
+  PPBO_REQUIRE_CAMPHOR_MODEL(ctx, m);
+  PPBO_REQUIRE(ctx, m->coords.d_Xc != nullptr, "coords.d_Xc (the design rows in the caller's coordinates)");
+  if (int rc = resolve_coords(ctx, &m->coords, PPBO_KERNEL_CAMPHOR, CAMPHOR_D, co)) return rc;
+  co.view = *m;
+  co.view.kernel_id = PPBO_KERNEL_CAMPHOR;
+  co.view.D = CAMPHOR_D;
+  co.view.d_X = m->coords.d_Xc;
+  co.view.d_G = nullptr;
+  co.view.d_Gt = nullptr;
+  co.model = &co.view;
+  return 0;
+}
+
+// m: the model in the caller's coordinates (co.model, where the call has a map)
 template <int KID>
-int launch_mean_ascent(ppbo_ctx* ctx, const ppbo_model* m, const KernParams& p, const double* starts, const int* count, int K,
-                       int iters, double tol, double* x_out, double* mu_out, int* it_out, hipStream_t s, int per_trial = 0,
-                       const double* d_scale = nullptr, const CamphorCoef* cam = nullptr) {
+int launch_mean_ascent(ppbo_ctx* ctx, const ppbo_model* m, const KernParams& p, const CoordMap& co, const double* starts,
+                       const int* count, int K, int iters, double tol, double* x_out, double* mu_out, int* it_out,
+                       hipStream_t s, int per_trial = 0) {
   double* Xt = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_TRANSPOSE, (size_t)m->N * m->D * sizeof(double));
   if (!Xt) return (int)hipErrorOutOfMemory;
   transpose_rows_kernel<<<(m->N + 255) / 256, 256, 0, s>>>(m->d_X, m->N, m->D, Xt);
@@ -784,15 +845,15 @@ int launch_mean_ascent(ppbo_ctx* ctx, const ppbo_model* m, const KernParams& p, 
   do {                                                                                                                \
     MeanEval<KID, DP, NT> ev{Xt, m->N, m->D, p, m->d_alpha};                                                        \
     if constexpr (kid_radial<KID>) {                                                                                  \
-      if (d_scale) {                                                                                                  \
-        ScaledMeanEval<KID, DP, NT> sev{ev, d_scale};                                                                 \
+      if (co.d_scale) {                                                                                               \
+        ScaledMeanEval<KID, DP, NT> sev{ev, co.d_scale};                                                              \
         bb_ascent_kernel<DP, ScaledMeanEval<KID, DP, NT>, NT><<<K, NT, 0, s>>>(sev, m->D, starts, count, iters, tol, x_out, mu_out, it_out, per_trial); \
         break;                                                                                                        \
       }                                                                                                               \
     }                                                                                                                 \
     if constexpr (KID == PPBO_KERNEL_CAMPHOR) {                                                                       \
-      if (cam) {                                                                                                      \
-        CamphorMeanEval<DP, NT> cev{Xt, m->N, p.sf2, *cam, m->d_alpha};                                               \
+      if (co.kind == PPBO_COORDS_CAMPHOR) {                                                                           \
+        CamphorMeanEval<DP, NT> cev{Xt, m->N, p.sf2, co.cam, m->d_alpha};                                             \
         bb_ascent_kernel<DP, CamphorMeanEval<DP, NT>, NT><<<K, NT, 0, s>>>(cev, m->D, starts, count, iters, tol, x_out, mu_out, it_out, per_trial); \
         break;                                                                                                        \
       }                                                                                                               \
@@ -821,21 +882,21 @@ void rff_ascent_run(const EV& ev, int D, int S, int K, const double* starts, con
     bb_ascent_kernel<DP, EV, NT><<<K, NT, 0, s>>>(ev, D, starts, count, iters, tol, x_out, v_out, nullptr, 0);
 }
 
-// the RFF ascent over the basis W_rows [F][D] (h_l = NULL) or the camphor basis W_rows [F][11] with starts and results in
-// the caller's six coordinates (h_l: its length scales)
-int launch_rff_ascent(ppbo_ctx* ctx, const double* W_rows, int F, int D, const double* h_l, const double* b,
+// the RFF ascent over the basis W_rows [F][D] or (PPBO_COORDS_CAMPHOR) the camphor basis W_rows [F][11] with starts and
+// results in the caller's six coordinates
+int launch_rff_ascent(ppbo_ctx* ctx, const double* W_rows, int F, int D, const CoordMap& co, const double* b,
                       const double* omega, double amp, const double* starts, const int* count, int S, int K, int iters,
                       double tol, double* x_out, double* v_out, hipStream_t s) {
-  const int DW = h_l ? CAMPHOR_E : D;
+  const bool camphor = co.kind == PPBO_COORDS_CAMPHOR;
+  const int DW = camphor ? CAMPHOR_E : D;
   double* W = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_TRANSPOSE, (size_t)F * DW * sizeof(double));
   if (!W) return (int)hipErrorOutOfMemory;
   transpose_rows_kernel<<<(F + 255) / 256, 256, 0, s>>>(W_rows, F, DW, W);
   const RffPoly P = make_rff_poly(1.0);
   const bool wide = F >= 1024;
-  if (h_l) {
-    const CamphorInvL L = camphor_inv_l(h_l);
+  if (camphor) {
 #define RA_LAUNCH(NT) \
-  rff_ascent_run<8, NT>(CamphorRffEval<NT>{W, F, b, omega, amp, P, L}, CAMPHOR_D, S, K, starts, count, iters, tol, x_out, v_out, s)
+  rff_ascent_run<8, NT>(CamphorRffEval<NT>{W, F, b, omega, amp, P, co.inv_l}, CAMPHOR_D, S, K, starts, count, iters, tol, x_out, v_out, s)
     // 11 embedded columns of point, gradient and feature row: ~170 VGPRs, so at most two wavefronts per SIMD (1024
     // threads would spill)
     if (wide) RA_LAUNCH(512); else RA_LAUNCH(256);
@@ -892,21 +953,46 @@ int launch_mean_grad(const ppbo_model* m, const KernParams& p, const double* d_X
 
 }  // namespace
 
+
 extern "C" int ppbo_mean_grad(ppbo_ctx* ctx, const ppbo_model* m, const double* d_Xc, int64_t M, double* d_mu,
                               double* d_grad, void* stream) {
   PPBO_ENTER(ctx);
-  PPBO_REQUIRE(ctx, m != nullptr && m->d_X && m->d_alpha, "model X/alpha");
-  PPBO_REQUIRE(ctx, m->N > 0 && m->D > 0 && m->D <= 64, "model sizes (D<=64)");
-  PPBO_REQUIRE_KERNEL(ctx, m->kernel_id, m->D);
+  CoordMap co;
+  if (int rc = resolve_model_coords(ctx, m, co)) return rc;
   PPBO_REQUIRE(ctx, d_Xc && d_mu && d_grad && M >= 0 && M < (1 << 30), "points / outputs");
   if (M == 0) return 0;
   hipStream_t s = (hipStream_t)stream;
+  if (int rc = co.upload(ctx, s)) return rc;
+  // the kernel runs in the model's coordinates: on the points mapped forward, its gradient pulled back afterwards
+  const double* pts = d_Xc;
+  double* g = d_grad;
+  const int64_t n = M * co.D;
+  if (co.kind == PPBO_COORDS_SCALED) {
+    double* rows = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_SCALE_SEARCH, (size_t)n * sizeof(double));
+    if (!rows) return (int)hipErrorOutOfMemory;
+    scale_points_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(d_Xc, n, co.D, co.d_scale, rows);
+    PPBO_LAUNCH_CHECK(ctx);
+    pts = rows;
+  } else if (co.kind == PPBO_COORDS_CAMPHOR) {
+    // workspace: the embedded points [M][11] | their gradient [M][11]
+    double* e = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_CAMPHOR, (size_t)2 * M * CAMPHOR_E * sizeof(double));
+    if (!e) return (int)hipErrorOutOfMemory;
+    if (int rc = ppbo_camphor_embed(ctx, d_Xc, M, co.h_coef, e, stream)) return rc;
+    pts = e;
+    g = e + (size_t)M * CAMPHOR_E;
+  }
   const KernParams p = make_kern_params(m->kernel_id, m->theta);
   if (int rc = ppbo_kernel_dispatch(ctx, m->kernel_id, [&](auto kid) {
-        return launch_mean_grad<decltype(kid)::value>(m, p, d_Xc, (int)M, d_mu, d_grad, s);
+        return launch_mean_grad<decltype(kid)::value>(m, p, pts, (int)M, d_mu, g, s);
       }))
     return rc;
   PPBO_LAUNCH_CHECK(ctx);
+  if (co.kind == PPBO_COORDS_SCALED) {          // d mu / d x_d = s_d d mu / d x~_d
+    scale_points_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(d_grad, n, co.D, co.d_scale, d_grad);
+    PPBO_LAUNCH_CHECK(ctx);
+  } else if (co.kind == PPBO_COORDS_CAMPHOR) {
+    return ppbo_camphor_pullback(ctx, pts, g, M, co.inv_l.v[2], d_grad, s);
+  }
   return 0;
 }
 
@@ -927,79 +1013,22 @@ extern "C" int ppbo_shift_points(ppbo_ctx* ctx, const double* d_in, int64_t M, i
   return 0;
 }
 
-// the ARD entries take h_scale (D host values s_d = 1 / l_d) and refuse kernels that are not radial
-#define PPBO_REQUIRE_SCALE(ctx, m, h_scale)                                                                           \
-  do {                                                                                                                \
-    PPBO_REQUIRE(ctx, h_scale != nullptr, "h_scale (D values)");                                                      \
-    PPBO_REQUIRE(ctx, (m)->kernel_id != PPBO_KERNEL_CAMPHOR, "invalid argument: per-dimension scales need a radial kernel"); \
-    for (int _d = 0; _d < (m)->D; ++_d)                                                                               \
-      PPBO_REQUIRE(ctx, h_scale[_d] > 0.0 && std::isfinite(h_scale[_d]), "h_scale: positive finite values");          \
-  } while (0)
-
-static int mean_ascent_impl(ppbo_ctx* ctx, const ppbo_model* m, const double* d_starts, int K, int iters, double tol,
-                            double* d_x, double* d_mu, int* d_iters, const double* h_scale, void* stream,
-                            const CamphorCoef* cam = nullptr) {
+extern "C" int ppbo_mean_ascent(ppbo_ctx* ctx, const ppbo_model* model, const double* d_starts, int K, int iters,
+                                double tol, double* d_x, double* d_mu, int* d_iters, void* stream) {
   PPBO_ENTER(ctx);
-  PPBO_REQUIRE(ctx, m != nullptr && m->d_X && m->d_alpha, "model X/alpha");
-  PPBO_REQUIRE(ctx, m->N > 0 && m->D > 0 && m->D <= 64, "model sizes (D<=64)");
-  PPBO_REQUIRE_KERNEL(ctx, m->kernel_id, m->D);
+  CoordMap co;
+  if (int rc = resolve_model_coords(ctx, model, co)) return rc;
   PPBO_REQUIRE(ctx, d_starts && d_x && d_mu && K > 0 && K <= 65536 && iters >= 0 && tol >= 0, "starts / outputs");
   hipStream_t s = (hipStream_t)stream;
-  double* d_scale = nullptr;
-  if (h_scale) {
-    PPBO_REQUIRE_SCALE(ctx, m, h_scale);
-    d_scale = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_SCALE, 64 * sizeof(double));
-    if (!d_scale) return (int)hipErrorOutOfMemory;
-    if (int rc = ppbo_upload_async(ctx, d_scale, h_scale, (size_t)m->D * sizeof(double), s)) return rc;
-  }
+  if (int rc = co.upload(ctx, s)) return rc;
+  const ppbo_model* m = co.model;
   const KernParams p = make_kern_params(m->kernel_id, m->theta);
-  // (d_scale is NULL for camphor-copper, cam for every other kernel)
   if (int rc = ppbo_kernel_dispatch(ctx, m->kernel_id, [&](auto kid) {
-        return launch_mean_ascent<decltype(kid)::value>(ctx, m, p, d_starts, nullptr, K, iters, tol, d_x, d_mu, d_iters, s,
-                                                        0, d_scale, cam);
+        return launch_mean_ascent<decltype(kid)::value>(ctx, m, p, co, d_starts, nullptr, K, iters, tol, d_x, d_mu, d_iters, s);
       }))
     return rc;
   PPBO_LAUNCH_CHECK(ctx);
   return 0;
-}
-
-extern "C" int ppbo_mean_ascent(ppbo_ctx* ctx, const ppbo_model* m, const double* d_starts, int K, int iters,
-                                double tol, double* d_x, double* d_mu, int* d_iters, void* stream) {
-  return mean_ascent_impl(ctx, m, d_starts, K, iters, tol, d_x, d_mu, d_iters, nullptr, stream);
-}
-
-extern "C" int ppbo_mean_ascent_scaled(ppbo_ctx* ctx, const ppbo_model* m, const double* d_starts, int K, int iters,
-                                       double tol, double* d_x, double* d_mu, int* d_iters, const double* h_scale,
-                                       void* stream) {
-  if (!h_scale) { PPBO_ENTER(ctx); return ppbo_set_error(ctx, -1, "invalid argument: h_scale is NULL"); }
-  return mean_ascent_impl(ctx, m, d_starts, K, iters, tol, d_x, d_mu, d_iters, h_scale, stream);
-}
-
-// the caller-coordinate view of a camphor model (SE on embedded rows): kernel camphor at D = 6 over d_Xc, the same
-// alpha and theta; its KernParams carry sf2 only, the coefficients travel in cc
-static int camphor_view(ppbo_ctx* ctx, const ppbo_model* m, const double* d_Xc, const double* h_l, ppbo_model& cm,
-                        CamphorCoef& cc) {
-  PPBO_REQUIRE_CAMPHOR_MODEL(ctx, m);
-  PPBO_REQUIRE_CAMPHOR_L(ctx, h_l);
-  PPBO_REQUIRE(ctx, d_Xc != nullptr, "d_Xc (the design rows in the caller's coordinates)");
-  cm = *m;
-  cm.kernel_id = PPBO_KERNEL_CAMPHOR;
-  cm.D = CAMPHOR_D;
-  cm.d_X = d_Xc;
-  cm.d_G = nullptr;
-  cm.d_Gt = nullptr;
-  cc = camphor_coef(h_l);
-  return 0;
-}
-
-extern "C" int ppbo_mean_ascent_camphor(ppbo_ctx* ctx, const ppbo_model* m, const double* d_starts, int K, int iters,
-                                        double tol, double* d_x, double* d_mu, int* d_iters, const double* d_Xc,
-                                        const double* h_l, void* stream) {
-  PPBO_ENTER(ctx);
-  ppbo_model cm;
-  CamphorCoef cc;
-  if (int rc = camphor_view(ctx, m, d_Xc, h_l, cm, cc)) return rc;
-  return mean_ascent_impl(ctx, &cm, d_starts, K, iters, tol, d_x, d_mu, d_iters, nullptr, stream, &cc);
 }
 
 extern "C" int ppbo_scale_points(ppbo_ctx* ctx, const double* d_in, int64_t M, int D, const double* h_scale,
@@ -1020,9 +1049,9 @@ extern "C" int ppbo_scale_points(ppbo_ctx* ctx, const double* d_in, int64_t M, i
 extern "C" int ppbo_mean_search(ppbo_ctx* ctx, const ppbo_model* m, const double* d_cand, int64_t M, int K, double sep,
                                 int iters, double tol, double* d_x, double* d_mu, int* h_found, void* stream) {
   PPBO_ENTER(ctx);
-  PPBO_REQUIRE(ctx, m != nullptr && m->d_X && m->d_alpha, "model X/alpha");
-  PPBO_REQUIRE(ctx, m->N > 0 && m->D > 0 && m->D <= 64, "model sizes (D<=64)");
-  PPBO_REQUIRE_KERNEL(ctx, m->kernel_id, m->D);
+  CoordMap co;
+  if (int rc = resolve_model_coords(ctx, m, co)) return rc;
+  PPBO_REQUIRE(ctx, co.kind == PPBO_COORDS_MODEL, "a model with a coordinate map: ppbo_mean_search_multi has that form");
   PPBO_REQUIRE(ctx, d_cand && d_x && d_mu && M > 0 && M < ((int64_t)1 << 31), "candidates / outputs");
   PPBO_REQUIRE(ctx, K > 0 && K <= 1024 && sep >= 0 && iters >= 0 && tol >= 0, "K (<= 1024) / sep / iters / tol");
   hipStream_t s = (hipStream_t)stream;
@@ -1036,7 +1065,7 @@ extern "C" int ppbo_mean_search(ppbo_ctx* ctx, const ppbo_model* m, const double
   sel.select(ctx, sep, d_cand, TrialCands{}, sel.counts, s);
   const KernParams p = make_kern_params(m->kernel_id, m->theta);
   if (int rc = ppbo_kernel_dispatch(ctx, m->kernel_id, [&](auto kid) {
-        return launch_mean_ascent<decltype(kid)::value>(ctx, m, p, sel.starts, sel.counts, K, iters, tol, d_x, d_mu, nullptr, s);
+        return launch_mean_ascent<decltype(kid)::value>(ctx, m, p, co, sel.starts, sel.counts, K, iters, tol, d_x, d_mu, nullptr, s);
       }))
     return rc;
   PPBO_LAUNCH_CHECK(ctx);
@@ -1078,16 +1107,16 @@ int launch_screen(const ppbo_model* m, const KernParams& p, const TrialCands& tc
   return 0;
 }
 
-static int mean_search_multi_impl(ppbo_ctx* ctx, const ppbo_model* m, const double* d_pool, int64_t M,
-                                  const double* h_shifts, int T, const double* d_extra, int E_rows,
-                                  const double* h_xprev, int K, double sep, int iters, double tol, int screen_fp32,
-                                  double* d_x, double* d_mu, const double* h_scale, void* stream,
-                                  const ppbo_model* emb = nullptr, const double* h_l = nullptr,
-                                  const CamphorCoef* cam = nullptr) {
+extern "C" int ppbo_mean_search_multi(ppbo_ctx* ctx, const ppbo_model* model, const double* d_pool, int64_t M,
+                                      const double* h_shifts, int T, const double* d_extra, int E_rows,
+                                      const double* h_xprev, int K, double sep, int iters, double tol, int screen_fp32,
+                                      double* d_x, double* d_mu, void* stream) {
   PPBO_ENTER(ctx);
-  PPBO_REQUIRE(ctx, m != nullptr && m->d_X && m->d_alpha, "model X/alpha");
-  PPBO_REQUIRE(ctx, m->N > 0 && m->D > 0 && m->D <= 64, "model sizes (D<=64)");
-  PPBO_REQUIRE_KERNEL(ctx, m->kernel_id, m->D);
+  CoordMap co;
+  if (int rc = resolve_model_coords(ctx, model, co)) return rc;
+  // m: the model in the caller's coordinates, where the search runs; emb (camphor): the embedded model, screened as SE
+  const ppbo_model* m = co.model;
+  const ppbo_model* emb = co.kind == PPBO_COORDS_CAMPHOR ? model : nullptr;
   PPBO_REQUIRE(ctx, d_pool && h_shifts && d_x && d_mu && M > 0 && E_rows >= 0 && M + E_rows + 1 < ((int64_t)1 << 31),
                "pool / shifts / extra points / outputs");
   const bool design = E_rows > 0 && !d_extra;
@@ -1095,14 +1124,13 @@ static int mean_search_multi_impl(ppbo_ctx* ctx, const ppbo_model* m, const doub
     PPBO_REQUIRE(ctx, E_rows == m->N, "d_extra = NULL stands for the model's N design points: E_rows must be N");
     d_extra = m->d_X;
   }
-  if (h_scale) PPBO_REQUIRE_SCALE(ctx, m, h_scale);
   const int E = E_rows + (h_xprev ? 1 : 0);
   PPBO_REQUIRE(ctx, T >= 1 && T <= 64 && K > 0 && K <= 1024 && sep >= 0 && iters >= 0 && tol >= 0, "T (<= 64) / K (<= 1024) / sep / iters / tol");
   hipStream_t s = (hipStream_t)stream;
   const int D = m->D;
   const long long Mt = M + E;
   // workspace: shifts[T][D] + xprev[D] ahead of the start selection's T score vectors; counts[T]
-  // (ARD: scale[D] + 1 / scale[D] and the design's rows in the caller's coordinates [N][D] in a slot of their own)
+  // (ARD: the design's rows in the caller's coordinates [N][D] in a slot of their own)
   StartSelection sel{Mt, T, D, K};
   if (!sel.alloc(ctx, (size_t)(T + 1) * D, T)) return (int)hipErrorOutOfMemory;
   double* shifts = sel.head;
@@ -1113,30 +1141,23 @@ static int mean_search_multi_impl(ppbo_ctx* ctx, const ppbo_model* m, const doub
   if (int rc = ppbo_upload_async(ctx, shifts, h_shifts, (size_t)T * D * sizeof(double), s)) return rc;
   if (h_xprev)
     if (int rc = ppbo_upload_async(ctx, xprev, h_xprev, (size_t)D * sizeof(double), s)) return rc;
-  double* d_scale = nullptr;
-  if (h_scale) {
-    // s and 1 / s in one upload; the design points (the model's scaled rows) are taken back to the caller's
-    // coordinates, x_i = x~_i / s, so that rotation, separation and box all live there
-    double* sc = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_SCALE_SEARCH,
-                                         (2 * (size_t)D + (design ? (size_t)m->N * D : 0)) * sizeof(double));
-    if (!sc) return (int)hipErrorOutOfMemory;
-    double hs[128];
-    for (int d = 0; d < D; ++d) { hs[d] = h_scale[d]; hs[D + d] = 1.0 / h_scale[d]; }
-    if (int rc = ppbo_upload_async(ctx, sc, hs, 2 * (size_t)D * sizeof(double), s)) return rc;
-    d_scale = sc;
-    if (design) {
-      double* xo = sc + 2 * D;
-      const int64_t n = (int64_t)m->N * D;
-      scale_points_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(m->d_X, n, D, sc + D, xo);
-      PPBO_LAUNCH_CHECK(ctx);
-      d_extra = xo;
-    }
+  if (int rc = co.upload(ctx, s)) return rc;
+  const double* d_scale = co.d_scale;
+  if (d_scale && design) {
+    // the design points (the model's scaled rows) are taken back to the caller's coordinates, x_i = x~_i / s, so that
+    // rotation, separation and box all live there
+    const int64_t n = (int64_t)m->N * D;
+    double* xo = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_SCALE_SEARCH, (size_t)n * sizeof(double));
+    if (!xo) return (int)hipErrorOutOfMemory;
+    scale_points_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(m->d_X, n, D, d_scale + D, xo);
+    PPBO_LAUNCH_CHECK(ctx);
+    d_extra = xo;
   }
   TrialCands tc;
   tc.pool = d_pool; tc.M = M; tc.shifts = shifts; tc.extra = d_extra; tc.xprev = h_xprev ? xprev : nullptr;
   tc.E_rows = E_rows; tc.E = E; tc.D = D;
   const KernParams p = make_kern_params(m->kernel_id, m->theta);
-  if (screen_fp32 && !d_scale && !emb) {
+  if (screen_fp32 && co.kind == PPBO_COORDS_MODEL) {
     // the trials in batches of <= 8 (bounds the partial sums: 8 x n_split x Mt doubles)
     const int blocks_x = (int)((Mt + SCR_T * SCR_CPT - 1) / (SCR_T * SCR_CPT));
     for (int t0 = 0; t0 < T; t0 += 8) {
@@ -1160,8 +1181,7 @@ static int mean_search_multi_impl(ppbo_ctx* ctx, const ppbo_model* m, const doub
     // what the one-trial entry does with the rows ppbo_shift_points leaves.  ARD: the rows are scaled to s (.) x first,
     // and the fp32 screening takes them as the extra points of a one-trial launch of mean_screen_kernel (which reads
     // extra points as they are), so that the kernel itself needs no scaled form
-    // camphor (emb: the embedded model, m its caller-coordinate view): the candidates are embedded and screened on
-    // the embedded model, as SE
+    // camphor: the candidates are embedded and screened on the embedded model, as SE
     double* rows = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_SEARCH_ROWS, (size_t)Mt * D * sizeof(double));
     if (!rows) return (int)hipErrorOutOfMemory;
     double* erows = rows;
@@ -1181,7 +1201,7 @@ static int mean_search_multi_impl(ppbo_ctx* ctx, const ppbo_model* m, const doub
       if (d_scale) scale_points_kernel<<<(unsigned)((nt * D + 255) / 256), 256, 0, s>>>(rows, nt * D, D, d_scale, rows);
       PPBO_LAUNCH_CHECK(ctx);
       if (emb)
-        if (int rc = ppbo_camphor_embed(ctx, rows, nt, h_l, erows, stream)) return rc;
+        if (int rc = ppbo_camphor_embed(ctx, rows, nt, co.h_coef, erows, stream)) return rc;
       if (screen_fp32) {
         TrialCands tr;
         tr.pool = erows; tr.M = 0; tr.shifts = shifts; tr.extra = erows; tr.E_rows = (int)nt; tr.E = (int)nt; tr.D = De;
@@ -1208,69 +1228,53 @@ static int mean_search_multi_impl(ppbo_ctx* ctx, const ppbo_model* m, const doub
   }
   sel.select(ctx, sep, nullptr, tc, sel.counts, s);
   PPBO_LAUNCH_CHECK(ctx);
-  // (d_scale is NULL for camphor-copper, cam for every other kernel)
   if (int rc = ppbo_kernel_dispatch(ctx, m->kernel_id, [&](auto kid) {
-        return launch_mean_ascent<decltype(kid)::value>(ctx, m, p, sel.starts, sel.counts, T * K, iters, tol, d_x, d_mu,
-                                                        nullptr, s, K, d_scale, cam);
+        return launch_mean_ascent<decltype(kid)::value>(ctx, m, p, co, sel.starts, sel.counts, T * K, iters, tol, d_x, d_mu,
+                                                        nullptr, s, K);
       }))
     return rc;
   PPBO_LAUNCH_CHECK(ctx);
   return 0;
 }
 
-extern "C" int ppbo_mean_search_multi(ppbo_ctx* ctx, const ppbo_model* m, const double* d_pool, int64_t M,
-                                      const double* h_shifts, int T, const double* d_extra, int E_rows,
-                                      const double* h_xprev, int K, double sep, int iters, double tol, int screen_fp32,
-                                      double* d_x, double* d_mu, void* stream) {
-  return mean_search_multi_impl(ctx, m, d_pool, M, h_shifts, T, d_extra, E_rows, h_xprev, K, sep, iters, tol, screen_fp32,
-                                d_x, d_mu, nullptr, stream);
+// the map of an RFF search: the identity, or the camphor basis over six caller coordinates
+static int resolve_rff_coords(ppbo_ctx* ctx, const ppbo_coords* coords, int D, CoordMap& co) {
+  PPBO_REQUIRE(ctx, !coords || coords->kind != PPBO_COORDS_SCALED, "coords: a scaled basis is a basis, pass W s");
+  return resolve_coords(ctx, coords, PPBO_KERNEL_SE, D, co);
 }
 
-extern "C" int ppbo_mean_search_multi_scaled(ppbo_ctx* ctx, const ppbo_model* m, const double* d_pool, int64_t M,
-                                             const double* h_shifts, int T, const double* d_extra, int E_rows,
-                                             const double* h_xprev, int K, double sep, int iters, double tol,
-                                             int screen_fp32, double* d_x, double* d_mu, const double* h_scale,
-                                             void* stream) {
-  if (!h_scale) { PPBO_ENTER(ctx); return ppbo_set_error(ctx, -1, "invalid argument: h_scale is NULL"); }
-  return mean_search_multi_impl(ctx, m, d_pool, M, h_shifts, T, d_extra, E_rows, h_xprev, K, sep, iters, tol, screen_fp32,
-                                d_x, d_mu, h_scale, stream);
+// the candidates a search scores: d_cand itself, or (camphor) its embedding at Dr = 11 columns in a workspace
+static int rff_score_rows(ppbo_ctx* ctx, const CoordMap& co, const double* d_cand, int64_t M, const double*& rows, int& Dr,
+                          void* stream) {
+  rows = d_cand;
+  Dr = co.D;
+  if (co.kind != PPBO_COORDS_CAMPHOR) return 0;
+  double* e = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_CAMPHOR_ROWS, (size_t)M * CAMPHOR_E * sizeof(double));
+  if (!e) return ppbo_set_error(ctx, (int)hipErrorOutOfMemory, "invalid argument: no workspace for the embedded candidates");
+  rows = e;
+  Dr = CAMPHOR_E;
+  return ppbo_camphor_embed(ctx, d_cand, M, co.h_coef, e, stream);
 }
 
-extern "C" int ppbo_mean_search_multi_camphor(ppbo_ctx* ctx, const ppbo_model* m, const double* d_pool, int64_t M,
-                                              const double* h_shifts, int T, const double* d_extra, int E_rows,
-                                              const double* h_xprev, int K, double sep, int iters, double tol,
-                                              int screen_fp32, double* d_x, double* d_mu, const double* d_Xc,
-                                              const double* h_l, void* stream) {
+extern "C" int ppbo_rff_search(ppbo_ctx* ctx, const double* d_cand, int64_t M, int D, const double* d_W, int F,
+                               const double* d_b, double sigma_f, const double* d_omega, const ppbo_coords* coords, int K,
+                               double sep, int iters, double tol, double* d_x, double* d_val, int* h_found, void* stream) {
   PPBO_ENTER(ctx);
-  ppbo_model cm;
-  CamphorCoef cc;
-  if (int rc = camphor_view(ctx, m, d_Xc, h_l, cm, cc)) return rc;
-  return mean_search_multi_impl(ctx, &cm, d_pool, M, h_shifts, T, d_extra, E_rows, h_xprev, K, sep, iters, tol, screen_fp32,
-                                d_x, d_mu, nullptr, stream, m, h_l, &cc);
-}
-
-// the single-sample RFF search: l = NULL the plain basis at D columns, else the camphor basis (d_cand in the caller's six
-// coordinates, scored on its embedding)
-static int rff_search_impl(ppbo_ctx* ctx, const double* d_cand, int64_t M, int D, const double* h_l, const double* d_W,
-                           int F, const double* d_b, double sigma_f, const double* d_omega, int K, double sep, int iters,
-                           double tol, double* d_x, double* d_val, int* h_found, void* stream) {
+  PPBO_REQUIRE(ctx, d_cand && d_W && d_b && d_omega && d_x && d_val, "null pointer");
+  PPBO_REQUIRE(ctx, M > 0 && M < ((int64_t)1 << 31) && D > 0 && D <= 64 && F > 0, "sizes (D <= 64)");
+  CoordMap co;
+  if (int rc = resolve_rff_coords(ctx, coords, D, co)) return rc;
   PPBO_REQUIRE(ctx, K > 0 && K <= 1024 && sep >= 0 && iters >= 0 && tol >= 0, "K (<= 1024) / sep / iters / tol");
   hipStream_t s = (hipStream_t)stream;
   StartSelection sel{M, 1, D, K};
   if (!sel.alloc(ctx, 0, 0)) return (int)hipErrorOutOfMemory;
-  const double* rows = d_cand;
-  int Dr = D;
-  if (h_l) {   // screening on the embedded candidates: the plain scorer at D = 11
-    double* e = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_CAMPHOR_ROWS, (size_t)M * CAMPHOR_E * sizeof(double));
-    if (!e) return (int)hipErrorOutOfMemory;
-    if (int rc = ppbo_camphor_embed(ctx, d_cand, M, h_l, e, stream)) return rc;
-    rows = e;
-    Dr = CAMPHOR_E;
-  }
+  const double* rows;
+  int Dr;
+  if (int rc = rff_score_rows(ctx, co, d_cand, M, rows, Dr, stream)) return rc;
   if (int rc = ppbo_rff_score(ctx, rows, M, Dr, d_W, F, d_b, sigma_f, d_omega, sel.scores, nullptr, nullptr, stream)) return rc;
   // start selection on the caller-coordinate rows: sep is in the caller's units
   sel.select(ctx, sep, d_cand, TrialCands{}, sel.counts, s);
-  if (int rc = launch_rff_ascent(ctx, d_W, F, D, h_l, d_b, d_omega, std::sqrt(2.0 * sigma_f * sigma_f / (double)F), sel.starts,
+  if (int rc = launch_rff_ascent(ctx, d_W, F, D, co, d_b, d_omega, std::sqrt(2.0 * sigma_f * sigma_f / (double)F), sel.starts,
                                  sel.counts, 0, K, iters, tol, d_x, d_val, s))
     return rc;
   PPBO_LAUNCH_CHECK(ctx);
@@ -1281,34 +1285,16 @@ static int rff_search_impl(ppbo_ctx* ctx, const double* d_cand, int64_t M, int D
   return 0;
 }
 
-extern "C" int ppbo_rff_search(ppbo_ctx* ctx, const double* d_cand, int64_t M, int D, const double* d_W, int F,
-                               const double* d_b, double sigma_f, const double* d_omega, int K, double sep, int iters,
-                               double tol, double* d_x, double* d_val, int* h_found, void* stream) {
+// ppbo_rff_search for S samples over one candidate set
+extern "C" int ppbo_rff_search_multi(ppbo_ctx* ctx, const double* d_cand, int64_t M, int D, const double* d_W, int F,
+                                     const double* d_b, double sigma_f, const double* d_omegas, const ppbo_coords* coords,
+                                     int S, int K, double sep, int iters, double tol, double* d_x, double* d_val,
+                                     int* d_found, void* stream) {
   PPBO_ENTER(ctx);
-  PPBO_REQUIRE(ctx, d_cand && d_W && d_b && d_omega && d_x && d_val, "null pointer");
-  PPBO_REQUIRE(ctx, M > 0 && M < ((int64_t)1 << 31) && D > 0 && D <= 64 && F > 0, "sizes (D <= 64)");
-  return rff_search_impl(ctx, d_cand, M, D, nullptr, d_W, F, d_b, sigma_f, d_omega, K, sep, iters, tol, d_x, d_val, h_found,
-                         stream);
-}
-
-extern "C" int ppbo_rff_search_camphor(ppbo_ctx* ctx, const double* d_cand, int64_t M, const double* h_l, const double* d_W,
-                                       int F, const double* d_b, double sigma_f, const double* d_omega, int K, double sep,
-                                       int iters, double tol, double* d_x, double* d_val, int* h_found, void* stream) {
-  PPBO_ENTER(ctx);
-  PPBO_REQUIRE(ctx, d_cand && d_W && d_b && d_omega && d_x && d_val, "null pointer");
-  PPBO_REQUIRE_CAMPHOR_L(ctx, h_l);
-  PPBO_REQUIRE(ctx, M > 0 && M < ((int64_t)1 << 31) && F > 0, "sizes");
-  return rff_search_impl(ctx, d_cand, M, CAMPHOR_D, h_l, d_W, F, d_b, sigma_f, d_omega, K, sep, iters, tol, d_x, d_val,
-                         h_found, stream);
-}
-
-// ppbo_rff_search(_camphor) for S samples over one candidate set: l = NULL the plain basis at D columns, else the camphor
-// basis (d_cand in the caller's six coordinates, scored on its embedding)
-static int rff_search_multi_impl(ppbo_ctx* ctx, const double* d_cand, int64_t M, int D, const double* h_l, const double* d_W,
-                                 int F, const double* d_b, double sigma_f, const double* d_omegas, int S, int K, double sep,
-                                 int iters, double tol, double* d_x, double* d_val, int* d_found, void* stream) {
   PPBO_REQUIRE(ctx, d_cand && d_W && d_b && d_omegas && d_x && d_val && d_found, "null pointer");
   PPBO_REQUIRE(ctx, M > 0 && M < ((int64_t)1 << 31) && D > 0 && D <= 64 && F > 0, "sizes (D <= 64)");
+  CoordMap co;
+  if (int rc = resolve_rff_coords(ctx, coords, D, co)) return rc;
   PPBO_REQUIRE(ctx, S > 0 && S <= PPBO_RFF_MULTI_MAX_S, "S (1 .. PPBO_RFF_MULTI_MAX_S samples)");
   PPBO_REQUIRE(ctx, K > 0 && K <= 1024 && sep >= 0 && iters >= 0 && tol >= 0, "K (<= 1024) / sep / iters / tol");
   hipStream_t s = (hipStream_t)stream;
@@ -1318,48 +1304,24 @@ static int rff_search_multi_impl(ppbo_ctx* ctx, const double* d_cand, int64_t M,
   if (!sel.alloc(ctx, 0, 0))
     return ppbo_set_error(ctx, (int)hipErrorOutOfMemory, "invalid argument: no workspace for %d samples of %lld candidates",
                           S, (long long)M);
-  const double* rows = d_cand;
-  int Dr = D;
-  if (h_l) {
-    double* e = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_CAMPHOR_ROWS, (size_t)M * CAMPHOR_E * sizeof(double));
-    if (!e) return ppbo_set_error(ctx, (int)hipErrorOutOfMemory, "invalid argument: no workspace for the embedded candidates");
-    if (int rc = ppbo_camphor_embed(ctx, d_cand, M, h_l, e, stream)) return rc;
-    rows = e;
-    Dr = CAMPHOR_E;
-  }
+  const double* rows;
+  int Dr;
+  if (int rc = rff_score_rows(ctx, co, d_cand, M, rows, Dr, stream)) return rc;
   if (int rc = ppbo_rff_score_multi(ctx, rows, M, Dr, d_W, F, d_b, sigma_f, d_omegas, S, sel.scores, stream)) return rc;
   sel.select(ctx, sep, d_cand, TrialCands{}, d_found, s);
   PPBO_LAUNCH_CHECK(ctx);
-  if (int rc = launch_rff_ascent(ctx, d_W, F, D, h_l, d_b, d_omegas, std::sqrt(2.0 * sigma_f * sigma_f / (double)F),
+  if (int rc = launch_rff_ascent(ctx, d_W, F, D, co, d_b, d_omegas, std::sqrt(2.0 * sigma_f * sigma_f / (double)F),
                                  sel.starts, d_found, S, K, iters, tol, d_x, d_val, s))
     return rc;
   PPBO_LAUNCH_CHECK(ctx);
   return 0;
 }
 
-extern "C" int ppbo_rff_search_multi(ppbo_ctx* ctx, const double* d_cand, int64_t M, int D, const double* d_W, int F,
-                                     const double* d_b, double sigma_f, const double* d_omegas, int S, int K, double sep,
-                                     int iters, double tol, double* d_x, double* d_val, int* d_found, void* stream) {
-  PPBO_ENTER(ctx);
-  return rff_search_multi_impl(ctx, d_cand, M, D, nullptr, d_W, F, d_b, sigma_f, d_omegas, S, K, sep, iters, tol, d_x, d_val,
-                               d_found, stream);
-}
-
-extern "C" int ppbo_rff_search_multi_camphor(ppbo_ctx* ctx, const double* d_cand, int64_t M, const double* h_l,
-                                             const double* d_W, int F, const double* d_b, double sigma_f,
-                                             const double* d_omegas, int S, int K, double sep, int iters, double tol,
-                                             double* d_x, double* d_val, int* d_found, void* stream) {
-  PPBO_ENTER(ctx);
-  PPBO_REQUIRE_CAMPHOR_L(ctx, h_l);
-  return rff_search_multi_impl(ctx, d_cand, M, CAMPHOR_D, h_l, d_W, F, d_b, sigma_f, d_omegas, S, K, sep, iters, tol, d_x,
-                               d_val, d_found, stream);
-}
-
 // ppbo_rff_search_multi for pathwise samples g_s = phi^T w_s + k(., X) v_s: the same three stages with the scoring launch
 // and the evaluator of the ascent replaced (ppbo_path_score_multi, PathEval)
 extern "C" int ppbo_path_search_multi(ppbo_ctx* ctx, int kernel_id, const double theta[3], const double* d_cand, int64_t M,
                                       int D, const double* d_W, int F, const double* d_b, const double* d_Wp,
-                                      const double* d_X, int N, const double* d_V, const double* h_scale, int S, int K,
+                                      const double* d_X, int N, const double* d_V, const ppbo_coords* coords, int S, int K,
                                       double sep, int iters, double tol, double* d_x, double* d_val, int* d_found,
                                       void* stream) {
   PPBO_ENTER(ctx);
@@ -1369,29 +1331,26 @@ extern "C" int ppbo_path_search_multi(ppbo_ctx* ctx, int kernel_id, const double
   PPBO_REQUIRE(ctx, K > 0 && K <= 1024 && sep >= 0 && iters >= 0 && tol >= 0, "K (<= 1024) / sep / iters / tol");
   PPBO_REQUIRE(ctx, kernel_id != PPBO_KERNEL_CAMPHOR && ppbo_kernel_id_valid(kernel_id),
                "kernel_id (a radial kernel: SE, RQ, Matern-5/2, Matern-3/2)");
-  if (h_scale)
-    for (int d = 0; d < D; ++d)
-      PPBO_REQUIRE(ctx, h_scale[d] > 0.0 && std::isfinite(h_scale[d]), "h_scale: positive finite values");
+  PPBO_REQUIRE(ctx, !coords || coords->kind != PPBO_COORDS_CAMPHOR, "coords: pathwise samples have no camphor form");
+  CoordMap co;
+  if (int rc = resolve_coords(ctx, coords, kernel_id, D, co)) return rc;
   hipStream_t s = (hipStream_t)stream;
   StartSelection sel{M, S, D, K};
   if (!sel.alloc(ctx, 0, 0))
     return ppbo_set_error(ctx, (int)hipErrorOutOfMemory, "invalid argument: no workspace for %d samples of %lld candidates",
                           S, (long long)M);
   // ARD: the scoring launch works in the model's coordinates -- the candidates scaled, the basis unscaled (w / s).(s x)
-  // = w.x -- in a slot of their own: s[D] | 1 / s[D] | cand s [M][D] | W / s [F][D]
-  const double *rows = d_cand, *Wm = d_W, *d_scale = nullptr;
-  if (h_scale) {
-    double* sc = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_SCALE_SEARCH, (2 * (size_t)D + ((size_t)M + F) * D) * sizeof(double));
-    if (!sc) return (int)hipErrorOutOfMemory;
-    double hs[128];
-    for (int d = 0; d < D; ++d) { hs[d] = h_scale[d]; hs[D + d] = 1.0 / h_scale[d]; }
-    if (int rc = ppbo_upload_async(ctx, sc, hs, 2 * (size_t)D * sizeof(double), s)) return rc;
-    double* cs = sc + 2 * D;
+  // = w.x -- in a slot of their own: cand s [M][D] | W / s [F][D]
+  const double *rows = d_cand, *Wm = d_W;
+  if (int rc = co.upload(ctx, s)) return rc;
+  if (co.d_scale) {
+    double* cs = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_SCALE_SEARCH, ((size_t)M + F) * D * sizeof(double));
+    if (!cs) return (int)hipErrorOutOfMemory;
     double* Ws = cs + (size_t)M * D;
-    scale_points_kernel<<<(unsigned)((M * D + 255) / 256), 256, 0, s>>>(d_cand, M * D, D, sc, cs);
-    scale_points_kernel<<<(unsigned)(((int64_t)F * D + 255) / 256), 256, 0, s>>>(d_W, (int64_t)F * D, D, sc + D, Ws);
+    scale_points_kernel<<<(unsigned)((M * D + 255) / 256), 256, 0, s>>>(d_cand, M * D, D, co.d_scale, cs);
+    scale_points_kernel<<<(unsigned)(((int64_t)F * D + 255) / 256), 256, 0, s>>>(d_W, (int64_t)F * D, D, co.d_scale + D, Ws);
     PPBO_LAUNCH_CHECK(ctx);
-    rows = cs; Wm = Ws; d_scale = sc;
+    rows = cs; Wm = Ws;
   }
   if (int rc = ppbo_path_score_multi(ctx, kernel_id, theta, rows, M, D, Wm, F, d_b, d_Wp, d_X, N, d_V, S, sel.scores, stream))
     return rc;
@@ -1401,7 +1360,7 @@ extern "C" int ppbo_path_search_multi(ppbo_ctx* ctx, int kernel_id, const double
   const KernParams p = make_kern_params(kernel_id, theta);
   const double amp = std::sqrt(2.0 * theta[2] * theta[2] / (double)F);
   if (int rc = ppbo_kernel_dispatch<true>(ctx, kernel_id, [&](auto kid) -> int {
-        return launch_path_ascent<decltype(kid)::value>(ctx, p, d_W, F, D, d_b, d_Wp, amp, d_X, N, d_V, d_scale, sel.starts,
+        return launch_path_ascent<decltype(kid)::value>(ctx, p, d_W, F, D, d_b, d_Wp, amp, d_X, N, d_V, co.d_scale, sel.starts,
                                                         d_found, S, K, iters, tol, d_x, d_val, s);
       }))
     return rc;

@@ -248,6 +248,13 @@ class Engine:
         md.kstar_fp32 = int(bool(kstar_fp32))
         md.d_Gt = 0
         md.form = post.form
+        # the coordinates post.X is in (ppbo_coords); md._coords keeps the host coefficients alive as long as md
+        if post.camphor is not None:
+            md._coords = _lib.coords(_lib.COORDS_CAMPHOR, post.camphor, post.Xc.data_ptr() if post.Xc is not None else None)
+            md.coords = md._coords
+        elif post.scale is not None:
+            md._coords = _lib.coords(_lib.COORDS_SCALED, post.scale)
+            md.coords = md._coords
         if md.d_G and post.form == FORM_NODE and N <= 1024 and post.kernel != "camphor_copper_kernel":
             # models the one-launch scoring kernel takes: its matrix-core loop reads G transposed -- formed ONCE per
             # posterior here (the library would otherwise do it in a workspace on every call)
@@ -698,29 +705,19 @@ class Engine:
         return mu, cov
 
     def mean_grad(self, post: Posterior, Xc):
-        """mu[M] and d mu / d x [M,D] at the rows of Xc (ppbo_mean_grad).  ARD: the gradient is taken back to the caller's
-        coordinates, d mu / d x_d = s_d d mu / d x~_d; camphor_copper_ard_kernel: through the embedding's Jacobian
-        (ppbo_mean_grad_camphor)."""
-        if post.camphor is not None:
-            Xc = self.dev(Xc)
-            if Xc.dim() != 2 or Xc.shape[1] != 6:
-                raise ValueError(f"points of shape {tuple(Xc.shape)} for a model of 6 dimensions")
-            M = Xc.shape[0]
-            md = self._model(post, False)
-            mu, grad = self.empty(M), self.empty(M, 6)
-            l = np.ascontiguousarray(post.camphor, dtype=np.float64)
-            rc = self.lib.ppbo_mean_grad_camphor(self.ctx, C.byref(md), _ptr(Xc), M, self._dptr(l), _ptr(mu), _ptr(grad),
-                                                 self._stream())
-            self._check(rc, "ppbo_mean_grad_camphor")
-            return mu, grad
-        Xc = self._points(post, Xc)
+        """mu[M] and d mu / d x [M,D] at the rows of Xc, in the caller's coordinates (ppbo_mean_grad reads the model's
+        coordinate map).  ARD: d mu / d x_d = s_d d mu / d x~_d; camphor_copper_ard_kernel: through the embedding's
+        Jacobian."""
+        Xc = self.dev(Xc)
+        if post.embedded:
+            Dm = post.X.shape[1] if post.camphor is None else 6
+            if Xc.dim() != 2 or Xc.shape[1] != Dm:
+                raise ValueError(f"points of shape {tuple(Xc.shape)} for a model of {Dm} dimensions")
         M, D = Xc.shape
         md = self._model(post, False)
         mu, grad = self.empty(M), self.empty(M, D)
         rc = self.lib.ppbo_mean_grad(self.ctx, C.byref(md), _ptr(Xc), M, _ptr(mu), _ptr(grad), self._stream())
         self._check(rc, "ppbo_mean_grad")
-        if post.scale is not None and M > 0:
-            self.scale_points(grad, post.scale, out=grad)
         return mu, grad
 
     def mean_search(self, post: Posterior, cand, K=32, sep=0.05, iters=100, tol=1e-9, sync=True):
@@ -778,20 +775,13 @@ class Engine:
         md = self._model(post, False)
         xs, mus = self.empty(T, K, D), self.empty(T, K)
         dp = C.POINTER(C.c_double)
-        args = (self.ctx, C.byref(md), _ptr(pool), M, sh.ctypes.data_as(dp), T, _ptr(ex_ptr), E,
-                xp.ctypes.data_as(dp) if xp is not None else None, int(K), float(sep), int(iters), float(tol),
-                int(bool(screen_fp32)), _ptr(xs), _ptr(mus))
-        if post.camphor is not None:     # the caller's coordinates; "design" = the caller's rows kept in post.Xc
-            l = np.ascontiguousarray(post.camphor, dtype=np.float64)
-            rc = self.lib.ppbo_mean_search_multi_camphor(*args, _ptr(post.Xc), self._dptr(l), self._stream())
-            self._check(rc, "ppbo_mean_search_multi_camphor")
-        elif post.scale is None:
-            rc = self.lib.ppbo_mean_search_multi(*args, self._stream())
-            self._check(rc, "ppbo_mean_search_multi")
-        else:       # everything in the caller's coordinates; "design" = the model's rows taken back to them
-            sc = np.ascontiguousarray(post.scale, dtype=np.float64)
-            rc = self.lib.ppbo_mean_search_multi_scaled(*args, self._dptr(sc), self._stream())
-            self._check(rc, "ppbo_mean_search_multi_scaled")
+        # under the model's coordinate map everything is in the caller's coordinates; "design" = the model's rows there
+        # (ARD: taken back to them; camphor: the caller's rows kept in post.Xc)
+        rc = self.lib.ppbo_mean_search_multi(self.ctx, C.byref(md), _ptr(pool), M, sh.ctypes.data_as(dp), T, _ptr(ex_ptr), E,
+                                             xp.ctypes.data_as(dp) if xp is not None else None, int(K), float(sep),
+                                             int(iters), float(tol), int(bool(screen_fp32)), _ptr(xs), _ptr(mus),
+                                             self._stream())
+        self._check(rc, "ppbo_mean_search_multi")
         return xs, mus
 
     def mean_ascent(self, post: Posterior, starts, iters=100, tol=1e-9):
@@ -800,22 +790,12 @@ class Engine:
         md = self._model(post, False)
         xs, mus = self.empty(K, D), self.empty(K)
         its = torch.zeros(K, dtype=torch.int32, device=self.device)
-        if post.camphor is not None:
-            if D != 6:
-                raise ValueError(f"mean_ascent: starts of shape {tuple(starts.shape)} for a model of 6 dimensions")
-            l = np.ascontiguousarray(post.camphor, dtype=np.float64)
-            rc = self.lib.ppbo_mean_ascent_camphor(self.ctx, C.byref(md), _ptr(starts), K, int(iters), float(tol), _ptr(xs),
-                                                   _ptr(mus), _ptr(its), _ptr(post.Xc), self._dptr(l), self._stream())
-            self._check(rc, "ppbo_mean_ascent_camphor")
-        elif post.scale is None:
-            rc = self.lib.ppbo_mean_ascent(self.ctx, C.byref(md), _ptr(starts), K, int(iters), float(tol), _ptr(xs), _ptr(mus),
-                                           _ptr(its), self._stream())
-            self._check(rc, "ppbo_mean_ascent")
-        else:       # starts, box and results in the caller's coordinates
-            sc = np.ascontiguousarray(post.scale, dtype=np.float64)
-            rc = self.lib.ppbo_mean_ascent_scaled(self.ctx, C.byref(md), _ptr(starts), K, int(iters), float(tol), _ptr(xs),
-                                                  _ptr(mus), _ptr(its), self._dptr(sc), self._stream())
-            self._check(rc, "ppbo_mean_ascent_scaled")
+        if post.camphor is not None and D != 6:
+            raise ValueError(f"mean_ascent: starts of shape {tuple(starts.shape)} for a model of 6 dimensions")
+        # starts, box and results in the caller's coordinates (the model's coordinate map)
+        rc = self.lib.ppbo_mean_ascent(self.ctx, C.byref(md), _ptr(starts), K, int(iters), float(tol), _ptr(xs), _ptr(mus),
+                                       _ptr(its), self._stream())
+        self._check(rc, "ppbo_mean_ascent")
         return xs, mus, its
 
     def shift_points(self, pool, shift, out=None):
@@ -930,6 +910,16 @@ class Engine:
         self._check(rc, "ppbo_randn")
         return out
 
+    @staticmethod
+    def _camphor_coords(what, ls):
+        """The `coords` argument of an RFF search: None (the identity) or the camphor map of the six length scales ls."""
+        if ls is None:
+            return None
+        l = np.ascontiguousarray(ls, dtype=np.float64).reshape(-1)
+        if l.size != 6:
+            raise ValueError(f"{what}: {l.size} length scales, 6 required")
+        return _lib.coords(_lib.COORDS_CAMPHOR, l)
+
     def _rff_search(self, what, cand, ls, W, b, sigma_f, omega, K, sep, iters, tol):
         cand, W, b, omega = self.dev(cand), self.dev(W), self.dev(b).reshape(-1), self.dev(omega).reshape(-1)
         if ls is None:
@@ -941,18 +931,11 @@ class Engine:
         F = self._rff_widths(what, D if ls is None else 11, W, b, omega)
         xs, vals = self.empty(K, D), self.empty(K)
         found = C.c_int(0)
-        if ls is None:
-            rc = self.lib.ppbo_rff_search(self.ctx, _ptr(cand), M, D, _ptr(W), F, _ptr(b), float(sigma_f), _ptr(omega),
-                                          int(K), float(sep), int(iters), float(tol), _ptr(xs), _ptr(vals), C.byref(found),
-                                          self._stream())
-        else:
-            l = np.ascontiguousarray(ls, dtype=np.float64).reshape(-1)
-            if l.size != 6:
-                raise ValueError(f"{what}: {l.size} length scales, 6 required")
-            rc = self.lib.ppbo_rff_search_camphor(self.ctx, _ptr(cand), M, self._dptr(l), _ptr(W), F, _ptr(b), float(sigma_f),
-                                                  _ptr(omega), int(K), float(sep), int(iters), float(tol), _ptr(xs), _ptr(vals),
-                                                  C.byref(found), self._stream())
-        self._check(rc, f"ppbo_{what}")
+        co = self._camphor_coords(what, ls)
+        rc = self.lib.ppbo_rff_search(self.ctx, _ptr(cand), M, D, _ptr(W), F, _ptr(b), float(sigma_f), _ptr(omega), co,
+                                      int(K), float(sep), int(iters), float(tol), _ptr(xs), _ptr(vals), C.byref(found),
+                                      self._stream())
+        self._check(rc, "ppbo_rff_search")
         n = found.value
         return xs[:n].cpu().numpy(), vals[:n].cpu().numpy()
 
@@ -962,9 +945,9 @@ class Engine:
         return self._rff_search("rff_search", cand, None, W, b, sigma_f, omega, K, sep, iters, tol)
 
     def rff_search_camphor(self, cand, ls, W, b, sigma_f, omega, K=32, sep=0.05, iters=200, tol=1e-10):
-        """rff_search for a camphor-copper basis (ppbo_rff_search_camphor): W [F, 11] acts on the embedding e(x) of the
-        six length scales ls; cand [M, 6], the box, sep and the refined maxima x[found, 6] are in the caller's
-        coordinates.  Returns x[found, 6], values[found] as NumPy arrays."""
+        """rff_search for a camphor-copper basis (ppbo_rff_search with the camphor coordinate map): W [F, 11] acts on the
+        embedding e(x) of the six length scales ls; cand [M, 6], the box, sep and the refined maxima x[found, 6] are in
+        the caller's coordinates.  Returns x[found, 6], values[found] as NumPy arrays."""
         return self._rff_search("rff_search_camphor", cand, ls, W, b, sigma_f, omega, K, sep, iters, tol)
 
     # ---- batches of posterior samples (S weight vectors per call) ---------------------------
@@ -1025,18 +1008,11 @@ class Engine:
         cand, W, b, omegas = self.dev(cand), self.dev(W), self.dev(b).reshape(-1), self.dev(omegas)
         xs, vals = self.empty(S, K, D), self.empty(S, K)
         found = torch.zeros(S, dtype=torch.int32, device=self.device)
-        if ls is None:
-            rc = self.lib.ppbo_rff_search_multi(self.ctx, _ptr(cand), M, D, _ptr(W), F, _ptr(b), float(sigma_f), _ptr(omegas),
-                                                S, int(K), float(sep), int(iters), float(tol), _ptr(xs), _ptr(vals),
-                                                _ptr(found), self._stream())
-        else:
-            l = np.ascontiguousarray(ls, dtype=np.float64).reshape(-1)
-            if l.size != 6:
-                raise ValueError(f"{what}: {l.size} length scales, 6 required")
-            rc = self.lib.ppbo_rff_search_multi_camphor(self.ctx, _ptr(cand), M, self._dptr(l), _ptr(W), F, _ptr(b),
-                                                        float(sigma_f), _ptr(omegas), S, int(K), float(sep), int(iters),
-                                                        float(tol), _ptr(xs), _ptr(vals), _ptr(found), self._stream())
-        self._check(rc, f"ppbo_{what}")
+        co = self._camphor_coords(what, ls)
+        rc = self.lib.ppbo_rff_search_multi(self.ctx, _ptr(cand), M, D, _ptr(W), F, _ptr(b), float(sigma_f), _ptr(omegas), co,
+                                            S, int(K), float(sep), int(iters), float(tol), _ptr(xs), _ptr(vals), _ptr(found),
+                                            self._stream())
+        self._check(rc, "ppbo_rff_search_multi")
         return xs.cpu().numpy(), vals.cpu().numpy(), found.cpu().numpy()
 
     def rff_search_multi(self, cand, W, b, sigma_f, omegas, K=32, sep=0.05, iters=200, tol=1e-10):
@@ -1047,8 +1023,8 @@ class Engine:
         return self._rff_search_multi("rff_search_multi", cand, D, None, W, b, sigma_f, omegas, K, sep, iters, tol)
 
     def rff_search_multi_camphor(self, cand, ls, W, b, sigma_f, omegas, K=32, sep=0.05, iters=200, tol=1e-10):
-        """rff_search_multi for a camphor-copper basis (ppbo_rff_search_multi_camphor): W [F, 11], cand [M, 6] and the
-        results x [S, K, 6] in the caller's coordinates."""
+        """rff_search_multi for a camphor-copper basis (ppbo_rff_search_multi with the camphor coordinate map): W [F, 11],
+        cand [M, 6] and the results x [S, K, 6] in the caller's coordinates."""
         return self._rff_search_multi("rff_search_multi_camphor", cand, 6, ls, W, b, sigma_f, omegas, K, sep, iters, tol)
 
     # ---- pathwise posterior samples g_s = phi^T w_s + k(., X) v_s -------------------------------------------
@@ -1095,16 +1071,15 @@ class Engine:
         M, D = cand.shape
         F, S, N, scale = self._path_widths("path_search_multi", D, W, b, Wp, V, X, kernel, theta, int(K))
         cand, W, b, X, Wp, V = self.dev(cand), self.dev(W), self.dev(b).reshape(-1), self.dev(X), self.dev(Wp), self.dev(V)
-        th, hs = theta, None
+        th, co = theta, None
         if scale is not None:
             X = self.scale_points(X, scale)
             th = (float(theta[0]), 1.0, float(theta[2]))
-            scale = np.ascontiguousarray(scale, dtype=np.float64)      # (kept alive until the call has returned)
-            hs = self._dptr(scale)
+            co = _lib.coords(_lib.COORDS_SCALED, scale)      # (keeps its copy of scale alive until the call has returned)
         xs, vals = self.empty(S, K, D), self.empty(S, K)
         found = torch.zeros(S, dtype=torch.int32, device=self.device)
         rc = self.lib.ppbo_path_search_multi(self.ctx, self._kid(kernel), self._theta(th), _ptr(cand), M, D, _ptr(W), F,
-                                             _ptr(b), _ptr(Wp), _ptr(X), N, _ptr(V), hs, S, int(K), float(sep), int(iters),
+                                             _ptr(b), _ptr(Wp), _ptr(X), N, _ptr(V), co, S, int(K), float(sep), int(iters),
                                              float(tol), _ptr(xs), _ptr(vals), _ptr(found), self._stream())
         self._check(rc, "ppbo_path_search_multi")
         return xs.cpu().numpy(), vals.cpu().numpy(), found.cpu().numpy()

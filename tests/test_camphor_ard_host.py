@@ -14,8 +14,9 @@ import evgrad_numpy as eg
 from conftest import ROOT
 from oracle import ppbo_oracle as orc
 
-ENTRIES = ("ppbo_camphor_embed", "ppbo_camphor_line_points", "ppbo_mean_grad_camphor",
-           "ppbo_mean_search_multi_camphor", "ppbo_mean_ascent_camphor")
+# the camphor entries, and those that read ppbo_model.coords (PPBO_COORDS_CAMPHOR)
+ENTRIES = ("ppbo_camphor_embed", "ppbo_camphor_line_points", "ppbo_mean_grad",
+           "ppbo_mean_search_multi", "ppbo_mean_ascent")
 PERIODIC = (0, 1, 3, 4, 5)
 
 
@@ -209,7 +210,7 @@ def test_entries_in_header_binding_map_and_library():
         assert re.search(r"PPBO_API int %s\(" % e, hdr), e
         assert e in _lib.SIGNATURES, e
         assert any(fnmatch.fnmatch(e, p) for p in pats), e
-    assert _lib.ABI_VERSION == 7
+    assert _lib.ABI_VERSION == 8
     assert "camphor_copper_ard_kernel" not in _lib.KERNEL_IDS        # no device kernel id: SE on embedded rows
     if not os.path.exists(_lib.LIB_PATH):
         pytest.fail("libppbo_hip.so is not built (build() runs before the suite)")

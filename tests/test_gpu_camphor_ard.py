@@ -259,8 +259,9 @@ def test_refusals(eng):
                                     eng._stream())
     assert rc < 0 and "overlap" in eng._err()
     md.D = 6
-    rc = eng.lib.ppbo_mean_grad_camphor(eng.ctx, C.byref(md), C.c_void_p(post.Xc.data_ptr()), 1, eng._dptr(SPREAD),
-                                        C.c_void_p(post.alpha.data_ptr()), C.c_void_p(post.X.data_ptr()), eng._stream())
+    assert md.coords.kind == 2 and md.coords.d_Xc == post.Xc.data_ptr()      # the camphor map, on a model that is not D = 11
+    rc = eng.lib.ppbo_mean_grad(eng.ctx, C.byref(md), C.c_void_p(post.Xc.data_ptr()), 1,
+                                C.c_void_p(post.alpha.data_ptr()), C.c_void_p(post.X.data_ptr()), eng._stream())
     assert rc < 0 and "invalid argument" in eng._err()
 
 

@@ -1,6 +1,6 @@
 """GPU: Hsampler with the RQ and camphor-copper bases -- Phi(X) on the device against the NumPy form, the weight-space
-terms and omega_MAP against the oracle, the maximiser of one sample (ppbo_rff_search for RQ, ppbo_rff_search_camphor
-for the camphor kernels, in the caller's coordinates), its argument checks, and the C5 cycle with camphor features."""
+terms and omega_MAP against the oracle, the maximiser of one sample (ppbo_rff_search: for RQ as it is, with the camphor
+coordinate map for the camphor kernels, in the caller's coordinates), its argument checks, and the C5 cycle with camphor features."""
 import ctypes as C
 import types
 
@@ -153,6 +153,7 @@ def test_camphor_return_xstar_for_dim(eng, name):
 
 
 def test_rff_search_camphor_rejects_bad_arguments(eng):
+    from ppbo_amd import _lib
     F, M = 64, 256
     rng = np.random.default_rng(15)
     cand, W, b, om = eng.dev(rng.random((M, 6))), eng.dev(rng.standard_normal((F, 11))), eng.dev(rng.random(F)), eng.dev(rng.standard_normal(F))
@@ -162,10 +163,10 @@ def test_rff_search_camphor_rejects_bad_arguments(eng):
     good = np.array([0.3, 0.3, 0.35, 0.3, 0.3, 0.3])
 
     def call(l=good, cand_p=cand, W_p=W, K=8, x_p=xs):
-        lp = l.ctypes.data_as(dp) if l is not None else None
+        co = _lib.Coords(_lib.COORDS_CAMPHOR, l.ctypes.data_as(dp) if l is not None else None, None)
         p = (lambda t: None if t is None else C.c_void_p(t.data_ptr()))
-        return eng.lib.ppbo_rff_search_camphor(eng.ctx, p(cand_p), M, lp, p(W_p), F, p(b), 0.5, p(om), K, 0.05, 10, 1e-10,
-                                               p(x_p), p(vals), C.byref(found), eng._stream())
+        return eng.lib.ppbo_rff_search(eng.ctx, p(cand_p), M, 6, p(W_p), F, p(b), 0.5, p(om), co, K, 0.05, 10, 1e-10,
+                                       p(x_p), p(vals), C.byref(found), eng._stream())
 
     assert call() == 0 and 0 < found.value <= 8
     for bad in (np.array([0.3, 0.3, -0.1, 0.3, 0.3, 0.3]), np.array([0.3, np.nan, 0.3, 0.3, 0.3, 0.3]),

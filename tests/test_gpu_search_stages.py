@@ -82,20 +82,16 @@ def _rff_scores(eng, rows, W, b, sf, omega):
 
 
 def _rff_search_raw(eng, cand, ls, W, b, sf, omega, K, sep, iters, tol):
-    """ppbo_rff_search / ppbo_rff_search_camphor with all K rows returned: x [K, D], val [K], found."""
+    """ppbo_rff_search (ls: with the camphor coordinate map) with all K rows returned: x [K, D], val [K], found."""
+    from ppbo_amd import _lib
     from ppbo_amd.engine import _ptr
     cand, W, b, omega = eng.dev(cand), eng.dev(W), eng.dev(b).reshape(-1), eng.dev(omega).reshape(-1)
     M, D = cand.shape
     xs, vals = torch.full((K, D), 7.0, dtype=torch.float64, device=eng.device), eng.empty(K)
     found = C.c_int(-1)
-    if ls is None:
-        rc = eng.lib.ppbo_rff_search(eng.ctx, _ptr(cand), M, D, _ptr(W), W.shape[0], _ptr(b), float(sf), _ptr(omega), int(K),
-                                     float(sep), int(iters), float(tol), _ptr(xs), _ptr(vals), C.byref(found), eng._stream())
-    else:
-        l = np.ascontiguousarray(ls, dtype=np.float64)
-        rc = eng.lib.ppbo_rff_search_camphor(eng.ctx, _ptr(cand), M, eng._dptr(l), _ptr(W), W.shape[0], _ptr(b), float(sf),
-                                             _ptr(omega), int(K), float(sep), int(iters), float(tol), _ptr(xs), _ptr(vals),
-                                             C.byref(found), eng._stream())
+    co = None if ls is None else _lib.coords(_lib.COORDS_CAMPHOR, ls)
+    rc = eng.lib.ppbo_rff_search(eng.ctx, _ptr(cand), M, D, _ptr(W), W.shape[0], _ptr(b), float(sf), _ptr(omega), co, int(K),
+                                 float(sep), int(iters), float(tol), _ptr(xs), _ptr(vals), C.byref(found), eng._stream())
     eng._check(rc, "ppbo_rff_search")
     return host(xs), host(vals), found.value
 

@@ -196,6 +196,7 @@ def test_sample_omegas(eng):
 
 # ---------------------------------------------------------------- 5. refusals
 def test_multi_refusals(eng):
+    from ppbo_amd import _lib
     rng = np.random.default_rng(40)
     M, D, F = 256, 6, 64
     cand, W, b, Om = rng.random((M, D)), rng.standard_normal((F, D)), rng.random(F), rng.standard_normal((3, F))
@@ -218,7 +219,7 @@ def test_multi_refusals(eng):
     p = (lambda t: None if t is None else C.c_void_p(t.data_ptr()))
 
     def search(S=3, K=8, Dv=D, cand_p=dc, x_p=xs, f_p=fnd):
-        return eng.lib.ppbo_rff_search_multi(eng.ctx, p(cand_p), M, Dv, p(dW), F, p(db), 0.5, p(dO), S, K, 0.05, 10, 1e-10,
+        return eng.lib.ppbo_rff_search_multi(eng.ctx, p(cand_p), M, Dv, p(dW), F, p(db), 0.5, p(dO), None, S, K, 0.05, 10, 1e-10,
                                              p(x_p), p(vals), p(f_p), eng._stream())
 
     assert search() == 0
@@ -234,8 +235,9 @@ def test_multi_refusals(eng):
     bad_l = np.array([0.3, 0.3, -0.1, 0.3, 0.3, 0.3])
     W11 = eng.dev(rng.standard_normal((F, 11)))
     for ll, S, K in ((bad_l, 3, 8), (l, 0, 8), (l, 3, 1025)):
-        rc = eng.lib.ppbo_rff_search_multi_camphor(eng.ctx, p(dc), M, ll.ctypes.data_as(dp), p(W11), F, p(db), 0.5, p(dO),
-                                                   S, K, 0.05, 10, 1e-10, p(xs), p(vals), p(fnd), eng._stream())
+        co = _lib.Coords(_lib.COORDS_CAMPHOR, ll.ctypes.data_as(dp), None)
+        rc = eng.lib.ppbo_rff_search_multi(eng.ctx, p(dc), M, 6, p(W11), F, p(db), 0.5, p(dO), co, S, K, 0.05, 10, 1e-10,
+                                           p(xs), p(vals), p(fnd), eng._stream())
         assert rc != 0 and "invalid argument" in eng._err()
     assert search() == 0                                # the context is still usable
     torch.cuda.synchronize()

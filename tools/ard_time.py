@@ -5,7 +5,7 @@
   C3 scoring step (N = 2048, D = 20, 65536 candidates, EI: K*, contraction, score, argmax)   wall clock of
       Engine.predict, synchronised; ARD adds one ppbo_scale_points pass over the candidates
   mu_star's device search at C3 (Engine.mean_search_multi: 3 trials over the 65536-row pool, the design and x_prev,
-      32 ascents per trial, fp32 screening)   wall clock; ARD = ppbo_mean_search_multi_scaled
+      32 ascents per trial, fp32 screening)   wall clock; ARD = ppbo_mean_search_multi on a PPBO_COORDS_SCALED model
   its ascent alone (Engine.mean_ascent from 96 fixed starts, 100 iterations at most)   wall clock
   one fit at C3 (Engine.gp_fit from the stored start)   wall clock; ARD adds the scaling of the design
 

@@ -3,7 +3,7 @@
 (SE, other, SE, other, ...) so that clock drift falls on both.
 
   C5 (tests/golden/c5.npz: N = 4096, D = 6, m = 31), F = 8192: camphor_copper_kernel features ([F, 11], embedded rows,
-     ppbo_rff_search_camphor) against SE features ([F, 6], ppbo_rff_search) at the same theta
+     ppbo_rff_search with the camphor coordinate map) against SE features ([F, 6], ppbo_rff_search) at the same theta
   C3 (tests/golden/c3.npz: N = 2048, D = 20), F = 4096: RQ features against SE features
 
   sample_xstar   Hsampler.sample_omega + return_xstar (score the rotated 65536-row pool plus the perturbed local maxima,
