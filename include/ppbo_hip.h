@@ -479,6 +479,39 @@ PPBO_API int ppbo_line_acq_xi(ppbo_ctx* ctx, const ppbo_model* model, const doub
                      const double* d_alpha, int alpha_per_line, int B, int G, double shrink, const double* d_z, int S,
                      double mustar, double jitter, double* d_ei, double* d_varmax, void* stream);
 
+/* ---- the answer to a query: choice probabilities over B groups of G points ------------------------------------------
+ * The likelihood is a choice model: on a query line the user marks the point they like best, and sum_Phi
+ * (src/gp_model.py:176-204) scores that answer as the marked point beating every other point of the line under noisy
+ * utilities.  The reference has no route to the prediction of such an answer; this extends ppbo_predict_pairs' reading
+ * of the likelihood from 2 items to G.  In draw s < S the user sees
+ *   u_g = f_g + noise_sd eps[s][g],   f = mu + L z[s],   L L' = cov + jitter I,
+ * with (mu, cov) the posterior mean and the symmetrised G x G posterior covariance of the group (the covariance
+ * ppbo_line_acq factors: prior block shrunk by `shrink`), and picks argmax_g u_g.  noise_sd = 0 (d_e may then be NULL)
+ * is the noise-free argmax of the posterior path; the likelihood's own noise is noise_sd = theta[0].
+ *   d_prob[B,G]   = count / S (double): the share of the S draws in which point g was picked
+ *   d_count[B,G]  (int32, may be NULL): the counts themselves; integer adds, so exact and independent of any order
+ *   d_choice[B,S] (int32, may be NULL): the point picked in draw s
+ * Rules: of equal values the LOWER index wins (np.argmax's rule); NaN never wins; a draw in which no value is a number
+ * (every u_g NaN or -inf) chooses -1 and counts nowhere, so the probabilities of its group sum to less than 1.  A group
+ * in which the mean of any point is NaN (a point with a NaN coordinate: its row of the covariance is no number either)
+ * chooses -1 in EVERY draw, all its counts 0; the other groups of the call are not touched.  d_choice and d_count do not
+ * depend on how the draws are spread over workgroups.
+ * d_z[S,G] and d_e[S,G] are shared by all groups (common random numbers), as d_z in ppbo_line_acq; ppbo_randn fills
+ * them.  The points are in the MODEL's coordinates, as ppbo_line_acq takes them, a line or G arbitrary points alike.
+ * G = 2: P(0 is picked) -> Phi(mu_d / sqrt(2 noise_sd^2 + var_d)) as S grows, ppbo_predict_pairs' p for the pair
+ * (a, b) = (point 0, point 1) at noise_sd = theta[0], up to the shrinkage of the prior block and the jitter.
+ * ppbo_line_choice_xi forms the points of line b on the device, {alpha[g] d_xi[b,:] + d_x[b,:]}, as ppbo_line_acq_xi.
+ * "invalid argument", nothing launched: a NULL model, d_grid (d_xi, d_x, d_alpha), d_z or d_prob; G outside 1 .. 128;
+ * B < 1 or S < 1; a negative or non-finite noise_sd or jitter; noise_sd > 0 with d_e == NULL; a model without d_G or
+ * Lambda. */
+PPBO_API int ppbo_line_choice(ppbo_ctx* ctx, const ppbo_model* model, const double* d_grid, int B, int G, double shrink,
+                     const double* d_z, const double* d_e, int S, double noise_sd, double jitter, double* d_prob,
+                     int* d_count, int* d_choice, void* stream);
+PPBO_API int ppbo_line_choice_xi(ppbo_ctx* ctx, const ppbo_model* model, const double* d_xi, const double* d_x,
+                        const double* d_alpha, int alpha_per_line, int B, int G, double shrink, const double* d_z,
+                        const double* d_e, int S, double noise_sd, double jitter, double* d_prob, int* d_count,
+                        int* d_choice, void* stream);
+
 
 /* standard normal draws for the Monte-Carlo acquisitions, generated on the device: d_out[n] = a pure function of
  * (seed, index) (Philox-4x32-10 + Box-Muller), i.e. reproducible and independent of the launch geometry.  Replaces

@@ -1036,28 +1036,13 @@ __global__ __launch_bounds__(256, (NT16 <= 5) ? 2 : 1) void line_cov_kernel(cons
   }
 }
 
-// Monte-Carlo part of EI / varmax on a line (acquisition.py:72-81, :170-178): f = mu + L z for S draws, max over the
-// line, statistics of the maxima.  grid = (lines, draw splits); one workgroup = one line x one slice of the draws.
-//   1. Cholesky of the G x G posterior covariance in LDS (every split of a line repeats it: 70 short steps, and the
-//      splits run side by side);
-//   2. F = Z L^T on the fp64 matrix cores: a wavefront takes 16 draws at a time (A fragments straight from the
-//      shared z[S][G], which stays in L2), one 16 x 16 tile of F per 16 grid points with mu as the accumulator's
-//      initial value and the contraction cut at the triangle's edge; the maximum over the line is an elementwise
-//      max over the tiles and one 16-lane reduction;
-//   3. partial sums (sum max(f - mustar, 0), sum f, sum f^2) per (line, split); mc_finish_kernel combines them.
-// Round 1-2's form (lane = draw, a scalar loop over the triangle with z re-read from memory) took 1.3 ms for 1200
-// draws of a 70-point line whatever the batch size; this one ~0.1 ms.
 constexpr int MC_MAXG16 = 128;
-__global__ __launch_bounds__(256) void line_mc_kernel(const double* __restrict__ mu, const double* __restrict__ cov,
-                                                      int G, const double* __restrict__ z, int S, double mustar,
-                                                      double jitter, int draws_per_split, double* __restrict__ part,
-                                                      const double* __restrict__ cov_parts = nullptr, int n_parts = 0,
-                                                      long long part_stride = 0, int parts_lower_only = 0) {
-  extern __shared__ __attribute__((aligned(16))) double sm[];
-  const int G16 = (G + 15) & ~15, ld = G16 + 2;
-  double* Lm = sm;                           // [G16][ld], rows / columns >= G zero
-  double* mus = sm + (size_t)G16 * ld;       // [G16], -inf beyond G: a padded grid point never is the maximum
-  double* red = mus + G16;                   // [3][4]
+// Step 1 of the Monte-Carlo kernels below, by the whole workgroup: the G x G posterior covariance of group blockIdx.x,
+// symmetrised, jitter on its diagonal, factored in LDS.  On return Lm[G16][ld] holds L (zeros above the diagonal and in
+// rows / columns >= G) and mus[G16] the group's mean (-inf beyond G); the last statement is a barrier.
+__device__ __forceinline__ void mc_factor_lds(double* Lm, double* mus, const double* mu, const double* cov, int G,
+                                              int G16, int ld, double jitter, const double* cov_parts, int n_parts,
+                                              long long part_stride, int parts_lower_only) {
   const double* c = cov + (size_t)blockIdx.x * G * G;
   const double* m = mu + (size_t)blockIdx.x * G;
   // cov_parts: the data term K*' Lambda K* + Y'Y as line_cov_kernel leaves it -- n_parts row-split slabs per line, the
@@ -1101,6 +1086,30 @@ __global__ __launch_bounds__(256) void line_mc_kernel(const double* __restrict__
     if (h > g) Lm[g * ld + h] = 0.0;
   }
   __syncthreads();
+}
+
+// Monte-Carlo part of EI / varmax on a line (acquisition.py:72-81, :170-178): f = mu + L z for S draws, max over the
+// line, statistics of the maxima.  grid = (lines, draw splits); one workgroup = one line x one slice of the draws.
+//   1. Cholesky of the G x G posterior covariance in LDS (every split of a line repeats it: 70 short steps, and the
+//      splits run side by side);
+//   2. F = Z L^T on the fp64 matrix cores: a wavefront takes 16 draws at a time (A fragments straight from the
+//      shared z[S][G], which stays in L2), one 16 x 16 tile of F per 16 grid points with mu as the accumulator's
+//      initial value and the contraction cut at the triangle's edge; the maximum over the line is an elementwise
+//      max over the tiles and one 16-lane reduction;
+//   3. partial sums (sum max(f - mustar, 0), sum f, sum f^2) per (line, split); mc_finish_kernel combines them.
+// Round 1-2's form (lane = draw, a scalar loop over the triangle with z re-read from memory) took 1.3 ms for 1200
+// draws of a 70-point line whatever the batch size; this one ~0.1 ms.
+__global__ __launch_bounds__(256) void line_mc_kernel(const double* __restrict__ mu, const double* __restrict__ cov,
+                                                      int G, const double* __restrict__ z, int S, double mustar,
+                                                      double jitter, int draws_per_split, double* __restrict__ part,
+                                                      const double* __restrict__ cov_parts = nullptr, int n_parts = 0,
+                                                      long long part_stride = 0, int parts_lower_only = 0) {
+  extern __shared__ __attribute__((aligned(16))) double sm[];
+  const int G16 = (G + 15) & ~15, ld = G16 + 2;
+  double* Lm = sm;                           // [G16][ld], rows / columns >= G zero
+  double* mus = sm + (size_t)G16 * ld;       // [G16], -inf beyond G: a padded grid point never is the maximum
+  double* red = mus + G16;                   // [3][4]
+  mc_factor_lds(Lm, mus, mu, cov, G, G16, ld, jitter, cov_parts, n_parts, part_stride, parts_lower_only);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, lr = lane & 15, lk = lane >> 4;
   const int s_beg = blockIdx.y * draws_per_split;
   int s_end = s_beg + draws_per_split;
@@ -1168,6 +1177,116 @@ __global__ __launch_bounds__(256) void mc_finish_kernel(const double* __restrict
   if (ei) ei[b] = e / S;
   const double mean = f1 / S;
   if (varmax) varmax[b] = f2 / S - mean * mean;
+}
+
+// The answer to a query: WHICH point of a group is the maximum of a draw, under the likelihood's noise (ppbo_line_choice).
+// line_mc_kernel's plan -- the same grid, factor, A fragments and MFMA chains -- with the other half of the draw kept:
+//   - the accumulator of (draw s, point g) starts at mu_g + noise_sd eps[s][g] (eps == NULL: at mu_g), so the chain
+//     leaves u = mu + L z + noise_sd eps; a lane's four loads of eps per tile are 16 consecutive g of one draw each:
+//     coalesced, and issued for all tiles before the first chain;
+//   - every lane keeps (value, point) of its best u over the tiles: strict >, tiles ascending, so of equal values the
+//     lower point stays and a NaN never enters; (-inf, -1) until something does -- a padded point (mu = -inf) never;
+//   - one 16-lane reduction of the pair, equal values to the lower point, gives the draw's choice (-1: no value of the
+//     draw was a number);
+//   - a group whose mean holds a NaN (a point with a NaN coordinate: its row of the covariance is no number either, and
+//     the factor would drop that point silently) chooses -1 in every draw;
+//   - a chosen point counts one in hist[G16] by an integer LDS add: exact, whatever the order.
+// A draw's row of F depends on no other row, so choice[s] does not depend on how the draws are cut into wavefronts,
+// workgroups or splits, and the counts are sums of integers.  part[(group, split)][G] <- hist; choice_finish_kernel adds
+// the splits.
+__global__ __launch_bounds__(256) void line_choice_kernel(const double* __restrict__ mu, const double* __restrict__ cov,
+                                                          int G, const double* __restrict__ z,
+                                                          const double* __restrict__ eps, int S, double noise_sd,
+                                                          double jitter, int draws_per_split, int* __restrict__ part,
+                                                          int* __restrict__ choice, const double* __restrict__ cov_parts,
+                                                          int n_parts, long long part_stride, int parts_lower_only) {
+  extern __shared__ __attribute__((aligned(16))) double sm[];
+  const int G16 = (G + 15) & ~15, ld = G16 + 2;
+  double* Lm = sm;                           // [G16][ld]
+  double* mus = sm + (size_t)G16 * ld;       // [G16]
+  int* hist = (int*)(mus + G16);             // [G16]
+  for (int g = threadIdx.x; g < G16; g += blockDim.x) hist[g] = 0;
+  mc_factor_lds(Lm, mus, mu, cov, G, G16, ld, jitter, cov_parts, n_parts, part_stride, parts_lower_only);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, lr = lane & 15, lk = lane >> 4;
+  const int s_beg = blockIdx.y * draws_per_split;
+  int s_end = s_beg + draws_per_split;
+  if (s_end > S) s_end = S;
+  const int nj = G16 >> 4;
+  bool poisoned = false;                                              // every lane reads the same word: a broadcast
+  for (int g = 0; g < G; ++g) poisoned |= mus[g] != mus[g];
+  for (int s0 = s_beg + 16 * wave; s0 < s_end; s0 += 64) {
+    // A fragments of the 16 draws s0 .. s0+15: lane (lr, lk) holds z[s0 + lr][4 kk + lk]
+    double az[MC_MAXG16 / 4];
+    const int sr = s0 + lr;
+    const double* zr = z + (size_t)(sr < s_end ? sr : s_beg) * G;
+#pragma unroll
+    for (int kk = 0; kk < MC_MAXG16 / 4; ++kk) {
+      const int k = 4 * kk + lk;
+      az[kk] = (kk < (G16 >> 2) && k < G) ? zr[k] : 0.0;
+    }
+    // the noise of this lane's (draw, point) pairs, all tiles at once: the loads are in flight under the first chains
+    double ev[MC_MAXG16 / 16][4];
+#pragma unroll
+    for (int j = 0; j < MC_MAXG16 / 16; ++j) {
+      if (j >= nj) break;
+      const int g = 16 * j + lr;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int sd = s0 + lk + 4 * r;
+        ev[j][r] = (eps && g < G && sd < s_end) ? eps[(size_t)sd * G + g] : 0.0;
+      }
+    }
+    double bv[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+    int bi[4] = {-1, -1, -1, -1};
+#pragma unroll
+    for (int j = 0; j < MC_MAXG16 / 16; ++j) {                        // unrolled: the triangle's edge is a constant per j
+      if (j >= nj) break;
+      const int g = 16 * j + lr;
+      const double mg = mus[g];
+      // acc[r] belongs to draw s0 + lk + 4 r and point g
+      double4_t acc;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) acc[r] = mg + noise_sd * ev[j][r];     // no noise: + 0
+      const double* lrow = Lm + (size_t)g * ld + lk;                  // B operand: L^T[k][g] = L[g][k]
+#pragma unroll
+      for (int kk = 0; kk < 4 * (j + 1); ++kk) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(az[kk], lrow[4 * kk], acc, 0, 0, 0);
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        if (acc[r] > bv[r]) { bv[r] = acc[r]; bi[r] = g; }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      double v = bv[r];
+      int i = bi[r];
+#pragma unroll
+      for (int msk = 1; msk < 16; msk <<= 1) {
+        const double ov = __shfl_xor(v, msk, 64);
+        const int oi = __shfl_xor(i, msk, 64);
+        if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
+      }
+      if (poisoned) i = -1;
+      const int sd = s0 + lk + 4 * r;
+      if (lr == 0 && sd < s_end) {
+        if (choice) choice[(size_t)blockIdx.x * S + sd] = i;
+        if (i >= 0) atomicAdd(&hist[i], 1);
+      }
+    }
+  }
+  __syncthreads();
+  int* o = part + ((size_t)blockIdx.x * gridDim.y + blockIdx.y) * G;
+  for (int g = threadIdx.x; g < G; g += blockDim.x) o[g] = hist[g];
+}
+
+// prob = count / S and the counts themselves from the per-split histograms, added in split order
+__global__ __launch_bounds__(256) void choice_finish_kernel(const int* __restrict__ part, int n, int G, int nsplit, int S,
+                                                            double* __restrict__ prob, int* __restrict__ count) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;      // (group, point)
+  if (e >= n) return;
+  const int b = e / G, g = e - b * G;
+  int c = 0;
+  for (int k = 0; k < nsplit; ++k) c += part[((size_t)b * nsplit + k) * G + g];
+  prob[e] = (double)c / (double)S;
+  if (count) count[e] = c;
 }
 
 // Standard normal draws for the Monte-Carlo acquisitions, generated where they are used (4800 x 70 draws cost the host
@@ -1679,10 +1798,21 @@ __global__ __launch_bounds__(256) void line_grid_kernel(const double* __restrict
   grid[e] = a * xi[(size_t)b * D + d] + x[(size_t)b * D + d];
 }
 
-// EI / varmax of B lines whose grid points are either given (d_grid) or formed on the device from (xi, x, alpha)
+// what ppbo_line_choice asks of the draws in place of EI / varmax: the chosen point of every draw, counted
+struct LineChoice {
+  const double* d_e;   // [S,G] or NULL
+  double noise_sd;
+  double* d_prob;      // [B,G]
+  int* d_count;        // [B,G] or NULL
+  int* d_choice;       // [B,S] or NULL
+};
+
+// EI / varmax of B lines whose grid points are either given (d_grid) or formed on the device from (xi, x, alpha); with
+// `ch` the choice probabilities of the same B groups instead (everything before the Monte-Carlo launch is shared)
 int line_acq_impl(ppbo_ctx* ctx, const ppbo_model* model, const double* d_grid, const double* d_xi, const double* d_x,
                   const double* d_alpha, int alpha_per_line, int B, int G, double shrink, const double* d_z, int S,
-                  double mustar, double jitter, double* d_ei, double* d_varmax, hipStream_t s) {
+                  double mustar, double jitter, double* d_ei, double* d_varmax, hipStream_t s,
+                  const LineChoice* ch = nullptr) {
   if (int rc = check_model(ctx, model)) return rc;
   PPBO_REQUIRE(ctx, (d_grid || (d_xi && d_x && d_alpha)) && d_z && B > 0 && G > 0 && G <= 128 && S > 0,
                "line arguments (G <= 128)");
@@ -1735,15 +1865,22 @@ int line_acq_impl(ppbo_ctx* ctx, const ppbo_model* model, const double* d_grid, 
   double* cov_parts = cov + (size_t)Bc_max * G * G;
   const int G16 = (G + 15) & ~15;
   const size_t mc_lds = ((size_t)G16 * (G16 + 2) + G16 + 16) * sizeof(double);   // G = 128: 134 KB of the CU's 160 KB
-  if (mc_lds > 64 * 1024) ppbo_lds_limit(ctx, (const void*)line_mc_kernel, (128 * 130 + 128 + 16) * (int)sizeof(double));
+  // the choice kernel: the same factor and mean, then its histogram (G = 128: 512 B more)
+  const size_t ch_lds = ((size_t)G16 * (G16 + 2) + G16) * sizeof(double) + (size_t)G16 * sizeof(int);
+  if (!ch && mc_lds > 64 * 1024) ppbo_lds_limit(ctx, (const void*)line_mc_kernel, (128 * 130 + 128 + 16) * (int)sizeof(double));
+  if (ch && ch_lds > 64 * 1024)
+    ppbo_lds_limit(ctx, (const void*)line_choice_kernel, (128 * 130 + 128) * (int)sizeof(double) + 128 * (int)sizeof(int));
   // draws of a line spread over several workgroups when the batch alone does not fill the chip (>= 64 draws each)
   int nsplit = (2 * 256 + Bc_max - 1) / Bc_max;
   if (nsplit > (S + 63) / 64) nsplit = (S + 63) / 64;
   if (nsplit < 1) nsplit = 1;
   const int draws_per_split = (((S + nsplit - 1) / nsplit) + 15) & ~15;
   nsplit = (S + draws_per_split - 1) / draws_per_split;
-  double* mc_part = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_SMALL, (size_t)Bc_max * nsplit * 3 * sizeof(double));
-  if (!mc_part) return (int)hipErrorOutOfMemory;
+  // per-(line, split) partial results: three sums, or a histogram of G counts
+  void* mc_ws = ppbo_workspace(ctx, ppbo_ctx::WS_SMALL,
+                               (size_t)Bc_max * nsplit * (ch ? (size_t)G * sizeof(int) : 3 * sizeof(double)));
+  if (!mc_ws) return (int)hipErrorOutOfMemory;
+  double* mc_part = (double*)mc_ws;
   for (int b0 = 0; b0 < B; b0 += Bc_max) {
     const int Bc = (B - b0 < Bc_max) ? (B - b0) : Bc_max;
     const int M = Bc * G;
@@ -1812,6 +1949,20 @@ int line_acq_impl(ppbo_ctx* ctx, const ppbo_model* model, const double* d_grid, 
       }
 #undef LC_LAUNCH
     }
+    if (ch) {
+      {
+        PpboProfScope pf(ctx, ppbo_ctx::PF_LINE_MC, s);
+        line_choice_kernel<<<dim3(Bc, nsplit), 256, ch_lds, s>>>(
+            mu, cov, G, d_z, ch->d_e, S, ch->noise_sd, jitter, draws_per_split, (int*)mc_ws,
+            ch->d_choice ? ch->d_choice + (size_t)b0 * S : nullptr, cov_parts, cov_splits, (long long)Bc_max * G * G,
+            sym ? 1 : 0);
+      }
+      choice_finish_kernel<<<(M + 255) / 256, 256, 0, s>>>((const int*)mc_ws, M, G, nsplit, S,
+                                                           ch->d_prob + (size_t)b0 * G,
+                                                           ch->d_count ? ch->d_count + (size_t)b0 * G : nullptr);
+      PPBO_LAUNCH_CHECK(ctx);
+      continue;
+    }
     {
       PpboProfScope pf(ctx, ppbo_ctx::PF_LINE_MC, s);
       line_mc_kernel<<<dim3(Bc, nsplit), 256, mc_lds, s>>>(mu, cov, G, d_z, S, mustar, jitter, draws_per_split, mc_part,
@@ -1821,6 +1972,15 @@ int line_acq_impl(ppbo_ctx* ctx, const ppbo_model* model, const double* d_grid, 
                                                       d_varmax ? d_varmax + b0 : nullptr);
     PPBO_LAUNCH_CHECK(ctx);
   }
+  return 0;
+}
+
+// the refusals of the choice entries that line_acq_impl does not make itself
+int choice_args(ppbo_ctx* ctx, const double* d_e, double noise_sd, double jitter, const double* d_prob) {
+  PPBO_REQUIRE(ctx, d_prob != nullptr, "d_prob");
+  PPBO_REQUIRE(ctx, noise_sd >= 0.0 && noise_sd <= 1.79769313486231570815e308, "noise_sd (finite, >= 0)");
+  PPBO_REQUIRE(ctx, jitter >= 0.0 && jitter <= 1.79769313486231570815e308, "jitter (finite, >= 0)");
+  PPBO_REQUIRE(ctx, noise_sd == 0.0 || d_e != nullptr, "noise_sd > 0 needs the draws d_e");
   return 0;
 }
 
@@ -1844,6 +2004,29 @@ int ppbo_line_acq_xi(ppbo_ctx* ctx, const ppbo_model* model, const double* d_xi,
   PPBO_REQUIRE(ctx, d_xi && d_x && d_alpha, "xi / x / alpha");
   return line_acq_impl(ctx, model, nullptr, d_xi, d_x, d_alpha, alpha_per_line != 0, B, G, shrink, d_z, S, mustar,
                        jitter, d_ei, d_varmax, (hipStream_t)stream);
+}
+
+int ppbo_line_choice(ppbo_ctx* ctx, const ppbo_model* model, const double* d_grid, int B, int G, double shrink,
+                     const double* d_z, const double* d_e, int S, double noise_sd, double jitter, double* d_prob,
+                     int* d_count, int* d_choice, void* stream) {
+  PPBO_ENTER(ctx);
+  PPBO_REQUIRE(ctx, d_grid != nullptr, "d_grid");
+  if (int rc = choice_args(ctx, d_e, noise_sd, jitter, d_prob)) return rc;
+  const LineChoice ch{noise_sd > 0.0 ? d_e : nullptr, noise_sd, d_prob, d_count, d_choice};
+  return line_acq_impl(ctx, model, d_grid, nullptr, nullptr, nullptr, 0, B, G, shrink, d_z, S, 0.0, jitter, nullptr,
+                       nullptr, (hipStream_t)stream, &ch);
+}
+
+int ppbo_line_choice_xi(ppbo_ctx* ctx, const ppbo_model* model, const double* d_xi, const double* d_x,
+                        const double* d_alpha, int alpha_per_line, int B, int G, double shrink, const double* d_z,
+                        const double* d_e, int S, double noise_sd, double jitter, double* d_prob, int* d_count,
+                        int* d_choice, void* stream) {
+  PPBO_ENTER(ctx);
+  PPBO_REQUIRE(ctx, d_xi && d_x && d_alpha, "xi / x / alpha");
+  if (int rc = choice_args(ctx, d_e, noise_sd, jitter, d_prob)) return rc;
+  const LineChoice ch{noise_sd > 0.0 ? d_e : nullptr, noise_sd, d_prob, d_count, d_choice};
+  return line_acq_impl(ctx, model, nullptr, d_xi, d_x, d_alpha, alpha_per_line != 0, B, G, shrink, d_z, S, 0.0, jitter,
+                       nullptr, nullptr, (hipStream_t)stream, &ch);
 }
 
 int ppbo_randn(ppbo_ctx* ctx, uint64_t seed, double* d_out, int64_t n, void* stream) {

@@ -858,6 +858,105 @@ class Engine:
         self._check(rc, "ppbo_line_acq_xi")
         return ei, vm
 
+    @staticmethod
+    def _choice_groups(what, post: Posterior, B, G, Dp):
+        """B groups of G points of width Dp, as shapes alone decide it."""
+        D = 6 if post.camphor is not None else post.X.shape[1]
+        if Dp != D:
+            raise ValueError(f"{what}: points of width {Dp} for a model of {D} dimensions")
+        if B < 1 or not 1 <= G <= 128:
+            raise ValueError(f"{what}: {B} groups of {G} points (B >= 1 and 1 <= G <= 128 are required)")
+
+    @staticmethod
+    def _choice_draws(what, post: Posterior, G, z, e, noise_sd, jitter):
+        """The refusals of line_choice / line_choice_xi that the draws and the two numbers decide (before anything reaches
+        the device): returns (S, noise_sd) with noise_sd = theta[0] where None was given."""
+        sz = tuple(np.shape(z))
+        if len(sz) != 2 or sz[1] != G or sz[0] < 1:
+            raise ValueError(f"{what}: draws z of shape {sz} for groups of {G} points ([S, {G}] with S >= 1 is required)")
+        if noise_sd is None:
+            noise_sd = float(post.theta[0])
+        noise_sd, jitter = float(noise_sd), float(jitter)
+        if not (np.isfinite(noise_sd) and noise_sd >= 0.0 and np.isfinite(jitter) and jitter >= 0.0):
+            raise ValueError(f"{what}: noise_sd = {noise_sd} and jitter = {jitter} must be finite and >= 0")
+        if e is None:
+            if noise_sd > 0.0:
+                raise ValueError(f"{what}: noise_sd = {noise_sd} > 0 needs the noise draws e [S, G]")
+        elif tuple(np.shape(e)) != sz:
+            raise ValueError(f"{what}: noise draws e of shape {tuple(np.shape(e))} beside z of shape {sz}")
+        return sz[0], noise_sd
+
+    def _choice_out(self, B, G, S, want_count, want_choice):
+        prob = self.empty(B, G)
+        count = torch.empty(B, G, dtype=torch.int32, device=self.device) if want_count else None
+        choice = torch.empty(B, S, dtype=torch.int32, device=self.device) if want_choice else None
+        return prob, count, choice
+
+    def line_choice(self, post: Posterior, grid, z, e=None, noise_sd=None, shrink=SHRINKAGE, jitter=0.0,
+                    want_count=False, want_choice=False):
+        """The answer to a query (ppbo_line_choice): for B groups of G <= 128 points grid[B, G, D] in the caller's
+        coordinates -- lines or arbitrary items -- the probability prob[b, g] that point g is the one picked, i.e. the
+        share of the S draws u = mu + L z[s] + noise_sd e[s] whose maximum it is (ties to the lower index; -1 and no count
+        for a draw without a number).  z, e: [S, G], shared by all groups; noise_sd = None: theta[0], the likelihood's
+        noise; e = None with noise_sd = 0: the noise-free argmax of the posterior path.  Returns the device tensors
+        dict(prob, count, choice) (count [B, G] and choice [B, S] int32, None where not asked for)."""
+        sg = tuple(np.shape(grid))
+        if len(sg) != 3:
+            raise ValueError(f"line_choice: the points must be [B, G, D] (got {sg})")
+        B, G = sg[:2]
+        self._choice_groups("line_choice", post, B, G, sg[2])
+        S, noise_sd = self._choice_draws("line_choice", post, G, z, e, noise_sd, jitter)
+        grid = self.dev(grid)
+        if post.embedded:
+            grid = self._points(post, grid.reshape(B * G, grid.shape[2]))
+            grid = grid.reshape(B, G, grid.shape[1])
+        return self._line_choice(post, grid, self.dev(z), None if e is None else self.dev(e), noise_sd, shrink, jitter,
+                                 want_count, want_choice)
+
+    def _line_choice(self, post, grid, z, e, noise_sd, shrink, jitter, want_count, want_choice):
+        """ppbo_line_choice on a device grid [B, G, D'] that is already in the rows' coordinates."""
+        B, G = grid.shape[:2]
+        S = z.shape[0]
+        md = self._model(post, True)
+        prob, count, choice = self._choice_out(B, G, S, want_count, want_choice)
+        rc = self.lib.ppbo_line_choice(self.ctx, C.byref(md), _ptr(grid), B, G, float(shrink), _ptr(z), _ptr(e), S,
+                                       float(noise_sd), float(jitter), _ptr(prob), _ptr(count), _ptr(choice),
+                                       self._stream())
+        self._check(rc, "ppbo_line_choice")
+        return dict(prob=prob, count=count, choice=choice)
+
+    def line_choice_xi(self, post: Posterior, xis, xs, alphas, z, e=None, noise_sd=None, shrink=SHRINKAGE, jitter=0.0,
+                       want_count=False, want_choice=False):
+        """line_choice on the B lines {alpha * xis[b] + xs[b]} (ppbo_line_choice_xi), the points formed on the device as
+        line_acq_xi forms them: alphas [G] (shared) or [B, G]; ARD through the scaled (xi, x), camphor_copper_ard_kernel
+        through its embedded grid (ppbo_camphor_line_points)."""
+        sxi, sx, sa = tuple(np.shape(xis)), tuple(np.shape(xs)), tuple(np.shape(alphas))
+        if len(sxi) != 2 or sx != sxi:
+            raise ValueError(f"line_choice_xi: xis and xs must both be [B, D] (got {sxi} and {sx})")
+        if len(sa) not in (1, 2) or (len(sa) == 2 and sa[0] != sxi[0]):
+            raise ValueError(f"line_choice_xi: abscissae must be [G] or [B, G] (got {sa} for {sxi[0]} lines)")
+        B, G = sxi[0], sa[-1]
+        self._choice_groups("line_choice_xi", post, B, G, sxi[1])
+        S, noise_sd = self._choice_draws("line_choice_xi", post, G, z, e, noise_sd, jitter)
+        xis, xs, alphas, z = self.dev(xis), self.dev(xs), self.dev(alphas), self.dev(z)
+        e = None if e is None else self.dev(e)
+        per_line = alphas.dim() == 2
+        if post.camphor is not None:
+            grid = self.empty(B, G, 11)
+            l = np.ascontiguousarray(post.camphor, dtype=np.float64)
+            rc = self.lib.ppbo_camphor_line_points(self.ctx, _ptr(xis), _ptr(xs), _ptr(alphas), int(per_line), B, G,
+                                                   self._dptr(l), _ptr(grid), self._stream())
+            self._check(rc, "ppbo_camphor_line_points")
+            return self._line_choice(post, grid, z, e, noise_sd, shrink, jitter, want_count, want_choice)
+        xis, xs = self._points(post, xis), self._points(post, xs)
+        md = self._model(post, True)
+        prob, count, choice = self._choice_out(B, G, S, want_count, want_choice)
+        rc = self.lib.ppbo_line_choice_xi(self.ctx, C.byref(md), _ptr(xis), _ptr(xs), _ptr(alphas), int(per_line), B, G,
+                                          float(shrink), _ptr(z), _ptr(e), S, float(noise_sd), float(jitter), _ptr(prob),
+                                          _ptr(count), _ptr(choice), self._stream())
+        self._check(rc, "ppbo_line_choice_xi")
+        return dict(prob=prob, count=count, choice=choice)
+
     # ---- RFF -------------------------------------------------------------------------
     @staticmethod
     def _rff_widths(what, D, W, b, omega=None):

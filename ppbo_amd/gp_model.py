@@ -860,21 +860,77 @@ class GPModel:
             raise RuntimeError("update_model()/update_fMAP() must run before predictions")
         return self._post_mean
 
-    def mu_Sigma_pred(self, X_pred):
+    def _var_post(self):
+        """The posterior with its variance operator, which every prediction beyond the mean needs."""
         if self._post is None or self._post.G is None:
             raise RuntimeError("posterior covariance unavailable (skipped during initialisation, gp_model.py:106-107)")
-        mu, cov = self.eng.predict_cov(self._post, np.atleast_2d(X_pred), self.COVARIANCE_SHRINKAGE)
+        return self._post
+
+    def mu_Sigma_pred(self, X_pred):
+        post = self._var_post()
+        mu, cov = self.eng.predict_cov(post, np.atleast_2d(X_pred), self.COVARIANCE_SHRINKAGE)
         return mu.cpu().numpy(), cov.cpu().numpy()
 
     def preference_pred(self, Xa, Xb):
         """(mu_d, var_d, p) as NumPy arrays for the duels (Xa[i], Xb[i]): the posterior mean and variance of
         f(a) - f(b) and p = P(a > b) = Phi(mu_d / sqrt(2 sigma^2 + var_d)) (ppbo_predict_pairs; no reference
         counterpart).  Host or device input; one pair may be given as two 1-D vectors."""
-        if self._post is None or self._post.G is None:
-            raise RuntimeError("posterior covariance unavailable (skipped during initialisation, gp_model.py:106-107)")
+        post = self._var_post()
         Xa, Xb = (x if x.dim() == 2 else x.reshape(1, -1) for x in (self.eng.dev(Xa), self.eng.dev(Xb)))
-        out = self.eng.predict_pairs(self._post, Xa, Xb, want_best=False)
+        out = self.eng.predict_pairs(post, Xa, Xb, want_best=False)
         return out["mu"].cpu().numpy(), out["var"].cpu().numpy(), out["prob"].cpu().numpy()
+
+    def _choice_draws(self, n_draws, G, noisy, seed):
+        """(z, e, noise_sd) of answer_pred / choice_pred: one ppbo_randn stream of 2 S G normals per seed, the first S G
+        of them z, the next S G the likelihood's noise e (drawn whether or not it is used, so that the paths of a seed
+        are the same with and without noise)."""
+        S = int(n_draws)
+        if S < 1:
+            raise ValueError(f"n_draws = {n_draws}: at least one draw is required")
+        if seed is None:
+            from .random_fourier_sampler import draw_seed
+            seed = draw_seed()
+        ze = self.eng.randn(seed, 2, S, G)
+        return ze[0], (ze[1] if noisy else None), (None if noisy else 0.0)
+
+    def answer_pred(self, xi, x, alphas=None, n_draws=4096, noisy=True, seed=None):
+        """Where on the query line {alpha xi + x} will the user stop?  (alphas [G], prob [G]) as NumPy arrays for one
+        line, prob [B, G] for stacked xi, x [B, D]: the probability that the point at alphas[g] is the one marked, under
+        the model's own likelihood (sum_Phi, gp_model.py:176-204: the marked point beats every other point of the line
+        under utilities with noise theta[0]) -- the share of n_draws posterior draws of f on the line, plus that noise,
+        whose maximum it is (ppbo_line_choice_xi; no reference counterpart).  alphas: the G <= 128 abscissae, by default
+        the 70 equispaced points of EI's grid without its noise; noisy = False: the noise-free argmax of the posterior
+        path.  (xi, x) in the scaled coordinates next_query(unscale=False) returns.  seed: None takes one off the global
+        NumPy stream; a fixed seed gives bitwise-equal results."""
+        post = self._var_post()
+        xi, x = np.asarray(xi, dtype=float), np.asarray(x, dtype=float)
+        if xi.shape != x.shape or xi.ndim not in (1, 2) or xi.shape[-1] != self.D or xi.shape[0] < 1:
+            raise ValueError(f"answer_pred: xi and x of shapes {xi.shape} and {x.shape}; two [{self.D}] vectors or two "
+                             f"[B, {self.D}] stacks are required")
+        alphas = np.linspace(0.005, 0.995, 70) if alphas is None else np.asarray(alphas, dtype=float)
+        if alphas.ndim != 1 or not 1 <= alphas.size <= 128:
+            raise ValueError(f"answer_pred: alphas of shape {alphas.shape}; 1 .. 128 abscissae in a vector are required")
+        z, e, noise_sd = self._choice_draws(n_draws, alphas.size, noisy, seed)
+        out = self.eng.line_choice_xi(post, np.atleast_2d(xi), np.atleast_2d(x), alphas, z, e, noise_sd,
+                                      self.COVARIANCE_SHRINKAGE, jitter=1e-10 * float(self.theta[2]) ** 2)
+        prob = out["prob"].cpu().numpy()
+        return alphas, (prob[0] if xi.ndim == 1 else prob)
+
+    def choice_pred(self, X_items, n_draws=4096, noisy=True, seed=None):
+        """Which of K shortlisted configurations will the user pick?  X_items [K, D] -> prob [K], or [B, K, D] ->
+        [B, K] for B shortlists (K <= 128), as NumPy: the probability that each item is the one picked, by the model
+        and the draws of answer_pred (ppbo_line_choice on arbitrary points).  K = 2 is preference_pred's p up to
+        Monte-Carlo error."""
+        post = self._var_post()
+        X = np.asarray(X_items, dtype=float)
+        if X.ndim not in (2, 3) or X.shape[-1] != self.D or not 1 <= X.shape[-2] <= 128 or X.shape[0] < 1:
+            raise ValueError(f"choice_pred: items of shape {X.shape}; [K, {self.D}] or [B, K, {self.D}] with 1 <= K <= 128 "
+                             "is required")
+        z, e, noise_sd = self._choice_draws(n_draws, X.shape[-2], noisy, seed)
+        out = self.eng.line_choice(post, X if X.ndim == 3 else X[None], z, e, noise_sd, self.COVARIANCE_SHRINKAGE,
+                                   jitter=1e-10 * float(self.theta[2]) ** 2)
+        prob = out["prob"].cpu().numpy()
+        return prob[0] if X.ndim == 2 else prob
 
     def mu_pred(self, X_pred):
         x = np.asarray(X_pred, dtype=float).reshape(1, self.D)
