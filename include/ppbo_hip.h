@@ -390,6 +390,36 @@ PPBO_API int ppbo_predict_pairs(ppbo_ctx* ctx, const ppbo_model* model, const do
                        int score_kind, double* d_mu, double* d_var, double* d_prob, double* d_score,
                        double* h_best_val, int64_t* h_best_idx, void* stream);
 
+/* ---- slopes: mean, variance and sign probability of d/da f(x + a xi) at a = 0 for M rows (no reference counterpart) --
+ * The infinitesimal form of a duel: does the utility rise when the query goes on from x along xi, and how sure is the
+ * model.  The directional derivative of a GP is Gaussian; with the column
+ *   g_j = d/da k(x + a xi, x_j) at a = 0 = 2 sigma_f^2 kappa'(rho_j^2) ((x - x_j).xi) / l^2     (k = sigma_f^2 kappa(rho^2),
+ *         rho_j^2 = |x - x_j|^2 / l^2;  camphor-copper: g_j = -k_j ds_j/da, s its exponent, kernels.py:36-53)
+ *   mu_s  = g' alpha
+ *   var_s = prior + g' Lambda g + |G g|^2                            (the operator of ppbo_posterior on g)
+ *   prior = xi' (d^2 k / dx dx')(x, x) xi = -2 kappa'(0) sigma_f^2 |xi|^2 / l^2: sigma_f^2 |xi|^2 / l^2 times 1 (SE, RQ),
+ *           5/3 (Matern-5/2), 3 (Matern-3/2);  camphor-copper: sigma_f^2 (sum_{d != 2} 4 pi^2 xi_d^2 / l^2 + xi_2^2 / (l + 0.05)^2)
+ *   p     = P(slope > 0) = Phi(mu_s / sqrt(max(var_s, 0)));  no noise term (a slope is not an observation);
+ *           var_s = 0: the sign of mu_s decides, mu_s = 0 gives 1/2
+ * The prior term is NOT shrunk (as in ppbo_predict_pairs).  x - x_j comes from direct differences and kappa' from a form
+ * that is finite at 0, so x on a design row gives g_j = 0 for that row; xi = 0 gives (0, 0, 1/2) exactly; -xi negates
+ * mu_s bit for bit and leaves var_s bitwise unchanged.
+ * d_X / d_Xi [M, D]: points and directions in the MODEL's coordinates, as ppbo_predict_pairs takes its sides (an ARD
+ * model: s . x and s . xi; embedded camphor rows: e(x) and J_e(x) xi).  Outputs, each may be NULL: d_mu, d_var, d_prob,
+ * d_score [M] (the quantity score_kind names) and h_best_val / h_best_idx, the largest score and its FIRST index; NaN
+ * never wins, (NaN, -1) when nothing scored.  A row with a NaN or infinite coordinate in x or xi gets NaN outputs; the
+ * other rows do not see it.  PPBO_SLOPE_MEAN with d_var == d_prob == NULL reads neither d_G nor Lambda and runs no
+ * contraction.  Rows go in chunks of 65536 through ppbo_predict's workspaces (kstar_slope_kernel, the quadform kernel of
+ * ppbo_predict, slope_score_kernel); both operator forms take the same three launches, whatever N.  The K* launch is
+ * timed under the "kstar" name of ppbo_profile_read.
+ * "invalid argument": a NULL model, d_X or d_Xi; M outside 1 .. 2^31 - 1; an unknown score_kind; model->kstar_fp32 set
+ * (fp64 only); a model without d_G (or Lambda) when the variance, the probability or a score other than the mean is
+ * asked for. */
+enum { PPBO_SLOPE_MEAN = 0, PPBO_SLOPE_VARIANCE = 1, PPBO_SLOPE_PROB = 2 };
+PPBO_API int ppbo_predict_slopes(ppbo_ctx* ctx, const ppbo_model* model, const double* d_X, const double* d_Xi, int64_t M,
+                        int score_kind, double* d_mu, double* d_var, double* d_prob, double* d_score,
+                        double* h_best_val, int64_t* h_best_idx, void* stream);
+
 /* full predictive covariance of small sets (the G=70 line grid of EI):
  * d_cov[M,M] = (1-s)K(Xc,Xc) + s sigma_f^2 I - K*^T A K*  (src/gp_model.py:447-450) */
 PPBO_API int ppbo_predict_cov(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc, int M,

@@ -618,6 +618,184 @@ __global__ __launch_bounds__(KS_THREADS) void kstar_pair_kernel(
   }
 }
 
+// d k / d r^2 times 2: the c with grad_x k(x, x') = c (x - x') at r^2 = s, finite at s = 0 (SE / RQ: kern_grad_coef's forms
+// on the value itself, Matern: matern_grad) -- never (dk/dr) / r
+template <int KID>
+__device__ __forceinline__ double kern_slope_coef(double s, const KernParams& p) {
+  if constexpr (KID == PPBO_KERNEL_SE) {
+    return -2.0 * p.c0 * (p.sf2 * exp_nonpos(-p.c0 * s));
+  } else if constexpr (KID == PPBO_KERNEL_RQ) {
+    const double t = 1.0 + p.c0 * s;
+    return -4.0 * p.c0 * p.sf2 / (t * t * t);
+  } else {
+    static_assert(kid_matern<KID>, "radial kernels only");
+    return matern_grad<KID>(matern_ae<KID>(s, p), p);
+  }
+}
+
+// Pass 1 of ppbo_predict_slopes: the column of a SLOPE, g_j = d/da k(x + a xi, x_j) at a = 0, in place of k*.  One lane
+// = ONE (point, direction) row, x and xi in the registers kstar_pair_kernel gives its two points.
+//   radial kernels: g_j = c(r_j^2) b_j with r_j^2 = |x - x_j|^2 and b_j = (x - x_j).xi from the DIRECT differences x - x_j
+//     (an add and two FMAs per dimension: nothing cancels next to a design row, where g_j -> 0, and x == x_j gives 0
+//     exactly) and c = kern_slope_coef: ONE kernel-function evaluation per design row;
+//   camphor-copper: g_j = -k_j ds_j/da in kstar_kernel's feature form; s_j is its ten-term dot product, and
+//     ds_j/da = sum_k (pi c0) xi_k sin(2 pi (x_k - x_jk)) + 2 c1 (x_2 - x_j2) xi_2 a second one on the same staged
+//     (cos, sin)(2 pi x_jk), with the candidate-side coefficients (pi c0) xi_k (sin, -cos)(2 pi x_k).
+// xi enters every row through ONE chain of FMAs whose terms are all linear in it (b_j, or ds_j/da), so -xi negates g_j
+// bit for bit and xi = 0 gives g_j = 0.  Everything that kstar_pair_kernel does with dv is done with g: the mean sum,
+// the star sums of g' Lambda g (ko = the observation row's g) and the stored column in node or edge form.  fp64 only.
+// Launch geometry: kstar_kernel's row splits, KS_THREADS rows per workgroup.  Registers: two D-vectors per lane, as
+// kstar_pair_kernel; no instance uses scratch (DP = 64: 256 VGPRs + 40-58 AGPRs, one wavefront per SIMD).  The buckets
+// up to DP = 16 fit 128 VGPRs (four wavefronts per SIMD) unbound; at DP = 20 SE and RQ are held there (137 / 119
+// unbound), the Matern kernels would spill three registers and keep their 137 (three wavefronts); the camphor instance
+// (two 12-vectors and the two dot products' temporaries) is left unbound as well: held to 128 it spills.
+template <int KID, int DP>
+__global__ __launch_bounds__(KS_THREADS, (KID != PPBO_KERNEL_CAMPHOR && (DP < 20 || (DP == 20 && !kid_matern<KID>))) ? 4 : 1) void kstar_slope_kernel(
+    const double* __restrict__ X, int N, int D, KernParams p, const double* __restrict__ alpha,
+    const double* __restrict__ lam_diag, const double* __restrict__ lam_off, int mblk,
+    const double* __restrict__ Xp, const double* __restrict__ Xi, int M, double* __restrict__ Kt, int ldk,
+    double* __restrict__ mu_part, double* __restrict__ t_part, int q_per_split, int n_q, int edge_k0) {
+  static_assert(KID != PPBO_KERNEL_CAMPHOR || DP == 12, "camphor-copper: the feature form only");
+  __shared__ __attribute__((aligned(16))) double xs[KS_RJ * DP];
+  __shared__ double s_alpha[KS_RJ], s_ld[KS_RJ], s_lo[KS_RJ];
+  constexpr bool CAMF = (KID == PPBO_KERNEL_CAMPHOR);     // see kstar_kernel for the feature form
+  const int c = blockIdx.x * KS_THREADS + threadIdx.x;
+  const bool live = c < M;
+  // xc: the point (camphor: its value features, as kstar_kernel's);  xw: the direction (camphor: the slope features)
+  double xc[DP], xw[DP];
+  double mu = 0.0, tl = 0.0, ko = 0.0;
+  // a non-finite coordinate in the point or the direction, found where they are loaded (NaN partial sums at the end, as
+  // kstar_kernel's; the flag rides through the row loop as a lane mask, the coordinates are not read a second time)
+  double chk = 0.0;
+  {
+    const double* __restrict__ px = Xp + (size_t)(live ? c : 0) * D;
+    const double* __restrict__ pw = Xi + (size_t)(live ? c : 0) * D;
+    if constexpr (CAMF) {
+      const double pc0 = 3.14159265358979323846 * p.c0;
+#pragma unroll
+      for (int k = 0; k < 5; ++k) {
+        const int d = k < 2 ? k : k + 1;
+        const double v = live ? px[d] : 0.0, w = live ? pw[d] : 0.0;
+        chk = fma(w, 0.0, fma(v, 0.0, chk));
+        double sn, cs;
+        sincospi(2.0 * v, &sn, &cs);
+        xc[k] = -0.5 * p.c0 * cs;
+        xc[5 + k] = -0.5 * p.c0 * sn;
+        xw[k] = (pc0 * sn) * w;              // meets cos 2 pi x_jk
+        xw[5 + k] = (-pc0 * cs) * w;         // meets sin 2 pi x_jk
+      }
+      xc[10] = live ? px[2] : 0.0;
+      xc[11] = 0.0;
+      xw[10] = (2.0 * p.c1) * (live ? pw[2] : 0.0);
+      xw[11] = 0.0;
+      chk = fma(xw[10], 0.0, fma(xc[10], 0.0, chk));
+    } else {
+#pragma unroll
+      for (int d = 0; d < DP; ++d) {
+        xc[d] = (d < D && live) ? px[d] : 0.0;
+        xw[d] = (d < D && live) ? pw[d] : 0.0;
+        chk = fma(xw[d], 0.0, fma(xc[d], 0.0, chk));
+      }
+    }
+  }
+  const bool finite = chk == 0.0;
+  const int j_beg = blockIdx.y * q_per_split * mblk;
+  int j_end = j_beg + q_per_split * mblk;
+  if (j_end > N) j_end = N;
+  const bool has_lam = (lam_diag != nullptr);
+  int rb = 0;  // row index inside the current star block (splits start on a block edge)
+  int qs = j_beg / mblk;  // ... and that block's star
+  for (int row0 = j_beg; row0 < j_end; row0 += KS_RJ) {
+    __syncthreads();
+    if constexpr (CAMF) {
+      for (int e = threadIdx.x; e < KS_RJ * 6; e += KS_THREADS) {
+        const int r = e / 6, k = e - r * 6;
+        const int j = row0 + r;
+        if (k < 5) {
+          const double v = (j < j_end) ? X[(size_t)j * D + (k < 2 ? k : k + 1)] : 0.0;
+          double sn, cs;
+          sincospi(2.0 * v, &sn, &cs);
+          xs[r * DP + k] = cs;
+          xs[r * DP + 5 + k] = sn;
+        } else {
+          xs[r * DP + 10] = (j < j_end) ? X[(size_t)j * D + 2] : 0.0;
+          xs[r * DP + 11] = 0.0;
+        }
+      }
+    } else {
+      for (int e = threadIdx.x; e < KS_RJ * DP; e += KS_THREADS) {
+        const int r = e / DP, d = e - r * DP;
+        const int j = row0 + r;
+        xs[e] = (j < j_end && d < D) ? X[(size_t)j * D + d] : 0.0;
+      }
+    }
+    if (threadIdx.x < KS_RJ) {
+      const int j = row0 + threadIdx.x;
+      const bool ok = j < j_end;
+      s_alpha[threadIdx.x] = ok ? alpha[j] : 0.0;
+      s_ld[threadIdx.x] = (ok && has_lam) ? lam_diag[j] : 0.0;
+      s_lo[threadIdx.x] = (ok && has_lam) ? lam_off[j] : 0.0;
+    }
+    __syncthreads();
+    const int rmax = (j_end - row0 < KS_RJ) ? (j_end - row0) : KS_RJ;
+    for (int r = 0; r < rmax; ++r) {
+      const double* __restrict__ xr = xs + r * DP;
+      double sv = 0.0, bv = 0.0, cf;
+      if constexpr (CAMF) {
+#pragma unroll
+        for (int d = 0; d < 10; ++d) {
+          const double x = xr[d];
+          sv = fma(x, xc[d], sv);
+          bv = fma(x, xw[d], bv);
+        }
+        const double dd = xc[10] - xr[10];
+        sv = fma(p.c1 * dd, dd, sv + 2.5 * p.c0);
+        bv = fma(xw[10], dd, bv);                       // ds_j / da
+        cf = -kern_finish<KID>(sv, p);
+      } else {
+#pragma unroll
+        for (int d = 0; d < DP; ++d) {
+          const double df = xc[d] - xr[d];
+          sv = fma(df, df, sv);
+          bv = fma(df, xw[d], bv);                      // (x - x_j).xi
+        }
+        cf = kern_slope_coef<KID>(sv, p);
+      }
+      // the two factors as opaque registers: the product below is formed alone, whatever ends the coefficient's chain
+      asm volatile("" : "+v"(cf), "+v"(bv));
+      const double dv = cf * bv;
+      if (Kt) {
+        // the layouts of kstar_kernel: node form row j, edge form row n_q + q m + t = lam_off[j] (g_j - g_obs)
+        int drow = row0 + r;
+        bool wr = true;
+        double ev = dv;
+        if (edge_k0 >= 0) {
+          if (rb == 0) {
+            drow = qs;
+            wr = qs >= edge_k0;
+            ev = 0.0;
+          } else {
+            drow = n_q + qs * (mblk - 1) + rb - 1;
+            ev = s_lo[r] * (dv - ko);
+          }
+        }
+        if (wr && live) store_through(Kt + (size_t)drow * ldk + c, ev);
+      }
+      mu += s_alpha[r] * dv;
+      if (has_lam) {
+        const double ld = s_ld[r];
+        if (rb == 0) { ko = dv; tl += ld * dv * dv; }
+        else tl += dv * (ld * dv + 2.0 * s_lo[r] * ko);
+      }
+      if (++rb == mblk) { rb = 0; ++qs; }
+    }
+  }
+  if (live) {
+    mu_part[(size_t)blockIdx.y * M + c] = finite ? mu : NAN;
+    if (t_part) t_part[(size_t)blockIdx.y * M + c] = finite ? tl : NAN;
+  }
+}
+
 // Y = G K* ; slab[mt][c] = sum over the BM rows of tile mt of Y[i,c]^2
 // EDGE: an edge-form operator (H lower triangular, zero in its first n_q rows and columns).  G and Kt then arrive offset
 // by kshift = n_q rounded down to the chunk depth (G + kshift, Kt + kshift ldk): the K loop starts at 0 of the shifted
@@ -1428,6 +1606,35 @@ int launch_kstar_pair(const ppbo_model* m, const KernParams& p, const double* d_
   return 0;
 }
 
+// kstar_slope_kernel in the same buckets and geometry: d_X the points, d_Xi the directions
+template <int KID>
+int launch_kstar_slope(const ppbo_model* m, const KernParams& p, const double* d_X, const double* d_Xi, int M, double* Kt,
+                       int ldk, double* mu_part, double* t_part, int q_per_split, int n_split, bool with_lam, int edge_k0,
+                       hipStream_t s) {
+  dim3 grid((M + KS_THREADS - 1) / KS_THREADS, n_split);
+  const int mblk = m->m + 1, n_q = (m->N + mblk - 1) / mblk;
+  const double* ld = with_lam ? m->d_lam_diag : nullptr;
+  const double* lo = with_lam ? m->d_lam_off : nullptr;
+#define KSS_LAUNCH(DP)                                                                                                 \
+  kstar_slope_kernel<KID, DP><<<grid, KS_THREADS, 0, s>>>(m->d_X, m->N, m->D, p, m->d_alpha, ld, lo, mblk, d_X, d_Xi, M, \
+                                                          Kt, ldk, mu_part, with_lam ? t_part : nullptr, q_per_split,   \
+                                                          n_q, edge_k0)
+  if constexpr (KID == PPBO_KERNEL_CAMPHOR) KSS_LAUNCH(12);
+  else if (m->D <= 4) KSS_LAUNCH(4);
+  else if (m->D <= 6) KSS_LAUNCH(6);
+  else if (m->D <= 8) KSS_LAUNCH(8);
+  else if (m->D <= 10) KSS_LAUNCH(10);
+  else if (m->D <= 12) KSS_LAUNCH(12);
+  else if (m->D <= 16) KSS_LAUNCH(16);
+  else if (m->D <= 20) KSS_LAUNCH(20);
+  else if (m->D <= 24) KSS_LAUNCH(24);
+  else if (m->D <= 32) KSS_LAUNCH(32);
+  else if (m->D <= 48) KSS_LAUNCH(48);
+  else KSS_LAUNCH(64);
+#undef KSS_LAUNCH
+  return 0;
+}
+
 int check_model(ppbo_ctx* ctx, const ppbo_model* m) {
   PPBO_REQUIRE(ctx, m != nullptr, "model");
   PPBO_REQUIRE(ctx, m->d_X && m->d_alpha, "model X/alpha");
@@ -1612,20 +1819,22 @@ int ppbo_predict_record(ppbo_ctx* ctx, const ppbo_model* model, const double* d_
                         index_offset, &chunk_best, &n_chunks, (hipStream_t)stream);
 }
 
-// Duels: per chunk of 65536 pairs kstar_pair -> quadform -> pair_score -> one-workgroup argmax, with predict_passes'
-// workspaces and operand padding.  Both operator forms take these three launches (the one-launch kernel of fused.hip
-// holds one point per column).
-int ppbo_predict_pairs(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xa, const double* d_Xb, int64_t M,
-                       int score_kind, double* d_mu, double* d_var, double* d_prob, double* d_score, double* h_best_val,
-                       int64_t* h_best_idx, void* stream) {
-  PPBO_ENTER(ctx);
-  hipStream_t s = (hipStream_t)stream;
+// Duels and slopes: two [M, D] point sets per column -- the sides (a, b) of a duel, or the point and the direction
+// (x, xi) of a slope.  Per chunk of 65536 columns kstar_pair / kstar_slope -> quadform -> pair_score / slope_score ->
+// one-workgroup argmax, with predict_passes' workspaces and operand padding.  Both operator forms take these three
+// launches (the one-launch kernel of fused.hip holds one point per column).  The score kinds of the two entries carry
+// the same values (mean, variance, probability).
+static_assert(PPBO_SLOPE_MEAN == PPBO_PAIR_MEAN && PPBO_SLOPE_VARIANCE == PPBO_PAIR_VARIANCE && PPBO_SLOPE_PROB == PPBO_PAIR_PROB,
+              "one score_kind check for both entries");
+static int two_set_passes(ppbo_ctx* ctx, const bool slopes, const ppbo_model* model, const double* d_Xa, const double* d_Xb,
+                          int64_t M, int score_kind, double* d_mu, double* d_var, double* d_prob, double* d_score,
+                          double* h_best_val, int64_t* h_best_idx, hipStream_t s) {
   if (int rc = check_model(ctx, model)) return rc;
-  PPBO_REQUIRE(ctx, d_Xa != nullptr && d_Xb != nullptr, "pairs (d_Xa / d_Xb)");
-  PPBO_REQUIRE(ctx, M >= 1 && M <= (int64_t)0x7fffffff, "pair count (1 .. 2^31 - 1)");
+  PPBO_REQUIRE(ctx, d_Xa != nullptr && d_Xb != nullptr, slopes ? "slopes (d_X / d_Xi)" : "pairs (d_Xa / d_Xb)");
+  PPBO_REQUIRE(ctx, M >= 1 && M <= (int64_t)0x7fffffff, slopes ? "row count (1 .. 2^31 - 1)" : "pair count (1 .. 2^31 - 1)");
   PPBO_REQUIRE(ctx, score_kind == PPBO_PAIR_MEAN || score_kind == PPBO_PAIR_VARIANCE || score_kind == PPBO_PAIR_PROB,
                "score_kind");
-  PPBO_REQUIRE(ctx, !model->kstar_fp32, "pairs are fp64 only (kstar_fp32)");
+  PPBO_REQUIRE(ctx, !model->kstar_fp32, slopes ? "slopes are fp64 only (kstar_fp32)" : "pairs are fp64 only (kstar_fp32)");
   const bool want_var = d_var || d_prob || score_kind != PPBO_PAIR_MEAN;
   PPBO_REQUIRE(ctx, !want_var || model->d_G != nullptr, "variance / probability need model->d_G");
   PPBO_REQUIRE(ctx, !want_var || (model->d_lam_diag && model->d_lam_off), "model Lambda");
@@ -1679,8 +1888,12 @@ int ppbo_predict_pairs(ppbo_ctx* ctx, const ppbo_model* model, const double* d_X
           constexpr int KID = decltype(kid)::value;
           {
             PpboProfScope pf(ctx, ppbo_ctx::PF_KSTAR, s);
-            launch_kstar_pair<KID>(model, p, xa, xb, Mc, Kt, ldk, mu_part, t_part, q_per_split, n_split_eff, want_var,
-                                   edge_k0, s);
+            if (slopes)
+              launch_kstar_slope<KID>(model, p, xa, xb, Mc, Kt, ldk, mu_part, t_part, q_per_split, n_split_eff, want_var,
+                                      edge_k0, s);
+            else
+              launch_kstar_pair<KID>(model, p, xa, xb, Mc, Kt, ldk, mu_part, t_part, q_per_split, n_split_eff, want_var,
+                                     edge_k0, s);
           }
           PPBO_LAUNCH_CHECK(ctx);
           if (want_var) {
@@ -1688,10 +1901,16 @@ int ppbo_predict_pairs(ppbo_ctx* ctx, const ppbo_model* model, const double* d_X
             if (int rc2 = dispatch_quadform(ctx, Gq, Nk, g_rows, N, Kt, ldk, Mc, mblk, slab, edge_k0, s)) return rc2;
           }
           PpboProfScope pfs(ctx, ppbo_ctx::PF_SCORE, s);
-          pair_score_kernel<KID><<<sblocks, SC_THREADS, 0, s>>>(
-              mu_part, n_split_eff, t_part, want_var ? slab : nullptr, ntm, Mc, xa, xb, model->D, p, two_sigma2, score_kind,
-              (long long)c_beg, d_mu ? d_mu + c_beg : nullptr, d_var ? d_var + c_beg : nullptr,
-              d_prob ? d_prob + c_beg : nullptr, d_score ? d_score + c_beg : nullptr, want_best ? bests : nullptr);
+          if (slopes)
+            slope_score_kernel<KID><<<sblocks, SC_THREADS, 0, s>>>(
+                mu_part, n_split_eff, t_part, want_var ? slab : nullptr, ntm, Mc, xb, model->D, p, score_kind,
+                (long long)c_beg, d_mu ? d_mu + c_beg : nullptr, d_var ? d_var + c_beg : nullptr,
+                d_prob ? d_prob + c_beg : nullptr, d_score ? d_score + c_beg : nullptr, want_best ? bests : nullptr);
+          else
+            pair_score_kernel<KID><<<sblocks, SC_THREADS, 0, s>>>(
+                mu_part, n_split_eff, t_part, want_var ? slab : nullptr, ntm, Mc, xa, xb, model->D, p, two_sigma2, score_kind,
+                (long long)c_beg, d_mu ? d_mu + c_beg : nullptr, d_var ? d_var + c_beg : nullptr,
+                d_prob ? d_prob + c_beg : nullptr, d_score ? d_score + c_beg : nullptr, want_best ? bests : nullptr);
           PPBO_LAUNCH_CHECK(ctx);
           return 0;
         }))
@@ -1708,9 +1927,27 @@ int ppbo_predict_pairs(ppbo_ctx* ctx, const ppbo_model* model, const double* d_X
     PPBO_LAUNCH_CHECK(ctx);
   }
   if (int rc = ppbo_host_record_wait(ctx, hr, s)) return rc;
-  if (h_best_val) *h_best_val = hr.h_rec[0];      // (NaN, -1) when no pair has a non-NaN score
+  if (h_best_val) *h_best_val = hr.h_rec[0];      // (NaN, -1) when no column has a non-NaN score
   if (h_best_idx) *h_best_idx = (int64_t)hr.h_rec[1];
   return 0;
+}
+
+int ppbo_predict_pairs(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xa, const double* d_Xb, int64_t M,
+                       int score_kind, double* d_mu, double* d_var, double* d_prob, double* d_score, double* h_best_val,
+                       int64_t* h_best_idx, void* stream) {
+  PPBO_ENTER(ctx);
+  return two_set_passes(ctx, false, model, d_Xa, d_Xb, M, score_kind, d_mu, d_var, d_prob, d_score, h_best_val, h_best_idx,
+                        (hipStream_t)stream);
+}
+
+// Slopes: the column g = d/da k(x + a xi, X) at a = 0 in place of a duel's difference column; the K* launches share the
+// "kstar" profile slot with ppbo_predict and ppbo_predict_pairs.
+int ppbo_predict_slopes(ppbo_ctx* ctx, const ppbo_model* model, const double* d_X, const double* d_Xi, int64_t M,
+                        int score_kind, double* d_mu, double* d_var, double* d_prob, double* d_score, double* h_best_val,
+                        int64_t* h_best_idx, void* stream) {
+  PPBO_ENTER(ctx);
+  return two_set_passes(ctx, true, model, d_X, d_Xi, M, score_kind, d_mu, d_var, d_prob, d_score, h_best_val, h_best_idx,
+                        (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -197,6 +197,88 @@ __global__ __launch_bounds__(SC_THREADS) void pair_score_kernel(const double* __
   if (lane == 0) blk_best[blockIdx.x] = b;
 }
 
+// Pass 3 of ppbo_predict_slopes: score_kernel's slab sums (same geometry) for the column g = d/da k(x + a xi, X), then
+//   mu_s = sum of the mean partials,   var_s = prior + g' Lambda g + |G g|^2,   p = Phi(mu_s / sqrt(max(var_s, 0)))
+// prior = xi' (d^2 k / dx dx')(x, x) xi, a sum of squares over the dimensions (wavefront w sums the dimensions w,
+// w + SC_WAVES, ... beside its slabs; the sums meet in wavefront order), so it does not see the sign of xi:
+//   radial kernels   -c(0) |xi|^2, c = 2 dk/dr^2 (kern_slope_coef): 2 c0 sf2 (SE), 4 c0 sf2 (RQ), sf2 c0^2 / 3 (Matern-5/2),
+//                    sf2 c0^2 (Matern-3/2) -- sf2 / l^2 times 1, 1, 5/3, 3
+//   camphor-copper   sf2 (sum_{d != 2} 2 pi^2 c0 xi_d^2 + 2 c1 xi_2^2)
+// No noise term: a slope is not an observation.  mu_s = var_s = 0 gives 1/2; a NaN mean (a non-finite coordinate) gives
+// NaN everywhere.
+template <int KID>
+__device__ __forceinline__ double slope_prior_weight(int d, const KernParams& p) {
+  if constexpr (KID == PPBO_KERNEL_SE) return 2.0 * p.c0 * p.sf2;
+  else if constexpr (KID == PPBO_KERNEL_RQ) return 4.0 * p.c0 * p.sf2;
+  else if constexpr (KID == PPBO_KERNEL_MATERN52) return p.sf2 * (p.c0 * p.c0) * (1.0 / 3.0);
+  else if constexpr (KID == PPBO_KERNEL_MATERN32) return p.sf2 * (p.c0 * p.c0);
+  else {
+    static_assert(KID == PPBO_KERNEL_CAMPHOR, "unknown kernel id");
+    return p.sf2 * (d == 2 ? 2.0 * p.c1 : 19.73920880217871723767 * p.c0);     // 2 pi^2
+  }
+}
+template <int KID>
+__global__ __launch_bounds__(SC_THREADS) void slope_score_kernel(const double* __restrict__ mu_part, int n_mu,
+                                                                 const double* __restrict__ t_part,
+                                                                 const double* __restrict__ slab, int n_slab, int M,
+                                                                 const double* __restrict__ Xi, int D, KernParams p,
+                                                                 int kind, long long idx_base,
+                                                                 double* __restrict__ mu_out, double* __restrict__ var_out,
+                                                                 double* __restrict__ prob_out,
+                                                                 double* __restrict__ score_out, Best* __restrict__ blk_best) {
+  __shared__ double part[4][SC_WAVES][SC_CAND];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int c = blockIdx.x * SC_CAND + lane;
+  double pm = 0.0, pt = 0.0, pq = 0.0, ps = 0.0;
+  if (c < M) {
+    for (int s = wave; s < n_mu; s += SC_WAVES) pm += mu_part[(size_t)s * M + c];
+    if (slab) {
+      for (int s = wave; s < n_mu; s += SC_WAVES) pt += t_part[(size_t)s * M + c];
+      for (int s = wave; s < n_slab; s += SC_WAVES) pq += slab[(size_t)s * M + c];
+      for (int d = wave; d < D; d += SC_WAVES) {
+        const double w = Xi[(size_t)c * D + d];
+        ps += slope_prior_weight<KID>(d, p) * (w * w);
+      }
+    }
+  }
+  part[0][wave][lane] = pm;
+  part[1][wave][lane] = pt;
+  part[2][wave][lane] = pq;
+  part[3][wave][lane] = ps;
+  __syncthreads();
+  if (wave != 0) return;                 // the rest is one wavefront's work
+  Best b{0.0, -1};
+  if (c < M) {
+    double mu = 0.0, t = 0.0, q = 0.0, s = 0.0;
+#pragma unroll
+    for (int w = 0; w < SC_WAVES; ++w) { mu += part[0][w][lane]; t += part[1][w][lane]; q += part[2][w][lane]; s += part[3][w][lane]; }
+    double var = NAN, pr = NAN, sc = mu;   // mean only (no slab): nothing but mu is formed
+    if (slab) {
+      var = s + t + q;
+      const double sd = sqrt(fmax(var, 0.0));
+      // sd = 0 (no variance): the sign of mu_s decides, a tie is 1/2
+      pr = norm_cdf(sd > 0.0 ? mu / sd : (mu > 0.0 ? INFINITY : (mu < 0.0 ? -INFINITY : 0.0)));
+      if (mu != mu) { var = mu; pr = mu; }
+      if (kind == PPBO_SLOPE_VARIANCE) sc = var;
+      else if (kind == PPBO_SLOPE_PROB) sc = pr;
+    }
+    if (mu_out) mu_out[c] = mu;
+    if (var_out) var_out[c] = var;
+    if (prob_out) prob_out[c] = pr;
+    if (score_out) score_out[c] = sc;
+    if (sc == sc) { b.val = sc; b.idx = idx_base + c; }
+  }
+  if (!blk_best) return;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    Best other;
+    other.val = __shfl_xor(b.val, o, 64);
+    other.idx = __shfl_xor(b.idx, o, 64);
+    b = best_merge(b, other);
+  }
+  if (lane == 0) blk_best[blockIdx.x] = b;
+}
+
 // per-block records of one launch -> *out; with `record` also the 16-byte (value, GLOBAL index as a double: exact
 // below 2^53; index + record_offset; (NaN, -1) when nothing scored) record that the sharded search all-gathers, and
 // with `publish` the flag publish[0] raised to `epoch` AFTER the record with system-scope release semantics (the

@@ -11,6 +11,7 @@ import torch
 from . import _lib
 from ._lib import KERNEL_IDS, SCORE_MEAN, SCORE_POINTWISE_EI, SCORE_VARIANCE, PPBO_ERR_NOT_PD  # noqa: F401
 from ._lib import PAIR_MEAN, PAIR_VARIANCE, PAIR_PROB  # noqa: F401
+from ._lib import SLOPE_MEAN, SLOPE_VARIANCE, SLOPE_PROB  # noqa: F401
 
 # Posterior.form: which variance operator G holds (include/ppbo_hip.h, PPBO_FORM_*)
 FORM_NODE = 0   # G = R Lambda, block lower triangular [N, N]
@@ -45,6 +46,22 @@ def camphor_lengthscales(theta, D):
     if not (np.all(np.isfinite(v)) and np.all(v > 0)):
         raise ValueError("theta[1]: every camphor length scale must be positive and finite")
     return v
+
+
+def camphor_embed_directions(X, Xi, ls):
+    """J_e(x_i) xi_i [M, 11] for caller rows X [M, 6] and directions Xi [M, 6]: the derivative of the embedding e of
+    include/ppbo_hip.h (columns c0, s0, c1, s1, z, c3, s3, c4, s4, c5, s5) along xi, d c_d = -2 pi sin(2 pi x_d) xi_d / l_d,
+    d s_d = 2 pi cos(2 pi x_d) xi_d / l_d, d z = xi_2 / l_2.  NumPy in and out."""
+    X, Xi = np.asarray(X, dtype=np.float64), np.asarray(Xi, dtype=np.float64)
+    ls = np.asarray(ls, dtype=np.float64)
+    cols = []
+    for d in range(6):
+        if d == 2:
+            cols.append(Xi[:, 2] / ls[2])
+        else:
+            w = 2.0 * np.pi * Xi[:, d] / ls[d]
+            cols += [-np.sin(2.0 * np.pi * X[:, d]) * w, np.cos(2.0 * np.pi * X[:, d]) * w]
+    return np.stack(cols, axis=1)
 
 
 def lengthscales(theta, D, kernel):
@@ -659,16 +676,17 @@ class Engine:
         return dict(mu=mu, var=var, score=sc, best_val=bv.value, best_idx=bi.value)
 
     @staticmethod
-    def _pair_shapes(post: Posterior, Xa, Xb):
-        """The refusals of predict_pairs that shapes alone decide (before anything reaches the device): returns M."""
+    def _pair_shapes(post: Posterior, Xa, Xb, what="predict_pairs", sets="the two sides", rows="pairs"):
+        """The refusals of predict_pairs / predict_slopes that shapes alone decide (before anything reaches the device):
+        returns M."""
         sa, sb = tuple(np.shape(Xa)), tuple(np.shape(Xb))
         D = 6 if post.camphor is not None else post.X.shape[1]
         if len(sa) != 2 or sa != sb:
-            raise ValueError(f"predict_pairs: the two sides have shapes {sa} and {sb}; two equal [M, D] sets are required")
+            raise ValueError(f"{what}: {sets} have shapes {sa} and {sb}; two equal [M, D] sets are required")
         if sa[1] != D:
-            raise ValueError(f"predict_pairs: points of width {sa[1]} for a model of {D} dimensions")
+            raise ValueError(f"{what}: points of width {sa[1]} for a model of {D} dimensions")
         if sa[0] < 1:
-            raise ValueError("predict_pairs: no pairs")
+            raise ValueError(f"{what}: no {rows}")
         return sa[0]
 
     def predict_pairs(self, post: Posterior, Xa, Xb, score=PAIR_PROB, want_mu=True, want_var=True, want_prob=True,
@@ -692,6 +710,39 @@ class Engine:
                                          _ptr(pr), _ptr(sc), C.byref(bv) if want_best else None,
                                          C.byref(bi) if want_best else None, self._stream())
         self._check(rc, "ppbo_predict_pairs")
+        return dict(mu=mu, var=var, prob=pr, score=sc, best_val=bv.value, best_idx=bi.value)
+
+    def _directions(self, post: Posterior, X, Xi):
+        """Directions in the caller's coordinates -> the coordinates the posterior's device state is in: the Jacobian of
+        _points' map at X applied to Xi (ARD: s (.) xi; camphor_copper_ard_kernel: J_e(x) xi, formed on the host)."""
+        if post.camphor is not None:
+            to_host = lambda a: a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a, dtype=np.float64)  # noqa: E731
+            return self.dev(camphor_embed_directions(to_host(X), to_host(Xi), post.camphor))
+        Xi = self.dev(Xi)
+        return Xi if post.scale is None else self.scale_points(Xi, post.scale)
+
+    def predict_slopes(self, post: Posterior, X, Xi, score=SLOPE_PROB, want_mu=True, want_var=True, want_prob=True,
+                       want_score=False, want_best=True):
+        """Slopes (ppbo_predict_slopes): for the M rows (X[i], Xi[i]) in the caller's coordinates the posterior mean and
+        variance of d/da f(x + a xi) at a = 0 and p = P(slope > 0), as device tensors mu / var / prob / score (None where
+        not asked for), with best_val / best_idx = the largest score (the quantity `score` names) and its first row.
+        SLOPE_MEAN without var and prob needs no variance operator."""
+        M = self._pair_shapes(post, X, Xi, "predict_slopes", "points and directions", "rows")
+        if score not in (SLOPE_MEAN, SLOPE_VARIANCE, SLOPE_PROB):
+            raise ValueError(f"predict_slopes: unknown score kind {score}")
+        Xi = self._directions(post, X, Xi)
+        X = self._points(post, X)
+        with_var = want_var or want_prob or score != SLOPE_MEAN
+        md = self._model(post, with_var)
+        mu = self.empty(M) if want_mu else None
+        var = self.empty(M) if want_var else None
+        pr = self.empty(M) if want_prob else None
+        sc = self.empty(M) if want_score else None
+        bv, bi = C.c_double(0.0), C.c_int64(-1)
+        rc = self.lib.ppbo_predict_slopes(self.ctx, C.byref(md), _ptr(X), _ptr(Xi), M, int(score), _ptr(mu), _ptr(var),
+                                          _ptr(pr), _ptr(sc), C.byref(bv) if want_best else None,
+                                          C.byref(bi) if want_best else None, self._stream())
+        self._check(rc, "ppbo_predict_slopes")
         return dict(mu=mu, var=var, prob=pr, score=sc, best_val=bv.value, best_idx=bi.value)
 
     def predict_cov(self, post: Posterior, Xc, shrink=SHRINKAGE):

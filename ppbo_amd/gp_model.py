@@ -19,6 +19,7 @@ import time
 
 import numpy as np
 import scipy.optimize
+import torch
 
 from . import kernels as _kernels
 from .engine import (ARD_KERNELS, CAMPHOR_ARD, NotPositiveDefinite, SCORE_MEAN, get_engine, lengthscales,
@@ -879,6 +880,24 @@ class GPModel:
         Xa, Xb = (x if x.dim() == 2 else x.reshape(1, -1) for x in (self.eng.dev(Xa), self.eng.dev(Xb)))
         out = self.eng.predict_pairs(post, Xa, Xb, want_best=False)
         return out["mu"].cpu().numpy(), out["var"].cpu().numpy(), out["prob"].cpu().numpy()
+
+    def slope_pred(self, X, Xi):
+        """(mu_s, var_s, p) as NumPy arrays for the rows (X[i], Xi[i]): the posterior mean and variance of the slope
+        d/da f(x + a xi) at a = 0 and p = P(slope > 0) = Phi(mu_s / sqrt(var_s)), without a noise term
+        (ppbo_predict_slopes; no reference counterpart).  Host or device input in the caller's coordinates; one row may
+        be given as two 1-D vectors.  ValueError when the two shapes differ or do not fit the model."""
+        post = self._var_post()
+        X, Xi = (a if isinstance(a, torch.Tensor) else np.asarray(a, dtype=float) for a in (X, Xi))
+        X, Xi = (a.reshape(1, -1) if a.ndim == 1 else a for a in (X, Xi))
+        out = self.eng.predict_slopes(post, X, Xi, want_best=False)
+        return out["mu"].cpu().numpy(), out["var"].cpu().numpy(), out["prob"].cpu().numpy()
+
+    def sensitivity(self, x=None):
+        """The D coordinate slopes at x (default: xstar) as three length-D NumPy arrays (mu_s, var_s, p): row d is
+        slope_pred(x, e_d).  p near 1/2 with a small |mu_s|: the parameter is locally settled; p near 0 or 1: the
+        model expects the utility to change along it."""
+        x = np.asarray(self.xstar if x is None else x, dtype=float).reshape(-1)
+        return self.slope_pred(np.tile(x, (x.size, 1)), np.eye(x.size))
 
     def _choice_draws(self, n_draws, G, noisy, seed):
         """(z, e, noise_sd) of answer_pred / choice_pred: one ppbo_randn stream of 2 S G normals per seed, the first S G
