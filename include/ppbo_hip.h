@@ -420,6 +420,44 @@ PPBO_API int ppbo_predict_slopes(ppbo_ctx* ctx, const ppbo_model* model, const d
                         int score_kind, double* d_mu, double* d_var, double* d_prob, double* d_score,
                         double* h_best_val, int64_t* h_best_idx, void* stream);
 
+/* ---- curvatures: mean, variance and sign probability of d^2/da^2 f(gamma(a)) at a = 0 for M rows (no reference counterpart) --
+ * The companion of a slope where the slope vanishes: is x a peak along xi, how sharp is it, and how sure is the model.
+ * gamma is a path in the MODEL's coordinates with gamma(0) = x, gamma'(0) = xi, gamma''(0) = acc (d_Xa == NULL: straight
+ * lines, acc = 0).  The second directional derivative of a GP is Gaussian; with the column
+ *   c_j = d^2/da^2 k(gamma(a), x_j) at a = 0 = 2 c'(s_j) b_j^2 + c(s_j) (n2 + (x - x_j).acc)
+ *         (radial kernels, k = sigma_f^2 kappa(rho^2): s_j = |x - x_j|^2 and b_j = (x - x_j).xi from direct differences,
+ *         n2 = |xi|^2, c(s) = 2 dk/ds as in ppbo_predict_slopes, c'(s) = 2 d^2k/ds^2 -- with c0 of the device's KernParams
+ *         SE: 2 c0^2 k;  RQ: 12 c0^2 sigma_f^2 / t^4, t = 1 + c0 s;  Matern-5/2: sigma_f^2 c0^4 e^(-c0 r) / 6; all finite at s = 0;
+ *         camphor-copper, k = sigma_f^2 e^-s: c_j = k_j ((ds_j/da)^2 - d^2 s_j/da^2),
+ *         d^2 s_j/da^2 = sum_{d != 2} 2 pi^2 c0 xi_d^2 cos 2 pi (x_d - x_jd) + 2 c1 xi_2^2)
+ *   mu_c  = c' alpha
+ *   var_c = prior + c' Lambda c + |G c|^2                            (the operator of ppbo_posterior on c)
+ *   prior = Var[d^2/da^2 f(gamma(a))] = q4 n2^2 + q2 |acc|^2 (no cross term: the kernels are stationary);  q2 = -c(0), the
+ *           constant of a slope's prior;  q4 = 12 kappa''(0) sigma_f^2 / l^4: sigma_f^2 / l^4 times 3 (SE), 9/2 (RQ),
+ *           25 (Matern-5/2);  camphor-copper: sigma_f^2 (12 A^2 + 8 pi^4 c0 sum_{d != 2} xi_d^4),
+ *           A = sum_{d != 2} pi^2 c0 xi_d^2 + c1 xi_2^2
+ *   p     = P(curvature < 0) = Phi(-mu_c / sqrt(max(var_c, 0)));  no noise term;  var_c = 0: the sign of mu_c decides,
+ *           mu_c = 0 gives 1/2
+ * The prior term is NOT shrunk (as in ppbo_predict_slopes).  Every term is of even degree in xi: with d_Xa NULL, xi = 0
+ * gives (0, 0, 1/2) exactly, -xi leaves all three outputs bitwise unchanged, and for the radial kernels 2 xi gives
+ * 4 mu_c and 16 var_c bit for bit.
+ * d_X / d_Xi / d_Xa [M, D]: points, directions and accelerations in the MODEL's coordinates (an ARD model: s . x and
+ * s . xi, straight lines stay straight; embedded camphor rows: e(x), J_e(x) xi and d^2 e(x + a xi) / da^2).  Outputs, each
+ * may be NULL: d_mu, d_var, d_prob, d_score [M] (the quantity score_kind names) and h_best_val / h_best_idx, the largest
+ * score and its FIRST index; NaN never wins, (NaN, -1) when nothing scored.  A row with a NaN or infinite coordinate in
+ * x, xi or acc gets NaN outputs; the other rows do not see it.  PPBO_CURV_MEAN with d_var == d_prob == NULL reads
+ * neither d_G nor Lambda and runs no contraction.  Rows go in chunks of 65536 through ppbo_predict's workspaces
+ * (kstar_curv_kernel, the quadform kernel of ppbo_predict, curv_score_kernel); both operator forms take the same three
+ * launches, whatever N.  The K* launch is timed under the "kstar" name of ppbo_profile_read.
+ * "invalid argument": everything ppbo_predict_slopes refuses (a NULL model, d_X or d_Xi; M outside 1 .. 2^31 - 1; an
+ * unknown score_kind; model->kstar_fp32; a model without d_G or Lambda when more than the mean is asked for);
+ * PPBO_KERNEL_MATERN32 (a sample path of that kernel is differentiable once only: c'(s) ~ 1 / sqrt(s), no finite variance);
+ * d_Xa with D > 16 or with PPBO_KERNEL_CAMPHOR (there the caller's coordinates are the model's: lines are straight). */
+enum { PPBO_CURV_MEAN = 0, PPBO_CURV_VARIANCE = 1, PPBO_CURV_PROB = 2 };
+PPBO_API int ppbo_predict_curvatures(ppbo_ctx* ctx, const ppbo_model* model, const double* d_X, const double* d_Xi,
+                        const double* d_Xa, int64_t M, int score_kind, double* d_mu, double* d_var, double* d_prob,
+                        double* d_score, double* h_best_val, int64_t* h_best_idx, void* stream);
+
 /* full predictive covariance of small sets (the G=70 line grid of EI):
  * d_cov[M,M] = (1-s)K(Xc,Xc) + s sigma_f^2 I - K*^T A K*  (src/gp_model.py:447-450) */
 PPBO_API int ppbo_predict_cov(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc, int M,

@@ -796,6 +796,221 @@ __global__ __launch_bounds__(KS_THREADS, (KID != PPBO_KERNEL_CAMPHOR && (DP < 20
   }
 }
 
+// The two coefficients of a CURVATURE column at r^2 = s: c = 2 dk/dr^2 (kern_slope_coef's value) and c' = 2 d^2k/d(r^2)^2,
+// both finite at s = 0, from ONE kernel-function evaluation (SE: one exponential; RQ: one reciprocal; Matern-5/2: the
+// exponential of matern_ae, c' = sf2 c0^4 e^-a / 6 -- never a quotient by r).  Matern-3/2 has no second coefficient: its
+// c' ~ 1 / sqrt(s), the curvature of its sample paths has no finite variance, and ppbo_predict_curvatures refuses it.
+struct CurvCoef { double c, cp; };
+template <int KID>
+__device__ __forceinline__ CurvCoef kern_curv_coef(double s, const KernParams& p) {
+  if constexpr (KID == PPBO_KERNEL_SE) {
+    const double k = p.sf2 * exp_nonpos(-p.c0 * s);
+    return CurvCoef{-2.0 * p.c0 * k, (2.0 * p.c0 * p.c0) * k};
+  } else if constexpr (KID == PPBO_KERNEL_RQ) {
+    const double r = 1.0 / (1.0 + p.c0 * s), r2 = r * r;
+    return CurvCoef{(-4.0 * p.c0 * p.sf2) * (r2 * r), (12.0 * p.c0 * p.c0 * p.sf2) * (r2 * r2)};
+  } else {
+    static_assert(KID == PPBO_KERNEL_MATERN52, "SE, RQ and Matern-5/2 only");
+    const MaternAE ae = matern_ae<KID>(s, p);
+    const double c2 = p.c0 * p.c0;
+    return CurvCoef{matern_grad<KID>(ae, p), (p.sf2 * c2 * c2 * (1.0 / 6.0)) * ae.e};
+  }
+}
+
+// wavefronts per SIMD that kstar_curv_kernel is held to (its second launch bound), from the register table of
+// profiles/r18_curvature.txt: 4 (128 VGPRs, no scratch) for the buckets up to DP = 16 without an acceleration, as
+// kstar_slope_kernel at DP = 20 for SE and RQ (unbound 141 / 123; Matern-5/2 would spill 12 bytes per lane there and keeps
+// its 141), and up to DP = 10 with an acceleration: held, DP = 12 with one spills 12 (SE) and 16 (Matern-5/2) bytes per
+// lane, so it and everything larger, and the camphor instance (three 12-vectors), stay unbound
+template <int KID, int DP, bool ACC>
+constexpr int curv_waves() {
+  if (KID == PPBO_KERNEL_CAMPHOR) return 1;
+  if (ACC) return DP <= 10 ? 4 : 1;
+  return (DP <= 16 || (DP == 20 && !kid_matern<KID>)) ? 4 : 1;
+}
+
+// Pass 1 of ppbo_predict_curvatures: the column of a CURVATURE, c_j = d^2/da^2 k(gamma(a), x_j) at a = 0 for a path with
+// gamma(0) = x, gamma'(0) = xi, gamma''(0) = acc (ACC = false: a straight line, acc = 0), in place of k*.  One lane = ONE
+// (x, xi[, acc]) row, on the plan of kstar_slope_kernel: its launch geometry, row splits, star bookkeeping, NaN flag
+// and node / edge stores.
+//   radial kernels: with s_j = |x - x_j|^2, b_j = (x - x_j).xi, n2 = |xi|^2 (formed once per lane, before the row loop),
+//     c_j = 2 c'(s_j) b_j^2 + c(s_j) (n2 + (x - x_j).acc),     (c, c') = kern_curv_coef: ONE evaluation per design row;
+//     the direct differences x - x_j feed two (ACC: three) FMA chains per dimension;
+//   camphor-copper (feature form, k = sf2 e^-s): c_j = k_j ((ds_j/da)^2 - d^2 s_j/da^2); s_j and ds_j/da are the slope
+//     kernel's two dot products, d^2 s_j/da^2 = sum_{d != 2} 2 pi^2 c0 xi_d^2 cos 2 pi (x_d - x_jd) + 2 c1 xi_2^2 a third
+//     one on the same staged (cos, sin)(2 pi x_jk) with the candidate-side coefficients 2 pi^2 c0 xi_k^2 (cos, sin)(2 pi x_k).
+//     No acceleration: the caller's coordinates are the model's.
+// Every term is of even degree in xi: -xi leaves c_j bitwise unchanged, xi = 0 (acc = 0) gives c_j = 0, and for the
+// radial kernels 2 xi gives 4 c_j exactly (b_j doubles, n2 quadruples, every product scales by a power of two).  fp64
+// only.  Registers: two D-vectors per lane (ACC: three, instantiated for DP <= 16 only -- the 11-column embedding is the
+// only source of an acceleration, and three 64-vectors do not fit the register file); no instance uses scratch.
+template <int KID, int DP, bool ACC>
+__global__ __launch_bounds__(KS_THREADS, (curv_waves<KID, DP, ACC>())) void kstar_curv_kernel(
+    const double* __restrict__ X, int N, int D, KernParams p, const double* __restrict__ alpha,
+    const double* __restrict__ lam_diag, const double* __restrict__ lam_off, int mblk,
+    const double* __restrict__ Xp, const double* __restrict__ Xi, const double* __restrict__ Xa, int M,
+    double* __restrict__ Kt, int ldk, double* __restrict__ mu_part, double* __restrict__ t_part, int q_per_split, int n_q,
+    int edge_k0) {
+  static_assert(KID != PPBO_KERNEL_CAMPHOR || (DP == 12 && !ACC), "camphor-copper: the feature form only, straight lines");
+  static_assert(!ACC || DP <= 16, "an acceleration vector: the buckets up to 16 only");
+  __shared__ __attribute__((aligned(16))) double xs[KS_RJ * DP];
+  __shared__ double s_alpha[KS_RJ], s_ld[KS_RJ], s_lo[KS_RJ];
+  constexpr bool CAMF = (KID == PPBO_KERNEL_CAMPHOR);     // see kstar_kernel for the feature form
+  constexpr int DA = (ACC || CAMF) ? DP : 1;
+  const int c = blockIdx.x * KS_THREADS + threadIdx.x;
+  const bool live = c < M;
+  // xc: the point (camphor: its value features);  xw: the direction (camphor: the slope features);  xa: the
+  // acceleration (camphor: the features of d^2 s / da^2)
+  double xc[DP], xw[DP];
+  [[maybe_unused]] double xa[DA];
+  double mu = 0.0, tl = 0.0, ko = 0.0;
+  [[maybe_unused]] double n2 = 0.0;       // |xi|^2 (camphor: unused, its constant 2 c1 xi_2^2 sits in xa[10])
+  double chk = 0.0;      // a non-finite coordinate, found where the row is loaded (kstar_slope_kernel)
+  {
+    const double* __restrict__ px = Xp + (size_t)(live ? c : 0) * D;
+    const double* __restrict__ pw = Xi + (size_t)(live ? c : 0) * D;
+    if constexpr (CAMF) {
+      const double pc0 = 3.14159265358979323846 * p.c0;
+      const double qc0 = 19.73920880217871723767 * p.c0;     // 2 pi^2 c0
+#pragma unroll
+      for (int k = 0; k < 5; ++k) {
+        const int d = k < 2 ? k : k + 1;
+        const double v = live ? px[d] : 0.0, w = live ? pw[d] : 0.0;
+        chk = fma(w, 0.0, fma(v, 0.0, chk));
+        double sn, cs;
+        sincospi(2.0 * v, &sn, &cs);
+        xc[k] = -0.5 * p.c0 * cs;
+        xc[5 + k] = -0.5 * p.c0 * sn;
+        xw[k] = (pc0 * sn) * w;              // meets cos 2 pi x_jk
+        xw[5 + k] = (-pc0 * cs) * w;         // meets sin 2 pi x_jk
+        const double w2 = qc0 * (w * w);
+        xa[k] = w2 * cs;                     // meets cos 2 pi x_jk
+        xa[5 + k] = w2 * sn;                 // meets sin 2 pi x_jk
+      }
+      const double w2 = live ? pw[2] : 0.0;
+      xc[10] = live ? px[2] : 0.0;
+      xc[11] = 0.0;
+      xw[10] = (2.0 * p.c1) * w2;
+      xw[11] = 0.0;
+      xa[10] = (2.0 * p.c1) * (w2 * w2);
+      xa[11] = 0.0;
+      chk = fma(xw[10], 0.0, fma(xc[10], 0.0, chk));
+    } else {
+      const double* __restrict__ pa = ACC ? Xa + (size_t)(live ? c : 0) * D : nullptr;
+#pragma unroll
+      for (int d = 0; d < DP; ++d) {
+        xc[d] = (d < D && live) ? px[d] : 0.0;
+        xw[d] = (d < D && live) ? pw[d] : 0.0;
+        chk = fma(xw[d], 0.0, fma(xc[d], 0.0, chk));
+        n2 = fma(xw[d], xw[d], n2);
+        if constexpr (ACC) {
+          xa[d] = (d < D && live) ? pa[d] : 0.0;
+          chk = fma(xa[d], 0.0, chk);
+        }
+      }
+    }
+  }
+  const bool finite = chk == 0.0;
+  const int j_beg = blockIdx.y * q_per_split * mblk;
+  int j_end = j_beg + q_per_split * mblk;
+  if (j_end > N) j_end = N;
+  const bool has_lam = (lam_diag != nullptr);
+  int rb = 0;  // row index inside the current star block (splits start on a block edge)
+  int qs = j_beg / mblk;  // ... and that block's star
+  for (int row0 = j_beg; row0 < j_end; row0 += KS_RJ) {
+    __syncthreads();
+    if constexpr (CAMF) {
+      for (int e = threadIdx.x; e < KS_RJ * 6; e += KS_THREADS) {
+        const int r = e / 6, k = e - r * 6;
+        const int j = row0 + r;
+        if (k < 5) {
+          const double v = (j < j_end) ? X[(size_t)j * D + (k < 2 ? k : k + 1)] : 0.0;
+          double sn, cs;
+          sincospi(2.0 * v, &sn, &cs);
+          xs[r * DP + k] = cs;
+          xs[r * DP + 5 + k] = sn;
+        } else {
+          xs[r * DP + 10] = (j < j_end) ? X[(size_t)j * D + 2] : 0.0;
+          xs[r * DP + 11] = 0.0;
+        }
+      }
+    } else {
+      for (int e = threadIdx.x; e < KS_RJ * DP; e += KS_THREADS) {
+        const int r = e / DP, d = e - r * DP;
+        const int j = row0 + r;
+        xs[e] = (j < j_end && d < D) ? X[(size_t)j * D + d] : 0.0;
+      }
+    }
+    if (threadIdx.x < KS_RJ) {
+      const int j = row0 + threadIdx.x;
+      const bool ok = j < j_end;
+      s_alpha[threadIdx.x] = ok ? alpha[j] : 0.0;
+      s_ld[threadIdx.x] = (ok && has_lam) ? lam_diag[j] : 0.0;
+      s_lo[threadIdx.x] = (ok && has_lam) ? lam_off[j] : 0.0;
+    }
+    __syncthreads();
+    const int rmax = (j_end - row0 < KS_RJ) ? (j_end - row0) : KS_RJ;
+    for (int r = 0; r < rmax; ++r) {
+      const double* __restrict__ xr = xs + r * DP;
+      double sv = 0.0, bv = 0.0, dv;
+      if constexpr (CAMF) {
+        double qv = 0.0;
+#pragma unroll
+        for (int d = 0; d < 10; ++d) {
+          const double x = xr[d];
+          sv = fma(x, xc[d], sv);
+          bv = fma(x, xw[d], bv);
+          qv = fma(x, xa[d], qv);
+        }
+        const double dd = xc[10] - xr[10];
+        sv = fma(p.c1 * dd, dd, sv + 2.5 * p.c0);
+        bv = fma(xw[10], dd, bv);                       // ds_j / da
+        qv += xa[10];                                   // d^2 s_j / da^2
+        dv = kern_finish<KID>(sv, p) * fma(bv, bv, -qv);
+      } else {
+        double av = n2;
+#pragma unroll
+        for (int d = 0; d < DP; ++d) {
+          const double df = xc[d] - xr[d];
+          sv = fma(df, df, sv);
+          bv = fma(df, xw[d], bv);                      // (x - x_j).xi
+          if constexpr (ACC) av = fma(df, xa[d], av);   // n2 + (x - x_j).acc
+        }
+        const CurvCoef cc = kern_curv_coef<KID>(sv, p);
+        dv = fma((2.0 * cc.cp) * bv, bv, cc.c * av);
+      }
+      if (Kt) {
+        // the layouts of kstar_kernel: node form row j, edge form row n_q + q m + t = lam_off[j] (c_j - c_obs)
+        int drow = row0 + r;
+        bool wr = true;
+        double ev = dv;
+        if (edge_k0 >= 0) {
+          if (rb == 0) {
+            drow = qs;
+            wr = qs >= edge_k0;
+            ev = 0.0;
+          } else {
+            drow = n_q + qs * (mblk - 1) + rb - 1;
+            ev = s_lo[r] * (dv - ko);
+          }
+        }
+        if (wr && live) store_through(Kt + (size_t)drow * ldk + c, ev);
+      }
+      mu += s_alpha[r] * dv;
+      if (has_lam) {
+        const double ld = s_ld[r];
+        if (rb == 0) { ko = dv; tl += ld * dv * dv; }
+        else tl += dv * (ld * dv + 2.0 * s_lo[r] * ko);
+      }
+      if (++rb == mblk) { rb = 0; ++qs; }
+    }
+  }
+  if (live) {
+    mu_part[(size_t)blockIdx.y * M + c] = finite ? mu : NAN;
+    if (t_part) t_part[(size_t)blockIdx.y * M + c] = finite ? tl : NAN;
+  }
+}
+
 // Y = G K* ; slab[mt][c] = sum over the BM rows of tile mt of Y[i,c]^2
 // EDGE: an edge-form operator (H lower triangular, zero in its first n_q rows and columns).  G and Kt then arrive offset
 // by kshift = n_q rounded down to the chunk depth (G + kshift, Kt + kshift ldk): the K loop starts at 0 of the shifted
@@ -1635,6 +1850,43 @@ int launch_kstar_slope(const ppbo_model* m, const KernParams& p, const double* d
   return 0;
 }
 
+// kstar_curv_kernel in the same buckets and geometry: d_X the points, d_Xi the directions, d_Xa the accelerations or
+// nullptr (the caller has refused d_Xa with D > 16 or on the camphor kernel, and Matern-3/2 altogether)
+template <int KID>
+int launch_kstar_curv(const ppbo_model* m, const KernParams& p, const double* d_X, const double* d_Xi, const double* d_Xa,
+                      int M, double* Kt, int ldk, double* mu_part, double* t_part, int q_per_split, int n_split,
+                      bool with_lam, int edge_k0, hipStream_t s) {
+  static_assert(KID != PPBO_KERNEL_MATERN32, "no curvature for Matern-3/2");
+  dim3 grid((M + KS_THREADS - 1) / KS_THREADS, n_split);
+  const int mblk = m->m + 1, n_q = (m->N + mblk - 1) / mblk;
+  const double* ld = with_lam ? m->d_lam_diag : nullptr;
+  const double* lo = with_lam ? m->d_lam_off : nullptr;
+#define KSC_LAUNCH_AS(DP, ACC)                                                                                         \
+  kstar_curv_kernel<KID, DP, ACC><<<grid, KS_THREADS, 0, s>>>(m->d_X, m->N, m->D, p, m->d_alpha, ld, lo, mblk, d_X, d_Xi, \
+                                                              d_Xa, M, Kt, ldk, mu_part, with_lam ? t_part : nullptr,   \
+                                                              q_per_split, n_q, edge_k0)
+#define KSC_LAUNCH(DP)                                                                                                 \
+  do {                                                                                                                 \
+    if (d_Xa) KSC_LAUNCH_AS(DP, true);                                                                                 \
+    else KSC_LAUNCH_AS(DP, false);                                                                                     \
+  } while (0)
+  if constexpr (KID == PPBO_KERNEL_CAMPHOR) KSC_LAUNCH_AS(12, false);
+  else if (m->D <= 4) KSC_LAUNCH(4);
+  else if (m->D <= 6) KSC_LAUNCH(6);
+  else if (m->D <= 8) KSC_LAUNCH(8);
+  else if (m->D <= 10) KSC_LAUNCH(10);
+  else if (m->D <= 12) KSC_LAUNCH(12);
+  else if (m->D <= 16) KSC_LAUNCH(16);
+  else if (m->D <= 20) KSC_LAUNCH_AS(20, false);
+  else if (m->D <= 24) KSC_LAUNCH_AS(24, false);
+  else if (m->D <= 32) KSC_LAUNCH_AS(32, false);
+  else if (m->D <= 48) KSC_LAUNCH_AS(48, false);
+  else KSC_LAUNCH_AS(64, false);
+#undef KSC_LAUNCH
+#undef KSC_LAUNCH_AS
+  return 0;
+}
+
 int check_model(ppbo_ctx* ctx, const ppbo_model* m) {
   PPBO_REQUIRE(ctx, m != nullptr, "model");
   PPBO_REQUIRE(ctx, m->d_X && m->d_alpha, "model X/alpha");
@@ -1826,15 +2078,29 @@ int ppbo_predict_record(ppbo_ctx* ctx, const ppbo_model* model, const double* d_
 // the same values (mean, variance, probability).
 static_assert(PPBO_SLOPE_MEAN == PPBO_PAIR_MEAN && PPBO_SLOPE_VARIANCE == PPBO_PAIR_VARIANCE && PPBO_SLOPE_PROB == PPBO_PAIR_PROB,
               "one score_kind check for both entries");
-static int two_set_passes(ppbo_ctx* ctx, const bool slopes, const ppbo_model* model, const double* d_Xa, const double* d_Xb,
-                          int64_t M, int score_kind, double* d_mu, double* d_var, double* d_prob, double* d_score,
-                          double* h_best_val, int64_t* h_best_idx, hipStream_t s) {
+// Curvatures (ppbo_predict_curvatures) are the third user: a point, a direction and optionally an acceleration per
+// column, kstar_curv -> quadform -> curv_score.
+static_assert(PPBO_CURV_MEAN == PPBO_PAIR_MEAN && PPBO_CURV_VARIANCE == PPBO_PAIR_VARIANCE && PPBO_CURV_PROB == PPBO_PAIR_PROB,
+              "one score_kind check for all three entries");
+enum { TS_PAIRS = 0, TS_SLOPES = 1, TS_CURV = 2 };
+static int two_set_passes(ppbo_ctx* ctx, const int what, const ppbo_model* model, const double* d_Xa, const double* d_Xb,
+                          const double* d_Xacc, int64_t M, int score_kind, double* d_mu, double* d_var, double* d_prob,
+                          double* d_score, double* h_best_val, int64_t* h_best_idx, hipStream_t s) {
+  const bool slopes = what == TS_SLOPES, curv = what == TS_CURV;
   if (int rc = check_model(ctx, model)) return rc;
-  PPBO_REQUIRE(ctx, d_Xa != nullptr && d_Xb != nullptr, slopes ? "slopes (d_X / d_Xi)" : "pairs (d_Xa / d_Xb)");
-  PPBO_REQUIRE(ctx, M >= 1 && M <= (int64_t)0x7fffffff, slopes ? "row count (1 .. 2^31 - 1)" : "pair count (1 .. 2^31 - 1)");
+  PPBO_REQUIRE(ctx, d_Xa != nullptr && d_Xb != nullptr,
+               curv ? "curvatures (d_X / d_Xi)" : slopes ? "slopes (d_X / d_Xi)" : "pairs (d_Xa / d_Xb)");
+  PPBO_REQUIRE(ctx, M >= 1 && M <= (int64_t)0x7fffffff, what != TS_PAIRS ? "row count (1 .. 2^31 - 1)" : "pair count (1 .. 2^31 - 1)");
   PPBO_REQUIRE(ctx, score_kind == PPBO_PAIR_MEAN || score_kind == PPBO_PAIR_VARIANCE || score_kind == PPBO_PAIR_PROB,
                "score_kind");
-  PPBO_REQUIRE(ctx, !model->kstar_fp32, slopes ? "slopes are fp64 only (kstar_fp32)" : "pairs are fp64 only (kstar_fp32)");
+  PPBO_REQUIRE(ctx, !model->kstar_fp32, curv ? "curvatures are fp64 only (kstar_fp32)"
+                                             : slopes ? "slopes are fp64 only (kstar_fp32)" : "pairs are fp64 only (kstar_fp32)");
+  if (curv) {
+    PPBO_REQUIRE(ctx, model->kernel_id != PPBO_KERNEL_MATERN32,
+                 "no curvature for Matern-3/2 (its sample paths are differentiable once only)");
+    PPBO_REQUIRE(ctx, d_Xacc == nullptr || (model->D <= 16 && model->kernel_id != PPBO_KERNEL_CAMPHOR),
+                 "accelerations (d_Xa): D <= 16 and not the camphor-copper kernel");
+  }
   const bool want_var = d_var || d_prob || score_kind != PPBO_PAIR_MEAN;
   PPBO_REQUIRE(ctx, !want_var || model->d_G != nullptr, "variance / probability need model->d_G");
   PPBO_REQUIRE(ctx, !want_var || (model->d_lam_diag && model->d_lam_off), "model Lambda");
@@ -1879,6 +2145,7 @@ static int two_set_passes(ppbo_ctx* ctx, const bool slopes, const ppbo_model* mo
     const int Mc = (int)((M - c_beg) < chunk_cap ? (M - c_beg) : chunk_cap);
     const double* xa = d_Xa + (size_t)c_beg * model->D;
     const double* xb = d_Xb + (size_t)c_beg * model->D;
+    const double* xacc = d_Xacc ? d_Xacc + (size_t)c_beg * model->D : nullptr;
     double* mu_part = part;
     double* t_part = part + (size_t)n_split_eff * Mc;
     double* slab = part + (size_t)2 * n_split_eff * Mc;
@@ -1888,7 +2155,11 @@ static int two_set_passes(ppbo_ctx* ctx, const bool slopes, const ppbo_model* mo
           constexpr int KID = decltype(kid)::value;
           {
             PpboProfScope pf(ctx, ppbo_ctx::PF_KSTAR, s);
-            if (slopes)
+            if (curv) {
+              if constexpr (KID != PPBO_KERNEL_MATERN32)       // refused above
+                launch_kstar_curv<KID>(model, p, xa, xb, xacc, Mc, Kt, ldk, mu_part, t_part, q_per_split, n_split_eff,
+                                       want_var, edge_k0, s);
+            } else if (slopes)
               launch_kstar_slope<KID>(model, p, xa, xb, Mc, Kt, ldk, mu_part, t_part, q_per_split, n_split_eff, want_var,
                                       edge_k0, s);
             else
@@ -1901,7 +2172,13 @@ static int two_set_passes(ppbo_ctx* ctx, const bool slopes, const ppbo_model* mo
             if (int rc2 = dispatch_quadform(ctx, Gq, Nk, g_rows, N, Kt, ldk, Mc, mblk, slab, edge_k0, s)) return rc2;
           }
           PpboProfScope pfs(ctx, ppbo_ctx::PF_SCORE, s);
-          if (slopes)
+          if (curv) {
+            if constexpr (KID != PPBO_KERNEL_MATERN32)
+              curv_score_kernel<KID><<<sblocks, SC_THREADS, 0, s>>>(
+                  mu_part, n_split_eff, t_part, want_var ? slab : nullptr, ntm, Mc, xb, xacc, model->D, p, score_kind,
+                  (long long)c_beg, d_mu ? d_mu + c_beg : nullptr, d_var ? d_var + c_beg : nullptr,
+                  d_prob ? d_prob + c_beg : nullptr, d_score ? d_score + c_beg : nullptr, want_best ? bests : nullptr);
+          } else if (slopes)
             slope_score_kernel<KID><<<sblocks, SC_THREADS, 0, s>>>(
                 mu_part, n_split_eff, t_part, want_var ? slab : nullptr, ntm, Mc, xb, model->D, p, score_kind,
                 (long long)c_beg, d_mu ? d_mu + c_beg : nullptr, d_var ? d_var + c_beg : nullptr,
@@ -1936,7 +2213,7 @@ int ppbo_predict_pairs(ppbo_ctx* ctx, const ppbo_model* model, const double* d_X
                        int score_kind, double* d_mu, double* d_var, double* d_prob, double* d_score, double* h_best_val,
                        int64_t* h_best_idx, void* stream) {
   PPBO_ENTER(ctx);
-  return two_set_passes(ctx, false, model, d_Xa, d_Xb, M, score_kind, d_mu, d_var, d_prob, d_score, h_best_val, h_best_idx,
+  return two_set_passes(ctx, TS_PAIRS, model, d_Xa, d_Xb, nullptr, M, score_kind, d_mu, d_var, d_prob, d_score, h_best_val, h_best_idx,
                         (hipStream_t)stream);
 }
 
@@ -1946,8 +2223,18 @@ int ppbo_predict_slopes(ppbo_ctx* ctx, const ppbo_model* model, const double* d_
                         int score_kind, double* d_mu, double* d_var, double* d_prob, double* d_score, double* h_best_val,
                         int64_t* h_best_idx, void* stream) {
   PPBO_ENTER(ctx);
-  return two_set_passes(ctx, true, model, d_X, d_Xi, M, score_kind, d_mu, d_var, d_prob, d_score, h_best_val, h_best_idx,
+  return two_set_passes(ctx, TS_SLOPES, model, d_X, d_Xi, nullptr, M, score_kind, d_mu, d_var, d_prob, d_score, h_best_val, h_best_idx,
                         (hipStream_t)stream);
+}
+
+// Curvatures: the column c = d^2/da^2 k(gamma(a), X) at a = 0 for the path through x with velocity xi and acceleration
+// acc (d_Xa == NULL: straight lines); the K* launches share the "kstar" profile slot.
+int ppbo_predict_curvatures(ppbo_ctx* ctx, const ppbo_model* model, const double* d_X, const double* d_Xi, const double* d_Xa,
+                            int64_t M, int score_kind, double* d_mu, double* d_var, double* d_prob, double* d_score,
+                            double* h_best_val, int64_t* h_best_idx, void* stream) {
+  PPBO_ENTER(ctx);
+  return two_set_passes(ctx, TS_CURV, model, d_X, d_Xi, d_Xa, M, score_kind, d_mu, d_var, d_prob, d_score, h_best_val,
+                        h_best_idx, (hipStream_t)stream);
 }
 
 }  // extern "C"

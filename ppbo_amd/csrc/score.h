@@ -279,6 +279,101 @@ __global__ __launch_bounds__(SC_THREADS) void slope_score_kernel(const double* _
   if (lane == 0) blk_best[blockIdx.x] = b;
 }
 
+// Pass 3 of ppbo_predict_curvatures: slope_score_kernel's plan for the column c = d^2/da^2 k(gamma(a), X) at a = 0, then
+//   mu_c = sum of the mean partials,   var_c = prior + c' Lambda c + |G c|^2,   p = P(curvature < 0) = Phi(-mu_c / sqrt(max(var_c, 0)))
+// prior = Var[d^2/da^2 f(gamma(a))] = q4 n2^2 + q2 |acc|^2 (the cross term vanishes for a stationary kernel), from two
+// sums over the dimensions, n2 = |xi|^2 and, when accelerations are given, |acc|^2 (wavefront w sums the dimensions w,
+// w + SC_WAVES, ... beside its slabs; the sums meet in wavefront order):
+//   q2 = -c(0), slope_prior_weight's constant;   q4 = 6 c'(0): 12 c0^2 sf2 (SE), 72 c0^2 sf2 (RQ), c0^4 sf2 (Matern-5/2)
+//                                                -- sf2 / l^4 times 3, 9/2, 25
+//   camphor-copper   sf2 (12 A^2 + 8 pi^4 c0 sum_{d != 2} xi_d^4), A = sum_{d != 2} pi^2 c0 xi_d^2 + c1 xi_2^2: the two
+//                    sums are A and sum xi_d^4 (no acceleration there)
+// Even in xi, so -xi leaves all three outputs bitwise unchanged.  No noise term.  var_c = 0: the sign of mu_c decides,
+// mu_c = 0 gives 1/2; a NaN mean (a non-finite coordinate) gives NaN everywhere.
+template <int KID>
+__global__ __launch_bounds__(SC_THREADS) void curv_score_kernel(const double* __restrict__ mu_part, int n_mu,
+                                                                const double* __restrict__ t_part,
+                                                                const double* __restrict__ slab, int n_slab, int M,
+                                                                const double* __restrict__ Xi, const double* __restrict__ Xa,
+                                                                int D, KernParams p, int kind, long long idx_base,
+                                                                double* __restrict__ mu_out, double* __restrict__ var_out,
+                                                                double* __restrict__ prob_out,
+                                                                double* __restrict__ score_out, Best* __restrict__ blk_best) {
+  static_assert(KID != PPBO_KERNEL_MATERN32, "no curvature for Matern-3/2");
+  __shared__ double part[5][SC_WAVES][SC_CAND];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int c = blockIdx.x * SC_CAND + lane;
+  double pm = 0.0, pt = 0.0, pq = 0.0, ps = 0.0, pa = 0.0;
+  if (c < M) {
+    for (int s = wave; s < n_mu; s += SC_WAVES) pm += mu_part[(size_t)s * M + c];
+    if (slab) {
+      for (int s = wave; s < n_mu; s += SC_WAVES) pt += t_part[(size_t)s * M + c];
+      for (int s = wave; s < n_slab; s += SC_WAVES) pq += slab[(size_t)s * M + c];
+      for (int d = wave; d < D; d += SC_WAVES) {
+        const double w = Xi[(size_t)c * D + d];
+        if constexpr (KID == PPBO_KERNEL_CAMPHOR) {
+          const double w2 = w * w;
+          ps += (d == 2 ? p.c1 : 9.86960440108935861883 * p.c0) * w2;      // pi^2
+          if (d != 2) pa += w2 * w2;
+        } else {
+          ps += w * w;
+          if (Xa) {
+            const double a = Xa[(size_t)c * D + d];
+            pa += a * a;
+          }
+        }
+      }
+    }
+  }
+  part[0][wave][lane] = pm;
+  part[1][wave][lane] = pt;
+  part[2][wave][lane] = pq;
+  part[3][wave][lane] = ps;
+  part[4][wave][lane] = pa;
+  __syncthreads();
+  if (wave != 0) return;                 // the rest is one wavefront's work
+  Best b{0.0, -1};
+  if (c < M) {
+    double mu = 0.0, t = 0.0, q = 0.0, s = 0.0, a = 0.0;
+#pragma unroll
+    for (int w = 0; w < SC_WAVES; ++w) {
+      mu += part[0][w][lane]; t += part[1][w][lane]; q += part[2][w][lane]; s += part[3][w][lane]; a += part[4][w][lane];
+    }
+    double var = NAN, pr = NAN, sc = mu;   // mean only (no slab): nothing but mu is formed
+    if (slab) {
+      double prior;
+      if constexpr (KID == PPBO_KERNEL_CAMPHOR) {
+        prior = p.sf2 * fma(12.0 * s, s, (779.27272827201949789152 * p.c0) * a);       // 8 pi^4
+      } else {
+        const double c02 = p.c0 * p.c0;
+        const double q4 = KID == PPBO_KERNEL_SE ? 12.0 * c02 * p.sf2 : (KID == PPBO_KERNEL_RQ ? 72.0 * c02 * p.sf2 : c02 * c02 * p.sf2);
+        prior = fma(q4 * s, s, slope_prior_weight<KID>(0, p) * a);
+      }
+      var = prior + t + q;
+      const double sd = sqrt(fmax(var, 0.0));
+      // sd = 0 (no variance): the sign of mu_c decides, a tie is 1/2
+      pr = norm_cdf(sd > 0.0 ? -mu / sd : (mu > 0.0 ? -INFINITY : (mu < 0.0 ? INFINITY : 0.0)));
+      if (mu != mu) { var = mu; pr = mu; }
+      if (kind == PPBO_CURV_VARIANCE) sc = var;
+      else if (kind == PPBO_CURV_PROB) sc = pr;
+    }
+    if (mu_out) mu_out[c] = mu;
+    if (var_out) var_out[c] = var;
+    if (prob_out) prob_out[c] = pr;
+    if (score_out) score_out[c] = sc;
+    if (sc == sc) { b.val = sc; b.idx = idx_base + c; }
+  }
+  if (!blk_best) return;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    Best other;
+    other.val = __shfl_xor(b.val, o, 64);
+    other.idx = __shfl_xor(b.idx, o, 64);
+    b = best_merge(b, other);
+  }
+  if (lane == 0) blk_best[blockIdx.x] = b;
+}
+
 // per-block records of one launch -> *out; with `record` also the 16-byte (value, GLOBAL index as a double: exact
 // below 2^53; index + record_offset; (NaN, -1) when nothing scored) record that the sharded search all-gathers, and
 // with `publish` the flag publish[0] raised to `epoch` AFTER the record with system-scope release semantics (the

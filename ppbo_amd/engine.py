@@ -12,6 +12,7 @@ from . import _lib
 from ._lib import KERNEL_IDS, SCORE_MEAN, SCORE_POINTWISE_EI, SCORE_VARIANCE, PPBO_ERR_NOT_PD  # noqa: F401
 from ._lib import PAIR_MEAN, PAIR_VARIANCE, PAIR_PROB  # noqa: F401
 from ._lib import SLOPE_MEAN, SLOPE_VARIANCE, SLOPE_PROB  # noqa: F401
+from ._lib import CURV_MEAN, CURV_VARIANCE, CURV_PROB  # noqa: F401
 
 # Posterior.form: which variance operator G holds (include/ppbo_hip.h, PPBO_FORM_*)
 FORM_NODE = 0   # G = R Lambda, block lower triangular [N, N]
@@ -61,6 +62,22 @@ def camphor_embed_directions(X, Xi, ls):
         else:
             w = 2.0 * np.pi * Xi[:, d] / ls[d]
             cols += [-np.sin(2.0 * np.pi * X[:, d]) * w, np.cos(2.0 * np.pi * X[:, d]) * w]
+    return np.stack(cols, axis=1)
+
+
+def camphor_embed_accelerations(X, Xi, ls):
+    """d^2 e(x_i + a xi_i) / da^2 at a = 0 [M, 11], beside camphor_embed_directions: a straight line in the caller's six
+    coordinates is a curved path in the embedding's eleven.  Each periodic pair (c_d, s_d) = (cos, sin)(2 pi x_d) / l_d is
+    scaled by -(2 pi xi_d)^2; the z column is 0.  NumPy in and out."""
+    X, Xi = np.asarray(X, dtype=np.float64), np.asarray(Xi, dtype=np.float64)
+    ls = np.asarray(ls, dtype=np.float64)
+    cols = []
+    for d in range(6):
+        if d == 2:
+            cols.append(np.zeros(X.shape[0]))
+        else:
+            w = -(2.0 * np.pi * Xi[:, d]) ** 2 / ls[d]
+            cols += [np.cos(2.0 * np.pi * X[:, d]) * w, np.sin(2.0 * np.pi * X[:, d]) * w]
     return np.stack(cols, axis=1)
 
 
@@ -743,6 +760,38 @@ class Engine:
                                           _ptr(pr), _ptr(sc), C.byref(bv) if want_best else None,
                                           C.byref(bi) if want_best else None, self._stream())
         self._check(rc, "ppbo_predict_slopes")
+        return dict(mu=mu, var=var, prob=pr, score=sc, best_val=bv.value, best_idx=bi.value)
+
+    def predict_curvatures(self, post: Posterior, X, Xi, score=CURV_PROB, want_mu=True, want_var=True, want_prob=True,
+                           want_score=False, want_best=True):
+        """Curvatures (ppbo_predict_curvatures): for the M rows (X[i], Xi[i]) in the caller's coordinates the posterior
+        mean and variance of d^2/da^2 f(x + a xi) at a = 0 and p = P(curvature < 0), as device tensors mu / var / prob /
+        score (None where not asked for), with best_val / best_idx = the largest score (the quantity `score` names) and
+        its first row.  CURV_MEAN without var and prob needs no variance operator.  A Matern-3/2 posterior is refused:
+        the curvature of its sample paths has no finite variance.  camphor_copper_ard_kernel: the line x + a xi is a
+        curved path in the embedding, whose acceleration is formed on the host and passed as d_Xa."""
+        M = self._pair_shapes(post, X, Xi, "predict_curvatures", "points and directions", "rows")
+        if score not in (CURV_MEAN, CURV_VARIANCE, CURV_PROB):
+            raise ValueError(f"predict_curvatures: unknown score kind {score}")
+        if post.kernel == "Matern32_kernel":
+            raise ValueError("predict_curvatures: no curvature for Matern32_kernel (its sample paths are differentiable once only)")
+        Xa = None
+        if post.camphor is not None:
+            to_host = lambda a: a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a, dtype=np.float64)  # noqa: E731
+            Xa = self.dev(camphor_embed_accelerations(to_host(X), to_host(Xi), post.camphor))
+        Xi = self._directions(post, X, Xi)
+        X = self._points(post, X)
+        with_var = want_var or want_prob or score != CURV_MEAN
+        md = self._model(post, with_var)
+        mu = self.empty(M) if want_mu else None
+        var = self.empty(M) if want_var else None
+        pr = self.empty(M) if want_prob else None
+        sc = self.empty(M) if want_score else None
+        bv, bi = C.c_double(0.0), C.c_int64(-1)
+        rc = self.lib.ppbo_predict_curvatures(self.ctx, C.byref(md), _ptr(X), _ptr(Xi), _ptr(Xa), M, int(score), _ptr(mu),
+                                              _ptr(var), _ptr(pr), _ptr(sc), C.byref(bv) if want_best else None,
+                                              C.byref(bi) if want_best else None, self._stream())
+        self._check(rc, "ppbo_predict_curvatures")
         return dict(mu=mu, var=var, prob=pr, score=sc, best_val=bv.value, best_idx=bi.value)
 
     def predict_cov(self, post: Posterior, Xc, shrink=SHRINKAGE):

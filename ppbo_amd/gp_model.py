@@ -899,6 +899,43 @@ class GPModel:
         x = np.asarray(self.xstar if x is None else x, dtype=float).reshape(-1)
         return self.slope_pred(np.tile(x, (x.size, 1)), np.eye(x.size))
 
+    def curvature_pred(self, X, Xi):
+        """(mu_c, var_c, p) as NumPy arrays for the rows (X[i], Xi[i]): the posterior mean and variance of the curvature
+        d^2/da^2 f(x + a xi) at a = 0 and p = P(curvature < 0) = Phi(-mu_c / sqrt(var_c)), without a noise term
+        (ppbo_predict_curvatures; no reference counterpart).  Input conventions and errors as slope_pred; a Matern-3/2
+        model is refused with a ValueError (the curvature of its sample paths has no finite variance)."""
+        post = self._var_post()
+        X, Xi = (a if isinstance(a, torch.Tensor) else np.asarray(a, dtype=float) for a in (X, Xi))
+        X, Xi = (a.reshape(1, -1) if a.ndim == 1 else a for a in (X, Xi))
+        out = self.eng.predict_curvatures(post, X, Xi, want_best=False)
+        return out["mu"].cpu().numpy(), out["var"].cpu().numpy(), out["prob"].cpu().numpy()
+
+    def sharpness(self, x=None):
+        """The D coordinate curvatures at x (default: xstar, where sensitivity() reads "settled" by construction) as three
+        length-D NumPy arrays (mu_c, var_c, p): row d is curvature_pred(x, e_d).  p near 1 with a large |mu_c|: a
+        confirmed, sharp peak in that parameter; p near 1/2: the model cannot tell a peak from a plateau there."""
+        x = np.asarray(self.xstar if x is None else x, dtype=float).reshape(-1)
+        return self.curvature_pred(np.tile(x, (x.size, 1)), np.eye(x.size))
+
+    def mean_hessian(self, x=None):
+        """The symmetric D x D Hessian of the posterior mean at x (default: xstar), by polarisation from the D (D + 1) / 2
+        mean curvatures along e_a and e_a + e_b: H_ab = (mu_c(e_a + e_b) - mu_c(e_a) - mu_c(e_b)) / 2.  Needs no variance
+        operator (a posterior without G serves; no posterior at all is _var_post's error).  Its eigenvalues tell a peak
+        from a ridge or a saddle."""
+        post = self._post if getattr(self, "_post", None) is not None else self._var_post()
+        x = np.asarray(self.xstar if x is None else x, dtype=float).reshape(-1)
+        D = x.size
+        ia, ib = np.triu_indices(D)
+        E = np.eye(D)
+        Xi = np.where((ia == ib)[:, None], E[ia], E[ia] + E[ib])
+        mu = self.eng.predict_curvatures(post, np.tile(x, (ia.size, 1)), Xi, score=0, want_var=False, want_prob=False,
+                                         want_best=False)["mu"].cpu().numpy()
+        H = np.zeros((D, D))
+        diag = mu[ia == ib]
+        H[ia, ib] = np.where(ia == ib, mu, 0.5 * (mu - diag[ia] - diag[ib]))
+        H[ib, ia] = H[ia, ib]
+        return H
+
     def _choice_draws(self, n_draws, G, noisy, seed):
         """(z, e, noise_sd) of answer_pred / choice_pred: one ppbo_randn stream of 2 S G normals per seed, the first S G
         of them z, the next S G the likelihood's noise e (drawn whether or not it is used, so that the paths of a seed
