@@ -458,6 +458,41 @@ PPBO_API int ppbo_predict_curvatures(ppbo_ctx* ctx, const ppbo_model* model, con
                         const double* d_Xa, int64_t M, int score_kind, double* d_mu, double* d_var, double* d_prob,
                         double* d_score, double* h_best_val, int64_t* h_best_idx, void* stream);
 
+/* ---- averages and contrasts: mean, variance and sign of L f = sum_g w_g f(x_g) for M groups of G points ---------------
+ * The general linear functional of the utility over a small group of points (no reference counterpart: the only route
+ * there is w' Sigma w through the dense covariance of mu_Sigma_pred, :441-452).  Averages (all weights 1 / G: the
+ * utility of a design under implementation tolerance, along a segment, over contexts) and contrasts (sum w = 0: is
+ * shortlist A better than shortlist B on average, is x better than the mean of its neighbours, any difference
+ * stencil).  With the column c = sum_g w_g k(x_g, X):
+ *   mu  = c' alpha
+ *   var = w' K w + c' Lambda c + |G c|^2                             (the operator of ppbo_posterior on c)
+ *   w' K w = sigma_f^2 (sum_g w_g)^2 - 2 sum_{g < h} w_g w_h (sigma_f^2 - k(x_g, x_h)),  the bracket from the direct
+ *           differences x_g - x_h in the non-cancelling form of ppbo_predict_pairs' prior term; NOT shrunk
+ *   p   = P(L f > threshold) = Phi((mu - threshold) / sqrt(max(var, 0)));  no noise term (as for slopes);
+ *           var = 0: the sign of mu - threshold decides, equality gives 1/2
+ * ONE contraction per group, whatever G is.  Every point of a group meets a design row in the same instruction chain
+ * and the column is accumulated as fma(w_g, k, c) in the order of g: two identical points get the same kernel bits
+ * (G = 2, w = (1, -1), a == b gives (0, 0, 1/2) exactly), all-zero weights give (0, 0, 1/2), -w negates mu bit for bit
+ * and leaves var bitwise unchanged, 2 w gives exactly 2 mu and 4 var.  No atomics and a fixed order of every sum: a
+ * call is bitwise repeatable and a group's results do not depend on its place in the call.
+ * d_Xg [M, G, D]: the groups in the MODEL's coordinates, as ppbo_predict_pairs takes its sides.  d_w: the weights,
+ * w_stride = 0: one row w[G] for all groups, w_stride = G: w[M, G].  Outputs, each may be NULL: d_mu, d_var, d_prob,
+ * d_score [M] (the quantity score_kind names) and h_best_val / h_best_idx, the largest score and its FIRST index; NaN
+ * never wins, (NaN, -1) when nothing scored.  A group with a NaN or infinite coordinate gets NaN outputs whatever its
+ * weights; the other groups do not see it.  PPBO_FUNCTIONAL_MEAN with d_var == d_prob == NULL reads neither d_G nor
+ * Lambda and runs no contraction.  Groups go in chunks of 65536 through ppbo_predict's workspaces (kstar_func_kernel on
+ * the fp64 matrix cores -- camphor-copper, id 2: a vector kernel in the feature form --, the quadform kernel of
+ * ppbo_predict, functional_score_kernel); both operator forms take the same three launches, whatever N.  The K* launch
+ * is timed under the "kstar" name of ppbo_profile_read.
+ * "invalid argument": everything ppbo_predict_pairs refuses (a NULL model; M outside 1 .. 2^31 - 1; an unknown
+ * score_kind; model->kstar_fp32; a model without d_G or Lambda when more than the mean is asked for); a NULL d_Xg or
+ * d_w; G outside 1 .. PPBO_FUNCTIONAL_MAX_G; w_stride other than 0 or G; a threshold that is not finite. */
+#define PPBO_FUNCTIONAL_MAX_G 64
+enum { PPBO_FUNCTIONAL_MEAN = 0, PPBO_FUNCTIONAL_VARIANCE = 1, PPBO_FUNCTIONAL_PROB = 2 };
+PPBO_API int ppbo_predict_functionals(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xg, const double* d_w,
+                        int w_stride, int64_t M, int G, double threshold, int score_kind, double* d_mu, double* d_var,
+                        double* d_prob, double* d_score, double* h_best_val, int64_t* h_best_idx, void* stream);
+
 /* full predictive covariance of small sets (the G=70 line grid of EI):
  * d_cov[M,M] = (1-s)K(Xc,Xc) + s sigma_f^2 I - K*^T A K*  (src/gp_model.py:447-450) */
 PPBO_API int ppbo_predict_cov(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc, int M,

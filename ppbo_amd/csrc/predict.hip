@@ -618,6 +618,282 @@ __global__ __launch_bounds__(KS_THREADS) void kstar_pair_kernel(
   }
 }
 
+// Pass 1 of ppbo_predict_functionals: the column of a LINEAR FUNCTIONAL L f = sum_g w_g f(x_g) over a group of G points,
+// c_j = sum_g w_g k(x_g, x_j), in place of k*.  G points of up to 64 coordinates do not fit one lane's registers, so the
+// radial kernels form their kernel values on the matrix cores (path_half's lane layout, pathwise.hip): a wavefront owns
+// 16 groups, the workgroup's four wavefronts 64, and all walk the design rows of their row split in staged slabs of
+// KF_RJ = 32.  Per slab the A fragments of its two 16-row tiles (design rows x dimensions, from LDS) stay in registers;
+// for g = 0 .. G - 1 in order the B fragment is the g-th point of the wavefront's 16 groups (read from global memory:
+// DP / 4 loads per lane, |x_g|^2 by two lane exchanges), v_mfma_f64_16x16x4_f64 with the accumulator started at
+// -|x_j|^2 / 2 gives x_j.x_g - |x_j|^2 / 2, r^2 = max(|x_g|^2 - 2 (that), 0) -- kstar_pair_kernel's expansion form --
+// then kern_finish and col = fma(w_g, k, col).  Register r of lane (lr, lk) is row lk + 4 r of group lr for every g, so
+// the column accumulates in place with no lane movement, and every g takes the same instruction chain: two identical
+// points of a group get the same bits, -w negates the column bit for bit and 2 w doubles it.
+// The tail is kstar_pair_kernel's, on the finished slab: the mean sum, the star sums of c' Lambda c and the node- or
+// edge-form store to Kt in that kernel's layouts and row splits.  Each lane keeps the rows it already holds (four
+// consecutive rows x 16 groups = 128-byte pieces per store instruction); only ko, the value of the row's observation
+// row, comes from elsewhere: every wavefront posts its slab of the column in a private LDS tile whose slot 0 carries the
+// last observation row of the slabs before (a row split starts on a star's edge, so the slot is written before it is
+// read).  Sums: each lane adds its rows in index order, the four row phases lk of a group meet by two exchanges in a
+// fixed order; no atomics, so a call is bitwise repeatable and a group's results do not depend on its place in the call.
+// A group with a non-finite coordinate leaves as NaN partial sums whatever its weights.  fp64 only.
+constexpr int KF_RJ = 32;        // design rows per slab (two MFMA row tiles)
+constexpr int KF_GROUPS = 64;    // groups per workgroup (16 per wavefront)
+template <int KID, int DP>
+__global__ __launch_bounds__(256) void kstar_func_kernel(
+    const double* __restrict__ X, int N, int D, KernParams p, const double* __restrict__ alpha,
+    const double* __restrict__ lam_diag, const double* __restrict__ lam_off, int mblk,
+    const double* __restrict__ Xg, const double* __restrict__ W, int w_stride, int G, int M, double* __restrict__ Kt,
+    int ldk, double* __restrict__ mu_part, double* __restrict__ t_part, int q_per_split, int n_q, int edge_k0) {
+  static_assert(kid_radial<KID> && DP % 4 == 0, "radial kernels, whole k-steps of 4");
+  constexpr int Q = DP / 4, LD = DP + 2, T = KF_RJ / 16, LC = 17;
+  __shared__ __attribute__((aligned(16))) double ws[KF_RJ * LD];
+  __shared__ double s_h[KF_RJ], s_alpha[KF_RJ], s_ld[KF_RJ], s_lo[KF_RJ];
+  __shared__ double colS[4][KF_RJ + 1][LC];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, lr = lane & 15, lk = lane >> 4;
+  const int c = blockIdx.x * KF_GROUPS + wv * 16 + lr;
+  const bool live = c < M;
+  const double* __restrict__ xg0 = Xg + (size_t)(live ? c : 0) * G * D;
+  const double* __restrict__ wp = W + (size_t)(live ? c : 0) * w_stride;
+  double mu = 0.0, tl = 0.0, chk = 0.0;
+  const int j_beg = blockIdx.y * q_per_split * mblk;
+  int j_end = j_beg + q_per_split * mblk;
+  if (j_end > N) j_end = N;
+  const bool has_lam = (lam_diag != nullptr);
+  for (int row0 = j_beg; row0 < j_end; row0 += KF_RJ) {
+    __syncthreads();
+    for (int e = threadIdx.x; e < KF_RJ * DP; e += 256) {
+      const int r = e / DP, d = e - r * DP;
+      const int j = row0 + r;
+      ws[r * LD + d] = (j < j_end && d < D) ? X[(size_t)j * D + d] : 0.0;
+    }
+    if (threadIdx.x < KF_RJ) {
+      const int j = row0 + threadIdx.x;
+      const bool ok = j < j_end;
+      s_alpha[threadIdx.x] = ok ? alpha[j] : 0.0;
+      s_ld[threadIdx.x] = (ok && has_lam) ? lam_diag[j] : 0.0;
+      s_lo[threadIdx.x] = (ok && has_lam) ? lam_off[j] : 0.0;
+      double nx = 0.0;
+      if (ok)
+        for (int d = 0; d < D; ++d) { const double v = X[(size_t)j * D + d]; nx = fma(v, v, nx); }
+      s_h[threadIdx.x] = -0.5 * nx;
+    }
+    __syncthreads();
+    double af[T][Q], hr[T][4];
+    double4_t col[T];
+#pragma unroll
+    for (int t = 0; t < T; ++t) {
+#pragma unroll
+      for (int kk = 0; kk < Q; ++kk) af[t][kk] = ws[(16 * t + lr) * LD + kk * 4 + lk];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) hr[t][r] = s_h[16 * t + lk + 4 * r];
+      col[t] = double4_t{0.0, 0.0, 0.0, 0.0};
+    }
+#pragma unroll 1
+    for (int g = 0; g < G; ++g) {
+      double xb[Q], xn = 0.0;
+#pragma unroll
+      for (int kk = 0; kk < Q; ++kk) {
+        const int d = kk * 4 + lk;
+        xb[kk] = (d < D && live) ? xg0[(size_t)g * D + d] : 0.0;
+        xn = fma(xb[kk], xb[kk], xn);
+      }
+      // |x_g|^2: the four lanes (lr, 0..3) hold the coordinates of group lr's point between them
+      xn += __shfl_xor(xn, 16, 64);
+      xn += __shfl_xor(xn, 32, 64);
+      chk = fma(xn, 0.0, chk);             // NaN once a coordinate is not finite
+      const double wg = live ? wp[g] : 0.0;
+#pragma unroll
+      for (int t = 0; t < T; ++t) {
+        double4_t ph = double4_t{hr[t][0], hr[t][1], hr[t][2], hr[t][3]};
+#pragma unroll
+        for (int kk = 0; kk < Q; ++kk) ph = __builtin_amdgcn_mfma_f64_16x16x4f64(af[t][kk], xb[kk], ph, 0, 0, 0);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          double kv = kern_finish<KID>(fmax(fma(-2.0, ph[r], xn), 0.0), p);
+          // an opaque register: the product that ends kern_finish must not be contracted into the accumulation
+          // (kstar_pair_kernel)
+          asm volatile("" : "+v"(kv));
+          col[t][r] = fma(wg, kv, col[t][r]);
+        }
+      }
+    }
+#pragma unroll
+    for (int t = 0; t < T; ++t)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) colS[wv][1 + 16 * t + lk + 4 * r][lr] = col[t][r];
+    __syncthreads();
+#pragma unroll
+    for (int t = 0; t < T; ++t)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int jr = 16 * t + lk + 4 * r, j = row0 + jr;
+        if (j >= j_end) continue;
+        const int qs = j / mblk, rb = j - qs * mblk;     // the row's star and its index inside it
+        const double dv = col[t][r];
+        const int jo = jr - rb;                          // the star's observation row: in this slab, or carried in slot 0
+        const double ko = colS[wv][jo >= 0 ? jo + 1 : 0][lr];
+        if (Kt) {
+          // the layouts of kstar_kernel: node form row j, edge form row n_q + q m + t = lam_off[j] (c_j - c_obs)
+          int drow = j;
+          bool wr = true;
+          double ev = dv;
+          if (edge_k0 >= 0) {
+            if (rb == 0) {
+              drow = qs;
+              wr = qs >= edge_k0;
+              ev = 0.0;
+            } else {
+              drow = n_q + qs * (mblk - 1) + rb - 1;
+              ev = s_lo[jr] * (dv - ko);
+            }
+          }
+          if (wr && live) store_through(Kt + (size_t)drow * ldk + c, ev);
+        }
+        mu += s_alpha[jr] * dv;
+        if (has_lam) {
+          const double ld = s_ld[jr];
+          if (rb == 0) tl += ld * dv * dv;
+          else tl += dv * (ld * dv + 2.0 * s_lo[jr] * ko);
+        }
+      }
+    __syncthreads();
+    {
+      // carry the slab's last observation row (if it holds one) into slot 0 for the slabs that follow
+      const int j_hi = (row0 + KF_RJ < j_end ? row0 + KF_RJ : j_end) - 1;
+      const int j_obs = (j_hi / mblk) * mblk;
+      if (j_obs >= row0 && lk == 0) colS[wv][0][lr] = colS[wv][j_obs - row0 + 1][lr];
+    }
+  }
+  mu += __shfl_xor(mu, 16, 64);
+  mu += __shfl_xor(mu, 32, 64);
+  tl += __shfl_xor(tl, 16, 64);
+  tl += __shfl_xor(tl, 32, 64);
+  if (live && lk == 0) {
+    const bool finite = chk == 0.0;
+    mu_part[(size_t)blockIdx.y * M + c] = finite ? mu : NAN;
+    if (t_part) t_part[(size_t)blockIdx.y * M + c] = finite ? tl : NAN;
+  }
+}
+
+// The camphor-copper instance of that pass: a plain vector kernel in kstar_pair_kernel's feature form (the kernel's
+// exponent is no squared distance of the raw coordinates).  One lane = ONE group; per staged slab of KS_RJ rows the
+// lane walks its G points in order -- the twelve feature values of a point formed from its six coordinates each time,
+// ten sincospi per (point, slab) against 32 rows x 12 FMAs + 32 exponentials -- and accumulates col[r] = fma(w_g, k, col[r])
+// in registers; then kstar_pair_kernel's sequential tail, one lane per group.
+__global__ __launch_bounds__(KS_THREADS) void kstar_func_camphor_kernel(
+    const double* __restrict__ X, int N, int D, KernParams p, const double* __restrict__ alpha,
+    const double* __restrict__ lam_diag, const double* __restrict__ lam_off, int mblk,
+    const double* __restrict__ Xg, const double* __restrict__ W, int w_stride, int G, int M, double* __restrict__ Kt,
+    int ldk, double* __restrict__ mu_part, double* __restrict__ t_part, int q_per_split, int n_q, int edge_k0) {
+  constexpr int KID = PPBO_KERNEL_CAMPHOR, DP = 12;
+  __shared__ __attribute__((aligned(16))) double xs[KS_RJ * DP];
+  __shared__ double s_alpha[KS_RJ], s_ld[KS_RJ], s_lo[KS_RJ];
+  const int c = blockIdx.x * KS_THREADS + threadIdx.x;
+  const bool live = c < M;
+  const double* __restrict__ xg0 = Xg + (size_t)(live ? c : 0) * G * D;
+  const double* __restrict__ wp = W + (size_t)(live ? c : 0) * w_stride;
+  double mu = 0.0, tl = 0.0, ko = 0.0;
+  const int j_beg = blockIdx.y * q_per_split * mblk;
+  int j_end = j_beg + q_per_split * mblk;
+  if (j_end > N) j_end = N;
+  const bool has_lam = (lam_diag != nullptr);
+  int rb = 0, qs = j_beg / mblk;
+  for (int row0 = j_beg; row0 < j_end; row0 += KS_RJ) {
+    __syncthreads();
+    for (int e = threadIdx.x; e < KS_RJ * 6; e += KS_THREADS) {
+      const int r = e / 6, k = e - r * 6;
+      const int j = row0 + r;
+      if (k < 5) {
+        const double v = (j < j_end) ? X[(size_t)j * D + (k < 2 ? k : k + 1)] : 0.0;
+        double sn, cs;
+        sincospi(2.0 * v, &sn, &cs);
+        xs[r * DP + k] = cs;
+        xs[r * DP + 5 + k] = sn;
+      } else {
+        xs[r * DP + 10] = (j < j_end) ? X[(size_t)j * D + 2] : 0.0;
+        xs[r * DP + 11] = 0.0;
+      }
+    }
+    if (threadIdx.x < KS_RJ) {
+      const int j = row0 + threadIdx.x;
+      const bool ok = j < j_end;
+      s_alpha[threadIdx.x] = ok ? alpha[j] : 0.0;
+      s_ld[threadIdx.x] = (ok && has_lam) ? lam_diag[j] : 0.0;
+      s_lo[threadIdx.x] = (ok && has_lam) ? lam_off[j] : 0.0;
+    }
+    __syncthreads();
+    double col[KS_RJ];
+#pragma unroll
+    for (int r = 0; r < KS_RJ; ++r) col[r] = 0.0;
+#pragma unroll 1
+    for (int g = 0; g < G; ++g) {
+      const double* __restrict__ src = xg0 + (size_t)g * D;
+      double xc[11];
+#pragma unroll
+      for (int k = 0; k < 5; ++k) {
+        const double v = live ? src[k < 2 ? k : k + 1] : 0.0;
+        double sn, cs;
+        sincospi(2.0 * v, &sn, &cs);
+        xc[k] = -0.5 * p.c0 * cs;
+        xc[5 + k] = -0.5 * p.c0 * sn;
+      }
+      xc[10] = live ? src[2] : 0.0;
+      const double wg = live ? wp[g] : 0.0;
+      const double base = 2.5 * p.c0;
+#pragma unroll
+      for (int r = 0; r < KS_RJ; ++r) {
+        const double* __restrict__ xr = xs + r * DP;
+        double sv = 0.0;
+#pragma unroll
+        for (int d = 0; d < 10; ++d) sv = fma(xr[d], xc[d], sv);
+        const double dd = xr[10] - xc[10];
+        sv = fma(p.c1 * dd, dd, sv + base);
+        double kv = kern_finish<KID>(sv, p);
+        asm volatile("" : "+v"(kv));
+        col[r] = fma(wg, kv, col[r]);
+      }
+    }
+    const int rmax = (j_end - row0 < KS_RJ) ? (j_end - row0) : KS_RJ;
+#pragma unroll
+    for (int r = 0; r < KS_RJ; ++r) {
+      if (r < rmax) {
+        const double dv = col[r];
+        if (Kt) {
+          int drow = row0 + r;
+          bool wr = true;
+          double ev = dv;
+          if (edge_k0 >= 0) {
+            if (rb == 0) {
+              drow = qs;
+              wr = qs >= edge_k0;
+              ev = 0.0;
+            } else {
+              drow = n_q + qs * (mblk - 1) + rb - 1;
+              ev = s_lo[r] * (dv - ko);
+            }
+          }
+          if (wr && live) store_through(Kt + (size_t)drow * ldk + c, ev);
+        }
+        mu += s_alpha[r] * dv;
+        if (has_lam) {
+          const double ld = s_ld[r];
+          if (rb == 0) { ko = dv; tl += ld * dv * dv; }
+          else tl += dv * (ld * dv + 2.0 * s_lo[r] * ko);
+        }
+        if (++rb == mblk) { rb = 0; ++qs; }
+      }
+    }
+  }
+  if (live) {
+    double chk = 0.0;
+    for (int e = 0; e < G * D; ++e) chk = fma(xg0[e], 0.0, chk);
+    const bool finite = chk == 0.0;
+    mu_part[(size_t)blockIdx.y * M + c] = finite ? mu : NAN;
+    if (t_part) t_part[(size_t)blockIdx.y * M + c] = finite ? tl : NAN;
+  }
+}
+
 // d k / d r^2 times 2: the c with grad_x k(x, x') = c (x - x') at r^2 = s, finite at s = 0 (SE / RQ: kern_grad_coef's forms
 // on the value itself, Matern: matern_grad) -- never (dk/dr) / r
 template <int KID>
@@ -1887,6 +2163,42 @@ int launch_kstar_curv(const ppbo_model* m, const KernParams& p, const double* d_
   return 0;
 }
 
+// ppbo_predict_functionals' extra operands: the groups are two_set_passes' first point set ([M, G, D]), the weights its second
+struct FuncArgs {
+  int G, w_stride;
+  double threshold;
+};
+
+// kstar_func_kernel in five D buckets (whole MFMA k-steps of 4 dimensions; KF_GROUPS groups per workgroup), the camphor
+// instance as a vector kernel with KS_THREADS groups per workgroup; n_split row splits as launch_kstar_pair
+template <int KID>
+int launch_kstar_func(const ppbo_model* m, const KernParams& p, const double* d_Xg, const double* d_w, const FuncArgs& fa,
+                      int M, double* Kt, int ldk, double* mu_part, double* t_part, int q_per_split, int n_split,
+                      bool with_lam, int edge_k0, hipStream_t s) {
+  const int mblk = m->m + 1, n_q = (m->N + mblk - 1) / mblk;
+  const double* ld = with_lam ? m->d_lam_diag : nullptr;
+  const double* lo = with_lam ? m->d_lam_off : nullptr;
+  if constexpr (KID == PPBO_KERNEL_CAMPHOR) {
+    dim3 grid((M + KS_THREADS - 1) / KS_THREADS, n_split);
+    kstar_func_camphor_kernel<<<grid, KS_THREADS, 0, s>>>(m->d_X, m->N, m->D, p, m->d_alpha, ld, lo, mblk, d_Xg, d_w,
+                                                          fa.w_stride, fa.G, M, Kt, ldk, mu_part,
+                                                          with_lam ? t_part : nullptr, q_per_split, n_q, edge_k0);
+  } else {
+    dim3 grid((M + KF_GROUPS - 1) / KF_GROUPS, n_split);
+#define KSF_LAUNCH(DP)                                                                                                  \
+  kstar_func_kernel<KID, DP><<<grid, 256, 0, s>>>(m->d_X, m->N, m->D, p, m->d_alpha, ld, lo, mblk, d_Xg, d_w, fa.w_stride, \
+                                                  fa.G, M, Kt, ldk, mu_part, with_lam ? t_part : nullptr, q_per_split,  \
+                                                  n_q, edge_k0)
+    if (m->D <= 8) KSF_LAUNCH(8);
+    else if (m->D <= 20) KSF_LAUNCH(20);
+    else if (m->D <= 32) KSF_LAUNCH(32);
+    else if (m->D <= 48) KSF_LAUNCH(48);
+    else KSF_LAUNCH(64);
+#undef KSF_LAUNCH
+  }
+  return 0;
+}
+
 int check_model(ppbo_ctx* ctx, const ppbo_model* m) {
   PPBO_REQUIRE(ctx, m != nullptr, "model");
   PPBO_REQUIRE(ctx, m->d_X && m->d_alpha, "model X/alpha");
@@ -2082,18 +2394,27 @@ static_assert(PPBO_SLOPE_MEAN == PPBO_PAIR_MEAN && PPBO_SLOPE_VARIANCE == PPBO_P
 // column, kstar_curv -> quadform -> curv_score.
 static_assert(PPBO_CURV_MEAN == PPBO_PAIR_MEAN && PPBO_CURV_VARIANCE == PPBO_PAIR_VARIANCE && PPBO_CURV_PROB == PPBO_PAIR_PROB,
               "one score_kind check for all three entries");
-enum { TS_PAIRS = 0, TS_SLOPES = 1, TS_CURV = 2 };
+// Functionals (ppbo_predict_functionals) are the fourth: d_Xa the groups [M, G, D], d_Xb the weights ([G], or [M, G]),
+// `fa` their sizes and the threshold; kstar_func -> quadform -> functional_score.  fa is NULL for the other three.
+enum { TS_PAIRS = 0, TS_SLOPES = 1, TS_CURV = 2, TS_FUNC = 3 };
 static int two_set_passes(ppbo_ctx* ctx, const int what, const ppbo_model* model, const double* d_Xa, const double* d_Xb,
                           const double* d_Xacc, int64_t M, int score_kind, double* d_mu, double* d_var, double* d_prob,
-                          double* d_score, double* h_best_val, int64_t* h_best_idx, hipStream_t s) {
-  const bool slopes = what == TS_SLOPES, curv = what == TS_CURV;
+                          double* d_score, double* h_best_val, int64_t* h_best_idx, hipStream_t s,
+                          const FuncArgs* fa = nullptr) {
+  const bool slopes = what == TS_SLOPES, curv = what == TS_CURV, func = what == TS_FUNC;
   if (int rc = check_model(ctx, model)) return rc;
   PPBO_REQUIRE(ctx, d_Xa != nullptr && d_Xb != nullptr,
-               curv ? "curvatures (d_X / d_Xi)" : slopes ? "slopes (d_X / d_Xi)" : "pairs (d_Xa / d_Xb)");
+               func ? "functionals (d_Xg / d_w)" : curv ? "curvatures (d_X / d_Xi)" : slopes ? "slopes (d_X / d_Xi)" : "pairs (d_Xa / d_Xb)");
   PPBO_REQUIRE(ctx, M >= 1 && M <= (int64_t)0x7fffffff, what != TS_PAIRS ? "row count (1 .. 2^31 - 1)" : "pair count (1 .. 2^31 - 1)");
+  if (func) {
+    PPBO_REQUIRE(ctx, fa != nullptr && fa->G >= 1 && fa->G <= PPBO_FUNCTIONAL_MAX_G, "G (1 .. PPBO_FUNCTIONAL_MAX_G points per group)");
+    PPBO_REQUIRE(ctx, fa->w_stride == 0 || fa->w_stride == fa->G, "w_stride (0: one weight row for all groups, G: one per group)");
+    PPBO_REQUIRE(ctx, std::isfinite(fa->threshold), "threshold (finite)");
+  }
   PPBO_REQUIRE(ctx, score_kind == PPBO_PAIR_MEAN || score_kind == PPBO_PAIR_VARIANCE || score_kind == PPBO_PAIR_PROB,
                "score_kind");
-  PPBO_REQUIRE(ctx, !model->kstar_fp32, curv ? "curvatures are fp64 only (kstar_fp32)"
+  PPBO_REQUIRE(ctx, !model->kstar_fp32, func ? "functionals are fp64 only (kstar_fp32)"
+                                             : curv ? "curvatures are fp64 only (kstar_fp32)"
                                              : slopes ? "slopes are fp64 only (kstar_fp32)" : "pairs are fp64 only (kstar_fp32)");
   if (curv) {
     PPBO_REQUIRE(ctx, model->kernel_id != PPBO_KERNEL_MATERN32,
@@ -2133,8 +2454,10 @@ static int two_set_passes(ppbo_ctx* ctx, const int what, const ppbo_model* model
     if (!Kt) return (int)hipErrorOutOfMemory;
     if (Nk != N) PPBO_HIP_CHECK(ctx, hipMemsetAsync(Kt + (size_t)N * ldk, 0, (size_t)(Nk - N) * ldk * sizeof(double), s));
   }
-  double* part = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_PART, (size_t)(2 * n_split_eff + ntm) * Mc_max * sizeof(double));
+  // (functionals: one more row of the partial-sum workspace for the groups' prior terms)
+  double* part = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_PART, (size_t)(2 * n_split_eff + ntm + (func ? 1 : 0)) * Mc_max * sizeof(double));
   if (!part) return (int)hipErrorOutOfMemory;
+  double* func_prior = func ? part + (size_t)(2 * n_split_eff + ntm) * Mc_max : nullptr;
   const int sblocks_max = score_blocks(Mc_max);
   Best* bests = (Best*)ppbo_workspace(ctx, ppbo_ctx::WS_SMALL, (size_t)(sblocks_max + n_chunks) * sizeof(Best));
   if (!bests) return (int)hipErrorOutOfMemory;
@@ -2143,8 +2466,8 @@ static int two_set_passes(ppbo_ctx* ctx, const int what, const ppbo_model* model
   for (int64_t ch = 0; ch < n_chunks; ++ch) {
     const int64_t c_beg = ch * chunk_cap;
     const int Mc = (int)((M - c_beg) < chunk_cap ? (M - c_beg) : chunk_cap);
-    const double* xa = d_Xa + (size_t)c_beg * model->D;
-    const double* xb = d_Xb + (size_t)c_beg * model->D;
+    const double* xa = d_Xa + (size_t)c_beg * model->D * (func ? fa->G : 1);
+    const double* xb = d_Xb + (size_t)c_beg * (func ? fa->w_stride : model->D);
     const double* xacc = d_Xacc ? d_Xacc + (size_t)c_beg * model->D : nullptr;
     double* mu_part = part;
     double* t_part = part + (size_t)n_split_eff * Mc;
@@ -2155,7 +2478,10 @@ static int two_set_passes(ppbo_ctx* ctx, const int what, const ppbo_model* model
           constexpr int KID = decltype(kid)::value;
           {
             PpboProfScope pf(ctx, ppbo_ctx::PF_KSTAR, s);
-            if (curv) {
+            if (func)
+              launch_kstar_func<KID>(model, p, xa, xb, *fa, Mc, Kt, ldk, mu_part, t_part, q_per_split, n_split_eff, want_var,
+                                     edge_k0, s);
+            else if (curv) {
               if constexpr (KID != PPBO_KERNEL_MATERN32)       // refused above
                 launch_kstar_curv<KID>(model, p, xa, xb, xacc, Mc, Kt, ldk, mu_part, t_part, q_per_split, n_split_eff,
                                        want_var, edge_k0, s);
@@ -2172,7 +2498,20 @@ static int two_set_passes(ppbo_ctx* ctx, const int what, const ppbo_model* model
             if (int rc2 = dispatch_quadform(ctx, Gq, Nk, g_rows, N, Kt, ldk, Mc, mblk, slab, edge_k0, s)) return rc2;
           }
           PpboProfScope pfs(ctx, ppbo_ctx::PF_SCORE, s);
-          if (curv) {
+          if (func) {
+            if (want_var) {
+              // one wavefront per group; as many per workgroup (4, 2, 1) as 48 KB of LDS hold of G (D + 1) doubles each
+              const size_t per_wave = (size_t)fa->G * (model->D + 1) * sizeof(double);
+              const int wpb = 4 * per_wave <= 49152 ? 4 : (2 * per_wave <= 49152 ? 2 : 1);
+              functional_prior_kernel<KID><<<(Mc + wpb - 1) / wpb, 64 * wpb, wpb * per_wave, s>>>(
+                  xa, xb, fa->w_stride, fa->G, model->D, Mc, p, func_prior);
+            }
+            functional_score_kernel<<<sblocks, SC_THREADS, 0, s>>>(
+                mu_part, n_split_eff, t_part, want_var ? slab : nullptr, ntm, Mc, func_prior, fa->threshold, score_kind,
+                (long long)c_beg, d_mu ? d_mu + c_beg : nullptr, d_var ? d_var + c_beg : nullptr,
+                d_prob ? d_prob + c_beg : nullptr, d_score ? d_score + c_beg : nullptr, want_best ? bests : nullptr);
+          }
+          else if (curv) {
             if constexpr (KID != PPBO_KERNEL_MATERN32)
               curv_score_kernel<KID><<<sblocks, SC_THREADS, 0, s>>>(
                   mu_part, n_split_eff, t_part, want_var ? slab : nullptr, ntm, Mc, xb, xacc, model->D, p, score_kind,
@@ -2235,6 +2574,20 @@ int ppbo_predict_curvatures(ppbo_ctx* ctx, const ppbo_model* model, const double
   PPBO_ENTER(ctx);
   return two_set_passes(ctx, TS_CURV, model, d_X, d_Xi, d_Xa, M, score_kind, d_mu, d_var, d_prob, d_score, h_best_val,
                         h_best_idx, (hipStream_t)stream);
+}
+
+// Functionals: the column c = sum_g w_g k(x_g, X) of L f = sum_g w_g f(x_g) for M groups of G points: ONE contraction per
+// group whatever G is; the K* launches share the "kstar" profile slot.
+static_assert(PPBO_FUNCTIONAL_MEAN == PPBO_PAIR_MEAN && PPBO_FUNCTIONAL_VARIANCE == PPBO_PAIR_VARIANCE &&
+                  PPBO_FUNCTIONAL_PROB == PPBO_PAIR_PROB,
+              "one score_kind check for all four entries");
+int ppbo_predict_functionals(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xg, const double* d_w, int w_stride,
+                             int64_t M, int G, double threshold, int score_kind, double* d_mu, double* d_var,
+                             double* d_prob, double* d_score, double* h_best_val, int64_t* h_best_idx, void* stream) {
+  PPBO_ENTER(ctx);
+  const FuncArgs fa{G, w_stride, threshold};
+  return two_set_passes(ctx, TS_FUNC, model, d_Xg, d_w, nullptr, M, score_kind, d_mu, d_var, d_prob, d_score, h_best_val,
+                        h_best_idx, (hipStream_t)stream, &fa);
 }
 
 }  // extern "C"

@@ -374,6 +374,121 @@ __global__ __launch_bounds__(SC_THREADS) void curv_score_kernel(const double* __
   if (lane == 0) blk_best[blockIdx.x] = b;
 }
 
+// The prior term of ppbo_predict_functionals, prior[c] = w' K w for group c, rearranged so that nothing cancels between
+// nearby points:
+//   w' K w = sigma_f^2 (sum_g w_g)^2 - 2 sigma_f^2 sum_{g < h} w_g w_h (1 - k(x_g, x_h) / sigma_f^2)
+// with the bracket from the direct differences x_g - x_h through kern_one_minus (pair_score_kernel's prior term): a
+// contrast (sum w = 0) between nearby points keeps its digits, and two coincident points contribute exactly 0.
+// One wavefront = one group: its G points go to LDS once (coalesced reads, rows padded to D + 1), lane l takes the pairs
+// l, l + 64, ... of the G (G - 1) / 2 in row-major order of (g, h), the lane sums meet in a fixed exchange order, and
+// sum_g w_g is added in index order.  w_g w_h and the square do not see the sign of w, so -w leaves the term bitwise
+// unchanged; 2 w gives exactly four times it.  (With slope_score_kernel's geometry -- one lane per group, the pairs
+// dealt to the workgroup's wavefronts -- every load of a point touched 64 cache lines: 25.4 ms for 65536 groups of
+// G = 64 at D = 20, 0.97 ms at G = 16.)  Dynamic LDS: (blockDim.x / 64) G (D + 1) doubles.
+__device__ __forceinline__ int functional_pair_offset(int g, int G) { return g * (2 * G - g - 1) / 2; }   // pairs before row g
+template <int KID>
+__global__ __launch_bounds__(256) void functional_prior_kernel(const double* __restrict__ Xg, const double* __restrict__ W,
+                                                               int w_stride, int G, int D, int M, KernParams p,
+                                                               double* __restrict__ prior) {
+  extern __shared__ double fp_lds[];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, LD = D + 1;
+  const int c = blockIdx.x * (blockDim.x >> 6) + wave;
+  if (c >= M) return;                      // (a whole wavefront; no workgroup barrier below)
+  double* __restrict__ xs = fp_lds + (size_t)wave * G * LD;
+  const double* __restrict__ xg = Xg + (size_t)c * G * D;
+  const double* __restrict__ w = W + (size_t)c * w_stride;
+  for (int e = lane; e < G * D; e += 64) {
+    const int g = e / D, d = e - g * D;
+    xs[g * LD + d] = xg[e];
+  }
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  const int npairs = G * (G - 1) / 2;
+  double ps = 0.0;
+  for (int q = lane; q < npairs; q += 64) {
+    // row g of pair q: the root of g (2 G - g - 1) / 2 = q, corrected by at most a step either way
+    const double tg = 2.0 * G - 1.0;
+    int g = (int)((tg - sqrt(tg * tg - 8.0 * q)) * 0.5);
+    if (g < 0) g = 0;
+    if (g > G - 2) g = G - 2;
+    while (g < G - 2 && functional_pair_offset(g + 1, G) <= q) ++g;
+    while (g > 0 && functional_pair_offset(g, G) > q) --g;
+    const int h = g + 1 + (q - functional_pair_offset(g, G));
+    double s = 0.0;
+    for (int d = 0; d < D; ++d) s += kern_term<KID>(xs[g * LD + d] - xs[h * LD + d], d, p);
+    ps += (w[g] * w[h]) * kern_one_minus<KID>(s, p);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) ps += __shfl_xor(ps, o, 64);
+  if (lane == 0) {
+    double sw = 0.0;
+    for (int g = 0; g < G; ++g) sw += w[g];
+    prior[c] = p.sf2 * (sw * sw - 2.0 * ps);
+  }
+}
+
+// Pass 3 of ppbo_predict_functionals: score_kernel's slab sums (same geometry) for the column c = sum_g w_g k(x_g, X),
+// then with prior[c] of functional_prior_kernel
+//   mu = sum of the mean partials,   var = prior + c' Lambda c + |G c|^2,   p = P(L f > threshold) = Phi((mu - threshold) / sqrt(max(var, 0)))
+// No noise term.  var = 0: the sign of mu - threshold decides, equality gives 1/2; a NaN mean (a non-finite coordinate)
+// gives NaN everywhere.
+__global__ __launch_bounds__(SC_THREADS) void functional_score_kernel(const double* __restrict__ mu_part, int n_mu,
+                                                                      const double* __restrict__ t_part,
+                                                                      const double* __restrict__ slab, int n_slab, int M,
+                                                                      const double* __restrict__ prior,
+                                                                      double threshold, int kind, long long idx_base,
+                                                                      double* __restrict__ mu_out, double* __restrict__ var_out,
+                                                                      double* __restrict__ prob_out,
+                                                                      double* __restrict__ score_out, Best* __restrict__ blk_best) {
+  __shared__ double part[3][SC_WAVES][SC_CAND];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int c = blockIdx.x * SC_CAND + lane;
+  double pm = 0.0, pt = 0.0, pq = 0.0;
+  if (c < M) {
+    for (int s = wave; s < n_mu; s += SC_WAVES) pm += mu_part[(size_t)s * M + c];
+    if (slab) {
+      for (int s = wave; s < n_mu; s += SC_WAVES) pt += t_part[(size_t)s * M + c];
+      for (int s = wave; s < n_slab; s += SC_WAVES) pq += slab[(size_t)s * M + c];
+    }
+  }
+  part[0][wave][lane] = pm;
+  part[1][wave][lane] = pt;
+  part[2][wave][lane] = pq;
+  __syncthreads();
+  if (wave != 0) return;                 // the rest is one wavefront's work
+  Best b{0.0, -1};
+  if (c < M) {
+    double mu = 0.0, t = 0.0, q = 0.0;
+#pragma unroll
+    for (int w = 0; w < SC_WAVES; ++w) { mu += part[0][w][lane]; t += part[1][w][lane]; q += part[2][w][lane]; }
+    double var = NAN, pr = NAN, sc = mu;   // mean only (no slab): nothing but mu is formed
+    if (slab) {
+      var = prior[c] + t + q;
+      const double sd = sqrt(fmax(var, 0.0)), dm = mu - threshold;
+      // sd = 0 (no variance): the sign of mu - threshold decides, a tie is 1/2
+      pr = norm_cdf(sd > 0.0 ? dm / sd : (dm > 0.0 ? INFINITY : (dm < 0.0 ? -INFINITY : 0.0)));
+      if (mu != mu) { var = mu; pr = mu; }
+      if (kind == PPBO_FUNCTIONAL_VARIANCE) sc = var;
+      else if (kind == PPBO_FUNCTIONAL_PROB) sc = pr;
+    }
+    if (mu_out) mu_out[c] = mu;
+    if (var_out) var_out[c] = var;
+    if (prob_out) prob_out[c] = pr;
+    if (score_out) score_out[c] = sc;
+    if (sc == sc) { b.val = sc; b.idx = idx_base + c; }
+  }
+  if (!blk_best) return;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    Best other;
+    other.val = __shfl_xor(b.val, o, 64);
+    other.idx = __shfl_xor(b.idx, o, 64);
+    b = best_merge(b, other);
+  }
+  if (lane == 0) blk_best[blockIdx.x] = b;
+}
+
 // per-block records of one launch -> *out; with `record` also the 16-byte (value, GLOBAL index as a double: exact
 // below 2^53; index + record_offset; (NaN, -1) when nothing scored) record that the sharded search all-gathers, and
 // with `publish` the flag publish[0] raised to `epoch` AFTER the record with system-scope release semantics (the

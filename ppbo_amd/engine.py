@@ -13,6 +13,7 @@ from ._lib import KERNEL_IDS, SCORE_MEAN, SCORE_POINTWISE_EI, SCORE_VARIANCE, PP
 from ._lib import PAIR_MEAN, PAIR_VARIANCE, PAIR_PROB  # noqa: F401
 from ._lib import SLOPE_MEAN, SLOPE_VARIANCE, SLOPE_PROB  # noqa: F401
 from ._lib import CURV_MEAN, CURV_VARIANCE, CURV_PROB  # noqa: F401
+from ._lib import FUNCTIONAL_MEAN, FUNCTIONAL_VARIANCE, FUNCTIONAL_PROB, FUNCTIONAL_MAX_G  # noqa: F401
 
 # Posterior.form: which variance operator G holds (include/ppbo_hip.h, PPBO_FORM_*)
 FORM_NODE = 0   # G = R Lambda, block lower triangular [N, N]
@@ -792,6 +793,54 @@ class Engine:
                                               _ptr(var), _ptr(pr), _ptr(sc), C.byref(bv) if want_best else None,
                                               C.byref(bi) if want_best else None, self._stream())
         self._check(rc, "ppbo_predict_curvatures")
+        return dict(mu=mu, var=var, prob=pr, score=sc, best_val=bv.value, best_idx=bi.value)
+
+    @staticmethod
+    def _functional_shapes(post: Posterior, Xg, w):
+        """The refusals of predict_functionals that shapes alone decide (before anything reaches the device): returns
+        (M, G, w_stride)."""
+        sx, sw = tuple(np.shape(Xg)), tuple(np.shape(w))
+        D = 6 if post.camphor is not None else post.X.shape[1]
+        if len(sx) != 3:
+            raise ValueError(f"predict_functionals: groups of shape {sx}; an [M, G, D] set is required")
+        M, G = sx[0], sx[1]
+        if sx[2] != D:
+            raise ValueError(f"predict_functionals: points of width {sx[2]} for a model of {D} dimensions")
+        if M < 1:
+            raise ValueError("predict_functionals: no groups")
+        if G < 1 or G > FUNCTIONAL_MAX_G:
+            raise ValueError(f"predict_functionals: {G} points per group (1 .. {FUNCTIONAL_MAX_G})")
+        if sw != (G,) and sw != (M, G):
+            raise ValueError(f"predict_functionals: weights of shape {sw} for groups of shape {sx}; [G] or [M, G] is required")
+        return M, G, (G if len(sw) == 2 else 0)
+
+    def predict_functionals(self, post: Posterior, Xg, w, threshold=0.0, score=FUNCTIONAL_PROB, want_mu=True,
+                            want_var=True, want_prob=True, want_score=False, want_best=True):
+        """Averages and contrasts (ppbo_predict_functionals): for the M groups Xg[i] of G points in the caller's
+        coordinates and the weights w ([G]: one row for all groups, or [M, G]) the posterior mean and variance of
+        L f = sum_g w[g] f(Xg[i, g]) and p = P(L f > threshold), as device tensors mu / var / prob / score (None where not
+        asked for), with best_val / best_idx = the largest score (the quantity `score` names) and its first group.
+        FUNCTIONAL_MEAN without var and prob needs no variance operator."""
+        M, G, w_stride = self._functional_shapes(post, Xg, w)
+        if score not in (FUNCTIONAL_MEAN, FUNCTIONAL_VARIANCE, FUNCTIONAL_PROB):
+            raise ValueError(f"predict_functionals: unknown score kind {score}")
+        if not np.isfinite(float(threshold)):
+            raise ValueError(f"predict_functionals: threshold {threshold} is not finite")
+        Xg = self.dev(Xg)
+        Xg = self._points(post, Xg.reshape(M * G, Xg.shape[2]))      # [M G, the model's D], group-major
+        w = self.dev(w)
+        with_var = want_var or want_prob or score != FUNCTIONAL_MEAN
+        md = self._model(post, with_var)
+        mu = self.empty(M) if want_mu else None
+        var = self.empty(M) if want_var else None
+        pr = self.empty(M) if want_prob else None
+        sc = self.empty(M) if want_score else None
+        bv, bi = C.c_double(0.0), C.c_int64(-1)
+        rc = self.lib.ppbo_predict_functionals(self.ctx, C.byref(md), _ptr(Xg), _ptr(w), int(w_stride), M, int(G),
+                                               float(threshold), int(score), _ptr(mu), _ptr(var), _ptr(pr), _ptr(sc),
+                                               C.byref(bv) if want_best else None, C.byref(bi) if want_best else None,
+                                               self._stream())
+        self._check(rc, "ppbo_predict_functionals")
         return dict(mu=mu, var=var, prob=pr, score=sc, best_val=bv.value, best_idx=bi.value)
 
     def predict_cov(self, post: Posterior, Xc, shrink=SHRINKAGE):

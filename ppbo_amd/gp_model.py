@@ -917,6 +917,74 @@ class GPModel:
         x = np.asarray(self.xstar if x is None else x, dtype=float).reshape(-1)
         return self.curvature_pred(np.tile(x, (x.size, 1)), np.eye(x.size))
 
+    def functional_pred(self, X_groups, weights, threshold=0.0):
+        """(mu, var, p) as NumPy arrays for the groups X_groups[i] ([M, G, D], or one group [G, D]) and the weights
+        ([G]: one row for all groups, or [M, G]): the posterior mean and variance of L f = sum_g w_g f(x_g) and
+        p = P(L f > threshold) = Phi((mu - threshold) / sqrt(var)), without a noise term (ppbo_predict_functionals; no
+        reference counterpart).  Host or device input in the caller's coordinates, mapped as preference_pred maps its
+        sides.  ValueError when the shapes do not fit each other or the model, or G > 64."""
+        post = self._var_post()
+        Xg, w = (a if isinstance(a, torch.Tensor) else np.asarray(a, dtype=float) for a in (X_groups, weights))
+        if Xg.ndim == 2:
+            Xg = Xg.reshape(1, *Xg.shape)
+        out = self.eng.predict_functionals(post, Xg, w, threshold=threshold, want_best=False)
+        return out["mu"].cpu().numpy(), out["var"].cpu().numpy(), out["prob"].cpu().numpy()
+
+    def _neighbourhoods(self, X, offsets):
+        """[M, G, D] clouds x + delta_g in the caller's coordinates, clipped to the box; the periodic coordinates of the
+        camphor kernels (all but the third) are left as they are: the kernel is periodic there."""
+        X = np.atleast_2d(np.asarray(X.cpu() if isinstance(X, torch.Tensor) else X, dtype=float))
+        off = np.atleast_2d(np.asarray(offsets.cpu() if isinstance(offsets, torch.Tensor) else offsets, dtype=float))
+        if X.shape[1] != self.D or off.shape[1] != self.D:
+            raise ValueError(f"points of shape {X.shape} and offsets of shape {off.shape} for a model of {self.D} dimensions")
+        Xg = X[:, None, :] + off[None, :, :]
+        lo = np.array([b[0] for b in self.bounds], dtype=float)
+        hi = np.array([b[1] for b in self.bounds], dtype=float)
+        clipped = np.clip(Xg, lo, hi)
+        if "camphor" in self.kernel.__name__:
+            periodic = np.arange(self.D) != 2
+            clipped[..., periodic] = Xg[..., periodic]
+        return clipped
+
+    def average_pred(self, X, offsets):
+        """(mu, var) as NumPy arrays of the neighbourhood average (1 / G) sum_g f(x + delta_g) at the rows of X [M, D] for
+        the shared offsets delta [G, D]: the expected utility of a design under implementation tolerance.  Offsets are
+        added in the caller's coordinates and clipped to the box (not the periodic coordinates of the camphor kernels)."""
+        Xg = self._neighbourhoods(X, offsets)
+        G = Xg.shape[1]
+        mu, var, _ = self.functional_pred(Xg, np.full(G, 1.0 / G))
+        return mu, var
+
+    def contrast_pred(self, XA, XB):
+        """(mu, var, p) of mean_{a in A} f(a) - mean_{b in B} f(b) for two shortlists XA [GA, D], XB [GB, D]
+        (GA + GB <= 64) with p = P(A is better on average); [M, GA, D] and [M, GB, D] give M contrasts."""
+        A, B = (a if isinstance(a, torch.Tensor) else np.asarray(a, dtype=float) for a in (XA, XB))
+        A, B = (a.reshape(1, -1) if a.ndim == 1 else a for a in (A, B))
+        if A.ndim != B.ndim or A.ndim not in (2, 3) or (A.ndim == 3 and A.shape[0] != B.shape[0]):
+            raise ValueError(f"contrast_pred: shortlists of shapes {tuple(A.shape)} and {tuple(B.shape)}")
+        ga, gb = A.shape[-2], B.shape[-2]
+        if ga + gb > 64:
+            raise ValueError(f"contrast_pred: {ga} + {gb} points (at most 64 together)")
+        Xg = torch.cat([self.eng.dev(A), self.eng.dev(B)], dim=-2)
+        w = np.concatenate([np.full(ga, 1.0 / ga), np.full(gb, -1.0 / gb)])
+        return self.functional_pred(Xg, w)
+
+    def robust_xstar(self, offsets):
+        """(x, mu_avg, var_avg): the row that maximises the neighbourhood-averaged posterior mean
+        (1 / G) sum_g mu(x + delta_g) over the resident candidate pool and xstars_local, through the entry's score and
+        argmax -- the robust optimum in place of the sharp one -- with the mean and variance of that average."""
+        post = self._var_post()
+        cand = self._candidate_pool().cpu().numpy()
+        if self.xstars_local is not None and len(self.xstars_local):
+            cand = np.concatenate([cand, np.atleast_2d(np.asarray(self.xstars_local, dtype=float))])
+        Xg = self._neighbourhoods(cand, offsets)
+        G = Xg.shape[1]
+        out = self.eng.predict_functionals(post, Xg, np.full(G, 1.0 / G), score=0, want_prob=False)
+        i = int(out["best_idx"])
+        if i < 0:
+            raise RuntimeError("robust_xstar: no candidate has a finite averaged mean")
+        return cand[i].copy(), float(out["mu"][i]), float(out["var"][i])
+
     def mean_hessian(self, x=None):
         """The symmetric D x D Hessian of the posterior mean at x (default: xstar), by polarisation from the D (D + 1) / 2
         mean curvatures along e_a and e_a + e_b: H_ab = (mu_c(e_a + e_b) - mu_c(e_a) - mu_c(e_b)) / 2.  Needs no variance
