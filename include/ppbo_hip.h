@@ -493,6 +493,65 @@ PPBO_API int ppbo_predict_functionals(ppbo_ctx* ctx, const ppbo_model* model, co
                         int w_stride, int64_t M, int G, double threshold, int score_kind, double* d_mu, double* d_var,
                         double* d_prob, double* d_score, double* h_best_val, int64_t* h_best_idx, void* stream);
 
+/* ---- main effects and interactions: f with all but at most two coordinates averaged over the unit box ------------------
+ * The global companion of the local entries above (no reference counterpart: its plots, camphor_copper/plot_results.py, are
+ * two-dimensional SLICES through x*).  Which coordinates matter, how does the utility depend on coordinate d once the
+ * others are averaged out, do d and e interact.  The SE kernel (scalar or per-dimension length scales) and the
+ * camphor-copper kernels are PRODUCTS over the caller's unit-box coordinates,
+ *   k(x, x') = sigma_f^2 prod_d kappa_d(x_d - x'_d),   kappa_d(D) = exp(-D^2 / (2 l_d^2))            (an SE axis)
+ *                                                      kappa_d(D) = exp(-2 sin^2(pi D) / l_d^2)      (a periodic axis)
+ * so the average of k(x, x_j) over [0,1] in any subset of coordinates is closed form, and a main effect or an
+ * interaction is one more linear functional with an exactly known column: nothing is sampled, no quadrature size.
+ *   I_d(c) = int_0^1 kappa_d(u - c) du = l sqrt(pi/2) (erf((1 - c) / (sqrt2 l)) + erf(c / (sqrt2 l)))   | e^-a I0(a), a = 1 / l^2
+ *   A_d    = int int kappa_d(u - u') du du' = 2 (l sqrt(pi/2) erf(1 / (sqrt2 l)) - l^2 (1 - e^(-1/(2 l^2))))   | e^-a I0(a)
+ * Per design row j: Q_jd = I_d(x_jd), P_j = sigma_f^2 prod_d Q_jd (the product in axis order).  A row of the call keeps the
+ * axes J (|J| = 0, 1 or 2) at the values t: r_d = kappa_d(t_d - x_jd) / Q_jd for d in J.  With S = sigma_f^2 prod_{d not in J} A_d,
+ * a_d = I_d(t_d) and b_d = 1 - 2 a_d + A_d:
+ *   PPBO_EFFECT_RAW          L f = f_J(t) = int f dx_{-J}           c_j = P_j prod_J r_d           prior = S
+ *   PPBO_EFFECT_CENTRED      f_J(t) - fbar, fbar = int f dx         c_j = P_j (prod_J r_d - 1)     prior = S (1 - 2 prod_J a_d + prod_J A_d)
+ *   PPBO_EFFECT_INTERACTION  f_de - f_d - f_e + fbar  (|J| = 2)     c_j = P_j (r_d - 1)(r_e - 1)   prior = S b_d b_e
+ *   mu = c' alpha,   var = prior + c' Lambda c + |G c|^2 (the operator of ppbo_posterior on c, as ppbo_predict_functionals),
+ *   p = P(L f > 0) = Phi(mu / sqrt(max(var, 0)));  no noise term;  var = 0: the sign of mu decides, mu = 0 gives 1/2
+ * A utility learned from preferences is defined up to a constant: CENTRED and INTERACTION are the identifiable ones.
+ * An order-0 row under CENTRED is the zero functional and gives (0, 0, 1/2) exactly.
+ * axes: Dc caller coordinates (the model's D; 6 for PPBO_KERNEL_CAMPHOR and for a PPBO_COORDS_CAMPHOR model), d_Xu[N, Dc]
+ * the design rows in those unit-box coordinates -- BEFORE the scaling of an ARD model or the camphor embedding --, and on
+ * the host l[Dc], periodic[Dc] (0: an SE axis, 1: a periodic one) and I0[Dc] = e^-a I0(a) of the periodic axes (the
+ * scaled Bessel function, scipy.special.ive(0, a): never a product of two factors; used on the periodic axes only, but
+ * every entry must be positive and finite).  The host
+ * arrays are consumed before the call returns.  From the model the entry reads alpha, Lambda, G, form, N, m and sigma_f
+ * (theta[2]); the column is formed from `axes`, NOT from model->d_X.  THE LIBRARY DOES NOT CHECK that d_Xu are the rows the
+ * model was fitted on, nor that l and periodic are its kernel's: other rows give a finite, plausible and wrong answer.
+ * d_dims [M, 2] (int): the kept axes of a row, -1 = unused: (-1, -1) order 0, (d, -1) order 1, (d, e) order 2.  d_t [M, 2]:
+ * their values (not read where the axis is -1).  A row's two axes are processed in ascending axis order whatever order
+ * the caller gave them: (d, e, t, u) and (e, d, u, t) give the same bits.  Every sum has a fixed order and there are no
+ * atomics: a call is bitwise repeatable, and a row's results depend neither on its place in the call nor on M (the row
+ * splits are those of a full chunk).
+ * score_kind (PPBO_PAIR_*: mean, variance, probability), the outputs (each may be NULL), the argmax record, the chunks of
+ * 65536 rows and the NaN rule are ppbo_predict_pairs': a row with a NaN or infinite t on a kept axis gets NaN outputs
+ * and never wins; the other rows do not see it.  The mean alone (d_var == d_prob == NULL) reads neither d_G nor Lambda.
+ * Launches: marginal_table_kernel once per call (1 / Q and P), then per chunk kstar_marginal_kernel, the quadform kernel
+ * of ppbo_predict, marginal_score_kernel; the K* launch is timed under the "kstar" name of ppbo_profile_read.
+ * "invalid argument", nothing written to an output, the context still usable: everything ppbo_predict_pairs refuses; a
+ * kernel id other than PPBO_KERNEL_SE and PPBO_KERNEL_CAMPHOR (RQ and the Matern kernels are radial, not products: sample
+ * the box with ppbo_predict_functionals); a NULL axes, d_Xu, h_l, h_periodic, h_I0, d_dims or d_t; Dc outside 1 .. 64 or
+ * not the model's; an l or an I0 that is not positive and finite (on any axis); a periodic flag other than 0 / 1;
+ * an unknown effect; and, looked for on the device before the first launch that writes an output (one small launch and a
+ * wait on the host-mapped record), a row of d_dims with an axis outside -1 .. Dc - 1, with d == e >= 0, with a first axis
+ * of -1 and a second >= 0, or of order below 2 under PPBO_EFFECT_INTERACTION.  On a stream that is being captured the host
+ * cannot wait: there the look is left out and such a row gets NaN outputs. */
+typedef struct ppbo_marginal_axes {
+  int Dc;                  /* caller coordinates: D, or 6 for the camphor kernels; 1 .. 64 */
+  const double* d_Xu;      /* [N,Dc] the design rows in unit-box caller coordinates */
+  const double* h_l;       /* [Dc] length scales */
+  const int* h_periodic;   /* [Dc] 0 SE axis, 1 camphor periodic axis */
+  const double* h_I0;      /* [Dc] e^-a I0(a), a = 1 / l^2, for the periodic axes */
+} ppbo_marginal_axes;
+enum { PPBO_EFFECT_RAW = 0, PPBO_EFFECT_CENTRED = 1, PPBO_EFFECT_INTERACTION = 2 };
+PPBO_API int ppbo_predict_marginals(ppbo_ctx* ctx, const ppbo_model* model, const ppbo_marginal_axes* axes, const int* d_dims,
+                        const double* d_t, int64_t M, int effect, int score_kind, double* d_mu, double* d_var,
+                        double* d_prob, double* d_score, double* h_best_val, int64_t* h_best_idx, void* stream);
+
 /* full predictive covariance of small sets (the G=70 line grid of EI):
  * d_cov[M,M] = (1-s)K(Xc,Xc) + s sigma_f^2 I - K*^T A K*  (src/gp_model.py:447-450) */
 PPBO_API int ppbo_predict_cov(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc, int M,

@@ -23,6 +23,8 @@ SLOPE_MEAN, SLOPE_VARIANCE, SLOPE_PROB = 0, 1, 2   # score kinds of ppbo_predict
 CURV_MEAN, CURV_VARIANCE, CURV_PROB = 0, 1, 2      # score kinds of ppbo_predict_curvatures (PPBO_CURV_*)
 FUNCTIONAL_MEAN, FUNCTIONAL_VARIANCE, FUNCTIONAL_PROB = 0, 1, 2   # ... of ppbo_predict_functionals (PPBO_FUNCTIONAL_*)
 FUNCTIONAL_MAX_G = 64                              # points per group (PPBO_FUNCTIONAL_MAX_G)
+EFFECT_RAW, EFFECT_CENTRED, EFFECT_INTERACTION = 0, 1, 2           # effects of ppbo_predict_marginals (PPBO_EFFECT_*)
+MARGINAL_MAX_DC = 64                               # caller coordinates of ppbo_marginal_axes
 
 
 class FitOpts(C.Structure):
@@ -51,6 +53,29 @@ class Model(C.Structure):
                 ("d_Gt", C.c_void_p), ("form", C.c_int), ("coords", Coords)]
 
 
+
+
+class MarginalAxes(C.Structure):
+    _fields_ = [("Dc", C.c_int), ("d_Xu", C.c_void_p), ("h_l", C.POINTER(C.c_double)), ("h_periodic", C.POINTER(C.c_int)),
+                ("h_I0", C.POINTER(C.c_double))]
+
+
+def marginal_axes(d_Xu, l, periodic, I0):
+    """A ppbo_marginal_axes over the device address d_Xu of the design rows in unit-box caller coordinates and the host
+    arrays l, periodic, I0 (one entry per coordinate); the copies the struct points into stay referenced from it."""
+    import numpy as np
+    ax = MarginalAxes()
+    ax._l = np.ascontiguousarray(l, dtype=np.float64).reshape(-1)
+    ax._per = np.ascontiguousarray(periodic, dtype=np.intc).reshape(-1)
+    ax._i0 = np.ascontiguousarray(I0, dtype=np.float64).reshape(-1)
+    if not (ax._l.size == ax._per.size == ax._i0.size):
+        raise ValueError("marginal_axes: l, periodic and I0 need one entry per coordinate")
+    ax.Dc = int(ax._l.size)
+    ax.d_Xu = d_Xu
+    ax.h_l = ax._l.ctypes.data_as(C.POINTER(C.c_double))
+    ax.h_periodic = ax._per.ctypes.data_as(C.POINTER(C.c_int))
+    ax.h_I0 = ax._i0.ctypes.data_as(C.POINTER(C.c_double))
+    return ax
 
 
 def coords(kind=COORDS_MODEL, coef=None, d_Xc=None):
@@ -104,6 +129,8 @@ SIGNATURES = {
     "ppbo_predict_curvatures": [_vp, C.POINTER(Model), _vp, _vp, _vp, _i64, _i, _vp, _vp, _vp, _vp, C.POINTER(_d), C.POINTER(_i64), _vp],
     "ppbo_predict_functionals": [_vp, C.POINTER(Model), _vp, _vp, _i, _i64, _i, _d, _i, _vp, _vp, _vp, _vp, C.POINTER(_d),
                                  C.POINTER(_i64), _vp],
+    "ppbo_predict_marginals": [_vp, C.POINTER(Model), C.POINTER(MarginalAxes), _vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp,
+                               C.POINTER(_d), C.POINTER(_i64), _vp],
     "ppbo_predict_cov": [_vp, C.POINTER(Model), _vp, _i, _d, _vp, _vp, _vp],
     "ppbo_transposed_G_shape": [_i, C.POINTER(_i), C.POINTER(_i)],
     "ppbo_transposed_G": [_vp, _vp, _i, _vp, _vp],

@@ -1287,6 +1287,166 @@ __global__ __launch_bounds__(KS_THREADS, (curv_waves<KID, DP, ACC>())) void ksta
   }
 }
 
+// ---- main effects and interactions (ppbo_predict_marginals) -----------------------------------------------------------
+// A kernel that is a PRODUCT over the caller's coordinates, k(x, x') = sf2 prod_d kappa_d(x_d - x'_d) with kappa_d SE or the
+// camphor kernel's periodic factor, integrates over the unit box in any subset of coordinates in closed form.  With
+//   Q_jd = I_d(x_jd) = int_0^1 kappa_d(u - x_jd) du,   P_j = sf2 prod_d Q_jd,   r_d = kappa_d(t_d - x_jd) / Q_jd
+// the column of f with every axis but the kept ones (at most two, at the values t) averaged out is c_j = P_j prod_kept r_d.
+//
+// The axes of a call by value (at most 1.6 KB of kernel arguments: nothing of the host's is read after the launch is
+// enqueued, and a captured launch carries its own copy).
+struct MargAxesArg {
+  double l[MG_AXES], i0[MG_AXES], a[MG_AXES];
+  unsigned long long periodic;     // bit d: axis d is periodic
+  int Dc;
+};
+inline size_t marginal_table_doubles(int N, int Dc) { return (size_t)MG_ROWS + (size_t)N * Dc + N; }
+
+// Once per call: the axis table (score.h; written by workgroup 0), 1 / Q[N, Dc] and P[N].  One lane per design row; P_j
+// is the product in axis order.  The by-value arrays are read with compile-time indices only (a lane-dependent index
+// into a by-value argument goes through scratch, see camphor_pick): lane d of a workgroup picks axis d by a chain of
+// selects and leaves it in LDS, where the row loop reads it.
+__global__ __launch_bounds__(256) void marginal_table_kernel(MargAxesArg ax, const double* __restrict__ Xu, int N, double sf2,
+                                                             double* __restrict__ tab) {
+  __shared__ double s_l[MG_AXES], s_i0[MG_AXES];
+  __shared__ int s_per[MG_AXES];
+  const int Dc = ax.Dc;
+  if (threadIdx.x < MG_AXES) {
+    const int d = threadIdx.x;
+    double l = 1.0, i0 = 1.0, a = 1.0;
+#pragma unroll
+    for (int k = 0; k < MG_AXES; ++k)
+      if (k == d) { l = ax.l[k]; i0 = ax.i0[k]; a = ax.a[k]; }
+    const int per = (int)((ax.periodic >> d) & 1ull);
+    s_l[d] = l; s_i0[d] = i0; s_per[d] = per;
+    if (blockIdx.x == 0 && d < Dc) {
+      tab[MG_COEF + d] = (per ? 2.0 : 0.5) / (l * l);
+      tab[MG_PER + d] = per ? 1.0 : 0.0;
+      tab[MG_I0 + d] = i0;
+      tab[MG_L + d] = l;
+      tab[MG_A + d] = a;
+    }
+  }
+  __syncthreads();
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= N) return;
+  double* __restrict__ iq = tab + MG_ROWS;
+  double P = sf2;
+  for (int d = 0; d < Dc; ++d) {
+    const double q = s_per[d] ? s_i0[d] : marginal_se_integral(Xu[(size_t)j * Dc + d], s_l[d]);
+    iq[(size_t)j * Dc + d] = 1.0 / q;
+    P *= q;
+  }
+  tab[MG_ROWS + (size_t)N * Dc + j] = P;
+}
+
+// Pass 1 of ppbo_predict_marginals: the column c_j = P_j F(r_d, r_e) in place of k*, on kstar_pair_kernel's plan: one lane =
+// ONE row of the call, the design rows (in the caller's unit-box coordinates) and their 1 / Q rows staged per KS_RJ-row
+// slab in LDS, its row splits, star bookkeeping and node / edge stores.  F = r_d r_e (RAW), r_d r_e - 1 (CENTRED),
+// (r_d - 1)(r_e - 1) (INTERACTION); an axis that is not kept has r = 1.  Per entry at most two factor values -- a
+// difference, sinpi on a periodic axis, the project's exp, a product with 1 / Q -- and no D-long distance.  The lanes of a
+// wavefront carry different axes: each reads ITS column of the staged slab (an LDS address per lane; nothing is
+// indexed in registers) and keeps its axes' two coefficients in registers.  Every row of the call takes the same
+// instruction chain on its canonical form (marginal_row), so swapped axes give the same bits and a row's sums do not
+// depend on its place in the call.  A row with a non-finite t on a kept axis, or one that breaks the entry's rules,
+// leaves as NaN partial sums.  Dynamic LDS: 2 KS_RJ Dc doubles.
+__global__ __launch_bounds__(KS_THREADS) void kstar_marginal_kernel(
+    const double* __restrict__ Xu, int N, int Dc, const double* __restrict__ tab, const double* __restrict__ alpha,
+    const double* __restrict__ lam_diag, const double* __restrict__ lam_off, int mblk, const int* __restrict__ dims,
+    const double* __restrict__ T, int effect, int M, double* __restrict__ Kt, int ldk, double* __restrict__ mu_part,
+    double* __restrict__ t_part, int q_per_split, int n_q, int edge_k0) {
+  extern __shared__ double mg_lds[];
+  __shared__ double s_P[KS_RJ], s_alpha[KS_RJ], s_ld[KS_RJ], s_lo[KS_RJ];
+  double* __restrict__ xs = mg_lds;
+  double* __restrict__ iqs = mg_lds + KS_RJ * Dc;
+  const int c = blockIdx.x * KS_THREADS + threadIdx.x;
+  const bool live = c < M;
+  const MargRow row = marginal_row(dims, T, live ? c : 0, Dc, effect);
+  const bool has_d = row.ok && row.lo >= 0, has_e = row.ok && row.hi >= 0;
+  const int di = has_d ? row.lo : 0, ei = has_e ? row.hi : 0;      // (a column of the slab that exists, read or not)
+  const double td = row.tlo, te = row.thi;
+  const double cf_d = -tab[MG_COEF + di], cf_e = -tab[MG_COEF + ei];
+  const bool per_d = tab[MG_PER + di] != 0.0, per_e = tab[MG_PER + ei] != 0.0;
+  const bool finite = row.ok && fma(has_d ? td : 0.0, 0.0, (has_e ? te : 0.0) * 0.0) == 0.0;
+  const double* __restrict__ tab_iq = tab + MG_ROWS;
+  const double* __restrict__ tab_P = tab_iq + (size_t)N * Dc;
+  double mu = 0.0, tl = 0.0, ko = 0.0;
+  const int j_beg = blockIdx.y * q_per_split * mblk;
+  int j_end = j_beg + q_per_split * mblk;
+  if (j_end > N) j_end = N;
+  const bool has_lam = (lam_diag != nullptr);
+  int rb = 0;  // row index inside the current star block (splits start on a block edge)
+  int qs = j_beg / mblk;  // ... and that block's star
+  for (int row0 = j_beg; row0 < j_end; row0 += KS_RJ) {
+    __syncthreads();
+    const int rmax = (j_end - row0 < KS_RJ) ? (j_end - row0) : KS_RJ;
+    for (int e = threadIdx.x; e < KS_RJ * Dc; e += KS_THREADS) {
+      const bool ok = e < rmax * Dc;
+      xs[e] = ok ? Xu[(size_t)row0 * Dc + e] : 0.0;
+      iqs[e] = ok ? tab_iq[(size_t)row0 * Dc + e] : 0.0;
+    }
+    if (threadIdx.x < KS_RJ) {
+      const int j = row0 + threadIdx.x;
+      const bool ok = j < j_end;
+      s_P[threadIdx.x] = ok ? tab_P[j] : 0.0;
+      s_alpha[threadIdx.x] = ok ? alpha[j] : 0.0;
+      s_ld[threadIdx.x] = (ok && has_lam) ? lam_diag[j] : 0.0;
+      s_lo[threadIdx.x] = (ok && has_lam) ? lam_off[j] : 0.0;
+    }
+    __syncthreads();
+    for (int r = 0; r < rmax; ++r) {
+      double rd = 1.0, re = 1.0;
+      if (has_d) {
+        const double dx = td - xs[r * Dc + di];
+        const double u = per_d ? sinpi(dx) : dx;
+        rd = exp_nonpos(cf_d * (u * u)) * iqs[r * Dc + di];
+      }
+      if (has_e) {
+        const double dx = te - xs[r * Dc + ei];
+        const double u = per_e ? sinpi(dx) : dx;
+        re = exp_nonpos(cf_e * (u * u)) * iqs[r * Dc + ei];
+      }
+      // the two ratios as opaque registers: F is formed from them alone, whichever branches produced them
+      asm volatile("" : "+v"(rd), "+v"(re));
+      double f;
+      if (effect == PPBO_EFFECT_INTERACTION) f = (rd - 1.0) * (re - 1.0);
+      else {
+        f = rd * re;
+        if (effect == PPBO_EFFECT_CENTRED) f -= 1.0;
+      }
+      const double dv = s_P[r] * f;
+      if (Kt) {
+        // the layouts of kstar_kernel: node form row j, edge form row n_q + q m + t = lam_off[j] (c_j - c_obs)
+        int drow = row0 + r;
+        bool wr = true;
+        double ev = dv;
+        if (edge_k0 >= 0) {
+          if (rb == 0) {
+            drow = qs;
+            wr = qs >= edge_k0;
+            ev = 0.0;
+          } else {
+            drow = n_q + qs * (mblk - 1) + rb - 1;
+            ev = s_lo[r] * (dv - ko);
+          }
+        }
+        if (wr && live) store_through(Kt + (size_t)drow * ldk + c, ev);
+      }
+      mu += s_alpha[r] * dv;
+      if (has_lam) {
+        const double ld = s_ld[r];
+        if (rb == 0) { ko = dv; tl += ld * dv * dv; }
+        else tl += dv * (ld * dv + 2.0 * s_lo[r] * ko);
+      }
+      if (++rb == mblk) { rb = 0; ++qs; }
+    }
+  }
+  if (live) {
+    mu_part[(size_t)blockIdx.y * M + c] = finite ? mu : NAN;
+    if (t_part) t_part[(size_t)blockIdx.y * M + c] = finite ? tl : NAN;
+  }
+}
+
 // Y = G K* ; slab[mt][c] = sum over the BM rows of tile mt of Y[i,c]^2
 // EDGE: an edge-form operator (H lower triangular, zero in its first n_q rows and columns).  G and Kt then arrive offset
 // by kshift = n_q rounded down to the chunk depth (G + kshift, Kt + kshift ldk): the K loop starts at 0 of the shifted
@@ -2199,6 +2359,47 @@ int launch_kstar_func(const ppbo_model* m, const KernParams& p, const double* d_
   return 0;
 }
 
+// ppbo_predict_marginals' operands: the rows of the call are d_dims / d_t [M, 2] (two_set_passes' point sets are not used)
+struct MargArgs {
+  const ppbo_marginal_axes* ax;
+  const int* d_dims;
+  const double* d_t;
+  int effect;
+  MargAxesArg arg;       // filled by marginal_axes_arg
+  double prod_A;         // prod_d A_d over ALL axes
+};
+
+// A_d = int int kappa_d(u - u') du du' on the host: 2 (l sqrt(pi / 2) erf(1 / (sqrt2 l)) - l^2 (1 - e^(-1 / (2 l^2)))) on an SE
+// axis, e^-a I0(a) on a periodic one
+int marginal_axes_arg(ppbo_ctx* ctx, MargArgs* ma) {
+  const ppbo_marginal_axes* ax = ma->ax;
+  PPBO_REQUIRE(ctx, ax != nullptr, "axes");
+  PPBO_REQUIRE(ctx, ax->Dc >= 1 && ax->Dc <= MG_AXES, "axes->Dc (1 .. 64)");
+  PPBO_REQUIRE(ctx, ax->d_Xu && ax->h_l && ax->h_periodic && ax->h_I0, "axes (d_Xu / h_l / h_periodic / h_I0)");
+  MargAxesArg& a = ma->arg;
+  a.Dc = ax->Dc;
+  a.periodic = 0;
+  ma->prod_A = 1.0;
+  for (int d = 0; d < MG_AXES; ++d) { a.l[d] = 1.0; a.i0[d] = 1.0; a.a[d] = 1.0; }
+  for (int d = 0; d < ax->Dc; ++d) {
+    const double l = ax->h_l[d];
+    PPBO_REQUIRE(ctx, std::isfinite(l) && l > 0.0, "axes->h_l: positive finite length scales");
+    PPBO_REQUIRE(ctx, ax->h_periodic[d] == 0 || ax->h_periodic[d] == 1, "axes->h_periodic (0 or 1)");
+    a.l[d] = l;
+    const double i0 = ax->h_I0[d];
+    PPBO_REQUIRE(ctx, std::isfinite(i0) && i0 > 0.0, "axes->h_I0: positive finite values (e^-a I0(a), a = 1 / l^2)");
+    a.i0[d] = i0;
+    if (ax->h_periodic[d]) {
+      a.periodic |= 1ull << d;
+      a.a[d] = i0;
+    } else {
+      a.a[d] = 2.0 * (1.25331413731550025121 * l * std::erf(0.70710678118654752440 / l) + l * l * std::expm1(-0.5 / (l * l)));
+    }
+    ma->prod_A *= a.a[d];
+  }
+  return 0;
+}
+
 int check_model(ppbo_ctx* ctx, const ppbo_model* m) {
   PPBO_REQUIRE(ctx, m != nullptr, "model");
   PPBO_REQUIRE(ctx, m->d_X && m->d_alpha, "model X/alpha");
@@ -2396,15 +2597,19 @@ static_assert(PPBO_CURV_MEAN == PPBO_PAIR_MEAN && PPBO_CURV_VARIANCE == PPBO_PAI
               "one score_kind check for all three entries");
 // Functionals (ppbo_predict_functionals) are the fourth: d_Xa the groups [M, G, D], d_Xb the weights ([G], or [M, G]),
 // `fa` their sizes and the threshold; kstar_func -> quadform -> functional_score.  fa is NULL for the other three.
-enum { TS_PAIRS = 0, TS_SLOPES = 1, TS_CURV = 2, TS_FUNC = 3 };
+// Marginals (ppbo_predict_marginals) are the fifth: the rows of the call are `ma`'s d_dims / d_t [M, 2] (d_Xa = d_Xb = d_t),
+// the column comes from ma's axes and the table marginal_table_kernel leaves per call, not from model->d_X;
+// kstar_marginal -> quadform -> marginal_score.  Its row splits are those of a FULL chunk whatever M is, so that a row's
+// sums do not depend on the size of the call.  ma is NULL for the other four.
+enum { TS_PAIRS = 0, TS_SLOPES = 1, TS_CURV = 2, TS_FUNC = 3, TS_MARG = 4 };
 static int two_set_passes(ppbo_ctx* ctx, const int what, const ppbo_model* model, const double* d_Xa, const double* d_Xb,
                           const double* d_Xacc, int64_t M, int score_kind, double* d_mu, double* d_var, double* d_prob,
                           double* d_score, double* h_best_val, int64_t* h_best_idx, hipStream_t s,
-                          const FuncArgs* fa = nullptr) {
-  const bool slopes = what == TS_SLOPES, curv = what == TS_CURV, func = what == TS_FUNC;
+                          const FuncArgs* fa = nullptr, MargArgs* ma = nullptr) {
+  const bool slopes = what == TS_SLOPES, curv = what == TS_CURV, func = what == TS_FUNC, marg = what == TS_MARG;
   if (int rc = check_model(ctx, model)) return rc;
   PPBO_REQUIRE(ctx, d_Xa != nullptr && d_Xb != nullptr,
-               func ? "functionals (d_Xg / d_w)" : curv ? "curvatures (d_X / d_Xi)" : slopes ? "slopes (d_X / d_Xi)" : "pairs (d_Xa / d_Xb)");
+               marg ? "marginals (d_dims / d_t)" : func ? "functionals (d_Xg / d_w)" : curv ? "curvatures (d_X / d_Xi)" : slopes ? "slopes (d_X / d_Xi)" : "pairs (d_Xa / d_Xb)");
   PPBO_REQUIRE(ctx, M >= 1 && M <= (int64_t)0x7fffffff, what != TS_PAIRS ? "row count (1 .. 2^31 - 1)" : "pair count (1 .. 2^31 - 1)");
   if (func) {
     PPBO_REQUIRE(ctx, fa != nullptr && fa->G >= 1 && fa->G <= PPBO_FUNCTIONAL_MAX_G, "G (1 .. PPBO_FUNCTIONAL_MAX_G points per group)");
@@ -2413,7 +2618,18 @@ static int two_set_passes(ppbo_ctx* ctx, const int what, const ppbo_model* model
   }
   PPBO_REQUIRE(ctx, score_kind == PPBO_PAIR_MEAN || score_kind == PPBO_PAIR_VARIANCE || score_kind == PPBO_PAIR_PROB,
                "score_kind");
-  PPBO_REQUIRE(ctx, !model->kstar_fp32, func ? "functionals are fp64 only (kstar_fp32)"
+  if (marg) {
+    PPBO_REQUIRE(ctx, ma != nullptr && ma->d_dims != nullptr, "marginals (d_dims / d_t)");
+    PPBO_REQUIRE(ctx, model->kernel_id == PPBO_KERNEL_SE || model->kernel_id == PPBO_KERNEL_CAMPHOR,
+                 "marginals need a kernel that is a product over coordinates (SE, camphor-copper); RQ and Matern: sample with "
+                 "ppbo_predict_functionals (average_pred)");
+    PPBO_REQUIRE(ctx, ma->effect == PPBO_EFFECT_RAW || ma->effect == PPBO_EFFECT_CENTRED || ma->effect == PPBO_EFFECT_INTERACTION,
+                 "effect");
+    if (int rc = marginal_axes_arg(ctx, ma)) return rc;
+    const bool six = model->kernel_id == PPBO_KERNEL_CAMPHOR || model->coords.kind == PPBO_COORDS_CAMPHOR;
+    PPBO_REQUIRE(ctx, ma->ax->Dc == (six ? 6 : model->D), "axes->Dc: the model's D (6 for the camphor kernels)");
+  }
+  PPBO_REQUIRE(ctx, !model->kstar_fp32, marg ? "marginals are fp64 only (kstar_fp32)" : func ? "functionals are fp64 only (kstar_fp32)"
                                              : curv ? "curvatures are fp64 only (kstar_fp32)"
                                              : slopes ? "slopes are fp64 only (kstar_fp32)" : "pairs are fp64 only (kstar_fp32)");
   if (curv) {
@@ -2445,7 +2661,7 @@ static int two_set_passes(ppbo_ctx* ctx, const int what, const ppbo_model* model
   }
   const int Mc_max = (int)(M < chunk_cap ? M : chunk_cap);
   const int ldk = (Mc_max + 127) & ~127;
-  const int n_split = pick_split(Mc_max, n_q);
+  const int n_split = pick_split(marg ? (int)chunk_cap : Mc_max, n_q);
   const int q_per_split = (n_q + n_split - 1) / n_split;
   const int n_split_eff = (n_q + q_per_split - 1) / q_per_split;
   double* Kt = nullptr;
@@ -2453,6 +2669,11 @@ static int two_set_passes(ppbo_ctx* ctx, const int what, const ppbo_model* model
     Kt = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_KSTAR, (size_t)Nk * ldk * sizeof(double));
     if (!Kt) return (int)hipErrorOutOfMemory;
     if (Nk != N) PPBO_HIP_CHECK(ctx, hipMemsetAsync(Kt + (size_t)N * ldk, 0, (size_t)(Nk - N) * ldk * sizeof(double), s));
+  }
+  double* marg_tab = nullptr;
+  if (marg) {
+    marg_tab = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_MARGINAL, marginal_table_doubles(N, ma->arg.Dc) * sizeof(double));
+    if (!marg_tab) return (int)hipErrorOutOfMemory;
   }
   // (functionals: one more row of the partial-sum workspace for the groups' prior terms)
   double* part = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_PART, (size_t)(2 * n_split_eff + ntm + (func ? 1 : 0)) * Mc_max * sizeof(double));
@@ -2463,6 +2684,32 @@ static int two_set_passes(ppbo_ctx* ctx, const int what, const ppbo_model* model
   if (!bests) return (int)hipErrorOutOfMemory;
   Best* chunk_best = bests + sblocks_max;
   const double two_sigma2 = 2.0 * model->theta[0] * model->theta[0];
+  if (marg) {
+    // the rows of d_dims are looked at on the device BEFORE anything is launched on the outputs: the first row that breaks
+    // the rules comes back through the host-mapped record.  A stream that is being captured cannot be waited on: there
+    // the look is left out, and such a row gets NaN results (marginal_row)
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    (void)hipStreamIsCapturing(s, &cap);
+    if (cap == hipStreamCaptureStatusNone) {
+      PpboHostRecord chk{};
+      if (int rc = ppbo_host_record(ctx, &chk)) return rc;
+      const int cblocks = (int)std::min<int64_t>((M + 255) / 256, (int64_t)sblocks_max);
+      marginal_check_kernel<<<cblocks, 256, 0, s>>>(ma->d_dims, (long long)M, ma->arg.Dc, ma->effect, bests);
+      PPBO_LAUNCH_CHECK(ctx);
+      argmax_final_kernel<<<1, 256, 0, s>>>(bests, cblocks, nullptr, chk.d_rec, 0, chk.d_flag, chk.epoch);
+      PPBO_LAUNCH_CHECK(ctx);
+      if (int rc = ppbo_host_record_wait(ctx, chk, s)) return rc;
+      const long long bad = (long long)chk.h_rec[1];
+      if (bad >= 0)
+        return ppbo_set_error(ctx, -1,
+                              "invalid argument: d_dims row %lld (axes in -1 .. Dc - 1, two different ones, no first axis of -1 "
+                              "with a second one, two axes for an interaction)", bad);
+      if (want_best)               // (a fresh epoch for the call's own record, behind the check's)
+        if (int rc = ppbo_host_record(ctx, &hr)) return rc;
+    }
+    marginal_table_kernel<<<(N + 255) / 256, 256, 0, s>>>(ma->arg, ma->ax->d_Xu, N, p.sf2, marg_tab);
+    PPBO_LAUNCH_CHECK(ctx);
+  }
   for (int64_t ch = 0; ch < n_chunks; ++ch) {
     const int64_t c_beg = ch * chunk_cap;
     const int Mc = (int)((M - c_beg) < chunk_cap ? (M - c_beg) : chunk_cap);
@@ -2478,7 +2725,14 @@ static int two_set_passes(ppbo_ctx* ctx, const int what, const ppbo_model* model
           constexpr int KID = decltype(kid)::value;
           {
             PpboProfScope pf(ctx, ppbo_ctx::PF_KSTAR, s);
-            if (func)
+            if (marg) {
+              dim3 grid((Mc + KS_THREADS - 1) / KS_THREADS, n_split_eff);
+              const int Dc = ma->arg.Dc;
+              kstar_marginal_kernel<<<grid, KS_THREADS, (size_t)2 * KS_RJ * Dc * sizeof(double), s>>>(
+                  ma->ax->d_Xu, N, Dc, marg_tab, model->d_alpha, want_var ? model->d_lam_diag : nullptr,
+                  want_var ? model->d_lam_off : nullptr, mblk, ma->d_dims + (size_t)c_beg * 2, ma->d_t + (size_t)c_beg * 2,
+                  ma->effect, Mc, Kt, ldk, mu_part, want_var ? t_part : nullptr, q_per_split, n_q, edge_k0);
+            } else if (func)
               launch_kstar_func<KID>(model, p, xa, xb, *fa, Mc, Kt, ldk, mu_part, t_part, q_per_split, n_split_eff, want_var,
                                      edge_k0, s);
             else if (curv) {
@@ -2498,7 +2752,13 @@ static int two_set_passes(ppbo_ctx* ctx, const int what, const ppbo_model* model
             if (int rc2 = dispatch_quadform(ctx, Gq, Nk, g_rows, N, Kt, ldk, Mc, mblk, slab, edge_k0, s)) return rc2;
           }
           PpboProfScope pfs(ctx, ppbo_ctx::PF_SCORE, s);
-          if (func) {
+          if (marg) {
+            marginal_score_kernel<<<sblocks, SC_THREADS, 0, s>>>(
+                mu_part, n_split_eff, t_part, want_var ? slab : nullptr, ntm, Mc, ma->d_dims + (size_t)c_beg * 2,
+                ma->d_t + (size_t)c_beg * 2, marg_tab, ma->arg.Dc, p.sf2, ma->prod_A, ma->effect, score_kind, (long long)c_beg,
+                d_mu ? d_mu + c_beg : nullptr, d_var ? d_var + c_beg : nullptr, d_prob ? d_prob + c_beg : nullptr,
+                d_score ? d_score + c_beg : nullptr, want_best ? bests : nullptr);
+          } else if (func) {
             if (want_var) {
               // one wavefront per group; as many per workgroup (4, 2, 1) as 48 KB of LDS hold of G (D + 1) doubles each
               const size_t per_wave = (size_t)fa->G * (model->D + 1) * sizeof(double);
@@ -2588,6 +2848,21 @@ int ppbo_predict_functionals(ppbo_ctx* ctx, const ppbo_model* model, const doubl
   const FuncArgs fa{G, w_stride, threshold};
   return two_set_passes(ctx, TS_FUNC, model, d_Xg, d_w, nullptr, M, score_kind, d_mu, d_var, d_prob, d_score, h_best_val,
                         h_best_idx, (hipStream_t)stream, &fa);
+}
+
+// Main effects and interactions: the column c_j = P_j F(r_d, r_e) of f with every axis but at most two averaged over the
+// unit box, from the caller's axes (not from model->d_X); the K* launches share the "kstar" profile slot.
+int ppbo_predict_marginals(ppbo_ctx* ctx, const ppbo_model* model, const ppbo_marginal_axes* axes, const int* d_dims,
+                           const double* d_t, int64_t M, int effect, int score_kind, double* d_mu, double* d_var,
+                           double* d_prob, double* d_score, double* h_best_val, int64_t* h_best_idx, void* stream) {
+  PPBO_ENTER(ctx);
+  MargArgs ma{};
+  ma.ax = axes;
+  ma.d_dims = d_dims;
+  ma.d_t = d_t;
+  ma.effect = effect;
+  return two_set_passes(ctx, TS_MARG, model, d_t, d_t, nullptr, M, score_kind, d_mu, d_var, d_prob, d_score, h_best_val,
+                        h_best_idx, (hipStream_t)stream, nullptr, &ma);
 }
 
 }  // extern "C"

@@ -489,6 +489,139 @@ __global__ __launch_bounds__(SC_THREADS) void functional_score_kernel(const doub
   if (lane == 0) blk_best[blockIdx.x] = b;
 }
 
+// ---- main effects and interactions (ppbo_predict_marginals) -----------------------------------------------------------
+// The axis table a call leaves in the ctx (marginal_table_kernel, predict.hip): five rows of MG_AXES doubles per axis d
+//   MG_COEF  the exponent's coefficient: 1 / (2 l^2) on an SE axis, 2 / l^2 on a periodic one
+//   MG_PER   1.0 on a periodic axis, else 0.0
+//   MG_I0    e^-a I0(a), a = 1 / l^2: the integral of a periodic factor over [0, 1], whatever its centre
+//   MG_L     l
+//   MG_A     A_d, the factor integrated over both of its arguments
+// followed by 1 / Q[N, Dc] and P[N] of the design rows.
+constexpr int MG_AXES = 64;
+enum { MG_COEF = 0, MG_PER = MG_AXES, MG_I0 = 2 * MG_AXES, MG_L = 3 * MG_AXES, MG_A = 4 * MG_AXES, MG_ROWS = 5 * MG_AXES };
+
+// I_d(c) = int_0^1 kappa_d(u - c) du of an SE axis: l sqrt(pi / 2) (erf((1 - c) / (sqrt2 l)) + erf(c / (sqrt2 l)))
+__device__ __forceinline__ double marginal_se_integral(double c, double l) {
+  const double il = 0.70710678118654752440 / l;
+  return (1.25331413731550025121 * l) * (erf((1.0 - c) * il) + erf(c * il));
+}
+
+// One row of the call in canonical form: its kept axes in ASCENDING order with their values (lo < hi, or hi = -1, or
+// both -1), so that (d, e, t, u) and (e, d, u, t) are the same row to every kernel.  ok = false: a row that breaks the
+// rules of the entry (an axis outside -1 .. Dc - 1, the same axis twice, a first axis of -1 with a second one, an
+// interaction of order below 2).  The entry refuses such a call before anything is launched; where it cannot look (a
+// stream that is being captured) the row gets NaN results.
+struct MargRow {
+  int lo, hi;
+  double tlo, thi;
+  bool ok;
+};
+__device__ __forceinline__ MargRow marginal_row(const int* __restrict__ dims, const double* __restrict__ T, long long c,
+                                                int Dc, int effect) {
+  MargRow r;
+  r.lo = dims[2 * c]; r.hi = dims[2 * c + 1];
+  r.tlo = T ? T[2 * c] : 0.0; r.thi = T ? T[2 * c + 1] : 0.0;
+  r.ok = r.lo >= -1 && r.lo < Dc && r.hi >= -1 && r.hi < Dc && (r.lo >= 0 || r.hi < 0) && (r.lo != r.hi || r.lo < 0) &&
+         (effect != PPBO_EFFECT_INTERACTION || r.hi >= 0);
+  if (r.hi >= 0 && r.hi < r.lo) {
+    const int d = r.lo; r.lo = r.hi; r.hi = d;
+    const double t = r.tlo; r.tlo = r.thi; r.thi = t;
+  }
+  return r;
+}
+
+// The first row of d_dims that breaks the rules, as a Best record per workgroup (value 1, the row's index; idx = -1:
+// none), merged by argmax_final_kernel into the host-mapped record: equal values, so the smallest index wins.
+__global__ __launch_bounds__(256) void marginal_check_kernel(const int* __restrict__ dims, long long M, int Dc, int effect,
+                                                             Best* __restrict__ blk_best) {
+  __shared__ Best sh[4];
+  Best b{0.0, -1};
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < M; i += (long long)gridDim.x * 256)
+    if (b.idx < 0 && !marginal_row(dims, nullptr, i, Dc, effect).ok) b = Best{1.0, i};
+  b = block_best(b, sh);
+  if (threadIdx.x == 0) blk_best[blockIdx.x] = b;
+}
+
+// Pass 3 of ppbo_predict_marginals: slope_score_kernel's geometry and slab sums for the column of a main effect or an
+// interaction, then
+//   mu = sum of the mean partials,   var = prior + c' Lambda c + |G c|^2,   p = P(L f > 0) = Phi(mu / sqrt(max(var, 0)))
+// With S = sf2 prod_{d not kept} A_d (the host's product over ALL axes divided by the kept A_d), a_d = I_d(t_d) (erf at t_d
+// on an SE axis, the table's constant on a periodic one) and b_d = 1 - 2 a_d + A_d:
+//   RAW S;   CENTRED S (1 - 2 prod a_d + prod A_d);   INTERACTION S b_d b_e          (products over the kept axes)
+// An order-0 row under CENTRED: 1 - 2 + 1 = 0 exactly, and its column is zero, so (0, 0, 1/2).  No noise term.  var = 0: the
+// sign of mu decides, mu = 0 gives 1/2; a NaN mean (a non-finite t on a kept axis) gives NaN everywhere.
+__global__ __launch_bounds__(SC_THREADS) void marginal_score_kernel(const double* __restrict__ mu_part, int n_mu,
+                                                                    const double* __restrict__ t_part,
+                                                                    const double* __restrict__ slab, int n_slab, int M,
+                                                                    const int* __restrict__ dims,
+                                                                    const double* __restrict__ T,
+                                                                    const double* __restrict__ tab, int Dc, double sf2,
+                                                                    double prod_A, int effect, int kind, long long idx_base,
+                                                                    double* __restrict__ mu_out, double* __restrict__ var_out,
+                                                                    double* __restrict__ prob_out,
+                                                                    double* __restrict__ score_out, Best* __restrict__ blk_best) {
+  __shared__ double part[3][SC_WAVES][SC_CAND];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int c = blockIdx.x * SC_CAND + lane;
+  double pm = 0.0, pt = 0.0, pq = 0.0;
+  if (c < M) {
+    for (int s = wave; s < n_mu; s += SC_WAVES) pm += mu_part[(size_t)s * M + c];
+    if (slab) {
+      for (int s = wave; s < n_mu; s += SC_WAVES) pt += t_part[(size_t)s * M + c];
+      for (int s = wave; s < n_slab; s += SC_WAVES) pq += slab[(size_t)s * M + c];
+    }
+  }
+  part[0][wave][lane] = pm;
+  part[1][wave][lane] = pt;
+  part[2][wave][lane] = pq;
+  __syncthreads();
+  if (wave != 0) return;                 // the rest is one wavefront's work
+  Best b{0.0, -1};
+  if (c < M) {
+    double mu = 0.0, t = 0.0, q = 0.0;
+#pragma unroll
+    for (int w = 0; w < SC_WAVES; ++w) { mu += part[0][w][lane]; t += part[1][w][lane]; q += part[2][w][lane]; }
+    double var = NAN, pr = NAN, sc = mu;   // mean only (no slab): nothing but mu is formed
+    if (slab) {
+      const MargRow row = marginal_row(dims, T, c, Dc, effect);
+      double S = sf2 * prod_A, pa = 1.0, pA = 1.0, bb = 1.0;
+#pragma unroll
+      for (int k = 0; k < 2; ++k) {
+        const int d = k ? row.hi : row.lo;
+        if (!row.ok || d < 0) continue;
+        const double A = tab[MG_A + d];
+        const double a = tab[MG_PER + d] != 0.0 ? tab[MG_I0 + d] : marginal_se_integral(k ? row.thi : row.tlo, tab[MG_L + d]);
+        S /= A;
+        pa *= a;
+        pA *= A;
+        bb *= (1.0 - 2.0 * a) + A;
+      }
+      const double prior = effect == PPBO_EFFECT_RAW ? S : (effect == PPBO_EFFECT_CENTRED ? S * ((1.0 - 2.0 * pa) + pA) : S * bb);
+      var = prior + t + q;
+      const double sd = sqrt(fmax(var, 0.0));
+      // sd = 0 (no variance): the sign of mu decides, a tie is 1/2
+      pr = norm_cdf(sd > 0.0 ? mu / sd : (mu > 0.0 ? INFINITY : (mu < 0.0 ? -INFINITY : 0.0)));
+      if (mu != mu) { var = mu; pr = mu; }
+      if (kind == PPBO_PAIR_VARIANCE) sc = var;
+      else if (kind == PPBO_PAIR_PROB) sc = pr;
+    }
+    if (mu_out) mu_out[c] = mu;
+    if (var_out) var_out[c] = var;
+    if (prob_out) prob_out[c] = pr;
+    if (score_out) score_out[c] = sc;
+    if (sc == sc) { b.val = sc; b.idx = idx_base + c; }
+  }
+  if (!blk_best) return;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    Best other;
+    other.val = __shfl_xor(b.val, o, 64);
+    other.idx = __shfl_xor(b.idx, o, 64);
+    b = best_merge(b, other);
+  }
+  if (lane == 0) blk_best[blockIdx.x] = b;
+}
+
 // per-block records of one launch -> *out; with `record` also the 16-byte (value, GLOBAL index as a double: exact
 // below 2^53; index + record_offset; (NaN, -1) when nothing scored) record that the sharded search all-gathers, and
 // with `publish` the flag publish[0] raised to `epoch` AFTER the record with system-scope release semantics (the

@@ -14,6 +14,7 @@ from ._lib import PAIR_MEAN, PAIR_VARIANCE, PAIR_PROB  # noqa: F401
 from ._lib import SLOPE_MEAN, SLOPE_VARIANCE, SLOPE_PROB  # noqa: F401
 from ._lib import CURV_MEAN, CURV_VARIANCE, CURV_PROB  # noqa: F401
 from ._lib import FUNCTIONAL_MEAN, FUNCTIONAL_VARIANCE, FUNCTIONAL_PROB, FUNCTIONAL_MAX_G  # noqa: F401
+from ._lib import EFFECT_RAW, EFFECT_CENTRED, EFFECT_INTERACTION, MARGINAL_MAX_DC  # noqa: F401
 
 # Posterior.form: which variance operator G holds (include/ppbo_hip.h, PPBO_FORM_*)
 FORM_NODE = 0   # G = R Lambda, block lower triangular [N, N]
@@ -110,6 +111,70 @@ def theta_key(theta):
     return (float(theta[0]), float(l) if np.ndim(l) == 0 else tuple(float(v) for v in np.ravel(l)), float(theta[2]))
 
 
+# ---- main effects and interactions (ppbo_predict_marginals): the host side of the axes and the rows of a call --------------
+EFFECTS = {"raw": EFFECT_RAW, "centred": EFFECT_CENTRED, "interaction": EFFECT_INTERACTION}
+
+
+def marginal_axis_params(kernel, theta, D, scale=None, camphor=None):
+    """(l [Dc], periodic [Dc], I0 [Dc]) of the per-coordinate factors of a kernel that is a product over the caller's
+    unit-box coordinates: SE with a scalar l or with per-dimension length scales (scale = 1 / l), the camphor-copper
+    kernel with its profile (l, l, l + 0.05, l, l, l) or with six length scales (camphor).  I0 is the scaled Bessel value
+    e^-a I0(a), a = 1 / l^2 (scipy.special.ive: never a product of two factors).  ValueError for any other kernel: RQ and
+    the Matern kernels are radial, not products -- GPModel.average_pred samples the box instead."""
+    from scipy.special import ive
+    if camphor is not None or kernel == CAMPHOR_ARD:
+        l = np.asarray(camphor if camphor is not None else camphor_lengthscales(theta, 6), dtype=float).reshape(-1)
+        periodic = np.array([1, 1, 0, 1, 1, 1], dtype=np.intc)
+    elif kernel == "camphor_copper_kernel":
+        l = float(theta[1]) + CAMPHOR_PROFILE
+        periodic = np.array([1, 1, 0, 1, 1, 1], dtype=np.intc)
+    elif kernel == "SE_kernel":
+        l = 1.0 / np.asarray(scale, dtype=float).reshape(-1) if scale is not None else np.full(int(D), float(theta[1]))
+        periodic = np.zeros(l.size, dtype=np.intc)
+    else:
+        raise ValueError(f"predict_marginals: {kernel} is not a product over coordinates (SE_kernel, camphor_copper_kernel and "
+                         f"{CAMPHOR_ARD} are); average_pred samples the box for a radial kernel")
+    if l.size < 1 or l.size > MARGINAL_MAX_DC or not (np.all(np.isfinite(l)) and np.all(l > 0.0)):
+        raise ValueError(f"predict_marginals: length scales {l} (1 .. {MARGINAL_MAX_DC} positive finite values)")
+    return l, periodic, ive(0, 1.0 / (l * l))
+
+
+def marginal_rows(dims, t, Dc, effect):
+    """The rows of a predict_marginals call as (dims [M, 2] int32, t [M, 2] float64) in canonical form: axes ascending,
+    -1 = unused and last, the value of an unused axis 0.  dims: [M, 2], [M, 1], or one-dimensional [M] = ONE axis per row
+    (order 1, whatever M is: a single order-2 row is [[d, e]], never [d, e]); a scalar is one order-1 row; t has the
+    shape of dims.  ValueError for an axis outside -1 .. Dc - 1, the same axis twice, a first axis of -1 with a second
+    one, an interaction of order below 2, or shapes that do not fit."""
+    dims = np.asarray(dims)
+    if dims.size and not np.all(np.equal(np.mod(dims, 1), 0)):
+        raise ValueError("predict_marginals: axes must be integers")
+    dims = dims.astype(np.int64)
+    t = np.asarray(t, dtype=float)
+    if dims.ndim == 0 and t.ndim == 0:
+        dims, t = dims.reshape(1, 1), t.reshape(1, 1)
+    elif dims.ndim == 1 and t.ndim == 1 and dims.size == t.size:
+        dims, t = dims.reshape(-1, 1), t.reshape(-1, 1)
+    if dims.ndim != 2 or dims.shape[1] not in (1, 2) or t.shape != dims.shape or dims.shape[0] < 1:
+        raise ValueError(f"predict_marginals: axes of shape {dims.shape} and values of shape {t.shape} ([M, 2] each)")
+    if dims.shape[1] == 1:
+        dims = np.concatenate([dims, np.full_like(dims, -1)], axis=1)
+        t = np.concatenate([t, np.zeros_like(t)], axis=1)
+    d, e = dims[:, 0], dims[:, 1]
+    if np.any(dims < -1) or np.any(dims >= Dc):
+        raise ValueError(f"predict_marginals: an axis outside -1 .. {Dc - 1}")
+    if np.any((d == e) & (d >= 0)):
+        raise ValueError("predict_marginals: a row names the same axis twice")
+    if np.any((d < 0) & (e >= 0)):
+        raise ValueError("predict_marginals: a first axis of -1 with a second one")
+    if effect == EFFECT_INTERACTION and np.any(e < 0):
+        raise ValueError("predict_marginals: an interaction needs two axes in every row")
+    swap = (e >= 0) & (e < d)
+    dims = np.where(swap[:, None], dims[:, ::-1], dims)
+    t = np.where(swap[:, None], t[:, ::-1], t)
+    t = np.where(dims < 0, 0.0, t)
+    return np.ascontiguousarray(dims, dtype=np.int32), np.ascontiguousarray(t, dtype=np.float64)
+
+
 class NotPositiveDefinite(RuntimeError):
     def __init__(self, msg, info=0):
         super().__init__(msg)
@@ -133,6 +198,7 @@ class Posterior:
     Gt: torch.Tensor | None = None  # transpose of G in the one-launch scoring kernel's layout (formed on first use)
     scale: np.ndarray | None = None  # ARD: s_d = 1 / l_d (None: a scalar length scale)
     camphor: np.ndarray | None = None  # camphor_copper_ard_kernel: l_0..l_5; X then holds the embedded rows [N, 11]
+    Xu: torch.Tensor | None = None     # ARD: the rows in the caller's unit-box coordinates (formed on first use, marginal_axes)
     Xc: torch.Tensor | None = None     # ... and this the caller's rows [N, 6] (mu_star searches in their coordinates)
     form: int = FORM_NODE              # FORM_NODE / FORM_EDGE: how G is to be read (ppbo_model.form)
 
@@ -841,6 +907,72 @@ class Engine:
                                                C.byref(bv) if want_best else None, C.byref(bi) if want_best else None,
                                                self._stream())
         self._check(rc, "ppbo_predict_functionals")
+        return dict(mu=mu, var=var, prob=pr, score=sc, best_val=bv.value, best_idx=bi.value)
+
+    def marginal_axes(self, post: Posterior):
+        """The ppbo_marginal_axes of a posterior: its design rows in unit-box caller coordinates (the rows themselves; an ARD
+        model's scaled rows divided by the scale again, kept on the posterior; the caller's six-column rows of a camphor model with
+        per-coordinate length scales) and marginal_axis_params' host arrays.  ValueError for a kernel that is not a
+        product over coordinates, before anything reaches the device."""
+        D = 6 if post.camphor is not None else post.X.shape[1]
+        l, periodic, I0 = marginal_axis_params(post.kernel, post.theta, D, post.scale, post.camphor)
+        if post.camphor is not None:
+            if post.Xc is None:
+                raise ValueError("predict_marginals: a camphor model without its rows in the caller's coordinates")
+            Xu = post.Xc
+        elif post.scale is not None:
+            # once per posterior, as Gt is (the scaled rows divided by the scale again: within an ulp of the caller's)
+            if post.Xu is None or post.Xu.device != post.X.device:
+                post.Xu = self.scale_points(post.X, 1.0 / np.asarray(post.scale, dtype=float))
+            Xu = post.Xu
+        else:
+            Xu = post.X
+        ax = _lib.marginal_axes(Xu.data_ptr(), l, periodic, I0)
+        ax._Xu = Xu
+        return ax
+
+    def predict_marginals(self, post: Posterior, dims, t, effect=EFFECT_CENTRED, kind=PAIR_PROB, want_best=True,
+                          want_mu=True, want_var=True, want_prob=True, want_score=False, axes=None):
+        """Main effects and interactions (ppbo_predict_marginals): row i keeps the axes dims[i] (0-based, -1 = unused; [M, 2],
+        or one-dimensional [M] = one axis per row) at the values t[i] in the unit box and averages f over every other coordinate.  effect:
+        EFFECT_RAW the marginal itself, EFFECT_CENTRED (default) minus the overall mean, EFFECT_INTERACTION the pure
+        interaction f_de - f_d - f_e + fbar.  Returns device tensors mu / var / prob / score (None where not asked for;
+        prob = P(L f > 0)) and best_val / best_idx of the quantity `kind` names (PAIR_MEAN / PAIR_VARIANCE / PAIR_PROB).
+        ValueError, before anything reaches the device, for a kernel that is not a product over coordinates (RQ, Matern)
+        and for rows that break the rules (marginal_rows).  Rows that already live on the device -- dims an int32 and t a
+        float64 tensor of shape [M, 2] there -- are handed over as they are (the library looks at them itself), and
+        axes = marginal_axes(post) may be formed once and passed to every call: such a call touches no host memory and
+        can be captured into a graph."""
+        effect = EFFECTS.get(effect, effect)
+        if effect not in (EFFECT_RAW, EFFECT_CENTRED, EFFECT_INTERACTION):
+            raise ValueError(f"predict_marginals: unknown effect {effect}")
+        if kind not in (PAIR_MEAN, PAIR_VARIANCE, PAIR_PROB):
+            raise ValueError(f"predict_marginals: unknown score kind {kind}")
+        ax = self.marginal_axes(post) if axes is None else axes
+        on_device = all(isinstance(a, torch.Tensor) and a.device == self.device and a.dim() == 2 and a.shape[1] == 2
+                        and a.is_contiguous() for a in (dims, t))
+        if on_device and dims.dtype == torch.int32 and t.dtype == torch.float64 and dims.shape == t.shape:
+            d_dims, d_t = dims, t
+        else:
+            if isinstance(dims, torch.Tensor):
+                dims = dims.cpu().numpy()
+            if isinstance(t, torch.Tensor):
+                t = t.cpu().numpy()
+            dims, t = marginal_rows(dims, t, ax.Dc, effect)
+            d_dims, d_t = self.dev(dims, dtype=torch.int32), self.dev(t)
+        M = d_dims.shape[0]
+        with_var = want_var or want_prob or kind != PAIR_MEAN
+        md = self._model(post, with_var)
+        mu = self.empty(M) if want_mu else None
+        var = self.empty(M) if want_var else None
+        pr = self.empty(M) if want_prob else None
+        sc = self.empty(M) if want_score else None
+        bv, bi = C.c_double(0.0), C.c_int64(-1)
+        rc = self.lib.ppbo_predict_marginals(self.ctx, C.byref(md), C.byref(ax), _ptr(d_dims), _ptr(d_t), M, int(effect),
+                                             int(kind), _ptr(mu), _ptr(var), _ptr(pr), _ptr(sc),
+                                             C.byref(bv) if want_best else None, C.byref(bi) if want_best else None,
+                                             self._stream())
+        self._check(rc, "ppbo_predict_marginals")
         return dict(mu=mu, var=var, prob=pr, score=sc, best_val=bv.value, best_idx=bi.value)
 
     def predict_cov(self, post: Posterior, Xc, shrink=SHRINKAGE):

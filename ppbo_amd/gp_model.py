@@ -22,7 +22,7 @@ import scipy.optimize
 import torch
 
 from . import kernels as _kernels
-from .engine import (ARD_KERNELS, CAMPHOR_ARD, NotPositiveDefinite, SCORE_MEAN, get_engine, lengthscales,
+from .engine import (ARD_KERNELS, CAMPHOR_ARD, NotPositiveDefinite, PAIR_MEAN, SCORE_MEAN, get_engine, lengthscales,
                      theta_key)
 from .feedback_processing import FeedbackProcessing
 
@@ -929,6 +929,71 @@ class GPModel:
             Xg = Xg.reshape(1, *Xg.shape)
         out = self.eng.predict_functionals(post, Xg, w, threshold=threshold, want_best=False)
         return out["mu"].cpu().numpy(), out["var"].cpu().numpy(), out["prob"].cpu().numpy()
+
+    def marginal_pred(self, dims, t, effect="centred"):
+        """(mu, var, p) as NumPy arrays of f with every coordinate but the kept ones averaged over the unit box
+        (ppbo_predict_marginals; no reference counterpart).  Row i keeps the 0-based axes dims[i] ([M, 2] with -1 = unused,
+        or one-dimensional [M] for ONE axis per row whatever M is: a single order-2 row is [[d, e]]) at the values t[i]; effect: "raw" the marginal itself, "centred" (default) minus the
+        overall mean of f, "interaction" the pure interaction f_de - f_d - f_e + fbar; p = P(effect > 0), without a
+        noise term.  A utility learned from preferences is defined up to a constant, so "centred" and "interaction"
+        are the identifiable quantities.  Closed form for SE_kernel (scalar or per-dimension length scales) and the
+        camphor-copper kernels; ValueError for RQ and the Matern kernels (average_pred samples the box instead) and for
+        rows that break the rules."""
+        post = self._var_post()
+        out = self.eng.predict_marginals(post, dims, t, effect=effect, want_best=False)
+        return out["mu"].cpu().numpy(), out["var"].cpu().numpy(), out["prob"].cpu().numpy()
+
+    @staticmethod
+    def _effect_grid(grid, default=65):
+        g = np.linspace(0.0, 1.0, default) if grid is None else np.asarray(grid, dtype=float).reshape(-1)
+        if g.size < 1:
+            raise ValueError("an effect needs at least one grid point")
+        return g
+
+    def main_effect(self, d, grid=None):
+        """(grid, mu, var, p) of the centred main effect of coordinate d (0-based, as the rows of sensitivity()): how the
+        utility depends on x_d once every other coordinate is averaged out, relative to the overall mean.  Default
+        grid: 65 equispaced points of [0, 1]."""
+        g = self._effect_grid(grid)
+        mu, var, p = self.marginal_pred(np.full((g.size, 1), int(d)), g.reshape(-1, 1), effect="centred")
+        return g, mu, var, p
+
+    def interaction_effect(self, d, e, grid_d=None, grid_e=None, pure=True):
+        """(mu, var, p) as [T_d, T_e] arrays over grid_d x grid_e (default 65 equispaced points each) of the interaction of
+        the coordinates d and e: pure=True the pure interaction f_de - f_d - f_e + fbar (zero where the two act
+        additively), pure=False the centred two-dimensional marginal f_de - fbar."""
+        gd, ge = self._effect_grid(grid_d), self._effect_grid(grid_e)
+        dims = np.tile(np.array([[int(d), int(e)]]), (gd.size * ge.size, 1))
+        t = np.stack(np.meshgrid(gd, ge, indexing="ij"), axis=-1).reshape(-1, 2)
+        mu, var, p = self.marginal_pred(dims, t, effect="interaction" if pure else "centred")
+        return tuple(a.reshape(gd.size, ge.size) for a in (mu, var, p))
+
+    def effect_importance(self, T=33):
+        """The global companion of sensitivity(): which coordinates matter over the whole box, and which pairs interact.
+        Returns a dict with, per axis, `main_range` [D] (max - min of the centred main-effect mean over T equispaced
+        points), `main_argmax` [D] (its maximiser) and `main_sd` [D] (the largest posterior sd on the grid), and per
+        pair d < e `pairs` [D (D - 1) / 2, 2] with `interaction_max` (the largest |mu| of the pure interaction on the
+        T x T grid).  All D main-effect maps come from ONE predict_marginals call, all pair maps from one more."""
+        post = self._var_post()
+        D = int(self.D)
+        g = self._effect_grid(None, int(T))
+        T = g.size
+        dims = np.repeat(np.arange(D), T)
+        out = self.eng.predict_marginals(post, dims.reshape(-1, 1), np.tile(g, D).reshape(-1, 1), effect="centred",
+                                         want_prob=False, kind=PAIR_MEAN, want_best=False)
+        mu = out["mu"].cpu().numpy().reshape(D, T)
+        sd = np.sqrt(np.maximum(out["var"].cpu().numpy().reshape(D, T), 0.0))
+        res = dict(grid=g, main_range=mu.max(axis=1) - mu.min(axis=1), main_argmax=g[mu.argmax(axis=1)],
+                   main_sd=sd.max(axis=1), pairs=np.zeros((0, 2), dtype=int), interaction_max=np.zeros(0))
+        pairs = np.array([(d, e) for d in range(D) for e in range(d + 1, D)], dtype=int).reshape(-1, 2)
+        if len(pairs):
+            tt = np.stack(np.meshgrid(g, g, indexing="ij"), axis=-1).reshape(-1, 2)
+            out = self.eng.predict_marginals(post, np.repeat(pairs, T * T, axis=0), np.tile(tt, (len(pairs), 1)),
+                                             effect="interaction", want_var=False, want_prob=False, kind=PAIR_MEAN,
+                                             want_best=False)
+            res["pairs"] = pairs
+            res["interaction_max"] = np.abs(out["mu"].cpu().numpy().reshape(len(pairs), T * T)).max(axis=1)
+        return res
 
     def _neighbourhoods(self, X, offsets):
         """[M, G, D] clouds x + delta_g in the caller's coordinates, clipped to the box; the periodic coordinates of the
