@@ -552,6 +552,49 @@ PPBO_API int ppbo_predict_marginals(ppbo_ctx* ctx, const ppbo_model* model, cons
                         const double* d_t, int64_t M, int effect, int score_kind, double* d_mu, double* d_var,
                         double* d_prob, double* d_score, double* h_best_val, int64_t* h_best_idx, void* stream);
 
+/* ---- tournaments: every candidate a_i against every opponent b_j, win matrix and scores (no reference counterpart) ----
+ * How does each of Ma candidates fare against a whole field of Mb opponents: the K x K win matrix of a shortlist, the
+ * Borda (soft-Copeland) winner of preferential Bayesian optimisation, the candidate with the best chance against its
+ * strongest opponent.  ppbo_predict_pairs on the Ma Mb explicit pairs pays one N^2 contraction per pair; the covariance
+ * is bilinear, so none of that is needed.  With sigma^2(x) = sigma_f^2 + k*' Lambda k* + |M k*|^2, M = G in the node form
+ * and M = H diag(w) D in the edge form ("the variance operator in EDGE form" below):
+ *   cov(f(a), f(b)) = k(a, b) + k_a' u_b,   u_b = (Lambda + M'M) k_b
+ *   var_d(a, b)     = var_a + var_b - 2 cov(a, b)
+ *   p(a > b)        = Phi((mu_a - mu_b) / sqrt(2 sigma^2 + max(var_d, 0))),  sigma = theta[0]
+ * The Mb opponents cost O(N^2 Mb) once per call (u_b for the whole field, in the row layout of the model's form), every
+ * candidate the one contraction ppbo_predict pays for var_a, and all Ma x Mb cross terms are ONE Ma x N x Mb product on
+ * the fp64 matrix cores whose epilogue adds the prior k(a, b) (direct differences) and forms cov, var_d and p in registers.
+ * d_Xa [Ma, D], d_Xb [Mb, D]: the two sets in the MODEL's coordinates, as ppbo_predict_pairs takes its sides (scaled rows
+ * of an ARD model, embedded rows of a camphor model with per-coordinate length scales).
+ * Outputs, each may be NULL: d_mu_a, d_var_a [Ma] and d_mu_b, d_var_b [Mb], bit for bit what ppbo_predict gives for the
+ * same set (the same launches); d_cov, d_prob [Ma, Mb] row-major -- nothing of size Ma Mb is formed unless asked for;
+ * d_score [Ma], the quantity score_kind names:
+ *   PPBO_TOURNAMENT_BORDA   (1 / Mb) sum_j p_ij, the chance of beating a random opponent of the field: summed in a FIXED
+ *                           order (the 16 opponents of a lane group, the groups of a 128- or 32-column tile, then the
+ *                           tiles in index order), so a repeated call is bitwise equal
+ *   PPBO_TOURNAMENT_WORST   min_j p_ij, the chance against the strongest opponent
+ * and h_best_val / h_best_idx, the largest score and its FIRST index; NaN never wins, (NaN, -1) when nothing scored.
+ * A non-finite coordinate in a_i gives NaN in row i only (mu, var, cov, p, score).  A non-finite coordinate in b_j gives
+ * NaN in column j and in EVERY row's score, sum and minimum alike: a NaN opponent poisons the field.
+ * The a rows go in chunks of 65536 through ppbo_predict's workspaces; a row's cov, var_d and p depend on its own mu_a and
+ * var_a and on the field only, so they follow ppbo_predict's own independence of the other rows of the call.
+ * Accuracy: var_d is formed from the three terms var_a, var_b and cov, each accurate to ~1e-15 sigma_f^2 in ABSOLUTE
+ * terms; it inherits that absolute accuracy, not the relative digits of a small difference.  For near-ties (a ~ b, where
+ * var_d << sigma_f^2 and its relative digits decide p) ppbo_predict_pairs remains the tool: it forms the difference
+ * column directly.  cov is clipped at (var_a + var_b) / 2, its bound from Var[f(a) - f(b)] >= 0, so var_d formed from
+ * the outputs in that order is never negative, and a == b gives var_d = 0 and p = 1/2 wherever ppbo_predict gives
+ * the point the same bits in both sets.
+ * "invalid argument", with nothing launched: a NULL model, d_Xa or d_Xb; Ma outside 1 .. 2^31 - 1; Mb outside
+ * 1 .. PPBO_TOURNAMENT_MAX_B (callers chunk the field); an unknown score_kind; model->kstar_fp32 set (fp64 only); a model
+ * without d_G or Lambda; a form outside {PPBO_FORM_NODE, PPBO_FORM_EDGE}.
+ * The launches of the cross product are timed as "tournament", the field pass as "tournament_field" (ppbo_profile_read). */
+#define PPBO_TOURNAMENT_MAX_B 1024
+enum { PPBO_TOURNAMENT_BORDA = 0, PPBO_TOURNAMENT_WORST = 1 };
+PPBO_API int ppbo_predict_tournament(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xa, int64_t Ma,
+                        const double* d_Xb, int Mb, int score_kind, double* d_mu_a, double* d_var_a, double* d_mu_b,
+                        double* d_var_b, double* d_cov, double* d_prob, double* d_score, double* h_best_val,
+                        int64_t* h_best_idx, void* stream);
+
 /* full predictive covariance of small sets (the G=70 line grid of EI):
  * d_cov[M,M] = (1-s)K(Xc,Xc) + s sigma_f^2 I - K*^T A K*  (src/gp_model.py:447-450) */
 PPBO_API int ppbo_predict_cov(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc, int M,

@@ -25,6 +25,8 @@ FUNCTIONAL_MEAN, FUNCTIONAL_VARIANCE, FUNCTIONAL_PROB = 0, 1, 2   # ... of ppbo_
 FUNCTIONAL_MAX_G = 64                              # points per group (PPBO_FUNCTIONAL_MAX_G)
 EFFECT_RAW, EFFECT_CENTRED, EFFECT_INTERACTION = 0, 1, 2           # effects of ppbo_predict_marginals (PPBO_EFFECT_*)
 MARGINAL_MAX_DC = 64                               # caller coordinates of ppbo_marginal_axes
+TOURNAMENT_BORDA, TOURNAMENT_WORST = 0, 1          # score kinds of ppbo_predict_tournament (PPBO_TOURNAMENT_*)
+TOURNAMENT_MAX_B = 1024                            # opponents per call (PPBO_TOURNAMENT_MAX_B)
 
 
 class FitOpts(C.Structure):
@@ -131,6 +133,8 @@ SIGNATURES = {
                                  C.POINTER(_i64), _vp],
     "ppbo_predict_marginals": [_vp, C.POINTER(Model), C.POINTER(MarginalAxes), _vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp,
                                C.POINTER(_d), C.POINTER(_i64), _vp],
+    "ppbo_predict_tournament": [_vp, C.POINTER(Model), _vp, _i64, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_d),
+                                C.POINTER(_i64), _vp],
     "ppbo_predict_cov": [_vp, C.POINTER(Model), _vp, _i, _d, _vp, _vp, _vp],
     "ppbo_transposed_G_shape": [_i, C.POINTER(_i), C.POINTER(_i)],
     "ppbo_transposed_G": [_vp, _vp, _i, _vp, _vp],

@@ -24,6 +24,9 @@
 //   all resident workgroups stream the same G row panel out of L2 while their K* chunk sits in the
 //   Infinity Cache.  PPBO_QF_VARIANT (default 4: 16 wavefronts of 32x32) selects the measured tile shapes, see DESIGN.md.
 // Pass 3 (score_kernel): slab sums -> var, score, per-block argmax; (argmax_final_kernel) -> 1 value.
+#include <functional>
+#include <optional>
+
 #include "gemm_f64.h"
 #include "linalg.h"
 #include "score.h"
@@ -1653,6 +1656,215 @@ __global__ __launch_bounds__(128) void edge_apply_kernel(const double* __restric
   E[(size_t)r * ld + c] = v;
 }
 
+// ---- tournaments (ppbo_predict_tournament): every a against every b ---------------------------------------------------
+// The covariance is bilinear: cov(f(a), f(b)) = k(a, b) + k_a' u_b with u_b = (Lambda + M'M) k_b, M = G (node form) or
+// H diag(w) D (edge form).  U [K rows][ldu] holds u_b for the Mb opponents in the row layout of a chunk's K* workspace:
+//   node form   U = Lambda K*_B + G'(G K*_B)                                     (lam_apply_kernel, two GEMMs)
+//   edge form   the K* pass stores e_a,j = lam_off[j] (k_a,j - k_a,obs) = w_j (k_a,obs - k_a,j) in row n_q + q m + t, so
+//               k_a' Lambda k_b = sum_j e_a,j (k_b,obs - k_b,j) and U = H'(H E_B) + Delta_B, Delta_B,j = k_b,obs - k_b,j
+//               (tournament_delta_kernel; the plain difference, not E_B / w: a zero edge weight is harmless)
+// so that all Ma x Mb cross terms are ONE product K*_A' U on the fp64 matrix cores.
+
+// Delta_B in the edge layout from the node-layout K*_B: rows [0, n_q) zero, row n_q + q m + t = K*[obs_q] - K*[q (m + 1) + 1 + t]
+__global__ __launch_bounds__(128) void tournament_delta_kernel(const double* __restrict__ Kt, int ld, int M, int mblk, int n_q,
+                                                               double* __restrict__ Dl) {
+  const int c = blockIdx.x * 128 + threadIdx.x, r = blockIdx.y;
+  if (c >= M) return;
+  double v = 0.0;
+  if (r >= n_q) {
+    const int m = mblk - 1, q = (r - n_q) / m, obs = q * mblk, j = obs + 1 + (r - n_q - q * m);
+    v = Kt[(size_t)obs * ld + c] - Kt[(size_t)j * ld + c];
+  }
+  Dl[(size_t)r * ld + c] = v;
+}
+
+// the smaller of two values, NaN if either is (fmin drops a NaN operand)
+__device__ __forceinline__ double nan_min(double a, double b) { return (a != a) ? a : ((b != b) ? b : fmin(a, b)); }
+
+// tile shapes: candidates (a) x opponents (b)
+using TQ_BIG = Cfg<4, 4, 2, 2>;     // 128 x 128, 16 wavefronts of 32 x 32 (the shape of the shipped quadform_kernel)
+using TQ_SMALL = Cfg<4, 1, 2, 2>;   // 128 x 32, 4 wavefronts of 32 x 32: fields of up to 64 opponents, and camphor-copper
+constexpr int TQ_DCH = 16;          // coordinates staged in LDS per step of the prior term
+
+// One BM x BN tile of the tournament: rows = the chunk's candidates, columns = the opponents.  Both operands are stored
+// [K][rows] (RC): the chunk's K* workspace and U, each offset to the first contracted row by the host, so the main loop
+// is the one quadform_kernel drives, with a full K range for every tile (U is dense).  The accumulators then hold
+// k_a' u_b in the MFMA C layout (column = lane & 15 = opponent, row = candidate): 16 consecutive opponents of one
+// candidate sit in 16 consecutive lanes, so the rows of the row-major [Ma][Mb] outputs are written in 128-byte runs.
+// Epilogue, in registers: the prior k(a, b) from direct differences (rows staged in LDS TQ_DCH coordinates at a time),
+//   cov = k(a, b) + k_a' u_b,  var_d = var_a + var_b - 2 cov,  p = Phi((mu_a - mu_b) / sqrt(2 sigma^2 + max(var_d, 0)))
+// and per candidate the sum and the minimum of p over the tile's opponents -> slab_sum / slab_min [b tile][Mc].  No
+// atomics: lanes meet by shuffles, wavefronts in LDS, in a fixed order.  A NaN mean on either side (a non-finite
+// coordinate) gives NaN cov and p; the minimum propagates NaN as the sum does.
+template <class C, int KID, bool ALWAYS_FAST>
+__global__ __launch_bounds__(C::NT, (C::NT == 1024) ? 4 : 2) void tournament_kernel(
+    const double* __restrict__ Kt, int ldk, const double* __restrict__ U, int ldu, int kext, int Mc, int Mb,
+    const double* __restrict__ Xa, const double* __restrict__ Xb, int D, KernParams p, double two_sigma2,
+    const double* __restrict__ mu_a, const double* __restrict__ var_a, const double* __restrict__ mu_b,
+    const double* __restrict__ var_b, double* __restrict__ cov_out, double* __restrict__ prob_out,
+    double* __restrict__ slab_sum, double* __restrict__ slab_min, int ntb) {
+  // opponent tile fastest: the workgroups that share a K* panel are neighbours
+  const int bt = blockIdx.x % ntb, at = blockIdx.x / ntb;
+  const int m0 = at * C::BM, n0 = bt * C::BN;
+  double4_t acc[C::TM][C::TN];
+  zero_acc<C>(acc);
+  // (every column of either workspace up to its row stride is backed by memory: the strides are the bounds)
+  mainloop<C, RC, RC, ALWAYS_FAST>(Kt, ldk, U, ldu, ldk, ldu, m0, n0, 0, kext, acc);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int wm = wave / C::WN, wn = wave % C::WN;
+  constexpr int XLD = TQ_DCH + 1;              // odd row stride: the 16 opponent rows of a read fall into distinct banks
+  double* xa_s = lds_dyn;                      // [BM][XLD]; mainloop ended with a barrier
+  double* xb_s = lds_dyn + C::BM * XLD;        // [BN][XLD]
+  double* red = xb_s + C::BN * XLD;            // [2][WN][BM]
+  static_assert((C::BM + C::BN) * XLD + 2 * C::WN * C::BM <= C::LDS_DOUBLES, "the epilogue's LDS fits the main loop's");
+  const int arow = wm * C::TM * 16 + (lane >> 4);   // + 16 i + 4 r
+  const int bcol = wn * C::TN * 16 + (lane & 15);   // + 16 j
+  double sq[C::TM][C::TN][4];
+#pragma unroll
+  for (int i = 0; i < C::TM; ++i)
+#pragma unroll
+    for (int j = 0; j < C::TN; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) sq[i][j][r] = 0.0;
+  for (int d0 = 0; d0 < D; d0 += TQ_DCH) {
+    const int dc = (D - d0) < TQ_DCH ? (D - d0) : TQ_DCH;
+    for (int e = threadIdx.x; e < (C::BM + C::BN) * TQ_DCH; e += C::NT) {
+      const int row = e / TQ_DCH, d = e % TQ_DCH;
+      double v = 0.0;
+      if (d < dc) {
+        if (row < C::BM) {
+          if (m0 + row < Mc) v = Xa[(size_t)(m0 + row) * D + d0 + d];
+        } else if (n0 + row - C::BM < Mb) {
+          v = Xb[(size_t)(n0 + row - C::BM) * D + d0 + d];
+        }
+      }
+      lds_dyn[row * XLD + d] = v;
+    }
+    __syncthreads();
+    for (int d = 0; d < dc; ++d) {
+      double bv[C::TN];
+#pragma unroll
+      for (int j = 0; j < C::TN; ++j) bv[j] = xb_s[(bcol + 16 * j) * XLD + d];
+#pragma unroll
+      for (int i = 0; i < C::TM; ++i)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const double av = xa_s[(arow + 16 * i + 4 * r) * XLD + d];
+#pragma unroll
+          for (int j = 0; j < C::TN; ++j) sq[i][j][r] += kern_term<KID>(av - bv[j], d0 + d, p);
+        }
+    }
+    __syncthreads();
+  }
+  double mb[C::TN], vb[C::TN];
+  bool bok[C::TN];
+#pragma unroll
+  for (int j = 0; j < C::TN; ++j) {
+    const int b = n0 + bcol + 16 * j;
+    bok[j] = b < Mb;
+    mb[j] = bok[j] ? mu_b[b] : 0.0;
+    vb[j] = bok[j] ? var_b[b] : 0.0;
+  }
+#pragma unroll
+  for (int i = 0; i < C::TM; ++i)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int al = arow + 16 * i + 4 * r, a = m0 + al;
+      const bool aok = a < Mc;
+      const double ma = aok ? mu_a[a] : 0.0, va = aok ? var_a[a] : 0.0;
+      double rs = 0.0, rm = INFINITY;
+#pragma unroll
+      for (int j = 0; j < C::TN; ++j) {
+        // Var[f(a) - f(b)] >= 0 bounds the covariance by the mean of the two variances: clipped there (a matter of the
+        // last bits, for a ~ b), var_a + var_b - 2 cov is never negative and exactly 0 for a == b
+        double cv = fmin(acc[i][j][r] + kern_finish<KID>(sq[i][j][r], p), 0.5 * (va + vb[j]));
+        const double vd = va + vb[j] - 2.0 * cv, mud = ma - mb[j];
+        const double den = sqrt(two_sigma2 + fmax(vd, 0.0));
+        // den = 0 (no noise, no variance): the sign of mu_d decides, a tie is 1/2 (pair_score_kernel's rule)
+        double pr = norm_cdf(den > 0.0 ? mud / den : (mud > 0.0 ? INFINITY : (mud < 0.0 ? -INFINITY : 0.0)));
+        if (mud != mud) { cv = mud; pr = mud; }
+        if (aok && bok[j]) {
+          const size_t o = (size_t)a * Mb + (n0 + bcol + 16 * j);
+          if (cov_out) cov_out[o] = cv;
+          if (prob_out) prob_out[o] = pr;
+          rs += pr;
+          rm = nan_min(rm, pr);
+        }
+      }
+#pragma unroll
+      for (int o = 1; o < 16; o <<= 1) {        // the 16 lanes of a row of the MFMA layout hold the row's 16 opponents
+        rs += __shfl_xor(rs, o, 64);
+        rm = nan_min(rm, __shfl_xor(rm, o, 64));
+      }
+      if ((lane & 15) == 0) {
+        red[wn * C::BM + al] = rs;
+        red[(C::WN + wn) * C::BM + al] = rm;
+      }
+    }
+  __syncthreads();
+  if (threadIdx.x < C::BM) {
+    const int a = m0 + threadIdx.x;
+    double ts = 0.0, tm = INFINITY;
+#pragma unroll
+    for (int w = 0; w < C::WN; ++w) {
+      ts += red[w * C::BM + threadIdx.x];
+      tm = nan_min(tm, red[(C::WN + w) * C::BM + threadIdx.x]);
+    }
+    if (a < Mc) {
+      slab_sum[(size_t)bt * Mc + a] = ts;
+      slab_min[(size_t)bt * Mc + a] = tm;
+    }
+  }
+}
+
+// the per-tile partials in tile order -> the score of every candidate of the chunk and the per-workgroup bests that the
+// one-workgroup argmax (argmax_final_kernel) merges; NaN never wins
+__global__ __launch_bounds__(256) void tournament_finish_kernel(const double* __restrict__ slab_sum,
+                                                                const double* __restrict__ slab_min, int ntb, int Mc, int Mb,
+                                                                int kind, long long idx_base, double* __restrict__ score_out,
+                                                                Best* __restrict__ blk_best) {
+  __shared__ Best sh[4];
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  Best b{0.0, -1};
+  if (c < Mc) {
+    double sc;
+    if (kind == PPBO_TOURNAMENT_BORDA) {
+      double t = 0.0;
+      for (int k = 0; k < ntb; ++k) t += slab_sum[(size_t)k * Mc + c];
+      sc = t / (double)Mb;
+    } else {
+      sc = INFINITY;
+      for (int k = 0; k < ntb; ++k) sc = nan_min(sc, slab_min[(size_t)k * Mc + c]);
+    }
+    if (score_out) score_out[c] = sc;
+    if (sc == sc) { b.val = sc; b.idx = idx_base + c; }
+  }
+  b = block_best(b, sh);
+  if (threadIdx.x == 0 && blk_best) blk_best[blockIdx.x] = b;
+}
+
+template <class C, int KID>
+int launch_tournament(ppbo_ctx* ctx, const double* Kt, int ldk, const double* U, int ldu, int kext, int Mc, int Mb,
+                      const double* Xa, const double* Xb, int D, const KernParams& p, double two_sigma2, const double* mu_a,
+                      const double* var_a, const double* mu_b, const double* var_b, double* cov_out, double* prob_out,
+                      double* slab_sum, double* slab_min, hipStream_t s) {
+  const size_t lds = C::LDS_DOUBLES * sizeof(double);
+  ppbo_lds_limit(ctx, (const void*)tournament_kernel<C, KID, true>, (int)lds);
+  ppbo_lds_limit(ctx, (const void*)tournament_kernel<C, KID, false>, (int)lds);
+  const int nta = (Mc + C::BM - 1) / C::BM, ntb = (Mb + C::BN - 1) / C::BN;
+  // every tile in bounds and 16-byte aligned, the K range a whole number of chunks?
+  const bool fast = (ldk >= nta * C::BM) && (ldu >= ntb * C::BN) && (kext % BK == 0) && (ldk % 2 == 0) && (ldu % 2 == 0) &&
+                    ((reinterpret_cast<uintptr_t>(Kt) & 15) == 0) && ((reinterpret_cast<uintptr_t>(U) & 15) == 0);
+  if (fast)
+    tournament_kernel<C, KID, true><<<nta * ntb, C::NT, lds, s>>>(Kt, ldk, U, ldu, kext, Mc, Mb, Xa, Xb, D, p, two_sigma2, mu_a,
+                                                                  var_a, mu_b, var_b, cov_out, prob_out, slab_sum, slab_min, ntb);
+  else
+    tournament_kernel<C, KID, false><<<nta * ntb, C::NT, lds, s>>>(Kt, ldk, U, ldu, kext, Mc, Mb, Xa, Xb, D, p, two_sigma2, mu_a,
+                                                                   var_a, mu_b, var_b, cov_out, prob_out, slab_sum, slab_min, ntb);
+  PPBO_LAUNCH_CHECK(ctx);
+  return 0;
+}
+
 // prior block of one line: cov_b[g][h] = (1-s) k(x_g, x_h), diagonal (1-s) sf2 + s sf2  (gp_model.py:447)
 template <int KID>
 __global__ __launch_bounds__(256) void line_prior_kernel(const double* __restrict__ grid, int G, int D,
@@ -2429,10 +2641,15 @@ extern "C" {
 // the scoring passes of ppbo_predict / ppbo_predict_record: per 65536-candidate chunk kstar -> quadform -> score ->
 // one-workgroup argmax.  Leaves the per-chunk bests in *chunk_best_out (device); with d_record and ONE chunk the
 // argmax launch writes the record (and raises the publication flag) itself.
+// after_chunk (ppbo_predict_tournament): called behind the launches of every chunk with the chunk's first row, its size and
+// its K* workspace -- Kt [Nk][ldk] in the layout of the model's form, valid until the next chunk's launches -- and ONCE,
+// with Kt == NULL and (0, M), on the one-launch path, which leaves no K* in memory.  The launches themselves do not change.
+using PredictChunkHook = std::function<int(int64_t c_beg, int64_t Mc, const double* Kt, int ldk, int Nk)>;
 static int predict_passes(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc, int64_t M, int score_kind,
                           double mustar, double* d_mu, double* d_var, double* d_score, bool want_best,
                           double* d_record, int64_t record_offset, Best** chunk_best_out, int* n_chunks_out,
-                          hipStream_t s, unsigned long long* publish = nullptr, unsigned long long epoch = 0) {
+                          hipStream_t s, unsigned long long* publish = nullptr, unsigned long long epoch = 0,
+                          const PredictChunkHook* after_chunk = nullptr) {
   if (int rc = check_model(ctx, model)) return rc;
   PPBO_REQUIRE(ctx, d_Xc != nullptr && M > 0, "candidates");
   PPBO_REQUIRE(ctx, score_kind >= 0 && score_kind <= 2, "score_kind");
@@ -2469,6 +2686,8 @@ static int predict_passes(ppbo_ctx* ctx, const ppbo_model* model, const double* 
     }
     *chunk_best_out = chunk_best;
     *n_chunks_out = 1;
+    if (after_chunk)
+      if (int rc = (*after_chunk)(0, M, nullptr, 0, 0)) return rc;
     return 0;
   }
   const int64_t chunk_cap = 65536;
@@ -2527,7 +2746,8 @@ static int predict_passes(ppbo_ctx* ctx, const ppbo_model* model, const double* 
       if (int rc = dispatch_quadform(ctx, Gq, Nk, g_rows, N, Kt, ldk, Mc, mblk, slab, edge_k0, s)) return rc;
     }
     const int sblocks = score_blocks(Mc);
-    PpboProfScope pfs(ctx, ppbo_ctx::PF_SCORE, s);
+    std::optional<PpboProfScope> pfs;          // (ends before after_chunk's launches)
+    pfs.emplace(ctx, ppbo_ctx::PF_SCORE, s);
     const bool one = (n_chunks == 1);
     score_kernel<<<sblocks, SC_THREADS, 0, s>>>(mu_part, n_split_eff, t_part, want_var ? slab : nullptr, ntm, Mc,
                                                 model->theta[2] * model->theta[2], score_kind, mustar,
@@ -2540,6 +2760,9 @@ static int predict_passes(ppbo_ctx* ctx, const ppbo_model* model, const double* 
                                             (long long)record_offset, one ? publish : nullptr, epoch);
       PPBO_LAUNCH_CHECK(ctx);
     }
+    pfs.reset();
+    if (after_chunk)
+      if (int rc = (*after_chunk)(c_beg, Mc, Kt, ldk, Nk)) return rc;
   }
   if (d_record && n_chunks > 1) {
     best_record_kernel<<<1, 64, 0, s>>>(chunk_best, (int)n_chunks, (long long)record_offset, d_record, publish, epoch);
@@ -2863,6 +3086,169 @@ int ppbo_predict_marginals(ppbo_ctx* ctx, const ppbo_model* model, const ppbo_ma
   ma.effect = effect;
   return two_set_passes(ctx, TS_MARG, model, d_t, d_t, nullptr, M, score_kind, d_mu, d_var, d_prob, d_score, h_best_val,
                         h_best_idx, (hipStream_t)stream, nullptr, &ma);
+}
+
+// Tournaments: every candidate a_i against every opponent b_j.  Field pass once per call (ppbo_predict's own launches on
+// d_Xb for mu_b / var_b, then K*_B in the node layout -> U, see tournament_kernel), then per chunk of 65536 candidates
+// ppbo_predict's own launches (predict_passes: mu_a, var_a and the chunk's K* workspace) -> tournament_kernel ->
+// tournament_finish_kernel -> one-workgroup argmax.  A model that the one-launch scoring kernel takes leaves no K* in
+// memory: there the chunks' K* are formed by a K* launch of their own, behind the scoring launch.
+int ppbo_predict_tournament(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xa, int64_t Ma, const double* d_Xb, int Mb,
+                            int score_kind, double* d_mu_a, double* d_var_a, double* d_mu_b, double* d_var_b, double* d_cov,
+                            double* d_prob, double* d_score, double* h_best_val, int64_t* h_best_idx, void* stream) {
+  PPBO_ENTER(ctx);
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = check_model(ctx, model)) return rc;
+  PPBO_REQUIRE(ctx, d_Xa != nullptr && d_Xb != nullptr, "tournament (d_Xa / d_Xb)");
+  PPBO_REQUIRE(ctx, Ma >= 1 && Ma <= (int64_t)0x7fffffff, "candidate count (1 .. 2^31 - 1)");
+  PPBO_REQUIRE(ctx, Mb >= 1 && Mb <= PPBO_TOURNAMENT_MAX_B, "opponent count (1 .. PPBO_TOURNAMENT_MAX_B; chunk the field)");
+  PPBO_REQUIRE(ctx, score_kind == PPBO_TOURNAMENT_BORDA || score_kind == PPBO_TOURNAMENT_WORST, "score_kind");
+  PPBO_REQUIRE(ctx, !model->kstar_fp32, "tournaments are fp64 only (kstar_fp32)");
+  PPBO_REQUIRE(ctx, model->d_G != nullptr, "tournaments need model->d_G");
+  PPBO_REQUIRE(ctx, model->d_lam_diag && model->d_lam_off, "model Lambda");
+  const bool want_best = h_best_val || h_best_idx;
+  const int N = model->N, D = model->D, mblk = model->m + 1, n_q = N / mblk;
+  const bool edge = model->form == PPBO_FORM_EDGE;
+  const int kshift = edge ? ppbo_edge_k0(n_q) : 0;
+  const KernParams p = make_kern_params(model->kernel_id, model->theta);
+  const double two_sigma2 = 2.0 * model->theta[0] * model->theta[0];
+  const int64_t chunk_cap = 65536;
+  const int64_t n_chunks = (Ma + chunk_cap - 1) / chunk_cap;
+  const int Mc_max = (int)(Ma < chunk_cap ? Ma : chunk_cap);
+  // camphor-copper always takes the small tile: its sin(pi |dx|) per element and coordinate needs more registers than
+  // the 128 a lane of the 16-wavefront shape has (the compiler spilled 116 bytes per lane there)
+  const bool small = Mb <= 2 * TQ_SMALL::BN || model->kernel_id == PPBO_KERNEL_CAMPHOR;
+  const int ntb = small ? (Mb + TQ_SMALL::BN - 1) / TQ_SMALL::BN : (Mb + TQ_BIG::BN - 1) / TQ_BIG::BN;
+  const int NkU = (N + BK - 1) & ~(BK - 1);            // rows of U: the K extent of a padded chunk workspace
+  const int ldu = (Mb + 127) & ~127;                   // whole opponent tiles
+  // the split of the field's own K* launch (its mean partials are not read)
+  const int n_split_b = pick_split(Mb, n_q);
+  const int q_per_split_b = (n_q + n_split_b - 1) / n_split_b;
+  const int n_split_b_eff = (n_q + q_per_split_b - 1) / q_per_split_b;
+  const int fblocks_max = (Mc_max + 255) / 256;
+  // every workspace of this entry before the first launch (growing one waits for the device)
+  double* U = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_TOURN_U, (size_t)NkU * ldu * sizeof(double));
+  if (!U) return (int)hipErrorOutOfMemory;
+  const size_t f_kb = 0, f_y = f_kb + (size_t)N * ldu, f_z = f_y + (size_t)N * ldu, f_mub = f_z + (size_t)N * ldu,
+               f_varb = f_mub + ldu, f_part = f_varb + ldu, f_slab = f_part + (size_t)n_split_b_eff * Mb,
+               f_mua = f_slab + (size_t)2 * ntb * Mc_max, f_bests = f_mua + (size_t)(d_mu_a ? 0 : Ma) + (size_t)(d_var_a ? 0 : Ma),
+               f_end = f_bests + (size_t)2 * (fblocks_max + n_chunks);   // (a Best is 16 bytes)
+  double* fw = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_TOURN_FIELD, f_end * sizeof(double));
+  if (!fw) return (int)hipErrorOutOfMemory;
+  double *KB = fw + f_kb, *Y = fw + f_y, *Z = fw + f_z, *mu_b = fw + f_mub, *var_b = fw + f_varb, *part_b = fw + f_part;
+  double *slab_sum = fw + f_slab, *slab_min = slab_sum + (size_t)ntb * Mc_max;
+  double* mu_a = d_mu_a ? d_mu_a : fw + f_mua;
+  double* var_a = d_var_a ? d_var_a : fw + f_mua + (d_mu_a ? 0 : Ma);
+  Best* bests = reinterpret_cast<Best*>(fw + f_bests);
+  Best* chunk_best = bests + fblocks_max;
+  PpboHostRecord hr{};
+  if (want_best)
+    if (int rc = ppbo_host_record(ctx, &hr)) return rc;
+  Best* cb_unused = nullptr;
+  int nc_unused = 0;
+
+  // ---- the field, once per call
+  // mu_b, var_b: exactly ppbo_predict's launches on d_Xb
+  if (int rc = predict_passes(ctx, model, d_Xb, Mb, PPBO_SCORE_MEAN, 0.0, mu_b, var_b, nullptr, false, nullptr, 0, &cb_unused,
+                              &nc_unused, s))
+    return rc;
+  if (d_mu_b) PPBO_HIP_CHECK(ctx, hipMemcpyAsync(d_mu_b, mu_b, (size_t)Mb * sizeof(double), hipMemcpyDeviceToDevice, s));
+  if (d_var_b) PPBO_HIP_CHECK(ctx, hipMemcpyAsync(d_var_b, var_b, (size_t)Mb * sizeof(double), hipMemcpyDeviceToDevice, s));
+  {
+    PpboProfScope pf(ctx, ppbo_ctx::PF_TOURNAMENT_FIELD, s);
+    PPBO_HIP_CHECK(ctx, hipMemsetAsync(U, 0, (size_t)NkU * ldu * sizeof(double), s));
+    dispatch_kstar(model, d_Xb, Mb, KB, ldu, part_b, nullptr, q_per_split_b, n_split_b_eff, false, s);
+    PPBO_LAUNCH_CHECK(ctx);
+    GemmArgs y{};
+    y.A = model->d_G; y.lda = N; y.B = KB; y.ldb = ldu; y.C = Y; y.ldc = ldu;
+    y.M = N; y.N = Mb; y.K = N; y.alpha = 1.0; y.beta = 0.0; y.khi_mode = 1; y.tri_block = mblk;
+    if (edge) {
+      edge_apply_kernel<<<dim3((Mb + 127) / 128, N), 128, 0, s>>>(KB, ldu, Mb, mblk, n_q, model->d_lam_off, Z);
+      PPBO_LAUNCH_CHECK(ctx);
+      tournament_delta_kernel<<<dim3((Mb + 127) / 128, N), 128, 0, s>>>(KB, ldu, Mb, mblk, n_q, U);
+      PPBO_LAUNCH_CHECK(ctx);
+      y.B = Z; y.tri_block = 1;    // H lower triangular
+    } else {
+      lam_apply_kernel<<<dim3((Mb + 127) / 128, n_q), 128, 0, s>>>(KB, ldu, N, Mb, mblk, model->d_lam_diag, model->d_lam_off, U);
+      PPBO_LAUNCH_CHECK(ctx);
+    }
+    if (int rc = ppbo_gemm_launch(ctx, y, 0, 0, s)) return rc;       // Y = G K*_B  (H E_B)
+    GemmArgs u{};
+    u.A = model->d_G; u.lda = N; u.B = Y; u.ldb = ldu; u.C = U; u.ldc = ldu;
+    u.M = N; u.N = Mb; u.K = N; u.alpha = 1.0; u.beta = 1.0; u.tri_block = 1;
+    if (int rc = ppbo_gemm_launch(ctx, u, 1, 0, s)) return rc;       // U += G' Y
+  }
+
+  // ---- the candidates: per chunk behind ppbo_predict's own launches
+  // one chunk with its K* workspace Kc [Nk][ldk] in the layout of the model's form
+  auto chunk = [&](int64_t c_beg, int Mc, const double* Kc, int ldk, int Nk, int ch) -> int {
+    const double* xa = d_Xa + (size_t)c_beg * D;
+    const int kext = Nk - kshift;
+    {
+      PpboProfScope pf(ctx, ppbo_ctx::PF_TOURNAMENT, s);
+      if (int rc = ppbo_kernel_dispatch(ctx, model->kernel_id, [&](auto kid) {
+            constexpr int KID = decltype(kid)::value;
+            const double* Ks = Kc + (size_t)kshift * ldk;
+            const double* Us = U + (size_t)kshift * ldu;
+            double* cov = d_cov ? d_cov + (size_t)c_beg * Mb : nullptr;
+            double* prob = d_prob ? d_prob + (size_t)c_beg * Mb : nullptr;
+            if (small)
+              return launch_tournament<TQ_SMALL, KID>(ctx, Ks, ldk, Us, ldu, kext, Mc, Mb, xa, d_Xb, D, p, two_sigma2, mu_a + c_beg,
+                                                      var_a + c_beg, mu_b, var_b, cov, prob, slab_sum, slab_min, s);
+            if constexpr (KID == PPBO_KERNEL_CAMPHOR) return -1;      // (not reached: `small` above)
+            else
+              return launch_tournament<TQ_BIG, KID>(ctx, Ks, ldk, Us, ldu, kext, Mc, Mb, xa, d_Xb, D, p, two_sigma2, mu_a + c_beg,
+                                                    var_a + c_beg, mu_b, var_b, cov, prob, slab_sum, slab_min, s);
+          }))
+        return rc;
+    }
+    const int fblocks = (Mc + 255) / 256;
+    tournament_finish_kernel<<<fblocks, 256, 0, s>>>(slab_sum, slab_min, ntb, Mc, Mb, score_kind, (long long)c_beg,
+                                                     d_score ? d_score + c_beg : nullptr, want_best ? bests : nullptr);
+    PPBO_LAUNCH_CHECK(ctx);
+    if (want_best) {
+      const bool one = (n_chunks == 1);
+      argmax_final_kernel<<<1, 256, 0, s>>>(bests, fblocks, chunk_best + ch, one ? hr.d_rec : nullptr, 0,
+                                            one ? hr.d_flag : nullptr, hr.epoch);
+      PPBO_LAUNCH_CHECK(ctx);
+    }
+    return 0;
+  };
+  const PredictChunkHook hook = [&](int64_t c_beg, int64_t Mh, const double* Kc, int ldk, int Nk) -> int {
+    if (Kc) return chunk(c_beg, (int)Mh, Kc, ldk, Nk, (int)(c_beg / chunk_cap));
+    // the one-launch path (node form): mu_a / var_a of all rows are enqueued; K* of each chunk by a launch of its own
+    const int ldk1 = (Mc_max + 127) & ~127;
+    const int n_split = pick_split(Mc_max, n_q);
+    const int q_per_split = (n_q + n_split - 1) / n_split;
+    const int n_split_eff = (n_q + q_per_split - 1) / q_per_split;
+    double* K1 = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_TOURN_K, ((size_t)NkU * ldk1 + (size_t)n_split_eff * Mc_max) * sizeof(double));
+    if (!K1) return (int)hipErrorOutOfMemory;
+    double* part1 = K1 + (size_t)NkU * ldk1;
+    if (NkU != N) PPBO_HIP_CHECK(ctx, hipMemsetAsync(K1 + (size_t)N * ldk1, 0, (size_t)(NkU - N) * ldk1 * sizeof(double), s));
+    for (int64_t ch = 0; ch < n_chunks; ++ch) {
+      const int64_t cb = ch * chunk_cap;
+      const int Mc = (int)((Ma - cb) < chunk_cap ? (Ma - cb) : chunk_cap);
+      {
+        PpboProfScope pf(ctx, ppbo_ctx::PF_KSTAR, s);
+        dispatch_kstar(model, d_Xa + (size_t)cb * D, Mc, K1, ldk1, part1, nullptr, q_per_split, n_split_eff, false, s);
+      }
+      PPBO_LAUNCH_CHECK(ctx);
+      if (int rc = chunk(cb, Mc, K1, ldk1, NkU, (int)ch)) return rc;
+    }
+    return 0;
+  };
+  if (int rc = predict_passes(ctx, model, d_Xa, Ma, PPBO_SCORE_MEAN, 0.0, mu_a, var_a, nullptr, false, nullptr, 0, &cb_unused,
+                              &nc_unused, s, nullptr, 0, &hook))
+    return rc;
+  if (!want_best) return 0;
+  if (n_chunks > 1) {
+    best_record_kernel<<<1, 64, 0, s>>>(chunk_best, (int)n_chunks, 0, hr.d_rec, hr.d_flag, hr.epoch);
+    PPBO_LAUNCH_CHECK(ctx);
+  }
+  if (int rc = ppbo_host_record_wait(ctx, hr, s)) return rc;
+  if (h_best_val) *h_best_val = hr.h_rec[0];      // (NaN, -1) when no candidate has a non-NaN score
+  if (h_best_idx) *h_best_idx = (int64_t)hr.h_rec[1];
+  return 0;
 }
 
 }  // extern "C"

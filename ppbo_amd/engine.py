@@ -15,6 +15,7 @@ from ._lib import SLOPE_MEAN, SLOPE_VARIANCE, SLOPE_PROB  # noqa: F401
 from ._lib import CURV_MEAN, CURV_VARIANCE, CURV_PROB  # noqa: F401
 from ._lib import FUNCTIONAL_MEAN, FUNCTIONAL_VARIANCE, FUNCTIONAL_PROB, FUNCTIONAL_MAX_G  # noqa: F401
 from ._lib import EFFECT_RAW, EFFECT_CENTRED, EFFECT_INTERACTION, MARGINAL_MAX_DC  # noqa: F401
+from ._lib import TOURNAMENT_BORDA, TOURNAMENT_WORST, TOURNAMENT_MAX_B  # noqa: F401
 
 # Posterior.form: which variance operator G holds (include/ppbo_hip.h, PPBO_FORM_*)
 FORM_NODE = 0   # G = R Lambda, block lower triangular [N, N]
@@ -974,6 +975,47 @@ class Engine:
                                              self._stream())
         self._check(rc, "ppbo_predict_marginals")
         return dict(mu=mu, var=var, prob=pr, score=sc, best_val=bv.value, best_idx=bi.value)
+
+    @staticmethod
+    def _tournament_shapes(post: Posterior, Xa, Xb):
+        """The refusals of predict_tournament that shapes alone decide (before anything reaches the device): (Ma, Mb)."""
+        sa, sb = tuple(np.shape(Xa)), tuple(np.shape(Xb))
+        D = 6 if post.camphor is not None else post.X.shape[1]
+        if len(sa) != 2 or len(sb) != 2:
+            raise ValueError(f"predict_tournament: the two sets have shapes {sa} and {sb}; [Ma, D] and [Mb, D] are required")
+        if sa[1] != D or sb[1] != D:
+            raise ValueError(f"predict_tournament: points of widths {sa[1]} and {sb[1]} for a model of {D} dimensions")
+        if sa[0] < 1 or sb[0] < 1:
+            raise ValueError("predict_tournament: an empty set")
+        if sb[0] > TOURNAMENT_MAX_B:
+            raise ValueError(f"predict_tournament: {sb[0]} opponents; at most {TOURNAMENT_MAX_B} per call (chunk the field)")
+        return sa[0], sb[0]
+
+    def predict_tournament(self, post: Posterior, Xa, Xb, score=TOURNAMENT_BORDA, want_cov=False, want_prob=False,
+                           want_best=True):
+        """Tournaments (ppbo_predict_tournament): every candidate Xa[i] against every opponent Xb[j], points in the
+        caller's coordinates.  Returns device tensors mu_a / var_a [Ma] and mu_b / var_b [Mb] (bit for bit predict's),
+        cov / prob [Ma, Mb] (None unless asked for: nothing of that size is formed otherwise; prob[i, j] = P(a_i > b_j)),
+        score [Ma] (TOURNAMENT_BORDA: the mean of row i of prob, TOURNAMENT_WORST: its minimum) and best_val / best_idx,
+        the largest score and its first row.  A non-finite opponent poisons every score.  ValueError, before anything
+        reaches the device, for shape errors and more than TOURNAMENT_MAX_B opponents."""
+        Ma, Mb = self._tournament_shapes(post, Xa, Xb)
+        if score not in (TOURNAMENT_BORDA, TOURNAMENT_WORST):
+            raise ValueError(f"predict_tournament: unknown score kind {score}")
+        Xa, Xb = self._points(post, Xa), self._points(post, Xb)
+        md = self._model(post, True)
+        mu_a, var_a, mu_b, var_b = self.empty(Ma), self.empty(Ma), self.empty(Mb), self.empty(Mb)
+        cov = self.empty(Ma, Mb) if want_cov else None
+        pr = self.empty(Ma, Mb) if want_prob else None
+        sc = self.empty(Ma)
+        bv, bi = C.c_double(0.0), C.c_int64(-1)
+        rc = self.lib.ppbo_predict_tournament(self.ctx, C.byref(md), _ptr(Xa), Ma, _ptr(Xb), Mb, int(score), _ptr(mu_a),
+                                              _ptr(var_a), _ptr(mu_b), _ptr(var_b), _ptr(cov), _ptr(pr), _ptr(sc),
+                                              C.byref(bv) if want_best else None, C.byref(bi) if want_best else None,
+                                              self._stream())
+        self._check(rc, "ppbo_predict_tournament")
+        return dict(mu_a=mu_a, var_a=var_a, mu_b=mu_b, var_b=var_b, cov=cov, prob=pr, score=sc, best_val=bv.value,
+                    best_idx=bi.value)
 
     def predict_cov(self, post: Posterior, Xc, shrink=SHRINKAGE):
         Xc = self._points(post, Xc)

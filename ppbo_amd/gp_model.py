@@ -1121,6 +1121,45 @@ class GPModel:
         prob = out["prob"].cpu().numpy()
         return prob[0] if X.ndim == 2 else prob
 
+    @staticmethod
+    def _numpy(out):
+        return {k: (v.cpu().numpy() if isinstance(v, torch.Tensor) else v) for k, v in out.items()}
+
+    def tournament_pred(self, XA, XB):
+        """Every candidate XA[i] against every opponent XB[j] (ppbo_predict_tournament; no reference counterpart), as a
+        dict of NumPy arrays: mu_a, var_a [Ma], mu_b, var_b [Mb], cov [Ma, Mb] = cov(f(a_i), f(b_j)), prob [Ma, Mb] =
+        P(a_i > b_j), score [Ma] = the Borda score (mean of row i of prob), best_val / best_idx its maximum and first
+        row.  At most 1024 opponents per call; for near-ties (a ~ b) preference_pred keeps more digits of var_d."""
+        post = self._var_post()
+        return self._numpy(self.eng.predict_tournament(post, np.atleast_2d(np.asarray(XA, dtype=float)),
+                                                       np.atleast_2d(np.asarray(XB, dtype=float)), want_cov=True,
+                                                       want_prob=True))
+
+    def default_field(self, n_field=256, seed=None):
+        """The default field of borda_pred: n_field uniform points of the unit box from np.random.default_rng(seed)."""
+        return np.random.default_rng(seed).random((int(n_field), self.D))
+
+    def borda_pred(self, X, field=None, n_field=256, seed=None):
+        """(score [M], winner): the Borda (soft-Copeland) score of each row of X -- its probability of beating an
+        opponent drawn at random from `field` [Mb, D] (default: default_field(n_field, seed)) -- and the index of the
+        row with the largest score.  No M x Mb matrix is formed."""
+        post = self._var_post()
+        field = self.default_field(n_field, seed) if field is None else np.atleast_2d(np.asarray(field, dtype=float))
+        out = self.eng.predict_tournament(post, np.atleast_2d(np.asarray(X, dtype=float)), field)
+        return out["score"].cpu().numpy(), int(out["best_idx"])
+
+    def ranking_pred(self, X_items):
+        """(P [K, K], borda [K], order [K]) for K <= 1024 shortlisted configurations: the win matrix P[i, j] =
+        P(item i > item j) (diagonal 1/2 to ~1e-8), each item's Borda score against the shortlist and the items ordered
+        from the highest score down (stable: of equal scores the lower index first).  The companion of choice_pred."""
+        post = self._var_post()
+        X = np.asarray(X_items, dtype=float)
+        if X.ndim != 2 or X.shape[1] != self.D or not 1 <= X.shape[0] <= 1024:
+            raise ValueError(f"ranking_pred: items of shape {X.shape}; [K, {self.D}] with 1 <= K <= 1024 is required")
+        out = self.eng.predict_tournament(post, X, X, want_prob=True, want_best=False)
+        borda = out["score"].cpu().numpy()
+        return out["prob"].cpu().numpy(), borda, np.argsort(-borda, kind="stable")
+
     def mu_pred(self, X_pred):
         x = np.asarray(X_pred, dtype=float).reshape(1, self.D)
         out = self.eng.predict(self._mean_post(), x, score=SCORE_MEAN, want_var=False, want_best=False)
