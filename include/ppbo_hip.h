@@ -923,6 +923,53 @@ PPBO_API int ppbo_posterior_form(ppbo_ctx* ctx, int kernel_id, int N, int D, int
 PPBO_API int ppbo_argmax_combine(ppbo_ctx* ctx, const double* d_records, int world, double* h_best_val, int64_t* h_best_idx,
                         void* stream);
 
+/* ---- the projected edge form: the variance contraction in a bounded low-rank basis (no reference counterpart) -------------
+ * |H e|^2 costs E^2 flops per candidate.  For every candidate x the extended Gram matrix [K k*; k*^T k(x,x)] is positive
+ * semidefinite, so k* k*^T <= k(x,x) K <= kappa Sigma with kappa = sigma_f^2 / (1 - s) (s = PPBO_VAR_PROJECTION_SHRINK, the
+ * covariance shrinkage; k(x,x) = sigma_f^2 for every kernel of this library).  With e = B k* (B the E x N edge map, rows
+ * lam_off_j (e_j - e_obs)), Sigma = L L^T and W = H B L, any Q with orthonormal columns (E x r) gives, for all candidates,
+ *   0 <= |H e|^2 - |Q^T H e|^2 = |(I - Q Q^T) H B k*|^2 <= kappa |(I - Q Q^T) W|_F^2.
+ * T = Q^T H is a dense r x E operator: 2 r E flops per candidate, and an error bounded once per model by a computed number.
+ * ppbo_var_projection_build forms Q on the device by a randomised range finder -- Y = W (W^T Omega), Omega the ppbo_randn
+ * stream of seed PPBO_VAR_PROJECTION_SEED as an [N][r_max] matrix, r_max the largest multiple of 128 with 2 r_max <= 0.8 E;
+ * orthonormalised in panels of 128 columns by block Gram-Schmidt with shifted, then plain Cholesky-QR -- takes the smallest
+ * multiple of 128 whose estimate |W|_F^2 - sum_{i<=r} |z_i|^2 (Z = Q^T W) meets tol, and certifies it without cancellation:
+ *   bound = kappa (|W - Q_r Z_r|_F^2 + 2 |Q_r^T Q_r - I|_F |W|_F^2)      (units of variance; tol is relative to sigma_f^2).
+ * If the certified bound misses tol sigma_f^2 the next multiple of 128 is tried once.  The result is bitwise reproducible:
+ * every rank of a sharded search builds the same T.
+ * d_T: the caller's buffer of rows_max_padded x ld doubles (ppbo_var_projection_shape; ld = N rounded up to 16); on return
+ * rows [rows, rows_max_padded) and columns [0, n_q) and [N, ld) hold explicit zeros, and *proj names it.
+ * proj->rows == 0 (d_T is then not to be used; not an error): the model is not an edge-form one with d_G, it is one the
+ * one-launch scoring kernel takes, r_max < 128, a factorization failed, or tol was not reached.
+ * The _p entries are ppbo_predict, ppbo_predict_record and ppbo_search_sharded with a trailing projection: NULL or
+ * rows == 0 run exactly the launches of those entries (which call the same code with NULL); otherwise the contraction
+ * launch reads T (rows_padded / 128 row tiles, each over the full K range) in place of H.  The mean, the k*^T Lambda k*
+ * term, the score rule and the argmax are the same.  A projection whose ld, row counts or form do not fit the model is
+ * refused ("invalid argument").  Every other consumer of d_G (pairs, slopes, covariances, line acquisitions, tournaments)
+ * needs H itself and takes no projection. */
+#define PPBO_VAR_PROJECTION_SEED 0x70726f6a65637431ull
+#define PPBO_VAR_PROJECTION_SHRINK 1e-6
+typedef struct ppbo_var_projection {
+  const double* d_T;   /* [rows_padded][ld] */
+  int rows;            /* r: rows of T in use; 0 = no projection */
+  int rows_padded;     /* r rounded up to the 128-row tile */
+  int ld;              /* row stride of d_T */
+  double bound;        /* certified bound on var - var_projected >= 0, units of variance */
+  double tol;          /* the tolerance it was built for, relative to sigma_f^2 */
+} ppbo_var_projection;
+PPBO_API int ppbo_var_projection_shape(const ppbo_model* model, int* rows_max_padded, int* ld);
+PPBO_API int ppbo_var_projection_build(ppbo_ctx* ctx, const ppbo_model* model, double tol, double* d_T,
+                                       ppbo_var_projection* proj, void* stream);
+PPBO_API int ppbo_predict_p(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc, int64_t M,
+                   int score_kind, double mustar, double* d_mu, double* d_var, double* d_score,
+                   double* h_best_val, int64_t* h_best_idx, void* stream, const ppbo_var_projection* proj);
+PPBO_API int ppbo_predict_record_p(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc, int64_t M, int score_kind,
+                          double mustar, int64_t index_offset, double* d_record, void* stream,
+                          const ppbo_var_projection* proj);
+PPBO_API int ppbo_search_sharded_p(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc, int64_t M, int score_kind,
+                          double mustar, int64_t index_offset, double* h_best_val, int64_t* h_best_idx, void* stream,
+                          const ppbo_var_projection* proj);
+
 /* y = op(A) x for a square fp64 matrix; lower != 0 reads only the lower triangle (A is then
  * treated as lower-triangular).  Used for alpha = Sigma^-1 f_MAP (src/gp_model.py:445) and
  * prior draws L z (src/gp_model.py:374). */

@@ -57,6 +57,12 @@ class Model(C.Structure):
 
 
 
+class VarProjection(C.Structure):
+    """ppbo_var_projection: a projected variance operator T = Q^T H and its certified error bound."""
+    _fields_ = [("d_T", C.c_void_p), ("rows", C.c_int), ("rows_padded", C.c_int), ("ld", C.c_int), ("bound", C.c_double),
+                ("tol", C.c_double)]
+
+
 class MarginalAxes(C.Structure):
     _fields_ = [("Dc", C.c_int), ("d_Xu", C.c_void_p), ("h_l", C.POINTER(C.c_double)), ("h_periodic", C.POINTER(C.c_int)),
                 ("h_I0", C.POINTER(C.c_double))]
@@ -176,6 +182,13 @@ SIGNATURES = {
     "ppbo_argmax_allgather_record": [_vp, _vp, C.POINTER(_d), C.POINTER(_i64), _vp],
     "ppbo_search_sharded": [_vp, C.POINTER(Model), _vp, _i64, _i, _d, _i64, C.POINTER(_d), C.POINTER(_i64), _vp],
     "ppbo_posterior_form": [_vp, _i, _i, _i, _i],
+    "ppbo_var_projection_shape": [C.POINTER(Model), C.POINTER(_i), C.POINTER(_i)],
+    "ppbo_var_projection_build": [_vp, C.POINTER(Model), _d, _vp, C.POINTER(VarProjection), _vp],
+    "ppbo_predict_p": [_vp, C.POINTER(Model), _vp, _i64, _i, _d, _vp, _vp, _vp, C.POINTER(_d), C.POINTER(_i64), _vp,
+                       C.POINTER(VarProjection)],
+    "ppbo_predict_record_p": [_vp, C.POINTER(Model), _vp, _i64, _i, _d, _i64, _vp, _vp, C.POINTER(VarProjection)],
+    "ppbo_search_sharded_p": [_vp, C.POINTER(Model), _vp, _i64, _i, _d, _i64, C.POINTER(_d), C.POINTER(_i64), _vp,
+                              C.POINTER(VarProjection)],
     "ppbo_argmax_combine": [_vp, _vp, _i, C.POINTER(_d), C.POINTER(_i64), _vp],
     "ppbo_dgemm": [_vp, _i, _i, _i, _i, _i, _d, _vp, _i, _vp, _i, _d, _vp, _i, _vp],
 }

@@ -26,7 +26,7 @@ struct ppbo_ctx {
   int device = 0;
   std::string err;
   // named workspace slots
-  enum { WS_KSTAR = 0, WS_PART, WS_SCRATCH, WS_LINALG, WS_LINALG2, WS_VEC, WS_SMALL, WS_POTRF, WS_APPEND, WS_DIST, WS_LBFGS, WS_SEARCH, WS_SEARCH_SMALL, WS_LBFGS_U, WS_TRANSPOSE, WS_GPAD, WS_SEARCH_ROWS, WS_SCALE, WS_SCALE_PTS, WS_SCALE_SEARCH, WS_EVGRAD, WS_EVGRAD_VEC, WS_CAMPHOR, WS_CAMPHOR_ROWS, WS_KSTAR_GEO, WS_MARGINAL, WS_TOURN_U, WS_TOURN_FIELD, WS_TOURN_K, WS_COUNT };
+  enum { WS_KSTAR = 0, WS_PART, WS_SCRATCH, WS_LINALG, WS_LINALG2, WS_VEC, WS_SMALL, WS_POTRF, WS_APPEND, WS_DIST, WS_LBFGS, WS_SEARCH, WS_SEARCH_SMALL, WS_LBFGS_U, WS_TRANSPOSE, WS_GPAD, WS_SEARCH_ROWS, WS_SCALE, WS_SCALE_PTS, WS_SCALE_SEARCH, WS_EVGRAD, WS_EVGRAD_VEC, WS_CAMPHOR, WS_CAMPHOR_ROWS, WS_KSTAR_GEO, WS_MARGINAL, WS_TOURN_U, WS_TOURN_FIELD, WS_TOURN_K, WS_PROJECT, WS_PROJECT_SMALL, WS_COUNT };
   void* ws[WS_COUNT] = {};
   size_t ws_bytes[WS_COUNT] = {};
   void* pinned = nullptr;  // small pinned host staging buffer
@@ -116,7 +116,10 @@ int ppbo_fused_score(ppbo_ctx* ctx, const ppbo_model* m, const double* Gt, int l
 // predict.hip, for dist.hip: one shard's scoring passes with the record published to host-mapped memory
 int ppbo_predict_record_publish(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc, int64_t M, int score_kind,
                                 double mustar, int64_t index_offset, double* d_record, unsigned long long* d_flag,
-                                unsigned long long epoch, hipStream_t s);
+                                unsigned long long epoch, hipStream_t s, const ppbo_var_projection* proj = nullptr);
+// predict.hip, for project.hip: E [N][ld] = the edge-layout rows of the node-layout Kt [N][ld] (edge_apply_kernel), M columns
+int ppbo_edge_apply_async(ppbo_ctx* ctx, const double* Kt, int ld, int M, int N, int mblk, const double* d_lam_off, double* E,
+                          hipStream_t s);
 
 // first row / column of an edge-form operator that the contractions read: the n_q observation coordinates hold zeros,
 // the K loops start at n_q rounded down to the chunk depth

@@ -1455,7 +1455,10 @@ __global__ __launch_bounds__(KS_THREADS) void kstar_marginal_kernel(
 // by kshift = n_q rounded down to the chunk depth (G + kshift, Kt + kshift ldk): the K loop starts at 0 of the shifted
 // operands, so the main loop is the node form's own code (a non-zero start in the loop cost 16 more bytes of spilled
 // state per lane and ~5 % of the matrix-core rate)
-template <class C, int MINW, bool ALWAYS_FAST, bool EDGE>
+// DENSE (FORM == QF_DENSE): the operand is a projected operator T = Q^T H (project.hip) -- ntm row tiles of a dense
+// matrix in the edge column layout, shifted like the edge form's; every tile and every wavefront runs the full K range
+constexpr int QF_NODE = 0, QF_EDGE = 1, QF_DENSE = 2;
+template <class C, int MINW, bool ALWAYS_FAST, int FORM>
 __global__ __launch_bounds__(C::NT, MINW) void quadform_kernel(const double* __restrict__ G, int N,
                                                                const double* __restrict__ Kt, int ldk, int M,
                                                                int tri_block, double* __restrict__ slab, int ntm,
@@ -1489,7 +1492,8 @@ __global__ __launch_bounds__(C::NT, MINW) void quadform_kernel(const double* __r
   // depth (g_build_kernel writes the zeros of every row explicitly, so the extra columns multiply zeros): every K
   // range is then a whole number of chunks whatever the star size -- m = 25, the reference's default, has 26-row stars
   // Edge form: the K range of a tile ends with the tile's rows, that of a wavefront with its 32 rows (both shifted)
-  const int e = EDGE ? m0 + C::BM : (((m0 + C::BM + tri_block - 1) / tri_block) * tri_block + BK - 1) & ~(BK - 1);
+  constexpr bool EDGE = (FORM == QF_EDGE);
+  const int e = FORM == QF_DENSE ? N : EDGE ? m0 + C::BM : (((m0 + C::BM + tri_block - 1) / tri_block) * tri_block + BK - 1) & ~(BK - 1);
   const int kend = (e < N ? e : N) - kshift;
   double4_t acc[C::TM][C::TN];
   zero_acc<C>(acc);
@@ -1497,7 +1501,7 @@ __global__ __launch_bounds__(C::NT, MINW) void quadform_kernel(const double* __r
   const int wrow_beg = m0 + ((int)(threadIdx.x >> 6) / C::WN) * C::TM * 16;
   const int wrow_end = wrow_beg + C::TM * 16;
   // (a wavefront whose rows all lie in the zero frame below the real matrix multiplies nothing)
-  const int wk = wrow_beg >= n_rows ? 0 : (EDGE ? wrow_end : ((wrow_end + tri_block - 1) / tri_block) * tri_block) - kshift;
+  const int wk = FORM == QF_DENSE ? kend : wrow_beg >= n_rows ? 0 : (EDGE ? wrow_end : ((wrow_end + tri_block - 1) / tri_block) * tri_block) - kshift;
   mainloop<C, KC, RC, ALWAYS_FAST>(G, N, Kt, ldk, N, M, m0, n0, 0, kend, acc, wk < kend ? wk : kend);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int wm = wave / C::WN, wn = wave % C::WN;
@@ -1538,16 +1542,19 @@ using QF5 = Cfg<8, 2, 2, 4>;   // 256 x 128 tile, 16 waves of 32x64, 1 WG/CU: K*
 // predict_passes pads its operands so that this always holds.
 template <class C, int MINW>
 int launch_quadform(ppbo_ctx* ctx, const double* G, int N, int g_rows, int n_rows, const double* Kt, int ldk, int Mc,
-                    int mblk, double* slab, int edge_k0, hipStream_t s) {
+                    int mblk, double* slab, int edge_k0, bool dense, hipStream_t s) {
   const size_t lds = C::LDS_DOUBLES * sizeof(double);
   const bool edge = edge_k0 >= 0;
   const int kshift = edge ? edge_k0 : 0;
-  if (edge) {
-    ppbo_lds_limit(ctx, (const void*)quadform_kernel<C, MINW, true, true>, (int)lds);
-    ppbo_lds_limit(ctx, (const void*)quadform_kernel<C, MINW, false, true>, (int)lds);
+  if (dense) {
+    ppbo_lds_limit(ctx, (const void*)quadform_kernel<C, MINW, true, QF_DENSE>, (int)lds);
+    ppbo_lds_limit(ctx, (const void*)quadform_kernel<C, MINW, false, QF_DENSE>, (int)lds);
+  } else if (edge) {
+    ppbo_lds_limit(ctx, (const void*)quadform_kernel<C, MINW, true, QF_EDGE>, (int)lds);
+    ppbo_lds_limit(ctx, (const void*)quadform_kernel<C, MINW, false, QF_EDGE>, (int)lds);
   } else {
-    ppbo_lds_limit(ctx, (const void*)quadform_kernel<C, MINW, true, false>, (int)lds);
-    ppbo_lds_limit(ctx, (const void*)quadform_kernel<C, MINW, false, false>, (int)lds);
+    ppbo_lds_limit(ctx, (const void*)quadform_kernel<C, MINW, true, QF_NODE>, (int)lds);
+    ppbo_lds_limit(ctx, (const void*)quadform_kernel<C, MINW, false, QF_NODE>, (int)lds);
   }
   const int ntm = (g_rows + C::BM - 1) / C::BM, ntn = (Mc + C::BN - 1) / C::BN;
   const int grid = ntm * ntn;
@@ -1561,10 +1568,12 @@ int launch_quadform(ppbo_ctx* ctx, const double* G, int N, int g_rows, int n_row
                     ((reinterpret_cast<uintptr_t>(G) & 15) == 0) && ((reinterpret_cast<uintptr_t>(Kt) & 15) == 0);
   const double* Gs = G + kshift;
   const double* Ks = Kt + (size_t)kshift * ldk;
-  if (edge && fast) quadform_kernel<C, MINW, true, true><<<grid, C::NT, lds, s>>>(Gs, N, Ks, ldk, Mc, mblk, slab, ntm, ntn, swz, n_rows, kshift);
-  else if (edge) quadform_kernel<C, MINW, false, true><<<grid, C::NT, lds, s>>>(Gs, N, Ks, ldk, Mc, mblk, slab, ntm, ntn, swz, n_rows, kshift);
-  else if (fast) quadform_kernel<C, MINW, true, false><<<grid, C::NT, lds, s>>>(G, N, Kt, ldk, Mc, mblk, slab, ntm, ntn, swz, n_rows, 0);
-  else quadform_kernel<C, MINW, false, false><<<grid, C::NT, lds, s>>>(G, N, Kt, ldk, Mc, mblk, slab, ntm, ntn, swz, n_rows, 0);
+  if (dense && fast) quadform_kernel<C, MINW, true, QF_DENSE><<<grid, C::NT, lds, s>>>(Gs, N, Ks, ldk, Mc, mblk, slab, ntm, ntn, swz, n_rows, kshift);
+  else if (dense) quadform_kernel<C, MINW, false, QF_DENSE><<<grid, C::NT, lds, s>>>(Gs, N, Ks, ldk, Mc, mblk, slab, ntm, ntn, swz, n_rows, kshift);
+  else if (edge && fast) quadform_kernel<C, MINW, true, QF_EDGE><<<grid, C::NT, lds, s>>>(Gs, N, Ks, ldk, Mc, mblk, slab, ntm, ntn, swz, n_rows, kshift);
+  else if (edge) quadform_kernel<C, MINW, false, QF_EDGE><<<grid, C::NT, lds, s>>>(Gs, N, Ks, ldk, Mc, mblk, slab, ntm, ntn, swz, n_rows, kshift);
+  else if (fast) quadform_kernel<C, MINW, true, QF_NODE><<<grid, C::NT, lds, s>>>(G, N, Kt, ldk, Mc, mblk, slab, ntm, ntn, swz, n_rows, 0);
+  else quadform_kernel<C, MINW, false, QF_NODE><<<grid, C::NT, lds, s>>>(G, N, Kt, ldk, Mc, mblk, slab, ntm, ntn, swz, n_rows, 0);
   PPBO_LAUNCH_CHECK(ctx);
   return 0;
 }
@@ -1576,15 +1585,18 @@ int launch_quadform(ppbo_ctx* ctx, const double* G, int N, int g_rows, int n_row
 // the loop to pay for, twice the wavefronts hide more of the LDS and barrier latency
 int quadform_variant(const ppbo_ctx* ctx) { return ctx->qf_variant; }
 
+// dense: G is a projected operator T (g_rows = n_rows = its padded row count, a multiple of 128) of an edge-form model
+// (edge_k0 >= 0); the 256-row tile of variant 5 does not divide every such count, so variant 5 runs it as variant 4
 int dispatch_quadform(ppbo_ctx* ctx, const double* G, int N, int g_rows, int n_rows, const double* Kt, int ldk, int Mc,
-                      int mblk, double* slab, int edge_k0, hipStream_t s) {
+                      int mblk, double* slab, int edge_k0, hipStream_t s, bool dense = false) {
   switch (quadform_variant(ctx)) {
-    case 1: return launch_quadform<QF1, 4>(ctx, G, N, g_rows, n_rows, Kt, ldk, Mc, mblk, slab, edge_k0, s);
-    case 2: return launch_quadform<QF2, 4>(ctx, G, N, g_rows, n_rows, Kt, ldk, Mc, mblk, slab, edge_k0, s);
-    case 3: return launch_quadform<QF3, 4>(ctx, G, N, g_rows, n_rows, Kt, ldk, Mc, mblk, slab, edge_k0, s);
-    case 4: return launch_quadform<QF4, 8>(ctx, G, N, g_rows, n_rows, Kt, ldk, Mc, mblk, slab, edge_k0, s);
-    case 5: return launch_quadform<QF5, 4>(ctx, G, N, g_rows, n_rows, Kt, ldk, Mc, mblk, slab, edge_k0, s);
-    default: return launch_quadform<QF0, 2>(ctx, G, N, g_rows, n_rows, Kt, ldk, Mc, mblk, slab, edge_k0, s);
+    case 1: return launch_quadform<QF1, 4>(ctx, G, N, g_rows, n_rows, Kt, ldk, Mc, mblk, slab, edge_k0, dense, s);
+    case 2: return launch_quadform<QF2, 4>(ctx, G, N, g_rows, n_rows, Kt, ldk, Mc, mblk, slab, edge_k0, dense, s);
+    case 3: return launch_quadform<QF3, 4>(ctx, G, N, g_rows, n_rows, Kt, ldk, Mc, mblk, slab, edge_k0, dense, s);
+    case 5: if (!dense) return launch_quadform<QF5, 4>(ctx, G, N, g_rows, n_rows, Kt, ldk, Mc, mblk, slab, edge_k0, false, s);
+            [[fallthrough]];
+    case 4: return launch_quadform<QF4, 8>(ctx, G, N, g_rows, n_rows, Kt, ldk, Mc, mblk, slab, edge_k0, dense, s);
+    default: return launch_quadform<QF0, 2>(ctx, G, N, g_rows, n_rows, Kt, ldk, Mc, mblk, slab, edge_k0, dense, s);
   }
 }
 
@@ -2649,9 +2661,20 @@ static int predict_passes(ppbo_ctx* ctx, const ppbo_model* model, const double* 
                           double mustar, double* d_mu, double* d_var, double* d_score, bool want_best,
                           double* d_record, int64_t record_offset, Best** chunk_best_out, int* n_chunks_out,
                           hipStream_t s, unsigned long long* publish = nullptr, unsigned long long epoch = 0,
-                          const PredictChunkHook* after_chunk = nullptr) {
+                          const PredictChunkHook* after_chunk = nullptr, const ppbo_var_projection* proj = nullptr) {
   if (int rc = check_model(ctx, model)) return rc;
   PPBO_REQUIRE(ctx, d_Xc != nullptr && M > 0, "candidates");
+  // a projected operator (ppbo_var_projection_build): rows == 0 or NULL = none, today's launches.  One with rows must
+  // have been built for a model of this shape and form.
+  if (proj && proj->rows <= 0) proj = nullptr;
+  if (proj) {
+    int rows_max = 0, ld = 0;
+    PPBO_REQUIRE(ctx, ppbo_var_projection_shape(model, &rows_max, &ld) == 0 && model->form == PPBO_FORM_EDGE &&
+                          !ppbo_fused_eligible(ctx, model) && proj->d_T && proj->ld == ld && proj->rows_padded % 128 == 0 &&
+                          proj->rows <= proj->rows_padded && proj->rows_padded <= rows_max,
+                 "the variance projection was not built for a model of this N, m and form");
+    if (!model->d_G) proj = nullptr;     // a mean-only call reads no operator
+  }
   PPBO_REQUIRE(ctx, score_kind >= 0 && score_kind <= 2, "score_kind");
   const bool want_var = (model->d_G != nullptr);
   PPBO_REQUIRE(ctx, want_var || (d_var == nullptr && score_kind == PPBO_SCORE_MEAN),
@@ -2693,7 +2716,8 @@ static int predict_passes(ppbo_ctx* ctx, const ppbo_model* model, const double* 
   const int64_t chunk_cap = 65536;
   const int64_t n_chunks = (M + chunk_cap - 1) / chunk_cap;
   const int qf_bm = (quadform_variant(ctx) == 5) ? 256 : 128;
-  const int ntm = (N + qf_bm - 1) / qf_bm;   // slabs = row tiles of the shipped quadform shape
+  // slabs = row tiles of the shipped quadform shape; of the projected operator when there is one
+  const int ntm = proj ? proj->rows_padded / 128 : (N + qf_bm - 1) / qf_bm;
   // The quadratic form's operands are PADDED so that every tile of its launch takes the unguarded main loop whatever
   // N, the star size and the candidate count are (the reference's default m = 25 gives N = 26 n_q: the guarded loop
   // cost 23 % at N = 2080, profiles/r05_ragged_shapes.txt): K extent Nk = N rounded up to the chunk depth (K* rows
@@ -2701,7 +2725,11 @@ static int predict_passes(ppbo_ctx* ctx, const ppbo_model* model, const double* 
   // stride up to a whole candidate tile (the surplus columns feed only their own, unread, outputs).
   int Nk = N, g_rows = N;
   const double* Gq = nullptr;
-  if (want_var) {
+  if (proj) {                      // T carries the padded shape itself: ld = N rounded up to the chunk depth
+    Gq = proj->d_T;
+    Nk = proj->ld;
+    g_rows = proj->rows_padded;
+  } else if (want_var) {
     Gq = padded_G(ctx, model, qf_bm, M >= 2048, &Nk, &g_rows, s);
     if (!Gq) return (int)hipErrorOutOfMemory;
     PPBO_LAUNCH_CHECK(ctx);
@@ -2743,7 +2771,8 @@ static int predict_passes(ppbo_ctx* ctx, const ppbo_model* model, const double* 
     PPBO_LAUNCH_CHECK(ctx);
     if (want_var) {
       PpboProfScope pf(ctx, ppbo_ctx::PF_QUADFORM, s);
-      if (int rc = dispatch_quadform(ctx, Gq, Nk, g_rows, N, Kt, ldk, Mc, mblk, slab, edge_k0, s)) return rc;
+      if (int rc = dispatch_quadform(ctx, Gq, Nk, g_rows, proj ? g_rows : N, Kt, ldk, Mc, mblk, slab, edge_k0, s, proj != nullptr))
+        return rc;
     }
     const int sblocks = score_blocks(Mc);
     std::optional<PpboProfScope> pfs;          // (ends before after_chunk's launches)
@@ -2776,6 +2805,12 @@ static int predict_passes(ppbo_ctx* ctx, const ppbo_model* model, const double* 
 int ppbo_predict(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc, int64_t M, int score_kind,
                  double mustar, double* d_mu, double* d_var, double* d_score, double* h_best_val,
                  int64_t* h_best_idx, void* stream) {
+  return ppbo_predict_p(ctx, model, d_Xc, M, score_kind, mustar, d_mu, d_var, d_score, h_best_val, h_best_idx, stream, nullptr);
+}
+
+int ppbo_predict_p(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc, int64_t M, int score_kind,
+                   double mustar, double* d_mu, double* d_var, double* d_score, double* h_best_val,
+                   int64_t* h_best_idx, void* stream, const ppbo_var_projection* proj) {
   PPBO_ENTER(ctx);
   hipStream_t s = (hipStream_t)stream;
   Best* chunk_best = nullptr;
@@ -2783,13 +2818,13 @@ int ppbo_predict(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc, int
   const bool want_best = h_best_val || h_best_idx;
   if (!want_best)
     return predict_passes(ctx, model, d_Xc, M, score_kind, mustar, d_mu, d_var, d_score, false, nullptr, 0,
-                          &chunk_best, &n_chunks, s);
+                          &chunk_best, &n_chunks, s, nullptr, 0, nullptr, proj);
   // the best comes back through the ctx's host-mapped record (written by the last score workgroup, flag polled by the
   // host) instead of a device-to-host copy + stream synchronisation
   PpboHostRecord hr;
   if (int rc = ppbo_host_record(ctx, &hr)) return rc;
   if (int rc = predict_passes(ctx, model, d_Xc, M, score_kind, mustar, d_mu, d_var, d_score, true, hr.d_rec, 0,
-                              &chunk_best, &n_chunks, s, hr.d_flag, hr.epoch))
+                              &chunk_best, &n_chunks, s, hr.d_flag, hr.epoch, nullptr, proj))
     return rc;
   if (int rc = ppbo_host_record_wait(ctx, hr, s)) return rc;
   if (h_best_val) *h_best_val = hr.h_rec[0];      // (NaN, -1) when no candidate has a non-NaN score
@@ -2799,12 +2834,18 @@ int ppbo_predict(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc, int
 
 int ppbo_predict_record(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc, int64_t M, int score_kind,
                         double mustar, int64_t index_offset, double* d_record, void* stream) {
+  return ppbo_predict_record_p(ctx, model, d_Xc, M, score_kind, mustar, index_offset, d_record, stream, nullptr);
+}
+
+int ppbo_predict_record_p(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc, int64_t M, int score_kind,
+                          double mustar, int64_t index_offset, double* d_record, void* stream,
+                          const ppbo_var_projection* proj) {
   PPBO_ENTER(ctx);
   PPBO_REQUIRE(ctx, d_record != nullptr, "d_record");
   Best* chunk_best = nullptr;
   int n_chunks = 0;
   return predict_passes(ctx, model, d_Xc, M, score_kind, mustar, nullptr, nullptr, nullptr, true, d_record,
-                        index_offset, &chunk_best, &n_chunks, (hipStream_t)stream);
+                        index_offset, &chunk_best, &n_chunks, (hipStream_t)stream, nullptr, 0, nullptr, proj);
 }
 
 // Duels and slopes: two [M, D] point sets per column -- the sides (a, b) of a duel, or the point and the direction
@@ -3256,11 +3297,19 @@ int ppbo_predict_tournament(ppbo_ctx* ctx, const ppbo_model* model, const double
 // internal (dist.hip): ppbo_predict_record whose record lives in host-mapped memory, the flag raised after it
 int ppbo_predict_record_publish(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc, int64_t M, int score_kind,
                                 double mustar, int64_t index_offset, double* d_record, unsigned long long* d_flag,
-                                unsigned long long epoch, hipStream_t s) {
+                                unsigned long long epoch, hipStream_t s, const ppbo_var_projection* proj) {
   Best* chunk_best = nullptr;
   int n_chunks = 0;
   return predict_passes(ctx, model, d_Xc, M, score_kind, mustar, nullptr, nullptr, nullptr, true, d_record,
-                        index_offset, &chunk_best, &n_chunks, s, d_flag, epoch);
+                        index_offset, &chunk_best, &n_chunks, s, d_flag, epoch, nullptr, proj);
+}
+
+// internal (project.hip): edge_apply_kernel on the caller's stream -- E [N][ld] = the edge-layout rows of Kt [N][ld]
+int ppbo_edge_apply_async(ppbo_ctx* ctx, const double* Kt, int ld, int M, int N, int mblk, const double* d_lam_off, double* E,
+                          hipStream_t s) {
+  edge_apply_kernel<<<dim3((M + 127) / 128, N), 128, 0, s>>>(Kt, ld, M, mblk, N / mblk, d_lam_off, E);
+  PPBO_LAUNCH_CHECK(ctx);
+  return 0;
 }
 
 extern "C" {

@@ -62,11 +62,19 @@ class ShardedSearch:
                           wait).  The 128-byte ncclUniqueId is created on rank 0 and broadcast through
                           torch.distributed's store-backed object broadcast (any transport would do).
 
+    project=True (and not PPBO_VAR_PROJECTION=0): the posterior's variance projection (Engine.project_variance) is built
+    once here and every step contracts the variance with it -- the operator depends on the posterior only, the candidates
+    may change from step to step.  Every rank builds the same bits.  Posteriors that take no projection score as before,
+    and so do those whose projection saves less than min_gain = 1.5 x of the contraction's flops (E / (2 rows), E = N - n_q:
+    the dense launch skips nothing of its tiles, the triangular one half of its diagonal ones, and a smaller saving does
+    not repay the loss of the exact operator; C3: 512 rows of 1984, 1.94 x -- taken; C4: 384 of 992, 1.29 x -- not taken, its
+    steps run the triangular launch and keep its flop accounting).
+
     Per step the host waits exactly once, for the reduced record.  On host tensors (gloo: the CPU tests and the
     shared-GPU test mode) the record is copied to the host and combine_best applies the same rule."""
 
     def __init__(self, engine, post, Xc_shard, shard_offset: int, score, mustar=0.0, group=None, collective="torch",
-                 host_collective=False):
+                 host_collective=False, project=True, min_gain=1.5):
         if getattr(post, "scale", None) is not None:
             # the shards would have to be scaled on every rank; no multi-GPU run of that exists to test it
             raise ValueError("ShardedSearch does not take a posterior with per-dimension length scales")
@@ -86,7 +94,15 @@ class ShardedSearch:
         from .engine import SCORE_MEAN, _ptr
         self._md = engine._model(post, score != SCORE_MEAN)
         self._md_ref = _C.byref(self._md)
-        self._search_fn, self._record_fn = engine.lib.ppbo_search_sharded, engine.lib.ppbo_predict_record
+        self._search_fn, self._record_fn = engine.lib.ppbo_search_sharded_p, engine.lib.ppbo_predict_record_p
+        import os as _os
+        self.projection = None
+        if project and score != SCORE_MEAN and post.G is not None and _os.environ.get("PPBO_VAR_PROJECTION", "1") != "0":
+            pj = engine.project_variance(post)
+            N = int(post.X.shape[0])
+            E = N - N // (int(post.m) + 1)
+            self.projection = pj if pj.rows > 0 and E >= min_gain * 2 * pj.rows else None
+        self._pj_ref = self.projection.ref if self.projection is not None else None
         self._xc_ptr, self._M = _ptr(self.Xc), int(self.Xc.shape[0])
         self._bv, self._bi = _C.c_double(0.0), _C.c_int64(-1)
         self._bv_ref, self._bi_ref = _C.byref(self._bv), _C.byref(self._bi)
@@ -111,11 +127,11 @@ class ShardedSearch:
         single = self.world == 1 and not self.host and not (dist.is_available() and dist.is_initialized())
         if (self.collective == "capi" or single) and not self.host:
             rc = self._search_fn(eng.ctx, self._md_ref, self._xc_ptr, self._M, int(self.score), self.mustar,
-                                             self.offset, self._bv_ref, self._bi_ref, eng._stream())
+                                             self.offset, self._bv_ref, self._bi_ref, eng._stream(), self._pj_ref)
             eng._check(rc, "ppbo_search_sharded")
             return self._bv.value, self._bi.value
         rc = self._record_fn(eng.ctx, self._md_ref, self._xc_ptr, self._M, int(self.score), self.mustar,
-                                         self.offset, self._rec_ptr, eng._stream())
+                                         self.offset, self._rec_ptr, eng._stream(), self._pj_ref)
         eng._check(rc, "ppbo_predict_record")
         if self.world == 1 and not dist.is_initialized():
             v, i = self.record.tolist()
@@ -195,4 +211,5 @@ def broadcast_posterior(post, src: int = 0, group=None):
     dist.broadcast(form, src=src, group=group)
     post.form = int(form.item())
     post.Gt = None            # the cached transpose of G (engine._model) belongs to the old contents
+    post.proj = None          # ... and so does its variance projection (engine.project_variance)
     return post

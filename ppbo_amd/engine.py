@@ -202,6 +202,7 @@ class Posterior:
     Xu: torch.Tensor | None = None     # ARD: the rows in the caller's unit-box coordinates (formed on first use, marginal_axes)
     Xc: torch.Tensor | None = None     # ... and this the caller's rows [N, 6] (mu_star searches in their coordinates)
     form: int = FORM_NODE              # FORM_NODE / FORM_EDGE: how G is to be read (ppbo_model.form)
+    proj: object = None                # the cached VarianceProjection of G (Engine.project_variance); dropped with Gt
 
     @property
     def embedded(self):
@@ -211,6 +212,19 @@ class Posterior:
 
 def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+
+
+class VarianceProjection:
+    """A projected variance operator of one Posterior (Engine.project_variance): the device matrix T = Q^T H and the
+    ppbo_var_projection that names it.  rows == 0: no projection (the scoring entries then run their usual launches);
+    otherwise 0 <= var - var_projected <= bound for every candidate, bound <= tol sigma_f^2."""
+
+    def __init__(self, T, struct, tol):
+        self.T, self.struct, self.tol = T, struct, float(tol)
+        self.ref = C.byref(struct)
+
+    rows = property(lambda self: self.struct.rows)
+    bound = property(lambda self: self.struct.bound)
 
 
 class Engine:
@@ -367,6 +381,25 @@ class Engine:
                 torch.cuda.current_stream(self.device).synchronize()
             md.d_Gt = post.Gt.data_ptr()
         return md
+
+    def project_variance(self, post: Posterior, tol=1e-10):
+        """The variance contraction of `post` in a bounded low-rank basis (ppbo_var_projection_build), built once and cached
+        on the posterior: a VarianceProjection with 0 <= var - var_projected <= tol sigma_f^2 for every candidate, or one
+        with rows == 0 where the model takes none (node form, the one-launch kernel's shapes, tolerance not reached).
+        Deterministic: every rank of a replicated fit builds the same bits."""
+        cached = post.proj
+        if cached is not None and cached.tol == float(tol) and cached.T.device == post.alpha.device:
+            return cached
+        md = self._model(post, True)
+        rows, ld = C.c_int(0), C.c_int(0)
+        self._check(self.lib.ppbo_var_projection_shape(C.byref(md), C.byref(rows), C.byref(ld)), "ppbo_var_projection_shape")
+        T = self.empty(max(rows.value, 1), ld.value)
+        st = _lib.VarProjection()
+        rc = self.lib.ppbo_var_projection_build(self.ctx, C.byref(md), float(tol), _ptr(T), C.byref(st), self._stream())
+        self._check(rc, "ppbo_var_projection_build")
+        torch.cuda.current_stream(self.device).synchronize()      # complete before any other stream is handed T
+        post.proj = VarianceProjection(T, st, tol)
+        return post.proj
 
     def posterior_form(self, kernel, N, D, m):
         """The operator form to build for a model of this shape (ppbo_posterior_form): FORM_NODE where the one-launch
@@ -745,7 +778,8 @@ class Engine:
 
     # ---- prediction ---------------------------------------------------------------
     def predict(self, post: Posterior, Xc, score=SCORE_MEAN, mustar=0.0, want_mu=True, want_var=True,
-                want_score=False, want_best=True, kstar_fp32=False):
+                want_score=False, want_best=True, kstar_fp32=False, projection=None):
+        """projection: a VarianceProjection of `post` (project_variance) to contract the variance with, or None."""
         Xc = self._points(post, Xc)
         M = Xc.shape[0]
         with_var = want_var or score != SCORE_MEAN
@@ -754,10 +788,10 @@ class Engine:
         var = self.empty(M) if (want_var and with_var) else None
         sc = self.empty(M) if want_score else None
         bv, bi = C.c_double(0.0), C.c_int64(-1)
-        rc = self.lib.ppbo_predict(self.ctx, C.byref(md), _ptr(Xc), M, int(score), float(mustar), _ptr(mu), _ptr(var),
-                                   _ptr(sc), C.byref(bv) if want_best else None, C.byref(bi) if want_best else None,
-                                   self._stream())
-        self._check(rc, "ppbo_predict")
+        rc = self.lib.ppbo_predict_p(self.ctx, C.byref(md), _ptr(Xc), M, int(score), float(mustar), _ptr(mu), _ptr(var),
+                                     _ptr(sc), C.byref(bv) if want_best else None, C.byref(bi) if want_best else None,
+                                     self._stream(), projection.ref if projection is not None else None)
+        self._check(rc, "ppbo_predict_p")
         return dict(mu=mu, var=var, score=sc, best_val=bv.value, best_idx=bi.value)
 
     @staticmethod
