@@ -7,6 +7,7 @@
 // camphor kernel on the vector ALUs (gram_kernel).  HBM-write bound: algorithmic bytes = 8 N^2 + 8 N D;
 // the write-only floor of the chip at these sizes is measured by tools/store_floor.hip.
 #include "common.h"
+#include "tile_walk.h"
 
 namespace {
 
@@ -216,30 +217,9 @@ __global__ __launch_bounds__(512) void gram_mfma_kernel(const double* __restrict
   double* nb = na + TS;            // [64] |x_j|^2
   double* Tw = nb + TS;            // [8 waves][16][LT]
 
-  // off-diagonal tiles first (row by row over the strict upper triangle), the nt diagonal tiles last: the
-  // diagonal tiles have no mirror image to write, and the last-dispatched workgroups are the ones that land as
-  // a third tile on an already busy CU (528 tiles on 256 CUs at N = 2048)
-  const int n1 = nt - 1, n_off = n1 * (n1 + 1) / 2;
+  // off-diagonal tiles first, the nt diagonal tiles last; row-major or diagonal-major (order): tile_walk.h
   int bi, bj;
-  if ((int)blockIdx.x >= n_off) {
-    bi = bj = blockIdx.x - n_off;
-  } else {
-    const int t = blockIdx.x;
-    const double q = 2.0 * n1 + 1.0;
-    bi = (int)floor((q - sqrt(q * q - 8.0 * (double)t)) * 0.5);
-    while (bi > 0 && t < bi * n1 - bi * (bi - 1) / 2) --bi;
-    while (t >= (bi + 1) * n1 - (bi + 1) * bi / 2) ++bi;
-    bj = bi + (t - (bi * n1 - bi * (bi - 1) / 2)) + 1;
-    if (order == 1) {
-      // diagonal-major: the same decomposition read as (distance k = bi + 1 from the diagonal, position r along
-      // it).  Row-major order makes co-resident workgroups share ONE 512-byte column window for their mirror
-      // stores (same bi, consecutive bj): with a power-of-two row pitch those all fall on the same memory
-      // channels.  Along a diagonal both the direct and the mirror windows move with every workgroup.
-      const int k = bi + 1, r = bj - bi - 1;
-      bi = r;
-      bj = r + k;
-    }
-  }
+  ppbo_gram_tile(blockIdx.x, nt, order, bi, bj);
   const int i0 = bi * TS, j0 = bj * TS;
 
   // 4 lanes per row, DP/4 elements each; threads 0-255 stage the row panel, 256-511 the column panel

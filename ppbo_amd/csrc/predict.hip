@@ -30,6 +30,7 @@
 #include "gemm_f64.h"
 #include "linalg.h"
 #include "score.h"
+#include "tile_walk.h"
 
 namespace {
 
@@ -1463,30 +1464,8 @@ __global__ __launch_bounds__(C::NT, MINW) void quadform_kernel(const double* __r
                                                                const double* __restrict__ Kt, int ldk, int M,
                                                                int tri_block, double* __restrict__ slab, int ntm,
                                                                int ntn, int swizzle, int n_rows, int kshift) {
-  int id = blockIdx.x;
-  if (swizzle & 1) {                   // XCD-aware: consecutive logical ids share an XCD / L2 (workgroup b runs on XCD b % 8)
-    const int per = gridDim.x >> 3, rem = gridDim.x & 7;
-    const int xcd = id & 7, pos = id >> 3;            // a bijection for any grid size: XCDs [0, rem) hold per + 1 ids
-    id = pos + (xcd < rem ? xcd * (per + 1) : rem * (per + 1) + (xcd - rem) * per);
-  }
-  int mt, nt;
-  if (swizzle & 2) {                   // candidate tile fastest: co-resident workgroups share one G row panel
-    const int ch = swizzle >> 2;       // optional: candidate tiles in chunks of ch (K* chunk stays in the Infinity Cache)
-    if (ch > 0 && ch < ntn) {
-      const int per_chunk = ntm * ch, full = ntn / ch;
-      if (id < full * per_chunk) {
-        const int c = id / per_chunk, r = id % per_chunk;
-        mt = ntm - 1 - (r / ch); nt = c * ch + (r % ch);
-      } else {                         // the last, narrower chunk
-        const int cw = ntn - full * ch, r = id - full * per_chunk;
-        mt = ntm - 1 - (r / cw); nt = full * ch + (r % cw);
-      }
-    } else {
-      mt = ntm - 1 - (id / ntn); nt = id % ntn;
-    }
-  } else {                             // row tile fastest, heaviest (largest K range) first: share one K* panel
-    mt = ntm - 1 - (id % ntm); nt = id / ntm;
-  }
+  int mt, nt;                          // the walk (XCD remap, candidate- or row-tile fastest, chunks): tile_walk.h
+  ppbo_qf_tile(blockIdx.x, gridDim.x, swizzle, ntm, ntn, mt, nt);
   const int m0 = mt * C::BM, n0 = nt * C::BN;
   // G is zero right of the last star that reaches into this row tile; the K range ends there, rounded UP to the chunk
   // depth (g_build_kernel writes the zeros of every row explicitly, so the extra columns multiply zeros): every K
@@ -1562,7 +1541,7 @@ int launch_quadform(ppbo_ctx* ctx, const double* G, int N, int g_rows, int n_row
   // profiles/r04_quadform_traffic_vs_order.txt), of 256 tiles up to N = 1024 (1026: the same 268 MB of K* per chunk as 128
   // tiles at N = 2048; round 6, interleaved on one box at C4: 0.899-0.903 against 0.891-0.894 of the MFMA peak)
   const int order = ctx->qf_order >= 0 ? ctx->qf_order : (N <= 1024 ? 1026 : 514);
-  const int swz = (grid >= 64 ? (order & 1) : 0) | (order & ~1);
+  const int swz = ppbo_qf_swizzle(order, grid);
   // every tile in bounds, 16-byte aligned, and every K range a multiple of 16?
   const bool fast = (g_rows % C::BM == 0) && (ldk >= ntn * C::BN) && (N % BK == 0) && (ldk % 2 == 0) &&
                     ((reinterpret_cast<uintptr_t>(G) & 15) == 0) && ((reinterpret_cast<uintptr_t>(Kt) & 15) == 0);
