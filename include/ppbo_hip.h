@@ -970,6 +970,19 @@ PPBO_API int ppbo_search_sharded_p(ppbo_ctx* ctx, const ppbo_model* model, const
                           double mustar, int64_t index_offset, double* h_best_val, int64_t* h_best_idx, void* stream,
                           const ppbo_var_projection* proj);
 
+/* The pruned search, a diagnostic of it.  A call that asks only for the best record (ppbo_search_sharded(_p),
+ * ppbo_predict_record(_p), ppbo_predict(_p) with no per-candidate output) of an edge-form model on the three-launch
+ * path, scored by pointwise EI or VARIANCE, contracts the variance only for the candidates that a certified upper bound
+ * of their score cannot rule out (env PPBO_PRUNE, default 1; 0 = contract all).  The record is bit for bit that of
+ * PPBO_PRUNE=0.  This entry runs the passes of ONE chunk (M <= 65536) with the pruning on, whatever PPBO_PRUNE says, and
+ * reports what they decided: per candidate (device arrays of M doubles, any may be NULL) u2 >= the contraction's sum of
+ * squares, and the score interval [s_lo, s_hi] (s_hi = +inf: a candidate with a non-finite sum, which always survives);
+ * on the host the threshold (the largest s_lo), the number of survivors and whether the chunk was pruned (0: more than
+ * the capacity survived, or no finite threshold -- the full contraction ran).  Synchronises the stream.  ABI 8. */
+PPBO_API int ppbo_predict_prune_report(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc, int64_t M,
+                          int score_kind, double mustar, const ppbo_var_projection* proj, double* d_u2, double* d_s_lo,
+                          double* d_s_hi, double* h_threshold, int* h_n_surv, int* h_pruned, void* stream);
+
 /* y = op(A) x for a square fp64 matrix; lower != 0 reads only the lower triangle (A is then
  * treated as lower-triangular).  Used for alpha = Sigma^-1 f_MAP (src/gp_model.py:445) and
  * prior draws L z (src/gp_model.py:374). */

@@ -189,6 +189,8 @@ SIGNATURES = {
     "ppbo_predict_record_p": [_vp, C.POINTER(Model), _vp, _i64, _i, _d, _i64, _vp, _vp, C.POINTER(VarProjection)],
     "ppbo_search_sharded_p": [_vp, C.POINTER(Model), _vp, _i64, _i, _d, _i64, C.POINTER(_d), C.POINTER(_i64), _vp,
                               C.POINTER(VarProjection)],
+    "ppbo_predict_prune_report": [_vp, C.POINTER(Model), _vp, _i64, _i, _d, C.POINTER(VarProjection), _vp, _vp, _vp,
+                                  C.POINTER(_d), C.POINTER(_i), C.POINTER(_i), _vp],
     "ppbo_argmax_combine": [_vp, _vp, _i, C.POINTER(_d), C.POINTER(_i64), _vp],
     "ppbo_dgemm": [_vp, _i, _i, _i, _i, _i, _d, _vp, _i, _vp, _i, _d, _vp, _i, _vp],
 }

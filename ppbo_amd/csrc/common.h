@@ -26,7 +26,7 @@ struct ppbo_ctx {
   int device = 0;
   std::string err;
   // named workspace slots
-  enum { WS_KSTAR = 0, WS_PART, WS_SCRATCH, WS_LINALG, WS_LINALG2, WS_VEC, WS_SMALL, WS_POTRF, WS_APPEND, WS_DIST, WS_LBFGS, WS_SEARCH, WS_SEARCH_SMALL, WS_LBFGS_U, WS_TRANSPOSE, WS_GPAD, WS_SEARCH_ROWS, WS_SCALE, WS_SCALE_PTS, WS_SCALE_SEARCH, WS_EVGRAD, WS_EVGRAD_VEC, WS_CAMPHOR, WS_CAMPHOR_ROWS, WS_KSTAR_GEO, WS_MARGINAL, WS_TOURN_U, WS_TOURN_FIELD, WS_TOURN_K, WS_PROJECT, WS_PROJECT_SMALL, WS_COUNT };
+  enum { WS_KSTAR = 0, WS_PART, WS_SCRATCH, WS_LINALG, WS_LINALG2, WS_VEC, WS_SMALL, WS_POTRF, WS_APPEND, WS_DIST, WS_LBFGS, WS_SEARCH, WS_SEARCH_SMALL, WS_LBFGS_U, WS_TRANSPOSE, WS_GPAD, WS_SEARCH_ROWS, WS_SCALE, WS_SCALE_PTS, WS_SCALE_SEARCH, WS_EVGRAD, WS_EVGRAD_VEC, WS_CAMPHOR, WS_CAMPHOR_ROWS, WS_KSTAR_GEO, WS_MARGINAL, WS_TOURN_U, WS_TOURN_FIELD, WS_TOURN_K, WS_PROJECT, WS_PROJECT_SMALL, WS_PRUNE, WS_PRUNE_KC, WS_COUNT };
   void* ws[WS_COUNT] = {};
   size_t ws_bytes[WS_COUNT] = {};
   void* pinned = nullptr;  // small pinned host staging buffer
@@ -52,6 +52,10 @@ struct ppbo_ctx {
   // PPBO_KSTAR_STAR: 1 (default) = kstar_kernel forms the rows of a collinear star from two inner products per star
   // (star_geom_kernel's table), 0 = always one inner product per row
   int kstar_star = 1;
+  // PPBO_PRUNE: 1 (default) = a search that returns only its best record (edge form, pointwise EI or VARIANCE, the
+  // three-launch path) contracts the variance only for the candidates that a certified bound cannot rule out
+  // (predict_passes), 0 = always for all.  PPBO_PRUNE_CAP (tests): the survivor capacity per chunk, 0 = a chunk's eighth
+  int prune = 1, prune_cap = 0;
   int gemm_big16 = 1;     // PPBO_GEMM_BIG16: large GEMMs on 16 wavefronts of 32 x 32 (default since round 6) instead of 8 of 32 x 64
   int n_cu = 0;           // compute units of the device (hipDeviceProp_t::multiProcessorCount)
   int fused_dbg = 0;      // PPBO_FUSED_DBG: measurement switches of fused.hip (results are wrong when set)

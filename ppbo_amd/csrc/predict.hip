@@ -136,12 +136,23 @@ __global__ __launch_bounds__(64 * SG_STARS) void star_geom_kernel(const double* 
 // (the fp64 radial buckets up to DP = 20 are held to 128 VGPRs = 4 wavefronts per SIMD, the occupancy the flagship shape
 // D = 20 had before the star path added r0^2 and beta to the live set; SE fits there without scratch.  RQ and the Matern
 // kernels would spill two registers at DP = 20 and are left unbound in that bucket: three wavefronts, no scratch)
-template <int KID, int DP, bool F32 = false>
-__global__ __launch_bounds__(KS_THREADS, (!F32 && KID != PPBO_KERNEL_CAMPHOR && (DP < 20 || (DP == 20 && KID == PPBO_KERNEL_SE))) ? 4 : 1) void kstar_kernel(
+// UB (the pruned search, predict_passes): an edge-layout launch that also leaves an upper bound of the contraction.
+// The stored column e is cut into its stars; with sig[s] >= the Frobenius norm of the operator's column block of star s
+// (block_norm_kernel), |op e| <= sum_s sig[s] |e_s| =: u (Cauchy-Schwarz per star).  The flagged instantiation sums
+// ev^2 over the rows of a star and adds sig[s] sqrt(.) at the star's end into u_part[split][c]; splits are whole stars,
+// so the partial sums add.  Nothing that the unflagged instantiation computes reads these sums: K*, mu_part and t_part
+// are bit for bit its own.  The lane's running u sits in LDS beside |c|^2 (touched once per star); the star's sum of
+// squares is two more live doubles, which the buckets DP = 16 and 20 do not have at 128 registers (12-64 bytes of scratch
+// per lane), so the flagged instantiation is left unbound there like RQ and Matern at DP = 20: 145 registers, no scratch (bound to
+// four wavefronts with the scratch it measured the same: 310 us against the unflagged 252 us at C3).
+template <int KID, int DP, bool F32 = false, bool UB = false>
+__global__ __launch_bounds__(KS_THREADS, (!F32 && KID != PPBO_KERNEL_CAMPHOR && (DP < 20 || (DP == 20 && KID == PPBO_KERNEL_SE)) && !(UB && DP >= 16)) ? 4 : 1) void kstar_kernel(
     const double* __restrict__ X, int N, int D, KernParams p, const double* __restrict__ alpha,
     const double* __restrict__ lam_diag, const double* __restrict__ lam_off, int mblk,
     const double* __restrict__ Xc, int M, double* __restrict__ Kt, int ldk, double* __restrict__ mu_part,
-    double* __restrict__ t_part, int q_per_split, int n_q, int edge_k0, const double* __restrict__ geo) {
+    double* __restrict__ t_part, int q_per_split, int n_q, int edge_k0, const double* __restrict__ geo,
+    const double* __restrict__ sig = nullptr, double* __restrict__ u_part = nullptr) {
+  static_assert(!UB || !F32, "the bound rides on the fp64 launches");
   __shared__ __attribute__((aligned(16))) double xs[KS_RJ * DP];
   __shared__ double s_alpha[KS_RJ], s_ld[KS_RJ], s_lo[KS_RJ], s_nx[KS_RJ];
   __shared__ int s_col[KS_RJ];
@@ -206,6 +217,13 @@ __global__ __launch_bounds__(KS_THREADS, (!F32 && KID != PPBO_KERNEL_CAMPHOR && 
 #pragma unroll
     for (int q = 0; q < KS_CPT; ++q) s_nc[q * KS_THREADS + threadIdx.x] = nc[q];
   }
+  __shared__ double s_up[UB ? KS_CPT * KS_THREADS : 1];
+  double se[KS_CPT];                       // UB: sum of ev^2 over the rows of the current star
+  (void)se;
+  if constexpr (UB) {
+#pragma unroll
+    for (int q = 0; q < KS_CPT; ++q) { s_up[q * KS_THREADS + threadIdx.x] = 0.0; se[q] = 0.0; }
+  }
   const int j_beg = blockIdx.y * q_per_split * mblk;
   int j_end = j_beg + q_per_split * mblk;
   if (j_end > N) j_end = N;
@@ -237,6 +255,10 @@ __global__ __launch_bounds__(KS_THREADS, (!F32 && KID != PPBO_KERNEL_CAMPHOR && 
           drow = n_q + qs * (mblk - 1) + rb - 1;
 #pragma unroll
           for (int q = 0; q < KS_CPT; ++q) ev[q] = lo * (kv[q] - ko[q]);
+          if constexpr (UB) {
+#pragma unroll
+            for (int q = 0; q < KS_CPT; ++q) se[q] = fma(ev[q], ev[q], se[q]);
+          }
         }
       } else {
 #pragma unroll
@@ -263,6 +285,16 @@ __global__ __launch_bounds__(KS_THREADS, (!F32 && KID != PPBO_KERNEL_CAMPHOR && 
         const double lo2 = 2.0 * lo;
 #pragma unroll
         for (int q = 0; q < KS_CPT; ++q) tl[q] += kv[q] * (ld * kv[q] + lo2 * ko[q]);
+      }
+    }
+    if constexpr (UB) {
+      if (rb + 1 == mblk) {                // the star's last row: its term of the bound (the slot is the lane's own)
+        const double sg = uniform_load(sig + qs);
+#pragma unroll
+        for (int q = 0; q < KS_CPT; ++q) {
+          s_up[q * KS_THREADS + threadIdx.x] = fma(sg, sqrt(se[q]), s_up[q * KS_THREADS + threadIdx.x]);
+          se[q] = 0.0;
+        }
       }
     }
     if (++rb == mblk) { rb = 0; ++qs; }
@@ -454,6 +486,7 @@ __global__ __launch_bounds__(KS_THREADS, (!F32 && KID != PPBO_KERNEL_CAMPHOR && 
       }
       mu_part[(size_t)blockIdx.y * M + ce + q] = finite ? mu[q] : NAN;
       if (t_part) t_part[(size_t)blockIdx.y * M + ce + q] = finite ? tl[q] : NAN;
+      if constexpr (UB) u_part[(size_t)blockIdx.y * M + ce + q] = finite ? s_up[q * KS_THREADS + threadIdx.x] : NAN;
     }
   }
 }
@@ -1458,15 +1491,32 @@ __global__ __launch_bounds__(KS_THREADS) void kstar_marginal_kernel(
 // state per lane and ~5 % of the matrix-core rate)
 // DENSE (FORM == QF_DENSE): the operand is a projected operator T = Q^T H (project.hip) -- ntm row tiles of a dense
 // matrix in the edge column layout, shifted like the edge form's; every tile and every wavefront runs the full K range
+// PLAN (the pruned search): the launch is one of a pair behind prune_select_kernel, and every workgroup first reads the
+// chunk's plan by scalar loads.  plan_compact = 1: the compact launch -- Kt is the gathered workspace Kc, column j the
+// compact position, M the survivor capacity; it runs when the plan is pruned, on the column tiles below n_surv.
+// plan_compact = 0: today's launch over all candidates, which runs when the plan is not pruned.  A workgroup that does
+// not run returns before it touches an operand.
 constexpr int QF_NODE = 0, QF_EDGE = 1, QF_DENSE = 2;
-template <class C, int MINW, bool ALWAYS_FAST, int FORM>
+template <class C, int MINW, bool ALWAYS_FAST, int FORM, bool PLAN = false>
 __global__ __launch_bounds__(C::NT, MINW) void quadform_kernel(const double* __restrict__ G, int N,
                                                                const double* __restrict__ Kt, int ldk, int M,
                                                                int tri_block, double* __restrict__ slab, int ntm,
-                                                               int ntn, int swizzle, int n_rows, int kshift) {
+                                                               int ntn, int swizzle, int n_rows, int kshift,
+                                                               const PrunePlan* __restrict__ plan = nullptr,
+                                                               int plan_compact = 0) {
+  int n_live = M;                      // PLAN: the columns of this launch that anything reads
+  (void)n_live;
+  if constexpr (PLAN) {
+    const int pruned = uniform_load_int(&plan->pruned);
+    if ((pruned != 0) != (plan_compact != 0)) return;
+    if (plan_compact) n_live = uniform_load_int(&plan->n_surv);
+  }
   int mt, nt;                          // the walk (XCD remap, candidate- or row-tile fastest, chunks): tile_walk.h
   ppbo_qf_tile(blockIdx.x, gridDim.x, swizzle, ntm, ntn, mt, nt);
   const int m0 = mt * C::BM, n0 = nt * C::BN;
+  if constexpr (PLAN) {
+    if (n0 >= n_live) return;
+  }
   // G is zero right of the last star that reaches into this row tile; the K range ends there, rounded UP to the chunk
   // depth (g_build_kernel writes the zeros of every row explicitly, so the extra columns multiply zeros): every K
   // range is then a whole number of chunks whatever the star size -- m = 25, the reference's default, has 26-row stars
@@ -1521,7 +1571,8 @@ using QF5 = Cfg<8, 2, 2, 4>;   // 256 x 128 tile, 16 waves of 32x64, 1 WG/CU: K*
 // predict_passes pads its operands so that this always holds.
 template <class C, int MINW>
 int launch_quadform(ppbo_ctx* ctx, const double* G, int N, int g_rows, int n_rows, const double* Kt, int ldk, int Mc,
-                    int mblk, double* slab, int edge_k0, bool dense, hipStream_t s) {
+                    int mblk, double* slab, int edge_k0, bool dense, hipStream_t s, const PrunePlan* plan = nullptr,
+                    int plan_compact = 0) {
   const size_t lds = C::LDS_DOUBLES * sizeof(double);
   const bool edge = edge_k0 >= 0;
   const int kshift = edge ? edge_k0 : 0;
@@ -1547,6 +1598,21 @@ int launch_quadform(ppbo_ctx* ctx, const double* G, int N, int g_rows, int n_row
                     ((reinterpret_cast<uintptr_t>(G) & 15) == 0) && ((reinterpret_cast<uintptr_t>(Kt) & 15) == 0);
   const double* Gs = G + kshift;
   const double* Ks = Kt + (size_t)kshift * ldk;
+  if (plan) {                          // (edge or dense form only: predict_passes prunes no node-form model)
+#define QF_PLAN(FAST, FORM)                                                                                          \
+  do {                                                                                                               \
+    ppbo_lds_limit(ctx, (const void*)quadform_kernel<C, MINW, FAST, FORM, true>, (int)lds);                          \
+    quadform_kernel<C, MINW, FAST, FORM, true><<<grid, C::NT, lds, s>>>(Gs, N, Ks, ldk, Mc, mblk, slab, ntm, ntn, swz, \
+                                                                        n_rows, kshift, plan, plan_compact);         \
+  } while (0)
+    if (dense && fast) QF_PLAN(true, QF_DENSE);
+    else if (dense) QF_PLAN(false, QF_DENSE);
+    else if (fast) QF_PLAN(true, QF_EDGE);
+    else QF_PLAN(false, QF_EDGE);
+#undef QF_PLAN
+    PPBO_LAUNCH_CHECK(ctx);
+    return 0;
+  }
   if (dense && fast) quadform_kernel<C, MINW, true, QF_DENSE><<<grid, C::NT, lds, s>>>(Gs, N, Ks, ldk, Mc, mblk, slab, ntm, ntn, swz, n_rows, kshift);
   else if (dense) quadform_kernel<C, MINW, false, QF_DENSE><<<grid, C::NT, lds, s>>>(Gs, N, Ks, ldk, Mc, mblk, slab, ntm, ntn, swz, n_rows, kshift);
   else if (edge && fast) quadform_kernel<C, MINW, true, QF_EDGE><<<grid, C::NT, lds, s>>>(Gs, N, Ks, ldk, Mc, mblk, slab, ntm, ntn, swz, n_rows, kshift);
@@ -1567,15 +1633,16 @@ int quadform_variant(const ppbo_ctx* ctx) { return ctx->qf_variant; }
 // dense: G is a projected operator T (g_rows = n_rows = its padded row count, a multiple of 128) of an edge-form model
 // (edge_k0 >= 0); the 256-row tile of variant 5 does not divide every such count, so variant 5 runs it as variant 4
 int dispatch_quadform(ppbo_ctx* ctx, const double* G, int N, int g_rows, int n_rows, const double* Kt, int ldk, int Mc,
-                      int mblk, double* slab, int edge_k0, hipStream_t s, bool dense = false) {
+                      int mblk, double* slab, int edge_k0, hipStream_t s, bool dense = false,
+                      const PrunePlan* plan = nullptr, int plan_compact = 0) {
   switch (quadform_variant(ctx)) {
-    case 1: return launch_quadform<QF1, 4>(ctx, G, N, g_rows, n_rows, Kt, ldk, Mc, mblk, slab, edge_k0, dense, s);
-    case 2: return launch_quadform<QF2, 4>(ctx, G, N, g_rows, n_rows, Kt, ldk, Mc, mblk, slab, edge_k0, dense, s);
-    case 3: return launch_quadform<QF3, 4>(ctx, G, N, g_rows, n_rows, Kt, ldk, Mc, mblk, slab, edge_k0, dense, s);
-    case 5: if (!dense) return launch_quadform<QF5, 4>(ctx, G, N, g_rows, n_rows, Kt, ldk, Mc, mblk, slab, edge_k0, false, s);
+    case 1: return launch_quadform<QF1, 4>(ctx, G, N, g_rows, n_rows, Kt, ldk, Mc, mblk, slab, edge_k0, dense, s, plan, plan_compact);
+    case 2: return launch_quadform<QF2, 4>(ctx, G, N, g_rows, n_rows, Kt, ldk, Mc, mblk, slab, edge_k0, dense, s, plan, plan_compact);
+    case 3: return launch_quadform<QF3, 4>(ctx, G, N, g_rows, n_rows, Kt, ldk, Mc, mblk, slab, edge_k0, dense, s, plan, plan_compact);
+    case 5: if (!dense) return launch_quadform<QF5, 4>(ctx, G, N, g_rows, n_rows, Kt, ldk, Mc, mblk, slab, edge_k0, false, s, plan, plan_compact);
             [[fallthrough]];
-    case 4: return launch_quadform<QF4, 8>(ctx, G, N, g_rows, n_rows, Kt, ldk, Mc, mblk, slab, edge_k0, dense, s);
-    default: return launch_quadform<QF0, 2>(ctx, G, N, g_rows, n_rows, Kt, ldk, Mc, mblk, slab, edge_k0, dense, s);
+    case 4: return launch_quadform<QF4, 8>(ctx, G, N, g_rows, n_rows, Kt, ldk, Mc, mblk, slab, edge_k0, dense, s, plan, plan_compact);
+    default: return launch_quadform<QF0, 2>(ctx, G, N, g_rows, n_rows, Kt, ldk, Mc, mblk, slab, edge_k0, dense, s, plan, plan_compact);
   }
 }
 
@@ -2365,7 +2432,7 @@ __global__ __launch_bounds__(256) void omega_draws_kernel(const double* __restri
 template <int KID>
 int launch_kstar(const ppbo_model* m, const KernParams& p, const double* d_Xc, int M, double* Kt, int ldk,
                  double* mu_part, double* t_part, int q_per_split, int n_split, bool with_lam, int edge_k0,
-                 const double* geo, hipStream_t s) {
+                 const double* geo, hipStream_t s, const double* sig = nullptr, double* u_part = nullptr) {
   dim3 grid((M + KS_THREADS * KS_CPT - 1) / (KS_THREADS * KS_CPT), n_split);
   const int mblk = m->m + 1, n_q = (m->N + mblk - 1) / mblk;
   const double* ld = with_lam ? m->d_lam_diag : nullptr;
@@ -2383,22 +2450,28 @@ int launch_kstar(const ppbo_model* m, const KernParams& p, const double* d_Xc, i
     return 0;
   }
 #undef KS_LAUNCH32
-#define KS_LAUNCH(DP)                                                                                          \
-  kstar_kernel<KID, DP><<<grid, KS_THREADS, 0, s>>>(m->d_X, m->N, m->D, p, m->d_alpha, ld, lo, mblk, d_Xc, M, \
-                                                    Kt, ldk, mu_part, with_lam ? t_part : nullptr,            \
-                                                    q_per_split, n_q, edge_k0, geo)
-  if constexpr (KID == PPBO_KERNEL_CAMPHOR) KS_LAUNCH(12);      // the feature form: 12 staged values per row
-  else if (m->D <= 4) KS_LAUNCH(4);
-  else if (m->D <= 6) KS_LAUNCH(6);
-  else if (m->D <= 8) KS_LAUNCH(8);
-  else if (m->D <= 10) KS_LAUNCH(10);
-  else if (m->D <= 12) KS_LAUNCH(12);
-  else if (m->D <= 16) KS_LAUNCH(16);
-  else if (m->D <= 20) KS_LAUNCH(20);
-  else if (m->D <= 24) KS_LAUNCH(24);
-  else if (m->D <= 32) KS_LAUNCH(32);
-  else if (m->D <= 48) KS_LAUNCH(48);
-  else KS_LAUNCH(64);
+  // (sig: the flagged instantiation, an edge-layout launch with Lambda and a K* store; predict_passes asks for no other)
+#define KS_LAUNCH(DP)                                                                                            \
+  if (sig)                                                                                                       \
+    kstar_kernel<KID, DP, false, true><<<grid, KS_THREADS, 0, s>>>(m->d_X, m->N, m->D, p, m->d_alpha, ld, lo,   \
+                                                                   mblk, d_Xc, M, Kt, ldk, mu_part, t_part,      \
+                                                                   q_per_split, n_q, edge_k0, geo, sig, u_part); \
+  else                                                                                                           \
+    kstar_kernel<KID, DP><<<grid, KS_THREADS, 0, s>>>(m->d_X, m->N, m->D, p, m->d_alpha, ld, lo, mblk, d_Xc, M, \
+                                                      Kt, ldk, mu_part, with_lam ? t_part : nullptr,            \
+                                                      q_per_split, n_q, edge_k0, geo)
+  if constexpr (KID == PPBO_KERNEL_CAMPHOR) { KS_LAUNCH(12); }  // the feature form: 12 staged values per row
+  else if (m->D <= 4) { KS_LAUNCH(4); }
+  else if (m->D <= 6) { KS_LAUNCH(6); }
+  else if (m->D <= 8) { KS_LAUNCH(8); }
+  else if (m->D <= 10) { KS_LAUNCH(10); }
+  else if (m->D <= 12) { KS_LAUNCH(12); }
+  else if (m->D <= 16) { KS_LAUNCH(16); }
+  else if (m->D <= 20) { KS_LAUNCH(20); }
+  else if (m->D <= 24) { KS_LAUNCH(24); }
+  else if (m->D <= 32) { KS_LAUNCH(32); }
+  else if (m->D <= 48) { KS_LAUNCH(48); }
+  else { KS_LAUNCH(64); }
 #undef KS_LAUNCH
   return 0;
 }
@@ -2407,12 +2480,12 @@ int launch_kstar(const ppbo_model* m, const KernParams& p, const double* d_Xc, i
 // geo: the model's star-geometry table (star_geometry), or NULL = one inner product per row
 int dispatch_kstar(const ppbo_model* m, const double* d_Xc, int M, double* Kt, int ldk, double* mu_part,
                    double* t_part, int q_per_split, int n_split, bool with_lam, hipStream_t s, int edge_k0 = -1,
-                   const double* geo = nullptr) {
+                   const double* geo = nullptr, const double* sig = nullptr, double* u_part = nullptr) {
   const KernParams p = make_kern_params(m->kernel_id, m->theta);
   // (no ctx: an unknown id returns -1 and sets no message; check_model rejects any such id first)
   return ppbo_kernel_dispatch(nullptr, m->kernel_id, [&](auto kid) {
     return launch_kstar<decltype(kid)::value>(m, p, d_Xc, M, Kt, ldk, mu_part, t_part, q_per_split, n_split, with_lam,
-                                              edge_k0, geo, s);
+                                              edge_k0, geo, s, sig, u_part);
   });
 }
 
@@ -2603,6 +2676,204 @@ int marginal_axes_arg(ppbo_ctx* ctx, MargArgs* ma) {
   return 0;
 }
 
+// ---- the pruned search (predict_passes) --------------------------------------------------------------------------------
+// A search that returns only its best record needs the variance of a candidate only if that candidate can be the argmax.
+// Pointwise EI and VARIANCE do not decrease in the variance at a fixed mean, so an interval [var_lo, var_hi] of a
+// candidate's variance gives an interval [s_lo, s_hi] of its score, and a candidate whose s_hi lies below the best s_lo of
+// the chunk cannot win.  With var = (sf2 + t) + q, q = |op e|^2 >= 0 the contraction (op: the operand of the launch, H or a
+// projected T; e: the candidate's edge-layout K* column):
+//   var_lo = sf2 + t          (exactly <= the fp var: q >= 0 and fp addition is monotone)
+//   var_hi = var_lo + (1 + 2^-20) u^2,  u = sum_s sig[s] |e_s|  >=  |op e|   (Cauchy-Schwarz per star s of the columns)
+// sig[s] = the Frobenius norm of op's column block of star s (block_norm_kernel, rounded up), |e_s| accumulated by the
+// flagged K* instantiation.  2^-20 covers every rounding between u and the fp q (sums of <= 2^17 non-negative terms,
+// relative error <= 2^-35 each, the sqrt's and the matrix cores' accumulation).
+// Per chunk: block_norm -> K* with bounds -> prune_bounds -> prune_select (threshold, stable compaction, the plan) ->
+// gather of the survivors' columns -> contraction (a compact and a full launch, one of which runs) -> score with the
+// plan -> argmax.  Nothing waits on the host; the plan lives in device memory.
+
+// sig[s] >= ||op[:, n_q + s m .. n_q + (s + 1) m)||_F for the n_q stars; op [rows][ld].  One workgroup per star, 32 rows x
+// 32 columns of lanes; formed on every call (the model's operator may be rewritten in place between calls).  A
+// non-finite entry gives a non-finite sig and through it candidates that always survive.
+constexpr int BN_THREADS = 1024;
+__global__ __launch_bounds__(BN_THREADS) void block_norm_kernel(const double* __restrict__ op, int rows, int ld, int n_q,
+                                                                int m, double* __restrict__ sig) {
+  __shared__ double red[BN_THREADS / 64];
+  const int s = blockIdx.x, tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  const double* __restrict__ col = op + n_q + (size_t)s * m;
+  double acc = 0.0;
+  for (int c = tx; c < m; c += 32) {
+#pragma unroll 8
+    for (int r = ty; r < rows; r += 32) { const double v = col[(size_t)r * ld + c]; acc = fma(v, v, acc); }
+  }
+  acc = wave_sum(acc);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t = 0.0;
+    for (int w = 0; w < BN_THREADS / 64; ++w) t += red[w];
+    sig[s] = sqrt(t) * (1.0 + 0x1.0p-30);   // (the sum of <= 2^22 squares: relative error <= 2^-31 before the root halves it)
+  }
+}
+
+// The bounds of a chunk's candidates, in score_kernel's geometry and summation order (mu and t are bit for bit what the
+// score pass forms): s_hi[c] (+inf = always survives: a non-finite partial sum or bound), per workgroup the largest s_lo
+// of its candidates with finite sums (-inf: none) and the largest |mu - mustar| + sd_hi (the scale of prune_select's
+// tolerance; 0 for VARIANCE).  rep_*: the report entry's per-candidate copies (NULL on the search path).
+__global__ __launch_bounds__(SC_THREADS) void prune_bounds_kernel(const double* __restrict__ mu_part, int n_mu,
+                                                                  const double* __restrict__ t_part,
+                                                                  const double* __restrict__ u_part, int M, double sf2,
+                                                                  int kind, double mustar, double* __restrict__ s_hi_out,
+                                                                  double* __restrict__ blk_lo, double* __restrict__ blk_scale,
+                                                                  double* __restrict__ rep_u2, double* __restrict__ rep_lo,
+                                                                  double* __restrict__ rep_hi) {
+  __shared__ double part[3][SC_WAVES][SC_CAND];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int c = blockIdx.x * SC_CAND + lane;
+  double pm = 0.0, pt = 0.0, pu = 0.0;
+  if (c < M) {
+    for (int s = wave; s < n_mu; s += SC_WAVES) pm += mu_part[(size_t)s * M + c];
+    for (int s = wave; s < n_mu; s += SC_WAVES) pt += t_part[(size_t)s * M + c];
+    for (int s = wave; s < n_mu; s += SC_WAVES) pu += u_part[(size_t)s * M + c];
+  }
+  part[0][wave][lane] = pm;
+  part[1][wave][lane] = pt;
+  part[2][wave][lane] = pu;
+  __syncthreads();
+  if (wave != 0) return;
+  double lo = -INFINITY, scale = 0.0;
+  if (c < M) {
+    double mu = 0.0, t = 0.0, u = 0.0;
+#pragma unroll
+    for (int w = 0; w < SC_WAVES; ++w) { mu += part[0][w][lane]; t += part[1][w][lane]; u += part[2][w][lane]; }
+    const double var_lo = sf2 + t;
+    const double u2 = u * u;
+    const double var_hi = var_lo + (1.0 + 0x1.0p-20) * u2;
+    double s_lo = score_value(mu, var_lo, kind, mustar), s_hi = score_value(mu, var_hi, kind, mustar);
+    const bool ok = fabs(mu) < INFINITY && fabs(var_lo) < INFINITY && fabs(var_hi) < INFINITY && fabs(s_lo) < INFINITY &&
+                    fabs(s_hi) < INFINITY;      // (every comparison is false on a NaN)
+    if (ok) {
+      lo = s_lo;
+      if (kind == PPBO_SCORE_POINTWISE_EI) scale = fabs(mu - mustar) + sqrt(fmax(var_hi, 0.0));
+    } else s_hi = INFINITY;
+    s_hi_out[c] = s_hi;
+    if (rep_u2) rep_u2[c] = u2;
+    if (rep_lo) rep_lo[c] = s_lo;
+    if (rep_hi) rep_hi[c] = s_hi;
+  }
+  lo = wave_max(lo);
+  scale = wave_max(scale);
+  if (lane == 0) { blk_lo[blockIdx.x] = lo; blk_scale[blockIdx.x] = scale; }
+}
+
+// One workgroup: the threshold b = max s_lo, the survivors {c : !(s_hi[c] + tol < b)} in ascending order (a STABLE
+// compaction: the score pass then breaks ties towards the lowest candidate exactly as the full pass does) and the plan.
+//   tol = 2^-36 max_c (|mu_c - mustar| + sd_hi,c) for pointwise EI, 0 for VARIANCE.
+// Why tol dominates the non-monotonicity of the fp score: VARIANCE is the identity, monotone as it stands.  The fp EI
+// F(var) = d Phi(z) + sd phi(z), z = d / sd, follows the exact EI f (which does not decrease in var) to within
+//   eps <= (|d| Phi + sd phi) (z^2 + 8) 2^-52  <=  2^-50 (|d| + sd):
+// sqrt and the division are correctly rounded, erfc and exp are good to <= 4 ulp (tests/test_gpu_elementary.py holds the
+// project's own exp and sqrt to <= 1 ulp), the rounding of z moves Phi and phi by <= z^2 2^-52 relative, and
+// (Phi + phi)(z^2 + 8) <= 4.  For the true fp winner w and the candidate a that sets b:
+//   F(var_hi,w) >= f(var_hi,w) - eps >= f(var_w) - eps >= F(var_w) - 2 eps >= F(var_a) - 2 eps >= F(var_lo,a) - 4 eps = b - 4 eps,
+// so w survives whenever tol >= 4 eps = 2^-48 scale: 2^-36 leaves 2^12.
+// pruned = 0 (every launch runs unpruned) when b is not finite, nothing or more than n_cap candidates survive.
+// Geometry: the candidates in groups of 64, group g = [64 g, 64 g + 64); in pass A the workgroup walks the groups 16 at a
+// time (wavefront w takes group 16 i + w) and leaves each group's ballot in LDS; thread g
+// then owns the count of group g for the workgroup-wide scan; pass B (a pruned plan only) writes the indices.
+// report[2] = (b, tol).
+constexpr int PS_THREADS = 1024, PS_BATCH = 8;    // (loads in flight per lane; 32 measured slower: 21 against 17 us at 65536 candidates)
+__global__ __launch_bounds__(PS_THREADS) void prune_select_kernel(const double* __restrict__ s_hi, int M,
+                                                                  const double* __restrict__ blk_lo,
+                                                                  const double* __restrict__ blk_scale, int n_blk,
+                                                                  int n_cap, int* __restrict__ idx,
+                                                                  PrunePlan* __restrict__ plan, double* __restrict__ report) {
+  constexpr int NW = PS_THREADS / 64;
+  __shared__ double sh_b[NW], sh_s[NW];
+  __shared__ unsigned long long masks[PS_THREADS];
+  __shared__ int excl[PS_THREADS], sh_cnt[NW];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  double b = -INFINITY, sc = 0.0;
+  for (int i = threadIdx.x; i < n_blk; i += PS_THREADS) { b = fmax(b, blk_lo[i]); sc = fmax(sc, blk_scale[i]); }
+  b = wave_max(b);
+  sc = wave_max(sc);
+  if (lane == 0) { sh_b[wave] = b; sh_s[wave] = sc; }
+  __syncthreads();
+  b = sh_b[0]; sc = sh_s[0];
+  for (int w = 1; w < NW; ++w) { b = fmax(b, sh_b[w]); sc = fmax(sc, sh_s[w]); }
+  const double tol = 0x1.0p-36 * sc;
+  const int it = (M + PS_THREADS - 1) / PS_THREADS;          // <= 64 (M <= 65536): at most PS_THREADS groups
+  for (int i0 = 0; i0 < 64; i0 += PS_BATCH) {
+    double v[PS_BATCH];
+#pragma unroll
+    for (int k = 0; k < PS_BATCH; ++k) {
+      const int c = ((i0 + k) * NW + wave) * 64 + lane;
+      v[k] = (i0 + k < it && c < M) ? s_hi[c] : -INFINITY;   // (beyond M: never kept -- b is finite wherever that matters)
+    }
+#pragma unroll
+    for (int k = 0; k < PS_BATCH; ++k) {
+      const int c = ((i0 + k) * NW + wave) * 64 + lane;
+      const unsigned long long bal = __ballot(c < M && i0 + k < it && !(v[k] + tol < b));
+      if (lane == 0) masks[(i0 + k) * NW + wave] = bal;
+    }
+  }
+  __syncthreads();
+  const int cnt = __popcll(masks[threadIdx.x]);
+  int incl = cnt;                                            // inclusive scan over the wavefront's 64 groups
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int v = __shfl_up(incl, o, 64);
+    if (lane >= o) incl += v;
+  }
+  if (lane == 63) sh_cnt[wave] = incl;
+  __syncthreads();
+  int base = 0, total = 0;
+  for (int w = 0; w < NW; ++w) { if (w < wave) base += sh_cnt[w]; total += sh_cnt[w]; }
+  excl[threadIdx.x] = base + incl - cnt;
+  const bool pruned = fabs(b) < INFINITY && total > 0 && total <= n_cap;
+  if (threadIdx.x == 0) {
+    plan->pruned = pruned ? 1 : 0;
+    plan->n_surv = total;
+    report[0] = b;
+    report[1] = tol;
+  }
+  if (!pruned) return;
+  __syncthreads();
+  const unsigned long long below = (1ull << lane) - 1ull;
+  for (int i = 0; i < it; ++i) {
+    const int g = i * NW + wave;
+    const unsigned long long bal = masks[g];
+    if ((bal >> lane) & 1ull) idx[excl[g] + __popcll(bal & below)] = g * 64 + lane;
+  }
+}
+
+// Kc[r][j] = Kt[r][idx[j]] for the rows [r_beg, Nk) that the contraction reads and the survivors j < n_surv of a pruned
+// plan; the columns of a tile beyond n_surv keep whatever they held (a column feeds only its own, unread, output)
+constexpr int GA_ROWS = 16;
+__global__ __launch_bounds__(128) void prune_gather_kernel(const double* __restrict__ Kt, int ldk, int r_beg, int Nk,
+                                                           const PrunePlan* __restrict__ plan, const int* __restrict__ idx,
+                                                           double* __restrict__ Kc, int n_cap) {
+  if (!uniform_load_int(&plan->pruned)) return;
+  const int n = uniform_load_int(&plan->n_surv);
+  if ((int)blockIdx.x * 128 >= n) return;
+  const int j = blockIdx.x * 128 + threadIdx.x;
+  if (j >= n) return;
+  const int c = idx[j];
+  const int r0 = r_beg + blockIdx.y * GA_ROWS;
+  double v[GA_ROWS];                       // (every load of the lane in flight at once)
+#pragma unroll
+  for (int k = 0; k < GA_ROWS; ++k) v[k] = r0 + k < Nk ? Kt[(size_t)(r0 + k) * ldk + c] : 0.0;
+#pragma unroll
+  for (int k = 0; k < GA_ROWS; ++k)
+    if (r0 + k < Nk) Kc[(size_t)(r0 + k) * n_cap + j] = v[k];
+}
+
+// what ppbo_predict_prune_report asks predict_passes to leave behind (device arrays of one chunk; any may be NULL)
+struct PruneReport {
+  double *d_u2 = nullptr, *d_s_lo = nullptr, *d_s_hi = nullptr;
+  const PrunePlan* d_plan = nullptr;       // out: the chunk's plan and (threshold, tol), in the ctx's workspace
+  const double* d_thr = nullptr;
+};
+
 int check_model(ppbo_ctx* ctx, const ppbo_model* m) {
   PPBO_REQUIRE(ctx, m != nullptr, "model");
   PPBO_REQUIRE(ctx, m->d_X && m->d_alpha, "model X/alpha");
@@ -2640,7 +2911,8 @@ static int predict_passes(ppbo_ctx* ctx, const ppbo_model* model, const double* 
                           double mustar, double* d_mu, double* d_var, double* d_score, bool want_best,
                           double* d_record, int64_t record_offset, Best** chunk_best_out, int* n_chunks_out,
                           hipStream_t s, unsigned long long* publish = nullptr, unsigned long long epoch = 0,
-                          const PredictChunkHook* after_chunk = nullptr, const ppbo_var_projection* proj = nullptr) {
+                          const PredictChunkHook* after_chunk = nullptr, const ppbo_var_projection* proj = nullptr,
+                          PruneReport* report = nullptr) {
   if (int rc = check_model(ctx, model)) return rc;
   PPBO_REQUIRE(ctx, d_Xc != nullptr && M > 0, "candidates");
   // a projected operator (ppbo_var_projection_build): rows == 0 or NULL = none, today's launches.  One with rows must
@@ -2662,6 +2934,13 @@ static int predict_passes(ppbo_ctx* ctx, const ppbo_model* model, const double* 
   const int N = model->N, mblk = model->m + 1, n_q = N / mblk;
   // an edge-form operator is always contracted by the three-launch form (the one-launch kernel reads node-form G)
   const int edge_k0 = (want_var && model->form == PPBO_FORM_EDGE) ? ppbo_edge_k0(n_q) : -1;
+  // the pruned search (above): the best record only, an edge-form operator on the three-launch path, a score that does
+  // not decrease in the variance, fp64 K*.  Every other call enqueues today's launches.
+  const bool prune = (ctx->prune || report) && want_best && !d_mu && !d_var && !d_score && !after_chunk && edge_k0 >= 0 &&
+                     !ppbo_fused_eligible(ctx, model) && !model->kstar_fp32 &&
+                     (score_kind == PPBO_SCORE_POINTWISE_EI || score_kind == PPBO_SCORE_VARIANCE);
+  PPBO_REQUIRE(ctx, !report || (prune && M <= 65536),
+               "the prune report takes one chunk of an edge-form model on the three-launch path, pointwise EI or VARIANCE");
   if (ppbo_fused_eligible(ctx, model)) {
     // Models of up to 1024 rows: ONE launch forms K* in LDS, contracts it with G on the matrix cores and scores
     // (fused.hip) -- no K* in HBM, no slab pass, no candidate chunks -- then the one-workgroup argmax.  The choice
@@ -2726,10 +3005,34 @@ static int predict_passes(ppbo_ctx* ctx, const ppbo_model* model, const double* 
     if (!Kt) return (int)hipErrorOutOfMemory;
     if (Nk != N) PPBO_HIP_CHECK(ctx, hipMemsetAsync(Kt + (size_t)N * ldk, 0, (size_t)(Nk - N) * ldk * sizeof(double), s));
   }
-  const size_t part_doubles = (size_t)(2 * n_split_eff + ntm) * Mc_max;
+  // the survivor capacity of a pruned chunk: an eighth of the chunk in whole 128-column tiles (PPBO_PRUNE_CAP: tests)
+  int n_cap = ((ctx->prune_cap > 0 ? ctx->prune_cap : Mc_max / 8) / 128) * 128;
+  if (n_cap < 128) n_cap = 128;
+  // (the compact launch's slabs, row stride n_cap, share the full launch's: one of the two writes them)
+  const size_t part_doubles = (size_t)2 * n_split_eff * Mc_max + (size_t)ntm * ((prune && n_cap > Mc_max) ? n_cap : Mc_max);
   double* part = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_PART, part_doubles * sizeof(double));
   if (!part) return (int)hipErrorOutOfMemory;
   const int sblocks_max = score_blocks(Mc_max);
+  // the pruned search's own arrays: u_part [n_split][Mc], s_hi [Mc], sig [n_q], per score workgroup (max s_lo, scale),
+  // (threshold, tol), then idx [n_cap] and the plan; the gathered columns Kc [Nk][n_cap]
+  double *u_part = nullptr, *s_hi = nullptr, *sig = nullptr, *blk_lo = nullptr, *blk_scale = nullptr, *thr = nullptr, *Kc = nullptr;
+  int* sidx = nullptr;
+  PrunePlan* plan = nullptr;
+  if (prune) {
+    const size_t nd = (size_t)(n_split_eff + 1) * Mc_max + n_q + 2 * (size_t)sblocks_max + 2;
+    char* pw = (char*)ppbo_workspace(ctx, ppbo_ctx::WS_PRUNE, nd * sizeof(double) + (size_t)(n_cap + 2) * sizeof(int));
+    Kc = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_PRUNE_KC, (size_t)Nk * n_cap * sizeof(double));
+    if (!pw || !Kc) return (int)hipErrorOutOfMemory;
+    u_part = (double*)pw;
+    s_hi = u_part + (size_t)n_split_eff * Mc_max;
+    sig = s_hi + Mc_max;
+    blk_lo = sig + n_q;
+    blk_scale = blk_lo + sblocks_max;
+    thr = blk_scale + sblocks_max;
+    sidx = (int*)(thr + 2);
+    plan = (PrunePlan*)(sidx + n_cap);
+    if (report) { report->d_plan = plan; report->d_thr = thr; }
+  }
   Best* bests = (Best*)ppbo_workspace(ctx, ppbo_ctx::WS_SMALL, (size_t)(sblocks_max + n_chunks) * sizeof(Best));
   if (!bests) return (int)hipErrorOutOfMemory;
   Best* chunk_best = bests + sblocks_max;
@@ -2745,20 +3048,44 @@ static int predict_passes(ppbo_ctx* ctx, const ppbo_model* model, const double* 
       bool oom = false;
       const double* geo = star_geometry(ctx, model, s, &oom);
       if (oom) return (int)hipErrorOutOfMemory;
-      dispatch_kstar(model, xc, Mc, Kt, ldk, mu_part, t_part, q_per_split, n_split_eff, want_var, s, edge_k0, geo);
+      if (prune) block_norm_kernel<<<n_q, BN_THREADS, 0, s>>>(Gq, g_rows, Nk, n_q, mblk - 1, sig);
+      dispatch_kstar(model, xc, Mc, Kt, ldk, mu_part, t_part, q_per_split, n_split_eff, want_var, s, edge_k0, geo,
+                     prune ? sig : nullptr, u_part);
     }
     PPBO_LAUNCH_CHECK(ctx);
+    const int sblocks = score_blocks(Mc);
+    const double sf2 = model->theta[2] * model->theta[2];
+    if (prune) {
+      PpboProfScope pf(ctx, ppbo_ctx::PF_QUADFORM, s);
+      prune_bounds_kernel<<<sblocks, SC_THREADS, 0, s>>>(mu_part, n_split_eff, t_part, u_part, Mc, sf2, score_kind, mustar,
+                                                         s_hi, blk_lo, blk_scale, report ? report->d_u2 : nullptr,
+                                                         report ? report->d_s_lo : nullptr, report ? report->d_s_hi : nullptr);
+      prune_select_kernel<<<1, PS_THREADS, 0, s>>>(s_hi, Mc, blk_lo, blk_scale, sblocks, n_cap, sidx, plan, thr);
+      prune_gather_kernel<<<dim3(n_cap / 128, (Nk - edge_k0 + GA_ROWS - 1) / GA_ROWS), 128, 0, s>>>(Kt, ldk, edge_k0, Nk, plan,
+                                                                                                    sidx, Kc, n_cap);
+      PPBO_LAUNCH_CHECK(ctx);
+      // the compact launch (runs when the plan is pruned), then today's (runs when it is not)
+      if (int rc = dispatch_quadform(ctx, Gq, Nk, g_rows, proj ? g_rows : N, Kc, n_cap, n_cap, mblk, slab, edge_k0, s,
+                                     proj != nullptr, plan, 1))
+        return rc;
+      if (int rc = dispatch_quadform(ctx, Gq, Nk, g_rows, proj ? g_rows : N, Kt, ldk, Mc, mblk, slab, edge_k0, s,
+                                     proj != nullptr, plan, 0))
+        return rc;
+    } else
     if (want_var) {
       PpboProfScope pf(ctx, ppbo_ctx::PF_QUADFORM, s);
       if (int rc = dispatch_quadform(ctx, Gq, Nk, g_rows, proj ? g_rows : N, Kt, ldk, Mc, mblk, slab, edge_k0, s, proj != nullptr))
         return rc;
     }
-    const int sblocks = score_blocks(Mc);
     std::optional<PpboProfScope> pfs;          // (ends before after_chunk's launches)
     pfs.emplace(ctx, ppbo_ctx::PF_SCORE, s);
     const bool one = (n_chunks == 1);
+    if (prune)
+      score_plan_kernel<<<sblocks, SC_THREADS, 0, s>>>(mu_part, n_split_eff, t_part, slab, ntm, Mc, sf2, score_kind, mustar,
+                                                       (long long)c_beg, bests, plan, sidx, n_cap);
+    else
     score_kernel<<<sblocks, SC_THREADS, 0, s>>>(mu_part, n_split_eff, t_part, want_var ? slab : nullptr, ntm, Mc,
-                                                model->theta[2] * model->theta[2], score_kind, mustar,
+                                                sf2, score_kind, mustar,
                                                 (long long)c_beg, d_mu ? d_mu + c_beg : nullptr,
                                                 d_var ? d_var + c_beg : nullptr, d_score ? d_score + c_beg : nullptr,
                                                 want_best ? bests : nullptr);
@@ -2825,6 +3152,32 @@ int ppbo_predict_record_p(ppbo_ctx* ctx, const ppbo_model* model, const double* 
   int n_chunks = 0;
   return predict_passes(ctx, model, d_Xc, M, score_kind, mustar, nullptr, nullptr, nullptr, true, d_record,
                         index_offset, &chunk_best, &n_chunks, (hipStream_t)stream, nullptr, 0, nullptr, proj);
+}
+
+int ppbo_predict_prune_report(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc, int64_t M, int score_kind,
+                              double mustar, const ppbo_var_projection* proj, double* d_u2, double* d_s_lo, double* d_s_hi,
+                              double* h_threshold, int* h_n_surv, int* h_pruned, void* stream) {
+  PPBO_ENTER(ctx);
+  hipStream_t s = (hipStream_t)stream;
+  Best* chunk_best = nullptr;
+  int n_chunks = 0;
+  PruneReport rep;
+  rep.d_u2 = d_u2; rep.d_s_lo = d_s_lo; rep.d_s_hi = d_s_hi;
+  PpboHostRecord hr;
+  if (int rc = ppbo_host_record(ctx, &hr)) return rc;
+  if (int rc = predict_passes(ctx, model, d_Xc, M, score_kind, mustar, nullptr, nullptr, nullptr, true, hr.d_rec, 0,
+                              &chunk_best, &n_chunks, s, hr.d_flag, hr.epoch, nullptr, proj, &rep))
+    return rc;
+  if (int rc = ppbo_host_record_wait(ctx, hr, s)) return rc;
+  PrunePlan pl{0, 0};
+  double thr[2] = {0.0, 0.0};
+  PPBO_HIP_CHECK(ctx, hipMemcpyAsync(&pl, rep.d_plan, sizeof(pl), hipMemcpyDeviceToHost, s));
+  PPBO_HIP_CHECK(ctx, hipMemcpyAsync(thr, rep.d_thr, sizeof(thr), hipMemcpyDeviceToHost, s));
+  PPBO_HIP_CHECK(ctx, hipStreamSynchronize(s));
+  if (h_threshold) *h_threshold = thr[0];
+  if (h_n_surv) *h_n_surv = pl.n_surv;
+  if (h_pruned) *h_pruned = pl.pruned;
+  return 0;
 }
 
 // Duels and slopes: two [M, D] point sets per column -- the sides (a, b) of a duel, or the point and the direction

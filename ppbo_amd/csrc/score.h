@@ -49,21 +49,62 @@ __device__ __forceinline__ Best block_best(Best b, Best* sh) {
 constexpr int SC_CAND = 64, SC_WAVES = 16, SC_THREADS = SC_CAND * SC_WAVES;
 static inline int score_blocks(long long M) { return (int)((M + SC_CAND - 1) / SC_CAND); }
 
-__global__ __launch_bounds__(SC_THREADS) void score_kernel(const double* __restrict__ mu_part, int n_mu,
-                                                           const double* __restrict__ t_part,
-                                                           const double* __restrict__ slab, int n_slab, int M,
-                                                           double sf2, int kind, double mustar, long long idx_base,
-                                                           double* __restrict__ mu_out, double* __restrict__ var_out,
-                                                           double* __restrict__ score_out, Best* __restrict__ blk_best) {
+// the score of a candidate from its mean and variance: score_kernel's expression, shared with the bounds of the pruned
+// search (prune_bounds_kernel evaluates it at the two ends of a variance interval)
+__device__ __forceinline__ double score_value(double mu, double var, int kind, double mustar) {
+  double sc;
+  if (mu != mu) sc = mu;                 // a NaN mean (kstar_kernel: a candidate with a non-finite coordinate) never scores
+  else if (kind == PPBO_SCORE_MEAN) sc = mu;
+  else if (kind == PPBO_SCORE_VARIANCE) sc = var;
+  else {
+    const double d = mu - mustar;
+    const double sd = sqrt(fmax(var, 0.0));
+    if (sd > 0.0) {
+      const double z = d / sd;
+      sc = d * norm_cdf(z) + sd * 0.39894228040143267794 * exp(-0.5 * z * z);
+    } else sc = fmax(d, 0.0);
+  }
+  return sc;
+}
+
+// The plan of a pruned search chunk (prune_select_kernel writes it, the launches behind it read it): pruned = 1: only
+// the n_surv candidates idx[0 .. n_surv), ascending, can hold the chunk's argmax and only they are contracted, in
+// compact columns; pruned = 0: every launch does what it does without a plan.
+struct PrunePlan {
+  int pruned, n_surv;
+};
+__device__ __forceinline__ int uniform_load_int(const int* p) {
+  return *reinterpret_cast<const __attribute__((address_space(4))) int*>(reinterpret_cast<uintptr_t>(p));
+}
+
+// PLAN: with a pruned plan column j = the compact position: the partial sums of candidate idx[j], the slab of column j
+// (row stride n_cap, the compact launch's), the reported index that of the candidate; columns from n_surv on are
+// empty.  With pruned = 0, and without PLAN, today's pass over all M candidates.
+template <bool PLAN>
+__device__ __forceinline__ void score_body(const double* __restrict__ mu_part, int n_mu,
+                                           const double* __restrict__ t_part,
+                                           const double* __restrict__ slab, int n_slab, int M,
+                                           double sf2, int kind, double mustar, long long idx_base,
+                                           double* __restrict__ mu_out, double* __restrict__ var_out,
+                                           double* __restrict__ score_out, Best* __restrict__ blk_best,
+                                           const PrunePlan* __restrict__ plan, const int* __restrict__ idx, int n_cap) {
   __shared__ double part[3][SC_WAVES][SC_CAND];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int c = blockIdx.x * SC_CAND + lane;
+  int c = blockIdx.x * SC_CAND + lane;   // the candidate
+  int j = c, ncol = M, lds = M;          // its slab column, the number of columns, the slab's row stride
+  if constexpr (PLAN) {
+    if (uniform_load_int(&plan->pruned)) {
+      ncol = uniform_load_int(&plan->n_surv);
+      lds = n_cap;
+      if (j < ncol) c = idx[j];
+    }
+  }
   double pm = 0.0, pt = 0.0, pq = 0.0;
-  if (c < M) {
+  if (j < ncol) {
     for (int s = wave; s < n_mu; s += SC_WAVES) pm += mu_part[(size_t)s * M + c];
     if (slab) {
       for (int s = wave; s < n_mu; s += SC_WAVES) pt += t_part[(size_t)s * M + c];
-      for (int s = wave; s < n_slab; s += SC_WAVES) pq += slab[(size_t)s * M + c];
+      for (int s = wave; s < n_slab; s += SC_WAVES) pq += slab[(size_t)s * lds + j];
     }
   }
   part[0][wave][lane] = pm;
@@ -72,23 +113,12 @@ __global__ __launch_bounds__(SC_THREADS) void score_kernel(const double* __restr
   __syncthreads();
   if (wave != 0) return;                 // the rest is one wavefront's work
   Best b{0.0, -1};
-  if (c < M) {
+  if (j < ncol) {
     double mu = 0.0, t = 0.0, q = 0.0;
 #pragma unroll
     for (int w = 0; w < SC_WAVES; ++w) { mu += part[0][w][lane]; t += part[1][w][lane]; q += part[2][w][lane]; }
     const double var = slab ? sf2 + t + q : sf2;
-    double sc;
-    if (mu != mu) sc = mu;                 // a NaN mean (kstar_kernel: a candidate with a non-finite coordinate) never scores
-    else if (kind == PPBO_SCORE_MEAN) sc = mu;
-    else if (kind == PPBO_SCORE_VARIANCE) sc = var;
-    else {
-      const double d = mu - mustar;
-      const double sd = sqrt(fmax(var, 0.0));
-      if (sd > 0.0) {
-        const double z = d / sd;
-        sc = d * norm_cdf(z) + sd * 0.39894228040143267794 * exp(-0.5 * z * z);
-      } else sc = fmax(d, 0.0);
-    }
+    const double sc = score_value(mu, var, kind, mustar);
     if (mu_out) mu_out[c] = mu;
     if (var_out) var_out[c] = var;
     if (score_out) score_out[c] = sc;
@@ -103,6 +133,27 @@ __global__ __launch_bounds__(SC_THREADS) void score_kernel(const double* __restr
     b = best_merge(b, other);
   }
   if (lane == 0) blk_best[blockIdx.x] = b;
+}
+
+__global__ __launch_bounds__(SC_THREADS) void score_kernel(const double* __restrict__ mu_part, int n_mu,
+                                                           const double* __restrict__ t_part,
+                                                           const double* __restrict__ slab, int n_slab, int M,
+                                                           double sf2, int kind, double mustar, long long idx_base,
+                                                           double* __restrict__ mu_out, double* __restrict__ var_out,
+                                                           double* __restrict__ score_out, Best* __restrict__ blk_best) {
+  score_body<false>(mu_part, n_mu, t_part, slab, n_slab, M, sf2, kind, mustar, idx_base, mu_out, var_out, score_out,
+                    blk_best, nullptr, nullptr, 0);
+}
+// score_kernel with a plan (the pruned search: the best only, no per-candidate output)
+__global__ __launch_bounds__(SC_THREADS) void score_plan_kernel(const double* __restrict__ mu_part, int n_mu,
+                                                                const double* __restrict__ t_part,
+                                                                const double* __restrict__ slab, int n_slab, int M,
+                                                                double sf2, int kind, double mustar, long long idx_base,
+                                                                Best* __restrict__ blk_best,
+                                                                const PrunePlan* __restrict__ plan,
+                                                                const int* __restrict__ idx, int n_cap) {
+  score_body<true>(mu_part, n_mu, t_part, slab, n_slab, M, sf2, kind, mustar, idx_base, nullptr, nullptr, nullptr,
+                   blk_best, plan, idx, n_cap);
 }
 
 // 1 - k(a, b) / sigma_f^2 from s, the summed kern_term<KID> of the DIRECT differences a - b, in a form that does not

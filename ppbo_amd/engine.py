@@ -466,6 +466,21 @@ class Engine:
         self._check(rc, "ppbo_predict_record")
         return rec
 
+    def prune_report(self, post, Xc, score, mustar=0.0, projection=None):
+        """What the pruned search decides for one chunk of candidates (ppbo_predict_prune_report; at most 65536 rows, an
+        edge-form posterior on the three-launch path, SCORE_POINTWISE_EI or SCORE_VARIANCE): device tensors u2 (>= the
+        contraction's sum of squares), s_lo, s_hi per candidate, and threshold, n_surv, pruned."""
+        Xc = self._points(post, self.dev(Xc))
+        M = Xc.shape[0]
+        md = self._model(post, True)
+        u2, lo, hi = self.empty(M), self.empty(M), self.empty(M)
+        thr, ns, pr = C.c_double(0.0), C.c_int(0), C.c_int(0)
+        rc = self.lib.ppbo_predict_prune_report(self.ctx, C.byref(md), _ptr(Xc), M, int(score), float(mustar),
+                                                projection.ref if projection is not None else None, _ptr(u2), _ptr(lo),
+                                                _ptr(hi), C.byref(thr), C.byref(ns), C.byref(pr), self._stream())
+        self._check(rc, "ppbo_predict_prune_report")
+        return dict(u2=u2, s_lo=lo, s_hi=hi, threshold=thr.value, n_surv=ns.value, pruned=pr.value)
+
     def search_sharded(self, post, Xc, score=SCORE_MEAN, mustar=0.0, index_offset=0, kstar_fp32=False):
         """One whole sharded search step in ONE library call (ppbo_search_sharded): score this rank's rows, RCCL
         all-gather of the 16-byte records (when dist_init has run on this ctx), reduction, one read-back.  Not for a
