@@ -595,6 +595,45 @@ PPBO_API int ppbo_predict_tournament(ppbo_ctx* ctx, const ppbo_model* model, con
                         double* d_var_b, double* d_cov, double* d_prob, double* d_score, double* h_best_val,
                         int64_t* h_best_idx, void* stream);
 
+/* ---- shortlists: q candidates picked greedily under the conditioned variance (no reference counterpart) ----------------
+ * "The q configurations worth showing next": the producer of the point sets that the choice, ranking and tournament
+ * predictions consume.  The q best values of ppbo_predict's d_score ignore the posterior correlation (q neighbours of one
+ * basin); this entry conditions the GP on every pick before it takes the next (kriging believer / pivoted Cholesky).
+ * Conditioning on "f(p) observed with noise tau^2 = noise_var" leaves the mean unchanged and subtracts a rank-one term
+ * from the variance.  With mu, var_0 exactly ppbo_predict's for the same rows (the same launches, bit for bit), for
+ * j = 0 .. q - 1:
+ *   p_j        = the FIRST index of the largest score(mu[c], var_j[c]) over the candidates not picked yet (score_kind and
+ *                mustar as in ppbo_predict); NaN never wins, and a picked index never scores again whatever tau is
+ *   c_j[c]     = cov_{j-1}(c, p_j) = k(c, p_j) + k_c' u_{p_j} - sum_{i<j} V_i[c] V_i[p_j],  u_b = (Lambda + M'M) k_b  (the
+ *                tournament's bilinear form; the prior term k(c, p_j) from direct differences, as in its epilogue)
+ *   V_j[c]     = c_j[c] / sqrt(var_j[p_j] + tau^2);  V_j = 0 where that denominator is 0 (tau = 0, a zero-variance pick)
+ *   var_j+1[c] = max(var_j[c] - V_j[c]^2, 0)
+ * d_Xc [M, D]: the candidates in the MODEL's coordinates, as ppbo_predict_tournament takes its sets.
+ * h_idx [q] = p_j and h_score [q] (may be NULL) = its score at the time of the pick; once nothing scoreable is left
+ * (M < q, NaN rows) the remaining entries are (-1, NaN).  d_mu, d_var, d_var_cond [M], each may be NULL: mu, var_0 and
+ * var_q.  A candidate with a non-finite coordinate has NaN mu, var and var_cond, is never picked and disturbs no other row.
+ * score_kind: PPBO_SCORE_POINTWISE_EI or PPBO_SCORE_VARIANCE; PPBO_SCORE_MEAN is refused (the mean does not change under
+ * this conditioning, so its shortlist is the q best values of d_score).
+ * Stages: ppbo_predict's launches (mu, var_0, pick 0), then per pick a gather of the pick's row, its var_j and its
+ * V_i[p_j] from the device-resident record, the tournament's field pass on that ONE row (O(N^2)), and ONE streaming pass
+ * over the candidates' K* (batch_step_kernel: an M x N matrix-vector product, the downdate with the q x M doubles of
+ * V, the new score and the block bests), then the one-workgroup argmax.  The whole loop is enqueued; the host waits once,
+ * at the end, for one copy of the q records.  All reductions run in a fixed order without floating-point atomics: a
+ * repeated call is bitwise equal.
+ * Cost: M <= 65536 reuses the K* workspace that ppbo_predict's launches left (8 N M bytes read per pick; behind the
+ * one-launch scoring path one K* launch of this entry's own forms it).  Above that every chunk's K* is formed AGAIN per
+ * pick, into a workspace of this entry's own: q K* passes over all M candidates on top of the reads.  The workspace of
+ * V is 8 q M bytes.  Without d_var_cond the last pick's pass is skipped (nobody reads var_q).
+ * "invalid argument", with nothing launched: a NULL model, d_Xc or h_idx; M outside 1 .. 2^31 - 1; q outside
+ * 1 .. PPBO_BATCH_MAX_Q; noise_var negative or not finite (a huge finite value is allowed: nothing is conditioned, the
+ * picks are the q best scores in index order); a score_kind other than EI or VARIANCE; model->kstar_fp32 set (fp64 only);
+ * a model without d_G or Lambda; a form outside {PPBO_FORM_NODE, PPBO_FORM_EDGE}.
+ * The streaming passes are timed as "batch_step", the gathers and field passes as "batch_field" (ppbo_profile_read). */
+#define PPBO_BATCH_MAX_Q 64
+PPBO_API int ppbo_search_batch(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc, int64_t M, int score_kind,
+                        double mustar, double noise_var, int q, int64_t* h_idx, double* h_score, double* d_mu,
+                        double* d_var, double* d_var_cond, void* stream);
+
 /* full predictive covariance of small sets (the G=70 line grid of EI):
  * d_cov[M,M] = (1-s)K(Xc,Xc) + s sigma_f^2 I - K*^T A K*  (src/gp_model.py:447-450) */
 PPBO_API int ppbo_predict_cov(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc, int M,

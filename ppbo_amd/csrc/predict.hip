@@ -1923,6 +1923,126 @@ int launch_tournament(ppbo_ctx* ctx, const double* Kt, int ldk, const double* U,
   return 0;
 }
 
+// ---- shortlists (ppbo_search_batch): q greedy picks under the conditioned variance ------------------------------------
+// Conditioning on "f(p_j) observed with noise tau^2" leaves the mean and subtracts a rank-one term from the variance:
+//   c_j[c] = cov_{j-1}(c, p_j) = k(c, p_j) + k_c' u_{p_j} - sum_{i<j} V_i[c] V_i[p_j],   V_j = c_j / sqrt(var_j[p_j] + tau^2),
+//   var_{j+1} = max(var_j - V_j^2, 0)
+// (the pivoted-Cholesky / kriging-believer rule).  Per pick: batch_gather_kernel reads the device-resident record of the
+// pick, the field pass of the tournament forms u_{p_j} for that ONE opponent, batch_ucol_kernel packs its column, and
+// batch_step_kernel streams the candidates' K* workspace once.
+
+// the pick's record (value, index as a double; (NaN, -1) = nothing left to pick) -> picks[j], the pick's row xp [D], the
+// earlier columns at the pick vp[i] = V_i[p_j], and pv[0] = sqrt(var_j[p_j] + tau^2), 0 where that is not positive
+__global__ __launch_bounds__(64) void batch_gather_kernel(const double* __restrict__ rec, const double* __restrict__ Xc, int D,
+                                                          const double* __restrict__ var, const double* __restrict__ V,
+                                                          long long M, int j, double noise_var, long long* __restrict__ picks,
+                                                          double* __restrict__ xp, double* __restrict__ vp,
+                                                          double* __restrict__ pv) {
+  const long long pick = (long long)rec[1];
+  const int t = threadIdx.x;
+  if (t == 0) {
+    picks[j] = pick;
+    const double den = pick >= 0 ? var[pick] + noise_var : 0.0;
+    pv[0] = den > 0.0 ? sqrt(den) : 0.0;
+  }
+  for (int d = t; d < D; d += 64) xp[d] = pick >= 0 ? Xc[(size_t)pick * D + d] : 0.0;
+  for (int i = t; i < j; i += 64) vp[i] = pick >= 0 ? V[(size_t)i * M + pick] : 0.0;
+}
+
+// column 0 of the field's U [kext][ldu] as a dense vector: batch_step_kernel reads it through scalar loads
+__global__ __launch_bounds__(256) void batch_ucol_kernel(const double* __restrict__ U, int ldu, int kext, double* __restrict__ uc) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < kext) uc[i] = U[(size_t)i * ldu];
+}
+
+// One greedy step for BS_CAND candidates per workgroup, in score_kernel's geometry doubled along c: a lane owns two adjacent
+// candidates, so every row of Ks [kext][ldk] is read by 16-byte loads in 1-KB runs along c; the K range is split into
+// SC_WAVES contiguous pieces, one per wavefront (u is wave-uniform: scalar loads), BS_UNROLL rows in flight per lane; the
+// wavefront sums meet in LDS and are added in wavefront order.  Wavefronts 0 and 1 then finish 64 candidates each: the prior
+// k(c, p_j) from direct differences, the downdate with V_0 .. V_{j-1}, V_j[c] and var_{j+1}[c], the new score, and the
+// workgroup's best over the candidates that are not picked yet (picks[0 .. j]); NaN never wins.  A pick of -1 (nothing
+// left) leaves var alone.  A NaN variance (a non-finite coordinate) stays NaN: fmax would drop it.
+// Ks is 16-byte aligned and ldk even and at least the grid's BS_CAND columns (the host checks): the columns past Mc are
+// read (whatever they hold) and feed nothing.
+constexpr int BS_CAND = 2 * SC_CAND, BS_UNROLL = 8;
+static inline int batch_blocks(long long M) { return (int)((M + BS_CAND - 1) / BS_CAND); }
+template <int KID>
+__global__ __launch_bounds__(SC_THREADS) void batch_step_kernel(
+    const double* __restrict__ Ks, int ldk, int kext, const double* __restrict__ uc, const double* __restrict__ Xc, int D,
+    KernParams p, int Mc, long long c_beg, long long M, const double* __restrict__ mu, double* __restrict__ var,
+    double* __restrict__ V, int j, const double* __restrict__ vp, const double* __restrict__ pv,
+    const long long* __restrict__ picks, const double* __restrict__ xp, int kind, double mustar, Best* __restrict__ blk_best) {
+  __shared__ double part[SC_WAVES][BS_CAND];
+  __shared__ Best sh[2];
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (picks[j] < 0) {                    // (uniform over the launch)
+    if (threadIdx.x == 0) blk_best[blockIdx.x] = Best{0.0, -1};
+    return;
+  }
+  const int per = (kext + SC_WAVES - 1) / SC_WAVES;
+  const int k0 = wave * per, k1 = (k0 + per < kext) ? k0 + per : kext;
+  const size_t ld2 = (size_t)(ldk >> 1);
+  const double2_t* kp = reinterpret_cast<const double2_t*>(Ks + (size_t)k0 * ldk + (size_t)blockIdx.x * BS_CAND) + lane;
+  double a0 = 0.0, a1 = 0.0;
+  int k = k0;
+  for (; k + BS_UNROLL <= k1; k += BS_UNROLL) {
+    double2_t v[BS_UNROLL];
+#pragma unroll
+    for (int t = 0; t < BS_UNROLL; ++t) v[t] = __builtin_nontemporal_load(kp + (size_t)t * ld2);
+#pragma unroll
+    for (int t = 0; t < BS_UNROLL; ++t) {
+      const double u = uniform_load(uc + k + t);
+      a0 = fma(v[t].x, u, a0);
+      a1 = fma(v[t].y, u, a1);
+    }
+    kp += (size_t)BS_UNROLL * ld2;
+  }
+  for (; k < k1; ++k) {
+    const double2_t v = __builtin_nontemporal_load(kp);
+    const double u = uniform_load(uc + k);
+    a0 = fma(v.x, u, a0);
+    a1 = fma(v.y, u, a1);
+    kp += ld2;
+  }
+  part[wave][2 * lane] = a0;
+  part[wave][2 * lane + 1] = a1;
+  __syncthreads();
+  if (wave < 2) {                        // the rest is two wavefronts' work, a candidate per lane
+    Best b{0.0, -1};
+    const int cl = wave * SC_CAND + lane, c = blockIdx.x * BS_CAND + cl;
+    if (c < Mc) {
+      double dot = 0.0;
+#pragma unroll
+      for (int w = 0; w < SC_WAVES; ++w) dot += part[w][cl];
+      const long long g = c_beg + c;
+      double sq = 0.0;
+      for (int d = 0; d < D; ++d) sq += kern_term<KID>(Xc[(size_t)g * D + d] - uniform_load(xp + d), d, p);
+      double cj = kern_finish<KID>(sq, p) + dot;
+      for (int i = 0; i < j; ++i) cj -= V[(size_t)i * M + g] * uniform_load(vp + i);
+      const double sd = uniform_load(pv);
+      const double vj = sd > 0.0 ? cj / sd : 0.0;
+      V[(size_t)j * M + g] = vj;
+      const double dv = var[g] - vj * vj;
+      const double vn = (dv == dv) ? fmax(dv, 0.0) : dv;
+      var[g] = vn;
+      bool taken = false;
+      for (int i = 0; i <= j; ++i) taken = taken || (picks[i] == g);
+      const double sc = score_value(mu[g], vn, kind, mustar);
+      if (!taken && sc == sc) { b.val = sc; b.idx = g; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      Best other;
+      other.val = __shfl_xor(b.val, o, 64);
+      other.idx = __shfl_xor(b.idx, o, 64);
+      b = best_merge(b, other);
+    }
+    if (lane == 0) sh[wave] = b;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) blk_best[blockIdx.x] = best_merge(sh[0], sh[1]);
+}
+
 // prior block of one line: cov_b[g][h] = (1-s) k(x_g, x_h), diagonal (1-s) sf2 + s sf2  (gp_model.py:447)
 template <int KID>
 __global__ __launch_bounds__(256) void line_prior_kernel(const double* __restrict__ grid, int G, int D,
@@ -3461,6 +3581,38 @@ int ppbo_predict_marginals(ppbo_ctx* ctx, const ppbo_model* model, const ppbo_ma
                         h_best_idx, (hipStream_t)stream, nullptr, &ma);
 }
 
+// The field pass of a tournament: U [NkU][ldu] = u_b = (Lambda + M'M) k_b for the Mb opponents d_Xb, in the row layout of the
+// model's form (see tournament_kernel).  KB, Y, Z: [N][ldu] each; part_b: the mean partials of the field's own K* launch
+// (not read).  Touches no workspace of predict_passes.  ppbo_search_batch runs it per pick with Mb = 1.
+static int tournament_field(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xb, int Mb, int ldu, int NkU, double* KB,
+                            double* Y, double* Z, double* U, double* part_b, int q_per_split_b, int n_split_b_eff,
+                            hipStream_t s) {
+  const int N = model->N, mblk = model->m + 1, n_q = N / mblk;
+  const bool edge = model->form == PPBO_FORM_EDGE;
+  PPBO_HIP_CHECK(ctx, hipMemsetAsync(U, 0, (size_t)NkU * ldu * sizeof(double), s));
+  dispatch_kstar(model, d_Xb, Mb, KB, ldu, part_b, nullptr, q_per_split_b, n_split_b_eff, false, s);
+  PPBO_LAUNCH_CHECK(ctx);
+  GemmArgs y{};
+  y.A = model->d_G; y.lda = N; y.B = KB; y.ldb = ldu; y.C = Y; y.ldc = ldu;
+  y.M = N; y.N = Mb; y.K = N; y.alpha = 1.0; y.beta = 0.0; y.khi_mode = 1; y.tri_block = mblk;
+  if (edge) {
+    edge_apply_kernel<<<dim3((Mb + 127) / 128, N), 128, 0, s>>>(KB, ldu, Mb, mblk, n_q, model->d_lam_off, Z);
+    PPBO_LAUNCH_CHECK(ctx);
+    tournament_delta_kernel<<<dim3((Mb + 127) / 128, N), 128, 0, s>>>(KB, ldu, Mb, mblk, n_q, U);
+    PPBO_LAUNCH_CHECK(ctx);
+    y.B = Z; y.tri_block = 1;    // H lower triangular
+  } else {
+    lam_apply_kernel<<<dim3((Mb + 127) / 128, n_q), 128, 0, s>>>(KB, ldu, N, Mb, mblk, model->d_lam_diag, model->d_lam_off, U);
+    PPBO_LAUNCH_CHECK(ctx);
+  }
+  if (int rc = ppbo_gemm_launch(ctx, y, 0, 0, s)) return rc;       // Y = G K*_B  (H E_B)
+  GemmArgs u{};
+  u.A = model->d_G; u.lda = N; u.B = Y; u.ldb = ldu; u.C = U; u.ldc = ldu;
+  u.M = N; u.N = Mb; u.K = N; u.alpha = 1.0; u.beta = 1.0; u.tri_block = 1;
+  if (int rc = ppbo_gemm_launch(ctx, u, 1, 0, s)) return rc;       // U += G' Y
+  return 0;
+}
+
 // Tournaments: every candidate a_i against every opponent b_j.  Field pass once per call (ppbo_predict's own launches on
 // d_Xb for mu_b / var_b, then K*_B in the node layout -> U, see tournament_kernel), then per chunk of 65536 candidates
 // ppbo_predict's own launches (predict_passes: mu_a, var_a and the chunk's K* workspace) -> tournament_kernel ->
@@ -3529,27 +3681,7 @@ int ppbo_predict_tournament(ppbo_ctx* ctx, const ppbo_model* model, const double
   if (d_var_b) PPBO_HIP_CHECK(ctx, hipMemcpyAsync(d_var_b, var_b, (size_t)Mb * sizeof(double), hipMemcpyDeviceToDevice, s));
   {
     PpboProfScope pf(ctx, ppbo_ctx::PF_TOURNAMENT_FIELD, s);
-    PPBO_HIP_CHECK(ctx, hipMemsetAsync(U, 0, (size_t)NkU * ldu * sizeof(double), s));
-    dispatch_kstar(model, d_Xb, Mb, KB, ldu, part_b, nullptr, q_per_split_b, n_split_b_eff, false, s);
-    PPBO_LAUNCH_CHECK(ctx);
-    GemmArgs y{};
-    y.A = model->d_G; y.lda = N; y.B = KB; y.ldb = ldu; y.C = Y; y.ldc = ldu;
-    y.M = N; y.N = Mb; y.K = N; y.alpha = 1.0; y.beta = 0.0; y.khi_mode = 1; y.tri_block = mblk;
-    if (edge) {
-      edge_apply_kernel<<<dim3((Mb + 127) / 128, N), 128, 0, s>>>(KB, ldu, Mb, mblk, n_q, model->d_lam_off, Z);
-      PPBO_LAUNCH_CHECK(ctx);
-      tournament_delta_kernel<<<dim3((Mb + 127) / 128, N), 128, 0, s>>>(KB, ldu, Mb, mblk, n_q, U);
-      PPBO_LAUNCH_CHECK(ctx);
-      y.B = Z; y.tri_block = 1;    // H lower triangular
-    } else {
-      lam_apply_kernel<<<dim3((Mb + 127) / 128, n_q), 128, 0, s>>>(KB, ldu, N, Mb, mblk, model->d_lam_diag, model->d_lam_off, U);
-      PPBO_LAUNCH_CHECK(ctx);
-    }
-    if (int rc = ppbo_gemm_launch(ctx, y, 0, 0, s)) return rc;       // Y = G K*_B  (H E_B)
-    GemmArgs u{};
-    u.A = model->d_G; u.lda = N; u.B = Y; u.ldb = ldu; u.C = U; u.ldc = ldu;
-    u.M = N; u.N = Mb; u.K = N; u.alpha = 1.0; u.beta = 1.0; u.tri_block = 1;
-    if (int rc = ppbo_gemm_launch(ctx, u, 1, 0, s)) return rc;       // U += G' Y
+    if (int rc = tournament_field(ctx, model, d_Xb, Mb, ldu, NkU, KB, Y, Z, U, part_b, q_per_split_b, n_split_b_eff, s)) return rc;
   }
 
   // ---- the candidates: per chunk behind ppbo_predict's own launches
@@ -3621,6 +3753,167 @@ int ppbo_predict_tournament(ppbo_ctx* ctx, const ppbo_model* model, const double
   if (int rc = ppbo_host_record_wait(ctx, hr, s)) return rc;
   if (h_best_val) *h_best_val = hr.h_rec[0];      // (NaN, -1) when no candidate has a non-NaN score
   if (h_best_idx) *h_best_idx = (int64_t)hr.h_rec[1];
+  return 0;
+}
+
+// Shortlists: q greedy picks under the conditioned variance (batch_step_kernel and its neighbours, above).  ppbo_predict's
+// own launches give mu, var_0 and pick 0; then per pick gather -> field pass on the one gathered row -> one streaming pass
+// over the candidates' K* -> one-workgroup argmax -> record.  One chunk (M <= 65536): the K* workspace predict_passes
+// left (or, behind the one-launch scoring path, one K* launch of this entry's own) serves every pick.  More chunks: every
+// chunk's K* is formed again per pick in a workspace of this entry's own.  Everything is enqueued; the host waits once,
+// for the copy of the q records.
+int ppbo_search_batch(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc, int64_t M, int score_kind, double mustar,
+                      double noise_var, int q, int64_t* h_idx, double* h_score, double* d_mu, double* d_var,
+                      double* d_var_cond, void* stream) {
+  PPBO_ENTER(ctx);
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = check_model(ctx, model)) return rc;
+  PPBO_REQUIRE(ctx, d_Xc != nullptr && h_idx != nullptr, "shortlist (d_Xc / h_idx)");
+  PPBO_REQUIRE(ctx, M >= 1 && M <= (int64_t)0x7fffffff, "candidate count (1 .. 2^31 - 1)");
+  PPBO_REQUIRE(ctx, q >= 1 && q <= PPBO_BATCH_MAX_Q, "q (1 .. PPBO_BATCH_MAX_Q)");
+  PPBO_REQUIRE(ctx, noise_var >= 0.0 && noise_var <= 1.7976931348623157e308, "noise_var (finite, >= 0)");
+  PPBO_REQUIRE(ctx, score_kind == PPBO_SCORE_POINTWISE_EI || score_kind == PPBO_SCORE_VARIANCE,
+               "score_kind (EI or VARIANCE: the mean does not change under this conditioning)");
+  PPBO_REQUIRE(ctx, !model->kstar_fp32, "shortlists are fp64 only (kstar_fp32)");
+  PPBO_REQUIRE(ctx, model->d_G != nullptr, "shortlists need model->d_G");
+  PPBO_REQUIRE(ctx, model->d_lam_diag && model->d_lam_off, "model Lambda");
+  const int N = model->N, D = model->D, mblk = model->m + 1, n_q = N / mblk;
+  const bool edge = model->form == PPBO_FORM_EDGE;
+  const int kshift = edge ? ppbo_edge_k0(n_q) : 0;
+  const KernParams p = make_kern_params(model->kernel_id, model->theta);
+  const int64_t chunk_cap = 65536;
+  const int64_t n_chunks = (M + chunk_cap - 1) / chunk_cap;
+  const int Mc_max = (int)(M < chunk_cap ? M : chunk_cap);
+  const int NkU = (N + BK - 1) & ~(BK - 1);
+  const int ldu = 128;                                  // one opponent, a whole opponent tile
+  const int n_split_b = pick_split(1, n_q);
+  const int q_per_split_b = (n_q + n_split_b - 1) / n_split_b;
+  const int n_split_b_eff = (n_q + q_per_split_b - 1) / q_per_split_b;
+  const int blocks_max = batch_blocks(Mc_max);
+  // the last step only finishes var_q: without d_var_cond nobody reads it
+  const int n_steps = d_var_cond ? q : q - 1;
+  // every workspace of this entry before the first launch (growing one waits for the device)
+  double* U = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_TOURN_U, (size_t)NkU * ldu * sizeof(double));
+  if (!U) return (int)hipErrorOutOfMemory;
+  const size_t f_y = (size_t)N * ldu, f_z = 2 * f_y, f_part = 3 * f_y, f_end = f_part + (size_t)n_split_b_eff;
+  double* fw = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_TOURN_FIELD, f_end * sizeof(double));
+  if (!fw) return (int)hipErrorOutOfMemory;
+  double *KB = fw, *Y = fw + f_y, *Z = fw + f_z, *part_b = fw + f_part;
+  const size_t b_rec = 0, b_picks = b_rec + 2 * (size_t)q, b_xp = b_picks + q, b_vp = b_xp + 64, b_pv = b_vp + PPBO_BATCH_MAX_Q,
+               b_uc = b_pv + 2, b_bests = b_uc + NkU, b_mu = b_bests + 2 * (size_t)(blocks_max + n_chunks),   // (a Best is 16 bytes)
+               b_var = b_mu + (size_t)(d_mu ? 0 : M), b_varw = b_var + (size_t)(d_var ? 0 : M),
+               b_V = b_varw + (size_t)(d_var_cond ? 0 : M), b_end = b_V + (size_t)(n_steps > 0 ? n_steps : 1) * (size_t)M;
+  double* bw = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_BATCH, b_end * sizeof(double));
+  if (!bw) return (int)hipErrorOutOfMemory;
+  double* rec = bw + b_rec;
+  long long* picks = reinterpret_cast<long long*>(bw + b_picks);
+  double *xp = bw + b_xp, *vp = bw + b_vp, *pv = bw + b_pv, *uc = bw + b_uc;
+  Best* bests = reinterpret_cast<Best*>(bw + b_bests);
+  Best* step_best = bests + blocks_max;
+  double* mu = d_mu ? d_mu : bw + b_mu;
+  double* var = d_var ? d_var : bw + b_var;
+  double* varw = d_var_cond ? d_var_cond : bw + b_varw;
+  double* V = bw + b_V;
+  double* hrec = (double*)ppbo_pinned(ctx, (size_t)2 * q * sizeof(double));
+  if (!hrec) return ppbo_set_error(ctx, (int)hipErrorOutOfMemory, "pinned staging");
+
+  // ---- mu, var_0 and pick 0: exactly ppbo_predict's launches; a single chunk's K* workspace stays for the picks
+  const double* Kr = nullptr;
+  int ldk = 0, kext = 0;
+  const PredictChunkHook hook = [&](int64_t, int64_t, const double* Kc, int ldk_c, int Nk_c) -> int {
+    if (Kc && n_chunks == 1) { Kr = Kc + (size_t)kshift * ldk_c; ldk = ldk_c; kext = Nk_c - kshift; }
+    return 0;
+  };
+  Best* chunk_best = nullptr;
+  int nc = 0;
+  if (int rc = predict_passes(ctx, model, d_Xc, M, score_kind, mustar, mu, var, nullptr, true, nullptr, 0, &chunk_best, &nc, s,
+                              nullptr, 0, &hook))
+    return rc;
+  best_record_kernel<<<1, 64, 0, s>>>(chunk_best, nc, 0, rec);
+  PPBO_LAUNCH_CHECK(ctx);
+  if (Kr && kext > NkU - kshift) return ppbo_set_error(ctx, -1, "shortlist: the K* workspace is deeper than the field's U");
+
+  // ---- a K* workspace of this entry's own where predict_passes left none that lasts
+  double *K2 = nullptr, *part2 = nullptr;
+  int n_split_eff = 0, q_per_split = 0;
+  const double* geo = nullptr;
+  if (!Kr && n_steps > 0) {
+    ldk = (Mc_max + 127) & ~127;
+    kext = N - kshift;
+    const int n_split = pick_split(Mc_max, n_q);
+    q_per_split = (n_q + n_split - 1) / n_split;
+    n_split_eff = (n_q + q_per_split - 1) / q_per_split;
+    K2 = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_BATCH_K, ((size_t)NkU * ldk + (size_t)2 * n_split_eff * Mc_max) * sizeof(double));
+    if (!K2) return (int)hipErrorOutOfMemory;
+    part2 = K2 + (size_t)NkU * ldk;
+  }
+  // K* of one chunk in the layout of the model's form (the partial sums of its mean and Lambda term are not read)
+  auto form_kstar = [&](int64_t c_beg, int Mc) -> int {
+    PpboProfScope pf(ctx, ppbo_ctx::PF_KSTAR, s);
+    const double* xc = d_Xc + (size_t)c_beg * D;
+    if (edge) {
+      bool oom = false;
+      geo = star_geometry(ctx, model, s, &oom);
+      if (oom) return (int)hipErrorOutOfMemory;
+      dispatch_kstar(model, xc, Mc, K2, ldk, part2, part2 + (size_t)n_split_eff * Mc, q_per_split, n_split_eff, true, s, kshift, geo);
+    } else {
+      dispatch_kstar(model, xc, Mc, K2, ldk, part2, nullptr, q_per_split, n_split_eff, false, s);
+    }
+    PPBO_LAUNCH_CHECK(ctx);
+    return 0;
+  };
+  if (K2 && n_chunks == 1) {
+    if (int rc = form_kstar(0, Mc_max)) return rc;
+    Kr = K2 + (size_t)kshift * ldk;
+  }
+  if (n_steps > 0) PPBO_HIP_CHECK(ctx, hipMemcpyAsync(varw, var, (size_t)M * sizeof(double), hipMemcpyDeviceToDevice, s));
+
+  // ---- the picks
+  for (int j = 0; j < n_steps; ++j) {
+    {
+      PpboProfScope pf(ctx, ppbo_ctx::PF_BATCH_FIELD, s);
+      batch_gather_kernel<<<1, 64, 0, s>>>(rec + 2 * j, d_Xc, D, varw, V, (long long)M, j, noise_var, picks, xp, vp, pv);
+      PPBO_LAUNCH_CHECK(ctx);
+      if (int rc = tournament_field(ctx, model, xp, 1, ldu, NkU, KB, Y, Z, U, part_b, q_per_split_b, n_split_b_eff, s)) return rc;
+      batch_ucol_kernel<<<(kext + 255) / 256, 256, 0, s>>>(U + (size_t)kshift * ldu, ldu, kext, uc);
+      PPBO_LAUNCH_CHECK(ctx);
+    }
+    for (int64_t ch = 0; ch < n_chunks; ++ch) {
+      const int64_t c_beg = ch * chunk_cap;
+      const int Mc = (int)((M - c_beg) < chunk_cap ? (M - c_beg) : chunk_cap);
+      const double* Ks = Kr;
+      if (n_chunks > 1) {
+        if (int rc = form_kstar(c_beg, Mc)) return rc;
+        Ks = K2 + (size_t)kshift * ldk;
+      }
+      PpboProfScope pf(ctx, ppbo_ctx::PF_BATCH_STEP, s);
+      const int blocks = batch_blocks(Mc);
+      if (ldk % 2 != 0 || ldk < blocks * BS_CAND || (reinterpret_cast<uintptr_t>(Ks) & 15) != 0)
+        return ppbo_set_error(ctx, -1, "shortlist: the K* workspace is not laid out for 16-byte loads");
+      if (int rc = ppbo_kernel_dispatch(ctx, model->kernel_id, [&](auto kid) {
+            constexpr int KID = decltype(kid)::value;
+            batch_step_kernel<KID><<<blocks, SC_THREADS, 0, s>>>(Ks, ldk, kext, uc, d_Xc, D, p, Mc, (long long)c_beg, (long long)M,
+                                                                 mu, varw, V, j, vp, pv, picks, xp, score_kind, mustar, bests);
+            return 0;
+          }))
+        return rc;
+      PPBO_LAUNCH_CHECK(ctx);
+      if (j + 1 < q) {
+        argmax_final_kernel<<<1, 256, 0, s>>>(bests, blocks, step_best + ch);
+        PPBO_LAUNCH_CHECK(ctx);
+      }
+    }
+    if (j + 1 < q) {
+      best_record_kernel<<<1, 64, 0, s>>>(step_best, (int)n_chunks, 0, rec + 2 * (j + 1));
+      PPBO_LAUNCH_CHECK(ctx);
+    }
+  }
+  PPBO_HIP_CHECK(ctx, hipMemcpyAsync(hrec, rec, (size_t)2 * q * sizeof(double), hipMemcpyDeviceToHost, s));
+  PPBO_HIP_CHECK(ctx, hipStreamSynchronize(s));
+  for (int j = 0; j < q; ++j) {
+    h_idx[j] = (int64_t)hrec[2 * j + 1];            // (NaN, -1) from the first pick that found nothing left
+    if (h_score) h_score[j] = hrec[2 * j];
+  }
   return 0;
 }
 

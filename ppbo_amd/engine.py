@@ -16,6 +16,7 @@ from ._lib import CURV_MEAN, CURV_VARIANCE, CURV_PROB  # noqa: F401
 from ._lib import FUNCTIONAL_MEAN, FUNCTIONAL_VARIANCE, FUNCTIONAL_PROB, FUNCTIONAL_MAX_G  # noqa: F401
 from ._lib import EFFECT_RAW, EFFECT_CENTRED, EFFECT_INTERACTION, MARGINAL_MAX_DC  # noqa: F401
 from ._lib import TOURNAMENT_BORDA, TOURNAMENT_WORST, TOURNAMENT_MAX_B  # noqa: F401
+from ._lib import BATCH_MAX_Q  # noqa: F401
 
 # Posterior.form: which variance operator G holds (include/ppbo_hip.h, PPBO_FORM_*)
 FORM_NODE = 0   # G = R Lambda, block lower triangular [N, N]
@@ -1065,6 +1066,40 @@ class Engine:
         self._check(rc, "ppbo_predict_tournament")
         return dict(mu_a=mu_a, var_a=var_a, mu_b=mu_b, var_b=var_b, cov=cov, prob=pr, score=sc, best_val=bv.value,
                     best_idx=bi.value)
+
+    def search_batch(self, post: Posterior, Xc, q, score=SCORE_POINTWISE_EI, mustar=0.0, noise_var=None,
+                     want_var_cond=False):
+        """A shortlist (ppbo_search_batch): q rows of Xc [M, D] (the caller's coordinates) picked greedily, each pick
+        the first row of the largest score -- SCORE_POINTWISE_EI or SCORE_VARIANCE, with mustar as in predict -- under
+        the variance CONDITIONED on the earlier picks observed with noise noise_var (None: theta[0]^2, the model's own
+        noise; 0: exact observations; the mean does not change).  Returns idx [q] int64 and score [q] (NumPy; the score
+        of a pick at its turn; (-1, NaN) once nothing scoreable is left), the device tensors mu, var [M] (bit for bit
+        predict's) and var_cond [M], the variance after all q picks (None unless want_var_cond).  ValueError, before
+        anything reaches the device, for shape errors, q outside 1 .. BATCH_MAX_Q, SCORE_MEAN or an unknown score kind,
+        and a negative or non-finite noise_var."""
+        shape = tuple(np.shape(Xc))
+        D = 6 if post.camphor is not None else post.X.shape[1]
+        if len(shape) != 2 or shape[1] != D or shape[0] < 1:
+            raise ValueError(f"search_batch: candidates of shape {shape}; [M, {D}] with M >= 1 is required")
+        if isinstance(q, bool) or not isinstance(q, (int, np.integer)) or not 1 <= q <= BATCH_MAX_Q:
+            raise ValueError(f"search_batch: q = {q!r}; an integer in 1 .. {BATCH_MAX_Q} is required")
+        if score not in (SCORE_POINTWISE_EI, SCORE_VARIANCE):
+            raise ValueError(f"search_batch: score kind {score!r}; SCORE_POINTWISE_EI or SCORE_VARIANCE is required (the mean "
+                             "does not change under the conditioning)")
+        nv = float(post.theta[0]) ** 2 if noise_var is None else float(noise_var)
+        if not (np.isfinite(nv) and nv >= 0.0):
+            raise ValueError(f"search_batch: noise_var = {noise_var!r}; a finite value >= 0 is required")
+        Xc = self._points(post, Xc)
+        M = Xc.shape[0]
+        md = self._model(post, True)
+        mu, var = self.empty(M), self.empty(M)
+        vc = self.empty(M) if want_var_cond else None
+        idx, sc = (C.c_int64 * int(q))(), (C.c_double * int(q))()
+        rc = self.lib.ppbo_search_batch(self.ctx, C.byref(md), _ptr(Xc), M, int(score), float(mustar), nv, int(q), idx, sc,
+                                        _ptr(mu), _ptr(var), _ptr(vc), self._stream())
+        self._check(rc, "ppbo_search_batch")
+        return dict(idx=np.array(idx[:], dtype=np.int64), score=np.array(sc[:], dtype=np.float64), mu=mu, var=var,
+                    var_cond=vc)
 
     def predict_cov(self, post: Posterior, Xc, shrink=SHRINKAGE):
         Xc = self._points(post, Xc)

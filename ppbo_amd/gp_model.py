@@ -22,8 +22,8 @@ import scipy.optimize
 import torch
 
 from . import kernels as _kernels
-from .engine import (ARD_KERNELS, CAMPHOR_ARD, NotPositiveDefinite, PAIR_MEAN, SCORE_MEAN, get_engine, lengthscales,
-                     theta_key)
+from .engine import (ARD_KERNELS, CAMPHOR_ARD, NotPositiveDefinite, PAIR_MEAN, SCORE_MEAN, SCORE_POINTWISE_EI, SCORE_VARIANCE,
+                     get_engine, lengthscales, theta_key)
 from .feedback_processing import FeedbackProcessing
 
 SEARCH_CANDIDATES = 65536      # uniform candidates per mu_star trial
@@ -1159,6 +1159,32 @@ class GPModel:
         out = self.eng.predict_tournament(post, X, X, want_prob=True, want_best=False)
         borda = out["score"].cpu().numpy()
         return out["prob"].cpu().numpy(), borda, np.argsort(-borda, kind="stable")
+
+    def shortlist(self, q=8, score="EI", X_cand=None, noise_var=None):
+        """(X [q, D], idx [q], score [q]): the q configurations worth showing next, picked greedily by `score` -- "EI"
+        (pointwise expected improvement over self.mustar) or "variance" -- under the posterior variance conditioned on
+        the earlier picks (ppbo_search_batch; no reference counterpart), so the picks spread over the basins instead of
+        crowding the best one.  The producer of the item sets that choice_pred, ranking_pred and tournament_pred
+        consume.  X_cand [M, D]: the candidates in the caller's coordinates; by default the resident candidate pool
+        under a fresh rotation, and idx then indexes those rotated rows.  noise_var: the noise of the imagined
+        observations (None: theta[0]^2; 0: exact).  X comes back in the caller's coordinates; picks that found nothing
+        scoreable left (fewer than q candidates, non-finite rows) are dropped."""
+        kinds = {"EI": SCORE_POINTWISE_EI, "variance": SCORE_VARIANCE}
+        if score not in kinds:
+            raise ValueError(f"shortlist: score {score!r}; \"EI\" or \"variance\" is required")
+        post = self._var_post()
+        if X_cand is None:
+            cand = self.eng.shift_points(self._candidate_pool(), np.random.uniform(0.0, 1.0, self.D))
+        elif isinstance(X_cand, torch.Tensor):
+            cand = self.eng.dev(X_cand if X_cand.dim() == 2 else X_cand.reshape(1, -1))
+        else:
+            cand = self.eng.dev(np.atleast_2d(np.asarray(X_cand, dtype=float)))
+        out = self.eng.search_batch(post, cand, int(q), score=kinds[score],
+                                    mustar=0.0 if self.mustar is None else float(self.mustar), noise_var=noise_var)
+        keep = out["idx"] >= 0
+        idx = out["idx"][keep]
+        X = cand[torch.as_tensor(idx, device=cand.device)].cpu().numpy() if idx.size else np.zeros((0, self.D))
+        return X, idx, out["score"][keep]
 
     def mu_pred(self, X_pred):
         x = np.asarray(X_pred, dtype=float).reshape(1, self.D)
