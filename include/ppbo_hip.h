@@ -420,6 +420,33 @@ PPBO_API int ppbo_predict_slopes(ppbo_ctx* ctx, const ppbo_model* model, const d
                         int score_kind, double* d_mu, double* d_var, double* d_prob, double* d_score,
                         double* h_best_val, int64_t* h_best_idx, void* stream);
 
+/* ---- gradients: mean and D x D covariance of grad f(x) for M points (no reference counterpart) --------------------------
+ * The object the slopes are projections of: grad f(x) ~ N(m(x), C(x)) with xi' m = mu_s and xi' C xi = var_s of
+ * ppbo_predict_slopes for every xi.  With the D columns g_d = d k(x, X) / d x_d of a point (radial kernels:
+ * g_jd = c(r_j^2) (x_d - x_jd), ONE kernel-function evaluation per design row for all D of them)
+ *   m_d  = g_d' alpha
+ *   C_de = P_de + g_d' Lambda g_e + (G g_d)'(G g_e)                   (the operator of ppbo_posterior, bilinear)
+ *   P    = (d^2 k / dx dx')(x, x), unshrunk and diagonal: the prior constant of ppbo_predict_slopes times I for the radial
+ *          kernels, diag(sigma_f^2 (4 pi^2 / l^2, ..., 1 / (l + 0.05)^2 at d = 2, ...)) for camphor-copper
+ * C is symmetric bit for bit.  d_X [M, D]: points in the MODEL's coordinates, as ppbo_predict_slopes takes them.  Outputs,
+ * each may be NULL: d_mean [M, D], d_cov [M, D, D], d_score [M] and h_best_val / h_best_idx, the largest score and its
+ * FIRST index; NaN never wins, (NaN, -1) when nothing scored (PPBO_GRAD_NONE scores nothing).  h_metric: NULL or D positive
+ * weights w_d (host);  PPBO_GRAD_TRACE = sum_d w_d C_dd, PPBO_GRAD_NORM2 = sum_d w_d (m_d^2 + C_dd) = E |grad f|_w^2 (an ARD
+ * caller passes s_d^2 and gets the score in its own coordinates).  A point with a NaN or infinite coordinate gets NaN in
+ * all its outputs; the other points do not see it.  With d_cov == NULL and PPBO_GRAD_NONE the call reads neither d_G nor
+ * Lambda and runs no contraction.  Points go in chunks of 512 (at most 512 x 64 columns, which the workspaces of the line
+ * entries hold for every D) through kstar_grad_kernel (camphor-copper: its direct-difference form), the
+ * Y = G K* product and line_cov_kernel of the line entries with the D columns of a point as one group, and
+ * grad_finish_kernel; both operator forms, the projected operator is not offered.  ppbo_profile_read: "grad_kstar",
+ * "line_y", "line_cov", "grad_finish".
+ * "invalid argument": a NULL model or d_X; M outside 1 .. 2^31 - 1; an unknown score_kind; a metric entry that is not
+ * positive and finite; model->kstar_fp32 set (fp64 only); a model without d_G (or Lambda) when the covariance or a score
+ * is asked for. */
+enum { PPBO_GRAD_NONE = 0, PPBO_GRAD_TRACE = 1, PPBO_GRAD_NORM2 = 2 };
+PPBO_API int ppbo_predict_gradients(ppbo_ctx* ctx, const ppbo_model* model, const double* d_X, int64_t M,
+                        const double* h_metric, int score_kind, double* d_mean, double* d_cov, double* d_score,
+                        double* h_best_val, int64_t* h_best_idx, void* stream);
+
 /* ---- curvatures: mean, variance and sign probability of d^2/da^2 f(gamma(a)) at a = 0 for M rows (no reference counterpart) --
  * The companion of a slope where the slope vanishes: is x a peak along xi, how sharp is it, and how sure is the model.
  * gamma is a path in the MODEL's coordinates with gamma(0) = x, gamma'(0) = xi, gamma''(0) = acc (d_Xa == NULL: straight

@@ -21,6 +21,7 @@ SCORE_MEAN, SCORE_POINTWISE_EI, SCORE_VARIANCE = 0, 1, 2
 PAIR_MEAN, PAIR_VARIANCE, PAIR_PROB = 0, 1, 2      # score kinds of ppbo_predict_pairs (PPBO_PAIR_*)
 SLOPE_MEAN, SLOPE_VARIANCE, SLOPE_PROB = 0, 1, 2   # score kinds of ppbo_predict_slopes (PPBO_SLOPE_*)
 CURV_MEAN, CURV_VARIANCE, CURV_PROB = 0, 1, 2      # score kinds of ppbo_predict_curvatures (PPBO_CURV_*)
+GRAD_NONE, GRAD_TRACE, GRAD_NORM2 = 0, 1, 2        # score kinds of ppbo_predict_gradients (PPBO_GRAD_*)
 FUNCTIONAL_MEAN, FUNCTIONAL_VARIANCE, FUNCTIONAL_PROB = 0, 1, 2   # ... of ppbo_predict_functionals (PPBO_FUNCTIONAL_*)
 FUNCTIONAL_MAX_G = 64                              # points per group (PPBO_FUNCTIONAL_MAX_G)
 EFFECT_RAW, EFFECT_CENTRED, EFFECT_INTERACTION = 0, 1, 2           # effects of ppbo_predict_marginals (PPBO_EFFECT_*)
@@ -135,6 +136,7 @@ SIGNATURES = {
     "ppbo_predict_record": [_vp, C.POINTER(Model), _vp, _i64, _i, _d, _i64, _vp, _vp],
     "ppbo_predict_pairs": [_vp, C.POINTER(Model), _vp, _vp, _i64, _i, _vp, _vp, _vp, _vp, C.POINTER(_d), C.POINTER(_i64), _vp],
     "ppbo_predict_slopes": [_vp, C.POINTER(Model), _vp, _vp, _i64, _i, _vp, _vp, _vp, _vp, C.POINTER(_d), C.POINTER(_i64), _vp],
+    "ppbo_predict_gradients": [_vp, C.POINTER(Model), _vp, _i64, C.POINTER(_d), _i, _vp, _vp, _vp, C.POINTER(_d), C.POINTER(_i64), _vp],
     "ppbo_predict_curvatures": [_vp, C.POINTER(Model), _vp, _vp, _vp, _i64, _i, _vp, _vp, _vp, _vp, C.POINTER(_d), C.POINTER(_i64), _vp],
     "ppbo_predict_functionals": [_vp, C.POINTER(Model), _vp, _vp, _i, _i64, _i, _d, _i, _vp, _vp, _vp, _vp, C.POINTER(_d),
                                  C.POINTER(_i64), _vp],

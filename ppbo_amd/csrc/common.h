@@ -38,7 +38,7 @@ struct ppbo_ctx {
   unsigned upload_next = 0;
   // optional per-kernel event timing
   bool profiling = false;
-  enum { PF_GRAM = 0, PF_KSTAR, PF_QUADFORM, PF_SCORE, PF_RFF_PROJECT, PF_RFF_SCORE, PF_POTRF, PF_LINE_KSTAR, PF_LINE_Y, PF_LINE_COV, PF_LINE_MC, PF_FUSED, PF_TOURNAMENT, PF_TOURNAMENT_FIELD, PF_BATCH_STEP, PF_BATCH_FIELD, PF_COUNT };
+  enum { PF_GRAM = 0, PF_KSTAR, PF_QUADFORM, PF_SCORE, PF_RFF_PROJECT, PF_RFF_SCORE, PF_POTRF, PF_LINE_KSTAR, PF_LINE_Y, PF_LINE_COV, PF_LINE_MC, PF_FUSED, PF_TOURNAMENT, PF_TOURNAMENT_FIELD, PF_BATCH_STEP, PF_BATCH_FIELD, PF_GRAD_KSTAR, PF_GRAD_FINISH, PF_COUNT };
   std::vector<std::pair<hipEvent_t, hipEvent_t>> pf_events[PF_COUNT];
   size_t pf_used[PF_COUNT] = {};
   // kernels whose dynamic-LDS limit has been raised on THIS ctx's device (hipFuncSetAttribute is per device)

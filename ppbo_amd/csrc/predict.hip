@@ -1109,6 +1109,148 @@ __global__ __launch_bounds__(KS_THREADS, (KID != PPBO_KERNEL_CAMPHOR && (DP < 20
   }
 }
 
+// Pass 1 of ppbo_predict_gradients: ALL D columns of a point's gradient, g_jd = d k(x, x_j) / d x_d =
+// c(r_j^2) (x_d - x_jd), from ONE kern_slope_coef per (point, design row) -- the D coordinate slopes of the point share
+// their coefficient, where kstar_slope_kernel on the rows (x, e_d) would evaluate it D times.  One lane = one point, its
+// coordinates and its D running mean sums in registers (two D-vectors per lane, kstar_slope_kernel's budget); the
+// workgroup is ONE wavefront of KG_PTS = 64 points.  The columns go to the node layout at column point D + d, so the 64 D
+// values a wavefront forms for one design row are one contiguous segment of that workspace row.  A lane storing its own D
+// values would scatter 8-byte pieces at a stride of D; instead the row's 64 x D tile is staged in LDS (row stride DP | 1
+// doubles: odd, the lanes of a write land in different banks) and read back in segment order, so that every store
+// instruction of the wavefront writes 512 contiguous bytes.  The kernel is store-bound by construction: D stores per
+// kernel-function evaluation.  The mean partials of a row split leave through the same tile.
+// x - x_j from direct differences (x on a design row gives g_j = 0 exactly).  A point with a non-finite coordinate is
+// taken as the origin here (finite columns: nothing non-finite reaches the contractions behind this pass);
+// grad_finish_kernel finds it again and gives it NaN results.  Launch geometry: kstar_slope_kernel's dimension buckets
+// and row splits (whole stars per split).  fp64 only, no Lambda sums, no edge layout (edge_apply_kernel forms it).
+// camphor-copper (D = 6): g_jd = -k_j ds_j / dx_d in the DIRECT-difference form, not kstar_slope_kernel's feature form: the
+// exponent and the five sines come from sincospi(x_d - x_jd), one per periodic coordinate, so a coordinate that equals
+// the design row's gives g_jd = 0 exactly and an entry of the mean keeps its digits relative to sum_j |g_jd alpha_j|
+// (the feature form's sin a cos b - cos a sin b leaves 1e-16 of k_j there, which is all of an entry when a whole star
+// shares that coordinate).  One exponential per design row for the six columns.
+constexpr int KG_PTS = 64;
+template <int KID, int DP>
+__global__ __launch_bounds__(KG_PTS) void kstar_grad_kernel(const double* __restrict__ X, int N, int D, KernParams p,
+                                                            const double* __restrict__ alpha, int mblk,
+                                                            const double* __restrict__ Xp, int P, double* __restrict__ Kt,
+                                                            int ldk, double* __restrict__ mu_part, int q_per_split) {
+  static_assert(KID != PPBO_KERNEL_CAMPHOR || DP == 6, "camphor-copper: D = 6");
+  constexpr int DS = DP | 1;
+  __shared__ __attribute__((aligned(16))) double xs[KS_RJ * DP];
+  __shared__ double s_alpha[KS_RJ];
+  __shared__ double tile[KG_PTS * DS];
+  const int lane = threadIdx.x;
+  const int p0 = blockIdx.x * KG_PTS;
+  const bool live = p0 + lane < P;
+  double xc[DP], mu[DP];
+  {
+    const double* __restrict__ px = Xp + (size_t)(live ? p0 + lane : 0) * D;
+    double chk = 0.0;
+#pragma unroll
+    for (int d = 0; d < DP; ++d) {
+      xc[d] = (d < D && live) ? px[d] : 0.0;
+      chk = fma(xc[d], 0.0, chk);
+      mu[d] = 0.0;
+    }
+    if (chk != 0.0) {
+#pragma unroll
+      for (int d = 0; d < DP; ++d) xc[d] = 0.0;
+    }
+  }
+  // the segment of this workgroup in a workspace row: nseg values from column p0 D on; lane L reads back its elements
+  // L, L + 64, ... (point pt, dimension dd: stepped without a division per element)
+  const int npts = (P - p0 < KG_PTS) ? (P - p0) : KG_PTS;
+  const int nseg = npts * D;
+  const int q64 = KG_PTS / D, r64 = KG_PTS - q64 * D;
+  const int pt0 = lane / D, dd0 = lane - pt0 * D;
+  const size_t seg0 = (size_t)p0 * D;
+  const int j_beg = blockIdx.y * q_per_split * mblk;
+  int j_end = j_beg + q_per_split * mblk;
+  if (j_end > N) j_end = N;
+  for (int row0 = j_beg; row0 < j_end; row0 += KS_RJ) {
+    __syncthreads();
+    for (int e = lane; e < KS_RJ * DP; e += KG_PTS) {
+      const int r = e / DP, d = e - r * DP;
+      const int j = row0 + r;
+      xs[e] = (j < j_end && d < D) ? X[(size_t)j * D + d] : 0.0;
+    }
+    if (lane < KS_RJ) s_alpha[lane] = (row0 + lane < j_end) ? alpha[row0 + lane] : 0.0;
+    __syncthreads();
+    const int rmax = (j_end - row0 < KS_RJ) ? (j_end - row0) : KS_RJ;
+    for (int r = 0; r < rmax; ++r) {
+      const double* __restrict__ xr = xs + r * DP;
+      const double a = s_alpha[r];
+      if constexpr (KID == PPBO_KERNEL_CAMPHOR) {
+        // b_d = ds_j / dx_d from the direct differences D_d = x_d - x_jd: pi c0 sin(2 pi D_d) = 2 pi c0 sin(pi D_d) cos(pi D_d)
+        // (d = 2: 2 c1 D_2), the exponent from the same sin(pi D_d); g_jd = -k_j b_d
+        double bd[DP], sv = 0.0;
+#pragma unroll
+        for (int d = 0; d < DP; ++d) {
+          const double df = xc[d] - xr[d];
+          if (d == 2) {
+            sv = fma(p.c1 * df, df, sv);
+            bd[d] = (2.0 * p.c1) * df;
+          } else {
+            double sn, cs;
+            sincospi(df, &sn, &cs);
+            sv = fma(p.c0 * sn, sn, sv);
+            bd[d] = (6.28318530717958647692 * p.c0) * (sn * cs);
+          }
+        }
+        double cf = -kern_finish<KID>(sv, p);
+        asm volatile("" : "+v"(cf));
+#pragma unroll
+        for (int d = 0; d < DP; ++d) {
+          const double g = cf * bd[d];
+          mu[d] += a * g;
+          if (Kt) tile[lane * DS + d] = g;
+        }
+      } else {
+        double sv = 0.0;
+#pragma unroll
+        for (int d = 0; d < DP; ++d) {
+          const double df = xc[d] - xr[d];
+          sv = fma(df, df, sv);
+        }
+        double cf = kern_slope_coef<KID>(sv, p);
+        asm volatile("" : "+v"(cf));              // the coefficient as an opaque register: every g_jd is one product
+#pragma unroll
+        for (int d = 0; d < DP; ++d) {
+          const double g = cf * (xc[d] - xr[d]);
+          mu[d] += a * g;
+          if (Kt) tile[lane * DS + d] = g;
+        }
+      }
+      if (Kt) {
+        __syncthreads();
+        double* __restrict__ dst = Kt + (size_t)(row0 + r) * ldk + seg0;
+        int pt = pt0, dd = dd0;
+        for (int e = lane; e < nseg; e += KG_PTS) {
+          store_through(dst + e, tile[pt * DS + dd]);
+          pt += q64;
+          dd += r64;
+          if (dd >= D) { dd -= D; ++pt; }
+        }
+        __syncthreads();
+      }
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int d = 0; d < DP; ++d) tile[lane * DS + d] = mu[d];
+  __syncthreads();
+  {
+    double* __restrict__ dst = mu_part + (size_t)blockIdx.y * P * D + seg0;
+    int pt = pt0, dd = dd0;
+    for (int e = lane; e < nseg; e += KG_PTS) {
+      dst[e] = tile[pt * DS + dd];
+      pt += q64;
+      dd += r64;
+      if (dd >= D) { dd -= D; ++pt; }
+    }
+  }
+}
+
 // The two coefficients of a CURVATURE column at r^2 = s: c = 2 dk/dr^2 (kern_slope_coef's value) and c' = 2 d^2k/d(r^2)^2,
 // both finite at s = 0, from ONE kernel-function evaluation (SE: one exponential; RQ: one reciprocal; Matern-5/2: the
 // exponential of matern_ae, c' = sf2 c0^4 e^-a / 6 -- never a quotient by r).  Matern-3/2 has no second coefficient: its
@@ -2682,6 +2824,30 @@ int launch_kstar_slope(const ppbo_model* m, const KernParams& p, const double* d
   return 0;
 }
 
+// kstar_grad_kernel in the same buckets and row splits: P points, KG_PTS of them per (one-wavefront) workgroup
+template <int KID>
+int launch_kstar_grad(const ppbo_model* m, const KernParams& p, const double* d_X, int P, double* Kt, int ldk,
+                      double* mu_part, int q_per_split, int n_split, hipStream_t s) {
+  dim3 grid((P + KG_PTS - 1) / KG_PTS, n_split);
+  const int mblk = m->m + 1;
+#define KSG_LAUNCH(DP) \
+  kstar_grad_kernel<KID, DP><<<grid, KG_PTS, 0, s>>>(m->d_X, m->N, m->D, p, m->d_alpha, mblk, d_X, P, Kt, ldk, mu_part, q_per_split)
+  if constexpr (KID == PPBO_KERNEL_CAMPHOR) KSG_LAUNCH(6);
+  else if (m->D <= 4) KSG_LAUNCH(4);
+  else if (m->D <= 6) KSG_LAUNCH(6);
+  else if (m->D <= 8) KSG_LAUNCH(8);
+  else if (m->D <= 10) KSG_LAUNCH(10);
+  else if (m->D <= 12) KSG_LAUNCH(12);
+  else if (m->D <= 16) KSG_LAUNCH(16);
+  else if (m->D <= 20) KSG_LAUNCH(20);
+  else if (m->D <= 24) KSG_LAUNCH(24);
+  else if (m->D <= 32) KSG_LAUNCH(32);
+  else if (m->D <= 48) KSG_LAUNCH(48);
+  else KSG_LAUNCH(64);
+#undef KSG_LAUNCH
+  return 0;
+}
+
 // kstar_curv_kernel in the same buckets and geometry: d_X the points, d_Xi the directions, d_Xa the accelerations or
 // nullptr (the caller has refused d_Xa with D > 16 or on the camphor kernel, and Matern-3/2 altogether)
 template <int KID>
@@ -4010,6 +4176,82 @@ __global__ __launch_bounds__(256) void line_grid_kernel(const double* __restrict
   grid[e] = a * xi[(size_t)b * D + d] + x[(size_t)b * D + d];
 }
 
+// row slices of the covariance's data term: enough (group, slice) workgroups for every CU to hold several
+// a slice walks its rows in chunks of cov_cs: whole stars (as many as fit the 32 staged rows) where a star has at most
+// 32 rows -- the symmetric form of line_cov_kernel --, else 32 rows of anything
+struct LineCovPlan {
+  bool sym;
+  int cov_cs, cov_splits, cov_rows;
+};
+LineCovPlan line_cov_plan(int N, int mblk, int Bc_max) {
+  LineCovPlan pl;
+  pl.sym = mblk <= 32;
+  pl.cov_cs = pl.sym ? (32 / mblk) * mblk : 32;
+  int cov_splits = (1024 + Bc_max - 1) / Bc_max;
+  if (cov_splits < (N + LC_MAXROWS - 1) / LC_MAXROWS) cov_splits = (N + LC_MAXROWS - 1) / LC_MAXROWS;   // <= LC_MAXROWS rows per slice
+  if (cov_splits > (N + pl.cov_cs - 1) / pl.cov_cs) cov_splits = (N + pl.cov_cs - 1) / pl.cov_cs;
+  if (cov_splits < 1) cov_splits = 1;
+  int cov_rows = ((((N + cov_splits - 1) / cov_splits) + pl.cov_cs - 1) / pl.cov_cs) * pl.cov_cs;
+  if (cov_rows > LC_MAXROWS) cov_rows = (LC_MAXROWS / pl.cov_cs) * pl.cov_cs;
+  pl.cov_rows = cov_rows;
+  pl.cov_splits = (N + cov_rows - 1) / cov_rows;
+  return pl;
+}
+
+// The contraction stage shared by the line entries and ppbo_predict_gradients: for the Bc groups of G columns each that Kt
+// [Nk][ld] holds in the node layout (M = Bc G columns), Y = G K* (edge form: E into Ke, then Y = H E) and the groups' data
+// terms K*' Lambda K* + Y'Y in cov_parts, pl.cov_splits row-slice slabs of stride pst.
+int line_y_cov(ppbo_ctx* ctx, const ppbo_model* model, const double* Gq, int Nk, int g_rows, const double* Kt, double* Y,
+               double* Ke, int ld, int M, int Bc, int G, const LineCovPlan& pl, double* cov_parts, long long pst,
+               hipStream_t s) {
+  const int N = model->N, mblk = model->m + 1, n_q = N / mblk;
+  const bool edge = model->form == PPBO_FORM_EDGE, sym = pl.sym;
+  const int cov_splits = pl.cov_splits, cov_rows = pl.cov_rows, cov_cs = pl.cov_cs;
+  GemmArgs y{};  // Y = G K*
+  y.A = Gq; y.lda = Nk; y.B = Kt; y.ldb = ld; y.C = Y; y.ldc = ld;
+  y.M = g_rows; y.N = (M + 127) & ~127; y.K = Nk; y.alpha = 1.0; y.beta = 0.0; y.khi_mode = 1; y.tri_block = mblk;
+  if (edge) {
+    edge_apply_kernel<<<dim3((M + 127) / 128, N), 128, 0, s>>>(Kt, ld, M, mblk, n_q, model->d_lam_off, Ke);
+    PPBO_LAUNCH_CHECK(ctx);
+    y.B = Ke; y.tri_block = 1;   // H lower triangular
+  }
+  // (rows [N, g_rows) of Y come out as zeros, columns [M, y.N) as whatever the K* padding holds: neither is read)
+  // column tiles in chunks through all row tiles, heaviest first (a chunk's slice of K* -- 134 MB at 64 tiles -- stays
+  // in the Infinity Cache); equal chunks of at most 72 tiles: a ragged last chunk costs 5 % (512 lines: 280 tiles in
+  // chunks of 70: 2.33 ms; 64 + ragged 24: 2.47; 56: 2.35; 96: 2.35; 128: 4.85; one chunk: 4.2)
+  const int y_tiles = (M + 127) / 128, y_chunks = (y_tiles + 71) / 72;
+  y.nt_chunk = ctx->line_y_chunk > 0 ? ctx->line_y_chunk : (y_tiles + y_chunks - 1) / y_chunks;
+  {
+    PpboProfScope pf(ctx, ppbo_ctx::PF_LINE_Y, s);
+    if (int rc = ppbo_gemm_launch(ctx, y, 0, 0, s)) return rc;
+  }
+  // data term of every group's covariance: K*' Lambda K* + Y'Y, one workgroup per (group, row slice)
+  {
+    PpboProfScope pf(ctx, ppbo_ctx::PF_LINE_COV, s);
+    const dim3 cg(Bc, cov_splits);
+    // sym: every chunk is whole stars: the symmetric form (lower-triangle tiles only)
+#define LC_LAUNCH(NT)                                                                                                   \
+  do {                                                                                                                  \
+    if (sym) line_cov_kernel<NT, true><<<cg, 256, 0, s>>>(Kt, Y, ld, N, G, mblk, model->d_lam_diag, model->d_lam_off,   \
+                                                          cov_rows, cov_parts, pst, cov_cs);                            \
+    else line_cov_kernel<NT, false><<<cg, 256, 0, s>>>(Kt, Y, ld, N, G, mblk, model->d_lam_diag, model->d_lam_off,      \
+                                                       cov_rows, cov_parts, pst, cov_cs);                               \
+  } while (0)
+    switch ((G + 15) / 16) {
+      case 1: LC_LAUNCH(1); break;
+      case 2: LC_LAUNCH(2); break;
+      case 3: LC_LAUNCH(3); break;
+      case 4: LC_LAUNCH(4); break;
+      case 5: LC_LAUNCH(5); break;
+      case 6: LC_LAUNCH(6); break;
+      case 7: LC_LAUNCH(7); break;
+      default: LC_LAUNCH(8); break;
+    }
+#undef LC_LAUNCH
+  }
+  return 0;
+}
+
 // what ppbo_line_choice asks of the draws in place of EI / varmax: the chosen point of every draw, counted
 struct LineChoice {
   const double* d_e;   // [S,G] or NULL
@@ -4056,18 +4298,9 @@ int line_acq_impl(ppbo_ctx* ctx, const ppbo_model* model, const double* d_grid, 
   const int n_split = pick_split(Bc_max * G, n_q);
   const int q_per_split = (n_q + n_split - 1) / n_split;
   const int n_split_eff = (n_q + q_per_split - 1) / q_per_split;
-  // row slices of the covariance's data term: enough (line, slice) workgroups for every CU to hold several
-  // a slice walks its rows in chunks of cov_cs: whole stars (as many as fit the 32 staged rows) where a star has at most
-  // 32 rows -- the symmetric form of line_cov_kernel --, else 32 rows of anything
-  const bool sym = mblk <= 32;
-  const int cov_cs = sym ? (32 / mblk) * mblk : 32;
-  int cov_splits = (1024 + Bc_max - 1) / Bc_max;
-  if (cov_splits < (N + LC_MAXROWS - 1) / LC_MAXROWS) cov_splits = (N + LC_MAXROWS - 1) / LC_MAXROWS;   // <= LC_MAXROWS rows per slice
-  if (cov_splits > (N + cov_cs - 1) / cov_cs) cov_splits = (N + cov_cs - 1) / cov_cs;
-  if (cov_splits < 1) cov_splits = 1;
-  int cov_rows = ((((N + cov_splits - 1) / cov_splits) + cov_cs - 1) / cov_cs) * cov_cs;
-  if (cov_rows > LC_MAXROWS) cov_rows = (LC_MAXROWS / cov_cs) * cov_cs;
-  cov_splits = (N + cov_rows - 1) / cov_rows;
+  const LineCovPlan lcp = line_cov_plan(N, mblk, Bc_max);
+  const bool sym = lcp.sym;
+  const int cov_splits = lcp.cov_splits;
   double* part = (double*)ppbo_workspace(
       ctx, ppbo_ctx::WS_PART,
       ((size_t)(n_split_eff + 1) * Bc_max * G + (size_t)(1 + cov_splits) * Bc_max * G * G) * sizeof(double));
@@ -4118,49 +4351,7 @@ int line_acq_impl(ppbo_ctx* ctx, const ppbo_model* model, const double* d_grid, 
         }))
       return rc;
     PPBO_LAUNCH_CHECK(ctx);
-    GemmArgs y{};  // Y = G K*
-    y.A = Gq; y.lda = Nk; y.B = Kt; y.ldb = ld; y.C = Y; y.ldc = ld;
-    y.M = g_rows; y.N = (M + 127) & ~127; y.K = Nk; y.alpha = 1.0; y.beta = 0.0; y.khi_mode = 1; y.tri_block = mblk;
-    if (edge) {
-      edge_apply_kernel<<<dim3((M + 127) / 128, N), 128, 0, s>>>(Kt, ld, M, mblk, n_q, model->d_lam_off, Ke);
-      PPBO_LAUNCH_CHECK(ctx);
-      y.B = Ke; y.tri_block = 1;   // H lower triangular
-    }
-    // (rows [N, g_rows) of Y come out as zeros, columns [M, y.N) as whatever the K* padding holds: neither is read)
-    // column tiles in chunks through all row tiles, heaviest first (a chunk's slice of K* -- 134 MB at 64 tiles -- stays
-    // in the Infinity Cache); equal chunks of at most 72 tiles: a ragged last chunk costs 5 % (512 lines: 280 tiles in
-    // chunks of 70: 2.33 ms; 64 + ragged 24: 2.47; 56: 2.35; 96: 2.35; 128: 4.85; one chunk: 4.2)
-    const int y_tiles = (M + 127) / 128, y_chunks = (y_tiles + 71) / 72;
-    y.nt_chunk = ctx->line_y_chunk > 0 ? ctx->line_y_chunk : (y_tiles + y_chunks - 1) / y_chunks;
-    {
-      PpboProfScope pf(ctx, ppbo_ctx::PF_LINE_Y, s);
-      if (int rc = ppbo_gemm_launch(ctx, y, 0, 0, s)) return rc;
-    }
-    // data term of every line's covariance: K*' Lambda K* + Y'Y, one workgroup per (line, row slice)
-    {
-      PpboProfScope pf(ctx, ppbo_ctx::PF_LINE_COV, s);
-      const dim3 cg(Bc, cov_splits);
-      const long long pst = (long long)Bc_max * G * G;
-      // sym: every chunk is whole stars: the symmetric form (lower-triangle tiles only)
-#define LC_LAUNCH(NT)                                                                                                   \
-  do {                                                                                                                  \
-    if (sym) line_cov_kernel<NT, true><<<cg, 256, 0, s>>>(Kt, Y, ld, N, G, mblk, model->d_lam_diag, model->d_lam_off,   \
-                                                          cov_rows, cov_parts, pst, cov_cs);                            \
-    else line_cov_kernel<NT, false><<<cg, 256, 0, s>>>(Kt, Y, ld, N, G, mblk, model->d_lam_diag, model->d_lam_off,      \
-                                                       cov_rows, cov_parts, pst, cov_cs);                               \
-  } while (0)
-      switch ((G + 15) / 16) {
-        case 1: LC_LAUNCH(1); break;
-        case 2: LC_LAUNCH(2); break;
-        case 3: LC_LAUNCH(3); break;
-        case 4: LC_LAUNCH(4); break;
-        case 5: LC_LAUNCH(5); break;
-        case 6: LC_LAUNCH(6); break;
-        case 7: LC_LAUNCH(7); break;
-        default: LC_LAUNCH(8); break;
-      }
-#undef LC_LAUNCH
-    }
+    if (int rc = line_y_cov(ctx, model, Gq, Nk, g_rows, Kt, Y, Ke, ld, M, Bc, G, lcp, cov_parts, (long long)Bc_max * G * G, s)) return rc;
     if (ch) {
       {
         PpboProfScope pf(ctx, ppbo_ctx::PF_LINE_MC, s);
@@ -4194,6 +4385,67 @@ int choice_args(ppbo_ctx* ctx, const double* d_e, double noise_sd, double jitter
   PPBO_REQUIRE(ctx, jitter >= 0.0 && jitter <= 1.79769313486231570815e308, "jitter (finite, >= 0)");
   PPBO_REQUIRE(ctx, noise_sd == 0.0 || d_e != nullptr, "noise_sd > 0 needs the draws d_e");
   return 0;
+}
+
+// ---- ppbo_predict_gradients: the posterior N(m, C) of grad f at P points per chunk --------------------------------------
+struct GradMetric {
+  double w[64];      // (check_model: D <= 64)
+};
+
+// Pass 3 of ppbo_predict_gradients, one workgroup per point b:
+//   m_d  = the mean partials of column b D + d, summed in split order
+//   C_de = P_de + the data term of line_cov_kernel's slabs (K*' Lambda K* + Y'Y of the point's D columns), added in slab
+//          order and symmetrised as mc_factor_lds does it -- v = (a + b) / 2 with a, b the sums at (d, e) and (e, d), so
+//          C_de and C_ed are the same bits;  P = the unshrunk prior diag(slope_prior_weight)
+//   score = sum_d w_d C_dd (PPBO_GRAD_TRACE) or sum_d w_d (m_d^2 + C_dd) (PPBO_GRAD_NORM2), summed in the order of d
+// A point with a non-finite coordinate (read again from d_X here) gets NaN everywhere and an empty record.
+template <int KID>
+__global__ __launch_bounds__(256) void grad_finish_kernel(const double* __restrict__ Xp, int P, int D, KernParams p,
+                                                          const double* __restrict__ mu_part, int n_mu,
+                                                          const double* __restrict__ cov_parts, int n_parts,
+                                                          long long part_stride, int parts_lower_only, GradMetric w,
+                                                          int kind, long long idx_base, double* __restrict__ mean_out,
+                                                          double* __restrict__ cov_out, double* __restrict__ score_out,
+                                                          Best* __restrict__ blk_best) {
+  __shared__ double s_m[64], s_c[64];
+  const int b = blockIdx.x, t = threadIdx.x;
+  double chk = 0.0;
+  for (int i = 0; i < D; ++i) chk = fma(Xp[(size_t)b * D + i], 0.0, chk);
+  const bool bad = chk != 0.0;
+  if (t < D) {
+    double m = 0.0;
+    for (int s = 0; s < n_mu; ++s) m += mu_part[(size_t)s * P * D + (size_t)b * D + t];
+    if (bad) m = NAN;
+    s_m[t] = m;
+    if (mean_out) mean_out[(size_t)b * D + t] = m;
+  }
+  if (cov_parts) {
+    const double* cp = cov_parts + (size_t)b * D * D;
+    for (int e = t; e < D * D; e += 256) {
+      const int g = e / D, h = e - g * D;
+      double a = (g == h) ? slope_prior_weight<KID>(g, p) : 0.0, c = a;
+      // parts_lower_only: the slabs are exactly symmetric and hold the 16 x 16 tiles of the lower triangle only
+      const bool up = parts_lower_only && (g >> 4) < (h >> 4);
+      const int ia = up ? h * D + g : g * D + h, ib = (parts_lower_only && !up && (g >> 4) > (h >> 4)) ? g * D + h : h * D + g;
+      for (int k = 0; k < n_parts; ++k) { a += cp[(size_t)k * part_stride + ia]; c += cp[(size_t)k * part_stride + ib]; }
+      double v = 0.5 * (a + c);
+      if (bad) v = NAN;
+      if (cov_out) cov_out[(size_t)b * D * D + e] = v;
+      if (g == h) s_c[g] = v;
+    }
+  }
+  if (kind == PPBO_GRAD_NONE) return;
+  __syncthreads();
+  if (t != 0) return;
+  double sc = 0.0;
+  for (int d = 0; d < D; ++d) sc += w.w[d] * (kind == PPBO_GRAD_NORM2 ? s_m[d] * s_m[d] + s_c[d] : s_c[d]);
+  if (bad) sc = NAN;
+  if (score_out) score_out[b] = sc;
+  if (blk_best) {
+    Best r{0.0, -1};
+    if (sc == sc) { r.val = sc; r.idx = idx_base + b; }
+    blk_best[b] = r;
+  }
 }
 
 }  // namespace
@@ -4239,6 +4491,116 @@ int ppbo_line_choice_xi(ppbo_ctx* ctx, const ppbo_model* model, const double* d_
   const LineChoice ch{noise_sd > 0.0 ? d_e : nullptr, noise_sd, d_prob, d_count, d_choice};
   return line_acq_impl(ctx, model, nullptr, d_xi, d_x, d_alpha, alpha_per_line != 0, B, G, shrink, d_z, S, 0.0, jitter,
                        nullptr, nullptr, (hipStream_t)stream, &ch);
+}
+
+// Gradients: per chunk of at most GRAD_CHUNK = 512 points kstar_grad ->
+// line_y_cov with the D columns of a point as one group -> grad_finish -> one-workgroup argmax.  A chunk is at most
+// 512 x 64 = 32768 columns, half of what the line entries put through the same workspaces (512 lines of 128 points), so
+// the cap is 512 for every D.  The column pass is timed as "grad_kstar", the contraction under the line entries' "line_y"
+// and "line_cov", the finishing pass as "grad_finish".
+int ppbo_predict_gradients(ppbo_ctx* ctx, const ppbo_model* model, const double* d_X, int64_t M, const double* h_metric,
+                           int score_kind, double* d_mean, double* d_cov, double* d_score, double* h_best_val,
+                           int64_t* h_best_idx, void* stream) {
+  PPBO_ENTER(ctx);
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = check_model(ctx, model)) return rc;
+  PPBO_REQUIRE(ctx, d_X != nullptr, "gradients (d_X)");
+  PPBO_REQUIRE(ctx, M >= 1 && M <= (int64_t)0x7fffffff, "point count (1 .. 2^31 - 1)");
+  PPBO_REQUIRE(ctx, score_kind == PPBO_GRAD_NONE || score_kind == PPBO_GRAD_TRACE || score_kind == PPBO_GRAD_NORM2, "score_kind");
+  PPBO_REQUIRE(ctx, !model->kstar_fp32, "gradients are fp64 only (kstar_fp32)");
+  const int N = model->N, D = model->D, mblk = model->m + 1, n_q = N / mblk;
+  GradMetric gm;
+  for (int d = 0; d < 64; ++d) gm.w[d] = 1.0;
+  if (h_metric)
+    for (int d = 0; d < D; ++d) {
+      PPBO_REQUIRE(ctx, h_metric[d] > 0.0 && h_metric[d] <= 1.79769313486231570815e308, "metric (positive, finite)");
+      gm.w[d] = h_metric[d];
+    }
+  const bool want_cov = d_cov || score_kind != PPBO_GRAD_NONE;
+  PPBO_REQUIRE(ctx, !want_cov || model->d_G != nullptr, "covariance / score need model->d_G");
+  PPBO_REQUIRE(ctx, !want_cov || (model->d_lam_diag && model->d_lam_off), "model Lambda");
+  const bool want_best = (h_best_val || h_best_idx) && score_kind != PPBO_GRAD_NONE;
+  if (score_kind == PPBO_GRAD_NONE) {      // nothing is scored
+    if (h_best_val) *h_best_val = NAN;
+    if (h_best_idx) *h_best_idx = -1;
+  }
+  PpboHostRecord hr{};
+  if (want_best)
+    if (int rc = ppbo_host_record(ctx, &hr)) return rc;
+  constexpr int GRAD_CHUNK = 512;
+  const KernParams p = make_kern_params(model->kernel_id, model->theta);
+  const bool edge = model->form == PPBO_FORM_EDGE;
+  const int Pc_max = (int)(M < GRAD_CHUNK ? M : GRAD_CHUNK);
+  const int64_t n_chunks = (M + GRAD_CHUNK - 1) / GRAD_CHUNK;
+  const int ld = ((Pc_max * D) + 127) & ~127;
+  int Nk = N, g_rows = N;
+  const double* Gq = nullptr;
+  double *Kt = nullptr, *Y = nullptr, *Ke = nullptr;
+  LineCovPlan lcp{};
+  if (want_cov) {
+    Gq = padded_G(ctx, model, 128, (long long)Pc_max * D >= 2048, &Nk, &g_rows, s);
+    if (!Gq) return (int)hipErrorOutOfMemory;
+    PPBO_LAUNCH_CHECK(ctx);
+    double* ws = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_KSTAR, (size_t)((edge ? 2 : 1) * Nk + g_rows) * ld * sizeof(double));
+    if (!ws) return (int)hipErrorOutOfMemory;
+    Kt = ws;
+    Y = ws + (size_t)Nk * ld;
+    Ke = edge ? Y + (size_t)g_rows * ld : nullptr;
+    if (Nk != N) PPBO_HIP_CHECK(ctx, hipMemsetAsync(Kt + (size_t)N * ld, 0, (size_t)(Nk - N) * ld * sizeof(double), s));
+    if (edge && Nk != N) PPBO_HIP_CHECK(ctx, hipMemsetAsync(Ke + (size_t)N * ld, 0, (size_t)(Nk - N) * ld * sizeof(double), s));
+    lcp = line_cov_plan(N, mblk, Pc_max);
+  }
+  const int n_split = pick_split(Pc_max * D, n_q);
+  const int q_per_split = (n_q + n_split - 1) / n_split;
+  const int n_split_eff = (n_q + q_per_split - 1) / q_per_split;
+  const long long pst = (long long)Pc_max * D * D;
+  double* part = (double*)ppbo_workspace(
+      ctx, ppbo_ctx::WS_PART,
+      ((size_t)n_split_eff * Pc_max * D + (want_cov ? (size_t)lcp.cov_splits * pst : 0)) * sizeof(double));
+  if (!part) return (int)hipErrorOutOfMemory;
+  double* cov_parts = want_cov ? part + (size_t)n_split_eff * Pc_max * D : nullptr;
+  Best* bests = (Best*)ppbo_workspace(ctx, ppbo_ctx::WS_SMALL, (size_t)(Pc_max + n_chunks) * sizeof(Best));
+  if (!bests) return (int)hipErrorOutOfMemory;
+  Best* chunk_best = bests + Pc_max;
+  for (int64_t ch = 0; ch < n_chunks; ++ch) {
+    const int64_t c_beg = ch * GRAD_CHUNK;
+    const int Pc = (int)((M - c_beg) < GRAD_CHUNK ? (M - c_beg) : GRAD_CHUNK);
+    const double* xp = d_X + (size_t)c_beg * D;
+    const bool one = (n_chunks == 1);
+    if (int rc = ppbo_kernel_dispatch(ctx, model->kernel_id, [&](auto kid) {
+          constexpr int KID = decltype(kid)::value;
+          {
+            PpboProfScope pf(ctx, ppbo_ctx::PF_GRAD_KSTAR, s);
+            launch_kstar_grad<KID>(model, p, xp, Pc, Kt, ld, part, q_per_split, n_split_eff, s);
+          }
+          PPBO_LAUNCH_CHECK(ctx);
+          if (want_cov)
+            if (int rc2 = line_y_cov(ctx, model, Gq, Nk, g_rows, Kt, Y, Ke, ld, Pc * D, Pc, D, lcp, cov_parts, pst, s)) return rc2;
+          PpboProfScope pf(ctx, ppbo_ctx::PF_GRAD_FINISH, s);
+          grad_finish_kernel<KID><<<Pc, 256, 0, s>>>(xp, Pc, D, p, part, n_split_eff, cov_parts, lcp.cov_splits, pst,
+                                                     lcp.sym ? 1 : 0, gm, score_kind, (long long)c_beg,
+                                                     d_mean ? d_mean + (size_t)c_beg * D : nullptr,
+                                                     d_cov ? d_cov + (size_t)c_beg * D * D : nullptr,
+                                                     d_score ? d_score + c_beg : nullptr, want_best ? bests : nullptr);
+          PPBO_LAUNCH_CHECK(ctx);
+          return 0;
+        }))
+      return rc;
+    if (want_best) {
+      argmax_final_kernel<<<1, 256, 0, s>>>(bests, Pc, chunk_best + ch, one ? hr.d_rec : nullptr, 0,
+                                            one ? hr.d_flag : nullptr, hr.epoch);
+      PPBO_LAUNCH_CHECK(ctx);
+    }
+  }
+  if (!want_best) return 0;
+  if (n_chunks > 1) {
+    best_record_kernel<<<1, 64, 0, s>>>(chunk_best, (int)n_chunks, 0, hr.d_rec, hr.d_flag, hr.epoch);
+    PPBO_LAUNCH_CHECK(ctx);
+  }
+  if (int rc = ppbo_host_record_wait(ctx, hr, s)) return rc;
+  if (h_best_val) *h_best_val = hr.h_rec[0];      // (NaN, -1) when no point has a non-NaN score
+  if (h_best_idx) *h_best_idx = (int64_t)hr.h_rec[1];
+  return 0;
 }
 
 int ppbo_randn(ppbo_ctx* ctx, uint64_t seed, double* d_out, int64_t n, void* stream) {

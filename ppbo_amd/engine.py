@@ -13,6 +13,7 @@ from ._lib import KERNEL_IDS, SCORE_MEAN, SCORE_POINTWISE_EI, SCORE_VARIANCE, PP
 from ._lib import PAIR_MEAN, PAIR_VARIANCE, PAIR_PROB  # noqa: F401
 from ._lib import SLOPE_MEAN, SLOPE_VARIANCE, SLOPE_PROB  # noqa: F401
 from ._lib import CURV_MEAN, CURV_VARIANCE, CURV_PROB  # noqa: F401
+from ._lib import GRAD_NONE, GRAD_TRACE, GRAD_NORM2  # noqa: F401
 from ._lib import FUNCTIONAL_MEAN, FUNCTIONAL_VARIANCE, FUNCTIONAL_PROB, FUNCTIONAL_MAX_G  # noqa: F401
 from ._lib import EFFECT_RAW, EFFECT_CENTRED, EFFECT_INTERACTION, MARGINAL_MAX_DC  # noqa: F401
 from ._lib import TOURNAMENT_BORDA, TOURNAMENT_WORST, TOURNAMENT_MAX_B  # noqa: F401
@@ -83,6 +84,40 @@ def camphor_embed_accelerations(X, Xi, ls):
             w = -(2.0 * np.pi * Xi[:, d]) ** 2 / ls[d]
             cols += [np.cos(2.0 * np.pi * X[:, d]) * w, np.sin(2.0 * np.pi * X[:, d]) * w]
     return np.stack(cols, axis=1)
+
+
+def camphor_embed_jacobians(X, ls):
+    """J_e(x_i) [M, 11, 6] for caller rows X [M, 6] as a torch tensor on X's device: the Jacobian of the embedding e whose
+    action on a direction camphor_embed_directions forms (column order and formulas as there: row c_d holds
+    -2 pi sin(2 pi x_d) / l_d, row s_d holds 2 pi cos(2 pi x_d) / l_d, row z holds 1 / l_2, each in column d)."""
+    X = torch.as_tensor(X, dtype=torch.float64)
+    ls = torch.as_tensor(np.asarray(ls, dtype=np.float64), device=X.device)
+    J = torch.zeros(X.shape[0], 11, 6, dtype=torch.float64, device=X.device)
+    row = 0
+    for d in range(6):
+        if d == 2:
+            J[:, row, 2] = 1.0 / ls[2]
+            row += 1
+        else:
+            w = 2.0 * np.pi / ls[d]
+            J[:, row, d] = -torch.sin(2.0 * np.pi * X[:, d]) * w
+            J[:, row + 1, d] = torch.cos(2.0 * np.pi * X[:, d]) * w
+            row += 2
+    return J
+
+
+def camphor_pull_back(X, ls, mean, cov):
+    """(J'm [M, 6], J'CJ [M, 6, 6]) for the gradient's mean [M, 11] and covariance [M, 11, 11] in the embedding's columns
+    at the caller rows X [M, 6] (either may be None), as batched torch products; J'CJ is symmetrised, (A + A') / 2, so it
+    is symmetric bit for bit.  A row of X with a non-finite coordinate comes out as NaN."""
+    J = camphor_embed_jacobians(X, ls)
+    Jt = J.transpose(1, 2)
+    m6 = torch.bmm(Jt, mean.unsqueeze(2)).squeeze(2) if mean is not None else None
+    c6 = None
+    if cov is not None:
+        c6 = torch.bmm(torch.bmm(Jt, cov), J)
+        c6 = 0.5 * (c6 + c6.transpose(1, 2))
+    return m6, c6
 
 
 def lengthscales(theta, D, kernel):
@@ -879,6 +914,78 @@ class Engine:
                                           C.byref(bi) if want_best else None, self._stream())
         self._check(rc, "ppbo_predict_slopes")
         return dict(mu=mu, var=var, prob=pr, score=sc, best_val=bv.value, best_idx=bi.value)
+
+    @staticmethod
+    def _gradient_shapes(post: Posterior, X, score):
+        """The refusals of predict_gradients that shapes alone decide (before anything reaches the device): returns M."""
+        sx = tuple(np.shape(X))
+        D = 6 if post.camphor is not None else post.X.shape[1]
+        if len(sx) != 2:
+            raise ValueError(f"predict_gradients: points of shape {sx}; one [M, D] set is required")
+        if sx[1] != D:
+            raise ValueError(f"predict_gradients: points of width {sx[1]} for a model of {D} dimensions")
+        if sx[0] < 1:
+            raise ValueError("predict_gradients: no points")
+        if score not in (GRAD_NONE, GRAD_TRACE, GRAD_NORM2):
+            raise ValueError(f"predict_gradients: unknown score kind {score}")
+        return sx[0]
+
+    def predict_gradients(self, post: Posterior, X, score=GRAD_NONE, want_mean=True, want_cov=True, want_score=False,
+                          want_best=True):
+        """Gradients (ppbo_predict_gradients): for the M points X[i] in the caller's coordinates the posterior of the
+        whole gradient, grad f(x) ~ N(mean, cov), as device tensors mean [M, D] and cov [M, D, D] (symmetric bit for bit;
+        None where not asked for), with score [M] = GRAD_TRACE: tr C, GRAD_NORM2: E |grad f|^2 = |m|^2 + tr C, and
+        best_val / best_idx = the largest score and its first row ((NaN, -1) with GRAD_NONE).  Everything is in the
+        caller's coordinates: an ARD model's m <- s (.) m, C <- S C S and the metric s^2; a camphor_copper_ard_kernel
+        model is pulled back from the embedding's 11 columns by its Jacobian (J'm, J'CJ) and scored here.  The mean alone
+        (want_cov = False, GRAD_NONE) needs no variance operator."""
+        M = self._gradient_shapes(post, X, score)
+        scored = score != GRAD_NONE
+        with_var = want_cov or scored
+        cam = post.camphor is not None
+        Xc = self.dev(X)
+        Xd = self._points(post, Xc)
+        D = Xd.shape[1]
+        md = self._model(post, with_var)
+        need_mean = want_mean or (cam and score == GRAD_NORM2)
+        mean = self.empty(M, D) if need_mean else None
+        cov = self.empty(M, D, D) if (want_cov or (cam and scored)) else None
+        sc = self.empty(M) if (want_score and not cam) else None
+        metric = None
+        if post.scale is not None:
+            metric = np.ascontiguousarray(np.asarray(post.scale, dtype=np.float64) ** 2)
+        bv, bi = C.c_double(float("nan")), C.c_int64(-1)
+        lib_best = want_best and scored and not cam
+        rc = self.lib.ppbo_predict_gradients(self.ctx, C.byref(md), _ptr(Xd), M, self._dptr(metric) if metric is not None else None,
+                                             GRAD_NONE if cam else int(score), _ptr(mean), _ptr(cov), _ptr(sc),
+                                             C.byref(bv) if lib_best else None, C.byref(bi) if lib_best else None,
+                                             self._stream())
+        self._check(rc, "ppbo_predict_gradients")
+        best_val, best_idx = bv.value, bi.value
+        if post.scale is not None:
+            s = self.dev(post.scale)
+            if mean is not None:
+                mean = mean * s
+            if cov is not None:
+                cov = cov * torch.outer(s, s)          # (s_d s_e = s_e s_d: the symmetry survives bit for bit)
+        elif cam:
+            mean, cov = camphor_pull_back(Xc, post.camphor, mean, cov)
+            if scored:
+                sc = torch.diagonal(cov, dim1=1, dim2=2).sum(dim=1)
+                if score == GRAD_NORM2:
+                    sc = sc + (mean * mean).sum(dim=1)
+                if want_best:
+                    ok = ~torch.isnan(sc)
+                    if bool(ok.any()):
+                        best_val = float(sc[ok].max())
+                        best_idx = int(torch.nonzero(ok & (sc == best_val))[0, 0])
+                if not want_score:
+                    sc = None
+            if not want_mean:
+                mean = None
+            if not want_cov:
+                cov = None
+        return dict(mean=mean, cov=cov, score=sc, best_val=best_val, best_idx=best_idx)
 
     def predict_curvatures(self, post: Posterior, X, Xi, score=CURV_PROB, want_mu=True, want_var=True, want_prob=True,
                            want_score=False, want_best=True):

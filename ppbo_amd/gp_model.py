@@ -1069,6 +1069,60 @@ class GPModel:
         H[ib, ia] = H[ia, ib]
         return H
 
+    def gradient_pred(self, X):
+        """(mean [M, D], cov [M, D, D]) as NumPy arrays: the posterior of the whole gradient, grad f(X[i]) ~ N(mean[i],
+        cov[i]), in the caller's coordinates (ppbo_predict_gradients; no reference counterpart).  slope_pred's numbers are
+        its projections: xi' mean and xi' cov xi.  Host or device input; one point may be given as a 1-D vector."""
+        post = self._var_post()
+        X = X if isinstance(X, torch.Tensor) else np.asarray(X, dtype=float)
+        X = X.reshape(1, -1) if X.ndim == 1 else X
+        out = self.eng.predict_gradients(post, X, want_best=False)
+        return out["mean"].cpu().numpy(), out["cov"].cpu().numpy()
+
+    def xstar_covariance(self, x=None):
+        """How well the optimum is located: by the delta method x* ~ N(x, H^-1 C H^-1) at the peak x of the posterior
+        mean (default: xstar), H = mean_hessian(x) and grad f(x) ~ N(m, C) from gradient_pred.  Returns dict(cov, hessian,
+        grad_mean, grad_cov, axes, lengths): axes [D, D] holds the principal axes of cov as unit ROWS and lengths [D] their
+        standard deviations (square roots of cov's eigenvalues), largest first.  ValueError unless H is negative definite
+        (x is no peak of the mean); a Matern-3/2 model is refused as mean_hessian refuses it."""
+        x = np.asarray(self.xstar if x is None else x, dtype=float).reshape(-1)
+        H = self.mean_hessian(x)
+        top = float(np.linalg.eigvalsh(H).max())
+        if not top < 0.0:
+            raise ValueError(f"xstar_covariance: the mean Hessian at x is not negative definite (largest eigenvalue {top:.3e}): "
+                             "x is no peak of the posterior mean")
+        m, Cg = self.gradient_pred(x)
+        m, Cg = m[0], Cg[0]
+        cov = np.linalg.solve(H, np.linalg.solve(H, Cg).T)
+        cov = 0.5 * (cov + cov.T)
+        w, V = np.linalg.eigh(cov)
+        order = np.argsort(w)[::-1]
+        return dict(cov=cov, hessian=H, grad_mean=m, grad_cov=Cg, axes=V[:, order].T.copy(),
+                    lengths=np.sqrt(np.maximum(w[order], 0.0)))
+
+    def loosest_direction(self, x=None):
+        """The direction in which the optimum is located worst -- the first principal axis of xstar_covariance(x) -- as a
+        query direction, normalised |xi| / max |xi| the way next_query normalises its own."""
+        xi = self.xstar_covariance(x)["axes"][0]
+        return np.abs(xi) / np.max(np.abs(xi))
+
+    def active_subspace(self, n_points=1024, seed=None, X=None):
+        """(eigenvalues [D], eigenvectors [D, D] as unit ROWS), largest first, of E_x[grad f grad f'] = mean_i(m_i m_i' +
+        C_i) over n_points uniform points of the unit box from np.random.default_rng(seed), or over the given points X: the
+        directions along which the utility varies over the whole box, rotated ones included (effect_importance and
+        sensitivity see coordinates only)."""
+        post = self._var_post()
+        if X is None:
+            X = np.random.default_rng(seed).random((int(n_points), 6 if post.camphor is not None else post.X.shape[1]))
+        X = X if isinstance(X, torch.Tensor) else np.atleast_2d(np.asarray(X, dtype=float))
+        out = self.eng.predict_gradients(post, X, want_best=False)
+        m, Cg = out["mean"], out["cov"]
+        A = ((m.unsqueeze(2) * m.unsqueeze(1) + Cg).mean(dim=0)).cpu().numpy()
+        A = 0.5 * (A + A.T)
+        w, V = np.linalg.eigh(A)
+        order = np.argsort(w)[::-1]
+        return w[order], V[:, order].T.copy()
+
     def _choice_draws(self, n_draws, G, noisy, seed):
         """(z, e, noise_sd) of answer_pred / choice_pred: one ppbo_randn stream of 2 S G normals per seed, the first S G
         of them z, the next S G the likelihood's noise e (drawn whether or not it is used, so that the paths of a seed
