@@ -726,6 +726,45 @@ PPBO_API int ppbo_mean_search_multi(ppbo_ctx* ctx, const ppbo_model* model, cons
                            int K, double sep, int iters, double tol, int screen_fp32, double* d_x, double* d_mu,
                            void* stream);
 
+/* ---- searches inside boxes: conditional optima, trust regions, profiles of the mean ------------------------------------
+ * A box is lo[D] followed by hi[D], 0 <= lo_d <= hi_d <= 1, all finite, in the caller's coordinates (model->coords);
+ * lo_d == hi_d fixes coordinate d.  Boxes are HOST arrays: a bad box is refused before anything is launched.
+ *
+ * ppbo_mean_ascent_boxes is ppbo_mean_ascent inside boxes: start k of d_starts[K,D] uses box k / per_box of
+ * h_boxes[B,2,D], B == ceil(K / per_box).  The iteration is the unit-box one with three changes: the start and every
+ * iterate are clipped to [lo, hi]; the projection zeroes g_d where x_d <= lo_d and g_d < 0 or x_d >= hi_d and g_d > 0; the
+ * first step is 0.02 max_d (hi_d - lo_d) / max(|g|, 1e-300), |g| the unprojected norm.  A fixed coordinate never moves and
+ * its gradient never enters the projected norm; a box with every side zero returns the point, the mean there and 0
+ * iterations.  With lo = 0, hi = 1 the results are ppbo_mean_ascent's bit for bit.  All three coordinate maps.
+ * d_x[K,D], d_mu[K], d_iters[K] (optional).
+ *
+ * ppbo_mean_search_boxes runs T searches, trial t inside box t of h_boxes[T,2,D], in one enqueue.  With
+ * u = frac(pool + h_shifts[t]) (u = pool when h_shifts is NULL) the candidates of trial t are fma(hi_t - lo_t, u, lo_t)
+ * for the M rows of d_pool[M,D], followed by the S rows d_seeds[t,S,D] clipped into box t: Mt = M + S slots in EVERY
+ * trial.  Screening, thinning and start selection are ppbo_mean_search_multi's (the rule above; `sep` is Euclidean in the
+ * caller's coordinates on the mapped candidates), then K ascents per trial inside its box.
+ * screen_fp32 = 1 without a coordinate map: nothing is written out, the boxed screening kernel forms the candidates on
+ * the fly with the trial in its grid; screen_fp32 = 0, and both screenings under a map: each trial's rows are written out,
+ * scaled or embedded, and scored by ppbo_predict or the one-trial screen, as ppbo_mean_search_multi does.
+ * Trials run in batches of at most 64 for screening, selection and ascent; the fp32 screening's row split depends on M, S
+ * and N alone, so a trial's result does not depend on T, on its position or on the batch it falls into (T one-trial calls
+ * return the same bits).  Unit boxes, no seeds and the same shifts return ppbo_mean_search_multi's bits (extra points and
+ * x_prev absent) wherever both use the same row split: always with screen_fp32 = 0, and with the fp32 screening while
+ * ceil(M / 1024) T_multi <= 128.
+ * d_x[T,K,D], d_mu[T,K]: the refined maxima per trial, best start first (rows past the trial's count: mu = -inf);
+ * d_count[T] (optional): starts found per trial.  iters = 0 returns the picked candidates and the mean there.
+ * Limits: 1 <= T <= 4096, 1 <= K <= 1024, T K <= 65536, 0 <= S <= 64, M >= 1, 64 (M + S) < 2^31, D <= 64.
+ * "invalid argument", with nothing launched and the outputs untouched: a NULL model, pool, starts, boxes or output; S > 0
+ * without seeds; a box with lo > hi, a bound outside [0, 1] or not finite; the sizes above; B != ceil(K / per_box);
+ * negative sep, iters or tol; a model that ppbo_mean_ascent refuses.  Nothing synchronises. */
+PPBO_API int ppbo_mean_ascent_boxes(ppbo_ctx* ctx, const ppbo_model* model, const double* d_starts, int K,
+                           const double* h_boxes, int B, int per_box, int iters, double tol, double* d_x, double* d_mu,
+                           int* d_iters, void* stream);
+PPBO_API int ppbo_mean_search_boxes(ppbo_ctx* ctx, const ppbo_model* model, const double* d_pool, int64_t M,
+                           const double* h_shifts, const double* h_boxes, int T, const double* d_seeds, int S, int K,
+                           double sep, int iters, double tol, int screen_fp32, double* d_x, double* d_mu, int* d_count,
+                           void* stream);
+
 /* ---- into a model's coordinates ("the coordinate map of a model" above) ------------------------------------------------ */
 PPBO_API int ppbo_scale_points(ppbo_ctx* ctx, const double* d_in, int64_t M, int D, const double* h_scale, double* d_out,
                       void* stream);

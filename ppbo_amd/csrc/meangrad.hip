@@ -951,6 +951,287 @@ int launch_mean_grad(const ppbo_model* m, const KernParams& p, const double* d_X
   return 0;
 }
 
+// ---- searches inside boxes (ppbo_mean_ascent_boxes, ppbo_mean_search_boxes) -------------------------------------------
+// Kernels of their own beside the unit-box ones, which keep their code: the box costs the ascent two registers per
+// coordinate lane, the screening two wave-uniform operands per coordinate.
+// A box on the device is lo[D] | hi[D] | hi - lo [D] | max_d (hi_d - lo_d): box_stride(D) doubles, packed on the host from
+// the validated h_boxes (one IEEE subtraction: the same bits wherever it is made).
+static inline size_t box_stride(int D) { return 3 * (size_t)D + 1; }
+
+// The candidates of the trials of one ppbo_mean_search_boxes launch, never materialised: slot i < M of trial t is
+// fma(hi_t - lo_t, u, lo_t) with u = frac(pool + shift_t) (u = pool without shifts), the S slots behind are trial t's seed
+// rows clipped into its box.  Every trial has all Mt = M + S slots.
+struct BoxCands {
+  const double* pool = nullptr; long long M = 0; const double* shifts = nullptr;
+  const double* boxes = nullptr;   // box_stride(D) doubles per trial
+  const double* seeds = nullptr;   // [trials][S][D]
+  int S = 0, D = 0;
+};
+__device__ __forceinline__ double box_coord(const BoxCands& c, int trial, long long i, int d) {
+  const double* __restrict__ b = c.boxes + (size_t)trial * (3 * c.D + 1);
+  if (i < c.M) {
+    double u = c.pool[(size_t)i * c.D + d];
+    if (c.shifts) { const double v = u + c.shifts[(size_t)trial * c.D + d]; u = v - floor(v); }
+    return fma(b[2 * c.D + d], u, b[d]);
+  }
+  return fmin(fmax(c.seeds[((size_t)trial * c.S + (i - c.M)) * c.D + d], b[d]), b[c.D + d]);
+}
+
+// mean_screen_kernel over BoxCands: the trial is blockIdx.z, so lo and hi - lo are wave-uniform (scalar loads), and
+// every slot of every trial is present.  The row loop is mean_screen_kernel's.
+template <int KID, int DP>
+__global__ __launch_bounds__(SCR_T) void box_screen_kernel(const double* __restrict__ X, int N, int D, KernParams p,
+                                                           const double* __restrict__ alpha, BoxCands bc,
+                                                           int rows_per_split, int n_split, double* __restrict__ part) {
+  constexpr int NP = SCR_CPT / 2;
+  __shared__ __attribute__((aligned(16))) float xs[SCR_RJ][DP];
+  __shared__ double sa[SCR_RJ];
+  const int trial = blockIdx.z;
+  const long long Mt = bc.M + bc.S;
+  const long long c0 = ((long long)blockIdx.x * SCR_T + threadIdx.x) * SCR_CPT;
+  float2_t xc[NP][DP];
+  double mu[SCR_CPT];
+#pragma unroll
+  for (int q = 0; q < SCR_CPT; ++q) {
+    mu[q] = 0.0;
+    const bool there = c0 + q < Mt;
+#pragma unroll
+    for (int d = 0; d < DP; ++d) {
+      const float v = (d < D && there) ? (float)box_coord(bc, trial, c0 + q, d) : 0.0f;
+      if (q & 1) xc[q >> 1][d].y = v; else xc[q >> 1][d].x = v;
+    }
+  }
+  const float c0f = (float)p.c0, c1f = (float)p.c1, sf2f = (float)p.sf2;
+  const int j_beg = blockIdx.y * rows_per_split;
+  int j_end = j_beg + rows_per_split;
+  if (j_end > N) j_end = N;
+  for (int row0 = j_beg; row0 < j_end; row0 += SCR_RJ) {
+    __syncthreads();
+    for (int e = threadIdx.x; e < SCR_RJ * DP; e += SCR_T) {
+      const int r = e / DP, d = e - r * DP, j = row0 + r;
+      xs[r][d] = (j < j_end && d < D) ? (float)X[(size_t)j * D + d] : 0.0f;
+    }
+    if (threadIdx.x < SCR_RJ) sa[threadIdx.x] = (row0 + (int)threadIdx.x < j_end) ? alpha[row0 + threadIdx.x] : 0.0;
+    __syncthreads();
+    const int rmax = (j_end - row0 < SCR_RJ) ? (j_end - row0) : SCR_RJ;
+    for (int r = 0; r < rmax; ++r) {
+      float2_t sv[NP];
+#pragma unroll
+      for (int q = 0; q < NP; ++q) sv[q] = float2_t{0.0f, 0.0f};
+#pragma unroll
+      for (int d = 0; d < DP; ++d) {
+        const float x = xs[r][d];
+        const float2_t xx = {x, x};
+#pragma unroll
+        for (int q = 0; q < NP; ++q) {
+          if (KID == PPBO_KERNEL_CAMPHOR) sv[q] += screen_term2<KID>(xx - xc[q][d], d, c0f, c1f);
+          else { const float2_t dx = xx - xc[q][d]; sv[q] = __builtin_elementwise_fma(dx, dx, sv[q]); }
+        }
+      }
+      const double a = sa[r];
+#pragma unroll
+      for (int q = 0; q < NP; ++q) {
+        mu[2 * q] = fma(a, (double)screen_finish<KID>(sv[q].x, sf2f, c0f), mu[2 * q]);
+        mu[2 * q + 1] = fma(a, (double)screen_finish<KID>(sv[q].y, sf2f, c0f), mu[2 * q + 1]);
+      }
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < SCR_CPT; ++q)
+    if (c0 + q < Mt) part[((size_t)trial * n_split + blockIdx.y) * Mt + c0 + q] = mu[q];
+}
+
+// candidates of trial t as rows (the fp64 screening and the screenings under a coordinate map)
+__global__ __launch_bounds__(256) void box_rows_kernel(BoxCands bc, int trial, double* __restrict__ out) {
+  const long long n = (bc.M + bc.S) * bc.D;
+  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= n) return;
+  out[e] = box_coord(bc, trial, e / bc.D, (int)(e % bc.D));
+}
+
+// group_max_kernel of the boxed trials (blockIdx.y): a group's survivor is also written out as a row, surv[trial][t][D],
+// and gidx[trial][t] names that row -- select_starts_kernel then reads its coordinates from `surv` as from any
+// candidate array and needs no boxed form
+__global__ __launch_bounds__(256) void box_group_max_kernel(const double* __restrict__ mu, int64_t Mt, int G, int T,
+                                                            BoxCands bc, double* __restrict__ gval,
+                                                            int* __restrict__ gidx, double* __restrict__ surv) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= T) return;
+  const int trial = blockIdx.y;
+  mu += (size_t)trial * Mt;
+  const int64_t lo = (int64_t)t * G, hi = (lo + G < Mt) ? lo + G : Mt;
+  double best = -INFINITY;
+  int64_t bi = lo;
+  for (int64_t i = lo; i < hi; ++i) {
+    const double v = mu[i];
+    if (v > best) { best = v; bi = i; }         // NaN never wins
+  }
+  const size_t row = (size_t)trial * T + t;
+  gval[row] = best;
+  gidx[row] = (int)row;
+  for (int d = 0; d < bc.D; ++d) surv[row * bc.D + d] = box_coord(bc, trial, bi, d);
+}
+
+// bb_ascent_kernel inside a box: start c uses box c / per_box (boxes: box_stride(D) doubles each).  lo_d and hi_d sit in
+// two registers of the coordinate's lane; the start and every iterate are clipped to [lo, hi], the projection zeroes g_d
+// at an active bound, the first move is 0.02 of the longest side.  A coordinate with lo == hi never moves and never
+// enters the projected norm; a box of one point ends at it = 0.  With lo = 0, hi = 1 every expression is
+// bb_ascent_kernel's (0.02 * 1.0 is exact).  count: one number of existing starts per box.
+template <int DP, class EVAL, int NT>
+__global__ __launch_bounds__(NT) void bb_ascent_box_kernel(EVAL ev, int D, const double* __restrict__ starts,
+                                                            const int* __restrict__ count,
+                                                            const double* __restrict__ boxes, int per_box, int iters,
+                                                            double tol, double* __restrict__ x_out,
+                                                            double* __restrict__ mu_out, int* __restrict__ it_out) {
+  static_assert(DP <= 64, "lane = coordinate");
+  constexpr int NW = NT / 16;              // one record per row of 16 lanes
+  __shared__ double red[NW][DP + 1];
+  __shared__ double sx[DP];
+  __shared__ int done;
+  const int c = blockIdx.x, tid = threadIdx.x;
+  const int b = c / per_box;
+  if (count && (c - b * per_box) >= count[b]) {
+    if (tid == 0) { mu_out[c] = -INFINITY; if (it_out) it_out[c] = 0; }
+    return;
+  }
+  const bool w0 = tid < 64;
+  const int d = tid;                       // coordinate of this lane (wavefront 0 only)
+  const bool live = w0 && d < D;
+  const double* __restrict__ bx = boxes + (size_t)b * (3 * D + 1);
+  const double lo = live ? bx[d] : 0.0, hi = live ? bx[D + d] : 0.0;
+  const double wmax = bx[3 * D];           // the longest side (the same for every lane)
+  double x = 0.0, g = 0.0, mu = 0.0, step = 0.0, xn = 0.0;
+  if (tid < DP) {
+    x = live ? fmin(fmax(starts[(size_t)c * D + d], lo), hi) : 0.0;
+    sx[tid] = x;
+  }
+  if (tid == 0) done = 0;
+  __syncthreads();
+  ev(sx, red);
+  __syncthreads();
+  if (w0) {
+    const int dd = d < DP ? d : DP - 1;
+    g = live ? red_col<NW, DP>(red, dd) : 0.0;
+    mu = red_col<NW, DP>(red, DP);
+    const double gn = sqrt(wave_sum_dpp(g * g));
+    step = (0.02 * wmax) / fmax(gn, 1e-300);        // first move: 0.02 of the longest side
+  }
+  int it = 0;
+  for (; it < iters; ++it) {
+    if (w0) {
+      const double pg = ((x <= lo && g < 0.0) || (x >= hi && g > 0.0)) ? 0.0 : g;
+      const double pn = sqrt(wave_sum_dpp(pg * pg));
+      if (!(pn * step >= tol) || !(wmax > 0.0)) { if (tid == 0) done = 1; }
+      else {
+        xn = fmin(fmax(x + step * pg, lo), hi);
+        if (tid < DP) sx[tid] = live ? xn : 0.0;
+      }
+    }
+    __syncthreads();
+    if (done) break;
+    ev(sx, red);
+    __syncthreads();
+    if (w0) {
+      const int dd = d < DP ? d : DP - 1;
+      const double gnew = live ? red_col<NW, DP>(red, dd) : 0.0;
+      const double mun = red_col<NW, DP>(red, DP);
+      const bool ok = mun >= mu;
+      const double sv = live ? xn - x : 0.0, yv = gnew - g;
+      const double curv = -wave_sum_dpp(sv * yv);          // > 0 where mu is locally concave along the move
+      const double ss = wave_sum_dpp(sv * sv);
+      step = ok ? (curv > 0.0 ? ss / fmax(curv, 1e-300) : 2.0 * step) : 0.25 * step;
+      if (ok) { x = xn; g = gnew; mu = mun; }
+    }
+    // the next write to sx / red happens after every wave has passed the barrier above
+  }
+  if (live) x_out[(size_t)c * D + d] = x;
+  if (tid == 0) { mu_out[c] = mu; if (it_out) it_out[c] = it; }
+}
+
+// launch_mean_ascent's buckets over bb_ascent_box_kernel; Xt: the design of m transposed (transposed_design)
+template <int KID>
+int launch_mean_ascent_boxes(const ppbo_model* m, const KernParams& p, const CoordMap& co, const double* Xt,
+                             const double* starts, const int* count, const double* boxes, int per_box, int K, int iters,
+                             double tol, double* x_out, double* mu_out, int* it_out, hipStream_t s) {
+#define MB_RUN(DP, NT, ev) \
+  bb_ascent_box_kernel<DP, decltype(ev), NT><<<K, NT, 0, s>>>(ev, m->D, starts, count, boxes, per_box, iters, tol, x_out, mu_out, it_out)
+#define MB_LAUNCH(DP, NT)                                                                                             \
+  do {                                                                                                                \
+    MeanEval<KID, DP, NT> ev{Xt, m->N, m->D, p, m->d_alpha};                                                        \
+    if constexpr (kid_radial<KID>) {                                                                                  \
+      if (co.d_scale) {                                                                                               \
+        ScaledMeanEval<KID, DP, NT> sev{ev, co.d_scale};                                                              \
+        MB_RUN(DP, NT, sev);                                                                                          \
+        break;                                                                                                        \
+      }                                                                                                               \
+    }                                                                                                                 \
+    if constexpr (KID == PPBO_KERNEL_CAMPHOR) {                                                                       \
+      if (co.kind == PPBO_COORDS_CAMPHOR) {                                                                           \
+        CamphorMeanEval<DP, NT> cev{Xt, m->N, p.sf2, co.cam, m->d_alpha};                                             \
+        MB_RUN(DP, NT, cev);                                                                                          \
+        break;                                                                                                        \
+      }                                                                                                               \
+    }                                                                                                                 \
+    MB_RUN(DP, NT, ev);                                                                                             \
+  } while (0)
+  const bool tall = m->N >= 1024;
+  if (KID == PPBO_KERNEL_CAMPHOR || m->D <= 8) { if (tall) MB_LAUNCH(8, 1024); else MB_LAUNCH(8, 256); }
+  else if constexpr (KID != PPBO_KERNEL_CAMPHOR) {     // (camphor-copper: D = 6)
+    if (m->D <= 24) { if (tall) MB_LAUNCH(24, 512); else MB_LAUNCH(24, 256); }
+    else MB_LAUNCH(64, 256);
+  }
+#undef MB_LAUNCH
+#undef MB_RUN
+  return 0;
+}
+
+// the design of m ([N][D]) transposed into the ascent's workspace slot
+static double* transposed_design(ppbo_ctx* ctx, const ppbo_model* m, hipStream_t s) {
+  double* Xt = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_TRANSPOSE, (size_t)m->N * m->D * sizeof(double));
+  if (Xt) transpose_rows_kernel<<<(m->N + 255) / 256, 256, 0, s>>>(m->d_X, m->N, m->D, Xt);
+  return Xt;
+}
+
+// h_boxes[B][2][D] validated and packed into the device form (box_stride(D) doubles per box)
+static int pack_boxes(ppbo_ctx* ctx, const double* h_boxes, int B, int D, std::vector<double>& out) {
+  const size_t bs = box_stride(D);
+  out.assign((size_t)B * bs, 0.0);
+  for (int b = 0; b < B; ++b) {
+    const double* lo = h_boxes + (size_t)b * 2 * D;
+    const double* hi = lo + D;
+    double* o = out.data() + (size_t)b * bs;
+    double wmax = 0.0;
+    for (int d = 0; d < D; ++d) {
+      PPBO_REQUIRE(ctx, std::isfinite(lo[d]) && std::isfinite(hi[d]) && lo[d] >= 0.0 && hi[d] <= 1.0 && lo[d] <= hi[d],
+                   "boxes: 0 <= lo <= hi <= 1, finite");
+      o[d] = lo[d]; o[D + d] = hi[d]; o[2 * D + d] = hi[d] - lo[d];
+      if (o[2 * D + d] > wmax) wmax = o[2 * D + d];
+    }
+    o[3 * D] = wmax;
+  }
+  return 0;
+}
+
+template <int KID>
+int launch_box_screen(const ppbo_model* m, const KernParams& p, const BoxCands& bc, int nb, int rows_per_split,
+                      int n_split, double* part, hipStream_t s) {
+  const long long Mt = bc.M + bc.S;
+  const dim3 grid((unsigned)((Mt + SCR_T * SCR_CPT - 1) / (SCR_T * SCR_CPT)), n_split, nb);
+#define SCR_LAUNCH(DP) box_screen_kernel<KID, DP><<<grid, SCR_T, 0, s>>>(m->d_X, m->N, m->D, p, m->d_alpha, bc, rows_per_split, n_split, part)
+  if constexpr (KID == PPBO_KERNEL_CAMPHOR) SCR_LAUNCH(6);     // (D = 6: a bucket of its own)
+  else if (m->D <= 4) SCR_LAUNCH(4);
+  else if (m->D <= 8) SCR_LAUNCH(8);
+  else if (m->D <= 12) SCR_LAUNCH(12);
+  else if (m->D <= 16) SCR_LAUNCH(16);
+  else if (m->D <= 20) SCR_LAUNCH(20);
+  else if (m->D <= 24) SCR_LAUNCH(24);
+  else if (m->D <= 32) SCR_LAUNCH(32);
+  else if (m->D <= 48) SCR_LAUNCH(48);
+  else SCR_LAUNCH(64);
+#undef SCR_LAUNCH
+  return 0;
+}
+
 }  // namespace
 
 
@@ -1238,6 +1519,162 @@ extern "C" int ppbo_mean_search_multi(ppbo_ctx* ctx, const ppbo_model* model, co
 }
 
 // the map of an RFF search: the identity, or the camphor basis over six caller coordinates
+extern "C" int ppbo_mean_ascent_boxes(ppbo_ctx* ctx, const ppbo_model* model, const double* d_starts, int K,
+                                      const double* h_boxes, int B, int per_box, int iters, double tol, double* d_x,
+                                      double* d_mu, int* d_iters, void* stream) {
+  PPBO_ENTER(ctx);
+  CoordMap co;
+  if (int rc = resolve_model_coords(ctx, model, co)) return rc;
+  PPBO_REQUIRE(ctx, d_starts && h_boxes && d_x && d_mu && K > 0 && K <= 65536 && iters >= 0 && tol >= 0,
+               "starts / boxes / outputs");
+  PPBO_REQUIRE(ctx, per_box >= 1 && B == (K + per_box - 1) / per_box, "B == ceil(K / per_box), per_box >= 1");
+  const ppbo_model* m = co.model;
+  std::vector<double> hb;
+  if (int rc = pack_boxes(ctx, h_boxes, B, m->D, hb)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  double* boxes = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_BOX, hb.size() * sizeof(double));
+  if (!boxes) return (int)hipErrorOutOfMemory;
+  if (int rc = ppbo_upload_async(ctx, boxes, hb.data(), hb.size() * sizeof(double), s)) return rc;
+  if (int rc = co.upload(ctx, s)) return rc;
+  const double* Xt = transposed_design(ctx, m, s);
+  if (!Xt) return (int)hipErrorOutOfMemory;
+  const KernParams p = make_kern_params(m->kernel_id, m->theta);
+  if (int rc = ppbo_kernel_dispatch(ctx, m->kernel_id, [&](auto kid) {
+        return launch_mean_ascent_boxes<decltype(kid)::value>(m, p, co, Xt, d_starts, nullptr, boxes, per_box, K, iters, tol,
+                                                              d_x, d_mu, d_iters, s);
+      }))
+    return rc;
+  PPBO_LAUNCH_CHECK(ctx);
+  return 0;
+}
+
+extern "C" int ppbo_mean_search_boxes(ppbo_ctx* ctx, const ppbo_model* model, const double* d_pool, int64_t M,
+                                      const double* h_shifts, const double* h_boxes, int T, const double* d_seeds, int S,
+                                      int K, double sep, int iters, double tol, int screen_fp32, double* d_x, double* d_mu,
+                                      int* d_count, void* stream) {
+  PPBO_ENTER(ctx);
+  CoordMap co;
+  if (int rc = resolve_model_coords(ctx, model, co)) return rc;
+  // m: the model in the caller's coordinates, where the search runs; emb (camphor): the embedded model, screened as SE
+  const ppbo_model* m = co.model;
+  const ppbo_model* emb = co.kind == PPBO_COORDS_CAMPHOR ? model : nullptr;
+  PPBO_REQUIRE(ctx, d_pool && h_boxes && d_x && d_mu && M >= 1, "pool / boxes / outputs");
+  PPBO_REQUIRE(ctx, T >= 1 && T <= 4096 && K >= 1 && K <= 1024 && (int64_t)T * K <= 65536, "T (<= 4096) / K (<= 1024) / T K (<= 65536)");
+  PPBO_REQUIRE(ctx, S >= 0 && S <= 64 && (S == 0 || d_seeds) && M < ((int64_t)1 << 31) / 64 - S, "seeds (S <= 64) / 64 (M + S) < 2^31");
+  PPBO_REQUIRE(ctx, sep >= 0 && iters >= 0 && tol >= 0, "sep / iters / tol");
+  const int D = m->D;
+  std::vector<double> hb;
+  if (int rc = pack_boxes(ctx, h_boxes, T, D, hb)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const long long Mt = M + S;
+  const size_t bs = box_stride(D);
+  constexpr int TB = 64;                 // trials per batch: bounds the score vectors (TB x Mt doubles)
+  const int nb_max = T < TB ? T : TB;
+  // device copies: the packed boxes of all trials, then the shifts -- one host array, one upload
+  const size_t n_box = hb.size();
+  if (h_shifts) hb.insert(hb.end(), h_shifts, h_shifts + (size_t)T * D);
+  double* boxes = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_BOX, hb.size() * sizeof(double));
+  if (!boxes) return (int)hipErrorOutOfMemory;
+  double* shifts = h_shifts ? boxes + n_box : nullptr;
+  StartSelection sel{Mt, nb_max, D, K};
+  if (!sel.alloc(ctx, 0, nb_max)) return (int)hipErrorOutOfMemory;
+  double* surv = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_BOX_SURV, (size_t)nb_max * sel.Tg * D * sizeof(double));
+  if (!surv) return (int)hipErrorOutOfMemory;
+  const bool on_the_fly = screen_fp32 && co.kind == PPBO_COORDS_MODEL;
+  // the row split of the fp32 screening depends on the candidates and the design alone, never on T or the batch: a
+  // trial's scores are the same bits in whichever call and batch it runs
+  const int blocks_x = (int)((Mt + SCR_T * SCR_CPT - 1) / (SCR_T * SCR_CPT));
+  int n_split = 1, rows_per_split = m->N;
+  screen_split(blocks_x, 1, m->N, n_split, rows_per_split);
+  double *rows = nullptr, *erows = nullptr, *part = nullptr;
+  int De = D;
+  if (on_the_fly) {
+    part = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_PART, (size_t)(nb_max < 8 ? nb_max : 8) * n_split * Mt * sizeof(double));
+    if (!part) return (int)hipErrorOutOfMemory;
+  } else {
+    erows = rows = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_SEARCH_ROWS, (size_t)Mt * D * sizeof(double));
+    if (!rows) return (int)hipErrorOutOfMemory;
+    if (emb) {
+      erows = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_CAMPHOR_ROWS, (size_t)Mt * CAMPHOR_E * sizeof(double));
+      if (!erows) return (int)hipErrorOutOfMemory;
+      De = CAMPHOR_E;
+    }
+    if (screen_fp32) {
+      part = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_PART, (size_t)n_split * Mt * sizeof(double));
+      if (!part) return (int)hipErrorOutOfMemory;
+    }
+  }
+  // every refusal lies above; the boxes and shifts leave the host through a pinned upload slot (nothing blocks)
+  if (int rc = ppbo_upload_async(ctx, boxes, hb.data(), hb.size() * sizeof(double), s)) return rc;
+  if (int rc = co.upload(ctx, s)) return rc;
+  const double* d_scale = co.d_scale;
+  const double* Xt = transposed_design(ctx, m, s);
+  if (!Xt) return (int)hipErrorOutOfMemory;
+  const KernParams p = make_kern_params(m->kernel_id, m->theta);
+  const ppbo_model* sm = emb ? emb : m;
+  const KernParams sp = emb ? make_kern_params(PPBO_KERNEL_SE, emb->theta) : p;
+  ppbo_model mean_only = *sm;
+  mean_only.d_G = nullptr;
+  double* mu = sel.scores;
+  for (int t0 = 0; t0 < T; t0 += TB) {
+    const int nb = (T - t0 < TB) ? (T - t0) : TB;
+    BoxCands bc;
+    bc.pool = d_pool; bc.M = M; bc.shifts = shifts ? shifts + (size_t)t0 * D : nullptr; bc.boxes = boxes + (size_t)t0 * bs;
+    bc.seeds = S ? d_seeds + (size_t)t0 * S * D : nullptr; bc.S = S; bc.D = D;
+    if (on_the_fly) {
+      for (int u0 = 0; u0 < nb; u0 += 8) {      // (bounds the partial sums: 8 x n_split x Mt doubles)
+        const int nu = (nb - u0 < 8) ? (nb - u0) : 8;
+        BoxCands bu = bc;
+        if (bu.shifts) bu.shifts += (size_t)u0 * D;
+        bu.boxes += (size_t)u0 * bs;
+        if (bu.seeds) bu.seeds += (size_t)u0 * S * D;
+        if (int rc = ppbo_kernel_dispatch(ctx, m->kernel_id, [&](auto kid) {
+              return launch_box_screen<decltype(kid)::value>(m, p, bu, nu, rows_per_split, n_split, part, s);
+            }))
+          return rc;
+        screen_sum_kernel<<<dim3((unsigned)((Mt + 255) / 256), nu), 256, 0, s>>>(part, n_split, Mt, Mt, -1, mu + (size_t)u0 * Mt);
+        PPBO_LAUNCH_CHECK(ctx);
+      }
+    } else {
+      // the routes of ppbo_mean_search_multi: a trial's candidates written out as rows, scaled (ARD) or embedded
+      // (camphor), and scored by ppbo_predict or by a one-trial launch of mean_screen_kernel over the rows
+      for (int t = 0; t < nb; ++t) {
+        box_rows_kernel<<<(unsigned)((Mt * D + 255) / 256), 256, 0, s>>>(bc, t, rows);
+        if (d_scale) scale_points_kernel<<<(unsigned)((Mt * D + 255) / 256), 256, 0, s>>>(rows, Mt * D, D, d_scale, rows);
+        PPBO_LAUNCH_CHECK(ctx);
+        if (emb)
+          if (int rc = ppbo_camphor_embed(ctx, rows, Mt, co.h_coef, erows, stream)) return rc;
+        if (screen_fp32) {
+          TrialCands tr;
+          tr.pool = erows; tr.M = 0; tr.shifts = erows; tr.extra = erows; tr.E_rows = (int)Mt; tr.E = (int)Mt; tr.D = De;
+          if (int rc = ppbo_kernel_dispatch<true>(ctx, sm->kernel_id, [&](auto kid) {
+                return launch_screen<decltype(kid)::value>(sm, sp, tr, 1, rows_per_split, n_split, part, 0, s);
+              }))
+            return rc;
+          screen_sum_kernel<<<dim3((unsigned)((Mt + 255) / 256), 1), 256, 0, s>>>(part, n_split, Mt, 0, 0, mu + (size_t)t * Mt);
+          PPBO_LAUNCH_CHECK(ctx);
+        } else if (int rc = ppbo_predict(ctx, &mean_only, erows, Mt, PPBO_SCORE_MEAN, 0.0, mu + (size_t)t * Mt, nullptr, nullptr,
+                                         nullptr, nullptr, stream)) {
+          return rc;
+        }
+      }
+    }
+    int* counts = d_count ? d_count + t0 : sel.counts;
+    box_group_max_kernel<<<dim3((sel.Tg + 255) / 256, nb), 256, 0, s>>>(mu, Mt, sel.G, sel.Tg, bc, sel.gval, sel.gidx, surv);
+    const size_t sel_lds = (size_t)sel.Tg * (1 + D) * sizeof(double);
+    if (sel_lds > 64 * 1024) ppbo_lds_limit(ctx, (const void*)select_starts_kernel, 150 * 1024);
+    select_starts_kernel<<<nb, 1024, sel_lds, s>>>(sel.gval, sel.gidx, sel.Tg, surv, D, K, sep * sep, sel.starts, counts, TrialCands{});
+    PPBO_LAUNCH_CHECK(ctx);
+    if (int rc = ppbo_kernel_dispatch(ctx, m->kernel_id, [&](auto kid) {
+          return launch_mean_ascent_boxes<decltype(kid)::value>(m, p, co, Xt, sel.starts, counts, bc.boxes, K, nb * K, iters, tol,
+                                                                d_x + (size_t)t0 * K * D, d_mu + (size_t)t0 * K, nullptr, s);
+        }))
+      return rc;
+    PPBO_LAUNCH_CHECK(ctx);
+  }
+  return 0;
+}
+
 static int resolve_rff_coords(ppbo_ctx* ctx, const ppbo_coords* coords, int D, CoordMap& co) {
   PPBO_REQUIRE(ctx, !coords || coords->kind != PPBO_COORDS_SCALED, "coords: a scaled basis is a basis, pass W s");
   return resolve_coords(ctx, coords, PPBO_KERNEL_SE, D, co);

@@ -1312,6 +1312,72 @@ class Engine:
         self._check(rc, "ppbo_mean_ascent")
         return xs, mus, its
 
+    def _boxes(self, boxes, D, what):
+        """Host boxes [B, 2, D] (lo row, hi row) as a contiguous float64 array; the library validates the values."""
+        bx = np.ascontiguousarray(np.asarray(boxes, dtype=np.float64))
+        if bx.ndim == 2:
+            bx = bx[None]
+        if bx.ndim != 3 or bx.shape[1] != 2 or bx.shape[2] != D:
+            raise ValueError(f"{what}: boxes must be [B, 2, {D}] (lo, hi), got {tuple(bx.shape)}")
+        return bx
+
+    def mean_ascent_boxes(self, post: Posterior, starts, boxes, per_box=1, iters=100, tol=1e-9):
+        """mean_ascent inside boxes (ppbo_mean_ascent_boxes): start k climbs inside boxes[k // per_box], boxes [B, 2, D]
+        with B = ceil(K / per_box), in the caller's coordinates.  lo == hi fixes a coordinate.  Returns the device tensors
+        x[K, D], mu[K], iterations[K]; the unit box gives mean_ascent's bits."""
+        starts = self.dev(starts)
+        K, D = starts.shape
+        Dm = post.X.shape[1] if post.camphor is None else 6
+        if D != Dm:
+            raise ValueError(f"mean_ascent_boxes: starts have {D} columns, the model {Dm}")
+        bx = self._boxes(boxes, D, "mean_ascent_boxes")
+        md = self._model(post, False)
+        xs, mus = self.empty(K, D), self.empty(K)
+        its = torch.zeros(K, dtype=torch.int32, device=self.device)
+        rc = self.lib.ppbo_mean_ascent_boxes(self.ctx, C.byref(md), _ptr(starts), K, bx.ctypes.data_as(C.POINTER(C.c_double)),
+                                             bx.shape[0], int(per_box), int(iters), float(tol), _ptr(xs), _ptr(mus),
+                                             _ptr(its), self._stream())
+        self._check(rc, "ppbo_mean_ascent_boxes")
+        return xs, mus, its
+
+    def mean_search_boxes(self, post: Posterior, pool, boxes, shifts=None, seeds=None, K=32, sep=0.05, iters=100, tol=1e-9,
+                          screen_fp32=True):
+        """T searches of the posterior mean, trial t inside boxes[t] ([T, 2, D]: lo, hi; lo == hi fixes a coordinate), in
+        one enqueue (ppbo_mean_search_boxes).  The candidates of trial t are lo + (hi - lo) * frac(pool + shifts[t])
+        (shifts None: the pool itself) followed by seeds[t] ([T, S, D], clipped into the box).  Returns the device tensors
+        x[T, K, D], mu[T, K] (mu = -inf behind a trial's count) and count[T]; nothing synchronises."""
+        pool = self.dev(pool)
+        M, D = pool.shape
+        Dm = post.X.shape[1] if post.camphor is None else 6       # camphor: the search is in the caller's 6 coordinates
+        if D != Dm:
+            # the library strides pool, boxes, shifts and seeds by the MODEL's D: a mismatch would read out of bounds
+            raise ValueError(f"mean_search_boxes: pool has {D} columns, the model {Dm}")
+        bx = self._boxes(boxes, D, "mean_search_boxes")
+        T = bx.shape[0]
+        dp = C.POINTER(C.c_double)
+        sh = None
+        if shifts is not None:
+            sh = np.ascontiguousarray(np.atleast_2d(np.asarray(shifts, dtype=np.float64)))
+            if sh.shape != (T, D):
+                raise ValueError(f"mean_search_boxes: shifts must be [{T}, {D}]")
+        S, sd = 0, None
+        if seeds is not None:
+            sd = self.dev(seeds)
+            if sd.dim() != 3 or sd.shape[0] != T or sd.shape[2] != D:
+                raise ValueError(f"mean_search_boxes: seeds must be [{T}, S, {D}]")
+            sd = sd.contiguous()
+            S = sd.shape[1]
+            if S == 0:
+                sd = None
+        md = self._model(post, False)
+        xs, mus = self.empty(T, K, D), self.empty(T, K)
+        cnt = torch.zeros(T, dtype=torch.int32, device=self.device)
+        rc = self.lib.ppbo_mean_search_boxes(self.ctx, C.byref(md), _ptr(pool), M, sh.ctypes.data_as(dp) if sh is not None else None,
+                                             bx.ctypes.data_as(dp), T, _ptr(sd), S, int(K), float(sep), int(iters), float(tol),
+                                             int(bool(screen_fp32)), _ptr(xs), _ptr(mus), _ptr(cnt), self._stream())
+        self._check(rc, "ppbo_mean_search_boxes")
+        return xs, mus, cnt
+
     def shift_points(self, pool, shift, out=None):
         """out = frac(pool + shift) row-wise (ppbo_shift_points)."""
         pool = self.dev(pool)

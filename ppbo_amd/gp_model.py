@@ -30,6 +30,8 @@ SEARCH_CANDIDATES = 65536      # uniform candidates per mu_star trial
 ASCENT_STARTS = 32             # best well-separated candidates refined together on the device
 ASCENT_ITERS = 100             # cap on ascent iterations per start (all inside one mean_ascent_kernel launch)
 POLISH_GRAD_TOL = 1e-6         # |projected grad mu| / |mu| above which mu_star's winner gets the L-BFGS-B polish
+PROFILE_CANDIDATES = 4096      # pool rows per box of a profile (profile_effect, profile_interaction): T boxes share one call
+PROFILE_STARTS = 8             # ascents per box of a profile
 ARD_FIT_GTOL = 1e-6            # optimize_theta_ard: f_MAP tolerance of each evaluation (the gradient's implicit term
                                # assumes grad T = 0; its error is of the order of |grad T|)
 THETA_BOX = ((0.01, 2.0), (0.1, 15.0))    # the reference's search box for l and sigma_f (gp_model.py:397-398), sigma = 1
@@ -1380,3 +1382,125 @@ class GPModel:
         xstars_local = P[keep].reshape(-1, D)
         mustar = winner_mu.get(xstar.tobytes())
         return xstar.reshape(D,), (self.mu_pred(xstar) if mustar is None else mustar), xstars_local
+
+    # ------------------------------------------------------------------ maximisers inside boxes
+    def _box(self, lower=None, upper=None, fixed=None):
+        """(lo [D], hi [D]) in the model's unit coordinates from bounds and a dict {d: value} of fixed coordinates."""
+        D = int(self.D)
+        lo = np.zeros(D) if lower is None else np.array(lower, dtype=float).reshape(-1)
+        hi = np.ones(D) if upper is None else np.array(upper, dtype=float).reshape(-1)
+        if lo.size != D or hi.size != D:
+            raise ValueError(f"bounds of {lo.size} and {hi.size} entries for a model of {D} dimensions")
+        for d, v in (fixed or {}).items():
+            if not 0 <= int(d) < D:
+                raise ValueError(f"fixed coordinate {d} of a model of {D} dimensions")
+            lo[int(d)] = hi[int(d)] = float(v)
+        if not (np.all(np.isfinite(lo)) and np.all(np.isfinite(hi)) and np.all((0.0 <= lo) & (lo <= hi) & (hi <= 1.0))):
+            raise ValueError("a box needs 0 <= lower <= upper <= 1 in every coordinate")
+        return lo, hi
+
+    def mu_star_in(self, lower=None, upper=None, fixed=None, trials=None):
+        """(x, mu, xstars_local): the maximiser of the posterior mean inside the box lower <= x <= upper with the
+        coordinates of `fixed` ({d: value}) held -- a conditional optimum, a trust region, or both; bounds in the model's
+        unit coordinates, like X.  mu_star's recipe inside the box, every trial in one enqueue (ppbo_mean_search_boxes):
+        the resident pool rotated per trial and mapped into the box, the current x* clipped into it as a seed,
+        ASCENT_STARTS ascents per trial more than 0.05 of the longest side apart, and one more device ascent inside the box
+        (four times the budget) for a trial's winner that is not yet stationary.  xstars_local: the distinct maxima found
+        (more than 0.1 of the longest side apart), best first."""
+        lo, hi = self._box(lower, upper, fixed)
+        D = int(self.D)
+        trials = max(1, int(self.mustar_finding_trials if trials is None else trials))
+        post = self._mean_post()
+        side = float((hi - lo).max())
+        box = np.stack([lo, hi])
+        shifts = np.stack([np.random.uniform(0.0, 1.0, D) for _ in range(trials)])
+        seed = np.asarray(self.xstar if self.xstar is not None else self.X[0], dtype=float).reshape(1, 1, D)
+        xs_d, mu_d, _ = self.eng.mean_search_boxes(post, self._candidate_pool(), np.tile(box, (trials, 1, 1)), shifts=shifts,
+                                                   seeds=np.tile(seed, (trials, 1, 1)), K=ASCENT_STARTS, sep=5e-2 * side,
+                                                   iters=ASCENT_ITERS, tol=1e-9, screen_fp32=self.mustar_screen_fp32)
+        all_x, all_v = xs_d.cpu().numpy(), mu_d.cpu().numpy()
+        best = np.argmax(all_v, axis=1)                                  # found rows come first, -inf behind them
+        wx, wv = all_x[np.arange(trials), best], all_v[np.arange(trials), best]
+        _, gw = self.eng.mean_grad(post, wx)
+        gw = gw.cpu().numpy()
+        pg = np.where(((wx <= lo) & (gw < 0.0)) | ((wx >= hi) & (gw > 0.0)), 0.0, gw)
+        todo = np.flatnonzero(np.abs(pg).max(axis=1) > POLISH_GRAD_TOL * np.maximum(np.abs(wv), 1e-300))
+        if todo.size:
+            self.polish_log["device_reascents"] += int(todo.size)
+            xa, ma, _ = self.eng.mean_ascent_boxes(post, wx[todo], box[None], per_box=int(todo.size), iters=4 * ASCENT_ITERS,
+                                                   tol=1e-12)
+            xa, ma = xa.cpu().numpy(), ma.cpu().numpy()
+            for j, t in enumerate(todo):
+                if ma[j] >= all_v[t, best[t]]:
+                    all_x[t, best[t]], all_v[t, best[t]] = xa[j], ma[j]
+        ok = np.isfinite(all_v)
+        P, v = all_x[ok], all_v[ok]
+        order = np.argsort(-v, kind="stable")
+        P, v = P[order], v[order]
+        sq = (P * P).sum(axis=1)
+        d2 = np.maximum(sq[:, None] + sq[None, :] - 2.0 * (P @ P.T), 0.0)
+        struck, keep = np.zeros(len(P), dtype=bool), []
+        for i in range(len(P)):
+            if not struck[i]:
+                keep.append(i)
+                struck |= d2[i] <= (0.1 * side) ** 2
+                struck[i] = True
+        return P[0].copy(), float(v[0]), P[keep].reshape(-1, D)
+
+    def conditional_xstar(self, fixed):
+        """(x, mu, xstars_local): the best configuration with the coordinates of `fixed` ({d: value}) held at their
+        values and the others free -- mu_star_in with nothing but `fixed`."""
+        return self.mu_star_in(fixed=fixed)
+
+    def _profile(self, dims, values):
+        """max over the other coordinates of the posterior mean with x[dims] = values[t] for each row t of values [T, n]:
+        ONE ppbo_mean_search_boxes call of T boxes.  Trial t is seeded with x* and every known local maximum moved onto
+        its slice (x[dims] := values[t]), so the profile never falls below the slice through x*.  Returns mu [T], x [T, D],
+        var [T]."""
+        D = int(self.D)
+        T = values.shape[0]
+        if T * PROFILE_STARTS > 65536 or T > 4096:
+            raise ValueError(f"a profile of {T} grid points: at most {min(4096, 65536 // PROFILE_STARTS)} in one call")
+        if not np.all((values >= 0.0) & (values <= 1.0)):
+            raise ValueError("grid values outside the unit interval")
+        post = self._mean_post()
+        boxes = np.tile(np.stack([np.zeros(D), np.ones(D)]), (T, 1, 1))
+        boxes[:, :, dims] = values[:, None, :]
+        x0 = np.asarray(self.xstar if self.xstar is not None else self.X[0], dtype=float).reshape(1, D)
+        pts = x0 if self.xstars_local is None else np.vstack([x0, np.asarray(self.xstars_local, dtype=float).reshape(-1, D)])
+        seeds = np.tile(pts[:64][None], (T, 1, 1))
+        seeds[:, :, dims] = values[:, None, :]
+        pool = self._candidate_pool()[:PROFILE_CANDIDATES]
+        xs_d, mu_d, _ = self.eng.mean_search_boxes(post, pool, boxes, shifts=None, seeds=seeds, K=PROFILE_STARTS, sep=5e-2,
+                                                   iters=ASCENT_ITERS, tol=1e-9, screen_fp32=self.mustar_screen_fp32)
+        xs, mus = xs_d.cpu().numpy(), mu_d.cpu().numpy()
+        best = np.argmax(mus, axis=1)
+        x, mu = xs[np.arange(T), best], mus[np.arange(T), best]
+        var = self.eng.predict(self._var_post(), x, want_mu=False, want_var=True, want_best=False)["var"].cpu().numpy()
+        return mu, x, var
+
+    def profile_effect(self, d, grid=None):
+        """The profile of coordinate d (0-based): for every t of the grid the largest posterior mean over all points with
+        x_d = t, max over the OTHER coordinates -- how good the utility can still get as a function of x_d.  It
+        complements main_effect, which averages the others out (and needs a product kernel): a profile exists for every
+        kernel family, and unlike a slice through x* it does not understate the utility where coordinates interact.
+        Returns a dict t [T], mu [T], x [T, D] (the maximisers, x[:, d] == t), var [T] (the posterior variance there).
+        Default grid: 65 equispaced points of [0, 1]."""
+        g = self._effect_grid(grid)
+        if not 0 <= int(d) < int(self.D):
+            raise ValueError(f"coordinate {d} of a model of {self.D} dimensions")
+        mu, x, var = self._profile([int(d)], g.reshape(-1, 1))
+        return dict(t=g, mu=mu, x=x, var=var)
+
+    def profile_interaction(self, d, e, grid_d=None, grid_e=None):
+        """The two-dimensional profile over grid_d x grid_e (default 33 equispaced points each): mu [Td, Te] the largest
+        posterior mean with x_d and x_e held, x [Td, Te, D] its maximisers, var [Td, Te]; one search call for the whole
+        grid.  Returns a dict t_d, t_e, mu, x, var."""
+        gd, ge = self._effect_grid(grid_d, 33), self._effect_grid(grid_e, 33)
+        D = int(self.D)
+        if not (0 <= int(d) < D and 0 <= int(e) < D and int(d) != int(e)):
+            raise ValueError(f"coordinates {d}, {e} of a model of {D} dimensions: two different ones are required")
+        t = np.stack(np.meshgrid(gd, ge, indexing="ij"), axis=-1).reshape(-1, 2)
+        mu, x, var = self._profile([int(d), int(e)], t)
+        return dict(t_d=gd, t_e=ge, mu=mu.reshape(gd.size, ge.size), x=x.reshape(gd.size, ge.size, D),
+                    var=var.reshape(gd.size, ge.size))
