@@ -146,6 +146,7 @@ int ppbo_ctx_create(int device, ppbo_ctx** out) {
   c->kstar_star = env_int("PPBO_KSTAR_STAR", 1);
   c->prune = env_int("PPBO_PRUNE", 1);
   c->prune_cap = env_int("PPBO_PRUNE_CAP", 0);
+  c->prune_thin = env_int("PPBO_PRUNE_THIN", 1);
   c->gemm_big16 = env_int("PPBO_GEMM_BIG16", 1);
   c->fused_dbg = env_int("PPBO_FUSED_DBG", 0);
   {

@@ -56,6 +56,10 @@ struct ppbo_ctx {
   // three-launch path) contracts the variance only for the candidates that a certified bound cannot rule out
   // (predict_passes), 0 = always for all.  PPBO_PRUNE_CAP (tests): the survivor capacity per chunk, 0 = a chunk's eighth
   int prune = 1, prune_cap = 0;
+  // PPBO_PRUNE_THIN: 1 (default) = the compact launch of a pruned chunk with at most THIN_MAX survivors contracts them
+  // on 16-column thin tiles (quadform_thin, predict.hip: the same bits), 0 = always on the tile shape of the launch;
+  // a value above 1 (measurements: the sweep that set THIN_MAX) is the switch point itself
+  int prune_thin = 1;
   int gemm_big16 = 1;     // PPBO_GEMM_BIG16: large GEMMs on 16 wavefronts of 32 x 32 (default since round 6) instead of 8 of 32 x 64
   int n_cu = 0;           // compute units of the device (hipDeviceProp_t::multiProcessorCount)
   int fused_dbg = 0;      // PPBO_FUSED_DBG: measurement switches of fused.hip (results are wrong when set)

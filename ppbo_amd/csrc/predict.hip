@@ -1639,19 +1639,196 @@ __global__ __launch_bounds__(KS_THREADS) void kstar_marginal_kernel(
 // plan_compact = 0: today's launch over all candidates, which runs when the plan is not pruned.  A workgroup that does
 // not run returns before it touches an operand.
 constexpr int QF_NODE = 0, QF_EDGE = 1, QF_DENSE = 2;
-template <class C, int MINW, bool ALWAYS_FAST, int FORM, bool PLAN = false>
+
+// One column of a wavefront's TM accumulator tiles, squared and summed over the tiles' rows: each lane its own
+// TM x 4 entries (tile i outermost, register r inside, from 0.0), then the butterfly over the four lane groups of the
+// C/D layout (row = (lane >> 4) + 4 r, column = lane & 15).  Every lane returns the sum of column lane & 15.
+// The tile kernel and the thin one both end in this function: a column's bits do not depend on which of them ran.
+template <int TM>
+__device__ __forceinline__ double col_square_sum(const double4_t (&a)[TM]) {
+  // What `s = 0.0; s += a * a; ...` compiled to before the split, spelled out so that no instance can come out
+  // differently: the compiler contracted the sum of the first two squares as fma(a00, a00, a01 a01) -- the ROUNDED product
+  // is the second entry's -- and every later term as fma(a, a, s).
+  double s = a[0][1] * a[0][1];
+  s = __builtin_fma(a[0][0], a[0][0], s);
+#pragma unroll
+  for (int i = 0; i < TM; ++i)
+#pragma unroll
+    for (int r = (i == 0 ? 2 : 0); r < 4; ++r) s = __builtin_fma(a[i][r], a[i][r], s);
+  s += __shfl_xor(s, 16, 64);
+  s += __shfl_xor(s, 32, 64);
+  return s;
+}
+
+// ---- the thin contraction: a handful of survivors of a pruned chunk ------------------------------------------------------
+// The compact launch of a chunk with n_surv survivors contracts ceil(n_surv / 128) column tiles of 128: with 2 survivors
+// (the headline step) 4 workgroups run 16 wavefronts x 4 accumulator tiles over the whole K range on the matrix cores of
+// 4 CUs, 126 of every 128 columns padding.  Here a wavefront owns ONE 16 x 16 tile of Y = G Kc over the whole K range:
+// a workgroup takes a row tile mt and C::WN / C::TM groups of 16 columns, wavefront (cg, wm, i) the rows
+// [mt BM + (wm TM + i) 16, + 16) of column group cg.  No operand is shared through LDS and no barrier stands in the K
+// loop; two rounds of 4 k-steps are in flight per wavefront:
+//   * Kc: a k-step's fragment is four whole 128-byte rows of the column group -- straight to registers (buffer loads
+//     with a fixed per-lane offset, the K walk on the SALU);
+//   * G: a fragment read straight from memory takes 32 bytes of 16 lines, and the lines of rows a power of two apart
+//     evict each other before the next k-step returns to them (measured: 138 us at the headline shape against 70).
+//     A round's 16 x 16 block is therefore fetched as whole lines (two 16-byte loads per lane) and turned into fragments
+//     through a wavefront-private LDS image in gemm64's padded layout: the wavefront's own LDS accesses execute in
+//     order, so the image needs neither a second buffer nor a barrier.
+// Bit identity with the tile kernel, per output column:
+//   * Y[r, c] is one chain of v_mfma_f64_16x16x4 over k = 0, 4, 8, ... of the shifted operands, as in gemm64::mainloop;
+//   * the chain ends where the tile kernel's wavefront (wm) ends it: the whole range (dense form), the end of its TM 16
+//     rows (edge form), nowhere in the zero frame;
+//   * wavefronts i > 0 hand their tile to wavefront i = 0 through LDS, which forms col_square_sum over the TM tiles;
+//     the WM partials are added in the order w = 0 .. WM-1.
+// The host launches it only where the lean loop would run (every tile in bounds, K ranges whole chunks).
+// THIN_MAX: the largest n_surv that takes it.  profiles/r27_thin_contraction.txt, section 2: at the headline operator
+// (4 row tiles) the thin path is ahead by 127 - 158 us at every count from 2 up to the 2048 its grid can hold (a quarter
+// of the capacity), and a second column group on a workgroup costs 47 us.  It reads the operator once per 32 columns
+// where the tiles read it once per 128, which only a launch that leaves most of the part idle can afford: 256 keeps
+// it to 8 workgroups per row tile, the range in which the tiles' grid (2 column tiles) cannot fill the part either.
+constexpr int THIN_MAX = 256;
+
+__device__ __forceinline__ double buffer_load1(const double* __restrict__ sbase, unsigned byte_off, int sbyte_off) {
+  typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+  const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(sbase), 0, -1, 0x00020000);
+  return __builtin_bit_cast(double, (u32x2)__builtin_amdgcn_raw_buffer_load_b64(r, (int)byte_off, sbyte_off, 0));
+}
+__device__ __forceinline__ double2 buffer_load2s(const double* __restrict__ sbase, unsigned byte_off, int sbyte_off) {
+  const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(sbase), 0, -1, 0x00020000);
+  return __builtin_bit_cast(double2, __builtin_amdgcn_raw_buffer_load_b128(r, (int)byte_off, sbyte_off, 0));
+}
+
+template <class C>
+struct Thin {
+  static constexpr int NW = C::NT / 64;                 // wavefronts of the launch's workgroup
+  static constexpr int NSUB = C::WM * C::TM;            // 16-row tiles of a row tile
+  static constexpr int CG = C::WN / C::TM;              // column groups of a workgroup
+  static constexpr int COLS = 16 * CG;
+  static constexpr int IMG = 16 * KC_LD;                // a wavefront's LDS image: [16 rows][16 + 2], doubles
+  static constexpr bool OK = (C::WN % C::TM == 0);      // (Cfg<2,2,4,4> has fewer wavefronts than 16-row tiles: tile path)
+};
+
+// One round of a thin chain: 4 k-steps from operands that are already in registers -- G's 16 x 16 block as whole lines in
+// `raw` (lane -> row (lane >> 3) + 8 h, k 2 (lane & 7)), Kc's fragments in `b` -- and the loads of round `nxt` into the
+// same registers.
+__device__ __forceinline__ void thin_round(const double* __restrict__ A, int lda, const double* __restrict__ B, int ldb,
+                                           int nxt, unsigned offA, unsigned offB, int wr, int rd, double2 (&raw)[2],
+                                           double (&b)[4], double4_t& acc) {
+  *reinterpret_cast<double2*>(&lds_dyn[wr]) = raw[0];
+  *reinterpret_cast<double2*>(&lds_dyn[wr + 8 * KC_LD]) = raw[1];
+  const double* pa = A + (size_t)nxt * BK;
+  const double* pb = B + (size_t)nxt * BK * ldb;
+  raw[0] = buffer_load2s(pa, offA, 0);
+  raw[1] = buffer_load2s(pa, offA, 64 * lda);
+  __builtin_amdgcn_wave_barrier();                     // (the image is the wavefront's own: program order is enough)
+  double a[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) a[j] = lds_dyn[rd + 4 * j];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[j], b[j], acc, 0, 0, 0);
+    b[j] = buffer_load1(pb, offB, j * 32 * ldb);
+  }
+  __builtin_amdgcn_wave_barrier();
+}
+
+template <class C, int FORM>
+__device__ __forceinline__ void quadform_thin(const double* __restrict__ G, int N, const double* __restrict__ Kt, int ldk,
+                                              int M, double* __restrict__ slab, int mt, int grp, int n_live, int n_rows,
+                                              int kshift) {
+  static_assert(FORM == QF_EDGE || FORM == QF_DENSE, "the pruned search contracts an edge-form or a projected operator");
+  using T = Thin<C>;
+  static_assert(T::IMG >= 256 && C::LDS_DOUBLES >= T::NW * T::IMG + T::CG * C::WM * 16, "images and hand-over fit the launch's LDS");
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int cg = wave / T::NSUB, sub = wave % T::NSUB, wm = sub / C::TM, ti = sub % C::TM;
+  const int m0 = mt * C::BM, n0 = grp * T::COLS;
+  // the K cut of the tile kernel's wavefront wm (quadform_kernel below)
+  const int e = FORM == QF_DENSE ? N : m0 + C::BM;
+  const int kend = (e < N ? e : N) - kshift;
+  const int wrow_beg = m0 + wm * C::TM * 16;
+  const int wk = FORM == QF_DENSE ? kend : wrow_beg >= n_rows ? 0 : wrow_beg + C::TM * 16 - kshift;
+  const int kmax = (n0 + cg * 16 < n_live) ? (wk < kend ? wk : kend) : 0;   // (a column group beyond the survivors: nothing)
+  const int img = wave * T::IMG;                       // this wavefront's image; its hand-over tile afterwards
+  double4_t acc = {0.0, 0.0, 0.0, 0.0};
+  if (kmax > 0) {
+    const int nr = kmax / BK;                          // (K ranges are whole chunks on this path)
+    const unsigned offA = (unsigned)((((sub * 16 + (lane >> 3)) * N) + (lane & 7) * 2) * 8);
+    const unsigned offB = (unsigned)((((lane >> 4) * ldk) + cg * 16 + (lane & 15)) * 8);
+    const int wr = img + (lane >> 3) * KC_LD + (lane & 7) * 2, rd = img + (lane & 15) * KC_LD + (lane >> 4);
+    const double* A = G + (size_t)m0 * N;
+    const double* B = Kt + n0;
+    double2 raw0[2], raw1[2];
+    double b0[4], b1[4];
+    const int r1 = nr > 1 ? 1 : 0;
+    raw0[0] = buffer_load2s(A, offA, 0);
+    raw0[1] = buffer_load2s(A, offA, 64 * N);
+    raw1[0] = buffer_load2s(A + (size_t)r1 * BK, offA, 0);
+    raw1[1] = buffer_load2s(A + (size_t)r1 * BK, offA, 64 * N);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      b0[j] = buffer_load1(B, offB, j * 32 * ldk);
+      b1[j] = buffer_load1(B + (size_t)r1 * BK * ldk, offB, j * 32 * ldk);
+    }
+    int r = 0;
+    // two rounds per turn, each refilling its registers for the round after next (the last rounds re-read the final
+    // one: no branch in the body)
+    for (; r + 2 <= nr; r += 2) {
+      thin_round(A, N, B, ldk, r + 2 < nr ? r + 2 : nr - 1, offA, offB, wr, rd, raw0, b0, acc);
+      thin_round(A, N, B, ldk, r + 3 < nr ? r + 3 : nr - 1, offA, offB, wr, rd, raw1, b1, acc);
+    }
+    if (r < nr) thin_round(A, N, B, ldk, nr - 1, offA, offB, wr, rd, raw0, b0, acc);
+  }
+  double* xch = lds_dyn + img;                         // [4][64]: the tile of a wavefront i > 0
+  double* red = lds_dyn + T::NW * T::IMG;              // [CG][WM][16]
+  if (ti != 0) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) xch[q * 64 + lane] = acc[q];
+  }
+  __syncthreads();
+  if (ti == 0) {
+    double4_t col[C::TM];
+    col[0] = acc;
+#pragma unroll
+    for (int i = 1; i < C::TM; ++i)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) col[i][q] = xch[i * T::IMG + q * 64 + lane];
+    const double s = col_square_sum<C::TM>(col);
+    if (lane < 16) red[(cg * C::WM + wm) * 16 + lane] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x < T::COLS) {
+    const int c = n0 + threadIdx.x;
+    double t = 0.0;
+#pragma unroll
+    for (int w = 0; w < C::WM; ++w) t += red[((threadIdx.x >> 4) * C::WM + w) * 16 + (threadIdx.x & 15)];
+    if (c < n_live) slab[(size_t)mt * M + c] = t;
+  }
+}
+
+// THIN (the compact launch of a pruned search, lean operands): a chunk with at most thin_max survivors is contracted by
+// quadform_thin on the first ntm ceil(n_surv / COLS) workgroups of the grid; any other chunk by the tiles below.
+template <class C, int MINW, bool ALWAYS_FAST, int FORM, bool PLAN = false, bool THIN = false>
 __global__ __launch_bounds__(C::NT, MINW) void quadform_kernel(const double* __restrict__ G, int N,
                                                                const double* __restrict__ Kt, int ldk, int M,
                                                                int tri_block, double* __restrict__ slab, int ntm,
                                                                int ntn, int swizzle, int n_rows, int kshift,
                                                                const PrunePlan* __restrict__ plan = nullptr,
-                                                               int plan_compact = 0) {
+                                                               int plan_compact = 0, int thin_max = 0) {
   int n_live = M;                      // PLAN: the columns of this launch that anything reads
   (void)n_live;
   if constexpr (PLAN) {
     const int pruned = uniform_load_int(&plan->pruned);
     if ((pruned != 0) != (plan_compact != 0)) return;
     if (plan_compact) n_live = uniform_load_int(&plan->n_surv);
+  }
+  if constexpr (THIN) {
+    static_assert(PLAN && ALWAYS_FAST && Thin<C>::OK, "the thin path: the compact launch on lean operands");
+    const int ng = (n_live + Thin<C>::COLS - 1) / Thin<C>::COLS;
+    if (n_live <= thin_max && ng * ntm <= (int)gridDim.x) {
+      if ((int)blockIdx.x >= ng * ntm) return;
+      quadform_thin<C, FORM>(G, N, Kt, ldk, M, slab, (int)blockIdx.x % ntm, (int)blockIdx.x / ntm, n_live, n_rows, kshift);
+      return;
+    }
   }
   int mt, nt;                          // the walk (XCD remap, candidate- or row-tile fastest, chunks): tile_walk.h
   ppbo_qf_tile(blockIdx.x, gridDim.x, swizzle, ntm, ntn, mt, nt);
@@ -1679,13 +1856,10 @@ __global__ __launch_bounds__(C::NT, MINW) void quadform_kernel(const double* __r
   double* red = lds_dyn;  // [WM][BN]; mainloop ended with a barrier
 #pragma unroll
   for (int j = 0; j < C::TN; ++j) {
-    double s = 0.0;
+    double4_t col[C::TM];
 #pragma unroll
-    for (int i = 0; i < C::TM; ++i)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) s += acc[i][j][r] * acc[i][j][r];
-    s += __shfl_xor(s, 16, 64);
-    s += __shfl_xor(s, 32, 64);
+    for (int i = 0; i < C::TM; ++i) col[i] = acc[i][j];
+    const double s = col_square_sum<C::TM>(col);
     if (lane < 16) red[wm * C::BN + (wn * C::TN + j) * 16 + lane] = s;
   }
   __syncthreads();
@@ -1747,7 +1921,23 @@ int launch_quadform(ppbo_ctx* ctx, const double* G, int N, int g_rows, int n_row
     quadform_kernel<C, MINW, FAST, FORM, true><<<grid, C::NT, lds, s>>>(Gs, N, Ks, ldk, Mc, mblk, slab, ntm, ntn, swz, \
                                                                         n_rows, kshift, plan, plan_compact);         \
   } while (0)
-    if (dense && fast) QF_PLAN(true, QF_DENSE);
+    // the compact launch on lean operands carries the thin path (PPBO_PRUNE_THIN; its per-lane byte offsets are 32-bit)
+    const int thin_max = ctx->prune_thin == 1 ? THIN_MAX : ctx->prune_thin;
+    const bool thin = Thin<C>::OK && plan_compact && fast && thin_max > 0 &&
+                      (size_t)C::BM * (size_t)N < ((size_t)1 << 28) && ldk < (1 << 20);
+    if (thin) {
+      if constexpr (Thin<C>::OK) {
+#define QF_THIN(FORM)                                                                                                \
+  do {                                                                                                               \
+    ppbo_lds_limit(ctx, (const void*)quadform_kernel<C, MINW, true, FORM, true, true>, (int)lds);                    \
+    quadform_kernel<C, MINW, true, FORM, true, true><<<grid, C::NT, lds, s>>>(Gs, N, Ks, ldk, Mc, mblk, slab, ntm, ntn, swz, \
+                                                                              n_rows, kshift, plan, plan_compact, thin_max); \
+  } while (0)
+        if (dense) QF_THIN(QF_DENSE);
+        else QF_THIN(QF_EDGE);
+#undef QF_THIN
+      }
+    } else if (dense && fast) QF_PLAN(true, QF_DENSE);
     else if (dense) QF_PLAN(false, QF_DENSE);
     else if (fast) QF_PLAN(true, QF_EDGE);
     else QF_PLAN(false, QF_EDGE);
