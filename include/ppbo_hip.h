@@ -765,6 +765,50 @@ PPBO_API int ppbo_mean_search_boxes(ppbo_ctx* ctx, const ppbo_model* model, cons
                            double sep, int iters, double tol, int screen_fp32, double* d_x, double* d_mu, int* d_count,
                            void* stream);
 
+/* ---- acquisition gradients and their ascent (no reference counterpart) --------------------------------------------------
+ * The reference evaluates EI and varmax on lines (src/acquisition.py:72-81, 170-178) and has no gradient of either; the
+ * ppbo_predict* and ppbo_search_* entries here return pool rows.  These two entries give the pointwise EI and the posterior variance
+ * their analytic gradients and a continuous maximiser.  Everything is in the MODEL's coordinates, as for every
+ * ppbo_predict* entry (model->coords is not applied; callers scale ARD points, boxes and gradients themselves).
+ * With k = k(x, X), J = dk/dx (analytic, direct differences) and M the variance operator of model->form:
+ *   mu = k' alpha,  grad mu = J' alpha;   var = sigma_f^2 + k' Lambda k + |M k|^2,  grad var = 2 J' u,  u = (Lambda + M'M) k
+ *   score: ppbo_predict's.  MEAN: grad mu.  VARIANCE: grad var.  POINTWISE_EI with sd = sqrt(max(var, 0)) > 0 and
+ *   z = (mu - mustar) / sd: Phi(z) grad mu + phi(z) grad var / (2 sd); with sd = 0: grad mu where mu > mustar, else 0.
+ * var is formed as ppbo_predict forms it (the Lambda term and the sum of squares of M k), not from k'u, which cancels; mu
+ * as ppbo_mean_grad forms it.  A point with a non-finite coordinate gets NaN in every output and disturbs no other row.
+ *
+ * ppbo_acq_grad: d_X[M,D] -> d_mu, d_var, d_score [M] and d_grad_mu, d_grad_var, d_grad_score [M,D]; each may be NULL,
+ * not all.  Points go in chunks of at most 1024: per chunk the tournament's field pass (K*, Y = M K*, U = (Lambda + M'M) K*)
+ * with its GEMM tile configuration pinned and a row split that depends on the model alone, then one workgroup per point
+ * (a value pass and one pass over the design rows per requested gradient).  With score_kind MEAN and neither d_var nor
+ * d_grad_var the operator is not read and no field pass runs.
+ *
+ * ppbo_acq_ascent: K <= 1024 starts d_starts[K,D] refined in lockstep inside ONE box h_box[2,D] (lo then hi, host, finite,
+ * lo <= hi, any range: an ARD model's unit box is [0, s_d]; NULL = the unit box; lo_d == hi_d fixes coordinate d).  The
+ * iteration is ppbo_mean_ascent_boxes' with the score in the place of the mean: clip the start; first step
+ * 0.02 max_d (hi_d - lo_d) / max(|g|, 1e-300); stop when |projected g| step < tol; trial point clip(x + step pg); accept iff
+ * s_new >= s (a NaN fails); Barzilai-Borwein step ss / curv when curv > 0, else twice the step; a quarter of it after a
+ * rejection.  One evaluation round per iteration for all K starts together -- ppbo_acq_grad's launches on the K trial
+ * points, then one judging launch (a wavefront per start) -- iters + 1 rounds, all enqueued: nothing synchronises, and a
+ * start that has stopped repeats its point.  iters = 0 returns the clipped starts and the values there.
+ * d_x[K,D], d_score[K], d_mu[K], d_var[K]: the refined points and ppbo_acq_grad's values there; d_iters[K] (optional): the
+ * evaluated moves.  A start with a NaN coordinate keeps it, gets NaN values and 0 iterations.
+ * Bits: a round's values are those ppbo_acq_grad returns for the same point; a start's result does not depend on K, on its
+ * position or on the other starts; M points in one call equal any split of them over several; no atomics, every sum in
+ * a fixed order, so a repeated call is bitwise equal.
+ * "invalid argument", with nothing launched and the outputs untouched: a NULL model, points or (ascent) output; every
+ * output of ppbo_acq_grad NULL; M outside 1 .. 2^31 - 1; K outside 1 .. 1024; iters outside 0 .. 1000; tol negative or not
+ * finite; a box with lo > hi or a non-finite bound; an unknown score_kind; model->kstar_fp32 set (fp64 only); a
+ * PPBO_COORDS_CAMPHOR model (a box in x is not a box in e(x)); where the operator is read (ppbo_acq_ascent always: d_var
+ * is an output), a model without d_G or Lambda or with a form outside {PPBO_FORM_NODE, PPBO_FORM_EDGE}.
+ * The field passes are timed as "acq_field", the launches of acq_grad_kernel as "acq_grad" (ppbo_profile_read). */
+PPBO_API int ppbo_acq_grad(ppbo_ctx* ctx, const ppbo_model* model, const double* d_X, int64_t M, int score_kind,
+                  double mustar, double* d_mu, double* d_var, double* d_score, double* d_grad_mu, double* d_grad_var,
+                  double* d_grad_score, void* stream);
+PPBO_API int ppbo_acq_ascent(ppbo_ctx* ctx, const ppbo_model* model, const double* d_starts, int K, const double* h_box,
+                    int score_kind, double mustar, int iters, double tol, double* d_x, double* d_score, double* d_mu,
+                    double* d_var, int* d_iters, void* stream);
+
 /* ---- into a model's coordinates ("the coordinate map of a model" above) ------------------------------------------------ */
 PPBO_API int ppbo_scale_points(ppbo_ctx* ctx, const double* d_in, int64_t M, int D, const double* h_scale, double* d_out,
                       void* stream);

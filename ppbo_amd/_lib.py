@@ -157,6 +157,8 @@ SIGNATURES = {
     "ppbo_mean_ascent_boxes": [_vp, C.POINTER(Model), _vp, _i, C.POINTER(_d), _i, _i, _i, _d, _vp, _vp, _vp, _vp],
     "ppbo_mean_search_boxes": [_vp, C.POINTER(Model), _vp, _i64, C.POINTER(_d), C.POINTER(_d), _i, _vp, _i, _i, _d, _i, _d, _i,
                                _vp, _vp, _vp, _vp],
+    "ppbo_acq_grad": [_vp, C.POINTER(Model), _vp, _i64, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "ppbo_acq_ascent": [_vp, C.POINTER(Model), _vp, _i, C.POINTER(_d), _i, _d, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp],
     "ppbo_scale_points": [_vp, _vp, _i64, _i, C.POINTER(_d), _vp, _vp],
     "ppbo_camphor_embed": [_vp, _vp, _i64, C.POINTER(_d), _vp, _vp],
     "ppbo_camphor_line_points": [_vp, _vp, _vp, _vp, _i, _i, _i, C.POINTER(_d), _vp, _vp],

@@ -38,7 +38,7 @@ struct ppbo_ctx {
   unsigned upload_next = 0;
   // optional per-kernel event timing
   bool profiling = false;
-  enum { PF_GRAM = 0, PF_KSTAR, PF_QUADFORM, PF_SCORE, PF_RFF_PROJECT, PF_RFF_SCORE, PF_POTRF, PF_LINE_KSTAR, PF_LINE_Y, PF_LINE_COV, PF_LINE_MC, PF_FUSED, PF_TOURNAMENT, PF_TOURNAMENT_FIELD, PF_BATCH_STEP, PF_BATCH_FIELD, PF_GRAD_KSTAR, PF_GRAD_FINISH, PF_COUNT };
+  enum { PF_GRAM = 0, PF_KSTAR, PF_QUADFORM, PF_SCORE, PF_RFF_PROJECT, PF_RFF_SCORE, PF_POTRF, PF_LINE_KSTAR, PF_LINE_Y, PF_LINE_COV, PF_LINE_MC, PF_FUSED, PF_TOURNAMENT, PF_TOURNAMENT_FIELD, PF_BATCH_STEP, PF_BATCH_FIELD, PF_GRAD_KSTAR, PF_GRAD_FINISH, PF_ACQ_FIELD, PF_ACQ_GRAD, PF_COUNT };
   std::vector<std::pair<hipEvent_t, hipEvent_t>> pf_events[PF_COUNT];
   size_t pf_used[PF_COUNT] = {};
   // kernels whose dynamic-LDS limit has been raised on THIS ctx's device (hipFuncSetAttribute is per device)
@@ -128,6 +128,12 @@ int ppbo_predict_record_publish(ppbo_ctx* ctx, const ppbo_model* model, const do
 // predict.hip, for project.hip: E [N][ld] = the edge-layout rows of the node-layout Kt [N][ld] (edge_apply_kernel), M columns
 int ppbo_edge_apply_async(ppbo_ctx* ctx, const double* Kt, int ld, int M, int N, int mblk, const double* d_lam_off, double* E,
                           hipStream_t s);
+// predict.hip, for acq.hip: the field pass of a tournament, U [NkU][ldu] = (Lambda + M'M) K* for the Mb <= 1024 points d_Xb
+// in the row layout of the model's form, beside K* (KB, node layout) and Y = M K* [N][ldu] each; Z [N][ldu] is scratch,
+// part_b [n_split_b_eff][Mb] the mean partials of its K* launch.  gemm_cfg: GemmArgs.force_cfg of its two GEMMs
+extern "C" int tournament_field(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xb, int Mb, int ldu, int NkU,
+                                double* KB, double* Y, double* Z, double* U, double* part_b, int q_per_split_b,
+                                int n_split_b_eff, hipStream_t s, int gemm_cfg = 0);
 
 // first row / column of an edge-form operator that the contractions read: the n_q observation coordinates hold zeros,
 // the K loops start at n_q rounded down to the chunk depth

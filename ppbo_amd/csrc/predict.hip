@@ -3939,10 +3939,11 @@ int ppbo_predict_marginals(ppbo_ctx* ctx, const ppbo_model* model, const ppbo_ma
 
 // The field pass of a tournament: U [NkU][ldu] = u_b = (Lambda + M'M) k_b for the Mb opponents d_Xb, in the row layout of the
 // model's form (see tournament_kernel).  KB, Y, Z: [N][ldu] each; part_b: the mean partials of the field's own K* launch
-// (not read).  Touches no workspace of predict_passes.  ppbo_search_batch runs it per pick with Mb = 1.
-static int tournament_field(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xb, int Mb, int ldu, int NkU, double* KB,
-                            double* Y, double* Z, double* U, double* part_b, int q_per_split_b, int n_split_b_eff,
-                            hipStream_t s) {
+// (not read).  Touches no workspace of predict_passes.  ppbo_search_batch runs it per pick with Mb = 1.  Declared in
+// common.h for acq.hip, which pins the tile configuration of the two GEMMs (gemm_cfg = GemmArgs.force_cfg; 0: by size).
+int tournament_field(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xb, int Mb, int ldu, int NkU, double* KB,
+                     double* Y, double* Z, double* U, double* part_b, int q_per_split_b, int n_split_b_eff,
+                     hipStream_t s, int gemm_cfg) {
   const int N = model->N, mblk = model->m + 1, n_q = N / mblk;
   const bool edge = model->form == PPBO_FORM_EDGE;
   PPBO_HIP_CHECK(ctx, hipMemsetAsync(U, 0, (size_t)NkU * ldu * sizeof(double), s));
@@ -3951,6 +3952,7 @@ static int tournament_field(ppbo_ctx* ctx, const ppbo_model* model, const double
   GemmArgs y{};
   y.A = model->d_G; y.lda = N; y.B = KB; y.ldb = ldu; y.C = Y; y.ldc = ldu;
   y.M = N; y.N = Mb; y.K = N; y.alpha = 1.0; y.beta = 0.0; y.khi_mode = 1; y.tri_block = mblk;
+  y.force_cfg = gemm_cfg;
   if (edge) {
     edge_apply_kernel<<<dim3((Mb + 127) / 128, N), 128, 0, s>>>(KB, ldu, Mb, mblk, n_q, model->d_lam_off, Z);
     PPBO_LAUNCH_CHECK(ctx);
@@ -3965,6 +3967,7 @@ static int tournament_field(ppbo_ctx* ctx, const ppbo_model* model, const double
   GemmArgs u{};
   u.A = model->d_G; u.lda = N; u.B = Y; u.ldb = ldu; u.C = U; u.ldc = ldu;
   u.M = N; u.N = Mb; u.K = N; u.alpha = 1.0; u.beta = 1.0; u.tri_block = 1;
+  u.force_cfg = gemm_cfg;
   if (int rc = ppbo_gemm_launch(ctx, u, 1, 0, s)) return rc;       // U += G' Y
   return 0;
 }

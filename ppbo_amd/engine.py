@@ -1378,6 +1378,71 @@ class Engine:
         self._check(rc, "ppbo_mean_search_boxes")
         return xs, mus, cnt
 
+    ACQ_MAX_K = 1024   # starts per ppbo_acq_ascent call
+
+    def _acq_args(self, what, post: Posterior, X, score):
+        """The refusals of acq_grad / acq_ascent that need no device: (points in the model's coordinates, scale or None)."""
+        if post.camphor is not None:
+            raise ValueError(f"{what}: no form for camphor_copper_ard_kernel (a box in x is not a box in the embedding)")
+        if score not in (SCORE_MEAN, SCORE_POINTWISE_EI, SCORE_VARIANCE):
+            raise ValueError(f"{what}: unknown score kind {score!r}")
+        shape = tuple(np.shape(X))
+        D = post.X.shape[1]
+        if len(shape) != 2 or shape[1] != D or shape[0] < 1:
+            raise ValueError(f"{what}: points of shape {shape}; [M, {D}] with M >= 1 is required")
+        return self._points(post, X), post.scale
+
+    def acq_grad(self, post: Posterior, X, score=SCORE_POINTWISE_EI, mustar=0.0, want_values=True, want_grad_mu=True,
+                 want_grad_var=True, want_grad_score=True):
+        """Values and gradients of the acquisition at the rows of X [M, D], in the caller's coordinates (ppbo_acq_grad):
+        device tensors mu, var, score [M] (None unless want_values) and grad_mu, grad_var, grad_score [M, D] (None where
+        not asked for).  score: SCORE_MEAN, SCORE_POINTWISE_EI (over mustar) or SCORE_VARIANCE.  ARD: the device works on
+        s (.) x and d / d x_d = s_d d / d x~_d.  ValueError for shape errors, an unknown score kind, nothing asked for, and
+        a camphor_copper_ard_kernel posterior."""
+        pts, scale = self._acq_args("acq_grad", post, X, score)
+        if not (want_values or want_grad_mu or want_grad_var or want_grad_score):
+            raise ValueError("acq_grad: nothing asked for")
+        M, D = pts.shape
+        md = self._model(post, True)
+        mu, var, sc = (self.empty(M), self.empty(M), self.empty(M)) if want_values else (None, None, None)
+        gm, gv, gs = (self.empty(M, D) if w else None for w in (want_grad_mu, want_grad_var, want_grad_score))
+        rc = self.lib.ppbo_acq_grad(self.ctx, C.byref(md), _ptr(pts), M, int(score), float(mustar), _ptr(mu), _ptr(var),
+                                    _ptr(sc), _ptr(gm), _ptr(gv), _ptr(gs), self._stream())
+        self._check(rc, "ppbo_acq_grad")
+        if scale is not None:
+            for g in (gm, gv, gs):
+                if g is not None:
+                    self.scale_points(g, scale, out=g)
+        return dict(mu=mu, var=var, score=sc, grad_mu=gm, grad_var=gv, grad_score=gs)
+
+    def acq_ascent(self, post: Posterior, starts, score=SCORE_POINTWISE_EI, mustar=0.0, lower=None, upper=None, iters=60,
+                   tol=1e-9):
+        """K <= ACQ_MAX_K starts [K, D] refined by the projected Barzilai-Borwein ascent on the score inside the box
+        lower <= x <= upper (None: 0 and 1; lower_d == upper_d fixes a coordinate), all in the caller's coordinates
+        (ppbo_acq_ascent; nothing synchronises).  Returns device tensors x [K, D], score, mu, var [K] and iters [K]
+        (int32).  ARD: the device climbs in s (.) x inside [lower s, upper s] (tol is measured there) and x comes back
+        divided by s."""
+        pts, scale = self._acq_args("acq_ascent", post, starts, score)
+        K, D = pts.shape
+        if K > self.ACQ_MAX_K:
+            raise ValueError(f"acq_ascent: {K} starts; at most {self.ACQ_MAX_K} per call")
+        lo = np.zeros(D) if lower is None else np.asarray(lower, dtype=np.float64).reshape(-1)
+        hi = np.ones(D) if upper is None else np.asarray(upper, dtype=np.float64).reshape(-1)
+        if lo.size != D or hi.size != D:
+            raise ValueError(f"acq_ascent: bounds of {lo.size} and {hi.size} entries for a model of {D} dimensions")
+        box = np.ascontiguousarray(np.stack([lo, hi]) * (1.0 if scale is None else scale))
+        md = self._model(post, True)
+        xs, sc, mu, var = self.empty(K, D), self.empty(K), self.empty(K), self.empty(K)
+        its = torch.zeros(K, dtype=torch.int32, device=self.device)
+        rc = self.lib.ppbo_acq_ascent(self.ctx, C.byref(md), _ptr(pts), K, self._dptr(box), int(score), float(mustar),
+                                      int(iters), float(tol), _ptr(xs), _ptr(sc), _ptr(mu), _ptr(var), _ptr(its),
+                                      self._stream())
+        self._check(rc, "ppbo_acq_ascent")
+        if scale is not None:       # back to the caller's coordinates, and into the caller's box to the last bit
+            self.scale_points(xs, 1.0 / scale, out=xs)
+            xs = torch.minimum(torch.maximum(xs, self.dev(lo)), self.dev(hi))
+        return dict(x=xs, score=sc, mu=mu, var=var, iters=its)
+
     def shift_points(self, pool, shift, out=None):
         """out = frac(pool + shift) row-wise (ppbo_shift_points)."""
         pool = self.dev(pool)

@@ -1242,6 +1242,46 @@ class GPModel:
         X = cand[torch.as_tensor(idx, device=cand.device)].cpu().numpy() if idx.size else np.zeros((0, self.D))
         return X, idx, out["score"][keep]
 
+    _ACQ_KINDS = {"mean": SCORE_MEAN, "EI": SCORE_POINTWISE_EI, "variance": SCORE_VARIANCE}
+
+    def acquisition_grad(self, X, score="EI"):
+        """dict(mu, var, score [M], grad_mu, grad_var, grad_score [M, D]) as NumPy arrays: the posterior mean, the variance
+        and the acquisition `score` -- "EI" (pointwise expected improvement over self.mustar), "variance" or "mean" -- at
+        the rows of X with their analytic gradients, in the caller's coordinates (ppbo_acq_grad; no reference
+        counterpart).  One point may be given as a 1-D vector."""
+        if score not in self._ACQ_KINDS:
+            raise ValueError(f"acquisition_grad: score {score!r}; \"EI\", \"variance\" or \"mean\" is required")
+        post = self._var_post()
+        X = X if isinstance(X, torch.Tensor) else np.asarray(X, dtype=float)
+        X = X.reshape(1, -1) if X.ndim == 1 else X
+        return self._numpy(self.eng.acq_grad(post, X, score=self._ACQ_KINDS[score],
+                                             mustar=0.0 if self.mustar is None else float(self.mustar)))
+
+    def maximize_acquisition(self, score="EI", n_starts=16, X_cand=None, lower=None, upper=None, fixed=None, iters=60):
+        """The continuous maximiser of the acquisition `score` ("EI" or "variance") inside the box lower <= x <= upper with
+        the coordinates of `fixed` ({d: value}) held: shortlist(q=n_starts, score, X_cand)'s picks -- spread over the
+        basins by the conditioned variance -- clipped into the box, each refined by the device ascent on the analytic
+        gradient (ppbo_acq_ascent; no reference counterpart), then the best.  Returns dict(x [D], score, mu, var, starts
+        [K, D], start_scores [K] (the shortlist's, at the time of each pick), xs [K, D], scores [K], iters [K]).  The
+        ascent is monotone, so with the default box scores[k] is never below the score of starts[k]."""
+        kinds = {"EI": SCORE_POINTWISE_EI, "variance": SCORE_VARIANCE}
+        if score not in kinds:
+            raise ValueError(f"maximize_acquisition: score {score!r}; \"EI\" or \"variance\" is required")
+        lo, hi = self._box(lower, upper, fixed)
+        post = self._var_post()
+        starts, _, start_scores = self.shortlist(q=int(n_starts), score=score, X_cand=X_cand)
+        if not len(starts):
+            raise ValueError("maximize_acquisition: the shortlist found no scoreable candidate")
+        out = self._numpy(self.eng.acq_ascent(post, starts, score=kinds[score],
+                                              mustar=0.0 if self.mustar is None else float(self.mustar), lower=lo, upper=hi,
+                                              iters=int(iters)))
+        ok = np.flatnonzero(~np.isnan(out["score"]))
+        if not ok.size:
+            raise ValueError("maximize_acquisition: no start has a score")
+        b = int(ok[np.argmax(out["score"][ok])])
+        return dict(x=out["x"][b].copy(), score=float(out["score"][b]), mu=float(out["mu"][b]), var=float(out["var"][b]),
+                    starts=starts, start_scores=start_scores, xs=out["x"], scores=out["score"], iters=out["iters"])
+
     def mu_pred(self, X_pred):
         x = np.asarray(X_pred, dtype=float).reshape(1, self.D)
         out = self.eng.predict(self._mean_post(), x, score=SCORE_MEAN, want_var=False, want_best=False)
