@@ -866,6 +866,49 @@ PPBO_API int ppbo_line_choice_xi(ppbo_ctx* ctx, const ppbo_model* model, const d
                         const double* d_e, int S, double noise_sd, double jitter, double* d_prob, int* d_count,
                         int* d_choice, void* stream);
 
+/* ---- scoring the answers: leave-one-query-out and held-out predictive checks ------------------------------------------
+ * How well does the model explain an answer?  The likelihood of an answer is sum_Phi's per-query term
+ * (src/gp_model.py:176-226): for a star of G = m + 1 points, point 0 the one the user chose,
+ *   l(f) = -(1/m) sum_j Phi((f_j - f_0) / (sigma sqrt 2)).
+ * Both entries below have no reference counterpart: the reference has no predictive score of its answers.  A group with
+ * mean mu and covariance C is scored by
+ *   edge probabilities  p_j  = Phi((mu_0 - mu_j) / sqrt(2 sigma^2 + C_00 + C_jj - 2 C_0j))   (ppbo_predict_pairs' rule)
+ *   agreement           a    = mean_j p_j                                                     (= 1 + E[l])
+ *   log score           lpd  = log((1/S) sum_s exp l(mu + L z_s)),   L L' = (C + C')/2 + jitter I
+ * with d_z[S,G] shared by all groups (common random numbers, as d_z in ppbo_line_acq; ppbo_randn fills it, draw s of
+ * point g at index s G + g).  exp l lies in (1/e, 1], so the mean is a plain one.  Every sum runs in an order fixed by
+ * the shapes: a call repeats bit for bit, and a group's bits do not depend on the other groups of the call.  A group
+ * whose mean holds a NaN gets NaN in all its outputs.
+ *
+ * ppbo_loo_answers: the cavity form of leave-one-out for the Laplace posterior N(f, P), P = (Sigma^-1 - Lambda)^-1 as
+ * ppbo_posterior returns it (d_P, leading dimension ldp) -- for star q, rows I = q b .. q b + m, b = m + 1, the query's
+ * own likelihood site is taken out of the Gaussian,
+ *   K_q = P_II^-1 + Lambda_q,   C_q = K_q^-1,   m_q = f_I - C_q g_q,
+ * with Lambda_q = sum_j w_j (e_0 - e_j)(e_0 - e_j)', w_j = Delta_j phi2(Delta_j) / (2 m sigma^2), and g_q the star's part
+ * of beta (g_0 = sum_j phi2(Delta_j) / (sigma m), g_j = -phi2(Delta_j) / (sigma m)), Delta_j = (f_j - f_0) / sigma, and the
+ * answer is scored under N(m_q, C_q).  No refit.
+ *   d_lpd[n_q], d_agree[n_q]     the two scores of every query
+ *   d_edge[N]                    row q b: a_q, rows q b + j: p_j
+ *   d_cav_mean[N], d_cav_var[N]  m_q and diag C_q;   d_cav_cov[n_q,b,b]: C_q
+ *   d_info[n_q] (int32)          0: fine; 1: P_II is not positive definite; 2: the cavity K_q is not.  For 1 and 2 every
+ *                                output of that star is NaN, and no other star is disturbed.
+ * Every output may be NULL, but not all of them.  S = 0 with d_z = d_lpd = NULL runs the closed-form part only.
+ *
+ * ppbo_score_answers: the held-out score of B new answers d_grid[B,G,D] (point 0 of each group the chosen one) under the
+ * full posterior: the group's mean and covariance by the stages ppbo_line_choice shares with ppbo_line_acq (the same
+ * `shrink` and `jitter`, points in the MODEL's coordinates), sigma = model->theta[0], m = G - 1.  d_lpd[B], d_agree[B],
+ * d_edge[B,G] (column 0: a, column j: p_j); each may be NULL, not all.
+ *
+ * "invalid argument", nothing launched, outputs untouched: NULL inputs; m < 1, m + 1 > 128, G outside 2 .. 128; N not a
+ * multiple of m + 1; ldp < N; S < 0, S > 0 without d_z, d_lpd with S = 0; sigma or jitter not finite, sigma <= 0,
+ * jitter < 0; every output NULL; for ppbo_score_answers B < 1 or a model without d_G or Lambda. */
+PPBO_API int ppbo_loo_answers(ppbo_ctx* ctx, const double* d_P, int ldp, const double* d_f, int N, int m, double sigma,
+                     const double* d_z, int S, double jitter, double* d_lpd, double* d_agree, double* d_edge,
+                     double* d_cav_mean, double* d_cav_var, double* d_cav_cov, int* d_info, void* stream);
+PPBO_API int ppbo_score_answers(ppbo_ctx* ctx, const ppbo_model* model, const double* d_grid, int B, int G, double shrink,
+                       const double* d_z, int S, double jitter, double* d_lpd, double* d_agree, double* d_edge,
+                       void* stream);
+
 
 /* standard normal draws for the Monte-Carlo acquisitions, generated on the device: d_out[n] = a pure function of
  * (seed, index) (Philox-4x32-10 + Box-Muller), i.e. reproducible and independent of the launch geometry.  Replaces

@@ -166,6 +166,8 @@ SIGNATURES = {
     "ppbo_line_acq_xi": [_vp, C.POINTER(Model), _vp, _vp, _vp, _i, _i, _i, _d, _vp, _i, _d, _d, _vp, _vp, _vp],
     "ppbo_line_choice": [_vp, C.POINTER(Model), _vp, _i, _i, _d, _vp, _vp, _i, _d, _d, _vp, _vp, _vp, _vp],
     "ppbo_line_choice_xi": [_vp, C.POINTER(Model), _vp, _vp, _vp, _i, _i, _i, _d, _vp, _vp, _i, _d, _d, _vp, _vp, _vp, _vp],
+    "ppbo_loo_answers": [_vp, _vp, _i, _vp, _i, _i, _d, _vp, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "ppbo_score_answers": [_vp, C.POINTER(Model), _vp, _i, _i, _d, _vp, _i, _d, _vp, _vp, _vp, _vp],
     "ppbo_randn": [_vp, C.c_uint64, _vp, _i64, _vp],
     "ppbo_rff_project": [_vp, _vp, _i, _i, _vp, _i, _vp, _d, _vp, _vp],
     "ppbo_rff_score": [_vp, _vp, _i64, _i, _vp, _i, _vp, _d, _vp, _vp, C.POINTER(_d), C.POINTER(_i64), _vp],

@@ -135,6 +135,15 @@ extern "C" int tournament_field(ppbo_ctx* ctx, const ppbo_model* model, const do
                                 double* KB, double* Y, double* Z, double* U, double* part_b, int q_per_split_b,
                                 int n_split_b_eff, hipStream_t s, int gemm_cfg = 0);
 
+// answers.hip, for predict.hip: scores Bc groups of G points (point 0 the chosen one) whose means mu [Bc][G] and
+// covariances cov [Bc][G][G] (+ cov_parts: mc_factor_lds' slabs) are on the device -- the closed-form edge probabilities
+// into d_edge [Bc][G] (column 0 the agreement) and d_agree [Bc], the Monte-Carlo log score of the S draws d_z [S][G] into
+// d_lpd [Bc]; any of the three may be NULL, S = 0 skips the draws
+int ppbo_answer_score_groups(ppbo_ctx* ctx, const double* mu, const double* cov, int Bc, int G, double sigma,
+                             const double* d_z, int S, double jitter, const double* cov_parts, int n_parts,
+                             long long part_stride, int parts_lower_only, double* d_lpd, double* d_agree, double* d_edge,
+                             hipStream_t s);
+
 // first row / column of an edge-form operator that the contractions read: the n_q observation coordinates hold zeros,
 // the K loops start at n_q rounded down to the chunk depth
 inline int ppbo_edge_k0(int n_q) { return n_q & ~15; }

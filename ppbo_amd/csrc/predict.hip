@@ -29,6 +29,7 @@
 
 #include "gemm_f64.h"
 #include "linalg.h"
+#include "mc_factor.h"
 #include "score.h"
 #include "tile_walk.h"
 
@@ -2587,57 +2588,7 @@ __global__ __launch_bounds__(256, (NT16 <= 5) ? 2 : 1) void line_cov_kernel(cons
   }
 }
 
-constexpr int MC_MAXG16 = 128;
-// Step 1 of the Monte-Carlo kernels below, by the whole workgroup: the G x G posterior covariance of group blockIdx.x,
-// symmetrised, jitter on its diagonal, factored in LDS.  On return Lm[G16][ld] holds L (zeros above the diagonal and in
-// rows / columns >= G) and mus[G16] the group's mean (-inf beyond G); the last statement is a barrier.
-__device__ __forceinline__ void mc_factor_lds(double* Lm, double* mus, const double* mu, const double* cov, int G,
-                                              int G16, int ld, double jitter, const double* cov_parts, int n_parts,
-                                              long long part_stride, int parts_lower_only) {
-  const double* c = cov + (size_t)blockIdx.x * G * G;
-  const double* m = mu + (size_t)blockIdx.x * G;
-  // cov_parts: the data term K*' Lambda K* + Y'Y as line_cov_kernel leaves it -- n_parts row-split slabs per line, the
-  // Lambda part in its one-sided form -- added here in slab order
-  const double* cp = cov_parts ? cov_parts + (size_t)blockIdx.x * G * G : nullptr;
-  for (int e = threadIdx.x; e < G16 * ld; e += blockDim.x) {
-    const int g = e / ld, h = e - g * ld;
-    double v = 0.0;
-    if (g < G && h < G) {
-      double a = c[g * G + h], b = c[h * G + g];
-      // parts_lower_only: the slabs are exactly symmetric and hold the 16 x 16 tiles of the lower triangle only
-      const bool up = parts_lower_only && (g >> 4) < (h >> 4);
-      const int ia = up ? h * G + g : g * G + h, ib = (parts_lower_only && !up && (g >> 4) > (h >> 4)) ? g * G + h : h * G + g;
-      for (int k = 0; k < n_parts; ++k) { a += cp[(size_t)k * part_stride + ia]; b += cp[(size_t)k * part_stride + ib]; }
-      // symmetrise (the contributions are symmetric only up to rounding; line_cov_kernel's Lambda term only after this)
-      v = 0.5 * (a + b) + ((g == h) ? jitter : 0.0);
-    }
-    Lm[e] = v;
-  }
-  for (int g = threadIdx.x; g < G16; g += blockDim.x) mus[g] = (g < G) ? m[g] : -INFINITY;
-  __syncthreads();
-  // right-looking Cholesky in LDS, two barriers per column: scale the column below the diagonal, then the 16 x 16
-  // thread grid sweeps the trailing lower triangle (no integer division per element)
-  const int ty = threadIdx.x >> 4, tx = threadIdx.x & 15;
-  for (int j = 0; j < G; ++j) {
-    const double d = Lm[j * ld + j];
-    const double piv = (d > 0.0) ? sqrt(d) : 0.0;     // semi-definite: drop the direction
-    for (int i = j + 1 + threadIdx.x; i < G; i += blockDim.x) Lm[i * ld + j] = (piv > 0.0) ? Lm[i * ld + j] / piv : 0.0;
-    __syncthreads();
-    if (threadIdx.x == 0) Lm[j * ld + j] = piv;        // nobody reads the diagonal entry below
-    for (int a = j + 1 + ty; a < G; a += 16) {
-      const double la = Lm[a * ld + j];
-      for (int b = j + 1 + tx; b <= a; b += 16) Lm[a * ld + b] -= la * Lm[b * ld + j];
-    }
-    __syncthreads();
-  }
-  // the strict upper triangle still holds the symmetric input: the contraction below stops at the diagonal TILE, so
-  // inside the diagonal tiles it must read zeros there
-  for (int e = threadIdx.x; e < G * G; e += blockDim.x) {
-    const int g = e / G, h = e - g * G;
-    if (h > g) Lm[g * ld + h] = 0.0;
-  }
-  __syncthreads();
-}
+// (MC_MAXG16 and mc_factor_lds, step 1 of the Monte-Carlo kernels below: mc_factor.h)
 
 // Monte-Carlo part of EI / varmax on a line (acquisition.py:72-81, :170-178): f = mu + L z for S draws, max over the
 // line, statistics of the maxima.  grid = (lines, draw splits); one workgroup = one line x one slice of the draws.
@@ -4453,15 +4404,23 @@ struct LineChoice {
   int* d_count;        // [B,G] or NULL
   int* d_choice;       // [B,S] or NULL
 };
+// what ppbo_score_answers asks of the groups instead: point 0 of each group is the answer, scored by answers.hip
+struct LineAnswers {
+  double sigma;
+  double* d_lpd;       // [B] or NULL
+  double* d_agree;     // [B] or NULL
+  double* d_edge;      // [B,G] or NULL
+};
 
 // EI / varmax of B lines whose grid points are either given (d_grid) or formed on the device from (xi, x, alpha); with
 // `ch` the choice probabilities of the same B groups instead (everything before the Monte-Carlo launch is shared)
 int line_acq_impl(ppbo_ctx* ctx, const ppbo_model* model, const double* d_grid, const double* d_xi, const double* d_x,
                   const double* d_alpha, int alpha_per_line, int B, int G, double shrink, const double* d_z, int S,
                   double mustar, double jitter, double* d_ei, double* d_varmax, hipStream_t s,
-                  const LineChoice* ch = nullptr) {
+                  const LineChoice* ch = nullptr, const LineAnswers* an = nullptr) {
   if (int rc = check_model(ctx, model)) return rc;
-  PPBO_REQUIRE(ctx, (d_grid || (d_xi && d_x && d_alpha)) && d_z && B > 0 && G > 0 && G <= 128 && S > 0,
+  // (the answers' own entry has checked d_z and S: it also runs without draws)
+  PPBO_REQUIRE(ctx, (d_grid || (d_xi && d_x && d_alpha)) && (an || (d_z && S > 0)) && B > 0 && G > 0 && G <= 128,
                "line arguments (G <= 128)");
   PPBO_REQUIRE(ctx, model->d_G && model->d_lam_diag && model->d_lam_off, "model G/Lambda");
   const int N = model->N, mblk = model->m + 1, n_q = N / mblk, D = model->D;
@@ -4505,19 +4464,20 @@ int line_acq_impl(ppbo_ctx* ctx, const ppbo_model* model, const double* d_grid, 
   const size_t mc_lds = ((size_t)G16 * (G16 + 2) + G16 + 16) * sizeof(double);   // G = 128: 134 KB of the CU's 160 KB
   // the choice kernel: the same factor and mean, then its histogram (G = 128: 512 B more)
   const size_t ch_lds = ((size_t)G16 * (G16 + 2) + G16) * sizeof(double) + (size_t)G16 * sizeof(int);
-  if (!ch && mc_lds > 64 * 1024) ppbo_lds_limit(ctx, (const void*)line_mc_kernel, (128 * 130 + 128 + 16) * (int)sizeof(double));
+  if (!ch && !an && mc_lds > 64 * 1024) ppbo_lds_limit(ctx, (const void*)line_mc_kernel, (128 * 130 + 128 + 16) * (int)sizeof(double));
   if (ch && ch_lds > 64 * 1024)
     ppbo_lds_limit(ctx, (const void*)line_choice_kernel, (128 * 130 + 128) * (int)sizeof(double) + 128 * (int)sizeof(int));
   // draws of a line spread over several workgroups when the batch alone does not fill the chip (>= 64 draws each)
   int nsplit = (2 * 256 + Bc_max - 1) / Bc_max;
   if (nsplit > (S + 63) / 64) nsplit = (S + 63) / 64;
   if (nsplit < 1) nsplit = 1;
-  const int draws_per_split = (((S + nsplit - 1) / nsplit) + 15) & ~15;
+  // (the answers' scores split their draws themselves, and may come with S = 0: this plan is not theirs)
+  const int draws_per_split = an ? 16 : (((S + nsplit - 1) / nsplit) + 15) & ~15;
   nsplit = (S + draws_per_split - 1) / draws_per_split;
-  // per-(line, split) partial results: three sums, or a histogram of G counts
-  void* mc_ws = ppbo_workspace(ctx, ppbo_ctx::WS_SMALL,
+  // per-(line, split) partial results: three sums, or a histogram of G counts (the answers' scores keep their own)
+  void* mc_ws = an ? nullptr : ppbo_workspace(ctx, ppbo_ctx::WS_SMALL,
                                (size_t)Bc_max * nsplit * (ch ? (size_t)G * sizeof(int) : 3 * sizeof(double)));
-  if (!mc_ws) return (int)hipErrorOutOfMemory;
+  if (!mc_ws && !an) return (int)hipErrorOutOfMemory;
   double* mc_part = (double*)mc_ws;
   for (int b0 = 0; b0 < B; b0 += Bc_max) {
     const int Bc = (B - b0 < Bc_max) ? (B - b0) : Bc_max;
@@ -4545,6 +4505,14 @@ int line_acq_impl(ppbo_ctx* ctx, const ppbo_model* model, const double* d_grid, 
       return rc;
     PPBO_LAUNCH_CHECK(ctx);
     if (int rc = line_y_cov(ctx, model, Gq, Nk, g_rows, Kt, Y, Ke, ld, M, Bc, G, lcp, cov_parts, (long long)Bc_max * G * G, s)) return rc;
+    if (an) {
+      if (int rc = ppbo_answer_score_groups(ctx, mu, cov, Bc, G, an->sigma, d_z, S, jitter, cov_parts, cov_splits,
+                                            (long long)Bc_max * G * G, sym ? 1 : 0, an->d_lpd ? an->d_lpd + b0 : nullptr,
+                                            an->d_agree ? an->d_agree + b0 : nullptr,
+                                            an->d_edge ? an->d_edge + (size_t)b0 * G : nullptr, s))
+        return rc;
+      continue;
+    }
     if (ch) {
       {
         PpboProfScope pf(ctx, ppbo_ctx::PF_LINE_MC, s);
@@ -4684,6 +4652,24 @@ int ppbo_line_choice_xi(ppbo_ctx* ctx, const ppbo_model* model, const double* d_
   const LineChoice ch{noise_sd > 0.0 ? d_e : nullptr, noise_sd, d_prob, d_count, d_choice};
   return line_acq_impl(ctx, model, nullptr, d_xi, d_x, d_alpha, alpha_per_line != 0, B, G, shrink, d_z, S, 0.0, jitter,
                        nullptr, nullptr, (hipStream_t)stream, &ch);
+}
+
+int ppbo_score_answers(ppbo_ctx* ctx, const ppbo_model* model, const double* d_grid, int B, int G, double shrink,
+                       const double* d_z, int S, double jitter, double* d_lpd, double* d_agree, double* d_edge,
+                       void* stream) {
+  PPBO_ENTER(ctx);
+  const double dmax = 1.79769313486231570815e308;
+  PPBO_REQUIRE(ctx, model != nullptr && d_grid != nullptr, "model / d_grid");
+  PPBO_REQUIRE(ctx, B >= 1 && G >= 2 && G <= 128, "groups (B >= 1, 2 <= G <= 128: the answer and at least one other point)");
+  PPBO_REQUIRE(ctx, S >= 0, "S >= 0");
+  PPBO_REQUIRE(ctx, S == 0 || d_z != nullptr, "S > 0 needs the draws d_z");
+  PPBO_REQUIRE(ctx, S > 0 || d_lpd == nullptr, "d_lpd needs S > 0 draws");
+  PPBO_REQUIRE(ctx, jitter >= 0.0 && jitter <= dmax, "jitter (finite, >= 0)");
+  PPBO_REQUIRE(ctx, model->theta[0] > 0.0 && model->theta[0] <= dmax, "sigma = theta[0] (finite, > 0)");
+  PPBO_REQUIRE(ctx, d_lpd || d_agree || d_edge, "every output is NULL");
+  const LineAnswers an{model->theta[0], d_lpd, d_agree, d_edge};
+  return line_acq_impl(ctx, model, d_grid, nullptr, nullptr, nullptr, 0, B, G, shrink, d_z, S, 0.0, jitter, nullptr,
+                       nullptr, (hipStream_t)stream, nullptr, &an);
 }
 
 // Gradients: per chunk of at most GRAD_CHUNK = 512 points kstar_grad ->

@@ -1602,6 +1602,84 @@ class Engine:
         self._check(rc, "ppbo_line_choice_xi")
         return dict(prob=prob, count=count, choice=choice)
 
+    # ---- scoring the answers ---------------------------------------------------------
+    def _answer_draws(self, what, G, z, S, seed, jitter):
+        """(z on the device or None, S) of loo_answers / score_answers: the given draws z [S, G], or S draws of the
+        ppbo_randn stream of `seed` (None: a seed off the global NumPy stream), or none at all (S = 0: the closed-form
+        scores only).  Refuses by shapes and values alone, before anything reaches the device."""
+        jitter = float(jitter)
+        if not (np.isfinite(jitter) and jitter >= 0.0):
+            raise ValueError(f"{what}: jitter = {jitter} must be finite and >= 0")
+        if z is not None:
+            sz = tuple(np.shape(z))
+            if len(sz) != 2 or sz[1] != G or sz[0] < 1:
+                raise ValueError(f"{what}: draws z of shape {sz} for groups of {G} points ([S, {G}] with S >= 1 is required)")
+            return self.dev(z), sz[0]
+        S = int(S)
+        if S < 0:
+            raise ValueError(f"{what}: S = {S} draws")
+        if S == 0:
+            return None, 0
+        if seed is None:
+            from .random_fourier_sampler import draw_seed
+            seed = draw_seed()
+        return self.randn(seed, S, G), S
+
+    def loo_answers(self, P, f, m, sigma, z=None, S=4096, seed=None, jitter=0.0, want_cov=False):
+        """Leave-one-query-out scores of the answers behind a Laplace posterior N(f, P) (ppbo_loo_answers): for each of
+        the n_q = N / (m + 1) stars the cavity -- the posterior without that query's likelihood site -- and the probability
+        it gives the answer.  Returns the device tensors dict(lpd [n_q], agreement [n_q], edge [n_q, m + 1] (column 0 the
+        agreement, column j the probability that the chosen point beats point j), cav_mean [N], cav_var [N], cav_cov
+        [n_q, b, b] or None, info [n_q] int32: 0 fine, 1 P_II not positive definite, 2 the cavity is not -- NaN scores).
+        z [S, m + 1]: the draws of the log score, shared by all stars; None: S draws of ppbo_randn's stream of `seed`; S = 0:
+        the closed-form scores only (lpd None)."""
+        sp, nf, m = tuple(np.shape(P)), int(np.prod(np.shape(f), dtype=np.int64)), int(m)
+        if len(sp) != 2 or sp[0] != sp[1] or sp[0] != nf or nf < 1:
+            raise ValueError(f"loo_answers: P of shape {sp} beside f of {nf} entries ([N, N] and [N] are required)")
+        if not 1 <= m <= 127 or nf % (m + 1):
+            raise ValueError(f"loo_answers: m = {m} for N = {nf} rows (1 <= m <= 127 and N a multiple of m + 1 are required)")
+        sigma = float(sigma)
+        if not (np.isfinite(sigma) and sigma > 0.0):
+            raise ValueError(f"loo_answers: sigma = {sigma} must be finite and > 0")
+        N, b = nf, m + 1
+        z, S = self._answer_draws("loo_answers", b, z, S, seed, jitter)
+        P, f = self.dev(P), self.dev(f).reshape(-1)
+        n_q = N // b
+        lpd = self.empty(n_q) if S > 0 else None
+        agree, edge, cm, cv = self.empty(n_q), self.empty(n_q, b), self.empty(N), self.empty(N)
+        cc = self.empty(n_q, b, b) if want_cov else None
+        info = torch.empty(n_q, dtype=torch.int32, device=self.device)
+        rc = self.lib.ppbo_loo_answers(self.ctx, _ptr(P), N, _ptr(f), N, m, sigma, _ptr(z), S, float(jitter), _ptr(lpd),
+                                       _ptr(agree), _ptr(edge), _ptr(cm), _ptr(cv), _ptr(cc), _ptr(info), self._stream())
+        self._check(rc, "ppbo_loo_answers")
+        return dict(lpd=lpd, agreement=agree, edge=edge, cav_mean=cm, cav_var=cv, cav_cov=cc, info=info)
+
+    def score_answers(self, post: Posterior, groups, z=None, S=4096, seed=None, shrink=SHRINKAGE, jitter=0.0):
+        """Held-out scores of B new answers under the full posterior (ppbo_score_answers): groups [B, G, D] in the caller's
+        coordinates, 2 <= G <= 128, point 0 of each group the chosen one.  Returns the device tensors dict(lpd [B] or None
+        (S = 0), agreement [B], edge [B, G]) as loo_answers does; the draws as there."""
+        sg = tuple(np.shape(groups))
+        if len(sg) != 3:
+            raise ValueError(f"score_answers: the points must be [B, G, D] (got {sg})")
+        B, G = sg[:2]
+        D = 6 if post.camphor is not None else post.X.shape[1]
+        if sg[2] != D:
+            raise ValueError(f"score_answers: points of width {sg[2]} for a model of {D} dimensions")
+        if B < 1 or not 2 <= G <= 128:
+            raise ValueError(f"score_answers: {B} groups of {G} points (B >= 1 and 2 <= G <= 128 are required)")
+        z, S = self._answer_draws("score_answers", G, z, S, seed, jitter)
+        grid = self.dev(groups)
+        if post.embedded:
+            grid = self._points(post, grid.reshape(B * G, grid.shape[2]))
+            grid = grid.reshape(B, G, grid.shape[1])
+        md = self._model(post, True)
+        lpd = self.empty(B) if S > 0 else None
+        agree, edge = self.empty(B), self.empty(B, G)
+        rc = self.lib.ppbo_score_answers(self.ctx, C.byref(md), _ptr(grid), B, G, float(shrink), _ptr(z), S, float(jitter),
+                                         _ptr(lpd), _ptr(agree), _ptr(edge), self._stream())
+        self._check(rc, "ppbo_score_answers")
+        return dict(lpd=lpd, agreement=agree, edge=edge)
+
     # ---- RFF -------------------------------------------------------------------------
     @staticmethod
     def _rff_widths(what, D, W, b, omega=None):

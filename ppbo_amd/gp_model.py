@@ -1177,6 +1177,82 @@ class GPModel:
         prob = out["prob"].cpu().numpy()
         return prob[0] if X.ndim == 2 else prob
 
+    # ------------------------------------------------------------------ scoring the answers
+    def _loo(self, P, f, theta, n_draws, seed):
+        """Engine.loo_answers on a posterior covariance P and mode f (device), with answer_pred's jitter and seed rule."""
+        S = int(n_draws)
+        if S < 1:
+            raise ValueError(f"n_draws = {n_draws}: at least one draw is required")
+        if seed is None:
+            from .random_fourier_sampler import draw_seed
+            seed = draw_seed()
+        return self.eng.loo_answers(P, f, self.m, float(theta[0]), S=S, seed=seed, jitter=1e-10 * float(theta[2]) ** 2)
+
+    def loo_pred(self, n_draws=4096, seed=None):
+        """How well does the model explain each answer it was trained on?  Leave-one-query-out in its cavity form
+        (ppbo_loo_answers; no reference counterpart): query q's likelihood site is taken out of the Laplace posterior --
+        no refit -- and the remaining belief is asked how probable the answer was.  A dict of NumPy arrays: lpd [n_q] the
+        log predictive score (n_draws Monte-Carlo draws of the star likelihood), agreement [n_q] the mean probability that
+        the chosen point beats another point of its line, edge_prob [n_q, m] those probabilities, cav_mean and cav_var
+        [N] the cavity's mean and variance at the design rows, info [n_q] (0 fine; 1 / 2: the block of P / the cavity is not
+        positive definite and the query's scores are NaN).  It reads only the posterior covariance and f_MAP, whatever the
+        kernel.  seed: None takes one off the global NumPy stream; a fixed seed gives bitwise-equal results."""
+        post = self._var_post()
+        if post.P is None:           # as posterior_covariance: formed on demand
+            self._post = post = self.eng.posterior(self._dX, self.theta, self.kernel.__name__, self._dSigma_inv,
+                                                   self.eng.dev(self.fMAP), self.m, want_P=True)
+        out = self._loo(post.P, self.eng.dev(self.fMAP), self.theta, n_draws, seed)
+        edge = out["edge"].cpu().numpy()
+        return dict(lpd=out["lpd"].cpu().numpy(), agreement=out["agreement"].cpu().numpy(), edge_prob=edge[:, 1:],
+                    cav_mean=out["cav_mean"].cpu().numpy(), cav_var=out["cav_var"].cpu().numpy(),
+                    info=out["info"].cpu().numpy())
+
+    def inconsistent_answers(self, k=5, n_draws=4096, seed=None):
+        """The k answers the model explains worst -- candidates for a slip of the slider: dict(query [k] the queries with
+        the lowest leave-one-out log score, lowest first, lpd [k], agreement [k], X [k, m + 1, D] their rows of the design,
+        the chosen point first)."""
+        r = self.loo_pred(n_draws, seed)
+        lpd = np.where(np.isnan(r["lpd"]), -np.inf, r["lpd"])          # a query that could not be scored comes first
+        order = np.argsort(lpd, kind="stable")[:max(int(k), 0)]
+        b = self.m + 1
+        return dict(query=order, lpd=r["lpd"][order], agreement=r["agreement"][order],
+                    X=np.asarray(self.X).reshape(-1, b, self.D)[order])
+
+    def answers_score(self, X_stars, n_draws=4096, seed=None):
+        """The held-out score of new answers under the full posterior (ppbo_score_answers; no reference counterpart), the
+        test-set number for comparing kernels and hyper-parameters.  X_stars [n (m + 1), D]: n stars in
+        FeedbackProcessing's row layout (the chosen point, then its m pseudo-observations), in the coordinates of the
+        design.  dict(lpd [n], agreement [n], edge_prob [n, m], total = sum lpd)."""
+        post = self._var_post()
+        X = np.asarray(X_stars, dtype=float)
+        b = self.m + 1
+        if X.ndim != 2 or X.shape[1] != self.D or X.shape[0] < b or X.shape[0] % b or not 2 <= b <= 128:
+            raise ValueError(f"answers_score: stars of shape {X.shape}; [n ({b}), {self.D}] with n >= 1 and at most 128 rows "
+                             "per star is required")
+        S = int(n_draws)
+        if S < 1:
+            raise ValueError(f"n_draws = {n_draws}: at least one draw is required")
+        if seed is None:
+            from .random_fourier_sampler import draw_seed
+            seed = draw_seed()
+        out = self.eng.score_answers(post, X.reshape(-1, b, self.D), S=S, seed=seed, shrink=self.COVARIANCE_SHRINKAGE,
+                                     jitter=1e-10 * float(self.theta[2]) ** 2)
+        lpd = out["lpd"].cpu().numpy()
+        return dict(lpd=lpd, agreement=out["agreement"].cpu().numpy(), edge_prob=out["edge"].cpu().numpy()[:, 1:],
+                    total=float(lpd.sum()))
+
+    def loo_score(self, theta=None, n_draws=4096, seed=None):
+        """sum_q lpd_q, the leave-one-query-out log score of the design: of the fitted model (theta = None: the sum of
+        loo_pred's lpd for the same seed), or of a fit at `theta` by the evidence's route (Gram matrix, inverse, f_MAP from
+        the current one, posterior), which leaves the model's own state alone.  NaN where a query cannot be scored."""
+        if theta is None:
+            return float(self.loo_pred(n_draws, seed)["lpd"].sum())
+        theta = _theta_list(theta)
+        f0 = self.eng.dev(self.fMAP) if getattr(self, "fMAP", None) is not None else self.eng.dev(np.zeros(self.N))
+        _, Sinv, fm, _, _, _ = self._evidence_fit(self.eng, theta, f0.reshape(-1).clone())
+        post = self.eng.posterior(self._dX, theta, self.kernel.__name__, Sinv, fm, self.m, want_P=True)
+        return float(self._loo(post.P, fm, theta, n_draws, seed)["lpd"].sum().item())
+
     @staticmethod
     def _numpy(out):
         return {k: (v.cpu().numpy() if isinstance(v, torch.Tensor) else v) for k, v in out.items()}
