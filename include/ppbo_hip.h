@@ -661,6 +661,61 @@ PPBO_API int ppbo_search_batch(ppbo_ctx* ctx, const ppbo_model* model, const dou
                         double mustar, double noise_var, int q, int64_t* h_idx, double* h_score, double* d_mu,
                         double* d_var, double* d_var_cond, void* stream);
 
+/* ---- knowledge gradient: a candidate scored by what observing it does to the maximum of the mean (no reference counterpart) --
+ * Users of the model take argmax mu as their answer.  Pointwise EI and the variance look at a candidate's own marginal;
+ * the knowledge gradient for correlated beliefs (Frazier, Powell and Dayanik 2009) measures what an observation at a_i
+ * would do to that answer: a point of small EI that is correlated with a broad basin can move the mean's maximum most.
+ * The imagined observation is the shortlist's convention (ppbo_search_batch): "f(a_i) observed with noise tau^2 =
+ * noise_var" -- a Gaussian observation of the latent value, NOT the answer to a preference query.  It moves the mean of
+ * every point x by cov(a_i, x) Z / s_i, Z ~ N(0, 1).  For candidate a_i and the field B = {b_j}, j < Mb:
+ *   v_i = max(var_i, 0),  s_i = sqrt(v_i + tau^2)
+ *   lines    the field's, intercept mu(b_j) and slope cov(a_i, b_j) / s_i, and the candidate's own, intercept mu(a_i) and
+ *            slope v_i / s_i: Mb + 1 beliefs about a mean after the observation
+ *   h_i(z) = the largest of the lines at z
+ *   KG_i   = E_Z[h_i(Z)] - h_i(0)  >= 0
+ * The field should hold the current recommendation (argmax mu): without it h_i(0) understates the present answer and
+ * KG is inflated.  With the lines of the upper envelope in order of slope, kinks c_k and slopes beta_k,
+ *   KG_i = sum_k (beta_{k+1} - beta_k) psi(|c_k|),   psi(c) = phi(c) - c Phi(-c)
+ * exactly: no quadrature.  s_i = 0 gives slopes 0 and KG_i = 0.
+ *
+ * ppbo_kg_envelope: lines in, KG out.  d_a [Mb]: the intercepts of the field lines, the same for every row; d_slope [Ma,
+ * ld] row-major (ld >= Mb): their slopes per row; d_self_a, d_self_b [Ma]: each row's own line, both NULL for none.
+ * d_kg [Ma]; d_kinks [Ma] (int32, may be NULL): the kinks of the row's envelope, at most (lines - 1); h_best_val /
+ * h_best_idx: the largest KG and its FIRST row, (NaN, -1) when nothing scored.
+ * A gift-wrapping march per row, a fixed group of 16 (Mb <= 256) or 64 lanes on it with the lines in registers: from the
+ * line of the smallest slope (of equal slopes the largest intercept) to the steeper line that crosses the current one
+ * first (of equal crossings the steepest, then the largest intercept), until no steeper line is left -- a counted loop of
+ * at most (lines) passes.  Every reduction is a minimum or a maximum and the sum runs in march order, so a row's result
+ * is a function of the SET of its lines: the order of the lines, duplicated lines and the other rows of the call change
+ * no bit of it, and a repeated call is bitwise equal.
+ * A row with a non-finite slope or own line gives NaN in that row only (kinks 0), and NaN never wins; a non-finite
+ * intercept in d_a gives NaN in EVERY row (the tournament's rule: a NaN opponent poisons the field).
+ * "invalid argument", with nothing launched: NULL d_a, d_slope or d_kg; Ma outside 1 .. 2^31 - 1; Mb outside
+ * 1 .. PPBO_KG_MAX_B; ld < Mb; one of d_self_a / d_self_b without the other.
+ *
+ * ppbo_predict_kg: KG of the candidates d_Xa [Ma, D] over the field d_Xb [Mb, D], both in the MODEL's coordinates as
+ * ppbo_predict_tournament takes its sets.  The tournament's stages unchanged -- ppbo_predict's launches on the field, the
+ * field pass, then per chunk of 65536 candidates ppbo_predict's launches and the cross product on the fp64 matrix cores,
+ * which writes the chunk's covariances [Mc, Mb] into a workspace of the ctx (8 Mc Mb bytes, 512 MB at the largest shape)
+ * -- then s_i and the own slope per row, the envelope march (which divides the covariances by s_i as it loads them) and
+ * the one-workgroup argmax.  Everything is enqueued; the host waits once, for the record.  cov is the tournament's,
+ * clipped at (var_a + var_b) / 2.  A field point that IS candidate i -- the same D coordinates and the same mean, bit for
+ * bit -- takes the own line's slope v_i / s_i: cov(a, a) is var(a), and the cross product sums that quadratic form in
+ * another order than ppbo_predict does (a few ulp apart), which would leave two beliefs where there is one.  So a candidate
+ * that is in the field scores as if its own point were not, and Mb = 1 with the field equal to the candidate gives
+ * KG = 0 exactly.  d_mu_a, d_var_a [Ma], d_mu_b, d_var_b [Mb], each may be NULL: bit for bit ppbo_predict's.
+ * d_kinks may be NULL.  A non-finite coordinate in a_i gives NaN in row i only; one in b_j gives NaN in every row.
+ * "invalid argument", with nothing launched: ppbo_predict_tournament's refusals, a NULL d_kg, and a noise_var that is
+ * negative or not finite.
+ * The envelope launches are timed as "kg", the cross product as "tournament" (ppbo_profile_read). */
+#define PPBO_KG_MAX_B 1024
+PPBO_API int ppbo_kg_envelope(ppbo_ctx* ctx, const double* d_a, const double* d_slope, int64_t ld, const double* d_self_a,
+                        const double* d_self_b, int64_t Ma, int Mb, double* d_kg, int* d_kinks, double* h_best_val,
+                        int64_t* h_best_idx, void* stream);
+PPBO_API int ppbo_predict_kg(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xa, int64_t Ma, const double* d_Xb,
+                        int Mb, double noise_var, double* d_kg, int* d_kinks, double* d_mu_a, double* d_var_a,
+                        double* d_mu_b, double* d_var_b, double* h_best_val, int64_t* h_best_idx, void* stream);
+
 /* full predictive covariance of small sets (the G=70 line grid of EI):
  * d_cov[M,M] = (1-s)K(Xc,Xc) + s sigma_f^2 I - K*^T A K*  (src/gp_model.py:447-450) */
 PPBO_API int ppbo_predict_cov(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc, int M,

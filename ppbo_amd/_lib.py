@@ -29,6 +29,7 @@ MARGINAL_MAX_DC = 64                               # caller coordinates of ppbo_
 TOURNAMENT_BORDA, TOURNAMENT_WORST = 0, 1          # score kinds of ppbo_predict_tournament (PPBO_TOURNAMENT_*)
 TOURNAMENT_MAX_B = 1024                            # opponents per call (PPBO_TOURNAMENT_MAX_B)
 BATCH_MAX_Q = 64                                   # picks per call of ppbo_search_batch (PPBO_BATCH_MAX_Q)
+KG_MAX_B = 1024                                    # field lines per call of ppbo_kg_envelope / ppbo_predict_kg (PPBO_KG_MAX_B)
 
 
 class FitOpts(C.Structure):
@@ -146,6 +147,9 @@ SIGNATURES = {
                                 C.POINTER(_i64), _vp],
     "ppbo_search_batch": [_vp, C.POINTER(Model), _vp, _i64, _i, _d, _d, _i, C.POINTER(_i64), C.POINTER(_d), _vp, _vp, _vp,
                           _vp],
+    "ppbo_kg_envelope": [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _i, _vp, _vp, C.POINTER(_d), C.POINTER(_i64), _vp],
+    "ppbo_predict_kg": [_vp, C.POINTER(Model), _vp, _i64, _vp, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_d),
+                        C.POINTER(_i64), _vp],
     "ppbo_predict_cov": [_vp, C.POINTER(Model), _vp, _i, _d, _vp, _vp, _vp],
     "ppbo_transposed_G_shape": [_i, C.POINTER(_i), C.POINTER(_i)],
     "ppbo_transposed_G": [_vp, _vp, _i, _vp, _vp],

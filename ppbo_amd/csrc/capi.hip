@@ -197,7 +197,7 @@ static int pf_slot(const char* name) {
   static const char* names[] = {"gram", "kstar", "quadform", "score", "rff_project", "rff_score", "potrf",
                                 "line_kstar", "line_y", "line_cov", "line_mc", "fused_score", "tournament",
                                 "tournament_field", "batch_step", "batch_field", "grad_kstar", "grad_finish",
-                                "acq_field", "acq_grad"};
+                                "acq_field", "acq_grad", "kg"};
   for (int i = 0; i < ppbo_ctx::PF_COUNT; ++i)
     if (std::strcmp(name, names[i]) == 0) return i;
   return -1;

@@ -38,7 +38,7 @@ struct ppbo_ctx {
   unsigned upload_next = 0;
   // optional per-kernel event timing
   bool profiling = false;
-  enum { PF_GRAM = 0, PF_KSTAR, PF_QUADFORM, PF_SCORE, PF_RFF_PROJECT, PF_RFF_SCORE, PF_POTRF, PF_LINE_KSTAR, PF_LINE_Y, PF_LINE_COV, PF_LINE_MC, PF_FUSED, PF_TOURNAMENT, PF_TOURNAMENT_FIELD, PF_BATCH_STEP, PF_BATCH_FIELD, PF_GRAD_KSTAR, PF_GRAD_FINISH, PF_ACQ_FIELD, PF_ACQ_GRAD, PF_COUNT };
+  enum { PF_GRAM = 0, PF_KSTAR, PF_QUADFORM, PF_SCORE, PF_RFF_PROJECT, PF_RFF_SCORE, PF_POTRF, PF_LINE_KSTAR, PF_LINE_Y, PF_LINE_COV, PF_LINE_MC, PF_FUSED, PF_TOURNAMENT, PF_TOURNAMENT_FIELD, PF_BATCH_STEP, PF_BATCH_FIELD, PF_GRAD_KSTAR, PF_GRAD_FINISH, PF_ACQ_FIELD, PF_ACQ_GRAD, PF_KG, PF_COUNT };
   std::vector<std::pair<hipEvent_t, hipEvent_t>> pf_events[PF_COUNT];
   size_t pf_used[PF_COUNT] = {};
   // kernels whose dynamic-LDS limit has been raised on THIS ctx's device (hipFuncSetAttribute is per device)
@@ -134,6 +134,19 @@ int ppbo_edge_apply_async(ppbo_ctx* ctx, const double* Kt, int ld, int M, int N,
 extern "C" int tournament_field(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xb, int Mb, int ldu, int NkU,
                                 double* KB, double* Y, double* Z, double* U, double* part_b, int q_per_split_b,
                                 int n_split_b_eff, hipStream_t s, int gemm_cfg = 0);
+
+// kg.hip, for predict.hip: the envelope march behind a chunk's cross product.  ppbo_kg_rows: d_s = sqrt(max(var, 0) +
+// noise_var) and the own line's slope d_self_b = max(var, 0) / d_s for M rows.  ppbo_kg_launch: the knowledge gradient of
+// Ma rows of lines (ppbo_kg_envelope's arguments; the slopes divided by d_div[row] on the way in when d_div is given),
+// rows numbered from idx_base in the ppbo_kg_blocks(Ma, Mb) per-workgroup bests blk_best (a Best each; NULL: none);
+// d_Xa [Ma][D], d_Xb [Mb][D]: the points behind the lines (NULL: none) -- a field point that is the row's candidate, bit
+// for bit, takes the own line's slope
+long long ppbo_kg_blocks(long long Ma, int Mb);
+int ppbo_kg_rows(ppbo_ctx* ctx, const double* d_var, double noise_var, int M, double* d_s, double* d_self_b, hipStream_t s);
+int ppbo_kg_launch(ppbo_ctx* ctx, const double* d_a, const double* d_slope, long long ld, const double* d_div,
+                   const double* d_self_a, const double* d_self_b, long long Ma, int Mb, long long idx_base, double* d_kg,
+                   int* d_kinks, void* blk_best, hipStream_t s, const double* d_Xa = nullptr, const double* d_Xb = nullptr,
+                   int D = 0);
 
 // answers.hip, for predict.hip: scores Bc groups of G points (point 0 the chosen one) whose means mu [Bc][G] and
 // covariances cov [Bc][G][G] (+ cov_parts: mc_factor_lds' slabs) are on the device -- the closed-form edge probabilities

@@ -3928,11 +3928,18 @@ int tournament_field(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xb,
 // ppbo_predict's own launches (predict_passes: mu_a, var_a and the chunk's K* workspace) -> tournament_kernel ->
 // tournament_finish_kernel -> one-workgroup argmax.  A model that the one-launch scoring kernel takes leaves no K* in
 // memory: there the chunks' K* are formed by a K* launch of their own, behind the scoring launch.
-int ppbo_predict_tournament(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xa, int64_t Ma, const double* d_Xb, int Mb,
-                            int score_kind, double* d_mu_a, double* d_var_a, double* d_mu_b, double* d_var_b, double* d_cov,
-                            double* d_prob, double* d_score, double* h_best_val, int64_t* h_best_idx, void* stream) {
-  PPBO_ENTER(ctx);
-  hipStream_t s = (hipStream_t)stream;
+// With `kg` (ppbo_predict_kg) the same stages run, tournament_kernel writes the chunk's covariances into a workspace
+// [Mc][Mb] behind the field's, and the envelope march of kg.hip stands where tournament_finish_kernel does: its
+// per-workgroup bests feed the same one-workgroup argmax.
+struct KgRequest {
+  double noise_var;   // tau^2 of the imagined observation
+  double* d_kg;       // [Ma]
+  int* d_kinks;       // [Ma], may be NULL
+};
+static int tournament_passes(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xa, int64_t Ma, const double* d_Xb, int Mb,
+                             int score_kind, double* d_mu_a, double* d_var_a, double* d_mu_b, double* d_var_b, double* d_cov,
+                             double* d_prob, double* d_score, double* h_best_val, int64_t* h_best_idx, hipStream_t s,
+                             const KgRequest* kg) {
   if (int rc = check_model(ctx, model)) return rc;
   PPBO_REQUIRE(ctx, d_Xa != nullptr && d_Xb != nullptr, "tournament (d_Xa / d_Xb)");
   PPBO_REQUIRE(ctx, Ma >= 1 && Ma <= (int64_t)0x7fffffff, "candidate count (1 .. 2^31 - 1)");
@@ -3960,16 +3967,19 @@ int ppbo_predict_tournament(ppbo_ctx* ctx, const ppbo_model* model, const double
   const int n_split_b = pick_split(Mb, n_q);
   const int q_per_split_b = (n_q + n_split_b - 1) / n_split_b;
   const int n_split_b_eff = (n_q + q_per_split_b - 1) / q_per_split_b;
-  const int fblocks_max = (Mc_max + 255) / 256;
+  const int fblocks_max = kg ? (int)ppbo_kg_blocks(Mc_max, Mb) : (Mc_max + 255) / 256;
   // every workspace of this entry before the first launch (growing one waits for the device)
   double* U = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_TOURN_U, (size_t)NkU * ldu * sizeof(double));
   if (!U) return (int)hipErrorOutOfMemory;
   const size_t f_kb = 0, f_y = f_kb + (size_t)N * ldu, f_z = f_y + (size_t)N * ldu, f_mub = f_z + (size_t)N * ldu,
                f_varb = f_mub + ldu, f_part = f_varb + ldu, f_slab = f_part + (size_t)n_split_b_eff * Mb,
                f_mua = f_slab + (size_t)2 * ntb * Mc_max, f_bests = f_mua + (size_t)(d_mu_a ? 0 : Ma) + (size_t)(d_var_a ? 0 : Ma),
-               f_end = f_bests + (size_t)2 * (fblocks_max + n_chunks);   // (a Best is 16 bytes)
+               f_kg = f_bests + (size_t)2 * (fblocks_max + n_chunks),   // (a Best is 16 bytes)
+               // the knowledge gradient's own: the chunk's covariances [Mc][Mb], s_i and the slope of the own line [Mc] each
+               f_end = f_kg + (kg ? (size_t)Mc_max * Mb + (size_t)2 * Mc_max : 0);
   double* fw = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_TOURN_FIELD, f_end * sizeof(double));
   if (!fw) return (int)hipErrorOutOfMemory;
+  double *kg_cov = fw + f_kg, *kg_s = kg_cov + (size_t)Mc_max * Mb, *kg_self_b = kg_s + Mc_max;
   double *KB = fw + f_kb, *Y = fw + f_y, *Z = fw + f_z, *mu_b = fw + f_mub, *var_b = fw + f_varb, *part_b = fw + f_part;
   double *slab_sum = fw + f_slab, *slab_min = slab_sum + (size_t)ntb * Mc_max;
   double* mu_a = d_mu_a ? d_mu_a : fw + f_mua;
@@ -4005,7 +4015,7 @@ int ppbo_predict_tournament(ppbo_ctx* ctx, const ppbo_model* model, const double
             constexpr int KID = decltype(kid)::value;
             const double* Ks = Kc + (size_t)kshift * ldk;
             const double* Us = U + (size_t)kshift * ldu;
-            double* cov = d_cov ? d_cov + (size_t)c_beg * Mb : nullptr;
+            double* cov = kg ? kg_cov : (d_cov ? d_cov + (size_t)c_beg * Mb : nullptr);
             double* prob = d_prob ? d_prob + (size_t)c_beg * Mb : nullptr;
             if (small)
               return launch_tournament<TQ_SMALL, KID>(ctx, Ks, ldk, Us, ldu, kext, Mc, Mb, xa, d_Xb, D, p, two_sigma2, mu_a + c_beg,
@@ -4017,10 +4027,20 @@ int ppbo_predict_tournament(ppbo_ctx* ctx, const ppbo_model* model, const double
           }))
         return rc;
     }
-    const int fblocks = (Mc + 255) / 256;
-    tournament_finish_kernel<<<fblocks, 256, 0, s>>>(slab_sum, slab_min, ntb, Mc, Mb, score_kind, (long long)c_beg,
-                                                     d_score ? d_score + c_beg : nullptr, want_best ? bests : nullptr);
-    PPBO_LAUNCH_CHECK(ctx);
+    const int fblocks = kg ? (int)ppbo_kg_blocks(Mc, Mb) : (Mc + 255) / 256;
+    if (kg) {
+      // lines of candidate i: the field's, intercept mu_b[j] and slope cov[i][j] / s_i, and its own (mu_a[i], v_i / s_i)
+      PpboProfScope pf(ctx, ppbo_ctx::PF_KG, s);
+      if (int rc = ppbo_kg_rows(ctx, var_a + c_beg, kg->noise_var, Mc, kg_s, kg_self_b, s)) return rc;
+      if (int rc = ppbo_kg_launch(ctx, mu_b, kg_cov, Mb, kg_s, mu_a + c_beg, kg_self_b, Mc, Mb, (long long)c_beg,
+                                  kg->d_kg + c_beg, kg->d_kinks ? kg->d_kinks + c_beg : nullptr,
+                                  want_best ? bests : nullptr, s, xa, d_Xb, D))
+        return rc;
+    } else {
+      tournament_finish_kernel<<<fblocks, 256, 0, s>>>(slab_sum, slab_min, ntb, Mc, Mb, score_kind, (long long)c_beg,
+                                                       d_score ? d_score + c_beg : nullptr, want_best ? bests : nullptr);
+      PPBO_LAUNCH_CHECK(ctx);
+    }
     if (want_best) {
       const bool one = (n_chunks == 1);
       argmax_final_kernel<<<1, 256, 0, s>>>(bests, fblocks, chunk_best + ch, one ? hr.d_rec : nullptr, 0,
@@ -4064,6 +4084,27 @@ int ppbo_predict_tournament(ppbo_ctx* ctx, const ppbo_model* model, const double
   if (h_best_val) *h_best_val = hr.h_rec[0];      // (NaN, -1) when no candidate has a non-NaN score
   if (h_best_idx) *h_best_idx = (int64_t)hr.h_rec[1];
   return 0;
+}
+
+int ppbo_predict_tournament(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xa, int64_t Ma, const double* d_Xb, int Mb,
+                            int score_kind, double* d_mu_a, double* d_var_a, double* d_mu_b, double* d_var_b, double* d_cov,
+                            double* d_prob, double* d_score, double* h_best_val, int64_t* h_best_idx, void* stream) {
+  PPBO_ENTER(ctx);
+  return tournament_passes(ctx, model, d_Xa, Ma, d_Xb, Mb, score_kind, d_mu_a, d_var_a, d_mu_b, d_var_b, d_cov, d_prob, d_score,
+                           h_best_val, h_best_idx, (hipStream_t)stream, nullptr);
+}
+
+// The knowledge gradient of every candidate a_i over the field B: the tournament's stages with the envelope march
+// (kg.hip) behind each chunk's cross product, see tournament_passes.
+int ppbo_predict_kg(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xa, int64_t Ma, const double* d_Xb, int Mb,
+                    double noise_var, double* d_kg, int* d_kinks, double* d_mu_a, double* d_var_a, double* d_mu_b,
+                    double* d_var_b, double* h_best_val, int64_t* h_best_idx, void* stream) {
+  PPBO_ENTER(ctx);
+  PPBO_REQUIRE(ctx, d_kg != nullptr, "knowledge gradient (d_kg)");
+  PPBO_REQUIRE(ctx, noise_var >= 0.0 && noise_var <= 1.7976931348623157e308, "noise_var (finite, >= 0)");
+  const KgRequest kg{noise_var, d_kg, d_kinks};
+  return tournament_passes(ctx, model, d_Xa, Ma, d_Xb, Mb, PPBO_TOURNAMENT_BORDA, d_mu_a, d_var_a, d_mu_b, d_var_b, nullptr,
+                           nullptr, nullptr, h_best_val, h_best_idx, (hipStream_t)stream, &kg);
 }
 
 // Shortlists: q greedy picks under the conditioned variance (batch_step_kernel and its neighbours, above).  ppbo_predict's

@@ -17,7 +17,7 @@ from ._lib import GRAD_NONE, GRAD_TRACE, GRAD_NORM2  # noqa: F401
 from ._lib import FUNCTIONAL_MEAN, FUNCTIONAL_VARIANCE, FUNCTIONAL_PROB, FUNCTIONAL_MAX_G  # noqa: F401
 from ._lib import EFFECT_RAW, EFFECT_CENTRED, EFFECT_INTERACTION, MARGINAL_MAX_DC  # noqa: F401
 from ._lib import TOURNAMENT_BORDA, TOURNAMENT_WORST, TOURNAMENT_MAX_B  # noqa: F401
-from ._lib import BATCH_MAX_Q  # noqa: F401
+from ._lib import BATCH_MAX_Q, KG_MAX_B  # noqa: F401
 
 # Posterior.form: which variance operator G holds (include/ppbo_hip.h, PPBO_FORM_*)
 FORM_NODE = 0   # G = R Lambda, block lower triangular [N, N]
@@ -1207,6 +1207,55 @@ class Engine:
         self._check(rc, "ppbo_search_batch")
         return dict(idx=np.array(idx[:], dtype=np.int64), score=np.array(sc[:], dtype=np.float64), mu=mu, var=var,
                     var_cond=vc)
+
+    def predict_kg(self, post: Posterior, Xa, Xb, noise_var=None, want_kinks=False, want_best=True):
+        """The knowledge gradient (ppbo_predict_kg) of every candidate Xa[i] over the field Xb [Mb <= KG_MAX_B, D], points
+        in the caller's coordinates: kg[i] = E[max of the mean over the field and Xa[i] after observing f(Xa[i]) with
+        noise noise_var] - the same maximum now (None: theta[0]^2, the model's own noise; 0: an exact observation; the
+        shortlist's convention for an imagined observation, not a preference answer).  The field should hold the current
+        recommendation.  Returns device tensors kg [Ma], kinks [Ma] (int32, the kinks of each envelope; None unless
+        asked for), mu_a / var_a [Ma] and mu_b / var_b [Mb] (bit for bit predict's) and best_val / best_idx, the largest
+        KG and its first row.  A non-finite field point poisons every row.  ValueError, before anything reaches the
+        device, for predict_tournament's shape errors and a negative or non-finite noise_var."""
+        Ma, Mb = self._tournament_shapes(post, Xa, Xb)
+        nv = float(post.theta[0]) ** 2 if noise_var is None else float(noise_var)
+        if not (np.isfinite(nv) and nv >= 0.0):
+            raise ValueError(f"predict_kg: noise_var = {noise_var!r}; a finite value >= 0 is required")
+        Xa, Xb = self._points(post, Xa), self._points(post, Xb)
+        md = self._model(post, True)
+        kg, mu_a, var_a, mu_b, var_b = self.empty(Ma), self.empty(Ma), self.empty(Ma), self.empty(Mb), self.empty(Mb)
+        kinks = torch.empty(Ma, dtype=torch.int32, device=self.device) if want_kinks else None
+        bv, bi = C.c_double(0.0), C.c_int64(-1)
+        rc = self.lib.ppbo_predict_kg(self.ctx, C.byref(md), _ptr(Xa), Ma, _ptr(Xb), Mb, nv, _ptr(kg), _ptr(kinks), _ptr(mu_a),
+                                      _ptr(var_a), _ptr(mu_b), _ptr(var_b), C.byref(bv) if want_best else None,
+                                      C.byref(bi) if want_best else None, self._stream())
+        self._check(rc, "ppbo_predict_kg")
+        return dict(kg=kg, kinks=kinks, mu_a=mu_a, var_a=var_a, mu_b=mu_b, var_b=var_b, best_val=bv.value, best_idx=bi.value)
+
+    def kg_envelope(self, a, slopes, self_a=None, self_b=None):
+        """E[max_j (a_j + b_ij Z)] - max_j a_j, Z ~ N(0, 1), per row i of lines (ppbo_kg_envelope): a [Mb <= KG_MAX_B] the
+        intercepts shared by all rows, slopes [Ma, Mb], and optionally one more line per row, (self_a[i], self_b[i]).
+        Returns device tensors kg [Ma] and kinks [Ma] (int32) and best_val / best_idx.  A row's result depends on the set
+        of its lines only.  ValueError, before anything reaches the device, for shape errors."""
+        sa, ss = tuple(np.shape(a)), tuple(np.shape(slopes))
+        if len(sa) != 1 or len(ss) != 2 or ss[1] != sa[0] or ss[0] < 1 or not 1 <= sa[0] <= KG_MAX_B:
+            raise ValueError(f"kg_envelope: intercepts of shape {sa} and slopes of shape {ss}; [Mb] and [Ma, Mb] with Ma >= 1 "
+                             f"and 1 <= Mb <= {KG_MAX_B} are required")
+        if (self_a is None) != (self_b is None):
+            raise ValueError("kg_envelope: the own line needs both self_a and self_b")
+        if self_a is not None and (tuple(np.shape(self_a)) != (ss[0],) or tuple(np.shape(self_b)) != (ss[0],)):
+            raise ValueError(f"kg_envelope: own lines of shapes {tuple(np.shape(self_a))} and {tuple(np.shape(self_b))}; "
+                             f"[{ss[0]}] each is required")
+        Ma, Mb = ss
+        a, slopes = self.dev(a), self.dev(slopes)
+        self_a, self_b = (None, None) if self_a is None else (self.dev(self_a), self.dev(self_b))
+        kg = self.empty(Ma)
+        kinks = torch.empty(Ma, dtype=torch.int32, device=self.device)
+        bv, bi = C.c_double(0.0), C.c_int64(-1)
+        rc = self.lib.ppbo_kg_envelope(self.ctx, _ptr(a), _ptr(slopes), Mb, _ptr(self_a), _ptr(self_b), Ma, Mb, _ptr(kg),
+                                       _ptr(kinks), C.byref(bv), C.byref(bi), self._stream())
+        self._check(rc, "ppbo_kg_envelope")
+        return dict(kg=kg, kinks=kinks, best_val=bv.value, best_idx=bi.value)
 
     def predict_cov(self, post: Posterior, Xc, shrink=SHRINKAGE):
         Xc = self._points(post, Xc)

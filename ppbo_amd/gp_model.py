@@ -1318,6 +1318,54 @@ class GPModel:
         X = cand[torch.as_tensor(idx, device=cand.device)].cpu().numpy() if idx.size else np.zeros((0, self.D))
         return X, idx, out["score"][keep]
 
+    def kg_field(self, n=64):
+        """[<= n, D]: the field of knowledge_gradient -- the points whose means compete for the maximum after the imagined
+        observation: xstar first, then the local maxima xstars_local, then shortlist(q, "EI") picks for the rows that are
+        left.  The current recommendation xstar MUST be in the field: h(0), the maximum of the mean now, is taken over
+        the field and the candidate, so a field without it understates the present answer and inflates every KG."""
+        n = int(n)
+        if not 1 <= n <= 1024:
+            raise ValueError(f"kg_field: n = {n}; 1 .. 1024 is required")
+        if self.xstar is None:
+            raise RuntimeError("kg_field: no recommendation yet (xstar is None): update the model first")
+        rows = [np.asarray(self.xstar, dtype=float).reshape(1, self.D)]
+        if self.xstars_local is not None and len(self.xstars_local):
+            rows.append(np.asarray(self.xstars_local, dtype=float).reshape(-1, self.D))
+        field = np.concatenate(rows)[:n]
+        while len(field) < n:                    # (a shortlist holds at most 64 picks)
+            q = min(n - len(field), 64)
+            picks = self.shortlist(q=q, score="EI")[0]
+            field = np.concatenate([field, picks])
+            if len(picks) < q:
+                break
+        return field
+
+    def knowledge_gradient(self, X_cand=None, field=None, noise_var=None):
+        """dict(kg [M], best_idx, x [D], field [Mb, D], mu [M], var [M]): the knowledge gradient for correlated beliefs
+        (Frazier, Powell and Dayanik 2009; ppbo_predict_kg, no reference counterpart) of every candidate -- the expected
+        rise of the maximum of the posterior mean over `field` and the candidate itself after one observation AT the
+        candidate -- with the row of the largest one (best_idx, x) and the candidates' mean and variance.  Pointwise EI
+        and the variance score a candidate by its own marginal; this scores it by what it does to argmax mu, the answer
+        users take from the model.
+        The imagined observation is the shortlist's convention, "f(x) observed with Gaussian noise noise_var" (None:
+        theta[0]^2; 0: exact).  It is NOT the answer to a preference query: a PPBO query returns a choice among the
+        points of a line, not a noisy value of f, so KG ranks where knowing f would help most, not queries.
+        X_cand [M, D]: the candidates in the caller's coordinates; by default the resident candidate pool under a fresh
+        rotation, as in shortlist, and best_idx then indexes those rotated rows.  field [Mb <= 1024, D]: by default
+        kg_field(); a field of one's own should hold xstar (see kg_field)."""
+        post = self._var_post()
+        field = self.kg_field() if field is None else np.atleast_2d(np.asarray(field, dtype=float))
+        if X_cand is None:
+            cand = self.eng.shift_points(self._candidate_pool(), np.random.uniform(0.0, 1.0, self.D))
+        elif isinstance(X_cand, torch.Tensor):
+            cand = self.eng.dev(X_cand if X_cand.dim() == 2 else X_cand.reshape(1, -1))
+        else:
+            cand = self.eng.dev(np.atleast_2d(np.asarray(X_cand, dtype=float)))
+        out = self.eng.predict_kg(post, cand, field, noise_var=noise_var)
+        b = int(out["best_idx"])
+        return dict(kg=out["kg"].cpu().numpy(), best_idx=b, x=cand[b].cpu().numpy() if b >= 0 else None, field=field,
+                    mu=out["mu_a"].cpu().numpy(), var=out["var_a"].cpu().numpy())
+
     _ACQ_KINDS = {"mean": SCORE_MEAN, "EI": SCORE_POINTWISE_EI, "variance": SCORE_VARIANCE}
 
     def acquisition_grad(self, X, score="EI"):
