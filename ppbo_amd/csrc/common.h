@@ -249,6 +249,33 @@ static inline int ppbo_kernel_dispatch(ppbo_ctx* ctx, int kernel_id, Fn&& fn,
   return ppbo_set_error(ctx, -1, "%s", err);
 }
 
+// The padded dimensions DP a kernel template is instantiated for, in rising order.  pick(D): the first rung >= D, the
+// last rung for everything above.  dispatch(D, fn): fn(std::integral_constant<int, pick(D)>{}), returning what fn returns.
+// A ladder is named once, next to the kernel it serves.
+template <int... DPS>
+struct DpLadder {
+  static constexpr int rungs[] = {DPS...};
+  static constexpr int pick(int D) {
+    for (int r : rungs)
+      if (D <= r) return r;
+    return rungs[sizeof...(DPS) - 1];
+  }
+  template <class Fn>
+  static decltype(auto) dispatch(int D, Fn&& fn) { return step<DPS...>(pick(D), fn); }
+
+ private:
+  template <int DP, int... REST, class Fn>
+  static decltype(auto) step(int dp, Fn& fn) {
+    if constexpr (sizeof...(REST) == 0) return fn(std::integral_constant<int, DP>{});
+    else if (dp == DP) return fn(std::integral_constant<int, DP>{});
+    else return step<REST...>(dp, fn);
+  }
+};
+static_assert(DpLadder<4, 6, 64>::pick(1) == 4 && DpLadder<4, 6, 64>::pick(4) == 4, "a rung takes D up to itself");
+static_assert(DpLadder<4, 6, 64>::pick(5) == 6 && DpLadder<4, 6, 64>::pick(7) == 64 && DpLadder<4, 6, 64>::pick(64) == 64,
+              "the next rung starts one above");
+static_assert(DpLadder<4, 6, 64>::pick(65) == 64 && DpLadder<6>::pick(100) == 6, "the last rung takes everything above");
+
 // ---- kernel-function parameters (host-prepared, passed by value) ------------
 struct KernParams {
   double sf2;      // sigma_f^2

@@ -193,6 +193,9 @@ __device__ __forceinline__ double gram_finish(double r2, const KernParams& p, do
   }
 }
 
+// the DP buckets gram_mfma_kernel is instantiated for
+using GramLadder = DpLadder<4, 8, 12, 16, 20, 24, 32, 48, 64>;
+
 // SE / RQ / Matern Gram tile with the pairwise dot products on the fp64 matrix cores and the reference's
 // expansion  r_ij^2 = (|x_i|^2 + |x_j|^2) - 2 x_i.x_j  (kernels.py:7-10), clipped at 0.  The MFMA chain
 // multiplies x_i by (-2 x_j): products and accumulation order are the same for (i,j) and (j,i), and
@@ -421,28 +424,17 @@ int ppbo_gram(ppbo_ctx* ctx, int kernel_id, const double* d_X, int N, int D, con
   // tile order (PPBO_GRAM_VARIANT: 0 row-major over the upper triangle, 1 diagonal-major, -1 = by size)
   const int order = ctx->gram_variant >= 0 ? ctx->gram_variant : (N >= 4096 ? 1 : 0);
   // the radial kernels: the MFMA form, one bucket per dimension range
-#define GM_LAUNCH(DPV)                                                                                       \
-  do {                                                                                                       \
-    constexpr int LDv = DPV + 2;                                                                             \
-    constexpr int body = 2 * TS * LDv + 2 * TS + 8 * 16 * 18;                                                \
-    const size_t lds = (size_t)body * sizeof(double);                                                        \
-    if (lds > 64 * 1024) ppbo_lds_limit(ctx, (const void*)gram_mfma_kernel<KID, DPV>, (int)lds);             \
-    gram_mfma_kernel<KID, DPV><<<nblk, 512, lds, s>>>(d_X, N, D, p, shrink, d_Sigma, nt, order);             \
-  } while (0)
   auto radial = [&](auto kid) {
     constexpr int KID = decltype(kid)::value;
-    if (D <= 4) GM_LAUNCH(4);
-    else if (D <= 8) GM_LAUNCH(8);
-    else if (D <= 12) GM_LAUNCH(12);
-    else if (D <= 16) GM_LAUNCH(16);
-    else if (D <= 20) GM_LAUNCH(20);
-    else if (D <= 24) GM_LAUNCH(24);
-    else if (D <= 32) GM_LAUNCH(32);
-    else if (D <= 48) GM_LAUNCH(48);
-    else GM_LAUNCH(64);
+    GramLadder::dispatch(D, [&](auto dp) {
+      constexpr int DP = decltype(dp)::value;
+      constexpr int body = 2 * TS * (DP + 2) + 2 * TS + 8 * 16 * 18;
+      const size_t lds = (size_t)body * sizeof(double);
+      if (lds > 64 * 1024) ppbo_lds_limit(ctx, (const void*)gram_mfma_kernel<KID, DP>, (int)lds);
+      gram_mfma_kernel<KID, DP><<<nblk, 512, lds, s>>>(d_X, N, D, p, shrink, d_Sigma, nt, order);
+    });
     return 0;
   };
-#undef GM_LAUNCH
   if (kernel_id != PPBO_KERNEL_CAMPHOR) {
     if (int rc = ppbo_kernel_dispatch<true>(ctx, kernel_id, radial)) return rc;
   } else {

@@ -112,6 +112,8 @@ __device__ __forceinline__ double trial_coord(const TrialCands& c, int trial, lo
 // accumulated in fp64 (alpha has both signs and |mu| << sum |alpha_i k_i|).  Relative error of mu ~1e-6: two candidates
 // closer than that may swap ranks.  grid (candidate blocks, row splits, trials); part[trial][split][Mt].
 constexpr int SCR_T = 256, SCR_CPT = 4, SCR_RJ = 64;
+// the DP buckets of mean_screen_kernel and box_screen_kernel (camphor-copper, D = 6: a bucket of its own)
+using ScreenLadder = DpLadder<4, 8, 12, 16, 20, 24, 32, 48, 64>;
 typedef float float2_t __attribute__((ext_vector_type(2)));
 // two candidates per packed operation (v_pk_add_f32 / v_pk_fma_f32: both halves at the price of one fp32 instruction)
 template <int KID>
@@ -1217,18 +1219,11 @@ int launch_box_screen(const ppbo_model* m, const KernParams& p, const BoxCands& 
                       int n_split, double* part, hipStream_t s) {
   const long long Mt = bc.M + bc.S;
   const dim3 grid((unsigned)((Mt + SCR_T * SCR_CPT - 1) / (SCR_T * SCR_CPT)), n_split, nb);
-#define SCR_LAUNCH(DP) box_screen_kernel<KID, DP><<<grid, SCR_T, 0, s>>>(m->d_X, m->N, m->D, p, m->d_alpha, bc, rows_per_split, n_split, part)
-  if constexpr (KID == PPBO_KERNEL_CAMPHOR) SCR_LAUNCH(6);     // (D = 6: a bucket of its own)
-  else if (m->D <= 4) SCR_LAUNCH(4);
-  else if (m->D <= 8) SCR_LAUNCH(8);
-  else if (m->D <= 12) SCR_LAUNCH(12);
-  else if (m->D <= 16) SCR_LAUNCH(16);
-  else if (m->D <= 20) SCR_LAUNCH(20);
-  else if (m->D <= 24) SCR_LAUNCH(24);
-  else if (m->D <= 32) SCR_LAUNCH(32);
-  else if (m->D <= 48) SCR_LAUNCH(48);
-  else SCR_LAUNCH(64);
-#undef SCR_LAUNCH
+  auto launch = [&](auto dp) {
+    box_screen_kernel<KID, decltype(dp)::value><<<grid, SCR_T, 0, s>>>(m->d_X, m->N, m->D, p, m->d_alpha, bc, rows_per_split, n_split, part);
+  };
+  if constexpr (KID == PPBO_KERNEL_CAMPHOR) launch(std::integral_constant<int, 6>{});
+  else ScreenLadder::dispatch(m->D, launch);
   return 0;
 }
 
@@ -1373,18 +1368,12 @@ int launch_screen(const ppbo_model* m, const KernParams& p, const TrialCands& tc
                   double* part, int extra_trial, hipStream_t s) {
   const long long Mt = tc.M + tc.E;
   const dim3 grid((unsigned)((Mt + SCR_T * SCR_CPT - 1) / (SCR_T * SCR_CPT)), n_split, nb);
-#define SCR_LAUNCH(DP) mean_screen_kernel<KID, DP><<<grid, SCR_T, 0, s>>>(m->d_X, m->N, m->D, p, m->d_alpha, tc, rows_per_split, n_split, part, extra_trial)
-  if constexpr (KID == PPBO_KERNEL_CAMPHOR) SCR_LAUNCH(6);     // (D = 6: a bucket of its own)
-  else if (m->D <= 4) SCR_LAUNCH(4);
-  else if (m->D <= 8) SCR_LAUNCH(8);
-  else if (m->D <= 12) SCR_LAUNCH(12);
-  else if (m->D <= 16) SCR_LAUNCH(16);
-  else if (m->D <= 20) SCR_LAUNCH(20);
-  else if (m->D <= 24) SCR_LAUNCH(24);
-  else if (m->D <= 32) SCR_LAUNCH(32);
-  else if (m->D <= 48) SCR_LAUNCH(48);
-  else SCR_LAUNCH(64);
-#undef SCR_LAUNCH
+  auto launch = [&](auto dp) {
+    mean_screen_kernel<KID, decltype(dp)::value><<<grid, SCR_T, 0, s>>>(m->d_X, m->N, m->D, p, m->d_alpha, tc, rows_per_split, n_split, part,
+                                                                        extra_trial);
+  };
+  if constexpr (KID == PPBO_KERNEL_CAMPHOR) launch(std::integral_constant<int, 6>{});
+  else ScreenLadder::dispatch(m->D, launch);
   return 0;
 }
 

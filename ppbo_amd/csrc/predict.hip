@@ -2832,50 +2832,60 @@ __global__ __launch_bounds__(256) void omega_draws_kernel(const double* __restri
   out[i] = __dadd_rn(om[f], __dmul_rn(sqrt(cov[f]), out[i]));
 }
 
+// The DP buckets of the K* kernels, named once: every launch_kstar* below dispatches through one of them.  The camphor-
+// copper instances take a fixed DP instead (12 staged features per row, or its 6 dimensions).
+using KstarLadder = DpLadder<4, 6, 8, 10, 12, 16, 20, 24, 32, 48, 64>;
+using KstarFuncLadder = DpLadder<8, 20, 32, 48, 64>;    // kstar_func_kernel: whole MFMA k-steps of 4 dimensions
+using KstarFp32Ladder = DpLadder<6, 20, 64>;            // the fp32-tolerance report: the BASELINE shapes' buckets and a generic one
+constexpr int KSTAR_CURV_ACC_MAX_DP = 16;               // kstar_curv_kernel's acceleration twins (ACC = true) exist up to here
+
+// What every K* launcher takes, and what each derives from it; unpacked at the <<<>>> statement.
+struct KstarLaunch {
+  const ppbo_model* m;
+  KernParams p;
+  double* Kt;
+  int ldk;
+  double *mu_part, *t_part;
+  int q_per_split, n_split;
+  bool with_lam;
+  int edge_k0;
+  hipStream_t s;
+  int mblk() const { return m->m + 1; }
+  int n_q() const { return (m->N + mblk() - 1) / mblk(); }
+  const double* lam_diag() const { return with_lam ? m->d_lam_diag : nullptr; }
+  const double* lam_off() const { return with_lam ? m->d_lam_off : nullptr; }
+  double* t_or_null() const { return with_lam ? t_part : nullptr; }
+  dim3 grid(int cols, int per_wg) const { return dim3((cols + per_wg - 1) / per_wg, n_split); }   // per_wg columns per workgroup
+};
+
 template <int KID>
-int launch_kstar(const ppbo_model* m, const KernParams& p, const double* d_Xc, int M, double* Kt, int ldk,
-                 double* mu_part, double* t_part, int q_per_split, int n_split, bool with_lam, int edge_k0,
-                 const double* geo, hipStream_t s, const double* sig = nullptr, double* u_part = nullptr) {
-  dim3 grid((M + KS_THREADS * KS_CPT - 1) / (KS_THREADS * KS_CPT), n_split);
-  const int mblk = m->m + 1, n_q = (m->N + mblk - 1) / mblk;
-  const double* ld = with_lam ? m->d_lam_diag : nullptr;
-  const double* lo = with_lam ? m->d_lam_off : nullptr;
-#define KS_LAUNCH32(DP)                                                                                              \
-  kstar_kernel<KID, DP, true><<<grid, KS_THREADS, 0, s>>>(m->d_X, m->N, m->D, p, m->d_alpha, ld, lo, mblk, d_Xc, M, \
-                                                          Kt, ldk, mu_part, with_lam ? t_part : nullptr,            \
-                                                          q_per_split, n_q, edge_k0, nullptr)
-  if (m->kstar_fp32) {       // the fp32-tolerance report: the BASELINE shapes get their own bucket, the rest a generic one
-    if (KID == PPBO_KERNEL_CAMPHOR || m->D <= 6) KS_LAUNCH32(6);
-    else if constexpr (KID != PPBO_KERNEL_CAMPHOR) {     // (camphor-copper: D = 6)
-      if (m->D <= 20) KS_LAUNCH32(20);
-      else KS_LAUNCH32(64);
-    }
+int launch_kstar(const KstarLaunch& k, const double* d_Xc, int M, const double* geo, const double* sig, double* u_part) {
+  const ppbo_model* m = k.m;
+  const dim3 grid = k.grid(M, KS_THREADS * KS_CPT);
+  if (m->kstar_fp32) {
+    auto launch32 = [&](auto dp) {
+      kstar_kernel<KID, decltype(dp)::value, true><<<grid, KS_THREADS, 0, k.s>>>(
+          m->d_X, m->N, m->D, k.p, m->d_alpha, k.lam_diag(), k.lam_off(), k.mblk(), d_Xc, M, k.Kt, k.ldk, k.mu_part,
+          k.t_or_null(), k.q_per_split, k.n_q(), k.edge_k0, nullptr);
+    };
+    if constexpr (KID == PPBO_KERNEL_CAMPHOR) launch32(std::integral_constant<int, 6>{});     // (camphor-copper: D = 6)
+    else KstarFp32Ladder::dispatch(m->D, launch32);
     return 0;
   }
-#undef KS_LAUNCH32
   // (sig: the flagged instantiation, an edge-layout launch with Lambda and a K* store; predict_passes asks for no other)
-#define KS_LAUNCH(DP)                                                                                            \
-  if (sig)                                                                                                       \
-    kstar_kernel<KID, DP, false, true><<<grid, KS_THREADS, 0, s>>>(m->d_X, m->N, m->D, p, m->d_alpha, ld, lo,   \
-                                                                   mblk, d_Xc, M, Kt, ldk, mu_part, t_part,      \
-                                                                   q_per_split, n_q, edge_k0, geo, sig, u_part); \
-  else                                                                                                           \
-    kstar_kernel<KID, DP><<<grid, KS_THREADS, 0, s>>>(m->d_X, m->N, m->D, p, m->d_alpha, ld, lo, mblk, d_Xc, M, \
-                                                      Kt, ldk, mu_part, with_lam ? t_part : nullptr,            \
-                                                      q_per_split, n_q, edge_k0, geo)
-  if constexpr (KID == PPBO_KERNEL_CAMPHOR) { KS_LAUNCH(12); }  // the feature form: 12 staged values per row
-  else if (m->D <= 4) { KS_LAUNCH(4); }
-  else if (m->D <= 6) { KS_LAUNCH(6); }
-  else if (m->D <= 8) { KS_LAUNCH(8); }
-  else if (m->D <= 10) { KS_LAUNCH(10); }
-  else if (m->D <= 12) { KS_LAUNCH(12); }
-  else if (m->D <= 16) { KS_LAUNCH(16); }
-  else if (m->D <= 20) { KS_LAUNCH(20); }
-  else if (m->D <= 24) { KS_LAUNCH(24); }
-  else if (m->D <= 32) { KS_LAUNCH(32); }
-  else if (m->D <= 48) { KS_LAUNCH(48); }
-  else { KS_LAUNCH(64); }
-#undef KS_LAUNCH
+  auto launch = [&](auto dp) {
+    constexpr int DP = decltype(dp)::value;
+    if (sig)
+      kstar_kernel<KID, DP, false, true><<<grid, KS_THREADS, 0, k.s>>>(
+          m->d_X, m->N, m->D, k.p, m->d_alpha, k.lam_diag(), k.lam_off(), k.mblk(), d_Xc, M, k.Kt, k.ldk, k.mu_part, k.t_part,
+          k.q_per_split, k.n_q(), k.edge_k0, geo, sig, u_part);
+    else
+      kstar_kernel<KID, DP><<<grid, KS_THREADS, 0, k.s>>>(
+          m->d_X, m->N, m->D, k.p, m->d_alpha, k.lam_diag(), k.lam_off(), k.mblk(), d_Xc, M, k.Kt, k.ldk, k.mu_part,
+          k.t_or_null(), k.q_per_split, k.n_q(), k.edge_k0, geo);
+  };
+  if constexpr (KID == PPBO_KERNEL_CAMPHOR) launch(std::integral_constant<int, 12>{});  // the feature form: 12 staged values per row
+  else KstarLadder::dispatch(m->D, launch);
   return 0;
 }
 
@@ -2884,12 +2894,11 @@ int launch_kstar(const ppbo_model* m, const KernParams& p, const double* d_Xc, i
 int dispatch_kstar(const ppbo_model* m, const double* d_Xc, int M, double* Kt, int ldk, double* mu_part,
                    double* t_part, int q_per_split, int n_split, bool with_lam, hipStream_t s, int edge_k0 = -1,
                    const double* geo = nullptr, const double* sig = nullptr, double* u_part = nullptr) {
-  const KernParams p = make_kern_params(m->kernel_id, m->theta);
+  const KstarLaunch k{m, make_kern_params(m->kernel_id, m->theta), Kt, ldk, mu_part, t_part, q_per_split, n_split, with_lam,
+                      edge_k0, s};
   // (no ctx: an unknown id returns -1 and sets no message; check_model rejects any such id first)
-  return ppbo_kernel_dispatch(nullptr, m->kernel_id, [&](auto kid) {
-    return launch_kstar<decltype(kid)::value>(m, p, d_Xc, M, Kt, ldk, mu_part, t_part, q_per_split, n_split, with_lam,
-                                              edge_k0, geo, s, sig, u_part);
-  });
+  return ppbo_kernel_dispatch(nullptr, m->kernel_id,
+                              [&](auto kid) { return launch_kstar<decltype(kid)::value>(k, d_Xc, M, geo, sig, u_part); });
 }
 
 // star_geom_kernel on `s` into the ctx's table for this model: the operand `geo` of the K* launch enqueued behind it.
@@ -2909,160 +2918,81 @@ const double* star_geometry(ppbo_ctx* ctx, const ppbo_model* m, hipStream_t s, b
 
 // kstar_pair_kernel in launch_kstar's D buckets (fp64 only); n_split rows splits as there, KS_THREADS pairs per workgroup
 template <int KID>
-int launch_kstar_pair(const ppbo_model* m, const KernParams& p, const double* d_Xa, const double* d_Xb, int M, double* Kt,
-                      int ldk, double* mu_part, double* t_part, int q_per_split, int n_split, bool with_lam, int edge_k0,
-                      hipStream_t s) {
-  dim3 grid((M + KS_THREADS - 1) / KS_THREADS, n_split);
-  const int mblk = m->m + 1, n_q = (m->N + mblk - 1) / mblk;
-  const double* ld = with_lam ? m->d_lam_diag : nullptr;
-  const double* lo = with_lam ? m->d_lam_off : nullptr;
-#define KSP_LAUNCH(DP)                                                                                               \
-  kstar_pair_kernel<KID, DP><<<grid, KS_THREADS, 0, s>>>(m->d_X, m->N, m->D, p, m->d_alpha, ld, lo, mblk, d_Xa, d_Xb, M, \
-                                                         Kt, ldk, mu_part, with_lam ? t_part : nullptr, q_per_split,   \
-                                                         n_q, edge_k0)
-  if constexpr (KID == PPBO_KERNEL_CAMPHOR) KSP_LAUNCH(12);
-  else if (m->D <= 4) KSP_LAUNCH(4);
-  else if (m->D <= 6) KSP_LAUNCH(6);
-  else if (m->D <= 8) KSP_LAUNCH(8);
-  else if (m->D <= 10) KSP_LAUNCH(10);
-  else if (m->D <= 12) KSP_LAUNCH(12);
-  else if (m->D <= 16) KSP_LAUNCH(16);
-  else if (m->D <= 20) KSP_LAUNCH(20);
-  else if (m->D <= 24) KSP_LAUNCH(24);
-  else if (m->D <= 32) KSP_LAUNCH(32);
-  else if (m->D <= 48) KSP_LAUNCH(48);
-  else KSP_LAUNCH(64);
-#undef KSP_LAUNCH
-  return 0;
+void launch_kstar_pair(const KstarLaunch& k, const double* d_Xa, const double* d_Xb, int M) {
+  const ppbo_model* m = k.m;
+  auto launch = [&](auto dp) {
+    kstar_pair_kernel<KID, decltype(dp)::value><<<k.grid(M, KS_THREADS), KS_THREADS, 0, k.s>>>(
+        m->d_X, m->N, m->D, k.p, m->d_alpha, k.lam_diag(), k.lam_off(), k.mblk(), d_Xa, d_Xb, M, k.Kt, k.ldk, k.mu_part,
+        k.t_or_null(), k.q_per_split, k.n_q(), k.edge_k0);
+  };
+  if constexpr (KID == PPBO_KERNEL_CAMPHOR) launch(std::integral_constant<int, 12>{});
+  else KstarLadder::dispatch(m->D, launch);
 }
 
 // kstar_slope_kernel in the same buckets and geometry: d_X the points, d_Xi the directions
 template <int KID>
-int launch_kstar_slope(const ppbo_model* m, const KernParams& p, const double* d_X, const double* d_Xi, int M, double* Kt,
-                       int ldk, double* mu_part, double* t_part, int q_per_split, int n_split, bool with_lam, int edge_k0,
-                       hipStream_t s) {
-  dim3 grid((M + KS_THREADS - 1) / KS_THREADS, n_split);
-  const int mblk = m->m + 1, n_q = (m->N + mblk - 1) / mblk;
-  const double* ld = with_lam ? m->d_lam_diag : nullptr;
-  const double* lo = with_lam ? m->d_lam_off : nullptr;
-#define KSS_LAUNCH(DP)                                                                                                 \
-  kstar_slope_kernel<KID, DP><<<grid, KS_THREADS, 0, s>>>(m->d_X, m->N, m->D, p, m->d_alpha, ld, lo, mblk, d_X, d_Xi, M, \
-                                                          Kt, ldk, mu_part, with_lam ? t_part : nullptr, q_per_split,   \
-                                                          n_q, edge_k0)
-  if constexpr (KID == PPBO_KERNEL_CAMPHOR) KSS_LAUNCH(12);
-  else if (m->D <= 4) KSS_LAUNCH(4);
-  else if (m->D <= 6) KSS_LAUNCH(6);
-  else if (m->D <= 8) KSS_LAUNCH(8);
-  else if (m->D <= 10) KSS_LAUNCH(10);
-  else if (m->D <= 12) KSS_LAUNCH(12);
-  else if (m->D <= 16) KSS_LAUNCH(16);
-  else if (m->D <= 20) KSS_LAUNCH(20);
-  else if (m->D <= 24) KSS_LAUNCH(24);
-  else if (m->D <= 32) KSS_LAUNCH(32);
-  else if (m->D <= 48) KSS_LAUNCH(48);
-  else KSS_LAUNCH(64);
-#undef KSS_LAUNCH
-  return 0;
+void launch_kstar_slope(const KstarLaunch& k, const double* d_X, const double* d_Xi, int M) {
+  const ppbo_model* m = k.m;
+  auto launch = [&](auto dp) {
+    kstar_slope_kernel<KID, decltype(dp)::value><<<k.grid(M, KS_THREADS), KS_THREADS, 0, k.s>>>(
+        m->d_X, m->N, m->D, k.p, m->d_alpha, k.lam_diag(), k.lam_off(), k.mblk(), d_X, d_Xi, M, k.Kt, k.ldk, k.mu_part,
+        k.t_or_null(), k.q_per_split, k.n_q(), k.edge_k0);
+  };
+  if constexpr (KID == PPBO_KERNEL_CAMPHOR) launch(std::integral_constant<int, 12>{});
+  else KstarLadder::dispatch(m->D, launch);
 }
 
-// kstar_grad_kernel in the same buckets and row splits: P points, KG_PTS of them per (one-wavefront) workgroup
+// kstar_grad_kernel in the same buckets and row splits: P points, KG_PTS of them per (one-wavefront) workgroup (the mean only)
 template <int KID>
-int launch_kstar_grad(const ppbo_model* m, const KernParams& p, const double* d_X, int P, double* Kt, int ldk,
-                      double* mu_part, int q_per_split, int n_split, hipStream_t s) {
-  dim3 grid((P + KG_PTS - 1) / KG_PTS, n_split);
-  const int mblk = m->m + 1;
-#define KSG_LAUNCH(DP) \
-  kstar_grad_kernel<KID, DP><<<grid, KG_PTS, 0, s>>>(m->d_X, m->N, m->D, p, m->d_alpha, mblk, d_X, P, Kt, ldk, mu_part, q_per_split)
-  if constexpr (KID == PPBO_KERNEL_CAMPHOR) KSG_LAUNCH(6);
-  else if (m->D <= 4) KSG_LAUNCH(4);
-  else if (m->D <= 6) KSG_LAUNCH(6);
-  else if (m->D <= 8) KSG_LAUNCH(8);
-  else if (m->D <= 10) KSG_LAUNCH(10);
-  else if (m->D <= 12) KSG_LAUNCH(12);
-  else if (m->D <= 16) KSG_LAUNCH(16);
-  else if (m->D <= 20) KSG_LAUNCH(20);
-  else if (m->D <= 24) KSG_LAUNCH(24);
-  else if (m->D <= 32) KSG_LAUNCH(32);
-  else if (m->D <= 48) KSG_LAUNCH(48);
-  else KSG_LAUNCH(64);
-#undef KSG_LAUNCH
-  return 0;
+void launch_kstar_grad(const KstarLaunch& k, const double* d_X, int P) {
+  const ppbo_model* m = k.m;
+  auto launch = [&](auto dp) {
+    kstar_grad_kernel<KID, decltype(dp)::value><<<k.grid(P, KG_PTS), KG_PTS, 0, k.s>>>(
+        m->d_X, m->N, m->D, k.p, m->d_alpha, k.mblk(), d_X, P, k.Kt, k.ldk, k.mu_part, k.q_per_split);
+  };
+  if constexpr (KID == PPBO_KERNEL_CAMPHOR) launch(std::integral_constant<int, 6>{});
+  else KstarLadder::dispatch(m->D, launch);
 }
 
 // kstar_curv_kernel in the same buckets and geometry: d_X the points, d_Xi the directions, d_Xa the accelerations or
 // nullptr (the caller has refused d_Xa with D > 16 or on the camphor kernel, and Matern-3/2 altogether)
 template <int KID>
-int launch_kstar_curv(const ppbo_model* m, const KernParams& p, const double* d_X, const double* d_Xi, const double* d_Xa,
-                      int M, double* Kt, int ldk, double* mu_part, double* t_part, int q_per_split, int n_split,
-                      bool with_lam, int edge_k0, hipStream_t s) {
+void launch_kstar_curv(const KstarLaunch& k, const double* d_X, const double* d_Xi, const double* d_Xa, int M) {
   static_assert(KID != PPBO_KERNEL_MATERN32, "no curvature for Matern-3/2");
-  dim3 grid((M + KS_THREADS - 1) / KS_THREADS, n_split);
-  const int mblk = m->m + 1, n_q = (m->N + mblk - 1) / mblk;
-  const double* ld = with_lam ? m->d_lam_diag : nullptr;
-  const double* lo = with_lam ? m->d_lam_off : nullptr;
-#define KSC_LAUNCH_AS(DP, ACC)                                                                                         \
-  kstar_curv_kernel<KID, DP, ACC><<<grid, KS_THREADS, 0, s>>>(m->d_X, m->N, m->D, p, m->d_alpha, ld, lo, mblk, d_X, d_Xi, \
-                                                              d_Xa, M, Kt, ldk, mu_part, with_lam ? t_part : nullptr,   \
-                                                              q_per_split, n_q, edge_k0)
-#define KSC_LAUNCH(DP)                                                                                                 \
-  do {                                                                                                                 \
-    if (d_Xa) KSC_LAUNCH_AS(DP, true);                                                                                 \
-    else KSC_LAUNCH_AS(DP, false);                                                                                     \
-  } while (0)
-  if constexpr (KID == PPBO_KERNEL_CAMPHOR) KSC_LAUNCH_AS(12, false);
-  else if (m->D <= 4) KSC_LAUNCH(4);
-  else if (m->D <= 6) KSC_LAUNCH(6);
-  else if (m->D <= 8) KSC_LAUNCH(8);
-  else if (m->D <= 10) KSC_LAUNCH(10);
-  else if (m->D <= 12) KSC_LAUNCH(12);
-  else if (m->D <= 16) KSC_LAUNCH(16);
-  else if (m->D <= 20) KSC_LAUNCH_AS(20, false);
-  else if (m->D <= 24) KSC_LAUNCH_AS(24, false);
-  else if (m->D <= 32) KSC_LAUNCH_AS(32, false);
-  else if (m->D <= 48) KSC_LAUNCH_AS(48, false);
-  else KSC_LAUNCH_AS(64, false);
-#undef KSC_LAUNCH
-#undef KSC_LAUNCH_AS
-  return 0;
+  const ppbo_model* m = k.m;
+  auto launch = [&](auto dp, auto acc) {
+    kstar_curv_kernel<KID, decltype(dp)::value, decltype(acc)::value><<<k.grid(M, KS_THREADS), KS_THREADS, 0, k.s>>>(
+        m->d_X, m->N, m->D, k.p, m->d_alpha, k.lam_diag(), k.lam_off(), k.mblk(), d_X, d_Xi, d_Xa, M, k.Kt, k.ldk, k.mu_part,
+        k.t_or_null(), k.q_per_split, k.n_q(), k.edge_k0);
+  };
+  if constexpr (KID == PPBO_KERNEL_CAMPHOR) launch(std::integral_constant<int, 12>{}, std::false_type{});
+  else
+    KstarLadder::dispatch(m->D, [&](auto dp) {
+      if constexpr (decltype(dp)::value <= KSTAR_CURV_ACC_MAX_DP)
+        if (d_Xa) return launch(dp, std::true_type{});
+      launch(dp, std::false_type{});
+    });
 }
-
-// ppbo_predict_functionals' extra operands: the groups are two_set_passes' first point set ([M, G, D]), the weights its second
-struct FuncArgs {
-  int G, w_stride;
-  double threshold;
-};
 
 // kstar_func_kernel in five D buckets (whole MFMA k-steps of 4 dimensions; KF_GROUPS groups per workgroup), the camphor
 // instance as a vector kernel with KS_THREADS groups per workgroup; n_split row splits as launch_kstar_pair
 template <int KID>
-int launch_kstar_func(const ppbo_model* m, const KernParams& p, const double* d_Xg, const double* d_w, const FuncArgs& fa,
-                      int M, double* Kt, int ldk, double* mu_part, double* t_part, int q_per_split, int n_split,
-                      bool with_lam, int edge_k0, hipStream_t s) {
-  const int mblk = m->m + 1, n_q = (m->N + mblk - 1) / mblk;
-  const double* ld = with_lam ? m->d_lam_diag : nullptr;
-  const double* lo = with_lam ? m->d_lam_off : nullptr;
+void launch_kstar_func(const KstarLaunch& k, const double* d_Xg, const double* d_w, int w_stride, int G, int M) {
+  const ppbo_model* m = k.m;
   if constexpr (KID == PPBO_KERNEL_CAMPHOR) {
-    dim3 grid((M + KS_THREADS - 1) / KS_THREADS, n_split);
-    kstar_func_camphor_kernel<<<grid, KS_THREADS, 0, s>>>(m->d_X, m->N, m->D, p, m->d_alpha, ld, lo, mblk, d_Xg, d_w,
-                                                          fa.w_stride, fa.G, M, Kt, ldk, mu_part,
-                                                          with_lam ? t_part : nullptr, q_per_split, n_q, edge_k0);
+    kstar_func_camphor_kernel<<<k.grid(M, KS_THREADS), KS_THREADS, 0, k.s>>>(
+        m->d_X, m->N, m->D, k.p, m->d_alpha, k.lam_diag(), k.lam_off(), k.mblk(), d_Xg, d_w, w_stride, G, M, k.Kt, k.ldk,
+        k.mu_part, k.t_or_null(), k.q_per_split, k.n_q(), k.edge_k0);
   } else {
-    dim3 grid((M + KF_GROUPS - 1) / KF_GROUPS, n_split);
-#define KSF_LAUNCH(DP)                                                                                                  \
-  kstar_func_kernel<KID, DP><<<grid, 256, 0, s>>>(m->d_X, m->N, m->D, p, m->d_alpha, ld, lo, mblk, d_Xg, d_w, fa.w_stride, \
-                                                  fa.G, M, Kt, ldk, mu_part, with_lam ? t_part : nullptr, q_per_split,  \
-                                                  n_q, edge_k0)
-    if (m->D <= 8) KSF_LAUNCH(8);
-    else if (m->D <= 20) KSF_LAUNCH(20);
-    else if (m->D <= 32) KSF_LAUNCH(32);
-    else if (m->D <= 48) KSF_LAUNCH(48);
-    else KSF_LAUNCH(64);
-#undef KSF_LAUNCH
+    KstarFuncLadder::dispatch(m->D, [&](auto dp) {
+      kstar_func_kernel<KID, decltype(dp)::value><<<k.grid(M, KF_GROUPS), 256, 0, k.s>>>(
+          m->d_X, m->N, m->D, k.p, m->d_alpha, k.lam_diag(), k.lam_off(), k.mblk(), d_Xg, d_w, w_stride, G, M, k.Kt, k.ldk,
+          k.mu_part, k.t_or_null(), k.q_per_split, k.n_q(), k.edge_k0);
+    });
   }
-  return 0;
 }
 
-// ppbo_predict_marginals' operands: the rows of the call are d_dims / d_t [M, 2] (two_set_passes' point sets are not used)
+// ppbo_predict_marginals' operands: the rows of the call are d_dims / d_t [M, 2]
 struct MargArgs {
   const ppbo_marginal_axes* ax;
   const int* d_dims;
@@ -3323,6 +3253,14 @@ int pick_split(int M, int n_q) {
   return want;
 }
 
+// the row splits of a K* launch over M columns: pick_split's count, the stars per split, the splits that hold a star
+struct RowSplit { int n_split, q_per_split, n_split_eff; };
+RowSplit row_split(int M, int n_q) {
+  const int n_split = pick_split(M, n_q);
+  const int q_per_split = (n_q + n_split - 1) / n_split;
+  return RowSplit{n_split, q_per_split, (n_q + q_per_split - 1) / q_per_split};
+}
+
 }  // namespace
 
 extern "C" {
@@ -3423,9 +3361,8 @@ static int predict_passes(ppbo_ctx* ctx, const ppbo_model* model, const double* 
   // workspaces sized for the largest chunk
   const int Mc_max = (int)(M < chunk_cap ? M : chunk_cap);
   const int ldk = (Mc_max + 127) & ~127;
-  const int n_split = pick_split(Mc_max, n_q);
-  const int q_per_split = (n_q + n_split - 1) / n_split;
-  const int n_split_eff = (n_q + q_per_split - 1) / q_per_split;
+  const RowSplit rs = row_split(Mc_max, n_q);
+  const int q_per_split = rs.q_per_split, n_split_eff = rs.n_split_eff;
   double* Kt = nullptr;
   if (want_var) {
     Kt = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_KSTAR, (size_t)Nk * ldk * sizeof(double));
@@ -3607,67 +3544,82 @@ int ppbo_predict_prune_report(ppbo_ctx* ctx, const ppbo_model* model, const doub
   return 0;
 }
 
-// Duels and slopes: two [M, D] point sets per column -- the sides (a, b) of a duel, or the point and the direction
-// (x, xi) of a slope.  Per chunk of 65536 columns kstar_pair / kstar_slope -> quadform -> pair_score / slope_score ->
-// one-workgroup argmax, with predict_passes' workspaces and operand padding.  Both operator forms take these three
-// launches (the one-launch kernel of fused.hip holds one point per column).  The score kinds of the two entries carry
-// the same values (mean, variance, probability).
+}  // extern "C"
+
+// The two-set predictors: duels, slopes, curvatures, functionals and marginals.  (Their entry points are extern "C" by
+// their declarations in ppbo_hip.h; the descriptors beside them hold templates, so this section is outside the block.)
+// Each scores M columns that are no single point -- the sides of a duel, a point and a direction, a group of points and
+// its weights, a pair of axes -- and brings a small descriptor with its messages, its own argument rules, its
+// preparation, and its K* and score launches for a chunk.  two_set_passes is what they share: per chunk of 65536
+// columns K* -> quadform -> score -> one-workgroup argmax, with predict_passes' workspaces and operand padding.  Both
+// operator forms take these three launches (the one-launch kernel of fused.hip holds one point per column).  The score
+// kinds of the five entries carry the same values (mean, variance, probability).
 static_assert(PPBO_SLOPE_MEAN == PPBO_PAIR_MEAN && PPBO_SLOPE_VARIANCE == PPBO_PAIR_VARIANCE && PPBO_SLOPE_PROB == PPBO_PAIR_PROB,
               "one score_kind check for both entries");
-// Curvatures (ppbo_predict_curvatures) are the third user: a point, a direction and optionally an acceleration per
-// column, kstar_curv -> quadform -> curv_score.
 static_assert(PPBO_CURV_MEAN == PPBO_PAIR_MEAN && PPBO_CURV_VARIANCE == PPBO_PAIR_VARIANCE && PPBO_CURV_PROB == PPBO_PAIR_PROB,
               "one score_kind check for all three entries");
-// Functionals (ppbo_predict_functionals) are the fourth: d_Xa the groups [M, G, D], d_Xb the weights ([G], or [M, G]),
-// `fa` their sizes and the threshold; kstar_func -> quadform -> functional_score.  fa is NULL for the other three.
-// Marginals (ppbo_predict_marginals) are the fifth: the rows of the call are `ma`'s d_dims / d_t [M, 2] (d_Xa = d_Xb = d_t),
-// the column comes from ma's axes and the table marginal_table_kernel leaves per call, not from model->d_X;
-// kstar_marginal -> quadform -> marginal_score.  Its row splits are those of a FULL chunk whatever M is, so that a row's
-// sums do not depend on the size of the call.  ma is NULL for the other four.
-enum { TS_PAIRS = 0, TS_SLOPES = 1, TS_CURV = 2, TS_FUNC = 3, TS_MARG = 4 };
-static int two_set_passes(ppbo_ctx* ctx, const int what, const ppbo_model* model, const double* d_Xa, const double* d_Xb,
-                          const double* d_Xacc, int64_t M, int score_kind, double* d_mu, double* d_var, double* d_prob,
-                          double* d_score, double* h_best_val, int64_t* h_best_idx, hipStream_t s,
-                          const FuncArgs* fa = nullptr, MargArgs* ma = nullptr) {
-  const bool slopes = what == TS_SLOPES, curv = what == TS_CURV, func = what == TS_FUNC, marg = what == TS_MARG;
+static_assert(PPBO_FUNCTIONAL_MEAN == PPBO_PAIR_MEAN && PPBO_FUNCTIONAL_VARIANCE == PPBO_PAIR_VARIANCE &&
+                  PPBO_FUNCTIONAL_PROB == PPBO_PAIR_PROB,
+              "one score_kind check for all four entries");
+
+// A code object holds its kernels in the order their instantiations are first asked for.  For this section that order
+// is stated here, per kernel id (the K* launchers, then the score kernels), so that it depends neither on the order of
+// the entry points below nor on how they share their code.  Never called; it names nothing that no entry point launches.
+template <int KID>
+static void two_set_kernel_order() {
+  (void)&launch_kstar_func<KID>;
+  if constexpr (KID != PPBO_KERNEL_MATERN32) (void)&launch_kstar_curv<KID>;
+  (void)&launch_kstar_slope<KID>;
+  (void)&launch_kstar_pair<KID>;
+  (void)&functional_prior_kernel<KID>;
+  if constexpr (KID != PPBO_KERNEL_MATERN32) (void)&curv_score_kernel<KID>;
+  (void)&slope_score_kernel<KID>;
+  (void)&pair_score_kernel<KID>;
+}
+template void two_set_kernel_order<PPBO_KERNEL_SE>();
+template void two_set_kernel_order<PPBO_KERNEL_RQ>();
+template void two_set_kernel_order<PPBO_KERNEL_MATERN52>();
+template void two_set_kernel_order<PPBO_KERNEL_MATERN32>();
+template void two_set_kernel_order<PPBO_KERNEL_CAMPHOR>();
+
+// A chunk's score launch: the sums of its K* and contraction launches (slab NULL: no variance; extra: the predictor's
+// extra_part_rows rows behind them), its first column, its results (stepped to the chunk, or NULL; bests NULL: no best)
+struct TwoSetScore {
+  const ppbo_model* m;
+  KernParams p;
+  const double *mu_part, *t_part, *slab;
+  double* extra;
+  int n_split, ntm, Mc, score_kind, sblocks;
+  long long c_beg;
+  double *d_mu, *d_var, *d_prob, *d_score;
+  Best* bests;
+  hipStream_t s;
+};
+// the parts of a descriptor that most predictors leave as they are
+struct TwoSetBase {
+  static constexpr const char* rows = "row count (1 .. 2^31 - 1)";
+  static constexpr bool full_chunk_splits = false;     // row splits picked for a full chunk whatever M is
+  static constexpr int extra_part_rows = 0;
+  int check(ppbo_ctx*, const ppbo_model*) { return 0; }                      // its own argument rules
+  // (once per call, before the first chunk; the Best records: sblocks_max of them that nothing has written yet)
+  int prepare(ppbo_ctx*, const ppbo_model*, const KernParams&, int64_t, Best*, int, hipStream_t) { return 0; }
+};
+
+template <class Pred>
+static int two_set_passes(ppbo_ctx* ctx, const ppbo_model* model, Pred& pr, int64_t M, int score_kind, double* d_mu,
+                          double* d_var, double* d_prob, double* d_score, double* h_best_val, int64_t* h_best_idx,
+                          hipStream_t s) {
   if (int rc = check_model(ctx, model)) return rc;
-  PPBO_REQUIRE(ctx, d_Xa != nullptr && d_Xb != nullptr,
-               marg ? "marginals (d_dims / d_t)" : func ? "functionals (d_Xg / d_w)" : curv ? "curvatures (d_X / d_Xi)" : slopes ? "slopes (d_X / d_Xi)" : "pairs (d_Xa / d_Xb)");
-  PPBO_REQUIRE(ctx, M >= 1 && M <= (int64_t)0x7fffffff, what != TS_PAIRS ? "row count (1 .. 2^31 - 1)" : "pair count (1 .. 2^31 - 1)");
-  if (func) {
-    PPBO_REQUIRE(ctx, fa != nullptr && fa->G >= 1 && fa->G <= PPBO_FUNCTIONAL_MAX_G, "G (1 .. PPBO_FUNCTIONAL_MAX_G points per group)");
-    PPBO_REQUIRE(ctx, fa->w_stride == 0 || fa->w_stride == fa->G, "w_stride (0: one weight row for all groups, G: one per group)");
-    PPBO_REQUIRE(ctx, std::isfinite(fa->threshold), "threshold (finite)");
-  }
+  PPBO_REQUIRE(ctx, pr.has_operands(), Pred::operands);
+  PPBO_REQUIRE(ctx, M >= 1 && M <= (int64_t)0x7fffffff, Pred::rows);
   PPBO_REQUIRE(ctx, score_kind == PPBO_PAIR_MEAN || score_kind == PPBO_PAIR_VARIANCE || score_kind == PPBO_PAIR_PROB,
                "score_kind");
-  if (marg) {
-    PPBO_REQUIRE(ctx, ma != nullptr && ma->d_dims != nullptr, "marginals (d_dims / d_t)");
-    PPBO_REQUIRE(ctx, model->kernel_id == PPBO_KERNEL_SE || model->kernel_id == PPBO_KERNEL_CAMPHOR,
-                 "marginals need a kernel that is a product over coordinates (SE, camphor-copper); RQ and Matern: sample with "
-                 "ppbo_predict_functionals (average_pred)");
-    PPBO_REQUIRE(ctx, ma->effect == PPBO_EFFECT_RAW || ma->effect == PPBO_EFFECT_CENTRED || ma->effect == PPBO_EFFECT_INTERACTION,
-                 "effect");
-    if (int rc = marginal_axes_arg(ctx, ma)) return rc;
-    const bool six = model->kernel_id == PPBO_KERNEL_CAMPHOR || model->coords.kind == PPBO_COORDS_CAMPHOR;
-    PPBO_REQUIRE(ctx, ma->ax->Dc == (six ? 6 : model->D), "axes->Dc: the model's D (6 for the camphor kernels)");
-  }
-  PPBO_REQUIRE(ctx, !model->kstar_fp32, marg ? "marginals are fp64 only (kstar_fp32)" : func ? "functionals are fp64 only (kstar_fp32)"
-                                             : curv ? "curvatures are fp64 only (kstar_fp32)"
-                                             : slopes ? "slopes are fp64 only (kstar_fp32)" : "pairs are fp64 only (kstar_fp32)");
-  if (curv) {
-    PPBO_REQUIRE(ctx, model->kernel_id != PPBO_KERNEL_MATERN32,
-                 "no curvature for Matern-3/2 (its sample paths are differentiable once only)");
-    PPBO_REQUIRE(ctx, d_Xacc == nullptr || (model->D <= 16 && model->kernel_id != PPBO_KERNEL_CAMPHOR),
-                 "accelerations (d_Xa): D <= 16 and not the camphor-copper kernel");
-  }
+  if (int rc = pr.check(ctx, model)) return rc;
+  PPBO_REQUIRE(ctx, !model->kstar_fp32, Pred::fp64_only);
   const bool want_var = d_var || d_prob || score_kind != PPBO_PAIR_MEAN;
   PPBO_REQUIRE(ctx, !want_var || model->d_G != nullptr, "variance / probability need model->d_G");
   PPBO_REQUIRE(ctx, !want_var || (model->d_lam_diag && model->d_lam_off), "model Lambda");
   const bool want_best = h_best_val || h_best_idx;
-  PpboHostRecord hr{};
-  if (want_best)
-    if (int rc = ppbo_host_record(ctx, &hr)) return rc;
   const int N = model->N, mblk = model->m + 1, n_q = N / mblk;
   const int edge_k0 = (want_var && model->form == PPBO_FORM_EDGE) ? ppbo_edge_k0(n_q) : -1;
   const KernParams p = make_kern_params(model->kernel_id, model->theta);
@@ -3684,90 +3636,42 @@ static int two_set_passes(ppbo_ctx* ctx, const int what, const ppbo_model* model
   }
   const int Mc_max = (int)(M < chunk_cap ? M : chunk_cap);
   const int ldk = (Mc_max + 127) & ~127;
-  const int n_split = pick_split(marg ? (int)chunk_cap : Mc_max, n_q);
-  const int q_per_split = (n_q + n_split - 1) / n_split;
-  const int n_split_eff = (n_q + q_per_split - 1) / q_per_split;
+  const RowSplit rs = row_split(Pred::full_chunk_splits ? (int)chunk_cap : Mc_max, n_q);
+  const int q_per_split = rs.q_per_split, n_split_eff = rs.n_split_eff;
   double* Kt = nullptr;
   if (want_var) {
     Kt = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_KSTAR, (size_t)Nk * ldk * sizeof(double));
     if (!Kt) return (int)hipErrorOutOfMemory;
     if (Nk != N) PPBO_HIP_CHECK(ctx, hipMemsetAsync(Kt + (size_t)N * ldk, 0, (size_t)(Nk - N) * ldk * sizeof(double), s));
   }
-  double* marg_tab = nullptr;
-  if (marg) {
-    marg_tab = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_MARGINAL, marginal_table_doubles(N, ma->arg.Dc) * sizeof(double));
-    if (!marg_tab) return (int)hipErrorOutOfMemory;
-  }
-  // (functionals: one more row of the partial-sum workspace for the groups' prior terms)
-  double* part = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_PART, (size_t)(2 * n_split_eff + ntm + (func ? 1 : 0)) * Mc_max * sizeof(double));
+  double* part = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_PART, (size_t)(2 * n_split_eff + ntm + Pred::extra_part_rows) * Mc_max * sizeof(double));
   if (!part) return (int)hipErrorOutOfMemory;
-  double* func_prior = func ? part + (size_t)(2 * n_split_eff + ntm) * Mc_max : nullptr;
   const int sblocks_max = score_blocks(Mc_max);
   Best* bests = (Best*)ppbo_workspace(ctx, ppbo_ctx::WS_SMALL, (size_t)(sblocks_max + n_chunks) * sizeof(Best));
   if (!bests) return (int)hipErrorOutOfMemory;
   Best* chunk_best = bests + sblocks_max;
-  const double two_sigma2 = 2.0 * model->theta[0] * model->theta[0];
-  if (marg) {
-    // the rows of d_dims are looked at on the device BEFORE anything is launched on the outputs: the first row that breaks
-    // the rules comes back through the host-mapped record.  A stream that is being captured cannot be waited on: there
-    // the look is left out, and such a row gets NaN results (marginal_row)
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    (void)hipStreamIsCapturing(s, &cap);
-    if (cap == hipStreamCaptureStatusNone) {
-      PpboHostRecord chk{};
-      if (int rc = ppbo_host_record(ctx, &chk)) return rc;
-      const int cblocks = (int)std::min<int64_t>((M + 255) / 256, (int64_t)sblocks_max);
-      marginal_check_kernel<<<cblocks, 256, 0, s>>>(ma->d_dims, (long long)M, ma->arg.Dc, ma->effect, bests);
-      PPBO_LAUNCH_CHECK(ctx);
-      argmax_final_kernel<<<1, 256, 0, s>>>(bests, cblocks, nullptr, chk.d_rec, 0, chk.d_flag, chk.epoch);
-      PPBO_LAUNCH_CHECK(ctx);
-      if (int rc = ppbo_host_record_wait(ctx, chk, s)) return rc;
-      const long long bad = (long long)chk.h_rec[1];
-      if (bad >= 0)
-        return ppbo_set_error(ctx, -1,
-                              "invalid argument: d_dims row %lld (axes in -1 .. Dc - 1, two different ones, no first axis of -1 "
-                              "with a second one, two axes for an interaction)", bad);
-      if (want_best)               // (a fresh epoch for the call's own record, behind the check's)
-        if (int rc = ppbo_host_record(ctx, &hr)) return rc;
-    }
-    marginal_table_kernel<<<(N + 255) / 256, 256, 0, s>>>(ma->arg, ma->ax->d_Xu, N, p.sf2, marg_tab);
-    PPBO_LAUNCH_CHECK(ctx);
-  }
+  if (int rc = pr.prepare(ctx, model, p, M, bests, sblocks_max, s)) return rc;
+  PpboHostRecord hr{};             // (behind the preparation, which may have used the ctx's record for a check of its own)
+  if (want_best)
+    if (int rc = ppbo_host_record(ctx, &hr)) return rc;
   for (int64_t ch = 0; ch < n_chunks; ++ch) {
     const int64_t c_beg = ch * chunk_cap;
     const int Mc = (int)((M - c_beg) < chunk_cap ? (M - c_beg) : chunk_cap);
-    const double* xa = d_Xa + (size_t)c_beg * model->D * (func ? fa->G : 1);
-    const double* xb = d_Xb + (size_t)c_beg * (func ? fa->w_stride : model->D);
-    const double* xacc = d_Xacc ? d_Xacc + (size_t)c_beg * model->D : nullptr;
     double* mu_part = part;
     double* t_part = part + (size_t)n_split_eff * Mc;
     double* slab = part + (size_t)2 * n_split_eff * Mc;
     const int sblocks = score_blocks(Mc);
     const bool one = (n_chunks == 1);
+    const KstarLaunch k{model, p, Kt, ldk, mu_part, t_part, q_per_split, n_split_eff, want_var, edge_k0, s};
+    const TwoSetScore sc{model, p, mu_part, t_part, want_var ? slab : nullptr, part + (size_t)(2 * n_split_eff + ntm) * Mc_max,
+                         n_split_eff, ntm, Mc, score_kind, sblocks, (long long)c_beg, d_mu ? d_mu + c_beg : nullptr,
+                         d_var ? d_var + c_beg : nullptr, d_prob ? d_prob + c_beg : nullptr,
+                         d_score ? d_score + c_beg : nullptr, want_best ? bests : nullptr, s};
     if (int rc = ppbo_kernel_dispatch(ctx, model->kernel_id, [&](auto kid) {
           constexpr int KID = decltype(kid)::value;
           {
             PpboProfScope pf(ctx, ppbo_ctx::PF_KSTAR, s);
-            if (marg) {
-              dim3 grid((Mc + KS_THREADS - 1) / KS_THREADS, n_split_eff);
-              const int Dc = ma->arg.Dc;
-              kstar_marginal_kernel<<<grid, KS_THREADS, (size_t)2 * KS_RJ * Dc * sizeof(double), s>>>(
-                  ma->ax->d_Xu, N, Dc, marg_tab, model->d_alpha, want_var ? model->d_lam_diag : nullptr,
-                  want_var ? model->d_lam_off : nullptr, mblk, ma->d_dims + (size_t)c_beg * 2, ma->d_t + (size_t)c_beg * 2,
-                  ma->effect, Mc, Kt, ldk, mu_part, want_var ? t_part : nullptr, q_per_split, n_q, edge_k0);
-            } else if (func)
-              launch_kstar_func<KID>(model, p, xa, xb, *fa, Mc, Kt, ldk, mu_part, t_part, q_per_split, n_split_eff, want_var,
-                                     edge_k0, s);
-            else if (curv) {
-              if constexpr (KID != PPBO_KERNEL_MATERN32)       // refused above
-                launch_kstar_curv<KID>(model, p, xa, xb, xacc, Mc, Kt, ldk, mu_part, t_part, q_per_split, n_split_eff,
-                                       want_var, edge_k0, s);
-            } else if (slopes)
-              launch_kstar_slope<KID>(model, p, xa, xb, Mc, Kt, ldk, mu_part, t_part, q_per_split, n_split_eff, want_var,
-                                      edge_k0, s);
-            else
-              launch_kstar_pair<KID>(model, p, xa, xb, Mc, Kt, ldk, mu_part, t_part, q_per_split, n_split_eff, want_var,
-                                     edge_k0, s);
+            pr.template kstar<KID>(k, c_beg, Mc);
           }
           PPBO_LAUNCH_CHECK(ctx);
           if (want_var) {
@@ -3775,41 +3679,7 @@ static int two_set_passes(ppbo_ctx* ctx, const int what, const ppbo_model* model
             if (int rc2 = dispatch_quadform(ctx, Gq, Nk, g_rows, N, Kt, ldk, Mc, mblk, slab, edge_k0, s)) return rc2;
           }
           PpboProfScope pfs(ctx, ppbo_ctx::PF_SCORE, s);
-          if (marg) {
-            marginal_score_kernel<<<sblocks, SC_THREADS, 0, s>>>(
-                mu_part, n_split_eff, t_part, want_var ? slab : nullptr, ntm, Mc, ma->d_dims + (size_t)c_beg * 2,
-                ma->d_t + (size_t)c_beg * 2, marg_tab, ma->arg.Dc, p.sf2, ma->prod_A, ma->effect, score_kind, (long long)c_beg,
-                d_mu ? d_mu + c_beg : nullptr, d_var ? d_var + c_beg : nullptr, d_prob ? d_prob + c_beg : nullptr,
-                d_score ? d_score + c_beg : nullptr, want_best ? bests : nullptr);
-          } else if (func) {
-            if (want_var) {
-              // one wavefront per group; as many per workgroup (4, 2, 1) as 48 KB of LDS hold of G (D + 1) doubles each
-              const size_t per_wave = (size_t)fa->G * (model->D + 1) * sizeof(double);
-              const int wpb = 4 * per_wave <= 49152 ? 4 : (2 * per_wave <= 49152 ? 2 : 1);
-              functional_prior_kernel<KID><<<(Mc + wpb - 1) / wpb, 64 * wpb, wpb * per_wave, s>>>(
-                  xa, xb, fa->w_stride, fa->G, model->D, Mc, p, func_prior);
-            }
-            functional_score_kernel<<<sblocks, SC_THREADS, 0, s>>>(
-                mu_part, n_split_eff, t_part, want_var ? slab : nullptr, ntm, Mc, func_prior, fa->threshold, score_kind,
-                (long long)c_beg, d_mu ? d_mu + c_beg : nullptr, d_var ? d_var + c_beg : nullptr,
-                d_prob ? d_prob + c_beg : nullptr, d_score ? d_score + c_beg : nullptr, want_best ? bests : nullptr);
-          }
-          else if (curv) {
-            if constexpr (KID != PPBO_KERNEL_MATERN32)
-              curv_score_kernel<KID><<<sblocks, SC_THREADS, 0, s>>>(
-                  mu_part, n_split_eff, t_part, want_var ? slab : nullptr, ntm, Mc, xb, xacc, model->D, p, score_kind,
-                  (long long)c_beg, d_mu ? d_mu + c_beg : nullptr, d_var ? d_var + c_beg : nullptr,
-                  d_prob ? d_prob + c_beg : nullptr, d_score ? d_score + c_beg : nullptr, want_best ? bests : nullptr);
-          } else if (slopes)
-            slope_score_kernel<KID><<<sblocks, SC_THREADS, 0, s>>>(
-                mu_part, n_split_eff, t_part, want_var ? slab : nullptr, ntm, Mc, xb, model->D, p, score_kind,
-                (long long)c_beg, d_mu ? d_mu + c_beg : nullptr, d_var ? d_var + c_beg : nullptr,
-                d_prob ? d_prob + c_beg : nullptr, d_score ? d_score + c_beg : nullptr, want_best ? bests : nullptr);
-          else
-            pair_score_kernel<KID><<<sblocks, SC_THREADS, 0, s>>>(
-                mu_part, n_split_eff, t_part, want_var ? slab : nullptr, ntm, Mc, xa, xb, model->D, p, two_sigma2, score_kind,
-                (long long)c_beg, d_mu ? d_mu + c_beg : nullptr, d_var ? d_var + c_beg : nullptr,
-                d_prob ? d_prob + c_beg : nullptr, d_score ? d_score + c_beg : nullptr, want_best ? bests : nullptr);
+          pr.template score<KID>(sc);
           PPBO_LAUNCH_CHECK(ctx);
           return 0;
         }))
@@ -3831,62 +3701,219 @@ static int two_set_passes(ppbo_ctx* ctx, const int what, const ppbo_model* model
   return 0;
 }
 
+// Duels: the sides (a, b) of a duel, [M, D] each; kstar_pair -> quadform -> pair_score
+struct PairsPred : TwoSetBase {
+  static constexpr const char* operands = "pairs (d_Xa / d_Xb)";
+  static constexpr const char* rows = "pair count (1 .. 2^31 - 1)";
+  static constexpr const char* fp64_only = "pairs are fp64 only (kstar_fp32)";
+  const double *d_Xa, *d_Xb;
+  bool has_operands() const { return d_Xa && d_Xb; }
+  template <int KID>
+  void kstar(const KstarLaunch& k, int64_t c_beg, int Mc) const {
+    const size_t o = (size_t)c_beg * k.m->D;
+    launch_kstar_pair<KID>(k, d_Xa + o, d_Xb + o, Mc);
+  }
+  template <int KID>
+  void score(const TwoSetScore& sc) const {
+    const size_t o = (size_t)sc.c_beg * sc.m->D;
+    const double two_sigma2 = 2.0 * sc.m->theta[0] * sc.m->theta[0];
+    pair_score_kernel<KID><<<sc.sblocks, SC_THREADS, 0, sc.s>>>(sc.mu_part, sc.n_split, sc.t_part, sc.slab, sc.ntm, sc.Mc,
+                                                                d_Xa + o, d_Xb + o, sc.m->D, sc.p, two_sigma2, sc.score_kind,
+                                                                sc.c_beg, sc.d_mu, sc.d_var, sc.d_prob, sc.d_score, sc.bests);
+  }
+};
 int ppbo_predict_pairs(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xa, const double* d_Xb, int64_t M,
                        int score_kind, double* d_mu, double* d_var, double* d_prob, double* d_score, double* h_best_val,
                        int64_t* h_best_idx, void* stream) {
   PPBO_ENTER(ctx);
-  return two_set_passes(ctx, TS_PAIRS, model, d_Xa, d_Xb, nullptr, M, score_kind, d_mu, d_var, d_prob, d_score, h_best_val, h_best_idx,
-                        (hipStream_t)stream);
+  PairsPred pr{{}, d_Xa, d_Xb};
+  return two_set_passes(ctx, model, pr, M, score_kind, d_mu, d_var, d_prob, d_score, h_best_val, h_best_idx, (hipStream_t)stream);
 }
 
-// Slopes: the column g = d/da k(x + a xi, X) at a = 0 in place of a duel's difference column; the K* launches share the
-// "kstar" profile slot with ppbo_predict and ppbo_predict_pairs.
+// Slopes: the column g = d/da k(x + a xi, X) at a = 0 in place of a duel's difference column, from the point and the
+// direction (x, xi), [M, D] each; kstar_slope -> quadform -> slope_score.  The K* launches share the "kstar" profile slot
+// with ppbo_predict and ppbo_predict_pairs.
+struct SlopesPred : TwoSetBase {
+  static constexpr const char* operands = "slopes (d_X / d_Xi)";
+  static constexpr const char* fp64_only = "slopes are fp64 only (kstar_fp32)";
+  const double *d_X, *d_Xi;
+  bool has_operands() const { return d_X && d_Xi; }
+  template <int KID>
+  void kstar(const KstarLaunch& k, int64_t c_beg, int Mc) const {
+    const size_t o = (size_t)c_beg * k.m->D;
+    launch_kstar_slope<KID>(k, d_X + o, d_Xi + o, Mc);
+  }
+  template <int KID>
+  void score(const TwoSetScore& sc) const {
+    slope_score_kernel<KID><<<sc.sblocks, SC_THREADS, 0, sc.s>>>(sc.mu_part, sc.n_split, sc.t_part, sc.slab, sc.ntm, sc.Mc,
+                                                                 d_Xi + (size_t)sc.c_beg * sc.m->D, sc.m->D, sc.p, sc.score_kind,
+                                                                 sc.c_beg, sc.d_mu, sc.d_var, sc.d_prob, sc.d_score, sc.bests);
+  }
+};
 int ppbo_predict_slopes(ppbo_ctx* ctx, const ppbo_model* model, const double* d_X, const double* d_Xi, int64_t M,
                         int score_kind, double* d_mu, double* d_var, double* d_prob, double* d_score, double* h_best_val,
                         int64_t* h_best_idx, void* stream) {
   PPBO_ENTER(ctx);
-  return two_set_passes(ctx, TS_SLOPES, model, d_X, d_Xi, nullptr, M, score_kind, d_mu, d_var, d_prob, d_score, h_best_val, h_best_idx,
-                        (hipStream_t)stream);
+  SlopesPred pr{{}, d_X, d_Xi};
+  return two_set_passes(ctx, model, pr, M, score_kind, d_mu, d_var, d_prob, d_score, h_best_val, h_best_idx, (hipStream_t)stream);
 }
 
 // Curvatures: the column c = d^2/da^2 k(gamma(a), X) at a = 0 for the path through x with velocity xi and acceleration
-// acc (d_Xa == NULL: straight lines); the K* launches share the "kstar" profile slot.
+// acc (d_Xa == NULL: straight lines), [M, D] each; kstar_curv -> quadform -> curv_score.  The K* launches share the
+// "kstar" profile slot.  Matern-3/2 is refused by check(), and nothing is instantiated for it.
+struct CurvaturesPred : TwoSetBase {
+  static constexpr const char* operands = "curvatures (d_X / d_Xi)";
+  static constexpr const char* fp64_only = "curvatures are fp64 only (kstar_fp32)";
+  const double *d_X, *d_Xi, *d_Xa;
+  bool has_operands() const { return d_X && d_Xi; }
+  int check(ppbo_ctx* ctx, const ppbo_model* model) {
+    PPBO_REQUIRE(ctx, model->kernel_id != PPBO_KERNEL_MATERN32,
+                 "no curvature for Matern-3/2 (its sample paths are differentiable once only)");
+    PPBO_REQUIRE(ctx, d_Xa == nullptr || (model->D <= KSTAR_CURV_ACC_MAX_DP && model->kernel_id != PPBO_KERNEL_CAMPHOR),
+                 "accelerations (d_Xa): D <= 16 and not the camphor-copper kernel");
+    return 0;
+  }
+  template <int KID>
+  void kstar(const KstarLaunch& k, int64_t c_beg, int Mc) const {
+    const size_t o = (size_t)c_beg * k.m->D;
+    if constexpr (KID != PPBO_KERNEL_MATERN32) launch_kstar_curv<KID>(k, d_X + o, d_Xi + o, d_Xa ? d_Xa + o : nullptr, Mc);
+  }
+  template <int KID>
+  void score(const TwoSetScore& sc) const {
+    const size_t o = (size_t)sc.c_beg * sc.m->D;
+    if constexpr (KID != PPBO_KERNEL_MATERN32)
+      curv_score_kernel<KID><<<sc.sblocks, SC_THREADS, 0, sc.s>>>(sc.mu_part, sc.n_split, sc.t_part, sc.slab, sc.ntm, sc.Mc,
+                                                                  d_Xi + o, d_Xa ? d_Xa + o : nullptr, sc.m->D, sc.p,
+                                                                  sc.score_kind, sc.c_beg, sc.d_mu, sc.d_var, sc.d_prob,
+                                                                  sc.d_score, sc.bests);
+  }
+};
 int ppbo_predict_curvatures(ppbo_ctx* ctx, const ppbo_model* model, const double* d_X, const double* d_Xi, const double* d_Xa,
                             int64_t M, int score_kind, double* d_mu, double* d_var, double* d_prob, double* d_score,
                             double* h_best_val, int64_t* h_best_idx, void* stream) {
   PPBO_ENTER(ctx);
-  return two_set_passes(ctx, TS_CURV, model, d_X, d_Xi, d_Xa, M, score_kind, d_mu, d_var, d_prob, d_score, h_best_val,
-                        h_best_idx, (hipStream_t)stream);
+  CurvaturesPred pr{{}, d_X, d_Xi, d_Xa};
+  return two_set_passes(ctx, model, pr, M, score_kind, d_mu, d_var, d_prob, d_score, h_best_val, h_best_idx, (hipStream_t)stream);
 }
 
-// Functionals: the column c = sum_g w_g k(x_g, X) of L f = sum_g w_g f(x_g) for M groups of G points: ONE contraction per
-// group whatever G is; the K* launches share the "kstar" profile slot.
-static_assert(PPBO_FUNCTIONAL_MEAN == PPBO_PAIR_MEAN && PPBO_FUNCTIONAL_VARIANCE == PPBO_PAIR_VARIANCE &&
-                  PPBO_FUNCTIONAL_PROB == PPBO_PAIR_PROB,
-              "one score_kind check for all four entries");
+// Functionals: the column c = sum_g w_g k(x_g, X) of L f = sum_g w_g f(x_g) for M groups of G points, d_Xg [M, G, D], with
+// the weights d_w ([G], or [M, G]): ONE contraction per group whatever G is; kstar_func -> quadform -> functional_score.
+// The groups' prior terms take one more row of the partial-sum workspace.  The K* launches share the "kstar" profile slot.
+struct FunctionalsPred : TwoSetBase {
+  static constexpr const char* operands = "functionals (d_Xg / d_w)";
+  static constexpr const char* fp64_only = "functionals are fp64 only (kstar_fp32)";
+  static constexpr int extra_part_rows = 1;
+  const double *d_Xg, *d_w;
+  int w_stride, G;
+  double threshold;
+  bool has_operands() const { return d_Xg && d_w; }
+  int check(ppbo_ctx* ctx, const ppbo_model*) {
+    PPBO_REQUIRE(ctx, G >= 1 && G <= PPBO_FUNCTIONAL_MAX_G, "G (1 .. PPBO_FUNCTIONAL_MAX_G points per group)");
+    PPBO_REQUIRE(ctx, w_stride == 0 || w_stride == G, "w_stride (0: one weight row for all groups, G: one per group)");
+    PPBO_REQUIRE(ctx, std::isfinite(threshold), "threshold (finite)");
+    return 0;
+  }
+  template <int KID>
+  void kstar(const KstarLaunch& k, int64_t c_beg, int Mc) const {
+    launch_kstar_func<KID>(k, d_Xg + (size_t)c_beg * k.m->D * G, d_w + (size_t)c_beg * w_stride, w_stride, G, Mc);
+  }
+  template <int KID>
+  void score(const TwoSetScore& sc) const {
+    const int D = sc.m->D;
+    if (sc.slab) {
+      // one wavefront per group; as many per workgroup (4, 2, 1) as 48 KB of LDS hold of G (D + 1) doubles each
+      const size_t per_wave = (size_t)G * (D + 1) * sizeof(double);
+      const int wpb = 4 * per_wave <= 49152 ? 4 : (2 * per_wave <= 49152 ? 2 : 1);
+      functional_prior_kernel<KID><<<(sc.Mc + wpb - 1) / wpb, 64 * wpb, wpb * per_wave, sc.s>>>(
+          d_Xg + (size_t)sc.c_beg * D * G, d_w + (size_t)sc.c_beg * w_stride, w_stride, G, D, sc.Mc, sc.p, sc.extra);
+    }
+    functional_score_kernel<<<sc.sblocks, SC_THREADS, 0, sc.s>>>(sc.mu_part, sc.n_split, sc.t_part, sc.slab, sc.ntm, sc.Mc,
+                                                                 sc.extra, threshold, sc.score_kind, sc.c_beg, sc.d_mu,
+                                                                 sc.d_var, sc.d_prob, sc.d_score, sc.bests);
+  }
+};
 int ppbo_predict_functionals(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xg, const double* d_w, int w_stride,
                              int64_t M, int G, double threshold, int score_kind, double* d_mu, double* d_var,
                              double* d_prob, double* d_score, double* h_best_val, int64_t* h_best_idx, void* stream) {
   PPBO_ENTER(ctx);
-  const FuncArgs fa{G, w_stride, threshold};
-  return two_set_passes(ctx, TS_FUNC, model, d_Xg, d_w, nullptr, M, score_kind, d_mu, d_var, d_prob, d_score, h_best_val,
-                        h_best_idx, (hipStream_t)stream, &fa);
+  FunctionalsPred pr{{}, d_Xg, d_w, w_stride, G, threshold};
+  return two_set_passes(ctx, model, pr, M, score_kind, d_mu, d_var, d_prob, d_score, h_best_val, h_best_idx, (hipStream_t)stream);
 }
 
 // Main effects and interactions: the column c_j = P_j F(r_d, r_e) of f with every axis but at most two averaged over the
-// unit box, from the caller's axes (not from model->d_X); the K* launches share the "kstar" profile slot.
+// unit box.  The rows of the call are d_dims / d_t [M, 2]; the column comes from the caller's axes and the table
+// marginal_table_kernel leaves per call, not from model->d_X; kstar_marginal -> quadform -> marginal_score.  Its row
+// splits are those of a FULL chunk whatever M is, so that a row's sums do not depend on the size of the call.  The K*
+// launches share the "kstar" profile slot.
+struct MarginalsPred : TwoSetBase {
+  static constexpr const char* operands = "marginals (d_dims / d_t)";
+  static constexpr const char* fp64_only = "marginals are fp64 only (kstar_fp32)";
+  static constexpr bool full_chunk_splits = true;
+  MargArgs ma;
+  double* tab = nullptr;
+  bool has_operands() const { return ma.d_dims && ma.d_t; }
+  int check(ppbo_ctx* ctx, const ppbo_model* model) {
+    PPBO_REQUIRE(ctx, model->kernel_id == PPBO_KERNEL_SE || model->kernel_id == PPBO_KERNEL_CAMPHOR,
+                 "marginals need a kernel that is a product over coordinates (SE, camphor-copper); RQ and Matern: sample with "
+                 "ppbo_predict_functionals (average_pred)");
+    PPBO_REQUIRE(ctx, ma.effect == PPBO_EFFECT_RAW || ma.effect == PPBO_EFFECT_CENTRED || ma.effect == PPBO_EFFECT_INTERACTION,
+                 "effect");
+    if (int rc = marginal_axes_arg(ctx, &ma)) return rc;
+    const bool six = model->kernel_id == PPBO_KERNEL_CAMPHOR || model->coords.kind == PPBO_COORDS_CAMPHOR;
+    PPBO_REQUIRE(ctx, ma.ax->Dc == (six ? 6 : model->D), "axes->Dc: the model's D (6 for the camphor kernels)");
+    return 0;
+  }
+  int prepare(ppbo_ctx* ctx, const ppbo_model* model, const KernParams& p, int64_t M, Best* bests, int sblocks_max, hipStream_t s) {
+    const int N = model->N;
+    tab = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_MARGINAL, marginal_table_doubles(N, ma.arg.Dc) * sizeof(double));
+    if (!tab) return (int)hipErrorOutOfMemory;
+    // the rows of d_dims are looked at on the device BEFORE anything is launched on the outputs: the first row that breaks
+    // the rules comes back through the host-mapped record.  A stream that is being captured cannot be waited on: there
+    // the look is left out, and such a row gets NaN results (marginal_row)
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    (void)hipStreamIsCapturing(s, &cap);
+    if (cap == hipStreamCaptureStatusNone) {
+      PpboHostRecord chk{};
+      if (int rc = ppbo_host_record(ctx, &chk)) return rc;
+      const int cblocks = (int)std::min<int64_t>((M + 255) / 256, (int64_t)sblocks_max);
+      marginal_check_kernel<<<cblocks, 256, 0, s>>>(ma.d_dims, (long long)M, ma.arg.Dc, ma.effect, bests);
+      PPBO_LAUNCH_CHECK(ctx);
+      argmax_final_kernel<<<1, 256, 0, s>>>(bests, cblocks, nullptr, chk.d_rec, 0, chk.d_flag, chk.epoch);
+      PPBO_LAUNCH_CHECK(ctx);
+      if (int rc = ppbo_host_record_wait(ctx, chk, s)) return rc;
+      const long long bad = (long long)chk.h_rec[1];
+      if (bad >= 0)
+        return ppbo_set_error(ctx, -1,
+                              "invalid argument: d_dims row %lld (axes in -1 .. Dc - 1, two different ones, no first axis of -1 "
+                              "with a second one, two axes for an interaction)", bad);
+    }
+    marginal_table_kernel<<<(N + 255) / 256, 256, 0, s>>>(ma.arg, ma.ax->d_Xu, N, p.sf2, tab);
+    PPBO_LAUNCH_CHECK(ctx);
+    return 0;
+  }
+  template <int KID>
+  void kstar(const KstarLaunch& k, int64_t c_beg, int Mc) const {
+    const int Dc = ma.arg.Dc;
+    kstar_marginal_kernel<<<k.grid(Mc, KS_THREADS), KS_THREADS, (size_t)2 * KS_RJ * Dc * sizeof(double), k.s>>>(
+        ma.ax->d_Xu, k.m->N, Dc, tab, k.m->d_alpha, k.lam_diag(), k.lam_off(), k.mblk(), ma.d_dims + (size_t)c_beg * 2,
+        ma.d_t + (size_t)c_beg * 2, ma.effect, Mc, k.Kt, k.ldk, k.mu_part, k.t_or_null(), k.q_per_split, k.n_q(), k.edge_k0);
+  }
+  template <int KID>
+  void score(const TwoSetScore& sc) const {
+    marginal_score_kernel<<<sc.sblocks, SC_THREADS, 0, sc.s>>>(
+        sc.mu_part, sc.n_split, sc.t_part, sc.slab, sc.ntm, sc.Mc, ma.d_dims + (size_t)sc.c_beg * 2, ma.d_t + (size_t)sc.c_beg * 2,
+        tab, ma.arg.Dc, sc.p.sf2, ma.prod_A, ma.effect, sc.score_kind, sc.c_beg, sc.d_mu, sc.d_var, sc.d_prob, sc.d_score, sc.bests);
+  }
+};
 int ppbo_predict_marginals(ppbo_ctx* ctx, const ppbo_model* model, const ppbo_marginal_axes* axes, const int* d_dims,
                            const double* d_t, int64_t M, int effect, int score_kind, double* d_mu, double* d_var,
                            double* d_prob, double* d_score, double* h_best_val, int64_t* h_best_idx, void* stream) {
   PPBO_ENTER(ctx);
-  MargArgs ma{};
-  ma.ax = axes;
-  ma.d_dims = d_dims;
-  ma.d_t = d_t;
-  ma.effect = effect;
-  return two_set_passes(ctx, TS_MARG, model, d_t, d_t, nullptr, M, score_kind, d_mu, d_var, d_prob, d_score, h_best_val,
-                        h_best_idx, (hipStream_t)stream, nullptr, &ma);
+  MarginalsPred pr{{}, MargArgs{axes, d_dims, d_t, effect, {}, 0.0}};
+  return two_set_passes(ctx, model, pr, M, score_kind, d_mu, d_var, d_prob, d_score, h_best_val, h_best_idx, (hipStream_t)stream);
 }
+
+extern "C" {
 
 // The field pass of a tournament: U [NkU][ldu] = u_b = (Lambda + M'M) k_b for the Mb opponents d_Xb, in the row layout of the
 // model's form (see tournament_kernel).  KB, Y, Z: [N][ldu] each; part_b: the mean partials of the field's own K* launch
@@ -3964,9 +3991,8 @@ static int tournament_passes(ppbo_ctx* ctx, const ppbo_model* model, const doubl
   const int NkU = (N + BK - 1) & ~(BK - 1);            // rows of U: the K extent of a padded chunk workspace
   const int ldu = (Mb + 127) & ~127;                   // whole opponent tiles
   // the split of the field's own K* launch (its mean partials are not read)
-  const int n_split_b = pick_split(Mb, n_q);
-  const int q_per_split_b = (n_q + n_split_b - 1) / n_split_b;
-  const int n_split_b_eff = (n_q + q_per_split_b - 1) / q_per_split_b;
+  const RowSplit rs_b = row_split(Mb, n_q);
+  const int q_per_split_b = rs_b.q_per_split, n_split_b_eff = rs_b.n_split_eff;
   const int fblocks_max = kg ? (int)ppbo_kg_blocks(Mc_max, Mb) : (Mc_max + 255) / 256;
   // every workspace of this entry before the first launch (growing one waits for the device)
   double* U = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_TOURN_U, (size_t)NkU * ldu * sizeof(double));
@@ -4053,9 +4079,8 @@ static int tournament_passes(ppbo_ctx* ctx, const ppbo_model* model, const doubl
     if (Kc) return chunk(c_beg, (int)Mh, Kc, ldk, Nk, (int)(c_beg / chunk_cap));
     // the one-launch path (node form): mu_a / var_a of all rows are enqueued; K* of each chunk by a launch of its own
     const int ldk1 = (Mc_max + 127) & ~127;
-    const int n_split = pick_split(Mc_max, n_q);
-    const int q_per_split = (n_q + n_split - 1) / n_split;
-    const int n_split_eff = (n_q + q_per_split - 1) / q_per_split;
+    const RowSplit rs = row_split(Mc_max, n_q);
+    const int q_per_split = rs.q_per_split, n_split_eff = rs.n_split_eff;
     double* K1 = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_TOURN_K, ((size_t)NkU * ldk1 + (size_t)n_split_eff * Mc_max) * sizeof(double));
     if (!K1) return (int)hipErrorOutOfMemory;
     double* part1 = K1 + (size_t)NkU * ldk1;
@@ -4137,9 +4162,8 @@ int ppbo_search_batch(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc
   const int Mc_max = (int)(M < chunk_cap ? M : chunk_cap);
   const int NkU = (N + BK - 1) & ~(BK - 1);
   const int ldu = 128;                                  // one opponent, a whole opponent tile
-  const int n_split_b = pick_split(1, n_q);
-  const int q_per_split_b = (n_q + n_split_b - 1) / n_split_b;
-  const int n_split_b_eff = (n_q + q_per_split_b - 1) / q_per_split_b;
+  const RowSplit rs_b = row_split(1, n_q);
+  const int q_per_split_b = rs_b.q_per_split, n_split_b_eff = rs_b.n_split_eff;
   const int blocks_max = batch_blocks(Mc_max);
   // the last step only finishes var_q: without d_var_cond nobody reads it
   const int n_steps = d_var_cond ? q : q - 1;
@@ -4191,9 +4215,8 @@ int ppbo_search_batch(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc
   if (!Kr && n_steps > 0) {
     ldk = (Mc_max + 127) & ~127;
     kext = N - kshift;
-    const int n_split = pick_split(Mc_max, n_q);
-    q_per_split = (n_q + n_split - 1) / n_split;
-    n_split_eff = (n_q + q_per_split - 1) / q_per_split;
+    const RowSplit rs = row_split(Mc_max, n_q);
+    q_per_split = rs.q_per_split; n_split_eff = rs.n_split_eff;
     K2 = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_BATCH_K, ((size_t)NkU * ldk + (size_t)2 * n_split_eff * Mc_max) * sizeof(double));
     if (!K2) return (int)hipErrorOutOfMemory;
     part2 = K2 + (size_t)NkU * ldk;
@@ -4304,9 +4327,8 @@ int ppbo_predict_cov(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc,
   double* Kt = ws;
   double* Z = ws + (size_t)N * ld;
   double* Y = ws + (size_t)2 * N * ld;
-  const int n_split = pick_split(M, n_q);
-  const int q_per_split = (n_q + n_split - 1) / n_split;
-  const int n_split_eff = (n_q + q_per_split - 1) / q_per_split;
+  const RowSplit rs = row_split(M, n_q);
+  const int q_per_split = rs.q_per_split, n_split_eff = rs.n_split_eff;
   double* part = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_PART, (size_t)n_split_eff * M * sizeof(double));
   if (!part) return (int)hipErrorOutOfMemory;
   dispatch_kstar(model, d_Xc, M, Kt, ld, part, nullptr, q_per_split, n_split_eff, false, s);
@@ -4488,9 +4510,8 @@ int line_acq_impl(ppbo_ctx* ctx, const ppbo_model* model, const double* d_grid, 
     gridws = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_SEARCH, (size_t)Bc_max * G * D * sizeof(double));
     if (!gridws) return (int)hipErrorOutOfMemory;
   }
-  const int n_split = pick_split(Bc_max * G, n_q);
-  const int q_per_split = (n_q + n_split - 1) / n_split;
-  const int n_split_eff = (n_q + q_per_split - 1) / q_per_split;
+  const RowSplit rs = row_split(Bc_max * G, n_q);
+  const int q_per_split = rs.q_per_split, n_split_eff = rs.n_split_eff;
   const LineCovPlan lcp = line_cov_plan(N, mblk, Bc_max);
   const bool sym = lcp.sym;
   const int cov_splits = lcp.cov_splits;
@@ -4770,9 +4791,8 @@ int ppbo_predict_gradients(ppbo_ctx* ctx, const ppbo_model* model, const double*
     if (edge && Nk != N) PPBO_HIP_CHECK(ctx, hipMemsetAsync(Ke + (size_t)N * ld, 0, (size_t)(Nk - N) * ld * sizeof(double), s));
     lcp = line_cov_plan(N, mblk, Pc_max);
   }
-  const int n_split = pick_split(Pc_max * D, n_q);
-  const int q_per_split = (n_q + n_split - 1) / n_split;
-  const int n_split_eff = (n_q + q_per_split - 1) / q_per_split;
+  const RowSplit rs = row_split(Pc_max * D, n_q);
+  const int q_per_split = rs.q_per_split, n_split_eff = rs.n_split_eff;
   const long long pst = (long long)Pc_max * D * D;
   double* part = (double*)ppbo_workspace(
       ctx, ppbo_ctx::WS_PART,
@@ -4791,7 +4811,7 @@ int ppbo_predict_gradients(ppbo_ctx* ctx, const ppbo_model* model, const double*
           constexpr int KID = decltype(kid)::value;
           {
             PpboProfScope pf(ctx, ppbo_ctx::PF_GRAD_KSTAR, s);
-            launch_kstar_grad<KID>(model, p, xp, Pc, Kt, ld, part, q_per_split, n_split_eff, s);
+            launch_kstar_grad<KID>(KstarLaunch{model, p, Kt, ld, part, nullptr, q_per_split, n_split_eff, false, -1, s}, xp, Pc);
           }
           PPBO_LAUNCH_CHECK(ctx);
           if (want_cov)

@@ -19,6 +19,13 @@ namespace {
 constexpr int TS = 64;
 constexpr double INV_SQRT_4PI = 0.28209479177387814347;
 
+// the DP buckets of this file's kernel templates
+using RffStripLadder = DpLadder<4, 8, 12, 16, 20, 24, 32>;        // rff_project_kernel in strips of NT tiles (D <= 32)
+using RffDeepLadder = DpLadder<48, 64>;                           // rff_project_kernel above them: one tile per workgroup
+using RffMfmaLadder = DpLadder<4, 8, 12, 16, 20, 24, 32, 48, 64>; // rff_score_mfma_kernel, rff_score_multi_kernel
+using RffScoreLadder = DpLadder<4, 6, 8, 10, 12, 16, 20, 24, 32, 48, 64>;   // rff_score_kernel
+constexpr int rff_multi_cg(int DP) { return DP <= 32 ? 4 : 2; }   // rff_score_multi_kernel's column groups per workgroup
+
 [[maybe_unused]] __device__ __forceinline__ void stage_T(const double* __restrict__ X, int n, int D, int r0, double* __restrict__ dstT) {
   for (int e = threadIdx.x; e < TS * D; e += blockDim.x) {
     const int r = e / D, d = e - r * D;
@@ -766,31 +773,22 @@ int ppbo_rff_project(ppbo_ctx* ctx, const double* d_X, int N, int D, const doubl
   dim3 grid((N + TS * nt - 1) / (TS * nt), (F + TS - 1) / TS);
   hipStream_t s = (hipStream_t)stream;
   PpboProfScope pf(ctx, ppbo_ctx::PF_RFF_PROJECT, s);
-#define RP_GO(DPV, NTV)                                                                                            \
-  do {                                                                                                             \
-    if (wide) rff_project_kernel<DPV, NTV, true><<<grid, 512, 0, s>>>(d_X, N, D, d_W, F, d_b, P, d_Phi);           \
-    else rff_project_kernel<DPV, NTV, false><<<grid, 512, 0, s>>>(d_X, N, D, d_W, F, d_b, P, d_Phi);               \
-  } while (0)
-#define RP_LAUNCH(DPV)            \
-  do {                            \
-    if (nt == 4) RP_GO(DPV, 4);   \
-    else if (nt == 2) RP_GO(DPV, 2); \
-    else RP_GO(DPV, 1);           \
-  } while (0)
-  if (D <= 4) RP_LAUNCH(4);
-  else if (D <= 8) RP_LAUNCH(8);
-  else if (D <= 12) RP_LAUNCH(12);
-  else if (D <= 16) RP_LAUNCH(16);
-  else if (D <= 20) RP_LAUNCH(20);
-  else if (D <= 24) RP_LAUNCH(24);
-  else if (D <= 32) RP_LAUNCH(32);
-  else {   // deep panels: one 64-point tile per workgroup (the strip would not leave room for 4 workgroups per CU)
+  // the <DP, NT> instance, with 16-byte stores where the output allows them
+  auto go = [&](auto dp, auto ntv) {
+    constexpr int DP = decltype(dp)::value, NT = decltype(ntv)::value;
+    if (wide) rff_project_kernel<DP, NT, true><<<grid, 512, 0, s>>>(d_X, N, D, d_W, F, d_b, P, d_Phi);
+    else rff_project_kernel<DP, NT, false><<<grid, 512, 0, s>>>(d_X, N, D, d_W, F, d_b, P, d_Phi);
+  };
+  if (D <= 32) {
+    RffStripLadder::dispatch(D, [&](auto dp) {
+      if (nt == 4) go(dp, std::integral_constant<int, 4>{});
+      else if (nt == 2) go(dp, std::integral_constant<int, 2>{});
+      else go(dp, std::integral_constant<int, 1>{});
+    });
+  } else {   // deep panels: one 64-point tile per workgroup (the strip would not leave room for 4 workgroups per CU)
     grid = dim3((N + TS - 1) / TS, (F + TS - 1) / TS);
-    if (D <= 48) RP_GO(48, 1);
-    else RP_GO(64, 1);
+    RffDeepLadder::dispatch(D, [&](auto dp) { go(dp, std::integral_constant<int, 1>{}); });
   }
-#undef RP_LAUNCH
-#undef RP_GO
   PPBO_LAUNCH_CHECK(ctx);
   return 0;
 }
@@ -828,33 +826,15 @@ int ppbo_rff_score(ppbo_ctx* ctx, const double* d_Xc, int64_t M, int D, const do
     PpboProfScope pf(ctx, ppbo_ctx::PF_RFF_SCORE, s);
     if (ctx->rff_score_mfma) {
       dim3 gm((Mc + 255) / 256, n_split);
-#define RM_LAUNCH(DP) \
-  rff_score_mfma_kernel<DP, 4, 2><<<gm, 256, 0, s>>>(xc, Mc, D, d_W, F, d_b, d_omega, make_rff_poly(scale), f_per_split, part)
-      if (D <= 4) RM_LAUNCH(4);
-      else if (D <= 8) RM_LAUNCH(8);
-      else if (D <= 12) RM_LAUNCH(12);
-      else if (D <= 16) RM_LAUNCH(16);
-      else if (D <= 20) RM_LAUNCH(20);
-      else if (D <= 24) RM_LAUNCH(24);
-      else if (D <= 32) RM_LAUNCH(32);
-      else if (D <= 48) RM_LAUNCH(48);
-      else RM_LAUNCH(64);
-#undef RM_LAUNCH
+      RffMfmaLadder::dispatch(D, [&](auto dp) {
+        rff_score_mfma_kernel<decltype(dp)::value, 4, 2><<<gm, 256, 0, s>>>(xc, Mc, D, d_W, F, d_b, d_omega, make_rff_poly(scale),
+                                                                            f_per_split, part);
+      });
     } else {
-#define RS_LAUNCH(DP) \
-  rff_score_kernel<DP><<<grid, RS_THREADS, 0, s>>>(xc, Mc, D, d_W, F, d_b, d_omega, make_rff_poly(scale), f_per_split, part)
-    if (D <= 4) RS_LAUNCH(4);
-    else if (D <= 6) RS_LAUNCH(6);
-    else if (D <= 8) RS_LAUNCH(8);
-    else if (D <= 10) RS_LAUNCH(10);
-    else if (D <= 12) RS_LAUNCH(12);
-    else if (D <= 16) RS_LAUNCH(16);
-    else if (D <= 20) RS_LAUNCH(20);
-    else if (D <= 24) RS_LAUNCH(24);
-    else if (D <= 32) RS_LAUNCH(32);
-    else if (D <= 48) RS_LAUNCH(48);
-    else RS_LAUNCH(64);
-#undef RS_LAUNCH
+      RffScoreLadder::dispatch(D, [&](auto dp) {
+        rff_score_kernel<decltype(dp)::value><<<grid, RS_THREADS, 0, s>>>(xc, Mc, D, d_W, F, d_b, d_omega, make_rff_poly(scale),
+                                                                          f_per_split, part);
+      });
     }
     PPBO_LAUNCH_CHECK(ctx);
     const int sblocks = score_blocks(Mc);
@@ -880,25 +860,12 @@ int ppbo_rff_score_multi(ppbo_ctx* ctx, const double* d_Xc, int64_t M, int D, co
   // of 64 samples; 4 x 4 accumulator tiles per lane)
   const bool one = S <= 16;
   const int mi = (int)M;
-#define RMM_GO(DP, CG, SB)                                                                                         \
-  rff_score_multi_kernel<DP, CG, SB><<<dim3((mi + 64 * CG - 1) / (64 * CG), (S + 16 * SB - 1) / (16 * SB)), 256, 0, s>>>( \
-      d_Xc, mi, D, d_W, F, d_b, d_omegas, S, P, d_score)
-#define RMM_LAUNCH(DP, CG)        \
-  do {                            \
-    if (one) RMM_GO(DP, CG, 1);   \
-    else RMM_GO(DP, CG, 4);       \
-  } while (0)
-  if (D <= 4) RMM_LAUNCH(4, 4);
-  else if (D <= 8) RMM_LAUNCH(8, 4);
-  else if (D <= 12) RMM_LAUNCH(12, 4);
-  else if (D <= 16) RMM_LAUNCH(16, 4);
-  else if (D <= 20) RMM_LAUNCH(20, 4);
-  else if (D <= 24) RMM_LAUNCH(24, 4);
-  else if (D <= 32) RMM_LAUNCH(32, 4);
-  else if (D <= 48) RMM_LAUNCH(48, 2);
-  else RMM_LAUNCH(64, 2);
-#undef RMM_LAUNCH
-#undef RMM_GO
+  RffMfmaLadder::dispatch(D, [&](auto dp) {
+    constexpr int DP = decltype(dp)::value, CG = rff_multi_cg(DP);
+    const int cblocks = (mi + 64 * CG - 1) / (64 * CG);
+    if (one) rff_score_multi_kernel<DP, CG, 1><<<dim3(cblocks, (S + 15) / 16), 256, 0, s>>>(d_Xc, mi, D, d_W, F, d_b, d_omegas, S, P, d_score);
+    else rff_score_multi_kernel<DP, CG, 4><<<dim3(cblocks, (S + 63) / 64), 256, 0, s>>>(d_Xc, mi, D, d_W, F, d_b, d_omegas, S, P, d_score);
+  });
   PPBO_LAUNCH_CHECK(ctx);
   return 0;
 }

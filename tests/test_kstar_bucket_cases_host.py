@@ -1,7 +1,9 @@
 """Host: the case matrix of tests/kstar_bucket_cases.py against the launch ladders of ppbo_amd/csrc/predict.hip, read as
-text.  Every launch_kstar* function is a hand-written `if (m->D <= ...)` chain of *_LAUNCH*(<DP>...) rungs; this test
-collects the DP values of every chain and holds the matrix to them, so that a new rung or a new launcher fails here until
-the matrix (and with it tests/test_gpu_kstar_buckets.py) is extended.  It looks for nothing but these launch macros."""
+text.  The ladders are named once (`using <Name> = DpLadder<...>;`), the limit of kstar_curv_kernel's acceleration twins is
+a named constant, and every launch_kstar* function dispatches through a named ladder (`<Name>::dispatch(`) or, for
+camphor-copper, launches a fixed DP (`std::integral_constant<int, DP>`).  This test reads those declarations and which
+ladder each launcher uses, and holds the matrix to them, so that a new rung or a new launcher fails here until the matrix
+(and with it tests/test_gpu_kstar_buckets.py) is extended."""
 import collections
 import os
 import re
@@ -9,33 +11,46 @@ import re
 import kstar_bucket_cases as kc
 
 SOURCE = os.path.join(os.path.dirname(os.path.abspath(__file__)), os.pardir, "ppbo_amd", "csrc", "predict.hip")
-RUNG = re.compile(r"\b(\w*_LAUNCH\w*)\s*\(\s*(\d+)\b")
-LAUNCHER = re.compile(r"^int\s+(launch_kstar\w*)\s*\(", re.M)
+LADDER = re.compile(r"^using\s+(\w+)\s*=\s*DpLadder<([\d,\s]+)>;", re.M)
+ACC_LIMIT = re.compile(r"^constexpr int KSTAR_CURV_ACC_MAX_DP = (\d+);", re.M)
+LAUNCHER = re.compile(r"^(?:int|void)\s+(launch_kstar\w*)\s*\(", re.M)
+DISPATCH = re.compile(r"\b(\w+)::dispatch\s*\(")
+FIXED = re.compile(r"\bstd::integral_constant<int,\s*(\d+)>")
 
 
 def ladders(text):
-    """{launcher: {macro: sorted DP values}} of every launch_kstar* function in the source text (a macro's definition has
-    a name, not a number, in the place of DP, so only its uses match)."""
+    """{launcher: {chain: sorted DP values}} of every launch_kstar* function in the source text: one chain per named ladder
+    it dispatches through, "fixed" for the DP values it launches without a ladder, and "acc" for the rungs of
+    launch_kstar_curv that have an acceleration twin."""
+    named = {name: sorted(int(n) for n in rungs.split(",")) for name, rungs in LADDER.findall(text)}
+    (acc_limit,) = ACC_LIMIT.findall(text)
     heads = list(LAUNCHER.finditer(text))
     out = {}
     for i, h in enumerate(heads):
         end = text.index("\n}\n", h.end())           # the function's closing brace, in column 0
         assert i + 1 == len(heads) or end < heads[i + 1].start()
-        per = collections.defaultdict(set)
-        for macro, n in RUNG.findall(text[h.end():end]):
-            per[macro].add(int(n))
-        assert per, f"{h.group(1)}: no launch rung found"
-        out[h.group(1)] = {k: sorted(v) for k, v in per.items()}
+        body = text[h.end():end]
+        used = DISPATCH.findall(body)
+        assert used, f"{h.group(1)}: no ladder dispatch found"
+        per = {name: named[name] for name in used}   # (KeyError: a dispatch through a ladder that is not declared)
+        fixed = sorted({int(n) for n in FIXED.findall(body)})
+        if fixed:
+            per["fixed"] = fixed
+        if "KSTAR_CURV_ACC_MAX_DP" in body:
+            per["acc"] = [n for name in used for n in named[name] if n <= int(acc_limit)]
+        out[h.group(1)] = per
     return out
 
 
 def missing(found, cases):
     """The (launcher, chain, rung, D) that no case of the matrix runs: every rung needs a case at D = rung and one at the
-    rung's lower edge, in each macro's own chain and in the launcher's chain of all its rungs."""
+    rung's lower edge, in each ladder's own chain and in the launcher's chain of all its rungs.  (A fixed DP is no bucket
+    of D: it has no edges of its own.)"""
     have = {c.D for c in cases}
     out = []
     for launcher, per in found.items():
-        chains = dict(per, all=sorted(set().union(*per.values())))
+        chains = {k: v for k, v in per.items() if k != "fixed"}
+        chains["all"] = sorted(set().union(*per.values()))
         for name, chain in chains.items():
             for n in chain:
                 out += [(launcher, name, n, D) for D in (n, kc.lower_edge(chain, n)) if D not in have]
@@ -60,9 +75,10 @@ def test_the_ladders_are_the_ones_the_matrix_was_built_for():
         assert rungs <= set(kc.BUCKETS), (launcher, sorted(rungs - set(kc.BUCKETS)))
         if launcher != "launch_kstar_func":
             assert rungs == set(kc.BUCKETS), (launcher, sorted(set(kc.BUCKETS) - rungs))
-    assert found["launch_kstar_func"] == {"KSF_LAUNCH": [8, 20, 32, 48, 64]}
-    assert found["launch_kstar"]["KS_LAUNCH32"] == [6, 20, 64]
-    assert max(found["launch_kstar_curv"]["KSC_LAUNCH"]) == 16          # the ACC twins: D <= 16
+            assert per["KstarLadder"] == list(kc.BUCKETS), launcher
+    assert found["launch_kstar_func"] == {"KstarFuncLadder": [8, 20, 32, 48, 64]}
+    assert found["launch_kstar"]["KstarFp32Ladder"] == [6, 20, 64]
+    assert max(found["launch_kstar_curv"]["acc"]) == 16                 # the ACC twins: D <= 16
 
 
 def test_every_rung_has_a_case_at_both_of_its_edges():
@@ -74,8 +90,17 @@ def test_a_missing_case_or_an_added_rung_is_noticed():
     for drop in (9, 24, 49):                         # a lower edge, an upper edge, kstar_func_kernel's last lower edge
         assert missing(found, [c for c in kc.CASES if c.D != drop])
     more = {k: dict(v) for k, v in found.items()}
-    more["launch_kstar_pair"]["KSP_LAUNCH"] = sorted(more["launch_kstar_pair"]["KSP_LAUNCH"] + [40])
+    more["launch_kstar_pair"]["KstarLadder"] = sorted(more["launch_kstar_pair"]["KstarLadder"] + [40])
     assert {(m[0], m[3]) for m in missing(more, kc.CASES)} == {("launch_kstar_pair", 40), ("launch_kstar_pair", 41)}
+    # the same probe through the source text: a rung 40 in a ladder of the pair launcher's own
+    with open(SOURCE) as fh:
+        text = fh.read()
+    head = LAUNCHER.search(text, text.index("void launch_kstar_pair(")).start()
+    body_end = text.index("\n}\n", head)
+    probe = (text[:head].replace("using KstarFuncLadder", "using ProbeLadder = DpLadder<4, 6, 8, 10, 12, 16, 20, 24, 32, 40, 48, 64>;\n"
+                                 "using KstarFuncLadder", 1)
+             + text[head:body_end].replace("KstarLadder::dispatch", "ProbeLadder::dispatch") + text[body_end:])
+    assert {(m[0], m[3]) for m in missing(ladders(probe), kc.CASES)} == {("launch_kstar_pair", 40), ("launch_kstar_pair", 41)}
 
 
 def test_the_matrix_rule():
