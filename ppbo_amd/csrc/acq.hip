@@ -261,8 +261,7 @@ int launch_acq_grad(const ppbo_model* m, const KernParams& p, const double* pts,
 struct AcqRound {
   const ppbo_model* m = nullptr;
   bool field = false;              // the operator is read: the field pass runs in front of acq_grad_kernel
-  int ldu = 0, NkU = 0, q_per_split = 0, n_split = 0;
-  double *U = nullptr, *KB = nullptr, *Y = nullptr, *Z = nullptr, *part = nullptr;
+  FieldPass fp;
   double* state = nullptr;         // state_doubles doubles of the caller's behind the field's arrays (the ascent's state)
 
   // every workspace before the first launch (growing one waits for the device); without a field pass there is none
@@ -270,30 +269,19 @@ struct AcqRound {
     m = model;
     field = with_field;
     if (!field) return 0;
-    const int N = m->N, n_q = N / (m->m + 1);
-    NkU = (N + 15) & ~15;                    // rows of U: the K extent of a padded chunk workspace
-    ldu = (Mc_max + 127) & ~127;
+    const int n_q = m->N / (m->m + 1);
     // the row split of the field's K* launch from the model alone (pick_split's answer for one column): it decides
     // nothing a column of K* depends on, and so it must not depend on the number of points either
-    const int want = n_q < 64 ? n_q : 64;
-    q_per_split = (n_q + want - 1) / want;
-    n_split = (n_q + q_per_split - 1) / q_per_split;
-    U = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_TOURN_U, (size_t)NkU * ldu * sizeof(double));
-    if (!U) return (int)hipErrorOutOfMemory;
-    const size_t f_y = (size_t)N * ldu;
-    KB = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_TOURN_FIELD,
-                                 (3 * f_y + (size_t)n_split * Mc_max + state_doubles) * sizeof(double));
-    if (!KB) return (int)hipErrorOutOfMemory;
-    Y = KB + f_y; Z = Y + f_y; part = Z + f_y; state = part + (size_t)n_split * Mc_max;
-    return 0;
+    const int want = n_q < 64 ? n_q : 64, q_per_split = (n_q + want - 1) / want;
+    state = fp.prepare(ctx, m, Mc_max, RowSplit{want, q_per_split, (n_q + q_per_split - 1) / q_per_split}, state_doubles);
+    return state ? 0 : (int)hipErrorOutOfMemory;
   }
   int run(ppbo_ctx* ctx, const double* pts, int Mc, int kind, double mustar, const AcqOut& o, hipStream_t s) const {
     AcqField f{};
     if (field) {
       PpboProfScope pf(ctx, ppbo_ctx::PF_ACQ_FIELD, s);
-      if (int rc = tournament_field(ctx, m, pts, Mc, ldu, NkU, KB, Y, Z, U, part, q_per_split, n_split, s, AQ_GEMM_CFG))
-        return rc;
-      f.KB = KB; f.Y = Y; f.U = U; f.ldu = ldu;
+      if (int rc = fp.run(ctx, pts, Mc, s, AQ_GEMM_CFG)) return rc;
+      f.KB = fp.KB; f.Y = fp.Y; f.U = fp.U; f.ldu = fp.ldu;
       f.lam_diag = m->d_lam_diag; f.lam_off = m->d_lam_off;
       f.mblk = m->m + 1; f.n_q = m->N / (m->m + 1); f.edge = m->form == PPBO_FORM_EDGE;
     }

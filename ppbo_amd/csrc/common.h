@@ -103,6 +103,25 @@ struct PpboSpinWait {
   }
 };
 
+// The chunks of a pass over M columns (points, lines), at most `cap` each: `for (const Chunk c : chunks)` walks them
+// in order with the chunk's number, its first column and its size.  Mc_max: the largest (what workspaces are sized for)
+struct Chunk { int64_t ch, beg; int Mc; };
+struct Chunks {
+  int64_t cap, M, n;
+  int Mc_max;
+  explicit Chunks(int64_t M_, int64_t cap_ = 65536)
+      : cap(cap_), M(M_), n((M_ + cap_ - 1) / cap_), Mc_max((int)(M_ < cap_ ? M_ : cap_)) {}
+  Chunk at(int64_t ch) const { return Chunk{ch, ch * cap, (int)((M - ch * cap) < cap ? (M - ch * cap) : cap)}; }
+  struct It {
+    const Chunks* c;
+    int64_t ch;                    // (what a range-for needs)
+    Chunk operator*() const { return c->at(ch); }
+    void operator++() { ++ch; }
+    bool operator!=(const It& o) const { return ch != o.ch; }
+  };
+  It begin() const { return It{this, 0}; }   It end() const { return It{this, n}; }
+};
+
 struct PpboHostRecord {
   double* d_rec;                     // device view of the record (2 doubles)
   unsigned long long* d_flag;        // device view of the flag
@@ -128,12 +147,20 @@ int ppbo_predict_record_publish(ppbo_ctx* ctx, const ppbo_model* model, const do
 // predict.hip, for project.hip: E [N][ld] = the edge-layout rows of the node-layout Kt [N][ld] (edge_apply_kernel), M columns
 int ppbo_edge_apply_async(ppbo_ctx* ctx, const double* Kt, int ld, int M, int N, int mblk, const double* d_lam_off, double* E,
                           hipStream_t s);
-// predict.hip, for acq.hip: the field pass of a tournament, U [NkU][ldu] = (Lambda + M'M) K* for the Mb <= 1024 points d_Xb
-// in the row layout of the model's form, beside K* (KB, node layout) and Y = M K* [N][ldu] each; Z [N][ldu] is scratch,
-// part_b [n_split_b_eff][Mb] the mean partials of its K* launch.  gemm_cfg: GemmArgs.force_cfg of its two GEMMs
-extern "C" int tournament_field(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xb, int Mb, int ldu, int NkU,
-                                double* KB, double* Y, double* Z, double* U, double* part_b, int q_per_split_b,
-                                int n_split_b_eff, hipStream_t s, int gemm_cfg = 0);
+// the row splits of a K* launch (row_split, predict.hip): pick_split's count, the stars per split, the splits that hold a star
+struct RowSplit { int n_split, q_per_split, n_split_eff; };
+// predict.hip, for acq.hip: the field pass of a tournament, U [NkU][ldu] = (Lambda + M'M) K* for the Mb <= Mb_max <= 1024
+// points d_Xb in the row layout of the model's form, beside K* (KB, node layout) and Y = M K* [N][ldu] each; Z [N][ldu] is
+// scratch, part [split.n_split_eff][Mb_max] the mean partials of its K* launch.  prepare(): U, and ONE WS_TOURN_FIELD of KB,
+// Y, Z, head_doubles, part, extra_doubles; returns the caller's extra (NULL: out of memory).  gemm_cfg: GemmArgs.force_cfg
+struct FieldPass {
+  const ppbo_model* model = nullptr;
+  int ldu = 0, NkU = 0;
+  RowSplit split{};
+  double *U = nullptr, *KB = nullptr, *Y = nullptr, *Z = nullptr, *head = nullptr, *part = nullptr;
+  double* prepare(ppbo_ctx* ctx, const ppbo_model* m, int Mb_max, const RowSplit& rs, size_t extra_doubles, size_t head_doubles = 0);
+  int run(ppbo_ctx* ctx, const double* d_Xb, int Mb, hipStream_t s, int gemm_cfg = 0) const;
+};
 
 // kg.hip, for predict.hip: the envelope march behind a chunk's cross product.  ppbo_kg_rows: d_s = sqrt(max(var, 0) +
 // noise_var) and the own line's slope d_self_b = max(var, 0) / d_s for M rows.  ppbo_kg_launch: the knowledge gradient of

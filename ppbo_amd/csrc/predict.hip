@@ -24,6 +24,11 @@
 //   all resident workgroups stream the same G row panel out of L2 while their K* chunk sits in the
 //   Infinity Cache.  PPBO_QF_VARIANT (default 4: 16 wavefronts of 32x32) selects the measured tile shapes, see DESIGN.md.
 // Pass 3 (score_kernel): slab sums -> var, score, per-block argmax; (argmax_final_kernel) -> 1 value.
+// Host drivers: every entry plans its call with the same objects, each on its caller's stack and each requesting its
+//   workspace slots once, before the caller's first launch.  Chunks (common.h) walks the chunks of a call; ScorePlan owns
+//   the padded operator, K* and the partial sums of predict_passes / two_set_passes, LineWorkspace those of the line
+//   entries and the gradients, OwnKstar a K* workspace of an entry's own, FieldPass (common.h) the tournament's field
+//   pass; BestReturn brings the best back through the host-mapped record; PredictRequest names what predict_passes is asked.
 #include <functional>
 #include <optional>
 
@@ -3254,30 +3259,191 @@ int pick_split(int M, int n_q) {
 }
 
 // the row splits of a K* launch over M columns: pick_split's count, the stars per split, the splits that hold a star
-struct RowSplit { int n_split, q_per_split, n_split_eff; };
 RowSplit row_split(int M, int n_q) {
   const int n_split = pick_split(M, n_q);
   const int q_per_split = (n_q + n_split - 1) / n_split;
   return RowSplit{n_split, q_per_split, (n_q + q_per_split - 1) / q_per_split};
 }
 
+// The operands and workspaces of a scoring pass (predict_passes, two_set_passes), sized for the largest chunk.
+// The quadratic form's operands are PADDED so that every tile of its launch takes the unguarded main loop whatever
+// N, the star size and the candidate count are (the reference's default m = 25 gives N = 26 n_q: the guarded loop
+// cost 23 % at N = 2080, profiles/r05_ragged_shapes.txt): K extent Nk = N rounded up to the chunk depth (K* rows
+// [N, Nk) zeroed), G's rows up to a whole row tile (copied into a zero frame when N itself is not one), K*'s row
+// stride up to a whole candidate tile (the surplus columns feed only their own, unread, outputs).
+struct ScorePlan {
+  const ppbo_var_projection* proj = nullptr;   // a projected operator: T carries the padded shape itself
+  bool full_chunk_splits = false;              // row splits picked for a full chunk whatever M is
+  int extra_part_rows = 0;                     // the predictor's own rows [Mc_max] behind the slabs
+  int slab_cols = 0;                           // the pruned search's wider slab rows (0: Mc_max)
+  int ntm = 0, Nk = 0, g_rows = 0, ldk = 0, Mc_max = 0, sblocks_max = 0;
+  const double* Gq = nullptr;
+  RowSplit rs{};
+  double *Kt = nullptr, *part = nullptr;
+  Best *bests = nullptr, *chunk_best = nullptr;
+  int prepare(ppbo_ctx* ctx, const ppbo_model* model, const Chunks& ck, bool want_var, hipStream_t s) {
+    const int N = model->N, n_q = N / (model->m + 1), qf_bm = (quadform_variant(ctx) == 5) ? 256 : 128;
+    // slabs = row tiles of the shipped quadform shape; of the projected operator when there is one
+    ntm = proj ? proj->rows_padded / 128 : (N + qf_bm - 1) / qf_bm;
+    Nk = g_rows = N;
+    if (proj) {                      // ld = N rounded up to the chunk depth
+      Gq = proj->d_T;
+      Nk = proj->ld;
+      g_rows = proj->rows_padded;
+    } else if (want_var) {
+      Gq = padded_G(ctx, model, qf_bm, ck.M >= 2048, &Nk, &g_rows, s);
+      if (!Gq) return (int)hipErrorOutOfMemory;
+      PPBO_LAUNCH_CHECK(ctx);
+    }
+    Mc_max = ck.Mc_max;
+    ldk = (Mc_max + 127) & ~127;
+    rs = row_split(full_chunk_splits ? (int)ck.cap : Mc_max, n_q);
+    if (want_var) {
+      Kt = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_KSTAR, (size_t)Nk * ldk * sizeof(double));
+      if (!Kt) return (int)hipErrorOutOfMemory;
+      if (Nk != N) PPBO_HIP_CHECK(ctx, hipMemsetAsync(Kt + (size_t)N * ldk, 0, (size_t)(Nk - N) * ldk * sizeof(double), s));
+    }
+    // (the compact launch's slabs of a pruned chunk, row stride slab_cols, share the full launch's: one of the two writes them)
+    part = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_PART, ((size_t)(2 * rs.n_split_eff + extra_part_rows) * Mc_max +
+                                                            (size_t)ntm * (slab_cols ? slab_cols : Mc_max)) * sizeof(double));
+    if (!part) return (int)hipErrorOutOfMemory;
+    sblocks_max = score_blocks(Mc_max);
+    bests = (Best*)ppbo_workspace(ctx, ppbo_ctx::WS_SMALL, (size_t)(sblocks_max + ck.n) * sizeof(Best));
+    if (!bests) return (int)hipErrorOutOfMemory;
+    chunk_best = bests + sblocks_max;
+    return 0;
+  }
+  // the partial sums of a chunk of Mc columns: the mean's and the Lambda term's per row split, the contraction's slabs
+  double* mu_part() const { return part; }
+  double* t_part(int Mc) const { return part + (size_t)rs.n_split_eff * Mc; }
+  double* slab(int Mc) const { return part + (size_t)2 * rs.n_split_eff * Mc; }
+  double* extra() const { return part + (size_t)(2 * rs.n_split_eff + ntm) * Mc_max; }
+};
+
+// The workspace of the line entries and ppbo_predict_gradients (cols_max columns in the largest chunk): the row split of
+// their K* launch and, with_operator, the padded operator and Kt [Nk][ld], Y [g_rows][ld] and -- edge form: Y = H E
+// with E the edge-layout K* beside the node-layout one -- Ke [Nk][ld] in one WS_KSTAR, rows [N, Nk) of Kt and Ke zeroed.
+struct LineWorkspace {
+  int ld = 0, Nk = 0, g_rows = 0;
+  RowSplit rs{};
+  const double* Gq = nullptr;
+  double *Kt = nullptr, *Y = nullptr, *Ke = nullptr;
+  // operands of Y = G K* padded to whole tiles / chunks, as in ScorePlan: every tile of that product then takes the
+  // unguarded loop whatever N, the star size and the column count are (m = 25: 4.16 -> 3.6 ms for 512 lines at N = 2080)
+  int prepare(ppbo_ctx* ctx, const ppbo_model* model, int cols_max, bool with_operator, bool worth_padding_G, hipStream_t s) {
+    const int N = model->N;
+    ld = (cols_max + 127) & ~127;
+    rs = row_split(cols_max, N / (model->m + 1));
+    if (!with_operator) return 0;
+    Nk = g_rows = N;
+    Gq = padded_G(ctx, model, 128, worth_padding_G, &Nk, &g_rows, s);
+    if (!Gq) return (int)hipErrorOutOfMemory;
+    PPBO_LAUNCH_CHECK(ctx);
+    const bool edge = model->form == PPBO_FORM_EDGE;
+    double* ws = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_KSTAR, (size_t)((edge ? 2 : 1) * Nk + g_rows) * ld * sizeof(double));
+    if (!ws) return (int)hipErrorOutOfMemory;
+    Kt = ws;
+    Y = ws + (size_t)Nk * ld;
+    Ke = edge ? Y + (size_t)g_rows * ld : nullptr;
+    if (Nk != N) PPBO_HIP_CHECK(ctx, hipMemsetAsync(Kt + (size_t)N * ld, 0, (size_t)(Nk - N) * ld * sizeof(double), s));
+    if (edge && Nk != N) PPBO_HIP_CHECK(ctx, hipMemsetAsync(Ke + (size_t)N * ld, 0, (size_t)(Nk - N) * ld * sizeof(double), s));
+    return 0;
+  }
+};
+
+// The best of a call comes back through the ctx's host-mapped record (written by the last argmax workgroup, flag polled
+// by the host) instead of a device-to-host copy + stream synchronisation.  begin() takes the record when a best is wanted
+// (else chunk() and finish() do nothing); chunk(): the one-workgroup argmax of a chunk, which with ONE chunk writes the
+// record itself; finish(): the record of several chunks, the wait, the copy out ((NaN, -1): no non-NaN score).
+struct BestReturn {
+  PpboHostRecord hr{};
+  bool want = false;
+  int begin(ppbo_ctx* ctx, bool want_best) { return (want = want_best) ? ppbo_host_record(ctx, &hr) : 0; }
+  int chunk(ppbo_ctx* ctx, const Best* blk_bests, int n_blocks, Best* chunk_best, int64_t ch, const Chunks& ck, hipStream_t s) const {
+    if (!want) return 0;
+    argmax_final_kernel<<<1, 256, 0, s>>>(blk_bests, n_blocks, chunk_best + ch, ck.n == 1 ? hr.d_rec : nullptr, 0,
+                                          ck.n == 1 ? hr.d_flag : nullptr, hr.epoch);
+    PPBO_LAUNCH_CHECK(ctx);
+    return 0;
+  }
+  int wait(ppbo_ctx* ctx, hipStream_t s, double* h_best_val, int64_t* h_best_idx) const {
+    if (int rc = ppbo_host_record_wait(ctx, hr, s)) return rc;
+    if (h_best_val) *h_best_val = hr.h_rec[0];
+    if (h_best_idx) *h_best_idx = (int64_t)hr.h_rec[1];
+    return 0;
+  }
+  int finish(ppbo_ctx* ctx, const Best* chunk_best, const Chunks& ck, hipStream_t s, double* h_best_val, int64_t* h_best_idx) const {
+    if (!want) return 0;
+    if (ck.n > 1) {
+      best_record_kernel<<<1, 64, 0, s>>>(chunk_best, (int)ck.n, 0, hr.d_rec, hr.d_flag, hr.epoch);
+      PPBO_LAUNCH_CHECK(ctx);
+    }
+    return wait(ctx, s, h_best_val, h_best_idx);
+  }
+};
+
+// A K* workspace of an entry's own (ppbo_predict_tournament behind the one-launch scoring path, ppbo_search_batch):
+// K [NkU][ldk] in the layout of the model's form and the part_rows (1: mean, 2: mean and Lambda term) x n_split_eff
+// partial sums of its launch, which nobody reads, in one slot; zero_tail: rows [N, NkU) zeroed.
+struct OwnKstar {
+  int ldk = 0;
+  RowSplit rs{};
+  double *K = nullptr, *part = nullptr;
+  int prepare(ppbo_ctx* ctx, int slot, const ppbo_model* model, int NkU, int Mc_max, int part_rows, bool zero_tail, hipStream_t s) {
+    const int N = model->N, n_q = N / (model->m + 1);
+    ldk = (Mc_max + 127) & ~127;
+    rs = row_split(Mc_max, n_q);
+    K = (double*)ppbo_workspace(ctx, slot, ((size_t)NkU * ldk + (size_t)part_rows * rs.n_split_eff * Mc_max) * sizeof(double));
+    if (!K) return (int)hipErrorOutOfMemory;
+    part = K + (size_t)NkU * ldk;
+    if (zero_tail && NkU != N) PPBO_HIP_CHECK(ctx, hipMemsetAsync(K + (size_t)N * ldk, 0, (size_t)(NkU - N) * ldk * sizeof(double), s));
+    return 0;
+  }
+  // K* of the Mc columns xc.  edge_k0 >= 0: the edge layout from that row on, with the Lambda term's sums; else the node layout
+  int form(ppbo_ctx* ctx, const ppbo_model* model, const double* xc, int Mc, hipStream_t s, int edge_k0 = -1) const {
+    PpboProfScope pf(ctx, ppbo_ctx::PF_KSTAR, s);
+    const bool edge = edge_k0 >= 0;
+    bool oom = false;
+    const double* geo = edge ? star_geometry(ctx, model, s, &oom) : nullptr;
+    if (oom) return (int)hipErrorOutOfMemory;
+    dispatch_kstar(model, xc, Mc, K, ldk, part, edge ? part + (size_t)rs.n_split_eff * Mc : nullptr, rs.q_per_split,
+                   rs.n_split_eff, edge, s, edge_k0, geo);
+    PPBO_LAUNCH_CHECK(ctx);
+    return 0;
+  }
+};
+
 }  // namespace
 
 extern "C" {
 
 // the scoring passes of ppbo_predict / ppbo_predict_record: per 65536-candidate chunk kstar -> quadform -> score ->
-// one-workgroup argmax.  Leaves the per-chunk bests in *chunk_best_out (device); with d_record and ONE chunk the
+// one-workgroup argmax.  Leaves the per-chunk bests in chunk_best (device); with d_record and ONE chunk the
 // argmax launch writes the record (and raises the publication flag) itself.
 // after_chunk (ppbo_predict_tournament): called behind the launches of every chunk with the chunk's first row, its size and
 // its K* workspace -- Kt [Nk][ldk] in the layout of the model's form, valid until the next chunk's launches -- and ONCE,
 // with Kt == NULL and (0, M), on the one-launch path, which leaves no K* in memory.  The launches themselves do not change.
 using PredictChunkHook = std::function<int(int64_t c_beg, int64_t Mc, const double* Kt, int ldk, int Nk)>;
-static int predict_passes(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc, int64_t M, int score_kind,
-                          double mustar, double* d_mu, double* d_var, double* d_score, bool want_best,
-                          double* d_record, int64_t record_offset, Best** chunk_best_out, int* n_chunks_out,
-                          hipStream_t s, unsigned long long* publish = nullptr, unsigned long long epoch = 0,
-                          const PredictChunkHook* after_chunk = nullptr, const ppbo_var_projection* proj = nullptr,
-                          PruneReport* report = nullptr) {
+// what a caller asks of the passes (points, score, outputs in this order; by name what else it uses) and what they leave
+struct PredictRequest {
+  const double* d_Xc = nullptr;                // [M][D]
+  int64_t M = 0;
+  int score_kind = PPBO_SCORE_MEAN;
+  double mustar = 0.0;
+  double *d_mu = nullptr, *d_var = nullptr, *d_score = nullptr;   // [M] each, any may be NULL
+  bool want_best = false;
+  double* d_record = nullptr;                  // the caller's record (value, index + record_offset); NULL: chunk bests only
+  int64_t record_offset = 0;
+  unsigned long long *publish = nullptr, epoch = 0;   // the flag raised to `epoch` behind the record
+  const PredictChunkHook* after_chunk = nullptr;
+  const ppbo_var_projection* proj = nullptr;
+  PruneReport* report = nullptr;
+  Best* chunk_best = nullptr;                  // results: [n_chunks] on the device
+  int n_chunks = 0;
+  int predict_passes(ppbo_ctx* ctx, const ppbo_model* model, hipStream_t s);
+};
+int PredictRequest::predict_passes(ppbo_ctx* ctx, const ppbo_model* model, hipStream_t s) {
+  const ppbo_var_projection* proj = this->proj;
   if (int rc = check_model(ctx, model)) return rc;
   PPBO_REQUIRE(ctx, d_Xc != nullptr && M > 0, "candidates");
   // a projected operator (ppbo_var_projection_build): rows == 0 or NULL = none, today's launches.  One with rows must
@@ -3330,53 +3496,26 @@ static int predict_passes(ppbo_ctx* ctx, const ppbo_model* model, const double* 
       argmax_final_kernel<<<1, 256, 0, s>>>(bests, (int)nblk, chunk_best, d_record, (long long)record_offset, publish, epoch);
       PPBO_LAUNCH_CHECK(ctx);
     }
-    *chunk_best_out = chunk_best;
-    *n_chunks_out = 1;
+    this->chunk_best = chunk_best;
+    n_chunks = 1;
     if (after_chunk)
       if (int rc = (*after_chunk)(0, M, nullptr, 0, 0)) return rc;
     return 0;
   }
-  const int64_t chunk_cap = 65536;
-  const int64_t n_chunks = (M + chunk_cap - 1) / chunk_cap;
-  const int qf_bm = (quadform_variant(ctx) == 5) ? 256 : 128;
-  // slabs = row tiles of the shipped quadform shape; of the projected operator when there is one
-  const int ntm = proj ? proj->rows_padded / 128 : (N + qf_bm - 1) / qf_bm;
-  // The quadratic form's operands are PADDED so that every tile of its launch takes the unguarded main loop whatever
-  // N, the star size and the candidate count are (the reference's default m = 25 gives N = 26 n_q: the guarded loop
-  // cost 23 % at N = 2080, profiles/r05_ragged_shapes.txt): K extent Nk = N rounded up to the chunk depth (K* rows
-  // [N, Nk) zeroed), G's rows up to a whole row tile (copied into a zero frame when N itself is not one), K*'s row
-  // stride up to a whole candidate tile (the surplus columns feed only their own, unread, outputs).
-  int Nk = N, g_rows = N;
-  const double* Gq = nullptr;
-  if (proj) {                      // T carries the padded shape itself: ld = N rounded up to the chunk depth
-    Gq = proj->d_T;
-    Nk = proj->ld;
-    g_rows = proj->rows_padded;
-  } else if (want_var) {
-    Gq = padded_G(ctx, model, qf_bm, M >= 2048, &Nk, &g_rows, s);
-    if (!Gq) return (int)hipErrorOutOfMemory;
-    PPBO_LAUNCH_CHECK(ctx);
-  }
-
-  // workspaces sized for the largest chunk
-  const int Mc_max = (int)(M < chunk_cap ? M : chunk_cap);
-  const int ldk = (Mc_max + 127) & ~127;
-  const RowSplit rs = row_split(Mc_max, n_q);
-  const int q_per_split = rs.q_per_split, n_split_eff = rs.n_split_eff;
-  double* Kt = nullptr;
-  if (want_var) {
-    Kt = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_KSTAR, (size_t)Nk * ldk * sizeof(double));
-    if (!Kt) return (int)hipErrorOutOfMemory;
-    if (Nk != N) PPBO_HIP_CHECK(ctx, hipMemsetAsync(Kt + (size_t)N * ldk, 0, (size_t)(Nk - N) * ldk * sizeof(double), s));
-  }
+  const Chunks ck(M);
+  const int Mc_max = ck.Mc_max;
   // the survivor capacity of a pruned chunk: an eighth of the chunk in whole 128-column tiles (PPBO_PRUNE_CAP: tests)
   int n_cap = ((ctx->prune_cap > 0 ? ctx->prune_cap : Mc_max / 8) / 128) * 128;
   if (n_cap < 128) n_cap = 128;
-  // (the compact launch's slabs, row stride n_cap, share the full launch's: one of the two writes them)
-  const size_t part_doubles = (size_t)2 * n_split_eff * Mc_max + (size_t)ntm * ((prune && n_cap > Mc_max) ? n_cap : Mc_max);
-  double* part = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_PART, part_doubles * sizeof(double));
-  if (!part) return (int)hipErrorOutOfMemory;
-  const int sblocks_max = score_blocks(Mc_max);
+  ScorePlan pl;
+  pl.proj = proj;
+  pl.slab_cols = (prune && n_cap > Mc_max) ? n_cap : 0;
+  if (int rc = pl.prepare(ctx, model, ck, want_var, s)) return rc;
+  const int ntm = pl.ntm, Nk = pl.Nk, g_rows = pl.g_rows, ldk = pl.ldk, sblocks_max = pl.sblocks_max;
+  const int q_per_split = pl.rs.q_per_split, n_split_eff = pl.rs.n_split_eff;
+  const double* const Gq = pl.Gq;
+  double* const Kt = pl.Kt;
+  Best *const bests = pl.bests, *const chunk_best = pl.chunk_best;
   // the pruned search's own arrays: u_part [n_split][Mc], s_hi [Mc], sig [n_q], per score workgroup (max s_lo, scale),
   // (threshold, tol), then idx [n_cap] and the plan; the gathered columns Kc [Nk][n_cap]
   double *u_part = nullptr, *s_hi = nullptr, *sig = nullptr, *blk_lo = nullptr, *blk_scale = nullptr, *thr = nullptr, *Kc = nullptr;
@@ -3397,16 +3536,10 @@ static int predict_passes(ppbo_ctx* ctx, const ppbo_model* model, const double* 
     plan = (PrunePlan*)(sidx + n_cap);
     if (report) { report->d_plan = plan; report->d_thr = thr; }
   }
-  Best* bests = (Best*)ppbo_workspace(ctx, ppbo_ctx::WS_SMALL, (size_t)(sblocks_max + n_chunks) * sizeof(Best));
-  if (!bests) return (int)hipErrorOutOfMemory;
-  Best* chunk_best = bests + sblocks_max;
-  for (int64_t ch = 0; ch < n_chunks; ++ch) {
-    const int64_t c_beg = ch * chunk_cap;
-    const int Mc = (int)((M - c_beg) < chunk_cap ? (M - c_beg) : chunk_cap);
-    const double* xc = d_Xc + (size_t)c_beg * model->D;
-    double* mu_part = part;
-    double* t_part = part + (size_t)n_split_eff * Mc;
-    double* slab = part + (size_t)2 * n_split_eff * Mc;
+  for (const Chunk c : ck) {
+    const int Mc = c.Mc;
+    const double* xc = d_Xc + (size_t)c.beg * model->D;
+    double *mu_part = pl.mu_part(), *t_part = pl.t_part(Mc), *slab = pl.slab(Mc);
     {
       PpboProfScope pf(ctx, ppbo_ctx::PF_KSTAR, s);
       bool oom = false;
@@ -3443,32 +3576,32 @@ static int predict_passes(ppbo_ctx* ctx, const ppbo_model* model, const double* 
     }
     std::optional<PpboProfScope> pfs;          // (ends before after_chunk's launches)
     pfs.emplace(ctx, ppbo_ctx::PF_SCORE, s);
-    const bool one = (n_chunks == 1);
+    const bool one = (ck.n == 1);
     if (prune)
       score_plan_kernel<<<sblocks, SC_THREADS, 0, s>>>(mu_part, n_split_eff, t_part, slab, ntm, Mc, sf2, score_kind, mustar,
-                                                       (long long)c_beg, bests, plan, sidx, n_cap);
+                                                       (long long)c.beg, bests, plan, sidx, n_cap);
     else
     score_kernel<<<sblocks, SC_THREADS, 0, s>>>(mu_part, n_split_eff, t_part, want_var ? slab : nullptr, ntm, Mc,
                                                 sf2, score_kind, mustar,
-                                                (long long)c_beg, d_mu ? d_mu + c_beg : nullptr,
-                                                d_var ? d_var + c_beg : nullptr, d_score ? d_score + c_beg : nullptr,
+                                                (long long)c.beg, d_mu ? d_mu + c.beg : nullptr,
+                                                d_var ? d_var + c.beg : nullptr, d_score ? d_score + c.beg : nullptr,
                                                 want_best ? bests : nullptr);
     PPBO_LAUNCH_CHECK(ctx);
     if (want_best) {
-      argmax_final_kernel<<<1, 256, 0, s>>>(bests, sblocks, chunk_best + ch, one ? d_record : nullptr,
+      argmax_final_kernel<<<1, 256, 0, s>>>(bests, sblocks, chunk_best + c.ch, one ? d_record : nullptr,
                                             (long long)record_offset, one ? publish : nullptr, epoch);
       PPBO_LAUNCH_CHECK(ctx);
     }
     pfs.reset();
     if (after_chunk)
-      if (int rc = (*after_chunk)(c_beg, Mc, Kt, ldk, Nk)) return rc;
+      if (int rc = (*after_chunk)(c.beg, Mc, Kt, ldk, Nk)) return rc;
   }
-  if (d_record && n_chunks > 1) {
-    best_record_kernel<<<1, 64, 0, s>>>(chunk_best, (int)n_chunks, (long long)record_offset, d_record, publish, epoch);
+  if (d_record && ck.n > 1) {
+    best_record_kernel<<<1, 64, 0, s>>>(chunk_best, (int)ck.n, (long long)record_offset, d_record, publish, epoch);
     PPBO_LAUNCH_CHECK(ctx);
   }
-  *chunk_best_out = chunk_best;
-  *n_chunks_out = (int)n_chunks;
+  this->chunk_best = chunk_best;
+  n_chunks = (int)ck.n;
   return 0;
 }
 
@@ -3483,23 +3616,15 @@ int ppbo_predict_p(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc, i
                    int64_t* h_best_idx, void* stream, const ppbo_var_projection* proj) {
   PPBO_ENTER(ctx);
   hipStream_t s = (hipStream_t)stream;
-  Best* chunk_best = nullptr;
-  int n_chunks = 0;
-  const bool want_best = h_best_val || h_best_idx;
-  if (!want_best)
-    return predict_passes(ctx, model, d_Xc, M, score_kind, mustar, d_mu, d_var, d_score, false, nullptr, 0,
-                          &chunk_best, &n_chunks, s, nullptr, 0, nullptr, proj);
-  // the best comes back through the ctx's host-mapped record (written by the last score workgroup, flag polled by the
-  // host) instead of a device-to-host copy + stream synchronisation
-  PpboHostRecord hr;
-  if (int rc = ppbo_host_record(ctx, &hr)) return rc;
-  if (int rc = predict_passes(ctx, model, d_Xc, M, score_kind, mustar, d_mu, d_var, d_score, true, hr.d_rec, 0,
-                              &chunk_best, &n_chunks, s, hr.d_flag, hr.epoch, nullptr, proj))
-    return rc;
-  if (int rc = ppbo_host_record_wait(ctx, hr, s)) return rc;
-  if (h_best_val) *h_best_val = hr.h_rec[0];      // (NaN, -1) when no candidate has a non-NaN score
-  if (h_best_idx) *h_best_idx = (int64_t)hr.h_rec[1];
-  return 0;
+  PredictRequest rq{d_Xc, M, score_kind, mustar, d_mu, d_var, d_score};
+  rq.proj = proj;
+  rq.want_best = h_best_val || h_best_idx;
+  // predict_passes writes the record itself: the ctx's when a best is wanted, taken before its refusals (else none)
+  BestReturn br;
+  if (int rc = br.begin(ctx, rq.want_best)) return rc;
+  rq.d_record = br.hr.d_rec; rq.publish = br.hr.d_flag; rq.epoch = br.hr.epoch;
+  if (int rc = rq.predict_passes(ctx, model, s)) return rc;
+  return rq.want_best ? br.wait(ctx, s, h_best_val, h_best_idx) : 0;
 }
 
 int ppbo_predict_record(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc, int64_t M, int score_kind,
@@ -3512,10 +3637,7 @@ int ppbo_predict_record_p(ppbo_ctx* ctx, const ppbo_model* model, const double* 
                           const ppbo_var_projection* proj) {
   PPBO_ENTER(ctx);
   PPBO_REQUIRE(ctx, d_record != nullptr, "d_record");
-  Best* chunk_best = nullptr;
-  int n_chunks = 0;
-  return predict_passes(ctx, model, d_Xc, M, score_kind, mustar, nullptr, nullptr, nullptr, true, d_record,
-                        index_offset, &chunk_best, &n_chunks, (hipStream_t)stream, nullptr, 0, nullptr, proj);
+  return ppbo_predict_record_publish(ctx, model, d_Xc, M, score_kind, mustar, index_offset, d_record, nullptr, 0, (hipStream_t)stream, proj);
 }
 
 int ppbo_predict_prune_report(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc, int64_t M, int score_kind,
@@ -3523,15 +3645,14 @@ int ppbo_predict_prune_report(ppbo_ctx* ctx, const ppbo_model* model, const doub
                               double* h_threshold, int* h_n_surv, int* h_pruned, void* stream) {
   PPBO_ENTER(ctx);
   hipStream_t s = (hipStream_t)stream;
-  Best* chunk_best = nullptr;
-  int n_chunks = 0;
   PruneReport rep;
   rep.d_u2 = d_u2; rep.d_s_lo = d_s_lo; rep.d_s_hi = d_s_hi;
   PpboHostRecord hr;
   if (int rc = ppbo_host_record(ctx, &hr)) return rc;
-  if (int rc = predict_passes(ctx, model, d_Xc, M, score_kind, mustar, nullptr, nullptr, nullptr, true, hr.d_rec, 0,
-                              &chunk_best, &n_chunks, s, hr.d_flag, hr.epoch, nullptr, proj, &rep))
-    return rc;
+  PredictRequest rq{d_Xc, M, score_kind, mustar};
+  rq.proj = proj; rq.report = &rep;
+  rq.want_best = true; rq.d_record = hr.d_rec; rq.publish = hr.d_flag; rq.epoch = hr.epoch;
+  if (int rc = rq.predict_passes(ctx, model, s)) return rc;
   if (int rc = ppbo_host_record_wait(ctx, hr, s)) return rc;
   PrunePlan pl{0, 0};
   double thr[2] = {0.0, 0.0};
@@ -3623,60 +3744,33 @@ static int two_set_passes(ppbo_ctx* ctx, const ppbo_model* model, Pred& pr, int6
   const int N = model->N, mblk = model->m + 1, n_q = N / mblk;
   const int edge_k0 = (want_var && model->form == PPBO_FORM_EDGE) ? ppbo_edge_k0(n_q) : -1;
   const KernParams p = make_kern_params(model->kernel_id, model->theta);
-  const int64_t chunk_cap = 65536;
-  const int64_t n_chunks = (M + chunk_cap - 1) / chunk_cap;
-  const int qf_bm = (quadform_variant(ctx) == 5) ? 256 : 128;
-  const int ntm = (N + qf_bm - 1) / qf_bm;
-  int Nk = N, g_rows = N;
-  const double* Gq = nullptr;
-  if (want_var) {
-    Gq = padded_G(ctx, model, qf_bm, M >= 2048, &Nk, &g_rows, s);
-    if (!Gq) return (int)hipErrorOutOfMemory;
-    PPBO_LAUNCH_CHECK(ctx);
-  }
-  const int Mc_max = (int)(M < chunk_cap ? M : chunk_cap);
-  const int ldk = (Mc_max + 127) & ~127;
-  const RowSplit rs = row_split(Pred::full_chunk_splits ? (int)chunk_cap : Mc_max, n_q);
-  const int q_per_split = rs.q_per_split, n_split_eff = rs.n_split_eff;
-  double* Kt = nullptr;
-  if (want_var) {
-    Kt = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_KSTAR, (size_t)Nk * ldk * sizeof(double));
-    if (!Kt) return (int)hipErrorOutOfMemory;
-    if (Nk != N) PPBO_HIP_CHECK(ctx, hipMemsetAsync(Kt + (size_t)N * ldk, 0, (size_t)(Nk - N) * ldk * sizeof(double), s));
-  }
-  double* part = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_PART, (size_t)(2 * n_split_eff + ntm + Pred::extra_part_rows) * Mc_max * sizeof(double));
-  if (!part) return (int)hipErrorOutOfMemory;
-  const int sblocks_max = score_blocks(Mc_max);
-  Best* bests = (Best*)ppbo_workspace(ctx, ppbo_ctx::WS_SMALL, (size_t)(sblocks_max + n_chunks) * sizeof(Best));
-  if (!bests) return (int)hipErrorOutOfMemory;
-  Best* chunk_best = bests + sblocks_max;
-  if (int rc = pr.prepare(ctx, model, p, M, bests, sblocks_max, s)) return rc;
-  PpboHostRecord hr{};             // (behind the preparation, which may have used the ctx's record for a check of its own)
-  if (want_best)
-    if (int rc = ppbo_host_record(ctx, &hr)) return rc;
-  for (int64_t ch = 0; ch < n_chunks; ++ch) {
-    const int64_t c_beg = ch * chunk_cap;
-    const int Mc = (int)((M - c_beg) < chunk_cap ? (M - c_beg) : chunk_cap);
-    double* mu_part = part;
-    double* t_part = part + (size_t)n_split_eff * Mc;
-    double* slab = part + (size_t)2 * n_split_eff * Mc;
+  const Chunks ck(M);
+  ScorePlan pl;
+  pl.full_chunk_splits = Pred::full_chunk_splits;
+  pl.extra_part_rows = Pred::extra_part_rows;
+  if (int rc = pl.prepare(ctx, model, ck, want_var, s)) return rc;
+  if (int rc = pr.prepare(ctx, model, p, M, pl.bests, pl.sblocks_max, s)) return rc;
+  BestReturn br;                   // (behind the preparation, which may have used the ctx's record for a check of its own)
+  if (int rc = br.begin(ctx, want_best)) return rc;
+  for (const Chunk c : ck) {
+    const int Mc = c.Mc;
+    double *mu_part = pl.mu_part(), *t_part = pl.t_part(Mc), *slab = pl.slab(Mc);
     const int sblocks = score_blocks(Mc);
-    const bool one = (n_chunks == 1);
-    const KstarLaunch k{model, p, Kt, ldk, mu_part, t_part, q_per_split, n_split_eff, want_var, edge_k0, s};
-    const TwoSetScore sc{model, p, mu_part, t_part, want_var ? slab : nullptr, part + (size_t)(2 * n_split_eff + ntm) * Mc_max,
-                         n_split_eff, ntm, Mc, score_kind, sblocks, (long long)c_beg, d_mu ? d_mu + c_beg : nullptr,
-                         d_var ? d_var + c_beg : nullptr, d_prob ? d_prob + c_beg : nullptr,
-                         d_score ? d_score + c_beg : nullptr, want_best ? bests : nullptr, s};
+    const KstarLaunch k{model, p, pl.Kt, pl.ldk, mu_part, t_part, pl.rs.q_per_split, pl.rs.n_split_eff, want_var, edge_k0, s};
+    const TwoSetScore sc{model, p, mu_part, t_part, want_var ? slab : nullptr, pl.extra(),
+                         pl.rs.n_split_eff, pl.ntm, Mc, score_kind, sblocks, (long long)c.beg, d_mu ? d_mu + c.beg : nullptr,
+                         d_var ? d_var + c.beg : nullptr, d_prob ? d_prob + c.beg : nullptr,
+                         d_score ? d_score + c.beg : nullptr, want_best ? pl.bests : nullptr, s};
     if (int rc = ppbo_kernel_dispatch(ctx, model->kernel_id, [&](auto kid) {
           constexpr int KID = decltype(kid)::value;
           {
             PpboProfScope pf(ctx, ppbo_ctx::PF_KSTAR, s);
-            pr.template kstar<KID>(k, c_beg, Mc);
+            pr.template kstar<KID>(k, c.beg, Mc);
           }
           PPBO_LAUNCH_CHECK(ctx);
           if (want_var) {
             PpboProfScope pf(ctx, ppbo_ctx::PF_QUADFORM, s);
-            if (int rc2 = dispatch_quadform(ctx, Gq, Nk, g_rows, N, Kt, ldk, Mc, mblk, slab, edge_k0, s)) return rc2;
+            if (int rc2 = dispatch_quadform(ctx, pl.Gq, pl.Nk, pl.g_rows, N, pl.Kt, pl.ldk, Mc, mblk, slab, edge_k0, s)) return rc2;
           }
           PpboProfScope pfs(ctx, ppbo_ctx::PF_SCORE, s);
           pr.template score<KID>(sc);
@@ -3684,21 +3778,9 @@ static int two_set_passes(ppbo_ctx* ctx, const ppbo_model* model, Pred& pr, int6
           return 0;
         }))
       return rc;
-    if (want_best) {
-      argmax_final_kernel<<<1, 256, 0, s>>>(bests, sblocks, chunk_best + ch, one ? hr.d_rec : nullptr, 0,
-                                            one ? hr.d_flag : nullptr, hr.epoch);
-      PPBO_LAUNCH_CHECK(ctx);
-    }
+    if (int rc = br.chunk(ctx, pl.bests, sblocks, pl.chunk_best, c.ch, ck, s)) return rc;
   }
-  if (!want_best) return 0;
-  if (n_chunks > 1) {
-    best_record_kernel<<<1, 64, 0, s>>>(chunk_best, (int)n_chunks, 0, hr.d_rec, hr.d_flag, hr.epoch);
-    PPBO_LAUNCH_CHECK(ctx);
-  }
-  if (int rc = ppbo_host_record_wait(ctx, hr, s)) return rc;
-  if (h_best_val) *h_best_val = hr.h_rec[0];      // (NaN, -1) when no column has a non-NaN score
-  if (h_best_idx) *h_best_idx = (int64_t)hr.h_rec[1];
-  return 0;
+  return br.finish(ctx, pl.chunk_best, ck, s, h_best_val, h_best_idx);
 }
 
 // Duels: the sides (a, b) of a duel, [M, D] each; kstar_pair -> quadform -> pair_score
@@ -3917,15 +3999,30 @@ extern "C" {
 
 // The field pass of a tournament: U [NkU][ldu] = u_b = (Lambda + M'M) k_b for the Mb opponents d_Xb, in the row layout of the
 // model's form (see tournament_kernel).  KB, Y, Z: [N][ldu] each; part_b: the mean partials of the field's own K* launch
-// (not read).  Touches no workspace of predict_passes.  ppbo_search_batch runs it per pick with Mb = 1.  Declared in
-// common.h for acq.hip, which pins the tile configuration of the two GEMMs (gemm_cfg = GemmArgs.force_cfg; 0: by size).
-int tournament_field(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xb, int Mb, int ldu, int NkU, double* KB,
-                     double* Y, double* Z, double* U, double* part_b, int q_per_split_b, int n_split_b_eff,
-                     hipStream_t s, int gemm_cfg) {
+// (not read).  Touches no workspace of predict_passes.  ppbo_search_batch runs it per pick with Mb = 1.  FieldPass is
+// declared in common.h for acq.hip, which pins the tile configuration of the two GEMMs (gemm_cfg = GemmArgs.force_cfg).
+double* FieldPass::prepare(ppbo_ctx* ctx, const ppbo_model* m, int Mb_max, const RowSplit& rs, size_t extra_doubles,
+                           size_t head_doubles) {
+  model = m;
+  split = rs;
+  const int N = m->N;
+  NkU = (N + BK - 1) & ~(BK - 1);            // rows of U: the K extent of a padded chunk workspace
+  ldu = (Mb_max + 127) & ~127;               // whole opponent tiles
+  // every workspace before the first launch (growing one waits for the device)
+  U = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_TOURN_U, (size_t)NkU * ldu * sizeof(double));
+  if (!U) return nullptr;
+  const size_t f_y = (size_t)N * ldu, f_part = 3 * f_y + head_doubles, f_extra = f_part + (size_t)rs.n_split_eff * Mb_max;
+  KB = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_TOURN_FIELD, (f_extra + extra_doubles) * sizeof(double));
+  if (!KB) return nullptr;
+  Y = KB + f_y; Z = Y + f_y; head = Z + f_y; part = KB + f_part;
+  return KB + f_extra;
+}
+
+int FieldPass::run(ppbo_ctx* ctx, const double* d_Xb, int Mb, hipStream_t s, int gemm_cfg) const {
   const int N = model->N, mblk = model->m + 1, n_q = N / mblk;
   const bool edge = model->form == PPBO_FORM_EDGE;
   PPBO_HIP_CHECK(ctx, hipMemsetAsync(U, 0, (size_t)NkU * ldu * sizeof(double), s));
-  dispatch_kstar(model, d_Xb, Mb, KB, ldu, part_b, nullptr, q_per_split_b, n_split_b_eff, false, s);
+  dispatch_kstar(model, d_Xb, Mb, KB, ldu, part, nullptr, split.q_per_split, split.n_split_eff, false, s);
   PPBO_LAUNCH_CHECK(ctx);
   GemmArgs y{};
   y.A = model->d_G; y.lda = N; y.B = KB; y.ldb = ldu; y.C = Y; y.ldc = ldu;
@@ -3981,53 +4078,40 @@ static int tournament_passes(ppbo_ctx* ctx, const ppbo_model* model, const doubl
   const int kshift = edge ? ppbo_edge_k0(n_q) : 0;
   const KernParams p = make_kern_params(model->kernel_id, model->theta);
   const double two_sigma2 = 2.0 * model->theta[0] * model->theta[0];
-  const int64_t chunk_cap = 65536;
-  const int64_t n_chunks = (Ma + chunk_cap - 1) / chunk_cap;
-  const int Mc_max = (int)(Ma < chunk_cap ? Ma : chunk_cap);
+  const Chunks ck(Ma);
+  const int Mc_max = ck.Mc_max;
   // camphor-copper always takes the small tile: its sin(pi |dx|) per element and coordinate needs more registers than
   // the 128 a lane of the 16-wavefront shape has (the compiler spilled 116 bytes per lane there)
   const bool small = Mb <= 2 * TQ_SMALL::BN || model->kernel_id == PPBO_KERNEL_CAMPHOR;
   const int ntb = small ? (Mb + TQ_SMALL::BN - 1) / TQ_SMALL::BN : (Mb + TQ_BIG::BN - 1) / TQ_BIG::BN;
-  const int NkU = (N + BK - 1) & ~(BK - 1);            // rows of U: the K extent of a padded chunk workspace
   const int ldu = (Mb + 127) & ~127;                   // whole opponent tiles
-  // the split of the field's own K* launch (its mean partials are not read)
-  const RowSplit rs_b = row_split(Mb, n_q);
-  const int q_per_split_b = rs_b.q_per_split, n_split_b_eff = rs_b.n_split_eff;
   const int fblocks_max = kg ? (int)ppbo_kg_blocks(Mc_max, Mb) : (Mc_max + 255) / 256;
-  // every workspace of this entry before the first launch (growing one waits for the device)
-  double* U = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_TOURN_U, (size_t)NkU * ldu * sizeof(double));
-  if (!U) return (int)hipErrorOutOfMemory;
-  const size_t f_kb = 0, f_y = f_kb + (size_t)N * ldu, f_z = f_y + (size_t)N * ldu, f_mub = f_z + (size_t)N * ldu,
-               f_varb = f_mub + ldu, f_part = f_varb + ldu, f_slab = f_part + (size_t)n_split_b_eff * Mb,
-               f_mua = f_slab + (size_t)2 * ntb * Mc_max, f_bests = f_mua + (size_t)(d_mu_a ? 0 : Ma) + (size_t)(d_var_a ? 0 : Ma),
-               f_kg = f_bests + (size_t)2 * (fblocks_max + n_chunks),   // (a Best is 16 bytes)
-               // the knowledge gradient's own: the chunk's covariances [Mc][Mb], s_i and the slope of the own line [Mc] each
-               f_end = f_kg + (kg ? (size_t)Mc_max * Mb + (size_t)2 * Mc_max : 0);
-  double* fw = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_TOURN_FIELD, f_end * sizeof(double));
+  // behind the field's arrays (mu_b, var_b [ldu] each in front of its partials): slabs, mu_a / var_a where the caller has
+  // none, the bests (a Best is 16 bytes), the knowledge gradient's chunk covariances [Mc][Mb], s_i and own slopes [Mc] each
+  const size_t f_mua = (size_t)2 * ntb * Mc_max, f_bests = f_mua + (size_t)(d_mu_a ? 0 : Ma) + (size_t)(d_var_a ? 0 : Ma),
+               f_kg = f_bests + (size_t)2 * (fblocks_max + ck.n), f_end = f_kg + (kg ? (size_t)Mc_max * Mb + (size_t)2 * Mc_max : 0);
+  FieldPass field;                 // (the split of the field's own K* launch, whose mean partials are not read)
+  double* fw = field.prepare(ctx, model, Mb, row_split(Mb, n_q), f_end, (size_t)2 * ldu);
   if (!fw) return (int)hipErrorOutOfMemory;
   double *kg_cov = fw + f_kg, *kg_s = kg_cov + (size_t)Mc_max * Mb, *kg_self_b = kg_s + Mc_max;
-  double *KB = fw + f_kb, *Y = fw + f_y, *Z = fw + f_z, *mu_b = fw + f_mub, *var_b = fw + f_varb, *part_b = fw + f_part;
-  double *slab_sum = fw + f_slab, *slab_min = slab_sum + (size_t)ntb * Mc_max;
+  double *mu_b = field.head, *var_b = mu_b + ldu;
+  double *slab_sum = fw, *slab_min = slab_sum + (size_t)ntb * Mc_max;
   double* mu_a = d_mu_a ? d_mu_a : fw + f_mua;
   double* var_a = d_var_a ? d_var_a : fw + f_mua + (d_mu_a ? 0 : Ma);
   Best* bests = reinterpret_cast<Best*>(fw + f_bests);
   Best* chunk_best = bests + fblocks_max;
-  PpboHostRecord hr{};
-  if (want_best)
-    if (int rc = ppbo_host_record(ctx, &hr)) return rc;
-  Best* cb_unused = nullptr;
-  int nc_unused = 0;
+  BestReturn br;
+  if (int rc = br.begin(ctx, want_best)) return rc;
 
   // ---- the field, once per call
   // mu_b, var_b: exactly ppbo_predict's launches on d_Xb
-  if (int rc = predict_passes(ctx, model, d_Xb, Mb, PPBO_SCORE_MEAN, 0.0, mu_b, var_b, nullptr, false, nullptr, 0, &cb_unused,
-                              &nc_unused, s))
-    return rc;
+  PredictRequest rq_b{d_Xb, Mb, PPBO_SCORE_MEAN, 0.0, mu_b, var_b};
+  if (int rc = rq_b.predict_passes(ctx, model, s)) return rc;
   if (d_mu_b) PPBO_HIP_CHECK(ctx, hipMemcpyAsync(d_mu_b, mu_b, (size_t)Mb * sizeof(double), hipMemcpyDeviceToDevice, s));
   if (d_var_b) PPBO_HIP_CHECK(ctx, hipMemcpyAsync(d_var_b, var_b, (size_t)Mb * sizeof(double), hipMemcpyDeviceToDevice, s));
   {
     PpboProfScope pf(ctx, ppbo_ctx::PF_TOURNAMENT_FIELD, s);
-    if (int rc = tournament_field(ctx, model, d_Xb, Mb, ldu, NkU, KB, Y, Z, U, part_b, q_per_split_b, n_split_b_eff, s)) return rc;
+    if (int rc = field.run(ctx, d_Xb, Mb, s)) return rc;
   }
 
   // ---- the candidates: per chunk behind ppbo_predict's own launches
@@ -4040,7 +4124,7 @@ static int tournament_passes(ppbo_ctx* ctx, const ppbo_model* model, const doubl
       if (int rc = ppbo_kernel_dispatch(ctx, model->kernel_id, [&](auto kid) {
             constexpr int KID = decltype(kid)::value;
             const double* Ks = Kc + (size_t)kshift * ldk;
-            const double* Us = U + (size_t)kshift * ldu;
+            const double* Us = field.U + (size_t)kshift * ldu;
             double* cov = kg ? kg_cov : (d_cov ? d_cov + (size_t)c_beg * Mb : nullptr);
             double* prob = d_prob ? d_prob + (size_t)c_beg * Mb : nullptr;
             if (small)
@@ -4067,48 +4151,23 @@ static int tournament_passes(ppbo_ctx* ctx, const ppbo_model* model, const doubl
                                                        d_score ? d_score + c_beg : nullptr, want_best ? bests : nullptr);
       PPBO_LAUNCH_CHECK(ctx);
     }
-    if (want_best) {
-      const bool one = (n_chunks == 1);
-      argmax_final_kernel<<<1, 256, 0, s>>>(bests, fblocks, chunk_best + ch, one ? hr.d_rec : nullptr, 0,
-                                            one ? hr.d_flag : nullptr, hr.epoch);
-      PPBO_LAUNCH_CHECK(ctx);
-    }
-    return 0;
+    return br.chunk(ctx, bests, fblocks, chunk_best, ch, ck, s);
   };
   const PredictChunkHook hook = [&](int64_t c_beg, int64_t Mh, const double* Kc, int ldk, int Nk) -> int {
-    if (Kc) return chunk(c_beg, (int)Mh, Kc, ldk, Nk, (int)(c_beg / chunk_cap));
+    if (Kc) return chunk(c_beg, (int)Mh, Kc, ldk, Nk, (int)(c_beg / ck.cap));
     // the one-launch path (node form): mu_a / var_a of all rows are enqueued; K* of each chunk by a launch of its own
-    const int ldk1 = (Mc_max + 127) & ~127;
-    const RowSplit rs = row_split(Mc_max, n_q);
-    const int q_per_split = rs.q_per_split, n_split_eff = rs.n_split_eff;
-    double* K1 = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_TOURN_K, ((size_t)NkU * ldk1 + (size_t)n_split_eff * Mc_max) * sizeof(double));
-    if (!K1) return (int)hipErrorOutOfMemory;
-    double* part1 = K1 + (size_t)NkU * ldk1;
-    if (NkU != N) PPBO_HIP_CHECK(ctx, hipMemsetAsync(K1 + (size_t)N * ldk1, 0, (size_t)(NkU - N) * ldk1 * sizeof(double), s));
-    for (int64_t ch = 0; ch < n_chunks; ++ch) {
-      const int64_t cb = ch * chunk_cap;
-      const int Mc = (int)((Ma - cb) < chunk_cap ? (Ma - cb) : chunk_cap);
-      {
-        PpboProfScope pf(ctx, ppbo_ctx::PF_KSTAR, s);
-        dispatch_kstar(model, d_Xa + (size_t)cb * D, Mc, K1, ldk1, part1, nullptr, q_per_split, n_split_eff, false, s);
-      }
-      PPBO_LAUNCH_CHECK(ctx);
-      if (int rc = chunk(cb, Mc, K1, ldk1, NkU, (int)ch)) return rc;
+    OwnKstar k1;
+    if (int rc = k1.prepare(ctx, ppbo_ctx::WS_TOURN_K, model, field.NkU, Mc_max, 1, true, s)) return rc;
+    for (const Chunk c : ck) {
+      if (int rc = k1.form(ctx, model, d_Xa + (size_t)c.beg * D, c.Mc, s)) return rc;
+      if (int rc = chunk(c.beg, c.Mc, k1.K, k1.ldk, field.NkU, (int)c.ch)) return rc;
     }
     return 0;
   };
-  if (int rc = predict_passes(ctx, model, d_Xa, Ma, PPBO_SCORE_MEAN, 0.0, mu_a, var_a, nullptr, false, nullptr, 0, &cb_unused,
-                              &nc_unused, s, nullptr, 0, &hook))
-    return rc;
-  if (!want_best) return 0;
-  if (n_chunks > 1) {
-    best_record_kernel<<<1, 64, 0, s>>>(chunk_best, (int)n_chunks, 0, hr.d_rec, hr.d_flag, hr.epoch);
-    PPBO_LAUNCH_CHECK(ctx);
-  }
-  if (int rc = ppbo_host_record_wait(ctx, hr, s)) return rc;
-  if (h_best_val) *h_best_val = hr.h_rec[0];      // (NaN, -1) when no candidate has a non-NaN score
-  if (h_best_idx) *h_best_idx = (int64_t)hr.h_rec[1];
-  return 0;
+  PredictRequest rq_a{d_Xa, Ma, PPBO_SCORE_MEAN, 0.0, mu_a, var_a};
+  rq_a.after_chunk = &hook;
+  if (int rc = rq_a.predict_passes(ctx, model, s)) return rc;
+  return br.finish(ctx, chunk_best, ck, s, h_best_val, h_best_idx);
 }
 
 int ppbo_predict_tournament(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xa, int64_t Ma, const double* d_Xb, int Mb,
@@ -4157,25 +4216,19 @@ int ppbo_search_batch(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc
   const bool edge = model->form == PPBO_FORM_EDGE;
   const int kshift = edge ? ppbo_edge_k0(n_q) : 0;
   const KernParams p = make_kern_params(model->kernel_id, model->theta);
-  const int64_t chunk_cap = 65536;
-  const int64_t n_chunks = (M + chunk_cap - 1) / chunk_cap;
-  const int Mc_max = (int)(M < chunk_cap ? M : chunk_cap);
-  const int NkU = (N + BK - 1) & ~(BK - 1);
-  const int ldu = 128;                                  // one opponent, a whole opponent tile
-  const RowSplit rs_b = row_split(1, n_q);
-  const int q_per_split_b = rs_b.q_per_split, n_split_b_eff = rs_b.n_split_eff;
+  const Chunks ck(M);
+  const int Mc_max = ck.Mc_max;
   const int blocks_max = batch_blocks(Mc_max);
   // the last step only finishes var_q: without d_var_cond nobody reads it
   const int n_steps = d_var_cond ? q : q - 1;
-  // every workspace of this entry before the first launch (growing one waits for the device)
-  double* U = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_TOURN_U, (size_t)NkU * ldu * sizeof(double));
-  if (!U) return (int)hipErrorOutOfMemory;
-  const size_t f_y = (size_t)N * ldu, f_z = 2 * f_y, f_part = 3 * f_y, f_end = f_part + (size_t)n_split_b_eff;
-  double* fw = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_TOURN_FIELD, f_end * sizeof(double));
-  if (!fw) return (int)hipErrorOutOfMemory;
-  double *KB = fw, *Y = fw + f_y, *Z = fw + f_z, *part_b = fw + f_part;
+  // every workspace of this entry before the first launch (growing one waits for the device); the field pass of one
+  // opponent: a whole opponent tile
+  FieldPass field;
+  if (!field.prepare(ctx, model, 1, row_split(1, n_q), 0)) return (int)hipErrorOutOfMemory;
+  const int NkU = field.NkU, ldu = field.ldu;
+  const double* U = field.U;
   const size_t b_rec = 0, b_picks = b_rec + 2 * (size_t)q, b_xp = b_picks + q, b_vp = b_xp + 64, b_pv = b_vp + PPBO_BATCH_MAX_Q,
-               b_uc = b_pv + 2, b_bests = b_uc + NkU, b_mu = b_bests + 2 * (size_t)(blocks_max + n_chunks),   // (a Best is 16 bytes)
+               b_uc = b_pv + 2, b_bests = b_uc + NkU, b_mu = b_bests + 2 * (size_t)(blocks_max + ck.n),   // (a Best is 16 bytes)
                b_var = b_mu + (size_t)(d_mu ? 0 : M), b_varw = b_var + (size_t)(d_var ? 0 : M),
                b_V = b_varw + (size_t)(d_var_cond ? 0 : M), b_end = b_V + (size_t)(n_steps > 0 ? n_steps : 1) * (size_t)M;
   double* bw = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_BATCH, b_end * sizeof(double));
@@ -4196,48 +4249,28 @@ int ppbo_search_batch(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc
   const double* Kr = nullptr;
   int ldk = 0, kext = 0;
   const PredictChunkHook hook = [&](int64_t, int64_t, const double* Kc, int ldk_c, int Nk_c) -> int {
-    if (Kc && n_chunks == 1) { Kr = Kc + (size_t)kshift * ldk_c; ldk = ldk_c; kext = Nk_c - kshift; }
+    if (Kc && ck.n == 1) { Kr = Kc + (size_t)kshift * ldk_c; ldk = ldk_c; kext = Nk_c - kshift; }
     return 0;
   };
-  Best* chunk_best = nullptr;
-  int nc = 0;
-  if (int rc = predict_passes(ctx, model, d_Xc, M, score_kind, mustar, mu, var, nullptr, true, nullptr, 0, &chunk_best, &nc, s,
-                              nullptr, 0, &hook))
-    return rc;
-  best_record_kernel<<<1, 64, 0, s>>>(chunk_best, nc, 0, rec);
+  PredictRequest rq{d_Xc, M, score_kind, mustar, mu, var};
+  rq.want_best = true; rq.after_chunk = &hook;
+  if (int rc = rq.predict_passes(ctx, model, s)) return rc;
+  best_record_kernel<<<1, 64, 0, s>>>(rq.chunk_best, rq.n_chunks, 0, rec);
   PPBO_LAUNCH_CHECK(ctx);
   if (Kr && kext > NkU - kshift) return ppbo_set_error(ctx, -1, "shortlist: the K* workspace is deeper than the field's U");
 
   // ---- a K* workspace of this entry's own where predict_passes left none that lasts
-  double *K2 = nullptr, *part2 = nullptr;
-  int n_split_eff = 0, q_per_split = 0;
-  const double* geo = nullptr;
+  OwnKstar k2;
   if (!Kr && n_steps > 0) {
-    ldk = (Mc_max + 127) & ~127;
+    if (int rc = k2.prepare(ctx, ppbo_ctx::WS_BATCH_K, model, NkU, Mc_max, 2, false, s)) return rc;
+    ldk = k2.ldk;
     kext = N - kshift;
-    const RowSplit rs = row_split(Mc_max, n_q);
-    q_per_split = rs.q_per_split; n_split_eff = rs.n_split_eff;
-    K2 = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_BATCH_K, ((size_t)NkU * ldk + (size_t)2 * n_split_eff * Mc_max) * sizeof(double));
-    if (!K2) return (int)hipErrorOutOfMemory;
-    part2 = K2 + (size_t)NkU * ldk;
   }
+  const double* const K2 = k2.K;
   // K* of one chunk in the layout of the model's form (the partial sums of its mean and Lambda term are not read)
-  auto form_kstar = [&](int64_t c_beg, int Mc) -> int {
-    PpboProfScope pf(ctx, ppbo_ctx::PF_KSTAR, s);
-    const double* xc = d_Xc + (size_t)c_beg * D;
-    if (edge) {
-      bool oom = false;
-      geo = star_geometry(ctx, model, s, &oom);
-      if (oom) return (int)hipErrorOutOfMemory;
-      dispatch_kstar(model, xc, Mc, K2, ldk, part2, part2 + (size_t)n_split_eff * Mc, q_per_split, n_split_eff, true, s, kshift, geo);
-    } else {
-      dispatch_kstar(model, xc, Mc, K2, ldk, part2, nullptr, q_per_split, n_split_eff, false, s);
-    }
-    PPBO_LAUNCH_CHECK(ctx);
-    return 0;
-  };
-  if (K2 && n_chunks == 1) {
-    if (int rc = form_kstar(0, Mc_max)) return rc;
+  auto form_kstar = [&](const Chunk& c) { return k2.form(ctx, model, d_Xc + (size_t)c.beg * D, c.Mc, s, edge ? kshift : -1); };
+  if (K2 && ck.n == 1) {
+    if (int rc = form_kstar(ck.at(0))) return rc;
     Kr = K2 + (size_t)kshift * ldk;
   }
   if (n_steps > 0) PPBO_HIP_CHECK(ctx, hipMemcpyAsync(varw, var, (size_t)M * sizeof(double), hipMemcpyDeviceToDevice, s));
@@ -4248,37 +4281,35 @@ int ppbo_search_batch(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc
       PpboProfScope pf(ctx, ppbo_ctx::PF_BATCH_FIELD, s);
       batch_gather_kernel<<<1, 64, 0, s>>>(rec + 2 * j, d_Xc, D, varw, V, (long long)M, j, noise_var, picks, xp, vp, pv);
       PPBO_LAUNCH_CHECK(ctx);
-      if (int rc = tournament_field(ctx, model, xp, 1, ldu, NkU, KB, Y, Z, U, part_b, q_per_split_b, n_split_b_eff, s)) return rc;
+      if (int rc = field.run(ctx, xp, 1, s)) return rc;
       batch_ucol_kernel<<<(kext + 255) / 256, 256, 0, s>>>(U + (size_t)kshift * ldu, ldu, kext, uc);
       PPBO_LAUNCH_CHECK(ctx);
     }
-    for (int64_t ch = 0; ch < n_chunks; ++ch) {
-      const int64_t c_beg = ch * chunk_cap;
-      const int Mc = (int)((M - c_beg) < chunk_cap ? (M - c_beg) : chunk_cap);
+    for (const Chunk c : ck) {
       const double* Ks = Kr;
-      if (n_chunks > 1) {
-        if (int rc = form_kstar(c_beg, Mc)) return rc;
+      if (ck.n > 1) {
+        if (int rc = form_kstar(c)) return rc;
         Ks = K2 + (size_t)kshift * ldk;
       }
       PpboProfScope pf(ctx, ppbo_ctx::PF_BATCH_STEP, s);
-      const int blocks = batch_blocks(Mc);
+      const int blocks = batch_blocks(c.Mc);
       if (ldk % 2 != 0 || ldk < blocks * BS_CAND || (reinterpret_cast<uintptr_t>(Ks) & 15) != 0)
         return ppbo_set_error(ctx, -1, "shortlist: the K* workspace is not laid out for 16-byte loads");
       if (int rc = ppbo_kernel_dispatch(ctx, model->kernel_id, [&](auto kid) {
             constexpr int KID = decltype(kid)::value;
-            batch_step_kernel<KID><<<blocks, SC_THREADS, 0, s>>>(Ks, ldk, kext, uc, d_Xc, D, p, Mc, (long long)c_beg, (long long)M,
+            batch_step_kernel<KID><<<blocks, SC_THREADS, 0, s>>>(Ks, ldk, kext, uc, d_Xc, D, p, c.Mc, (long long)c.beg, (long long)M,
                                                                  mu, varw, V, j, vp, pv, picks, xp, score_kind, mustar, bests);
             return 0;
           }))
         return rc;
       PPBO_LAUNCH_CHECK(ctx);
       if (j + 1 < q) {
-        argmax_final_kernel<<<1, 256, 0, s>>>(bests, blocks, step_best + ch);
+        argmax_final_kernel<<<1, 256, 0, s>>>(bests, blocks, step_best + c.ch);
         PPBO_LAUNCH_CHECK(ctx);
       }
     }
     if (j + 1 < q) {
-      best_record_kernel<<<1, 64, 0, s>>>(step_best, (int)n_chunks, 0, rec + 2 * (j + 1));
+      best_record_kernel<<<1, 64, 0, s>>>(step_best, (int)ck.n, 0, rec + 2 * (j + 1));
       PPBO_LAUNCH_CHECK(ctx);
     }
   }
@@ -4297,10 +4328,9 @@ int ppbo_search_batch(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc
 int ppbo_predict_record_publish(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc, int64_t M, int score_kind,
                                 double mustar, int64_t index_offset, double* d_record, unsigned long long* d_flag,
                                 unsigned long long epoch, hipStream_t s, const ppbo_var_projection* proj) {
-  Best* chunk_best = nullptr;
-  int n_chunks = 0;
-  return predict_passes(ctx, model, d_Xc, M, score_kind, mustar, nullptr, nullptr, nullptr, true, d_record,
-                        index_offset, &chunk_best, &n_chunks, s, d_flag, epoch, nullptr, proj);
+  PredictRequest rq{d_Xc, M, score_kind, mustar};
+  rq.proj = proj; rq.want_best = true; rq.d_record = d_record; rq.record_offset = index_offset; rq.publish = d_flag; rq.epoch = epoch;
+  return rq.predict_passes(ctx, model, s);
 }
 
 // internal (project.hip): edge_apply_kernel on the caller's stream -- E [N][ld] = the edge-layout rows of Kt [N][ld]
@@ -4408,19 +4438,20 @@ LineCovPlan line_cov_plan(int N, int mblk, int Bc_max) {
 // The contraction stage shared by the line entries and ppbo_predict_gradients: for the Bc groups of G columns each that Kt
 // [Nk][ld] holds in the node layout (M = Bc G columns), Y = G K* (edge form: E into Ke, then Y = H E) and the groups' data
 // terms K*' Lambda K* + Y'Y in cov_parts, pl.cov_splits row-slice slabs of stride pst.
-int line_y_cov(ppbo_ctx* ctx, const ppbo_model* model, const double* Gq, int Nk, int g_rows, const double* Kt, double* Y,
-               double* Ke, int ld, int M, int Bc, int G, const LineCovPlan& pl, double* cov_parts, long long pst,
-               hipStream_t s) {
+int line_y_cov(ppbo_ctx* ctx, const ppbo_model* model, const LineWorkspace& lw, int M, int Bc, int G, const LineCovPlan& pl,
+               double* cov_parts, long long pst, hipStream_t s) {
   const int N = model->N, mblk = model->m + 1, n_q = N / mblk;
+  const int ld = lw.ld;
+  const double* const Kt = lw.Kt;
   const bool edge = model->form == PPBO_FORM_EDGE, sym = pl.sym;
   const int cov_splits = pl.cov_splits, cov_rows = pl.cov_rows, cov_cs = pl.cov_cs;
   GemmArgs y{};  // Y = G K*
-  y.A = Gq; y.lda = Nk; y.B = Kt; y.ldb = ld; y.C = Y; y.ldc = ld;
-  y.M = g_rows; y.N = (M + 127) & ~127; y.K = Nk; y.alpha = 1.0; y.beta = 0.0; y.khi_mode = 1; y.tri_block = mblk;
+  y.A = lw.Gq; y.lda = lw.Nk; y.B = Kt; y.ldb = ld; y.C = lw.Y; y.ldc = ld;
+  y.M = lw.g_rows; y.N = (M + 127) & ~127; y.K = lw.Nk; y.alpha = 1.0; y.beta = 0.0; y.khi_mode = 1; y.tri_block = mblk;
   if (edge) {
-    edge_apply_kernel<<<dim3((M + 127) / 128, N), 128, 0, s>>>(Kt, ld, M, mblk, n_q, model->d_lam_off, Ke);
+    edge_apply_kernel<<<dim3((M + 127) / 128, N), 128, 0, s>>>(Kt, ld, M, mblk, n_q, model->d_lam_off, lw.Ke);
     PPBO_LAUNCH_CHECK(ctx);
-    y.B = Ke; y.tri_block = 1;   // H lower triangular
+    y.B = lw.Ke; y.tri_block = 1;   // H lower triangular
   }
   // (rows [N, g_rows) of Y come out as zeros, columns [M, y.N) as whatever the K* padding holds: neither is read)
   // column tiles in chunks through all row tiles, heaviest first (a chunk's slice of K* -- 134 MB at 64 tiles -- stays
@@ -4439,9 +4470,9 @@ int line_y_cov(ppbo_ctx* ctx, const ppbo_model* model, const double* Gq, int Nk,
     // sym: every chunk is whole stars: the symmetric form (lower-triangle tiles only)
 #define LC_LAUNCH(NT)                                                                                                   \
   do {                                                                                                                  \
-    if (sym) line_cov_kernel<NT, true><<<cg, 256, 0, s>>>(Kt, Y, ld, N, G, mblk, model->d_lam_diag, model->d_lam_off,   \
+    if (sym) line_cov_kernel<NT, true><<<cg, 256, 0, s>>>(Kt, lw.Y, ld, N, G, mblk, model->d_lam_diag, model->d_lam_off,   \
                                                           cov_rows, cov_parts, pst, cov_cs);                            \
-    else line_cov_kernel<NT, false><<<cg, 256, 0, s>>>(Kt, Y, ld, N, G, mblk, model->d_lam_diag, model->d_lam_off,      \
+    else line_cov_kernel<NT, false><<<cg, 256, 0, s>>>(Kt, lw.Y, ld, N, G, mblk, model->d_lam_diag, model->d_lam_off,      \
                                                        cov_rows, cov_parts, pst, cov_cs);                               \
   } while (0)
     switch ((G + 15) / 16) {
@@ -4486,32 +4517,18 @@ int line_acq_impl(ppbo_ctx* ctx, const ppbo_model* model, const double* d_grid, 
   PPBO_REQUIRE(ctx, (d_grid || (d_xi && d_x && d_alpha)) && (an || (d_z && S > 0)) && B > 0 && G > 0 && G <= 128,
                "line arguments (G <= 128)");
   PPBO_REQUIRE(ctx, model->d_G && model->d_lam_diag && model->d_lam_off, "model G/Lambda");
-  const int N = model->N, mblk = model->m + 1, n_q = N / mblk, D = model->D;
+  const int N = model->N, mblk = model->m + 1, D = model->D;
   const KernParams p = make_kern_params(model->kernel_id, model->theta);
-  const int Bc_max = (B < 512) ? B : 512;
-  // operands of Y = G K* padded to whole tiles / chunks, as in predict_passes: every tile of that product then takes
-  // the unguarded loop whatever N, the star size and B G are (m = 25: 4.16 -> 3.6 ms for 512 lines at N = 2080)
-  int Nk = N, g_rows = N;
-  const double* Gq = padded_G(ctx, model, 128, (long long)B * G >= 2048, &Nk, &g_rows, s);
-  if (!Gq) return (int)hipErrorOutOfMemory;
-  PPBO_LAUNCH_CHECK(ctx);
-  const int ld = ((Bc_max * G) + 127) & ~127;
-  // edge form: Y = H E with E the edge-layout K* beside the node-layout one (which the mean and K*' Lambda K* read)
-  const bool edge = model->form == PPBO_FORM_EDGE;
-  double* ws = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_KSTAR, (size_t)((edge ? 2 : 1) * Nk + g_rows) * ld * sizeof(double));
-  if (!ws) return (int)hipErrorOutOfMemory;
-  double* Kt = ws;
-  double* Y = ws + (size_t)Nk * ld;
-  double* Ke = edge ? Y + (size_t)g_rows * ld : nullptr;
-  if (Nk != N) PPBO_HIP_CHECK(ctx, hipMemsetAsync(Kt + (size_t)N * ld, 0, (size_t)(Nk - N) * ld * sizeof(double), s));
-  if (edge && Nk != N) PPBO_HIP_CHECK(ctx, hipMemsetAsync(Ke + (size_t)N * ld, 0, (size_t)(Nk - N) * ld * sizeof(double), s));
+  const Chunks ck(B, 512);
+  const int Bc_max = ck.Mc_max;
+  LineWorkspace lw;
+  if (int rc = lw.prepare(ctx, model, Bc_max * G, true, (long long)B * G >= 2048, s)) return rc;
   double* gridws = nullptr;
   if (!d_grid) {
     gridws = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_SEARCH, (size_t)Bc_max * G * D * sizeof(double));
     if (!gridws) return (int)hipErrorOutOfMemory;
   }
-  const RowSplit rs = row_split(Bc_max * G, n_q);
-  const int q_per_split = rs.q_per_split, n_split_eff = rs.n_split_eff;
+  const int q_per_split = lw.rs.q_per_split, n_split_eff = lw.rs.n_split_eff;
   const LineCovPlan lcp = line_cov_plan(N, mblk, Bc_max);
   const bool sym = lcp.sym;
   const int cov_splits = lcp.cov_splits;
@@ -4541,8 +4558,8 @@ int line_acq_impl(ppbo_ctx* ctx, const ppbo_model* model, const double* d_grid, 
                                (size_t)Bc_max * nsplit * (ch ? (size_t)G * sizeof(int) : 3 * sizeof(double)));
   if (!mc_ws && !an) return (int)hipErrorOutOfMemory;
   double* mc_part = (double*)mc_ws;
-  for (int b0 = 0; b0 < B; b0 += Bc_max) {
-    const int Bc = (B - b0 < Bc_max) ? (B - b0) : Bc_max;
+  for (const Chunk c : ck) {
+    const int b0 = (int)c.beg, Bc = c.Mc;
     const int M = Bc * G;
     const double* xg;
     if (d_grid) {
@@ -4556,7 +4573,7 @@ int line_acq_impl(ppbo_ctx* ctx, const ppbo_model* model, const double* d_grid, 
     }
     {
       PpboProfScope pf(ctx, ppbo_ctx::PF_LINE_KSTAR, s);
-      dispatch_kstar(model, xg, M, Kt, ld, part, nullptr, q_per_split, n_split_eff, false, s);
+      dispatch_kstar(model, xg, M, lw.Kt, lw.ld, part, nullptr, q_per_split, n_split_eff, false, s);
     }
     score_kernel<<<score_blocks(M), SC_THREADS, 0, s>>>(part, n_split_eff, nullptr, nullptr, 0, M, 0.0, PPBO_SCORE_MEAN,
                                                         0.0, 0, mu, nullptr, nullptr, nullptr);
@@ -4566,7 +4583,7 @@ int line_acq_impl(ppbo_ctx* ctx, const ppbo_model* model, const double* d_grid, 
         }))
       return rc;
     PPBO_LAUNCH_CHECK(ctx);
-    if (int rc = line_y_cov(ctx, model, Gq, Nk, g_rows, Kt, Y, Ke, ld, M, Bc, G, lcp, cov_parts, (long long)Bc_max * G * G, s)) return rc;
+    if (int rc = line_y_cov(ctx, model, lw, M, Bc, G, lcp, cov_parts, (long long)Bc_max * G * G, s)) return rc;
     if (an) {
       if (int rc = ppbo_answer_score_groups(ctx, mu, cov, Bc, G, an->sigma, d_z, S, jitter, cov_parts, cov_splits,
                                             (long long)Bc_max * G * G, sym ? 1 : 0, an->d_lpd ? an->d_lpd + b0 : nullptr,
@@ -4749,7 +4766,7 @@ int ppbo_predict_gradients(ppbo_ctx* ctx, const ppbo_model* model, const double*
   PPBO_REQUIRE(ctx, M >= 1 && M <= (int64_t)0x7fffffff, "point count (1 .. 2^31 - 1)");
   PPBO_REQUIRE(ctx, score_kind == PPBO_GRAD_NONE || score_kind == PPBO_GRAD_TRACE || score_kind == PPBO_GRAD_NORM2, "score_kind");
   PPBO_REQUIRE(ctx, !model->kstar_fp32, "gradients are fp64 only (kstar_fp32)");
-  const int N = model->N, D = model->D, mblk = model->m + 1, n_q = N / mblk;
+  const int N = model->N, D = model->D, mblk = model->m + 1;
   GradMetric gm;
   for (int d = 0; d < 64; ++d) gm.w[d] = 1.0;
   if (h_metric)
@@ -4765,82 +4782,50 @@ int ppbo_predict_gradients(ppbo_ctx* ctx, const ppbo_model* model, const double*
     if (h_best_val) *h_best_val = NAN;
     if (h_best_idx) *h_best_idx = -1;
   }
-  PpboHostRecord hr{};
-  if (want_best)
-    if (int rc = ppbo_host_record(ctx, &hr)) return rc;
+  BestReturn br;
+  if (int rc = br.begin(ctx, want_best)) return rc;
   constexpr int GRAD_CHUNK = 512;
   const KernParams p = make_kern_params(model->kernel_id, model->theta);
-  const bool edge = model->form == PPBO_FORM_EDGE;
-  const int Pc_max = (int)(M < GRAD_CHUNK ? M : GRAD_CHUNK);
-  const int64_t n_chunks = (M + GRAD_CHUNK - 1) / GRAD_CHUNK;
-  const int ld = ((Pc_max * D) + 127) & ~127;
-  int Nk = N, g_rows = N;
-  const double* Gq = nullptr;
-  double *Kt = nullptr, *Y = nullptr, *Ke = nullptr;
-  LineCovPlan lcp{};
-  if (want_cov) {
-    Gq = padded_G(ctx, model, 128, (long long)Pc_max * D >= 2048, &Nk, &g_rows, s);
-    if (!Gq) return (int)hipErrorOutOfMemory;
-    PPBO_LAUNCH_CHECK(ctx);
-    double* ws = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_KSTAR, (size_t)((edge ? 2 : 1) * Nk + g_rows) * ld * sizeof(double));
-    if (!ws) return (int)hipErrorOutOfMemory;
-    Kt = ws;
-    Y = ws + (size_t)Nk * ld;
-    Ke = edge ? Y + (size_t)g_rows * ld : nullptr;
-    if (Nk != N) PPBO_HIP_CHECK(ctx, hipMemsetAsync(Kt + (size_t)N * ld, 0, (size_t)(Nk - N) * ld * sizeof(double), s));
-    if (edge && Nk != N) PPBO_HIP_CHECK(ctx, hipMemsetAsync(Ke + (size_t)N * ld, 0, (size_t)(Nk - N) * ld * sizeof(double), s));
-    lcp = line_cov_plan(N, mblk, Pc_max);
-  }
-  const RowSplit rs = row_split(Pc_max * D, n_q);
-  const int q_per_split = rs.q_per_split, n_split_eff = rs.n_split_eff;
+  const Chunks ck(M, GRAD_CHUNK);
+  const int Pc_max = ck.Mc_max;
+  LineWorkspace lw;
+  if (int rc = lw.prepare(ctx, model, Pc_max * D, want_cov, (long long)Pc_max * D >= 2048, s)) return rc;
+  const LineCovPlan lcp = want_cov ? line_cov_plan(N, mblk, Pc_max) : LineCovPlan{};
+  const int q_per_split = lw.rs.q_per_split, n_split_eff = lw.rs.n_split_eff;
   const long long pst = (long long)Pc_max * D * D;
   double* part = (double*)ppbo_workspace(
       ctx, ppbo_ctx::WS_PART,
       ((size_t)n_split_eff * Pc_max * D + (want_cov ? (size_t)lcp.cov_splits * pst : 0)) * sizeof(double));
   if (!part) return (int)hipErrorOutOfMemory;
   double* cov_parts = want_cov ? part + (size_t)n_split_eff * Pc_max * D : nullptr;
-  Best* bests = (Best*)ppbo_workspace(ctx, ppbo_ctx::WS_SMALL, (size_t)(Pc_max + n_chunks) * sizeof(Best));
+  Best* bests = (Best*)ppbo_workspace(ctx, ppbo_ctx::WS_SMALL, (size_t)(Pc_max + ck.n) * sizeof(Best));
   if (!bests) return (int)hipErrorOutOfMemory;
   Best* chunk_best = bests + Pc_max;
-  for (int64_t ch = 0; ch < n_chunks; ++ch) {
-    const int64_t c_beg = ch * GRAD_CHUNK;
-    const int Pc = (int)((M - c_beg) < GRAD_CHUNK ? (M - c_beg) : GRAD_CHUNK);
-    const double* xp = d_X + (size_t)c_beg * D;
-    const bool one = (n_chunks == 1);
+  for (const Chunk c : ck) {
+    const int Pc = c.Mc;
+    const double* xp = d_X + (size_t)c.beg * D;
     if (int rc = ppbo_kernel_dispatch(ctx, model->kernel_id, [&](auto kid) {
           constexpr int KID = decltype(kid)::value;
           {
             PpboProfScope pf(ctx, ppbo_ctx::PF_GRAD_KSTAR, s);
-            launch_kstar_grad<KID>(KstarLaunch{model, p, Kt, ld, part, nullptr, q_per_split, n_split_eff, false, -1, s}, xp, Pc);
+            launch_kstar_grad<KID>(KstarLaunch{model, p, lw.Kt, lw.ld, part, nullptr, q_per_split, n_split_eff, false, -1, s}, xp, Pc);
           }
           PPBO_LAUNCH_CHECK(ctx);
           if (want_cov)
-            if (int rc2 = line_y_cov(ctx, model, Gq, Nk, g_rows, Kt, Y, Ke, ld, Pc * D, Pc, D, lcp, cov_parts, pst, s)) return rc2;
+            if (int rc2 = line_y_cov(ctx, model, lw, Pc * D, Pc, D, lcp, cov_parts, pst, s)) return rc2;
           PpboProfScope pf(ctx, ppbo_ctx::PF_GRAD_FINISH, s);
           grad_finish_kernel<KID><<<Pc, 256, 0, s>>>(xp, Pc, D, p, part, n_split_eff, cov_parts, lcp.cov_splits, pst,
-                                                     lcp.sym ? 1 : 0, gm, score_kind, (long long)c_beg,
-                                                     d_mean ? d_mean + (size_t)c_beg * D : nullptr,
-                                                     d_cov ? d_cov + (size_t)c_beg * D * D : nullptr,
-                                                     d_score ? d_score + c_beg : nullptr, want_best ? bests : nullptr);
+                                                     lcp.sym ? 1 : 0, gm, score_kind, (long long)c.beg,
+                                                     d_mean ? d_mean + (size_t)c.beg * D : nullptr,
+                                                     d_cov ? d_cov + (size_t)c.beg * D * D : nullptr,
+                                                     d_score ? d_score + c.beg : nullptr, want_best ? bests : nullptr);
           PPBO_LAUNCH_CHECK(ctx);
           return 0;
         }))
       return rc;
-    if (want_best) {
-      argmax_final_kernel<<<1, 256, 0, s>>>(bests, Pc, chunk_best + ch, one ? hr.d_rec : nullptr, 0,
-                                            one ? hr.d_flag : nullptr, hr.epoch);
-      PPBO_LAUNCH_CHECK(ctx);
-    }
+    if (int rc = br.chunk(ctx, bests, Pc, chunk_best, c.ch, ck, s)) return rc;
   }
-  if (!want_best) return 0;
-  if (n_chunks > 1) {
-    best_record_kernel<<<1, 64, 0, s>>>(chunk_best, (int)n_chunks, 0, hr.d_rec, hr.d_flag, hr.epoch);
-    PPBO_LAUNCH_CHECK(ctx);
-  }
-  if (int rc = ppbo_host_record_wait(ctx, hr, s)) return rc;
-  if (h_best_val) *h_best_val = hr.h_rec[0];      // (NaN, -1) when no point has a non-NaN score
-  if (h_best_idx) *h_best_idx = (int64_t)hr.h_rec[1];
-  return 0;
+  return br.finish(ctx, chunk_best, ck, s, h_best_val, h_best_idx);
 }
 
 int ppbo_randn(ppbo_ctx* ctx, uint64_t seed, double* d_out, int64_t n, void* stream) {

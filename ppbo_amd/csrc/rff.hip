@@ -801,9 +801,8 @@ int ppbo_rff_score(ppbo_ctx* ctx, const double* d_Xc, int64_t M, int D, const do
   PPBO_REQUIRE(ctx, M > 0 && D > 0 && D <= 64 && F > 0, "sizes (D<=64)");
   hipStream_t s = (hipStream_t)stream;
   const double scale = std::sqrt(2.0 * sigma_f * sigma_f / (double)F);
-  const int64_t chunk_cap = 65536;
-  const int64_t n_chunks = (M + chunk_cap - 1) / chunk_cap;
-  const int Mc_max = (int)(M < chunk_cap ? M : chunk_cap);
+  const Chunks ck(M);
+  const int Mc_max = ck.Mc_max;
   const int cblocks = (Mc_max + RS_THREADS * 2 - 1) / (RS_THREADS * 2);
   int n_split = (2048 + cblocks - 1) / cblocks;
   if (n_split > (F + RS_RF - 1) / RS_RF) n_split = (F + RS_RF - 1) / RS_RF;
@@ -815,36 +814,34 @@ int ppbo_rff_score(ppbo_ctx* ctx, const double* d_Xc, int64_t M, int D, const do
   double* part = (double*)ppbo_workspace(ctx, ppbo_ctx::WS_PART, (size_t)n_split * Mc_max * sizeof(double));
   if (!part) return (int)hipErrorOutOfMemory;
   const int sblocks_max = score_blocks(Mc_max);
-  Best* bests = (Best*)ppbo_workspace(ctx, ppbo_ctx::WS_SMALL, (size_t)(sblocks_max + n_chunks) * sizeof(Best));
+  Best* bests = (Best*)ppbo_workspace(ctx, ppbo_ctx::WS_SMALL, (size_t)(sblocks_max + ck.n) * sizeof(Best));
   if (!bests) return (int)hipErrorOutOfMemory;
   Best* chunk_best = bests + sblocks_max;
-  for (int64_t ch = 0; ch < n_chunks; ++ch) {
-    const int64_t c_beg = ch * chunk_cap;
-    const int Mc = (int)((M - c_beg) < chunk_cap ? (M - c_beg) : chunk_cap);
-    const double* xc = d_Xc + (size_t)c_beg * D;
-    dim3 grid((Mc + RS_THREADS * 2 - 1) / (RS_THREADS * 2), n_split);
+  for (const Chunk c : ck) {
+    const double* xc = d_Xc + (size_t)c.beg * D;
+    dim3 grid((c.Mc + RS_THREADS * 2 - 1) / (RS_THREADS * 2), n_split);
     PpboProfScope pf(ctx, ppbo_ctx::PF_RFF_SCORE, s);
     if (ctx->rff_score_mfma) {
-      dim3 gm((Mc + 255) / 256, n_split);
+      dim3 gm((c.Mc + 255) / 256, n_split);
       RffMfmaLadder::dispatch(D, [&](auto dp) {
-        rff_score_mfma_kernel<decltype(dp)::value, 4, 2><<<gm, 256, 0, s>>>(xc, Mc, D, d_W, F, d_b, d_omega, make_rff_poly(scale),
+        rff_score_mfma_kernel<decltype(dp)::value, 4, 2><<<gm, 256, 0, s>>>(xc, c.Mc, D, d_W, F, d_b, d_omega, make_rff_poly(scale),
                                                                             f_per_split, part);
       });
     } else {
       RffScoreLadder::dispatch(D, [&](auto dp) {
-        rff_score_kernel<decltype(dp)::value><<<grid, RS_THREADS, 0, s>>>(xc, Mc, D, d_W, F, d_b, d_omega, make_rff_poly(scale),
+        rff_score_kernel<decltype(dp)::value><<<grid, RS_THREADS, 0, s>>>(xc, c.Mc, D, d_W, F, d_b, d_omega, make_rff_poly(scale),
                                                                           f_per_split, part);
       });
     }
     PPBO_LAUNCH_CHECK(ctx);
-    const int sblocks = score_blocks(Mc);
-    score_kernel<<<sblocks, SC_THREADS, 0, s>>>(part, n_split, nullptr, nullptr, 0, Mc, 0.0, PPBO_SCORE_MEAN, 0.0,
-                                         (long long)c_beg, nullptr, nullptr, d_score ? d_score + c_beg : nullptr,
+    const int sblocks = score_blocks(c.Mc);
+    score_kernel<<<sblocks, SC_THREADS, 0, s>>>(part, n_split, nullptr, nullptr, 0, c.Mc, 0.0, PPBO_SCORE_MEAN, 0.0,
+                                         (long long)c.beg, nullptr, nullptr, d_score ? d_score + c.beg : nullptr,
                                          bests);
-    argmax_final_kernel<<<1, 256, 0, s>>>(bests, sblocks, chunk_best + ch);
+    argmax_final_kernel<<<1, 256, 0, s>>>(bests, sblocks, chunk_best + c.ch);
     PPBO_LAUNCH_CHECK(ctx);
   }
-  return merge_chunk_bests(ctx, chunk_best, (int)n_chunks, h_best_val, h_best_idx, s);
+  return merge_chunk_bests(ctx, chunk_best, (int)ck.n, h_best_val, h_best_idx, s);
 }
 
 int ppbo_rff_score_multi(ppbo_ctx* ctx, const double* d_Xc, int64_t M, int D, const double* d_W, int F,

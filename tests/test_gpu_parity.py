@@ -736,6 +736,32 @@ def test_line_acq_shapes(eng, golden, B, G, S):
         assert host(ei2)[-1] == host(ei2)[0] and host(vm2)[-1] == host(vm2)[0]
 
 
+def test_line_acq_chunk_edge(eng, golden):
+    """513 lines = a chunk of 512 and a chunk of one: the last line of the first chunk and the only line of the second
+    (and line 0) against the oracle on the same draws, at the tolerances of test_line_acq_shapes (whose batches above 512
+    lines check their first, middle and last line only)."""
+    g = golden("smoke")
+    post, _ = _posterior(eng, g)
+    B, G, S, D = 513, 3, 65, int(g["D"])
+    rng = np.random.default_rng(513)
+    al = np.sort(rng.random(G))
+    xis = np.zeros((B, D)); xis[np.arange(B), rng.integers(0, D, B)] = 1.0
+    xs = rng.random((B, D)) * (xis == 0)
+    grid = al[None, :, None] * xis[:, None, :] + xs[:, None, :]
+    z = rng.standard_normal((S, G))
+    sf2 = float(g["theta"][2]) ** 2
+    mustar, jit = float(g["line_mustar"]), 1e-9 * sf2
+    ei, vm = eng.line_acq(post, grid, z, mustar, jitter=jit)
+    ei, vm = host(ei), host(vm)
+    assert ei.shape == (B,) and vm.shape == (B,)
+    for b in (0, 511, 512):
+        mu_b, cov_b = eng.predict_cov(post, grid[b])
+        e0 = orc.line_ei(host(mu_b), host(cov_b), z, mustar, jitter=jit)
+        v0 = orc.line_varmax(host(mu_b), host(cov_b), z, jitter=jit)
+        assert abs(ei[b] - e0) <= 1e-6 * max(abs(e0), 1e-3 * np.sqrt(sf2)), (b, ei[b], e0)
+        assert abs(vm[b] - v0) <= 1e-5 * max(abs(v0), 1e-6 * sf2), (b, vm[b], v0)
+
+
 @pytest.mark.parametrize("m,n_q,B,G", [(25, 10, 40, 70), (25, 7, 3, 70), (9, 13, 33, 64), (30, 5, 50, 48), (25, 21, 30, 70), (40, 5, 30, 70),
                                        (1, 100, 8, 70), (15, 12, 35, 70), (33, 6, 30, 17), (25, 24, 600, 16)])
 def test_line_acq_ragged_star_sizes(eng, m, n_q, B, G):
