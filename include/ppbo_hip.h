@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define PPBO_ABI_VERSION 8
+#define PPBO_ABI_VERSION 9
 #define PPBO_ERR_NOT_PD 1001
 
 /* The library is built with -fvisibility=hidden: the entry points declared here are its ONLY dynamic symbols
@@ -318,6 +318,16 @@ typedef struct ppbo_coords {
   const double* d_Xc;    /* CAMPHOR, model entries only: the design rows in the caller's coordinates [N,6] */
 } ppbo_coords;
 
+/* a projected variance operator T = Q^T H of one model ("the projected edge form" below; ABI 9: ppbo_model.proj) */
+typedef struct ppbo_var_projection {
+  const double* d_T;   /* [rows_padded][ld] */
+  int rows;            /* r: rows of T in use; 0 = no projection */
+  int rows_padded;     /* r rounded up to the 128-row tile */
+  int ld;              /* row stride of d_T */
+  double bound;        /* certified bound on var - var_projected >= 0, units of variance */
+  double tol;          /* the tolerance it was built for, relative to sigma_f^2 */
+} ppbo_var_projection;
+
 typedef struct ppbo_model {
   int kernel_id, N, D, m;
   double theta[3];
@@ -344,6 +354,8 @@ typedef struct ppbo_model {
                              * Ignored where no operator is read: d_G == NULL, and the mean-only ppbo_mean_* entries */
   ppbo_coords coords;       /* (ABI 8) the coordinates d_X is in, relative to the caller's ("the coordinate map of a model"
                              * above); zero-initialised: the same */
+  ppbo_var_projection proj; /* (ABI 9) the projected operator built for THIS model (ppbo_var_projection_build; "the projected
+                             * edge form" below, which names the entries that read it); zero-initialised (rows == 0): none */
 } ppbo_model;
 
 /* The transpose of G = R Lambda in the layout the one-launch scoring kernel reads: d_Gt[rows][ld] with
@@ -1188,47 +1200,39 @@ PPBO_API int ppbo_argmax_combine(ppbo_ctx* ctx, const double* d_records, int wor
  * rows [rows, rows_max_padded) and columns [0, n_q) and [N, ld) hold explicit zeros, and *proj names it.
  * proj->rows == 0 (d_T is then not to be used; not an error): the model is not an edge-form one with d_G, it is one the
  * one-launch scoring kernel takes, r_max < 128, a factorization failed, or tol was not reached.
- * The _p entries are ppbo_predict, ppbo_predict_record and ppbo_search_sharded with a trailing projection: NULL or
- * rows == 0 run exactly the launches of those entries (which call the same code with NULL); otherwise the contraction
- * launch reads T (rows_padded / 128 row tiles, each over the full K range) in place of H.  The mean, the k*^T Lambda k*
- * term, the score rule and the argmax are the same.  A projection whose ld, row counts or form do not fit the model is
- * refused ("invalid argument").  Every other consumer of d_G (pairs, slopes, covariances, line acquisitions, tournaments)
- * needs H itself and takes no projection. */
+ * A projection is built for one model and is data of that model -- ppbo_model.proj (ABI 9) -- not a function name and not a
+ * trailing argument: the caller copies the struct that ppbo_var_projection_build filled into the model it built it for.
+ * Who reads it: ppbo_predict, ppbo_predict_record, ppbo_search_sharded and ppbo_predict_prune_report read model->proj.
+ * rows <= 0 (a zero-initialised model): exactly the launches of a model without one; otherwise the contraction launch reads
+ * T (rows_padded / 128 row tiles, each over the full K range) in place of H.  The mean, the k*^T Lambda k* term, the score
+ * rule and the argmax are the same.  A projection whose ld, row counts or form do not fit the model is refused ("invalid
+ * argument", with nothing launched); a call whose model has d_G == NULL reads no operator and no projection.
+ * EVERY other entry that takes a model ignores proj (it needs H itself, or no operator): the two-set predictors
+ * (ppbo_predict_pairs, _slopes, _curvatures, _functionals, _marginals), ppbo_predict_tournament, ppbo_predict_kg,
+ * ppbo_search_batch, ppbo_predict_cov, the ppbo_line_* entries and ppbo_score_answers, ppbo_predict_gradients, ppbo_acq_grad
+ * and ppbo_acq_ascent, the ppbo_mean_* entries, and ppbo_var_projection_shape / _build themselves (so _build may write
+ * straight into the proj of the model it is given).  The consequence: the mu / var that ppbo_predict_tournament,
+ * ppbo_predict_kg and ppbo_search_batch return are bit for bit those of ppbo_predict on the same model WITHOUT a projection,
+ * whatever model->proj holds. */
 #define PPBO_VAR_PROJECTION_SEED 0x70726f6a65637431ull
 #define PPBO_VAR_PROJECTION_SHRINK 1e-6
-typedef struct ppbo_var_projection {
-  const double* d_T;   /* [rows_padded][ld] */
-  int rows;            /* r: rows of T in use; 0 = no projection */
-  int rows_padded;     /* r rounded up to the 128-row tile */
-  int ld;              /* row stride of d_T */
-  double bound;        /* certified bound on var - var_projected >= 0, units of variance */
-  double tol;          /* the tolerance it was built for, relative to sigma_f^2 */
-} ppbo_var_projection;
 PPBO_API int ppbo_var_projection_shape(const ppbo_model* model, int* rows_max_padded, int* ld);
 PPBO_API int ppbo_var_projection_build(ppbo_ctx* ctx, const ppbo_model* model, double tol, double* d_T,
                                        ppbo_var_projection* proj, void* stream);
-PPBO_API int ppbo_predict_p(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc, int64_t M,
-                   int score_kind, double mustar, double* d_mu, double* d_var, double* d_score,
-                   double* h_best_val, int64_t* h_best_idx, void* stream, const ppbo_var_projection* proj);
-PPBO_API int ppbo_predict_record_p(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc, int64_t M, int score_kind,
-                          double mustar, int64_t index_offset, double* d_record, void* stream,
-                          const ppbo_var_projection* proj);
-PPBO_API int ppbo_search_sharded_p(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc, int64_t M, int score_kind,
-                          double mustar, int64_t index_offset, double* h_best_val, int64_t* h_best_idx, void* stream,
-                          const ppbo_var_projection* proj);
 
-/* The pruned search, a diagnostic of it.  A call that asks only for the best record (ppbo_search_sharded(_p),
- * ppbo_predict_record(_p), ppbo_predict(_p) with no per-candidate output) of an edge-form model on the three-launch
+/* The pruned search, a diagnostic of it.  A call that asks only for the best record (ppbo_search_sharded,
+ * ppbo_predict_record, ppbo_predict with no per-candidate output) of an edge-form model on the three-launch
  * path, scored by pointwise EI or VARIANCE, contracts the variance only for the candidates that a certified upper bound
  * of their score cannot rule out (env PPBO_PRUNE, default 1; 0 = contract all).  The record is bit for bit that of
  * PPBO_PRUNE=0.  This entry runs the passes of ONE chunk (M <= 65536) with the pruning on, whatever PPBO_PRUNE says, and
  * reports what they decided: per candidate (device arrays of M doubles, any may be NULL) u2 >= the contraction's sum of
  * squares, and the score interval [s_lo, s_hi] (s_hi = +inf: a candidate with a non-finite sum, which always survives);
  * on the host the threshold (the largest s_lo), the number of survivors and whether the chunk was pruned (0: more than
- * the capacity survived, or no finite threshold -- the full contraction ran).  Synchronises the stream.  ABI 8. */
+ * the capacity survived, or no finite threshold -- the full contraction ran).  Synchronises the stream.  ABI 8; it
+ * reads model->proj since ABI 9. */
 PPBO_API int ppbo_predict_prune_report(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc, int64_t M,
-                          int score_kind, double mustar, const ppbo_var_projection* proj, double* d_u2, double* d_s_lo,
-                          double* d_s_hi, double* h_threshold, int* h_n_surv, int* h_pruned, void* stream);
+                          int score_kind, double mustar, double* d_u2, double* d_s_lo, double* d_s_hi,
+                          double* h_threshold, int* h_n_surv, int* h_pruned, void* stream);
 
 /* y = op(A) x for a square fp64 matrix; lower != 0 reads only the lower triangle (A is then
  * treated as lower-triangular).  Used for alpha = Sigma^-1 f_MAP (src/gp_model.py:445) and

@@ -51,19 +51,17 @@ class Coords(C.Structure):
     _fields_ = [("kind", C.c_int), ("h_coef", C.POINTER(C.c_double)), ("d_Xc", C.c_void_p)]
 
 
-class Model(C.Structure):
-    _fields_ = [("kernel_id", C.c_int), ("N", C.c_int), ("D", C.c_int), ("m", C.c_int),
-                ("theta", C.c_double * 3), ("d_X", C.c_void_p), ("d_alpha", C.c_void_p),
-                ("d_lam_diag", C.c_void_p), ("d_lam_off", C.c_void_p), ("d_G", C.c_void_p), ("kstar_fp32", C.c_int),
-                ("d_Gt", C.c_void_p), ("form", C.c_int), ("coords", Coords)]
-
-
-
-
 class VarProjection(C.Structure):
     """ppbo_var_projection: a projected variance operator T = Q^T H and its certified error bound."""
     _fields_ = [("d_T", C.c_void_p), ("rows", C.c_int), ("rows_padded", C.c_int), ("ld", C.c_int), ("bound", C.c_double),
                 ("tol", C.c_double)]
+
+
+class Model(C.Structure):
+    _fields_ = [("kernel_id", C.c_int), ("N", C.c_int), ("D", C.c_int), ("m", C.c_int),
+                ("theta", C.c_double * 3), ("d_X", C.c_void_p), ("d_alpha", C.c_void_p),
+                ("d_lam_diag", C.c_void_p), ("d_lam_off", C.c_void_p), ("d_G", C.c_void_p), ("kstar_fp32", C.c_int),
+                ("d_Gt", C.c_void_p), ("form", C.c_int), ("coords", Coords), ("proj", VarProjection)]
 
 
 class MarginalAxes(C.Structure):
@@ -200,19 +198,14 @@ SIGNATURES = {
     "ppbo_posterior_form": [_vp, _i, _i, _i, _i],
     "ppbo_var_projection_shape": [C.POINTER(Model), C.POINTER(_i), C.POINTER(_i)],
     "ppbo_var_projection_build": [_vp, C.POINTER(Model), _d, _vp, C.POINTER(VarProjection), _vp],
-    "ppbo_predict_p": [_vp, C.POINTER(Model), _vp, _i64, _i, _d, _vp, _vp, _vp, C.POINTER(_d), C.POINTER(_i64), _vp,
-                       C.POINTER(VarProjection)],
-    "ppbo_predict_record_p": [_vp, C.POINTER(Model), _vp, _i64, _i, _d, _i64, _vp, _vp, C.POINTER(VarProjection)],
-    "ppbo_search_sharded_p": [_vp, C.POINTER(Model), _vp, _i64, _i, _d, _i64, C.POINTER(_d), C.POINTER(_i64), _vp,
-                              C.POINTER(VarProjection)],
-    "ppbo_predict_prune_report": [_vp, C.POINTER(Model), _vp, _i64, _i, _d, C.POINTER(VarProjection), _vp, _vp, _vp,
-                                  C.POINTER(_d), C.POINTER(_i), C.POINTER(_i), _vp],
+    "ppbo_predict_prune_report": [_vp, C.POINTER(Model), _vp, _i64, _i, _d, _vp, _vp, _vp, C.POINTER(_d), C.POINTER(_i),
+                                  C.POINTER(_i), _vp],
     "ppbo_argmax_combine": [_vp, _vp, _i, C.POINTER(_d), C.POINTER(_i64), _vp],
     "ppbo_dgemm": [_vp, _i, _i, _i, _i, _i, _d, _vp, _i, _vp, _i, _d, _vp, _i, _vp],
 }
 
 _lib = None
-ABI_VERSION = 8     # must equal PPBO_ABI_VERSION of include/ppbo_hip.h
+ABI_VERSION = 9    # must equal PPBO_ABI_VERSION of include/ppbo_hip.h
 
 
 def _check_stamp():

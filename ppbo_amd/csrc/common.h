@@ -143,7 +143,7 @@ int ppbo_fused_score(ppbo_ctx* ctx, const ppbo_model* m, const double* Gt, int l
 // predict.hip, for dist.hip: one shard's scoring passes with the record published to host-mapped memory
 int ppbo_predict_record_publish(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc, int64_t M, int score_kind,
                                 double mustar, int64_t index_offset, double* d_record, unsigned long long* d_flag,
-                                unsigned long long epoch, hipStream_t s, const ppbo_var_projection* proj = nullptr);
+                                unsigned long long epoch, hipStream_t s);
 // predict.hip, for project.hip: E [N][ld] = the edge-layout rows of the node-layout Kt [N][ld] (edge_apply_kernel), M columns
 int ppbo_edge_apply_async(ppbo_ctx* ctx, const double* Kt, int ld, int M, int N, int mblk, const double* d_lam_off, double* E,
                           hipStream_t s);

@@ -201,12 +201,6 @@ int ppbo_argmax_allgather_record(ppbo_ctx* ctx, const double* d_record, double* 
 
 int ppbo_search_sharded(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc, int64_t M, int score_kind,
                         double mustar, int64_t index_offset, double* h_best_val, int64_t* h_best_idx, void* stream) {
-  return ppbo_search_sharded_p(ctx, model, d_Xc, M, score_kind, mustar, index_offset, h_best_val, h_best_idx, stream, nullptr);
-}
-
-int ppbo_search_sharded_p(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc, int64_t M, int score_kind,
-                          double mustar, int64_t index_offset, double* h_best_val, int64_t* h_best_idx, void* stream,
-                          const ppbo_var_projection* proj) {
   PPBO_ENTER(ctx);
   PPBO_REQUIRE(ctx, h_best_val || h_best_idx, "outputs");
   if (!ctx->dist) {
@@ -214,7 +208,7 @@ int ppbo_search_sharded_p(ppbo_ctx* ctx, const ppbo_model* model, const double* 
     PpboHostRecord hr;
     if (int rc = ppbo_host_record(ctx, &hr)) return rc;
     if (int rc = ppbo_predict_record_publish(ctx, model, d_Xc, M, score_kind, mustar, index_offset, hr.d_rec, hr.d_flag,
-                                             hr.epoch, (hipStream_t)stream, proj))
+                                             hr.epoch, (hipStream_t)stream))
       return rc;
     if (int rc = ppbo_host_record_wait(ctx, hr, (hipStream_t)stream)) return rc;
     if (h_best_val) *h_best_val = hr.h_rec[0];
@@ -226,7 +220,7 @@ int ppbo_search_sharded_p(ppbo_ctx* ctx, const ppbo_model* model, const double* 
   if (!dev) return ppbo_set_error(ctx, (int)hipErrorOutOfMemory, "collective staging");
   // this rank's (best score, global index) stays on the device: scoring, the all-gather, the reduction and the
   // publication of the 16-byte record are enqueued behind each other on ONE stream and the host waits once
-  if (int rc = ppbo_predict_record_p(ctx, model, d_Xc, M, score_kind, mustar, index_offset, dev + 2, stream, proj)) return rc;
+  if (int rc = ppbo_predict_record(ctx, model, d_Xc, M, score_kind, mustar, index_offset, dev + 2, stream)) return rc;
   return gather_reduce_readback(ctx, dev + 2, h_best_val, h_best_idx, (hipStream_t)stream);
 }
 

@@ -1335,6 +1335,7 @@ extern "C" int ppbo_mean_search(ppbo_ctx* ctx, const ppbo_model* m, const double
   if (!sel.alloc(ctx, 0, 0)) return (int)hipErrorOutOfMemory;
   ppbo_model mean_only = *m;
   mean_only.d_G = nullptr;
+  mean_only.proj.rows = 0;   // the mean entries ignore model->proj (ppbo_predict would check that it fits)
   if (int rc = ppbo_predict(ctx, &mean_only, d_cand, M, PPBO_SCORE_MEAN, 0.0, sel.scores, nullptr, nullptr, nullptr, nullptr,
                             stream))
     return rc;
@@ -1465,6 +1466,7 @@ extern "C" int ppbo_mean_search_multi(ppbo_ctx* ctx, const ppbo_model* model, co
     const KernParams sp = emb ? make_kern_params(PPBO_KERNEL_SE, emb->theta) : p;
     ppbo_model mean_only = *sm;
     mean_only.d_G = nullptr;
+    mean_only.proj.rows = 0;   // the mean entries ignore model->proj (ppbo_predict would check that it fits)
     for (int t = 0; t < T; ++t) {
       const long long nt = M + (t == 0 ? E : 0);
       trial_rows_kernel<<<(unsigned)((nt * D + 255) / 256), 256, 0, s>>>(tc, t, rows);
@@ -1604,6 +1606,7 @@ extern "C" int ppbo_mean_search_boxes(ppbo_ctx* ctx, const ppbo_model* model, co
   const KernParams sp = emb ? make_kern_params(PPBO_KERNEL_SE, emb->theta) : p;
   ppbo_model mean_only = *sm;
   mean_only.d_G = nullptr;
+  mean_only.proj.rows = 0;   // the mean entries ignore model->proj (ppbo_predict would check that it fits)
   double* mu = sel.scores;
   for (int t0 = 0; t0 < T; t0 += TB) {
     const int nb = (T - t0 < TB) ? (T - t0) : TB;

@@ -3436,17 +3436,17 @@ struct PredictRequest {
   int64_t record_offset = 0;
   unsigned long long *publish = nullptr, epoch = 0;   // the flag raised to `epoch` behind the record
   const PredictChunkHook* after_chunk = nullptr;
-  const ppbo_var_projection* proj = nullptr;
+  bool projected = false;                      // read model->proj (the entries the header names); else the model has none
   PruneReport* report = nullptr;
   Best* chunk_best = nullptr;                  // results: [n_chunks] on the device
   int n_chunks = 0;
   int predict_passes(ppbo_ctx* ctx, const ppbo_model* model, hipStream_t s);
 };
 int PredictRequest::predict_passes(ppbo_ctx* ctx, const ppbo_model* model, hipStream_t s) {
-  const ppbo_var_projection* proj = this->proj;
   if (int rc = check_model(ctx, model)) return rc;
+  const ppbo_var_projection* proj = projected ? &model->proj : nullptr;
   PPBO_REQUIRE(ctx, d_Xc != nullptr && M > 0, "candidates");
-  // a projected operator (ppbo_var_projection_build): rows == 0 or NULL = none, today's launches.  One with rows must
+  // a projected operator (ppbo_var_projection_build): rows == 0 = none, today's launches.  One with rows must
   // have been built for a model of this shape and form.
   if (proj && proj->rows <= 0) proj = nullptr;
   if (proj) {
@@ -3608,16 +3608,10 @@ int PredictRequest::predict_passes(ppbo_ctx* ctx, const ppbo_model* model, hipSt
 int ppbo_predict(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc, int64_t M, int score_kind,
                  double mustar, double* d_mu, double* d_var, double* d_score, double* h_best_val,
                  int64_t* h_best_idx, void* stream) {
-  return ppbo_predict_p(ctx, model, d_Xc, M, score_kind, mustar, d_mu, d_var, d_score, h_best_val, h_best_idx, stream, nullptr);
-}
-
-int ppbo_predict_p(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc, int64_t M, int score_kind,
-                   double mustar, double* d_mu, double* d_var, double* d_score, double* h_best_val,
-                   int64_t* h_best_idx, void* stream, const ppbo_var_projection* proj) {
   PPBO_ENTER(ctx);
   hipStream_t s = (hipStream_t)stream;
   PredictRequest rq{d_Xc, M, score_kind, mustar, d_mu, d_var, d_score};
-  rq.proj = proj;
+  rq.projected = true;
   rq.want_best = h_best_val || h_best_idx;
   // predict_passes writes the record itself: the ctx's when a best is wanted, taken before its refusals (else none)
   BestReturn br;
@@ -3629,20 +3623,14 @@ int ppbo_predict_p(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc, i
 
 int ppbo_predict_record(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc, int64_t M, int score_kind,
                         double mustar, int64_t index_offset, double* d_record, void* stream) {
-  return ppbo_predict_record_p(ctx, model, d_Xc, M, score_kind, mustar, index_offset, d_record, stream, nullptr);
-}
-
-int ppbo_predict_record_p(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc, int64_t M, int score_kind,
-                          double mustar, int64_t index_offset, double* d_record, void* stream,
-                          const ppbo_var_projection* proj) {
   PPBO_ENTER(ctx);
   PPBO_REQUIRE(ctx, d_record != nullptr, "d_record");
-  return ppbo_predict_record_publish(ctx, model, d_Xc, M, score_kind, mustar, index_offset, d_record, nullptr, 0, (hipStream_t)stream, proj);
+  return ppbo_predict_record_publish(ctx, model, d_Xc, M, score_kind, mustar, index_offset, d_record, nullptr, 0, (hipStream_t)stream);
 }
 
 int ppbo_predict_prune_report(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc, int64_t M, int score_kind,
-                              double mustar, const ppbo_var_projection* proj, double* d_u2, double* d_s_lo, double* d_s_hi,
-                              double* h_threshold, int* h_n_surv, int* h_pruned, void* stream) {
+                              double mustar, double* d_u2, double* d_s_lo, double* d_s_hi, double* h_threshold,
+                              int* h_n_surv, int* h_pruned, void* stream) {
   PPBO_ENTER(ctx);
   hipStream_t s = (hipStream_t)stream;
   PruneReport rep;
@@ -3650,7 +3638,7 @@ int ppbo_predict_prune_report(ppbo_ctx* ctx, const ppbo_model* model, const doub
   PpboHostRecord hr;
   if (int rc = ppbo_host_record(ctx, &hr)) return rc;
   PredictRequest rq{d_Xc, M, score_kind, mustar};
-  rq.proj = proj; rq.report = &rep;
+  rq.projected = true; rq.report = &rep;
   rq.want_best = true; rq.d_record = hr.d_rec; rq.publish = hr.d_flag; rq.epoch = hr.epoch;
   if (int rc = rq.predict_passes(ctx, model, s)) return rc;
   if (int rc = ppbo_host_record_wait(ctx, hr, s)) return rc;
@@ -4327,9 +4315,9 @@ int ppbo_search_batch(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc
 // internal (dist.hip): ppbo_predict_record whose record lives in host-mapped memory, the flag raised after it
 int ppbo_predict_record_publish(ppbo_ctx* ctx, const ppbo_model* model, const double* d_Xc, int64_t M, int score_kind,
                                 double mustar, int64_t index_offset, double* d_record, unsigned long long* d_flag,
-                                unsigned long long epoch, hipStream_t s, const ppbo_var_projection* proj) {
+                                unsigned long long epoch, hipStream_t s) {
   PredictRequest rq{d_Xc, M, score_kind, mustar};
-  rq.proj = proj; rq.want_best = true; rq.d_record = d_record; rq.record_offset = index_offset; rq.publish = d_flag; rq.epoch = epoch;
+  rq.projected = true; rq.want_best = true; rq.d_record = d_record; rq.record_offset = index_offset; rq.publish = d_flag; rq.epoch = epoch;
   return rq.predict_passes(ctx, model, s);
 }
 

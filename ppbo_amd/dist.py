@@ -92,9 +92,6 @@ class ShardedSearch:
         # the ctypes arguments of a step are built once (the model descriptor alone costs ~10 us of Python per call)
         import ctypes as _C
         from .engine import SCORE_MEAN, _ptr
-        self._md = engine._model(post, score != SCORE_MEAN)
-        self._md_ref = _C.byref(self._md)
-        self._search_fn, self._record_fn = engine.lib.ppbo_search_sharded_p, engine.lib.ppbo_predict_record_p
         import os as _os
         self.projection = None
         if project and score != SCORE_MEAN and post.G is not None and _os.environ.get("PPBO_VAR_PROJECTION", "1") != "0":
@@ -102,7 +99,8 @@ class ShardedSearch:
             N = int(post.X.shape[0])
             E = N - N // (int(post.m) + 1)
             self.projection = pj if pj.rows > 0 and E >= min_gain * 2 * pj.rows else None
-        self._pj_ref = self.projection.ref if self.projection is not None else None
+        self._md = engine._model(post, score != SCORE_MEAN, projection=self.projection)
+        self._md_ref = _C.byref(self._md)
         self._xc_ptr, self._M = _ptr(self.Xc), int(self.Xc.shape[0])
         self._bv, self._bi = _C.c_double(0.0), _C.c_int64(-1)
         self._bv_ref, self._bi_ref = _C.byref(self._bv), _C.byref(self._bi)
@@ -126,12 +124,12 @@ class ShardedSearch:
         # a stream synchronisation for 16 bytes (~10 us of a 120 us step at C2)
         single = self.world == 1 and not self.host and not (dist.is_available() and dist.is_initialized())
         if (self.collective == "capi" or single) and not self.host:
-            rc = self._search_fn(eng.ctx, self._md_ref, self._xc_ptr, self._M, int(self.score), self.mustar,
-                                             self.offset, self._bv_ref, self._bi_ref, eng._stream(), self._pj_ref)
+            rc = eng.lib.ppbo_search_sharded(eng.ctx, self._md_ref, self._xc_ptr, self._M, int(self.score), self.mustar,
+                                             self.offset, self._bv_ref, self._bi_ref, eng._stream())
             eng._check(rc, "ppbo_search_sharded")
             return self._bv.value, self._bi.value
-        rc = self._record_fn(eng.ctx, self._md_ref, self._xc_ptr, self._M, int(self.score), self.mustar,
-                                         self.offset, self._rec_ptr, eng._stream(), self._pj_ref)
+        rc = eng.lib.ppbo_predict_record(eng.ctx, self._md_ref, self._xc_ptr, self._M, int(self.score), self.mustar,
+                                         self.offset, self._rec_ptr, eng._stream())
         eng._check(rc, "ppbo_predict_record")
         if self.world == 1 and not dist.is_initialized():
             v, i = self.record.tolist()

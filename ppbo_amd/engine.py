@@ -257,7 +257,6 @@ class VarianceProjection:
 
     def __init__(self, T, struct, tol):
         self.T, self.struct, self.tol = T, struct, float(tol)
-        self.ref = C.byref(struct)
 
     rows = property(lambda self: self.struct.rows)
     bound = property(lambda self: self.struct.bound)
@@ -386,7 +385,8 @@ class Engine:
         return Posterior(kernel, theta_key(theta), m, Xd, alpha, None, None, None, scale=scale,
                          **self._camphor_fields(X, theta, kernel))
 
-    def _model(self, post: Posterior, with_var=True, kstar_fp32=False):
+    def _model(self, post: Posterior, with_var=True, kstar_fp32=False, projection=None):
+        """projection: a VarianceProjection of `post` (project_variance) for the entries that read ppbo_model.proj."""
         N, D = post.X.shape
         md = _lib.Model()
         md.kernel_id = self._kid(post.kernel)
@@ -407,6 +407,10 @@ class Engine:
         elif post.scale is not None:
             md._coords = _lib.coords(_lib.COORDS_SCALED, post.scale)
             md.coords = md._coords
+        if projection is not None:
+            # ppbo_model.proj, a copy of the struct; md._projection keeps T alive as long as md
+            md._projection = projection
+            md.proj = projection.struct
         if md.d_G and post.form == FORM_NODE and N <= 1024 and post.kernel != "camphor_copper_kernel":
             # models the one-launch scoring kernel takes: its matrix-core loop reads G transposed -- formed ONCE per
             # posterior here (the library would otherwise do it in a workspace on every call)
@@ -490,12 +494,13 @@ class Engine:
         self._check(rc, "ppbo_argmax_allgather_record")
         return bv.value, bi.value
 
-    def predict_record(self, post, Xc, score=SCORE_MEAN, mustar=0.0, index_offset=0, out=None, kstar_fp32=False):
+    def predict_record(self, post, Xc, score=SCORE_MEAN, mustar=0.0, index_offset=0, out=None, kstar_fp32=False,
+                       projection=None):
         """One shard of a sharded search, enqueue only (ppbo_predict_record): out[2] (device) = (best score,
-        index_offset + first row index as a float64); nothing is read back, nothing synchronises."""
+        index_offset + first row index as a float64); nothing is read back, nothing synchronises.  projection: as predict's."""
         Xc = self.dev(Xc)
         Xc = self._points(post, Xc)
-        md = self._model(post, score != SCORE_MEAN, kstar_fp32)
+        md = self._model(post, score != SCORE_MEAN, kstar_fp32, projection)
         rec = self.empty(2) if out is None else out
         rc = self.lib.ppbo_predict_record(self.ctx, C.byref(md), _ptr(Xc), Xc.shape[0], int(score), float(mustar),
                                           int(index_offset), _ptr(rec), self._stream())
@@ -508,23 +513,23 @@ class Engine:
         contraction's sum of squares), s_lo, s_hi per candidate, and threshold, n_surv, pruned."""
         Xc = self._points(post, self.dev(Xc))
         M = Xc.shape[0]
-        md = self._model(post, True)
+        md = self._model(post, True, projection=projection)
         u2, lo, hi = self.empty(M), self.empty(M), self.empty(M)
         thr, ns, pr = C.c_double(0.0), C.c_int(0), C.c_int(0)
         rc = self.lib.ppbo_predict_prune_report(self.ctx, C.byref(md), _ptr(Xc), M, int(score), float(mustar),
-                                                projection.ref if projection is not None else None, _ptr(u2), _ptr(lo),
-                                                _ptr(hi), C.byref(thr), C.byref(ns), C.byref(pr), self._stream())
+                                                _ptr(u2), _ptr(lo), _ptr(hi), C.byref(thr), C.byref(ns), C.byref(pr),
+                                                self._stream())
         self._check(rc, "ppbo_predict_prune_report")
         return dict(u2=u2, s_lo=lo, s_hi=hi, threshold=thr.value, n_surv=ns.value, pruned=pr.value)
 
-    def search_sharded(self, post, Xc, score=SCORE_MEAN, mustar=0.0, index_offset=0, kstar_fp32=False):
+    def search_sharded(self, post, Xc, score=SCORE_MEAN, mustar=0.0, index_offset=0, kstar_fp32=False, projection=None):
         """One whole sharded search step in ONE library call (ppbo_search_sharded): score this rank's rows, RCCL
         all-gather of the 16-byte records (when dist_init has run on this ctx), reduction, one read-back.  Not for a
-        camphor_copper_ard_kernel posterior."""
+        camphor_copper_ard_kernel posterior.  projection: as predict's."""
         if post.camphor is not None:
             raise ValueError("search_sharded does not take a camphor_copper_ard_kernel posterior")
         Xc = self._points(post, Xc)
-        md = self._model(post, score != SCORE_MEAN, kstar_fp32)
+        md = self._model(post, score != SCORE_MEAN, kstar_fp32, projection)
         bv, bi = C.c_double(0.0), C.c_int64(-1)
         rc = self.lib.ppbo_search_sharded(self.ctx, C.byref(md), _ptr(Xc), Xc.shape[0], int(score), float(mustar),
                                           int(index_offset), C.byref(bv), C.byref(bi), self._stream())
@@ -834,15 +839,15 @@ class Engine:
         Xc = self._points(post, Xc)
         M = Xc.shape[0]
         with_var = want_var or score != SCORE_MEAN
-        md = self._model(post, with_var, kstar_fp32)
+        md = self._model(post, with_var, kstar_fp32, projection)
         mu = self.empty(M) if want_mu else None
         var = self.empty(M) if (want_var and with_var) else None
         sc = self.empty(M) if want_score else None
         bv, bi = C.c_double(0.0), C.c_int64(-1)
-        rc = self.lib.ppbo_predict_p(self.ctx, C.byref(md), _ptr(Xc), M, int(score), float(mustar), _ptr(mu), _ptr(var),
-                                     _ptr(sc), C.byref(bv) if want_best else None, C.byref(bi) if want_best else None,
-                                     self._stream(), projection.ref if projection is not None else None)
-        self._check(rc, "ppbo_predict_p")
+        rc = self.lib.ppbo_predict(self.ctx, C.byref(md), _ptr(Xc), M, int(score), float(mustar), _ptr(mu), _ptr(var),
+                                   _ptr(sc), C.byref(bv) if want_best else None, C.byref(bi) if want_best else None,
+                                   self._stream())
+        self._check(rc, "ppbo_predict")
         return dict(mu=mu, var=var, score=sc, best_val=bv.value, best_idx=bi.value)
 
     @staticmethod

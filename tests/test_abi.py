@@ -28,8 +28,8 @@ def test_library_exports_every_declared_symbol():
     for s in header_symbols():
         assert hasattr(lib, s), f"libppbo_hip.so does not export {s}"
         assert s in _lib.SIGNATURES, f"ctypes binding lacks {s}"
-    assert set(_lib.SIGNATURES) == set(header_symbols())
-    assert lib.ppbo_abi_version() == _lib.ABI_VERSION == 8
+    assert set(_lib.SIGNATURES) == set(header_symbols()) and len(header_symbols()) == 84
+    assert lib.ppbo_abi_version() == _lib.ABI_VERSION == 9
 
 
 def test_library_exports_nothing_but_the_c_abi():
@@ -50,8 +50,8 @@ def test_library_exports_nothing_but_the_c_abi():
 
 
 def test_no_edge_twins_anywhere():
-    """The operator's form is ppbo_model.form / the form argument, and a model's coordinate map is ppbo_model.coords / a
-    ppbo_coords argument: never a function name."""
+    """The operator's form is ppbo_model.form / the form argument, a model's coordinate map is ppbo_model.coords / a
+    ppbo_coords argument, and its variance projection is ppbo_model.proj: never a function name."""
     import shutil
     import subprocess
     from ppbo_amd import _lib
@@ -63,23 +63,26 @@ def test_no_edge_twins_anywhere():
     exported = [ln.split()[-1] for ln in out.splitlines() if ln.strip()]
     assert len(exported) > 50
     for names in (header_symbols(), list(_lib.SIGNATURES), exported):
-        assert not [n for n in names if n.endswith(("_edge", "_scaled", "_camphor"))]
+        assert not [n for n in names if n.endswith(("_edge", "_scaled", "_camphor", "_p"))]
 
 
 def test_model_struct_matches_the_header(tmp_path):
-    """_lib.Model is ppbo_model: `coords` (a ppbo_coords) is its last member behind `form`, and the sizes and every field
-    offset -- those of coords.kind, coords.h_coef and coords.d_Xc included -- are what the C compiler gives the header's
-    structs."""
+    """_lib.Model is ppbo_model: `coords` (a ppbo_coords) and `proj` (a ppbo_var_projection) are its last members behind
+    `form`, and the sizes and every field offset -- those of the members of coords and of proj included -- are what the C
+    compiler gives the header's structs."""
     import ctypes as C
     import shutil
     import subprocess
     from ppbo_amd import _lib
     names = [f[0] for f in _lib.Model._fields_]
-    assert names[-2:] == ["form", "coords"] and _lib.Model.form.size == C.sizeof(C.c_int)
+    assert names[-3:] == ["form", "coords", "proj"] and _lib.Model.form.size == C.sizeof(C.c_int)
     assert _lib.Model().form == 0          # a zero-initialised model is a node-form model ...
     assert _lib.Model().coords.kind == 0 and not _lib.Model().coords.h_coef and not _lib.Model().coords.d_Xc   # ... in the caller's coordinates
+    assert _lib.Model().proj.rows == 0 and not _lib.Model().proj.d_T          # ... without a projection
     cnames = [f[0] for f in _lib.Coords._fields_]
     assert cnames == ["kind", "h_coef", "d_Xc"]
+    pnames = [f[0] for f in _lib.VarProjection._fields_]
+    assert pnames == ["d_T", "rows", "rows_padded", "ld", "bound", "tol"]
     cc = shutil.which("cc") or shutil.which("gcc") or shutil.which("clang")
     assert cc, "no C compiler to lay out ppbo_model with"
     src = tmp_path / "layout.c"
@@ -88,6 +91,8 @@ def test_model_struct_matches_the_header(tmp_path):
                    + "".join(f'  printf(" %zu", offsetof(ppbo_model, {n}));\n' for n in names)
                    + '  printf(" %zu", sizeof(ppbo_coords));\n'
                    + "".join(f'  printf(" %zu", offsetof(ppbo_model, coords.{n}));\n' for n in cnames)
+                   + '  printf(" %zu", sizeof(ppbo_var_projection));\n'
+                   + "".join(f'  printf(" %zu", offsetof(ppbo_model, proj.{n}));\n' for n in pnames)
                    + '  printf(" %d %d %d", PPBO_COORDS_MODEL, PPBO_COORDS_SCALED, PPBO_COORDS_CAMPHOR);\n'
                    + '  printf(" %d %d", PPBO_FORM_NODE, PPBO_FORM_EDGE); return 0; }\n')
     exe = tmp_path / "layout"
@@ -98,9 +103,11 @@ def test_model_struct_matches_the_header(tmp_path):
     assert out[1:1 + nm] == [getattr(_lib.Model, n).offset for n in names]
     assert out[1 + nm] == C.sizeof(_lib.Coords) == _lib.Model.coords.size
     assert out[2 + nm:5 + nm] == [_lib.Model.coords.offset + getattr(_lib.Coords, n).offset for n in cnames]
-    assert _lib.Model.coords.offset + C.sizeof(_lib.Coords) == C.sizeof(_lib.Model)      # nothing behind coords
-    assert out[5 + nm:8 + nm] == [_lib.COORDS_MODEL, _lib.COORDS_SCALED, _lib.COORDS_CAMPHOR] == [0, 1, 2]
-    assert out[-2:] == [0, 1] and len(out) == 10 + nm
+    assert out[5 + nm] == C.sizeof(_lib.VarProjection) == _lib.Model.proj.size
+    assert out[6 + nm:12 + nm] == [_lib.Model.proj.offset + getattr(_lib.VarProjection, n).offset for n in pnames]
+    assert _lib.Model.proj.offset + C.sizeof(_lib.VarProjection) == C.sizeof(_lib.Model)      # nothing behind proj
+    assert out[12 + nm:15 + nm] == [_lib.COORDS_MODEL, _lib.COORDS_SCALED, _lib.COORDS_CAMPHOR] == [0, 1, 2]
+    assert out[-2:] == [0, 1] and len(out) == 17 + nm
 
 
 def test_no_gpu_means_loud_failure():

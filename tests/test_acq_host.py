@@ -113,7 +113,7 @@ def test_header_and_binding_have_the_two_entries():
         assert mt, f"include/ppbo_hip.h does not declare {name}"
         assert len(mt.group(1).split(",")) == nargs
         assert name in _lib.SIGNATURES and len(_lib.SIGNATURES[name]) == nargs
-    assert _lib.ABI_VERSION == 8 and "#define PPBO_ABI_VERSION 8" in open(os.path.join(ROOT, "include", "ppbo_hip.h")).read()
+    assert _lib.ABI_VERSION == 9 and "#define PPBO_ABI_VERSION 9" in open(os.path.join(ROOT, "include", "ppbo_hip.h")).read()
     assert "acq.hip" in __import__("ppbo_amd.build", fromlist=["SOURCES"]).SOURCES
 
 

@@ -40,7 +40,7 @@ def test_header_and_signatures_list_the_new_entry_points():
         assert re.search(r"PPBO_API int " + name + r"\(", hdr), name
         assert name in _lib.SIGNATURES, name
     assert "no reference counterpart" in hdr
-    assert _lib.ABI_VERSION == 8
+    assert _lib.ABI_VERSION == 9
 
 
 def test_library_exports_the_new_entry_points():

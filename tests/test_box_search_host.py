@@ -123,9 +123,9 @@ def test_box_rows():
 
 def test_header_declares_both_entries_at_abi_8():
     h = open(os.path.join(ROOT, "include", "ppbo_hip.h")).read()
-    assert re.search(r"#define\s+PPBO_ABI_VERSION\s+8\b", h)
+    assert re.search(r"#define\s+PPBO_ABI_VERSION\s+9\b", h)
     for name in ("ppbo_mean_ascent_boxes", "ppbo_mean_search_boxes"):
         assert re.search(r"PPBO_API\s+int\s+" + name + r"\s*\(", h), name
     from ppbo_amd import _lib
-    assert _lib.ABI_VERSION == 8
+    assert _lib.ABI_VERSION == 9
     assert len(_lib.SIGNATURES["ppbo_mean_ascent_boxes"]) == 13 and len(_lib.SIGNATURES["ppbo_mean_search_boxes"]) == 18

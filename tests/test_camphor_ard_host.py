@@ -210,7 +210,7 @@ def test_entries_in_header_binding_map_and_library():
         assert re.search(r"PPBO_API int %s\(" % e, hdr), e
         assert e in _lib.SIGNATURES, e
         assert any(fnmatch.fnmatch(e, p) for p in pats), e
-    assert _lib.ABI_VERSION == 8
+    assert _lib.ABI_VERSION == 9
     assert "camphor_copper_ard_kernel" not in _lib.KERNEL_IDS        # no device kernel id: SE on embedded rows
     if not os.path.exists(_lib.LIB_PATH):
         pytest.fail("libppbo_hip.so is not built (build() runs before the suite)")

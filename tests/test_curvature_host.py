@@ -189,12 +189,12 @@ def test_reference_removes_variance_only():
 # ---------------------------------------------------------------- the plumbing
 def test_binding_header_and_constants():
     from ppbo_amd import _lib, engine
-    assert _lib.ABI_VERSION == 8
+    assert _lib.ABI_VERSION == 9
     assert "ppbo_predict_curvatures" in _lib.SIGNATURES and len(_lib.SIGNATURES["ppbo_predict_curvatures"]) == 14
     slopes = _lib.SIGNATURES["ppbo_predict_slopes"]
     assert _lib.SIGNATURES["ppbo_predict_curvatures"] == slopes[:4] + [slopes[3]] + slopes[4:]
     txt = open(os.path.join(ROOT, "include", "ppbo_hip.h")).read()
-    assert re.search(r"#define\s+PPBO_ABI_VERSION\s+8\b", txt)
+    assert re.search(r"#define\s+PPBO_ABI_VERSION\s+9\b", txt)
     code = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
     assert "ppbo_predict_curvatures" in set(re.findall(r"\bint\s+(ppbo_[a-z_A-Z0-9]+)\s*\(", code))
     assert re.search(r"PPBO_CURV_MEAN\s*=\s*0\s*,\s*PPBO_CURV_VARIANCE\s*=\s*1\s*,\s*PPBO_CURV_PROB\s*=\s*2", code)

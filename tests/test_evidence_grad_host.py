@@ -75,7 +75,7 @@ def test_header_version_script_and_library_list_the_entry():
     hdr = open(os.path.join(ROOT, "include", "ppbo_hip.h")).read()
     assert re.search(r"PPBO_API int ppbo_evidence_grad\(", hdr)
     assert "ppbo_evidence_grad" in _lib.SIGNATURES
-    assert _lib.ABI_VERSION == 8
+    assert _lib.ABI_VERSION == 9
     vs = open(os.path.join(ROOT, "ppbo_amd", "csrc", "libppbo_hip.map")).read()
     pats = [p.strip() for p in vs.split("global:")[1].split("local:")[0].split(";") if p.strip()]
     assert any(fnmatch.fnmatch("ppbo_evidence_grad", p) for p in pats)

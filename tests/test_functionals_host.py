@@ -125,10 +125,10 @@ def test_reference_reduces_to_the_duel_and_the_point():
 
 def test_binding_header_and_constants():
     from ppbo_amd import _lib, engine
-    assert _lib.ABI_VERSION == 8
+    assert _lib.ABI_VERSION == 9
     assert "ppbo_predict_functionals" in _lib.SIGNATURES and len(_lib.SIGNATURES["ppbo_predict_functionals"]) == 16
     txt = open(os.path.join(ROOT, "include", "ppbo_hip.h")).read()
-    assert re.search(r"#define\s+PPBO_ABI_VERSION\s+8\b", txt)
+    assert re.search(r"#define\s+PPBO_ABI_VERSION\s+9\b", txt)
     assert re.search(r"#define\s+PPBO_FUNCTIONAL_MAX_G\s+64\b", txt)
     code = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
     assert "ppbo_predict_functionals" in set(re.findall(r"\bint\s+(ppbo_[a-z_A-Z0-9]+)\s*\(", code))

@@ -186,7 +186,7 @@ def test_tile_shapes_agree_with_each_other():
 # ---- dense operands: a hand-built projection -----------------------------------------------------------------------------
 @functools.lru_cache(maxsize=None)
 def dense_case(r):
-    """An edge-form Hand of N = 676, a random dense T [r][ld] in the layout ppbo_predict_p expects (columns [0, n_q) and
+    """An edge-form Hand of N = 676, a random dense T [r][ld] in the layout ppbo_model.proj names (columns [0, n_q) and
     [N, ld) zero), and {M: (Xc, mu0, var0)} with var0 = sf2 + t + |T E|^2: mean_var_ref with T's first N columns as the
     operator (its rows [0, n_q) of E are zero, the columns beyond N meet the zeroed K* rows)."""
     n_q, m, D, kernel = DENSE

@@ -1,4 +1,5 @@
-"""GPU: the projected edge form (ppbo_var_projection_build and the _p scoring entries) against the unprojected entries.
+"""GPU: the projected edge form (ppbo_var_projection_build and the entries that read ppbo_model.proj) against the same entries
+without a projection.
 
 The models are real edge-form posteriors of small star designs (ppbo_posterior on a smooth latent vector, or ppbo_gp_fit):
 a RANDOM operator of the edge form's sparsity has no decaying spectrum, so nothing could be projected.  N = 384 (n_q = 12,
@@ -82,48 +83,40 @@ def built(eng):
     return out
 
 
-# ---- the six entries, called directly ---------------------------------------------------------------------------------
+# ---- the three entries, called directly: pj (None or a VarianceProjection) travels in the model, ppbo_model.proj -------------
 def call_predict(eng, post, Xc, score, mustar, pj):
-    """(mu, var, score, best value, best index) of ppbo_predict (pj is None) or ppbo_predict_p (pj: a VarianceProjection)."""
+    """(mu, var, score, best value, best index) of ppbo_predict."""
     from ppbo_amd.engine import _ptr
     Xd = eng._points(post, Xc)
     M = Xd.shape[0]
-    md = eng._model(post, True)
+    md = eng._model(post, True, projection=pj)
     mu, var, sc = eng.empty(M), eng.empty(M), eng.empty(M)
     bv, bi = C.c_double(0.0), C.c_int64(-1)
-    args = [eng.ctx, C.byref(md), _ptr(Xd), M, int(score), float(mustar), _ptr(mu), _ptr(var), _ptr(sc), C.byref(bv),
-            C.byref(bi), eng._stream()]
-    if pj is None:
-        eng._check(eng.lib.ppbo_predict(*args), "ppbo_predict")
-    else:
-        eng._check(eng.lib.ppbo_predict_p(*args, pj.ref), "ppbo_predict_p")
+    rc = eng.lib.ppbo_predict(eng.ctx, C.byref(md), _ptr(Xd), M, int(score), float(mustar), _ptr(mu), _ptr(var), _ptr(sc),
+                              C.byref(bv), C.byref(bi), eng._stream())
+    eng._check(rc, "ppbo_predict")
     return host(mu), host(var), host(sc), bv.value, bi.value
 
 
 def call_record(eng, post, Xc, score, mustar, pj, offset=1000):
     from ppbo_amd.engine import _ptr
     Xd = eng._points(post, Xc)
-    md = eng._model(post, True)
+    md = eng._model(post, True, projection=pj)
     rec = eng.empty(2)
-    args = [eng.ctx, C.byref(md), _ptr(Xd), Xd.shape[0], int(score), float(mustar), offset, _ptr(rec), eng._stream()]
-    if pj is None:
-        eng._check(eng.lib.ppbo_predict_record(*args), "ppbo_predict_record")
-    else:
-        eng._check(eng.lib.ppbo_predict_record_p(*args, pj.ref), "ppbo_predict_record_p")
+    rc = eng.lib.ppbo_predict_record(eng.ctx, C.byref(md), _ptr(Xd), Xd.shape[0], int(score), float(mustar), offset, _ptr(rec),
+                                     eng._stream())
+    eng._check(rc, "ppbo_predict_record")
     return host(rec)
 
 
 def call_search(eng, post, Xc, score, mustar, pj, offset=1000):
     from ppbo_amd.engine import _ptr
     Xd = eng._points(post, Xc)
-    md = eng._model(post, True)
+    md = eng._model(post, True, projection=pj)
     bv, bi = C.c_double(0.0), C.c_int64(-1)
-    args = [eng.ctx, C.byref(md), _ptr(Xd), Xd.shape[0], int(score), float(mustar), offset, C.byref(bv), C.byref(bi),
-            eng._stream()]
-    if pj is None:
-        eng._check(eng.lib.ppbo_search_sharded(*args), "ppbo_search_sharded")
-    else:
-        eng._check(eng.lib.ppbo_search_sharded_p(*args, pj.ref), "ppbo_search_sharded_p")
+    rc = eng.lib.ppbo_search_sharded(eng.ctx, C.byref(md), _ptr(Xd), Xd.shape[0], int(score), float(mustar), offset,
+                                     C.byref(bv), C.byref(bi), eng._stream())
+    eng._check(rc, "ppbo_search_sharded")
     return bv.value, bi.value
 
 
@@ -179,7 +172,7 @@ def assert_same_bits(eng, post, pj, Xc):
 
 def test_tolerance_out_of_reach(eng):
     """D = 20, a short length scale, N = 384, fitted: r_max = 128 leaves ~4e-11 sf2 (the shrinkage nugget), so a tolerance of
-    1e-13 is refused -- rows == 0, and the _p entries give the old entries' bits."""
+    1e-13 is refused -- rows == 0, and a model that carries it gives the bits of one that carries none."""
     from ppbo_amd.engine import FORM_EDGE
     rng = np.random.default_rng(1)
     X = star_design(rng, 12, 31, 20)
@@ -198,17 +191,39 @@ def test_node_form_models_take_no_projection(eng, n_q, D):
     assert_same_bits(eng, post, eng.project_variance(post, TOL), rng.random((600, D)))
 
 
+REFUSED = "invalid argument: the variance projection was not built for a model of this N, m and form"
+
+
 def test_a_projection_of_another_model_is_refused(eng, built):
     from ppbo_amd.engine import SCORE_VARIANCE
     post, _, Xall = built["ragged"]
     other = built["se"][1]
-    with pytest.raises(RuntimeError, match="invalid argument"):
+    with pytest.raises(RuntimeError, match=REFUSED):
         call_predict(eng, post, Xall[:64], SCORE_VARIANCE, 0.0, other)
     # ... and so is one handed to a node-form model
     from ppbo_amd.engine import FORM_NODE
     node, rng = smooth_posterior(eng, 12, 31, 20, "SE_kernel", 2.5, form=FORM_NODE)
-    with pytest.raises(RuntimeError, match="invalid argument"):
+    with pytest.raises(RuntimeError, match=REFUSED):
         call_predict(eng, node, rng.random((64, 20)), SCORE_VARIANCE, 0.0, other)
+
+
+@pytest.mark.parametrize("field,value", [("ld", 400), ("rows_padded", 192), ("rows", 256), ("rows_padded", 1 << 20), ("d_T", None)])
+def test_a_projection_that_does_not_fit_is_refused(eng, built, field, value):
+    """The model's own projection (N = 384: ld = 384, rows = rows_padded = 128) with one member spoiled, in model.proj: a
+    wrong stride, a padded row count that is no multiple of 128, more rows than padded rows, more padded rows than the model
+    allows, no T -- each refused by all four reading entries."""
+    from ppbo_amd import _lib
+    from ppbo_amd.engine import SCORE_VARIANCE, VarianceProjection
+    post, pj, Xall = built["se"]
+    assert (pj.struct.ld, pj.struct.rows, pj.struct.rows_padded) == (384, 128, 128)
+    st = _lib.VarProjection.from_buffer_copy(pj.struct)
+    setattr(st, field, value)
+    bad = VarianceProjection(pj.T, st, TOL)
+    for call in (call_predict, call_record, call_search):
+        with pytest.raises(RuntimeError, match=REFUSED):
+            call(eng, post, Xall[:64], SCORE_VARIANCE, 0.0, bad)
+    with pytest.raises(RuntimeError, match=REFUSED):
+        eng.prune_report(post, Xall[:64], SCORE_VARIANCE, projection=bad)
 
 
 def test_c3_fixture(eng):
@@ -239,3 +254,55 @@ def test_c3_fixture(eng):
     assert on.projection is pj and off.projection is None
     (v_on, i_on), (v_off, i_off) = on.step(), off.step()
     assert i_on == i_off == bi and abs(v_on - v_off) <= 1e-9 * abs(v_off)
+
+
+def bits(out):
+    """Every array and number of an entry's result (a dict, a tuple, a tensor, an array or a scalar), as bytes."""
+    if isinstance(out, dict):
+        return [b for k in sorted(out) for b in bits(out[k])]
+    if isinstance(out, (tuple, list)):
+        return [b for v in out for b in bits(v)]
+    if out is None:
+        return [b""]
+    return [np.ascontiguousarray(host(out) if hasattr(out, "detach") else out).tobytes()]
+
+
+def test_every_other_entry_ignores_the_models_projection(eng, built, monkeypatch):
+    """With EVERY descriptor carrying the posterior's projection (Engine._model patched), the entries that do not read
+    ppbo_model.proj return the bits of the unpatched call; ppbo_predict, which reads it, stays within the projection's bound
+    of the unprojected variance and does not return its bits, so the projection is not simply dropped everywhere."""
+    from ppbo_amd.engine import Engine, SCORE_POINTWISE_EI, SCORE_VARIANCE
+    post, pj, Xall = built["se"]          # N = 384, rows = 128: the smallest design of this file that is projected
+    assert pj.rows > 0
+    sf2 = 1.3 ** 2
+    rng = np.random.default_rng(7)
+    Xa, Xb, Xf = Xall[:300], Xall[300:600], Xall[600:616]
+    Xi = rng.standard_normal((300, 2))
+    grid, z = rng.random((4, 8, 2)), rng.standard_normal((16, 8))
+    calls = {
+        "pairs": lambda: eng.predict_pairs(post, Xa, Xb, want_score=True),
+        "slopes": lambda: eng.predict_slopes(post, Xa, Xi, want_score=True),
+        "tournament": lambda: eng.predict_tournament(post, Xa, Xf, want_cov=True, want_prob=True),
+        "kg": lambda: eng.predict_kg(post, Xa, Xf, want_kinks=True),
+        "search_batch": lambda: eng.search_batch(post, Xa, 3, SCORE_POINTWISE_EI, 0.1, want_var_cond=True),
+        "cov": lambda: eng.predict_cov(post, Xa[:64]),
+        "line_acq": lambda: eng.line_acq(post, grid, z, 0.1, jitter=1e-9 * sf2),
+        "gradients": lambda: eng.predict_gradients(post, Xa),
+        "mean_grad": lambda: eng.mean_grad(post, Xa),
+    }
+    plain = {name: bits(call()) for name, call in calls.items()}
+    exact = eng.predict(post, Xa, SCORE_VARIANCE)
+    projected = eng.predict(post, Xa, SCORE_VARIANCE, projection=pj)
+    d = host(projected["var"]) - host(exact["var"])
+    print(f"predict: var_p - var in [{d.min() / sf2:.2e}, {d.max() / sf2:.2e}] sf2, bound {pj.bound / sf2:.2e} sf2")
+    assert np.array_equal(host(projected["mu"]), host(exact["mu"]))
+    assert np.abs(d).max() <= pj.bound + ROUND * sf2 and d.any()
+
+    model = Engine._model
+    monkeypatch.setattr(Engine, "_model", lambda self, p, with_var=True, kstar_fp32=False, projection=None:
+                        model(self, p, with_var, kstar_fp32, pj))
+    assert eng._model(post).proj.rows == pj.rows
+    for name, call in calls.items():
+        assert bits(call()) == plain[name], name
+    # ... and predict now reads it without being asked to
+    assert bits(eng.predict(post, Xa, SCORE_VARIANCE)) == bits(projected)

@@ -113,10 +113,10 @@ def test_rotated_ridge_leads_the_active_subspace():
 # ---------------------------------------------------------------- the plumbing
 def test_binding_header_and_constants():
     from ppbo_amd import _lib, engine
-    assert _lib.ABI_VERSION == 8
+    assert _lib.ABI_VERSION == 9
     assert len(_lib.SIGNATURES["ppbo_predict_gradients"]) == 12
     txt = open(os.path.join(ROOT, "include", "ppbo_hip.h")).read()
-    assert re.search(r"#define\s+PPBO_ABI_VERSION\s+8\b", txt)
+    assert re.search(r"#define\s+PPBO_ABI_VERSION\s+9\b", txt)
     code = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
     assert "ppbo_predict_gradients" in set(re.findall(r"\bint\s+(ppbo_[a-z_A-Z0-9]+)\s*\(", code))
     assert re.search(r"PPBO_GRAD_NONE\s*=\s*0\s*,\s*PPBO_GRAD_TRACE\s*=\s*1\s*,\s*PPBO_GRAD_NORM2\s*=\s*2", code)

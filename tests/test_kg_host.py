@@ -24,10 +24,10 @@ def _scale(a, b):
 # ---------------------------------------------------------------- 1. the surface
 def test_binding_header_and_constants():
     from ppbo_amd import _lib, engine
-    assert _lib.ABI_VERSION == 8
+    assert _lib.ABI_VERSION == 9
     assert len(_lib.SIGNATURES["ppbo_kg_envelope"]) == 13 and len(_lib.SIGNATURES["ppbo_predict_kg"]) == 16
     txt = open(os.path.join(ROOT, "include", "ppbo_hip.h")).read()
-    assert re.search(r"#define\s+PPBO_ABI_VERSION\s+8\b", txt)
+    assert re.search(r"#define\s+PPBO_ABI_VERSION\s+9\b", txt)
     assert re.search(r"#define\s+PPBO_KG_MAX_B\s+1024\b", txt)
     code = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
     names = set(re.findall(r"\bint\s+(ppbo_[a-z_A-Z0-9]+)\s*\(", code))
@@ -55,7 +55,7 @@ def test_library_exports_the_entry_points():
         build(verbose=False)
     lib = _lib.load()
     assert hasattr(lib, "ppbo_kg_envelope") and hasattr(lib, "ppbo_predict_kg")
-    assert lib.ppbo_abi_version() == 8
+    assert lib.ppbo_abi_version() == 9
 
 
 class _NoDevice:

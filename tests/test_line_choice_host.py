@@ -53,9 +53,9 @@ def test_restatement_rules():
 
 def test_binding_header_and_version_script():
     from ppbo_amd import _lib, engine
-    assert _lib.ABI_VERSION == 8
+    assert _lib.ABI_VERSION == 9
     txt = open(os.path.join(ROOT, "include", "ppbo_hip.h")).read()
-    assert re.search(r"#define\s+PPBO_ABI_VERSION\s+8\b", txt)
+    assert re.search(r"#define\s+PPBO_ABI_VERSION\s+9\b", txt)
     code = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
     declared = {m.group(1): m.group(2) for m in re.finditer(r"\bint\s+(ppbo_[a-z_A-Z0-9]+)\s*\(([^)]*)\)", code)}
     script = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "ppbo_amd", "csrc", "libppbo_hip.map")).read(), flags=re.S)
@@ -80,7 +80,7 @@ def test_library_exports_the_entry_points():
         from ppbo_amd.build import build
         build(verbose=False)
     lib = _lib.load()
-    assert lib.ppbo_abi_version() == 8
+    assert lib.ppbo_abi_version() == 9
     for name in ENTRIES:
         assert hasattr(lib, name)
 

@@ -125,9 +125,9 @@ def test_status_of_the_statement():
 def test_header_binding_sources_and_slots():
     from ppbo_amd import _lib, build, engine
     from ppbo_amd.gp_model import GPModel
-    assert _lib.ABI_VERSION == 8
+    assert _lib.ABI_VERSION == 9
     txt = open(os.path.join(ROOT, "include", "ppbo_hip.h")).read()
-    assert re.search(r"#define\s+PPBO_ABI_VERSION\s+8\b", txt)
+    assert re.search(r"#define\s+PPBO_ABI_VERSION\s+9\b", txt)
     code = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
     declared = {m.group(1): m.group(2) for m in re.finditer(r"\bint\s+(ppbo_[a-z_A-Z0-9]+)\s*\(([^)]*)\)", code)}
     for name, nargs in ENTRIES.items():
@@ -155,7 +155,7 @@ def test_library_exports_the_entry_points():
         from ppbo_amd.build import build
         build(verbose=False)
     lib = _lib.load()
-    assert lib.ppbo_abi_version() == 8
+    assert lib.ppbo_abi_version() == 9
     for name in ENTRIES:
         assert hasattr(lib, name)
 

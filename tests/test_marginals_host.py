@@ -309,6 +309,6 @@ def test_binding_and_header():
     txt = open(os.path.join(ROOT, "include", "ppbo_hip.h")).read()
     assert re.search(r"PPBO_EFFECT_RAW = 0, PPBO_EFFECT_CENTRED = 1, PPBO_EFFECT_INTERACTION = 2", txt)
     assert "typedef struct ppbo_marginal_axes" in txt and "DOES NOT CHECK" in txt
-    assert re.search(r"#define PPBO_ABI_VERSION 8\b", txt)
+    assert re.search(r"#define PPBO_ABI_VERSION 9\b", txt)
     fields = [f[0] for f in _lib.MarginalAxes._fields_]
     assert fields == ["Dc", "d_Xu", "h_l", "h_periodic", "h_I0"]

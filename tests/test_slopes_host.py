@@ -155,11 +155,11 @@ def test_camphor_ard_directions_are_the_embeddings_derivative():
 # ---------------------------------------------------------------- the plumbing
 def test_binding_header_and_constants():
     from ppbo_amd import _lib, engine
-    assert _lib.ABI_VERSION == 8
+    assert _lib.ABI_VERSION == 9
     assert "ppbo_predict_slopes" in _lib.SIGNATURES
     assert _lib.SIGNATURES["ppbo_predict_slopes"] == _lib.SIGNATURES["ppbo_predict_pairs"] and len(_lib.SIGNATURES["ppbo_predict_slopes"]) == 13
     txt = open(os.path.join(ROOT, "include", "ppbo_hip.h")).read()
-    assert re.search(r"#define\s+PPBO_ABI_VERSION\s+8\b", txt)
+    assert re.search(r"#define\s+PPBO_ABI_VERSION\s+9\b", txt)
     code = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
     assert "ppbo_predict_slopes" in set(re.findall(r"\bint\s+(ppbo_[a-z_A-Z0-9]+)\s*\(", code))
     assert re.search(r"PPBO_SLOPE_MEAN\s*=\s*0\s*,\s*PPBO_SLOPE_VARIANCE\s*=\s*1\s*,\s*PPBO_SLOPE_PROB\s*=\s*2", code)

@@ -59,10 +59,10 @@ def test_reductions_on_a_hand_made_matrix():
 
 def test_binding_header_and_constants():
     from ppbo_amd import _lib, engine
-    assert _lib.ABI_VERSION == 8
+    assert _lib.ABI_VERSION == 9
     assert len(_lib.SIGNATURES["ppbo_predict_tournament"]) == 17
     txt = open(os.path.join(ROOT, "include", "ppbo_hip.h")).read()
-    assert re.search(r"#define\s+PPBO_ABI_VERSION\s+8\b", txt)
+    assert re.search(r"#define\s+PPBO_ABI_VERSION\s+9\b", txt)
     assert re.search(r"#define\s+PPBO_TOURNAMENT_MAX_B\s+1024\b", txt)
     code = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
     assert "ppbo_predict_tournament" in set(re.findall(r"\bint\s+(ppbo_[a-z_A-Z0-9]+)\s*\(", code))
